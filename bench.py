@@ -2,7 +2,8 @@
 """
 bench.py — headline benchmark of the MI355X-native mdhelper hot path.
 
-    python bench.py --gpus N --steps K --warmup W [--workload rdf|rdf_wide|sq|msd|isf]
+    python bench.py --gpus N --steps K --warmup W [--workload rdf|rdf_wide|sq|msd|isf] [--full]
+                    [--dump-outputs DIR]
 
 Default workload (BASELINE.json configs[1], "C2"): RDF on 32 768 atoms, cubic
 box L = 68.94 A (rho = 0.1 A^-3), n_bins = 201, range = (0, 15) A, self RDF with
@@ -24,12 +25,18 @@ Prints one JSON line on rank 0:
   roofline     = dominant kernel (rdf_cell_pair_kernel): the VALU issue bound that binds it
                  (hot-loop trips counted live x instruction counts from the SQ-counter profile of
                  the same sources) with the HBM figure beside it under "hbm"
-  cpu_baseline = NumPy restatement of the reference path on one core; cpu_baseline_parallel =
+  cpu_baseline = (--full) NumPy restatement of the reference path on one core; cpu_baseline_parallel =
                  the same over every core of the affinity mask; cpu_baseline_c = the C/OpenMP
                  restatement on whole frames, whose counts are also checked bit-for-bit
                  against the GPU's.
-  extra        = short C3 S(q), C4 MSD and C2(ii) wide-range legs (N = 1 only), each a full
-                 line of its own workload with roofline + cpu_baseline.
+  extra        = (--full) short C3 S(q), C4 MSD and C2(ii) wide-range legs (N = 1 only), each a full
+                 line of its own workload with roofline + cpu_baseline, and the RDF ingest legs.
+
+A plain run sets up, warms up, times the K steps and prints the line; the CPU baselines and the side
+legs (extra, the S(q) / ISF ingest legs, the MSD Onsager legs) run with --full only.
+--dump-outputs DIR writes what the timed path returned after its last step (RDF: the bin counts; S(q):
+the summed structure factors; ISF: the coherent and incoherent functions; MSD: msd and the summed
+trajectories) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded sample beyond that).
 """
 
 import argparse
@@ -67,6 +74,13 @@ def parse(argv=None):
     ap.add_argument("--n-points", type=int, default=8,
                     help="sq: grid points per axis (8 -> the 512 wavevectors of C3; 32 -> the reference's "
                          "default StructureFactor grid of 32 768, structure.py:1324, 1376-1381)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines, the extra C3 / C4 / "
+                         "C2(ii) lines and ingest legs of rdf, the ingest legs of sq / isf, the Onsager legs of msd "
+                         "(each --no-* flag below still drops its part; --workload ingest runs its legs either way)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last step as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="rdf at N=1: skip the short C3 / C4 / C2(ii) legs embedded under 'extra'")
@@ -231,6 +245,27 @@ def max_rel_deviation(got, ref, floor=1e-9):
     mag = np.abs(ref)
     keep = mag > floor * mag.max()
     return float((np.abs(got - ref)[keep] / mag[keep]).max())
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: every array as ``path/<name>.npy`` in float64 (float32 stays float32).  Above
+    DUMP_BYTES in all, each array keeps its share of the budget as a fixed, seeded sample of its flattened
+    elements (the same indices for the same shapes, so that two builds compare element for element)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if v is not None}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    budget = DUMP_BYTES - 256 * len(arrays)                # (.npy headers)
+    for name, a in arrays.items():
+        if total > budget:
+            keep = int(budget * (a.nbytes / total)) // a.itemsize
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def write_amber_netcdf_fast(path, positions, box):
@@ -464,6 +499,7 @@ def bench_rdf(args, world, wide=False):
         "pairs_binned_per_frame": binned / max(frames_total, 1),
         "result_digest": hashlib.sha256(np.ascontiguousarray(counts, dtype=np.int64).tobytes()).hexdigest()[:16],
         "roofline": roofline,
+        "_outputs": {"counts": counts},
     }
     if world.rank == 0 and world.world == 1 and not args.no_cpu_baseline:
         out.update(cpu_baseline_rdf(args, traj, box, edges, rng, n_bins, N, eng))
@@ -641,6 +677,7 @@ def bench_sq(args, world):
                              "frac": achieved / HBM_PEAK_GBS, "algorithmic_bytes_per_step": alg}},
         "checksum": float(ssf.sum()),
         "result_digest": [float(x) for x in ssf[:, 1:4].ravel()],
+        "_outputs": {"ssf": ssf},
     }
     if world.rank == 0 and world.world == 1 and not args.no_cpu_baseline:
         from oracle import fourier as of
@@ -747,6 +784,7 @@ def bench_isf(args, world):
         "frames_per_sec": args.steps * F * world.world / dt,
         "roofline": isf_roofline(N, len(q), F, lagged, kernel_s, per_step, achieved, alg),
         "checksum": float(cisf.sum() + iisf.sum()),
+        "_outputs": {"cisf": cisf, "iisf": iisf},
     }
     if world.rank == 0 and world.world == 1 and not args.no_cpu_baseline:
         from oracle import fourier as of
@@ -892,6 +930,7 @@ def bench_msd(args, world):
         "result_ms": result_ms,
         "physics_check_msd_over_3sigma2m": float(msd[10] / (3 * 0.01 * 10)),
         "result_digest": [float(x) for x in box["msd"][:, 0, 1:4].ravel()],
+        "_outputs": {"msd": box["msd"], "traj": box["traj"]},
     }
     if world.rank == 0 and world.world == 1 and not args.no_cpu_baseline:
         # the reference's msd_fft (scipy FFTs, one core) on a bounded sample of particles, and
@@ -1310,6 +1349,7 @@ def run_extras(args, world):
                 extra[name] = bench_msd(a, world)
             else:
                 extra[name] = bench_rdf(a, world, wide=True)
+            extra[name].pop("_outputs", None)
             extra[name]["leg_wall_s"] = time.perf_counter() - t0
         except Exception as exc:            # an extra leg never takes the headline line down
             extra[name] = {"error": f"{type(exc).__name__}: {exc}"}
@@ -1448,6 +1488,9 @@ def product_library():
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run: the headline path alone
+        args.no_cpu_baseline = args.no_extras = args.no_ingest = args.no_onsager = True
     library = product_library()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -1472,6 +1515,9 @@ def main():
         out = bench_isf(args, world)
     else:
         out = bench_msd(args, world)
+    outputs = out.pop("_outputs")
+    if args.dump_outputs and world.rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     plain = not (args.host_path or args.traj_file or args.shard_fixed or args.atoms or args.algo != "auto")
     if args.workload == "rdf" and world.world == 1 and plain and not args.no_extras:
         out["extra"] = run_extras(args, world)

@@ -8,6 +8,7 @@ protocol of RdfEngine, SqEngine and MsdEngine: a FIXED frame / particle set give
 (``MDX_FORCE_COMM=1``), and with 2 real ranks wherever two devices are visible.
 Reference counterpart: analysis/base.py:385-386, 491-501; analysis/structure.py:841-844.
 """
+import hashlib
 import json
 import os
 import subprocess
@@ -22,10 +23,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
 
-def _bench(*flags, env=None, timeout=900):
+def _bench(*flags, env=None, timeout=900, plain=False):
     e = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MDX_RDZV_KEY")}
     e.update(env or {})
-    out = subprocess.run([sys.executable, BENCH, "--no-cpu-baseline", "--no-extras", *flags],
+    quiet = () if plain else ("--no-cpu-baseline", "--no-extras")
+    out = subprocess.run([sys.executable, BENCH, *quiet, *flags],
                          capture_output=True, text=True, timeout=timeout, env=e)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -55,6 +57,27 @@ def test_two_ranks_equal_one_rank_rdf_sq_msd():
     two = _bench(*MSD, "--gpus", "3", "--share-devices")
     assert two["n_gpus"] == 3
     assert np.allclose(two["result_digest"], one["result_digest"], rtol=1e-9, atol=1e-12)
+
+
+def test_bench_dumps_what_the_timed_path_returned(tmp_path):
+    """``--dump-outputs DIR``: the arrays the timed path returned after its last step, in float64 — the RDF counts
+    hash to the line's digest, a second run on the same arguments writes the same counts, the S(q) / MSD arrays
+    carry the numbers the line quotes.  A plain run (no --full) carries no CPU baseline."""
+    out = _bench(*RDF, "--dump-outputs", str(tmp_path / "rdf"), plain=True)
+    assert "cpu_baseline" not in out and "extra" not in out and out["steps"] == 2 and out["ms_per_step"] > 0
+    counts = np.load(tmp_path / "rdf" / "counts.npy")
+    assert counts.dtype == np.float64 and counts.shape == (201,) and counts.sum() > 0
+    assert hashlib.sha256(counts.astype(np.int64).tobytes()).hexdigest()[:16] == out["result_digest"]
+    _bench(*RDF, "--dump-outputs", str(tmp_path / "rdf2"), plain=True)
+    assert np.array_equal(np.load(tmp_path / "rdf2" / "counts.npy"), counts)
+    out = _bench(*SQ, "--dump-outputs", str(tmp_path / "sq"))
+    ssf = np.load(tmp_path / "sq" / "ssf.npy")
+    assert ssf.dtype == np.float64 and ssf.shape == (3, 512)
+    assert np.array_equal(ssf[:, 1:4].ravel(), out["result_digest"]) and np.isclose(ssf.sum(), out["checksum"])
+    out = _bench(*MSD, "--dump-outputs", str(tmp_path / "msd"))
+    msd, traj = np.load(tmp_path / "msd" / "msd.npy"), np.load(tmp_path / "msd" / "traj.npy")
+    assert msd.shape == (2, 1, 4096) and traj.shape == (2, 1, 4096, 3)
+    assert np.array_equal(msd[:, 0, 1:4].ravel(), out["result_digest"])
 
 
 def test_rccl_data_plane_single_rank_through_bench():

@@ -253,7 +253,8 @@ def test_bench_contract_without_a_device(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True,
                          text=True, env=env, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--blocks", "--host-path", "--traj-file"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--blocks", "--host-path", "--traj-file", "--full",
+                 "--dump-outputs"):
         assert flag in out.stdout
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"], capture_output=True,
                          text=True, env=env, timeout=120)
@@ -263,6 +264,30 @@ def test_bench_contract_without_a_device(tmp_path):
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0"],
                              capture_output=True, text=True, env=env, timeout=300)
         assert out.returncode != 0 and out.stdout.strip() == ""      # no JSON line without a GPU
+
+
+def test_bench_output_dump_keeps_to_its_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: float64 (float32 kept) .npy files; above the budget a fixed, seeded sample of each
+    array, the same on every call."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    counts = np.arange(201, dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "small"), {"counts": counts, "none": None})
+    got = np.load(tmp_path / "small" / "counts.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, counts) and os.listdir(tmp_path / "small") == ["counts.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40_000)
+    big = {"a": np.arange(20_000, dtype=np.float64), "b": np.arange(3_000, dtype=np.float32).reshape(1000, 3)}
+    for d in ("one", "two"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    sizes = sum(os.path.getsize(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one"))
+    assert sizes <= 40_000
+    a, b = np.load(tmp_path / "one" / "a.npy"), np.load(tmp_path / "one" / "b.npy")
+    assert a.dtype == np.float64 and b.dtype == np.float32 and 0 < a.size < 20_000 and 0 < b.size < 3_000
+    assert np.all(np.diff(a) > 0) and np.isin(a, big["a"]).all()           # sorted sample of the elements
+    assert np.array_equal(a, np.load(tmp_path / "two" / "a.npy"))
+    assert np.array_equal(b, np.load(tmp_path / "two" / "b.npy"))
 
 
 def test_fragments_and_make_whole_images():
