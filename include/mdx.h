@@ -229,6 +229,13 @@ int mdx_sq_reset(mdx_sq_t h);
  * molecules.  Groups with groupings="atoms" enter as molecules of one particle and mass 1.
  * n_molecules <= 0 removes the grouping. */
 int mdx_sq_set_grouping(mdx_sq_t h, int64_t n_molecules, const int64_t *offsets, const double *masses);
+/* Single-chain structure factor (SingleChainStructureFactor._single_frame, polymer.py:1095-1099): the points —
+ * counted after mdx_sq_set_grouping — form chains of chain_length consecutive points, and mdx_sq_result returns
+ * float64[1][n_q] un-normalised sums over frames of sum_c |sum_{j in chain c} exp(i q.r_j)|^2.  Needs a handle
+ * created with one group over all points and pairs = {(-1,-1)}, and a point count divisible by chain_length;
+ * only before the first frame (after mdx_sq_create or mdx_sq_reset).  chain_length <= 0 restores the normal
+ * mode.  Every accumulate entry point, mdx_sq_allreduce and the statistics work as in the normal mode. */
+int mdx_sq_set_chains(mdx_sq_t h, int64_t chain_length);
 int mdx_sq_accumulate(mdx_sq_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Positions already in HBM.  ASYNCHRONOUS on the handle's stream: the call may return while kernels still read
  * d_pos; a producer that rewrites the buffer (an MD engine feeding batches) calls mdx_sq_synchronize first.

@@ -366,6 +366,12 @@ class SqEngine(_Engine):
             raise ValueError("masses must hold one entry per particle of the grouping.")
         check(fn(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
 
+    def set_chains(self, chain_length):
+        """Single-chain mode (``mdx_sq_set_chains``): the points form chains of ``chain_length``
+        consecutive points and ``result()[0]`` is the sum over frames of ``sum_c |rho_c(q)|^2``;
+        ``chain_length <= 0`` restores the normal mode.  Only before the first frame."""
+        check(lib().mdx_sq_set_chains(self.handle, int(chain_length)))
+
     def accumulate(self, pos):
         p = np.ascontiguousarray(pos, dtype=np.float32)
         if p.ndim == 2:

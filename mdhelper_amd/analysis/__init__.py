@@ -3,5 +3,5 @@
 from . import base, polymer, structure, transport  # noqa: F401
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
-from .polymer import EndToEndVector  # noqa: F401
+from .polymer import EndToEndVector, SingleChainStructureFactor  # noqa: F401
 from .transport import Onsager  # noqa: F401

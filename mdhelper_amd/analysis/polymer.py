@@ -1,7 +1,8 @@
 """
-Polymer dynamics (operator surface of ``mdhelper.analysis.polymer`` for the time-correlation
-hot path): ``EndToEndVector`` — the end-to-end vector autocorrelation function of polymer
-chains and the orientational relaxation time fitted to it.
+Polymer dynamics and structure (operator surface of ``mdhelper.analysis.polymer``):
+``EndToEndVector`` — the end-to-end vector autocorrelation function of polymer chains and the
+orientational relaxation time fitted to it — and ``SingleChainStructureFactor`` — the
+single-chain structure factor on the reciprocal grid.
 
 Mirrors reference ``src/mdhelper/analysis/polymer.py``: ``correlation_fft`` /
 ``correlation_shift`` aliases (:30-57), ``calculate_relaxation_time`` (:59-108),
@@ -17,6 +18,10 @@ spectra over chains and components and inverts once per (group, block); the ACF 
 trajectories are gathered for all frames in one vectorised step; unwrapping is the same
 image-flag rule as ``unwrap`` (topology.py:366-376), evaluated for all frames at once.
 With ``comm=`` the chains shard across ranks (one all-reduce of the accumulators).
+
+``SingleChainStructureFactor`` (reference :805-1130) runs on the structure-factor engine in
+single-chain mode (``mdx_sq_set_chains``): per frame and chain the device forms
+``rho_c(q) = sum_{j in c} exp(i q.r_j)`` and adds ``|rho_c|^2``; frames shard across ranks.
 """
 
 from __future__ import annotations
@@ -32,7 +37,7 @@ from ..algorithm import correlation
 from ..algorithm.topology import unwrap_edge
 from ..algorithm.unit import strip_unit
 from ..comm import shard_range
-from .base import DynamicAnalysisBase
+from .base import DynamicAnalysisBase, FrameBatcher
 
 _GROUPINGS = {"atoms", "residues"}
 
@@ -344,6 +349,208 @@ class EndToEndVector(_PolymerAnalysisBase):
                 valid = np.where(acf >= 0)[0]
                 self.results.relaxation_times[i, j] = calculate_relaxation_time(
                     self.results.times[valid], acf[valid])
+
+
+class SingleChainStructureFactor(DynamicAnalysisBase):
+    r"""
+    Single-chain structure factor of a homopolymer (reference :805-1130):
+
+    .. math:: S_\mathrm{sc}(\mathbf q)=\frac{1}{MN_\mathrm p}\sum_{m=1}^M\left\langle
+              \left|\sum_{j\in m}e^{i\mathbf q\cdot\mathbf r_j}\right|^2\right\rangle
+
+    averaged over the wavevectors of equal wavenumber.  In the Guinier regime
+    :math:`S_\mathrm{sc}(q)\approx N_\mathrm p(1-(qR_g)^2/3)` gives the radius of gyration; the
+    slope :math:`s` of the log-log plot in the intermediate regime gives the scaling exponent
+    :math:`\nu=-1/s`.
+
+    Parameters (reference :934-938)
+    ----------
+    group : AtomGroup — the chains, all of one length
+    grouping : {"atoms", "residues"}
+    n_points : int, default 32 — wavevectors ``2 pi n / L``, ``n = 0 ... n_points - 1`` per axis
+    n_chains, n_monomers : int, keyword-only, optional — read from the topology (chains =
+        segments) when either is missing
+    dimensions : array-like (3,), keyword-only, optional — box lengths in Å
+    unwrap : bool, keyword-only — accepted; it changes nothing (see below)
+    parallel : bool, keyword-only — accepted and ignored
+    comm, device : keyword-only (extension) — frames shard across ranks, one all-reduce at the end
+
+    Results: ``results.wavenumbers`` ``[N_q]`` (Å⁻¹), ``results.scsf`` ``[N_q]``, ``results.units``.
+
+    Where this differs from the reference:
+
+    * ``unwrap`` computes on the coordinates as given, for both values.  Image shifts are whole
+      multiples of the box lengths the wavevectors are built from, so every phase moves by a
+      multiple of :math:`2\pi` and the result is the same; the reference applies the shifts in
+      float32 (topology.py:376), so its ``unwrap=True`` result only loses digits.
+    * ``"residues"``: the monomer centres of mass are float32, formed on the device (as in
+      ``StructureFactor``); the reference keeps them in float64.
+    * ``"residues"`` read from the topology: one chain per segment and ``n_monomers`` = residues per
+      chain.  The reference sets it to atoms per chain, which only works with one atom per residue;
+      wherever the reference runs, both agree.
+    * A point count other than ``n_chains * n_monomers`` and segments of unequal length raise
+      ``ValueError`` before any work (the reference fails in a reshape).
+    """
+
+    def __init__(self, group, grouping: str = "atoms", n_points: int = 32, *, n_chains: int = None,
+                 n_monomers: int = None, dimensions=None, unwrap: bool = False,
+                 parallel: bool = False, verbose: bool = True, **kwargs) -> None:
+        self._group = group
+        self.universe = group.universe
+        super().__init__(self.universe.trajectory, parallel, verbose, **kwargs)
+
+        if dimensions is not None:
+            if len(dimensions) != 3:
+                raise ValueError("'dimensions' must have length 3.")
+            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
+        elif self.universe.dimensions is not None:
+            self._dimensions = np.array(self.universe.dimensions[:3], dtype=float)
+        else:
+            raise ValueError("No system dimensions found or provided.")
+
+        if grouping not in _GROUPINGS:
+            raise ValueError(f"Invalid grouping '{grouping}'. Valid values: "
+                             f"{', '.join(sorted(_GROUPINGS))}.")
+        self._grouping = grouping
+
+        if n_chains is None or n_monomers is None:
+            self._internal = True
+            seg = np.asarray(group.segindices)
+            _, seg_sizes = np.unique(seg, return_counts=True)
+            self._n_chains = len(seg_sizes)
+            if grouping == "residues":
+                _, first = np.unique(np.asarray(group.resindices), return_index=True)
+                _, per_seg = np.unique(seg[first], return_counts=True)      # residues per segment
+                if np.any(per_seg != per_seg[0]):
+                    raise ValueError("All segments must hold the same number of residues.")
+                self._n_monomers = int(per_seg[0])
+            else:
+                if np.any(seg_sizes != seg_sizes[0]):
+                    raise ValueError("All segments must hold the same number of atoms.")
+                self._n_monomers = group.n_atoms // self._n_chains
+        else:
+            self._internal = False
+            if not isinstance(n_chains, (int, np.integer)):
+                raise ValueError("The number of chains must be specified when the universe does "
+                                 "not contain segment information.")
+            if not isinstance(n_monomers, (int, np.integer)):
+                raise ValueError("The number of monomers per chain must be specified when the "
+                                 "universe does not contain segment information.")
+            self._n_chains, self._n_monomers = int(n_chains), int(n_monomers)
+        self._N = self._n_chains * self._n_monomers
+        n_have = group.n_atoms if grouping == "atoms" or not self._internal else \
+            len(np.unique(np.asarray(group.resindices)))
+        if self._N <= 0 or (n_have % self._N if grouping == "residues" and not self._internal
+                            else n_have != self._N):
+            what = "atoms" if grouping == "atoms" or not self._internal else "residues"
+            raise ValueError(f"The group holds {n_have} {what}, which do not form n_chains * "
+                             f"n_monomers = {self._n_chains} * {self._n_monomers} = {self._N} "
+                             f"monomers.")
+
+        # reference :1016-1023; numpy.meshgrid's default 'xy' indexing fixes the row order
+        self._n_points = n_points
+        self._wavevectors = np.stack(
+            np.meshgrid(*[2 * np.pi * np.arange(n_points) / L for L in self._dimensions]),
+            -1).reshape(-1, 3)
+        self._wavenumbers = np.linalg.norm(self._wavevectors, axis=1)
+        self._unwrap = unwrap
+        self._verbose = verbose
+
+    # ------------------------------------------------------------------ points
+
+    def _selection(self):
+        """(particle indices in chain order, monomer offsets or None, masses or None)."""
+        g = self._group
+        idx = np.asarray(g.indices)
+        if self._grouping == "atoms":
+            return idx, None, None
+        masses = np.asarray(g.masses, dtype=np.float64)
+        if not self._internal:
+            # a monomer is n_atoms / (n_chains n_monomers) consecutive atoms
+            return idx, np.arange(self._N + 1, dtype=np.int64) * (g.n_atoms // self._N), masses
+        # residues of the topology, molecule by molecule; a chain is a segment
+        _, inverse = np.unique(np.asarray(g.resindices), return_inverse=True)
+        order = np.argsort(inverse, kind="stable")
+        offsets = np.concatenate(([0], np.cumsum(np.bincount(inverse)))).astype(np.int64)
+        seg = np.asarray(g.segindices)[order][offsets[:-1]].reshape(self._n_chains, self._n_monomers)
+        if np.any(seg != seg[:, :1]) or len(np.unique(seg[:, 0])) != self._n_chains:
+            raise ValueError("The residues of every segment must be consecutive.")
+        return idx[order], offsets, masses[order]
+
+    def _points(self, sel):
+        """Positions float[N, 3] of the points in the current frame (per-frame path)."""
+        idx, off, m = sel
+        pos = np.asarray(self.universe.trajectory.ts.positions, dtype=float)[idx]
+        if off is None:
+            return pos
+        msum = np.add.reduceat(m, off[:-1])
+        return np.add.reduceat(pos * m[:, None], off[:-1], axis=0) / msum[:, None]
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        self.results.wavenumbers = np.unique(self._wavenumbers.round(11))
+        self.results.units = {"results.wavenumbers": "angstrom^-1"}
+        self._sel = self._selection()
+        self._engine = _core.SqEngine(self._wavevectors, [self._N], ((None, None),), dev=self._device)
+        self._engine.set_chains(self._n_monomers)
+        self._batch = FrameBatcher(int(self._N), lambda p, b: self._engine.accumulate(p[0]),
+                                   with_box=False)
+        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
+
+    def _single_frame(self) -> None:
+        lo, hi = self._frames_mine
+        if not lo <= self._frame_index < hi:
+            return
+        self._batch.add([self._points(self._sel)])
+
+    # in-memory, HBM-resident and file trajectories: whole blocks of frames go to the engine, as in
+    # StructureFactor.run; monomer centres of mass are formed on the device
+    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
+        from .structure import _device_frames, _is_array_trajectory
+        traj = self._trajectory
+        if not _is_array_trajectory(traj):
+            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
+                               **kwargs)
+        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
+        self._prepare()
+        numbers = self._frame_numbers()
+        self.frames[:] = numbers
+        self.times[:] = numbers * traj.dt
+        lo, hi = self._frames_mine
+        mine = numbers[lo:hi]
+        index, offsets, masses = self._sel
+        if offsets is not None:
+            self._engine.set_grouping(offsets, masses)
+        identity = len(index) == traj.n_atoms and np.array_equal(index, np.arange(len(index)))
+        native = getattr(traj, "native", None)
+        block = 4096 if native is not None else max(self._batch.capacity,
+                                                     (1 << 30) // max(12 * traj.n_atoms, 1))
+        for b0 in np.arange(0, len(mine), block):
+            sel = mine[b0:b0 + block]
+            resident = _device_frames(traj, sel) if (identity and offsets is None) else None
+            if native is not None:
+                self._engine.accumulate_traj(native, sel, None if identity else index)
+            elif resident is not None:
+                self._engine.accumulate_device(resident.ptr, traj.n_atoms, len(sel))   # frames already in HBM
+            else:
+                pos = traj.frame_block(sel)
+                self._engine.accumulate(pos if identity else pos[:, index])
+        self._conclude()
+        return self
+
+    def _conclude(self) -> None:
+        from .structure import _mean_over_equal_wavenumbers
+        self._batch.flush()
+        if self._comm.world_size > 1 and getattr(self._comm, "device_collectives", False):
+            self._engine.allreduce(self._comm)
+            acc = self._engine.result()[0]
+        else:
+            acc = self._comm.allreduce(self._engine.result()[0])
+        self._engine.close()
+        scsf = acc / (self._n_chains * self._n_monomers * self.n_frames)
+        self.results.scsf = _mean_over_equal_wavenumbers(scsf, self._wavenumbers,
+                                                         self.results.wavenumbers)
 
 
 def _ordered_unique(ids):

@@ -83,6 +83,32 @@ __global__ __launch_bounds__(PAIR_Q * PAIR_FS) void sq_pair_kernel(
     }
 }
 
+// Single-chain mode: acc[qmap[col]] += sum over frames and splits of part[frame][split][col] (qmap NULL: col is the
+// wavevector), in a fixed order as sq_pair_kernel does — results do not depend on scheduling.
+__global__ __launch_bounds__(PAIR_Q * PAIR_FS) void sq_chain_merge_kernel(
+    const double *__restrict__ part, int n_frames, int n_split, int64_t n_cols, const int *__restrict__ qmap,
+    double *__restrict__ acc)
+{
+    __shared__ double red[PAIR_FS][PAIR_Q];
+    const int lane = threadIdx.x % PAIR_Q, fs = threadIdx.x / PAIR_Q;
+    const int64_t col = int64_t(blockIdx.x) * PAIR_Q + lane;
+    double sum = 0.0;
+    if (col < n_cols)
+        for (int f = fs; f < n_frames; f += PAIR_FS)
+            for (int s = 0; s < n_split; ++s)
+                sum += part[(int64_t(f) * n_split + s) * n_cols + col];
+    red[fs][lane] = sum;
+    __syncthreads();
+    if (fs == 0 && col < n_cols) {
+        double total = 0.0;
+        for (int s = 0; s < PAIR_FS; ++s)
+            total += red[s][lane];
+        const int q = qmap ? qmap[col] : (int)col;
+        if (q >= 0)
+            acc[q] += total;
+    }
+}
+
 // float64 positions -> F[q] for the function-level drop-in (one pseudo-frame, one group)
 __global__ __launch_bounds__(SQ_THREADS) void sq_fourier_sum_f64_kernel(
     const double *__restrict__ pos, int64_t n, const double *__restrict__ qv, int n_q, int n_split,
@@ -221,7 +247,19 @@ struct mdx_sq {
     SqLattice col_lat{};
     size_t col_lds = 0;
     DeviceBuffer d_items;
+    // single-chain mode (mdx_sq_set_chains): chain length in points, 0 = off
+    std::vector<double> q_host;  // the wavevectors, for the chain kernel's plan
+    bool all_points = false;     // one group from point 0 and pairs = {(-1, -1)}: what the mode needs
+    bool fed = false;            // a frame has been accumulated since creation / the last reset
+    int64_t chain_len = 0;
+    bool chain_planned = false, chain_quads = false;
+    int chain_items = 0, chain_ipb = 1, chain_regular = 0;
+    SqLattice chain_lat{};
+    size_t chain_lds = 0;
+    DeviceBuffer d_chain_items, d_chain_qmap;
 };
+
+static int sq_accumulate_chains(mdx_sq *h, const float *d_pos, int64_t n, int64_t n_frames);
 
 static int sq_accumulate_points(mdx_sq *h, const float *d_pos, int64_t n, int64_t n_frames);
 
@@ -244,6 +282,9 @@ static int sq_accumulate_points(mdx_sq *h, const float *d_pos, int64_t n, int64_
         return MDX_OK;
     MDX_REQUIRE(n >= h->n_total, "positions hold %lld particles but the groups span %lld",
                 (long long)n, (long long)h->n_total);
+    h->fed = true;
+    if (h->chain_len > 0)
+        return sq_accumulate_chains(h, d_pos, n, n_frames);
     const int qblocks = h->quads     ? (int)ceil_div(int64_t(h->n_qitems), int64_t(h->ipb))
                         : h->columns ? (int)ceil_div(h->n_items, h->col_threads)
                                      : (int)ceil_div(h->n_q, SQ_QPB);
@@ -300,6 +341,83 @@ static int sq_accumulate_points(mdx_sq *h, const float *d_pos, int64_t n, int64_
     return MDX_OK;
 }
 
+// Single-chain mode: sum_c |rho_c|^2 over the frames into acc[0][q].  Particle splits are whole chains.
+static int sq_accumulate_chains(mdx_sq *h, const float *d_pos, int64_t n, int64_t n_frames)
+{
+    const int64_t n_chains = h->n_total / h->chain_len;
+    const int qblocks = h->chain_quads ? (int)ceil_div(int64_t(h->chain_items), int64_t(h->chain_ipb))
+                                       : (int)ceil_div(h->n_q, SQ_QPB);
+    // split the chains when frames x q-blocks alone would not fill the chip (the rule of sq_accumulate_points)
+    constexpr int block_waves = SQ_QUAD_THREADS / 64;
+    static_assert(SQ_QUAD_THREADS == SQ_THREADS, "both chain kernels run 256-thread blocks");
+    constexpr int64_t want_waves = 4096;
+    int n_split = 1;
+    while (int64_t(qblocks) * block_waves * n_split * std::min<int64_t>(n_frames, 4096) < want_waves &&
+           n_split < 64 && n_chains >= 2 * int64_t(n_split) && h->n_total / (n_split * 2) >= 2 * SQ_TILE)
+        n_split *= 2;
+    const int64_t per = ceil_div(n_chains, int64_t(n_split));   // chains per split
+    n_split = (int)ceil_div(n_chains, per);                     // no empty split
+    const int64_t n_cols = h->chain_quads ? int64_t(SQ_QCOLS * SQ_ZPT) * h->chain_items : h->n_q;
+    const int64_t part_per_frame = int64_t(n_split) * n_cols * 8;
+    int64_t slab = std::max<int64_t>(1, (int64_t(512) << 20) / part_per_frame);
+    slab = std::min<int64_t>(std::min<int64_t>(slab, 32768), n_frames);
+    MDX_TRY(h->d_rho.ensure(size_t(part_per_frame) * slab));
+    double *part = h->d_rho.as<double>();
+    hipEvent_t ev = h->timer.begin();
+    for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
+        const int64_t nf = std::min(slab, n_frames - f0);
+        if (h->chain_quads)
+            hipLaunchKernelGGL(sq_chain_quads_pick(h->chain_regular), dim3(qblocks, n_split, (unsigned)nf),
+                               dim3(SQ_QUAD_THREADS), h->chain_lds, h->stream, d_pos + f0 * n * 3, n,
+                               h->d_chain_items.as<SqQuadItem>(), h->chain_items, h->chain_ipb, h->chain_lat,
+                               h->n_total, h->chain_len, per, n_split, part);
+        else
+            hipLaunchKernelGGL(sq_chain_sincos_kernel, dim3(qblocks, n_split, (unsigned)nf), dim3(SQ_THREADS), 0,
+                               h->stream, d_pos + f0 * n * 3, n, h->d_q.as<double>(), (int)h->n_q, h->n_total,
+                               h->chain_len, per, n_split, part);
+        hipLaunchKernelGGL(sq_chain_merge_kernel, dim3((unsigned)ceil_div(n_cols, int64_t(PAIR_Q))),
+                           dim3(PAIR_Q * PAIR_FS), 0, h->stream, part, (int)nf, n_split, n_cols,
+                           h->chain_quads ? h->d_chain_qmap.as<int>() : nullptr, h->d_acc.as<double>());
+    }
+    h->timer.end(ev);
+    MDX_HIP(hipGetLastError());
+    return MDX_OK;
+}
+
+// The chain kernel's plan: quad items with one copy each when the wavevectors form a lattice the quad planner takes
+// (and neither MDX_SQ_NO_QUADS nor MDX_SQ_NO_COLUMNS is set), else the plain sincos kernel.
+static int sq_plan_chains(mdx_sq *h)
+{
+    h->chain_quads = false;
+    SqLattice lat{};
+    std::vector<short> trip;
+    std::vector<SqQuadItem> items;
+    SqQuadShape shape;
+    if (getenv("MDX_SQ_NO_COLUMNS") || getenv("MDX_SQ_NO_QUADS") ||
+        !sq_detect_lattice(h->q_host.data(), h->n_q, lat, trip) ||
+        !sq_quad_plan(trip, h->n_q, lat, items, shape, true, 1) || shape.n_sub != 1)
+        return MDX_OK;
+    const int n_items = shape.n_items;
+    std::vector<int> qmap(size_t(SQ_QCOLS) * SQ_ZPT * n_items);
+    for (int k = 0; k < n_items; ++k)
+        for (int c = 0; c < SQ_QCOLS; ++c)
+            for (int j = 0; j < SQ_ZPT; ++j)
+                qmap[size_t(c * SQ_ZPT + j) * n_items + k] = items[(size_t)k].q[c][j];
+    MDX_TRY(h->d_chain_items.ensure(sizeof(SqQuadItem) * items.size()));
+    MDX_TRY(h->d_chain_qmap.ensure(sizeof(int) * qmap.size()));
+    MDX_HIP(hipMemcpy(h->d_chain_items.ptr, items.data(), sizeof(SqQuadItem) * items.size(), hipMemcpyHostToDevice));
+    MDX_HIP(hipMemcpy(h->d_chain_qmap.ptr, qmap.data(), sizeof(int) * qmap.size(), hipMemcpyHostToDevice));
+    MDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(sq_chain_quads_pick(shape.regular_stride)),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.lds));
+    h->chain_items = n_items;
+    h->chain_ipb = shape.ipb;
+    h->chain_regular = shape.regular_stride;
+    h->chain_lat = shape.lat;
+    h->chain_lds = shape.lds;
+    h->chain_quads = true;
+    return MDX_OK;
+}
+
 extern "C" {
 
 int mdx_sq_create(mdx_sq_t *out, int dev, const double *wavevectors, int64_t n_q,
@@ -325,6 +443,8 @@ int mdx_sq_create(mdx_sq_t *out, int dev, const double *wavevectors, int64_t n_q
     h->n_pairs = n_pairs;
     h->offsets.assign(group_offsets, group_offsets + n_groups + 1);
     h->n_total = group_offsets[n_groups];
+    h->q_host.assign(wavevectors, wavevectors + 3 * n_q);
+    h->all_points = n_groups == 1 && group_offsets[0] == 0 && n_pairs == 1 && pairs[0] == -1 && pairs[1] == -1;
     int rc = MDX_OK;
     do {
         if ((rc = stream_acquire(&h->stream)) != MDX_OK)
@@ -420,7 +540,8 @@ int mdx_sq_destroy(mdx_sq_t h)
     // (every stream that touched them is idle: blocks and stream go back to the per-device pools, so that an
     // analysis object per call does not pay hipMalloc / hipFree / stream creation each time)
     for (DeviceBuffer *b : {&h->d_q, &h->d_offsets, &h->d_pairs, &h->d_acc, &h->d_rho, &h->d_stage[0],
-                            &h->d_stage[1], &h->d_index, &h->d_mtrip, &h->d_items, &h->d_qitems})
+                            &h->d_stage[1], &h->d_index, &h->d_mtrip, &h->d_items, &h->d_qitems,
+                            &h->d_chain_items, &h->d_chain_qmap})
         b->recycle();
     h->mol.recycle();
     if (h->stream)
@@ -436,6 +557,29 @@ int mdx_sq_reset(mdx_sq_t h)
     MDX_HIP(hipMemsetAsync(h->d_acc.ptr, 0, size_t(8) * h->n_pairs * h->n_q, h->stream));
     MDX_HIP(hipStreamSynchronize(h->stream));
     h->timer.reset();
+    h->fed = false;
+    return MDX_OK;
+}
+
+int mdx_sq_set_chains(mdx_sq_t h, int64_t chain_length)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    MDX_REQUIRE(!h->fed, "mdx_sq_set_chains must be called before the first frame");
+    if (chain_length <= 0) {
+        h->chain_len = 0;
+        return MDX_OK;
+    }
+    MDX_REQUIRE(h->all_points, "single-chain mode needs one group over all points and pairs = {(-1, -1)}");
+    MDX_REQUIRE(h->n_total >= chain_length && h->n_total % chain_length == 0,
+                "%lld points are not a whole number of chains of %lld", (long long)h->n_total,
+                (long long)chain_length);
+    if (!h->chain_planned) {
+        MDX_TRY(sq_plan_chains(h));
+        h->chain_planned = true;
+    }
+    h->chain_len = chain_length;
     return MDX_OK;
 }
 

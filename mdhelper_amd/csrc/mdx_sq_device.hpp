@@ -9,6 +9,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <map>
+#include <type_traits>
 #include <vector>
 
 namespace mdx_sq_dev {
@@ -389,6 +390,36 @@ __device__ __forceinline__ SqQuadThread sq_quad_thread(const SqQuadItem *items, 
     return t;
 }
 
+// Chain boundaries of sq_quad_frame.  SqNoChains (the S(q) and ISF kernels): none, the particles of [lo, hi) form one
+// sum.  SqChainFold (single-chain structure factor, sq_chain_quads_kernel): every `len` particles from `lo` a chain
+// ends; fold() adds |rho_c|^2 of the thread's 4 x 8 block to the thread's own partial sums in global memory (one
+// slot per wavevector of the block: no other thread touches them) and clears the
+// accumulators.  The fold needs n_sub == 1: every live thread then walks the same particles in the same order, so a
+// chain boundary falls on the same particle for every lane.
+struct SqNoChains {};
+struct SqChainFold {
+    int64_t next;      // first particle past the current chain
+    int64_t len;       // particles per chain
+    double *base;      // the block's partial sums: entry (c, j) of item `item` at base[(c * SQ_ZPT + j) * stride + item]
+    int stride, item;
+    __device__ __forceinline__ void fold(double (&ar)[SQ_QCOLS][SQ_ZPT], double (&ai)[SQ_QCOLS][SQ_ZPT])
+    {
+        // a wave-uniform row address plus the lane's item, the latter made opaque here: left alone the compiler
+        // hoists all 32 per-lane 64-bit addresses out of the particle loop, 64 VGPRs that push the kernel into scratch
+        int lane_item = item;
+        asm volatile("" : "+v"(lane_item));
+#pragma unroll
+        for (int c = 0; c < SQ_QCOLS; ++c)
+#pragma unroll
+            for (int j = 0; j < SQ_ZPT; ++j) {
+                double *row = base + (c * SQ_ZPT + j) * stride;
+                row[lane_item] += ar[c][j] * ar[c][j] + ai[c][j] * ai[c][j];
+                ar[c][j] = ai[c][j] = 0.0;
+            }
+        next += len;
+    }
+};
+
 // The regular form of sq_quad_frame (RS > 0: see there).  Beyond the item shape the host guarantees a SIMPLE
 // lattice: every axis has m = 0 ... R - 1 with one R (the reference's grids, n = arange(n_points):
 // structure.py:1376-1381), and lat.tile = RS - SQ_QUAD_PAD.  That makes the table fill branch-free and the same
@@ -397,11 +428,11 @@ __device__ __forceinline__ SqQuadThread sq_quad_thread(const SqQuadItem *items, 
 // its coordinate, its axis' base, mmin and R per lane and runs per-lane trip counts: ~175 instructions and one
 // memory latency per tile and thread against ~100 and none here).  E(m) is the same chain of products as in
 // sq_quad_fill (E(1) = 1 * (c, s) exactly), so both forms give the same bits.
-template <bool REAL_ONLY, int RS>
+template <bool REAL_ONLY, int RS, class Chains = SqNoChains>
 __device__ __forceinline__ void sq_quad_frame_regular(double2 *lat_tab, const SqLattice &lat,
                                                       const SqQuadThread &t, const float *P, const float *Pprev,
                                                       int64_t lo, int64_t hi, double (&ar)[SQ_QCOLS][SQ_ZPT],
-                                                      double (&ai)[SQ_QCOLS][SQ_ZPT])
+                                                      double (&ai)[SQ_QCOLS][SQ_ZPT], Chains *chains = nullptr)
 {
     constexpr int A = RS - SQ_QUAD_PAD;                                          // particles per tile
     constexpr int NT = (3 * A + SQ_QUAD_THREADS - 1) / SQ_QUAD_THREADS;         // fill tasks per thread
@@ -521,22 +552,50 @@ __device__ __forceinline__ void sq_quad_frame_regular(double2 *lat_tab, const Sq
         // U particles per trip (a tile of 80 gives every thread a multiple of five, the other tiles of four):
         // one set of address updates and one branch per U particles
         constexpr int U = A % 5 == 0 ? 5 : 4;
-        int i = 0;
+        if constexpr (std::is_same_v<Chains, SqNoChains>) {
+            int i = 0;
 #pragma unroll 1
-        for (; i + U <= mine; i += U) {
+            for (; i + U <= mine; i += U) {
 #pragma unroll
-            for (int u = 0; u < U; ++u)
-                particle(16 * u);
-            px += 16 * U;
-            py += 16 * U;
-            pz += 16 * U;
-        }
+                for (int u = 0; u < U; ++u)
+                    particle(16 * u);
+                px += 16 * U;
+                py += 16 * U;
+                pz += 16 * U;
+            }
 #pragma unroll 1
-        for (; i < mine; ++i) {
-            particle(0);
-            px += 16;
-            py += 16;
-            pz += 16;
+            for (; i < mine; ++i) {
+                particle(0);
+                px += 16;
+                py += 16;
+                pz += 16;
+            }
+        } else {
+            // the same trips, cut into segments that end where a chain ends (the same particle for every live lane);
+            // the pipeline state (the next particle's e_x, e_y) carries over a fold
+            int i = 0;
+#pragma unroll 1
+            while (i < mine) {
+                const int end = (int)min<int64_t>(mine, chains->next - base);
+#pragma unroll 1
+                for (; i + U <= end; i += U) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u)
+                        particle(16 * u);
+                    px += 16 * U;
+                    py += 16 * U;
+                    pz += 16 * U;
+                }
+#pragma unroll 1
+                for (; i < end; ++i) {
+                    particle(0);
+                    px += 16;
+                    py += 16;
+                    pz += 16;
+                }
+                if (base + i == chains->next)
+                    chains->fold(ar, ai);
+            }
         }
         __syncthreads();
     }
@@ -550,14 +609,14 @@ __device__ __forceinline__ void sq_quad_frame_regular(double2 *lat_tab, const Sq
 // one address each: 13 LDS reads and three address registers where the general form has 16 and 16 (the address
 // arithmetic was 0.5 of the 6.3 VALU instructions per 64 terms, the reads 0.5 per term).  Full grids — the
 // reference's default wavevector sets, structure.py:1376-1381 — are regular; anything else takes RS = 0.
-template <bool REAL_ONLY, int RS>
+template <bool REAL_ONLY, int RS, class Chains = SqNoChains>
 __device__ __forceinline__ void sq_quad_frame(double2 *lat_tab, const SqLattice &lat,
                                               const SqQuadThread &t, const float *P, const float *Pprev,
                                               int64_t lo, int64_t hi, double (&ar)[SQ_QCOLS][SQ_ZPT],
-                                              double (&ai)[SQ_QCOLS][SQ_ZPT])
+                                              double (&ai)[SQ_QCOLS][SQ_ZPT], Chains *chains = nullptr)
 {
     if constexpr (RS > 0) {
-        sq_quad_frame_regular<REAL_ONLY, RS>(lat_tab, lat, t, P, Pprev, lo, hi, ar, ai);
+        sq_quad_frame_regular<REAL_ONLY, RS, Chains>(lat_tab, lat, t, P, Pprev, lo, hi, ar, ai, chains);
         return;
     }
     const int tid = threadIdx.x, A = lat.tile;
@@ -616,6 +675,10 @@ __device__ __forceinline__ void sq_quad_frame(double2 *lat_tab, const SqLattice 
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 ez = ezn;
+            }
+            if constexpr (!std::is_same_v<Chains, SqNoChains>) {
+                if (base + i + 1 == chains->next)
+                    chains->fold(ar, ai);
             }
         }
         __syncthreads();
@@ -753,6 +816,126 @@ inline IsfIncQuadsFn isf_incoherent_quads_pick(int regular_stride)
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Single-chain structure factor: sum_c |rho_c(q)|^2 with rho_c(q) = sum_{j in chain c} exp(i q . r_j), chain c =
+// points [c len, (c + 1) len).  Particle splits are whole chains (chains_per_split of them from split sp), so no
+// chain spans two blocks and every |rho_c|^2 is formed in the block that sums rho_c.
+
+// Register-blocked lattice form: the tables, tile pipeline and 4 x 8 accumulator block of sq_rho_quads_kernel with
+// one copy per item (n_sub = 1), folding |rho_c|^2 at every chain end into the thread's own slots of
+// part[frame][split][c * SQ_ZPT + j][item] (SqChainFold: read, add, write by the one thread that owns the slot).
+// The running sums stay in memory, not in registers: 32 more fp64 values would take the kernel past 256 VGPRs,
+// to one wave per SIMD.
+template <int RS>
+__global__ __launch_bounds__(SQ_QUAD_THREADS, 2) void sq_chain_quads_kernel(
+    const float *__restrict__ pos, int64_t n_atoms, const SqQuadItem *__restrict__ items, int n_items, int ipb,
+    SqLattice lat, int64_t n_points, int64_t chain_len, int64_t chains_per_split, int n_split,
+    double *__restrict__ part)
+{
+    extern __shared__ double2 lat_tab[];
+    const SqQuadThread t = sq_quad_thread(items, n_items, ipb, 1, lat);
+    const int sp = blockIdx.y;
+    const int frame = blockIdx.z;
+    double ar[SQ_QCOLS][SQ_ZPT], ai[SQ_QCOLS][SQ_ZPT];
+#pragma unroll
+    for (int c = 0; c < SQ_QCOLS; ++c)
+#pragma unroll
+        for (int j = 0; j < SQ_ZPT; ++j)
+            ar[c][j] = ai[c][j] = 0.0;
+    const int64_t lo = min(n_points, sp * chains_per_split * chain_len);
+    const int64_t hi = min(n_points, lo + chains_per_split * chain_len);
+    SqChainFold chains;
+    chains.next = lo + chain_len;
+    chains.len = chain_len;
+    chains.base = part + (int64_t(frame) * n_split + sp) * (SQ_QCOLS * SQ_ZPT) * int64_t(n_items);
+    chains.stride = n_items;
+    chains.item = t.item;
+    if (t.live) {
+#pragma unroll
+        for (int k = 0; k < SQ_QCOLS * SQ_ZPT; ++k)
+            chains.base[k * chains.stride + chains.item] = 0.0;
+    }
+    sq_quad_frame<false, RS, SqChainFold>(lat_tab, lat, t, pos + int64_t(frame) * n_atoms * 3, nullptr, lo, hi, ar,
+                                          ai, &chains);
+}
+
+using SqChainQuadsFn = void (*)(const float *, int64_t, const SqQuadItem *, int, int, SqLattice, int64_t, int64_t,
+                                int64_t, int, double *);
+inline SqChainQuadsFn sq_chain_quads_pick(int regular_stride)
+{
+    switch (regular_stride) {
+#define MDX_CASE(S) case S: return sq_chain_quads_kernel<S>;
+        MDX_SQ_QUAD_STRIDES(MDX_CASE)
+#undef MDX_CASE
+    default: return sq_chain_quads_kernel<0>;
+    }
+}
+
+// Plain form for any wavevector set (the quad planner's rejects, MDX_SQ_NO_QUADS=1): SQ_QPT wavevectors per thread,
+// one sincos_f64 per term as in sq_rho_kernel; the particles stream through LDS, every thread walks them in the same
+// order, so the chain ends are block-uniform.  part[frame][split][q].
+__global__ __launch_bounds__(SQ_THREADS) void sq_chain_sincos_kernel(
+    const float *__restrict__ pos, int64_t n_atoms, const double *__restrict__ qv, int n_q, int64_t n_points,
+    int64_t chain_len, int64_t chains_per_split, int n_split, double *__restrict__ part)
+{
+    __shared__ float sx[SQ_TILE], sy[SQ_TILE], sz[SQ_TILE];
+    const int tid = threadIdx.x;
+    const int qb = blockIdx.x;
+    const int sp = blockIdx.y;
+    const int frame = blockIdx.z;
+
+    double q0[SQ_QPT], q1[SQ_QPT], q2[SQ_QPT], ac[SQ_QPT], as[SQ_QPT], sum[SQ_QPT];
+#pragma unroll
+    for (int u = 0; u < SQ_QPT; ++u) {
+        int qi = qb * SQ_QPB + u * SQ_THREADS + tid;
+        bool ok = qi < n_q;
+        q0[u] = ok ? qv[3 * int64_t(qi) + 0] : 0.0;
+        q1[u] = ok ? qv[3 * int64_t(qi) + 1] : 0.0;
+        q2[u] = ok ? qv[3 * int64_t(qi) + 2] : 0.0;
+        ac[u] = as[u] = sum[u] = 0.0;
+    }
+    const int64_t lo = min(n_points, sp * chains_per_split * chain_len);
+    const int64_t hi = min(n_points, lo + chains_per_split * chain_len);
+    const float *P = pos + int64_t(frame) * n_atoms * 3;
+    int64_t next = lo + chain_len;
+
+    for (int64_t base = lo; base < hi; base += SQ_TILE) {
+        const int cnt = (int)min<int64_t>(SQ_TILE, hi - base);
+        __syncthreads();
+        for (int e = tid; e < cnt * 3; e += SQ_THREADS) {
+            float v = P[base * 3 + e];
+            int a = e / 3, k = e - 3 * a;
+            (k == 0 ? sx : k == 1 ? sy : sz)[a] = v;
+        }
+        __syncthreads();
+        for (int a = 0; a < cnt; ++a) {
+            const double x = (double)sx[a], y = (double)sy[a], z = (double)sz[a];
+#pragma unroll
+            for (int u = 0; u < SQ_QPT; ++u) {
+                double ph = fma(q2[u], z, fma(q1[u], y, q0[u] * x));
+                double s, c;
+                sincos_f64(ph, s, c);
+                ac[u] += c;
+                as[u] += s;
+            }
+            if (base + a + 1 == next) {
+#pragma unroll
+                for (int u = 0; u < SQ_QPT; ++u) {
+                    sum[u] += ac[u] * ac[u] + as[u] * as[u];
+                    ac[u] = as[u] = 0.0;
+                }
+                next += chain_len;
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < SQ_QPT; ++u) {
+        int qi = qb * SQ_QPB + u * SQ_THREADS + tid;
+        if (qi < n_q)
+            part[(int64_t(frame) * n_split + sp) * n_q + qi] = sum[u];
+    }
+}
+
 // Host: quad items of a detected lattice set.  Columns are cut into chunks of SQ_ZPT consecutive
 // m_z; chunks with the same m_z list are grouped four at a time (the last group of a list is
 // padded with a repeated column that writes nothing).  Returns false when less than 60 % of the
@@ -881,8 +1064,10 @@ struct SqQuadShape {
     int blocks() const { return (n_items + ipb - 1) / ipb; }
 };
 
+// max_sub caps the copies per item (1 for the single-chain kernel).
 inline bool sq_quad_plan(const std::vector<short> &trip, int64_t n_q, const SqLattice &base,
-                         std::vector<SqQuadItem> &items, SqQuadShape &sh, bool allow_regular = true)
+                         std::vector<SqQuadItem> &items, SqQuadShape &sh, bool allow_regular = true,
+                         int max_sub = SQ_QUAD_THREADS)
 {
     // regular items (aligned blocks) where they use their accumulators about as well as the general items: the
     // regular form of the kernel does ~1.1 x the slots per second (measured on full 10^3 / 20^3 grids and sphere
@@ -915,7 +1100,7 @@ inline bool sq_quad_plan(const std::vector<short> &trip, int64_t n_q, const SqLa
             return false;
         SqQuadShape again;
         std::vector<SqQuadItem> gen;
-        const bool ok = sq_quad_plan(trip, n_q, base, gen, again, false);
+        const bool ok = sq_quad_plan(trip, n_q, base, gen, again, false, max_sub);
         if (ok) {
             items.swap(gen);
             sh = again;
@@ -950,7 +1135,7 @@ inline bool sq_quad_plan(const std::vector<short> &trip, int64_t n_q, const SqLa
         if (ipb > SQ_QUAD_THREADS)
             continue;
         const int blocks = (sh.n_items + ipb - 1) / ipb;
-        int c = SQ_QUAD_THREADS / ipb, tile = 0;
+        int c = std::min(SQ_QUAD_THREADS / ipb, max_sub), tile = 0;
         while (c >= 1 && !(tile = tile_for(c)))
             --c;
         if (c >= 1) {
