@@ -22,6 +22,21 @@ def _level_ids(group, grouping):
     return np.asarray(ids)
 
 
+def molecule_rows(group, grouping):
+    """
+    ``(particle indices, CSR offsets, masses)`` of ``group`` with the rows sorted molecule by molecule (atom
+    order kept inside a molecule): what the engines form residue / segment centres of mass on the device
+    from.  ``grouping="atoms"``: ``(indices, None, None)``.
+    """
+    idx = np.asarray(group.indices)
+    if grouping == "atoms":
+        return idx, None, None
+    _, inverse = np.unique(_level_ids(group, grouping), return_inverse=True)
+    order = np.argsort(inverse, kind="stable")
+    offsets = np.concatenate(([0], np.cumsum(np.bincount(inverse))))
+    return idx[order], offsets, np.asarray(group.masses, dtype=np.float64)[order]
+
+
 def center_of_mass(group=None, grouping: str = None, *, masses=None, positions=None,
                    images=None, dimensions=None, n_groups: int = None, raw: bool = False):
     r"""

@@ -26,7 +26,7 @@ from typing import Any, TextIO, Union
 
 import numpy as np
 
-from ..comm import SerialComm
+from ..comm import SerialComm, shard_range
 
 
 class Hash(dict):
@@ -91,6 +91,23 @@ class AnalysisBase:
         if hasattr(st, "frames"):
             return np.asarray(st.frames, dtype=int)
         return np.arange(self.start, self.stop, self.step)
+
+    def _batched_frames(self, start, stop, step, frames, *, shard: bool) -> np.ndarray:
+        """
+        Prologue of a ``run()`` that hands whole blocks of frames to an engine: ``_setup_frames`` →
+        ``_prepare`` → ``frames`` / ``times`` of every selected frame.  Returns the frame numbers this
+        rank analyses: its contiguous share when frames shard across ranks (``shard``), else all of them.
+        """
+        traj = self._trajectory
+        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
+        self._prepare()
+        numbers = self._frame_numbers()
+        self.frames[:] = numbers
+        self.times[:] = numbers * traj.dt
+        if not shard:
+            return numbers
+        lo, hi = shard_range(len(numbers), self._comm.rank, self._comm.world_size)
+        return numbers[lo:hi]
 
     def _prepare(self):
         pass
@@ -213,3 +230,67 @@ class FrameBatcher:
             self._flush([b[:self._n] for b in self._pos],
                         None if self._box is None else self._box[:self._n])
             self._n = 0
+
+
+# The batched frame feed of the classes' run(): trajectories with block access hand whole blocks of frames to an
+# engine, read from a trajectory file, from float32 frames already in HBM or from host memory.
+
+FILE_BLOCK = 4096       # frames per trajectory-file call, at least (the library pipelines inside a call)
+
+
+def has_frame_blocks(traj) -> bool:
+    """Whether ``traj`` hands out blocks of frames (``ArrayTrajectory``, ``DeviceTrajectory``,
+    ``io.FileTrajectory``); other readers go through the per-frame ``AnalysisBase.run``."""
+    return hasattr(traj, "frame_block") and hasattr(traj, "box_block")
+
+
+def block_frames(n_atoms: int, least: int, nbytes: int) -> int:
+    """Frames per engine call: as many as ``nbytes`` of float32 positions of ``n_atoms`` hold, at least ``least``."""
+    return max(least, nbytes // max(12 * n_atoms, 1))
+
+
+def frame_blocks(frames, size):
+    """``frames`` in consecutive blocks of ``size``."""
+    for b0 in range(0, len(frames), size):
+        yield frames[b0:b0 + size]
+
+
+def all_particles(index, n_atoms) -> bool:
+    """Whether ``index`` is every particle in order: the engines then read the frames without a gather."""
+    return len(index) == n_atoms and np.array_equal(index, np.arange(len(index)))
+
+
+def block_source(traj, frames, hbm: bool):
+    """
+    Where the engine reads the block ``frames`` from: ``("file", TrajectoryFile)`` (frames stream file -> pinned
+    memory -> HBM inside the library); ``("hbm", rows)`` when ``hbm`` allows it and the frames are consecutive
+    float32 frames already in HBM (``ArrayUniverse.from_device``: the kernels read them where they lie); else
+    ``("host", positions[len(frames), n_atoms, 3])`` for the caller to gather from.
+    """
+    native = getattr(traj, "native", None)
+    if native is not None:
+        return "file", native
+    if hbm and getattr(traj, "device_block", None) is not None and traj.device_array.dtype == np.float32:
+        rows = traj.device_block(frames)
+        if rows is not None:
+            return "hbm", rows
+    return "host", traj.frame_block(frames)
+
+
+def accumulate_blocks(engine, traj, frames, index, capacity: int, *, hbm: bool) -> None:
+    """
+    ``frames`` into a Fourier-sum engine (``SqEngine``, ``IsfEngine``), particles ``index`` of every frame in that
+    order, block by block: ``FILE_BLOCK`` frames per ``accumulate_traj`` from a file, else ~1 GiB (at least
+    ``capacity`` frames) per ``accumulate_device`` (``hbm``: the engine has no grouping set) or ``accumulate``.
+    """
+    whole = all_particles(index, traj.n_atoms)
+    size = (FILE_BLOCK if getattr(traj, "native", None) is not None
+            else block_frames(traj.n_atoms, capacity, 1 << 30))
+    for sel in frame_blocks(frames, size):
+        route, src = block_source(traj, sel, hbm and whole)
+        if route == "file":
+            engine.accumulate_traj(src, sel, None if whole else index)
+        elif route == "hbm":
+            engine.accumulate_device(src.ptr, traj.n_atoms, len(sel))
+        else:
+            engine.accumulate(src if whole else src[:, index])

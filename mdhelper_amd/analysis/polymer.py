@@ -37,7 +37,8 @@ from ..algorithm import correlation
 from ..algorithm.topology import unwrap_edge
 from ..algorithm.unit import strip_unit
 from ..comm import shard_range
-from .base import DynamicAnalysisBase, FrameBatcher
+from .base import (DynamicAnalysisBase, FrameBatcher, accumulate_blocks, block_frames, frame_blocks,
+                   has_frame_blocks)
 
 _GROUPINGS = {"atoms", "residues"}
 
@@ -288,20 +289,17 @@ class EndToEndVector(_PolymerAnalysisBase):
     def run(self, start=None, stop=None, step=None, frames=None, n_jobs: int = 1, verbose=None,
             **kwargs):
         traj = self._trajectory
-        if not hasattr(traj, "frame_block"):
+        if not has_frame_blocks(traj):
             return super().run(start=start, stop=stop, step=step, frames=frames, n_jobs=n_jobs,
                                verbose=verbose, **kwargs)
-        # in-memory and native-file trajectories: the end monomers of all frames at once
-        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
-        self._prepare()
-        numbers = self._frame_numbers()
-        self.frames[:] = numbers
-        self.times[:] = numbers * traj.dt
-        chunk = max(1, int(2 ** 28 // (12 * self.universe.atoms.n_atoms)))
-        for f0 in range(0, len(numbers), chunk):
-            block = traj.frame_block(numbers[f0:f0 + chunk])
+        # trajectories with block access: the end monomers of ~256 MiB of frames at a time
+        first = 0
+        for chunk in frame_blocks(self._batched_frames(start, stop, step, frames, shard=False),
+                                  block_frames(self.universe.atoms.n_atoms, 1, 1 << 28)):
+            block = traj.frame_block(chunk)
             for sel, s in zip(self._selections, self._slices):
-                self._store(f0, self._ends_of_block(block[:, sel[0]], sel), s)
+                self._store(first, self._ends_of_block(block[:, sel[0]], sel), s)
+            first += len(chunk)
         self._conclude()
         return self
 
@@ -504,38 +502,18 @@ class SingleChainStructureFactor(DynamicAnalysisBase):
             return
         self._batch.add([self._points(self._sel)])
 
-    # in-memory, HBM-resident and file trajectories: whole blocks of frames go to the engine, as in
-    # StructureFactor.run; monomer centres of mass are formed on the device
+    # batched run (the frame feed of base.py), as in StructureFactor.run; monomer centres of mass are
+    # formed on the device
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        from .structure import _device_frames, _is_array_trajectory
-        traj = self._trajectory
-        if not _is_array_trajectory(traj):
+        if not has_frame_blocks(self._trajectory):
             return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
                                **kwargs)
-        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
-        self._prepare()
-        numbers = self._frame_numbers()
-        self.frames[:] = numbers
-        self.times[:] = numbers * traj.dt
-        lo, hi = self._frames_mine
-        mine = numbers[lo:hi]
+        mine = self._batched_frames(start, stop, step, frames, shard=True)
         index, offsets, masses = self._sel
         if offsets is not None:
             self._engine.set_grouping(offsets, masses)
-        identity = len(index) == traj.n_atoms and np.array_equal(index, np.arange(len(index)))
-        native = getattr(traj, "native", None)
-        block = 4096 if native is not None else max(self._batch.capacity,
-                                                     (1 << 30) // max(12 * traj.n_atoms, 1))
-        for b0 in np.arange(0, len(mine), block):
-            sel = mine[b0:b0 + block]
-            resident = _device_frames(traj, sel) if (identity and offsets is None) else None
-            if native is not None:
-                self._engine.accumulate_traj(native, sel, None if identity else index)
-            elif resident is not None:
-                self._engine.accumulate_device(resident.ptr, traj.n_atoms, len(sel))   # frames already in HBM
-            else:
-                pos = traj.frame_block(sel)
-                self._engine.accumulate(pos if identity else pos[:, index])
+        accumulate_blocks(self._engine, self._trajectory, mine, index, self._batch.capacity,
+                          hbm=offsets is None)
         self._conclude()
         return self
 

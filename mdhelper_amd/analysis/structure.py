@@ -29,12 +29,13 @@ from scipy.signal import argrelextrema
 from scipy.special import jv
 
 from .. import _core
-from ..algorithm.molecule import center_of_mass
+from ..algorithm.molecule import center_of_mass, molecule_rows
 from ..algorithm.unit import strip_unit
 from ..algorithm.utility import get_closest_factors
 from ..comm import shard_range
 from ..universe import box_volumes
-from .base import DynamicAnalysisBase, FrameBatcher, NumbaAnalysisBase
+from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, NumbaAnalysisBase, accumulate_blocks,
+                   all_particles, block_frames, block_source, frame_blocks, has_frame_blocks)
 
 _GROUPINGS_RDF = {"atoms", "residues", "segments"}
 _KB_KJ_PER_MOL_K = 8.31446261815324e-3   # N_A * k_B in kJ/(mol K)
@@ -142,19 +143,6 @@ def calculate_structure_factor(r, g, equal: bool, rho: float, x_i: float = 1, x_
 
 def _group_positions(group, grouping):
     return group.positions if grouping == "atoms" else center_of_mass(group, grouping)
-
-
-def _is_array_trajectory(traj) -> bool:
-    return hasattr(traj, "frame_block") and hasattr(traj, "box_block")
-
-
-def _device_frames(traj, frames):
-    """The listed frames as a float32 device array without a copy (a ``universe.DeviceTrajectory`` over float32
-    frames, consecutive frames), else None: the caller then goes through host memory."""
-    block = getattr(traj, "device_block", None)
-    if block is None or traj.device_array.dtype != np.float32:
-        return None
-    return block(frames)
 
 
 class RadialDistributionFunction(DynamicAnalysisBase):
@@ -300,56 +288,32 @@ class RadialDistributionFunction(DynamicAnalysisBase):
                                * self.n_frames / self._area_or_volume)
         self.results.rdf = self.results.counts / norm
 
-    # batched fast path for in-memory and file trajectories: frames go to the engine in
-    # contiguous blocks instead of one Python iteration per frame; residue / segment centres
-    # of mass are formed on the device (mdx_rdf_set_grouping)
-    @staticmethod
-    def _selection(ag, grouping):
-        """(particle indices, CSR offsets or None, masses or None) of one side of the histogram."""
-        idx = np.asarray(ag.indices)
-        if grouping == "atoms":
-            return idx, None, None
-        from ..algorithm.molecule import _level_ids
-        _, inverse = np.unique(_level_ids(ag, grouping), return_inverse=True)
-        order = np.argsort(inverse, kind="stable")        # molecule by molecule, atom order kept
-        offsets = np.concatenate(([0], np.cumsum(np.bincount(inverse))))
-        return idx[order], offsets, np.asarray(ag.masses, dtype=np.float64)[order]
-
+    # batched run (the frame feed of base.py): frames go to the engine in blocks instead of one Python
+    # iteration per frame; residue / segment centres of mass are formed on the device (mdx_rdf_set_grouping)
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
         traj = self._trajectory
-        fast = _is_array_trajectory(traj)
-        if not fast:
+        if not has_frame_blocks(traj):
             return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
                                **kwargs)
-        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
-        self._prepare()
-        numbers = self._frame_numbers()
-        self.frames[:] = numbers
-        self.times[:] = numbers * traj.dt
-        lo, hi = self._frames_mine
-        mine = numbers[lo:hi]
-        block = self._batch.capacity
-        i1, off1, m1 = self._selection(self.ag1, self._groupings[0])
-        i2, off2, m2 = (i1, off1, m1) if self._same else self._selection(self.ag2, self._groupings[1])
+        mine = self._batched_frames(start, stop, step, frames, shard=True)
+        i1, off1, m1 = molecule_rows(self.ag1, self._groupings[0])
+        i2, off2, m2 = (i1, off1, m1) if self._same else molecule_rows(self.ag2, self._groupings[1])
         if off1 is not None:
             self._engine.set_grouping(1, off1, m1)
         if off2 is not None and not self._same:
             self._engine.set_grouping(2, off2, m2)
         # 2-D mode: the coordinate is zeroed and the cell stretched on the device (:761-766)
         self._engine.set_drop_axis(self._drop_axis)
-        all1 = len(i1) == traj.n_atoms and np.array_equal(i1, np.arange(len(i1)))
-        native = getattr(traj, "native", None)
-        contiguous = len(mine) < 2 or bool(np.all(np.diff(mine) == 1))
-        if native is not None:
-            # trajectory file: raw frames stream file -> pinned memory -> HBM inside the library
-            block = max(block, 4096, (4 << 30) // max(12 * traj.n_atoms, 1))
+        all1 = all_particles(i1, traj.n_atoms)
+        if getattr(traj, "native", None) is not None:
+            size = block_frames(traj.n_atoms, max(self._batch.capacity, FILE_BLOCK), 4 << 30)
         else:
             # in-memory frames are handed over where they lie (slices, no copy): ~4 GiB per call (1 GiB when
-            # the selection has to be gathered first); the library pipelines inside a call (copy of slab
+            # the frames have to be gathered first); the library pipelines inside a call (copy of slab
             # k + 1 beside the kernels of slab k), every call boundary drains that pipeline once
-            block = max(block, ((4 if contiguous else 1) << 30) // max(12 * traj.n_atoms, 1))
-        for b0 in np.arange(0, len(mine), block):
-            sel = mine[b0:b0 + block]
+            contiguous = len(mine) < 2 or bool(np.all(np.diff(mine) == 1))
+            size = block_frames(traj.n_atoms, self._batch.capacity, (4 if contiguous else 1) << 30)
+        for sel in frame_blocks(mine, size):
             boxes = traj.box_block(sel)
             if self._drop_axis is None:
                 self._area_or_volume += float(box_volumes(boxes).sum())
@@ -357,28 +321,23 @@ class RadialDistributionFunction(DynamicAnalysisBase):
                 self._area_or_volume += float(
                     np.delete(np.asarray(boxes, dtype=np.float32)[:, :3], self._drop_axis, axis=1)
                     .prod(axis=1, dtype=np.float32).astype(float).sum())
-            if native is not None:
-                self._engine.accumulate_traj(native, sel, boxes, None if all1 else i1,
+            # frames in HBM are read where they lie for one group of every particle
+            route, src = block_source(traj, sel, all1 and self._same and off1 is None)
+            if route == "file":
+                self._engine.accumulate_traj(src, sel, boxes, None if all1 else i1,
                                              None if self._same else i2, same=self._same)
-                continue
-            resident = _device_frames(traj, sel) if (all1 and self._same and off1 is None) else None
-            if resident is not None:
-                # float32 frames already in HBM (ArrayUniverse.from_device), every particle, one group: the
-                # kernels read them where they lie
+            elif route == "hbm":
                 d_boxes = _core.DeviceArray.from_host(
                     np.ascontiguousarray(np.broadcast_to(np.asarray(boxes, dtype=np.float32), (len(sel), 6))),
                     self._device)
                 try:
-                    self._engine.accumulate_device(resident.ptr, traj.n_atoms, None, traj.n_atoms, d_boxes.ptr,
+                    self._engine.accumulate_device(src.ptr, traj.n_atoms, None, traj.n_atoms, d_boxes.ptr,
                                                    len(sel))
                     self._engine.synchronize()
                 finally:
                     d_boxes.free()
-                continue
-            pos = traj.frame_block(sel)
-            p1 = pos if all1 else pos[:, i1]
-            p2 = None if self._same else pos[:, i2]
-            self._engine.accumulate(p1, p2, boxes)
+            else:
+                self._engine.accumulate(src if all1 else src[:, i1], None if self._same else src[:, i2], boxes)
         self._conclude()
         return self
 
@@ -613,58 +572,29 @@ class StructureFactor(NumbaAnalysisBase):
             self._positions[s] = _group_positions(g, gr)
         self._batch.add([self._positions])
 
-    # batched fast path (in-memory and file trajectories, groupings="atoms"): whole blocks of
-    # frames go to the engine, gathered in concatenated-group order, instead of one Python
-    # iteration per frame.  Shared with IntermediateScatteringFunction.
+    _shard_frames = True     # frames shard across ranks (IntermediateScatteringFunction shards wavevectors)
+
+    # batched run (the frame feed of base.py), shared with IntermediateScatteringFunction: whole blocks of
+    # frames go to the engine, gathered in concatenated-group order, instead of one Python iteration per frame
     def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not _is_array_trajectory(traj):
+        if not has_frame_blocks(self._trajectory):
             return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
                                **kwargs)
-        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
-        self._prepare()
-        numbers = self._frame_numbers()
-        self.frames[:] = numbers
-        self.times[:] = numbers * traj.dt
-        lo, hi = getattr(self, "_frames_mine", (0, len(numbers)))
-        mine = numbers[lo:hi]
-        if all(g == "atoms" for g in self._groupings):
-            index = np.concatenate([np.asarray(g.indices) for g in self._groups])
-        elif self._engine is not None:
-            # residue / segment centres of mass are formed on the device: rows sorted molecule
-            # by molecule; plain-atom groups enter as molecules of one particle and unit mass
-            rows, sizes, masses = [], [], []
-            for g, gr in zip(self._groups, self._groupings):
-                idx, off, m = RadialDistributionFunction._selection(g, gr)
-                rows.append(idx)
-                sizes.append(np.ones(len(idx), dtype=np.int64) if off is None else np.diff(off))
-                masses.append(np.ones(len(idx)) if m is None else m)
-            index = np.concatenate(rows)
-            self._engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
-                                      np.concatenate(masses))
-        else:
-            index = np.zeros(0, dtype=int)
-        identity = len(index) == traj.n_atoms and np.array_equal(index, np.arange(len(index)))
-        native = getattr(traj, "native", None)
-        block = 4096 if native is not None else max(self._batch.capacity,
-                                                     (1 << 30) // max(12 * traj.n_atoms, 1))
-        for b0 in np.arange(0, len(mine), block):
-            sel = mine[b0:b0 + block]
-            if self._engine is None:       # an ISF rank without wavevectors of its own
-                break
-            resident = _device_frames(traj, sel) if (identity and not self._engine_has_grouping()) else None
-            if native is not None:
-                self._engine.accumulate_traj(native, sel, None if identity else index)
-            elif resident is not None:
-                self._engine.accumulate_device(resident.ptr, traj.n_atoms, len(sel))      # frames already in HBM
-            else:
-                pos = traj.frame_block(sel)
-                self._engine.accumulate(pos if identity else pos[:, index])
+        mine = self._batched_frames(start, stop, step, frames, shard=self._shard_frames)
+        if self._engine is not None:        # (an ISF rank without wavevectors of its own adds nothing)
+            grouped = any(g != "atoms" for g in self._groupings)
+            rows = [molecule_rows(g, gr) for g, gr in zip(self._groups, self._groupings)]
+            if grouped:
+                # residue / segment centres of mass are formed on the device: rows sorted molecule
+                # by molecule; plain-atom groups enter as molecules of one particle and unit mass
+                sizes = [np.ones(len(i), dtype=np.int64) if off is None else np.diff(off) for i, off, _ in rows]
+                masses = [np.ones(len(i)) if m is None else m for i, _, m in rows]
+                self._engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
+                                          np.concatenate(masses))
+            accumulate_blocks(self._engine, self._trajectory, mine, np.concatenate([r[0] for r in rows]),
+                              self._batch.capacity, hbm=not grouped)
         self._conclude()
         return self
-
-    def _engine_has_grouping(self) -> bool:
-        return any(g != "atoms" for g in self._groupings)
 
     def _conclude(self) -> None:
         self._batch.flush()
@@ -710,6 +640,8 @@ class IntermediateScatteringFunction(StructureFactor):
     sums live on the GPU (``mdx_isf_*``).  Frames are consumed in order, so this
     analysis does not shard over frames.
     """
+
+    _shard_frames = False    # every rank sees all frames and owns a block of wavevectors (_prepare)
 
     def __init__(self, groups, groupings: Union[str, tuple] = "atoms", *, mode: str = None,
                  form: str = "exp", dimensions=None, dt=None, n_points: int = 32,

@@ -20,6 +20,7 @@ Fits and unit conversions are O(N_t) host NumPy exactly as in the reference.
 
 from __future__ import annotations
 
+import functools
 import itertools
 import time
 import warnings
@@ -30,11 +31,11 @@ from scipy import optimize
 
 from .. import _core
 from ..algorithm import correlation
-from ..algorithm.molecule import center_of_mass
+from ..algorithm.molecule import center_of_mass, molecule_rows
 from ..algorithm.topology import make_whole_images, unwrap, wrap
 from ..algorithm.unit import strip_unit
 from ..comm import shard_range
-from .base import SerialAnalysisBase
+from .base import SerialAnalysisBase, has_frame_blocks
 
 _KB_KJ_PER_MOL_K = 8.31446261815324e-3      # N_A k_B, kJ/(mol K)
 _NA_E2 = 6.02214076e23 * 1.602176634e-19 ** 2   # N_A e^2 (C^2/mol), reference :331-334
@@ -138,6 +139,40 @@ def calculate_transference_number(L_ij, z) -> np.ndarray:
     z = np.asarray(z, dtype=float)
     s = z * (np.asarray(L_ij) * z).sum(axis=-1)
     return s / s.sum(axis=-1, keepdims=True)
+
+
+def _frame_route(eng, traj, numbers, native, resident):
+    """
+    ``(system_com(rows, masses, **kw), push(group, rows, **kw))`` over the analysed frames ``numbers``, by where
+    they are: in HBM (``resident``), in a trajectory file (``native``), or float32 in host memory — the same device
+    stages, fed from there.
+    """
+    if resident is not None:
+        return (functools.partial(eng.system_com_device, resident, resident.shape[1]),
+                functools.partial(_push_resident, eng, resident))
+    if native is not None:
+        return (functools.partial(eng.system_com_traj, native, numbers),
+                lambda g, rows, **kw: eng.push_traj(g, native, numbers, rows, **kw))
+    block = traj.frame_block(numbers)
+    return (lambda rows, masses, **kw: eng.system_com_f32(block if rows is None else block[:, rows], masses, **kw),
+            lambda g, rows, **kw: eng.push_f32(g, block[:, rows], **kw))
+
+
+def _push_resident(eng, frames, g, rows, **kw):
+    """Group ``g`` out of the frames in HBM ``[T, n_total, 3]``."""
+    n_total = frames.shape[1]
+    plain = (not eng.has_grouping and kw.get("shift") is None and kw.get("unwrap_dims") is None and len(rows)
+             and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))))
+    if plain and frames.dtype == np.float64:
+        # float64 frames in HBM, a contiguous range of particles, nothing to prepare: the correlation kernels
+        # read them where they lie
+        eng.push_device(g, frames.ptr, n_total, int(rows[0]), len(rows), kw.get("zero_dims", 0))
+    elif plain and frames.dtype == np.float32 and eng.reads_f32:
+        # ... and so do float32 frames where the first pass widens them as it stages them
+        # (mdx_msd_push_device_f32: the 400 x R2 transforms; no float64 copy of the group)
+        eng.push_device_f32(g, frames.ptr, n_total, int(rows[0]), len(rows), kw.get("zero_dims", 0))
+    else:
+        eng.push_frames_device(g, frames, n_total, rows, **kw)
 
 
 class Onsager(SerialAnalysisBase):
@@ -387,104 +422,17 @@ class Onsager(SerialAnalysisBase):
                 streamed = self._stream_host_groups(eng, numbers, native, zero_mask, unwrap_dims)
                 resident = None if streamed else self._resident_frames(numbers, native)
                 mark("frames_to_hbm")
-                if resident is not None:
-                    n_total = resident.shape[1]
-
-                    def system_com(rows, masses, **kw):
-                        return eng.system_com_device(resident, n_total, rows, masses, **kw)
-
-                    def push(g, rows, **kw):
-                        plain = (not eng.has_grouping and kw.get("shift") is None
-                                 and kw.get("unwrap_dims") is None and len(rows)
-                                 and np.array_equal(rows, np.arange(rows[0], rows[0] + len(rows))))
-                        if plain and resident.dtype == np.float64:
-                            # float64 frames in HBM, a contiguous range of particles, nothing to prepare:
-                            # the correlation kernels read them where they lie
-                            eng.push_device(g, resident.ptr, n_total, int(rows[0]), len(rows),
-                                            kw.get("zero_dims", 0))
-                        elif plain and resident.dtype == np.float32 and eng.reads_f32:
-                            # ... and so do float32 frames where the first pass widens them as it stages them
-                            # (mdx_msd_push_device_f32: the 400 x R2 transforms; no float64 copy of the group)
-                            eng.push_device_f32(g, resident.ptr, n_total, int(rows[0]), len(rows),
-                                                kw.get("zero_dims", 0))
-                        else:
-                            eng.push_frames_device(g, resident, n_total, rows, **kw)
-                elif native is not None:
-                    def system_com(rows, masses, **kw):
-                        return eng.system_com_traj(native, numbers, rows, masses, **kw)
-
-                    def push(g, rows, **kw):
-                        eng.push_traj(g, native, numbers, rows, **kw)
-                else:
-                    # in-memory float32 frames: the same device stages, fed from host memory
-                    block = self._trajectory.frame_block(numbers)
-
-                    def system_com(rows, masses, **kw):
-                        return eng.system_com_f32(block if rows is None else block[:, rows], masses, **kw)
-
-                    def push(g, rows, **kw):
-                        eng.push_f32(g, block[:, rows], **kw)
-                def start_images(rows):
-                    # image flags the rows start from (molecules made whole in the first frame)
-                    # (the reference's first unwrap call moves a flag by sign(x - x_whole) only, reference
-                    # topology.py:366-376: a particle k >= 2 images away from its made-whole place starts at
-                    # +-1 like the host path's, not at k)
-                    if self._unwrap:
-                        eng.set_initial_images(None if self._images0 is None else
-                                               np.sign(self._images0 if rows is None else self._images0[rows]))
-
-                shift = None
-                if self._center:
-                    # system centre of mass per frame (reference :993-1014), every rank the same
-                    wrap_dims = self._dimensions if self._center_wrap else None
-                    if self._center_atom:
-                        start_images(None)
-                        shift = system_com(None, self.universe.atoms.masses,
-                                           unwrap_dims=unwrap_dims, wrap_dims=wrap_dims)
-                    elif wrap_dims is None or all(gr == "atoms" for gr in self._groupings):
-                        start_images(np.concatenate([g.indices for g in self._groups]))
-                        shift = system_com(np.concatenate([g.indices for g in self._groups]),
-                                           np.concatenate([g.masses for g in self._groups]),
-                                           unwrap_dims=unwrap_dims, wrap_dims=wrap_dims)
-                    else:
-                        # wrapped CENTRES of the molecules (reference :1004-1014: wrap(frame) acts on
-                        # the residue / segment centres): per group on the device, mass-weighted here
-                        from .structure import RadialDistributionFunction as _R
-                        num, mass = 0.0, 0.0
-                        for grp, gr in zip(self._groups, self._groupings):
-                            if gr == "atoms":
-                                eng.set_grouping(None, None)
-                                rows, m = grp.indices, np.asarray(grp.masses, dtype=float)
-                            else:
-                                rows, off, m = _R._selection(grp, gr)
-                                eng.set_grouping(off, m)
-                            start_images(rows)
-                            com = system_com(rows, m, unwrap_dims=unwrap_dims, wrap_dims=wrap_dims)
-                            num = num + com * m.sum()
-                            mass += m.sum()
-                        eng.set_grouping(None, None)
-                        shift = num / mass
-                from .structure import RadialDistributionFunction
-                for g, (grp, gr, (lo, hi)) in enumerate(zip(self._groups, self._groupings, self._own)):
-                    if hi <= lo or streamed:
-                        continue
-                    if gr == "atoms":
-                        eng.set_grouping(None, None)
-                        rows = grp.indices[lo:hi]
-                    else:
-                        # molecules lo .. hi of this rank: rows sorted molecule by molecule, the
-                        # float64 centres of the unwrapped particles are formed on the device
-                        idx, off, m = RadialDistributionFunction._selection(grp, gr)
-                        eng.set_grouping(off[lo:hi + 1] - off[lo], m[off[lo]:off[hi]])
-                        rows = idx[off[lo]:off[hi]]
-                    start_images(rows)
-                    push(g, rows, unwrap_dims=unwrap_dims, zero_dims=zero_mask, shift=shift)
+                if not streamed:
+                    system_com, push = _frame_route(eng, self._trajectory, numbers, native, resident)
+                    shift = self._system_com(eng, system_com, unwrap_dims) if self._center else None
+                    self._push_groups(eng, push, unwrap_dims, zero_mask, shift)
                 if resident is not None and getattr(resident, "base", None) is None:
                     _core.synchronize(self._device)
                     resident.free()
-            for g, own in enumerate(self._own_slices):
-                if own.stop > own.start and not self._from_file:
-                    eng.push(g, self._positions, own.start, own.stop - own.start, zero_mask)
+            else:
+                for g, own in enumerate(self._own_slices):
+                    if own.stop > own.start:
+                        eng.push(g, self._positions, own.start, own.stop - own.start, zero_mask)
             mark("prepare_and_push")
             cross = None
             if multi and getattr(self._comm, "device_collectives", False):
@@ -535,6 +483,59 @@ class Onsager(SerialAnalysisBase):
         self.results.msd_cross /= D
         self.results.msd_self /= D
         mark("cross_msds")
+
+    def _start_images(self, eng, rows):
+        """Image flags the rows start from (molecules made whole in the first frame).  (The reference's first
+        unwrap call moves a flag by sign(x - x_whole) only, reference topology.py:366-376: a particle k >= 2 images
+        away from its made-whole place starts at +-1 like the host path's, not at k.)"""
+        if self._unwrap:
+            eng.set_initial_images(None if self._images0 is None else
+                                   np.sign(self._images0 if rows is None else self._images0[rows]))
+
+    def _system_com(self, eng, system_com, unwrap_dims):
+        """System centre of mass per frame (reference :993-1014), every rank the same."""
+        wrap_dims = self._dimensions if self._center_wrap else None
+        if self._center_atom:
+            self._start_images(eng, None)
+            return system_com(None, self.universe.atoms.masses, unwrap_dims=unwrap_dims, wrap_dims=wrap_dims)
+        if wrap_dims is None or all(gr == "atoms" for gr in self._groupings):
+            rows = np.concatenate([g.indices for g in self._groups])
+            self._start_images(eng, rows)
+            return system_com(rows, np.concatenate([g.masses for g in self._groups]),
+                              unwrap_dims=unwrap_dims, wrap_dims=wrap_dims)
+        # wrapped CENTRES of the molecules (reference :1004-1014: wrap(frame) acts on the residue / segment
+        # centres): per group on the device, mass-weighted here
+        num, mass = 0.0, 0.0
+        for grp, gr in zip(self._groups, self._groupings):
+            if gr == "atoms":
+                eng.set_grouping(None, None)
+                rows, m = grp.indices, np.asarray(grp.masses, dtype=float)
+            else:
+                rows, off, m = molecule_rows(grp, gr)
+                eng.set_grouping(off, m)
+            self._start_images(eng, rows)
+            com = system_com(rows, m, unwrap_dims=unwrap_dims, wrap_dims=wrap_dims)
+            num = num + com * m.sum()
+            mass += m.sum()
+        eng.set_grouping(None, None)
+        return num / mass
+
+    def _push_groups(self, eng, push, unwrap_dims, zero_mask, shift):
+        """This rank's particles of every group into the engine."""
+        for g, (grp, gr, (lo, hi)) in enumerate(zip(self._groups, self._groupings, self._own)):
+            if hi <= lo:
+                continue
+            if gr == "atoms":
+                eng.set_grouping(None, None)
+                rows = grp.indices[lo:hi]
+            else:
+                # molecules lo .. hi of this rank: rows sorted molecule by molecule, the float64 centres of
+                # the unwrapped particles are formed on the device
+                idx, off, m = molecule_rows(grp, gr)
+                eng.set_grouping(off[lo:hi + 1] - off[lo], m[off[lo]:off[hi]])
+                rows = idx[off[lo]:off[hi]]
+            self._start_images(eng, rows)
+            push(g, rows, unwrap_dims=unwrap_dims, zero_dims=zero_mask, shift=shift)
 
     def _stream_host_groups(self, eng, numbers, native, zero_mask, unwrap_dims) -> bool:
         """
@@ -627,34 +628,23 @@ class Onsager(SerialAnalysisBase):
             return out
         return _core.DeviceArray.upload(traj.frame_block(numbers), dev)
 
-    # in-memory trajectories, plain atom groups: copy the positions in one vectorised step
+    # batched run (the frame feed of base.py): with the FFT engine nothing is staged on the host — unwrapping,
+    # residue / segment centres of mass and the removal of the system centre of mass happen on the device
+    # (_conclude); without it, plain atom groups are copied out of one host block in a vectorised step
     def run(self, start=None, stop=None, step=None, frames=None, n_jobs: int = 1, verbose=None,
             **kwargs):
         traj = self._trajectory
-        atoms_only = all(g == "atoms" for g in self._groupings)
-        # trajectory files: nothing is staged on the host — unwrapping, residue / segment centres
-        # of mass and the removal of the system centre of mass (of atoms, of group particles, or of
-        # the wrapped molecule centres) happen on the device
-        native = getattr(traj, "native", None) is not None
-        # ... and so do in-memory frames (what an MDAnalysis memory reader holds) and frames resident in HBM
-        batched = hasattr(traj, "frame_block") or hasattr(traj, "device_block")
-        self._from_file = bool(self._fft and (native or batched))
-        fast = self._from_file or (hasattr(traj, "frame_block") and atoms_only
-                                   and not (self._unwrap or self._center))
-        if not fast:
+        blocks = has_frame_blocks(traj)
+        self._from_file = bool(self._fft and blocks)
+        if not (self._from_file or (blocks and all(g == "atoms" for g in self._groupings)
+                                    and not (self._unwrap or self._center))):
             return super().run(start=start, stop=stop, step=step, frames=frames, n_jobs=n_jobs,
                                verbose=verbose, **kwargs)
-        self._setup_frames(traj, start=start, stop=stop, step=step, frames=frames)
-        self._prepare()
-        numbers = self._frame_numbers()
-        self.frames[:] = numbers
-        self.times[:] = numbers * traj.dt
-        if self._from_file:
-            self._conclude()
-            return self
-        block = traj.frame_block(numbers)
-        for g, own, (lo, hi) in zip(self._groups, self._own_slices, self._own):
-            self._positions[:, own] = block[:, g.indices[lo:hi]]
+        numbers = self._batched_frames(start, stop, step, frames, shard=False)
+        if not self._from_file:
+            block = traj.frame_block(numbers)
+            for g, own, (lo, hi) in zip(self._groups, self._own_slices, self._own):
+                self._positions[:, own] = block[:, g.indices[lo:hi]]
         self._conclude()
         return self
 
