@@ -449,6 +449,48 @@ int mdx_msd_system_com_device(mdx_msd_t h, const void *d_pos, int elem_bytes, in
  * weighted with its molecule's mass: Onsager(center=True, center_atom=False, center_wrap=True)
  * with residue / segment groupings (transport.py:1004-1014). */
 
+/* ---- density profiles: per-axis histograms of positions (reference analysis/profile.py DensityProfile) -----------
+ * Counts of points along the requested axes, per group, equal to numpy.histogram(x, n_bins, (0, L)) count for count
+ * after the reference's `wrap` (x < 0 or x > L: x -= floor(x / L) * L), all in float64; coordinates that are not
+ * finite are not counted.  Rows arrive in the order of the concatenated groups: group g holds points
+ * [group_offsets[g], group_offsets[g+1]), group_offsets[0] == 0.  axes[n_axes] (distinct, 0..2) and n_bins[n_axes]
+ * name the profiles; dims[3] are the fixed box lengths.  per_frame == 0: one total per (group, bin) over all
+ * frames; else one row per frame.  Argument errors return MDX_ERR_INVALID_VALUE before any device is touched. */
+typedef struct mdx_prof *mdx_prof_t;
+int mdx_prof_create(mdx_prof_t *out, int dev, int n_groups, const int64_t *group_offsets, int n_axes,
+                    const int32_t *axes, const int64_t *n_bins, const double *dims, int per_frame);
+int mdx_prof_destroy(mdx_prof_t h);
+/* Zeroes the counts, forgets the frames seen and the unwrap state of the recentring. */
+int mdx_prof_reset(mdx_prof_t h);
+/* Incoming rows become particles sorted molecule by molecule (CSR offsets[n_molecules + 1], masses per row) and
+ * the points are the float64 mass-weighted centres, summed in row order and divided once; n_molecules must equal
+ * the number of points of the groups (<= 0 removes the grouping).  Only before the first frame. */
+int mdx_prof_set_grouping(mdx_prof_t h, int64_t n_molecules, const int64_t *offsets, const double *masses);
+/* Recentring (profile.py:782-801): per frame, over all points, the reference's global unwrap (a displacement since
+ * the previous frame of |d| >= dims / 2 changes the image count by -sign(d)), then every point is shifted by
+ * scom - target, scom the centre of the unwrapped points of `group` weighted with masses[points of the group]; a
+ * NaN component of target leaves that axis alone.  Frames must then be fed in analysis order; the result does not
+ * depend on how they are split into calls.  group < 0 switches it off.  Only before the first frame. */
+int mdx_prof_set_recenter(mdx_prof_t h, int group, const double *masses, const double *target);
+/* Host float32 [n_frames][n][3] through the pinned ring. */
+int mdx_prof_accumulate(mdx_prof_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3], read where they lie; index: host int32[n_index] rows of a
+ * frame in incoming order, or NULL for all n_atoms rows.  Asynchronous (mdx_prof_synchronize). */
+int mdx_prof_accumulate_device(mdx_prof_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                               const int32_t *index, int64_t n_index);
+int mdx_prof_accumulate_traj(mdx_prof_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                             const int32_t *index, int64_t n_index);
+int mdx_prof_synchronize(mdx_prof_t h);
+/* out: int64 [n_groups][n_bins of the slot], or [n_groups][frames seen][n_bins] for per_frame engines. */
+int mdx_prof_counts(mdx_prof_t h, int axis_slot, int64_t *out);
+/* replicas: LDS copies of the counters the kernels use (8, 4, 2, 1), 0 = they bin straight into global memory. */
+int mdx_prof_stats(mdx_prof_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int *replicas);
+int mdx_prof_enable_timing(mdx_prof_t h, int on);
+/* Caps the LDS copies of the counters at `replicas` (8, 4, 2, 1; fewer where they do not fit), 0 makes the kernels
+ * bin straight into global memory, -1 restores the engine's own choice.  The counts do not depend on it; it exists
+ * for measurements and tests.  Only before the first frame. */
+int mdx_prof_set_replicas(mdx_prof_t h, int replicas);
+
 #ifdef __cplusplus
 }
 #endif

@@ -484,6 +484,110 @@ class IsfEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": fr.value}
 
 
+class ProfileEngine(_Engine):
+    """``mdx_prof_*``: per-axis, per-group position histograms with ``numpy.histogram``'s counts."""
+
+    _destroy = "mdx_prof_destroy"
+
+    def __init__(self, group_sizes, axes, n_bins, dims, *, per_frame=False, dev=0, timing=False, replicas=None):
+        self.offsets = np.concatenate(([0], np.cumsum(group_sizes))).astype(np.int64)
+        self.axes = np.ascontiguousarray(np.atleast_1d(axes), dtype=np.int32)
+        self.n_bins = np.ascontiguousarray(np.broadcast_to(n_bins, self.axes.shape), dtype=np.int64)
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.n_groups = len(self.offsets) - 1
+        self.per_frame = bool(per_frame)
+        h = c_void_p()
+        check(lib().mdx_prof_create(byref(h), dev, self.n_groups, _ptr(self.offsets), len(self.axes),
+                                    _ptr(self.axes), _ptr(self.n_bins), _ptr(self.dims), int(self.per_frame)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_prof_enable_timing(h, 1))
+        if replicas is not None:
+            self.set_replicas(replicas)
+
+    def set_replicas(self, replicas):
+        """Caps the LDS copies of the counters (8, 4, 2, 1), 0: global atomics, -1: the engine's own choice.
+        For measurements and tests: the counts do not depend on it."""
+        check(lib().mdx_prof_set_replicas(self.handle, int(replicas)))
+
+    def set_grouping(self, offsets, masses):
+        """Incoming rows become particles of molecules ``[offsets[m], offsets[m+1])`` — one per point of the
+        groups — whose float64 centres of mass are binned; ``offsets=None`` removes the grouping."""
+        if offsets is None:
+            check(lib().mdx_prof_set_grouping(self.handle, 0, None, None))
+            return
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if len(m) != o[-1]:
+            raise ValueError("masses must hold one entry per particle of the grouping.")
+        check(lib().mdx_prof_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+
+    def set_recenter(self, group, masses=None, target=None):
+        """Every frame is shifted so that the mass-weighted centre of the globally unwrapped points of
+        ``group`` sits at ``target`` (a NaN component leaves that axis alone); ``group=None`` switches it
+        off.  Frames must then be fed in analysis order."""
+        if group is None:
+            check(lib().mdx_prof_set_recenter(self.handle, -1, None, None))
+            return
+        group = int(group)
+        if not 0 <= group < self.n_groups:
+            raise ValueError("Invalid group index.")
+        n = int(self.offsets[group + 1] - self.offsets[group])
+        m = np.ones(n) if masses is None else np.ascontiguousarray(masses, dtype=np.float64)
+        if len(m) != n:
+            raise ValueError("masses must hold one entry per point of the group.")
+        t = np.ascontiguousarray(self.dims / 2 if target is None else target, dtype=np.float64)
+        if t.shape != (3,):
+            raise ValueError("target must hold three coordinates.")
+        check(lib().mdx_prof_set_recenter(self.handle, group, _ptr(m), _ptr(t)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows in concatenated-group order."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_prof_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
+        the engine's stream: ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_prof_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                               0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_prof_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                             0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_prof_synchronize(self.handle))
+
+    def counts(self):
+        """One int64 array per axis: ``[G, n_bins]``, or ``[G, frames seen, n_bins]`` for per-frame engines."""
+        frames = self.stats()["frames"]
+        out = []
+        for slot, nb in enumerate(self.n_bins):
+            shape = (self.n_groups, frames, int(nb)) if self.per_frame else (self.n_groups, int(nb))
+            c = np.zeros(shape, dtype=np.int64)
+            check(lib().mdx_prof_counts(self.handle, slot, _ptr(c)))
+            out.append(c)
+        return out
+
+    def reset(self):
+        check(lib().mdx_prof_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames, rep = c_int64(), c_double(), c_int64(), c_int()
+        check(lib().mdx_prof_stats(self.handle, byref(n), byref(ms), byref(frames), byref(rep)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "replicas": rep.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

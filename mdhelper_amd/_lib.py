@@ -146,6 +146,20 @@ _SIGNATURES = {
                                            c_int, _vp]),
     "mdx_msd_system_com_device": (c_int, [_vp, _vp, c_int, c_int64, c_int64, _vp, c_int64, _vp, c_int, _vp,
                                           c_int, _vp]),
+    # density profiles
+    "mdx_prof_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int, _vp, _vp, _vp, c_int]),
+    "mdx_prof_destroy": (c_int, [_vp]),
+    "mdx_prof_reset": (c_int, [_vp]),
+    "mdx_prof_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
+    "mdx_prof_set_recenter": (c_int, [_vp, c_int, _vp, _vp]),
+    "mdx_prof_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_prof_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_prof_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_prof_synchronize": (c_int, [_vp]),
+    "mdx_prof_counts": (c_int, [_vp, c_int, _vp]),
+    "mdx_prof_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int)]),
+    "mdx_prof_enable_timing": (c_int, [_vp, c_int]),
+    "mdx_prof_set_replicas": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)
