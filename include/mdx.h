@@ -491,6 +491,49 @@ int mdx_prof_enable_timing(mdx_prof_t h, int on);
  * for measurements and tests.  Only before the first frame. */
 int mdx_prof_set_replicas(mdx_prof_t h, int replicas);
 
+/* ---- radii of gyration of polymer chains (reference analysis/polymer.py Gyradius, algorithm/molecule.py
+ * radius_of_gyration) ------------------------------------------------------------------------------------------------
+ * Rows arrive in the order of the concatenated groups: group g holds n_chains[g] * n_monomers[g] consecutive points,
+ * a chain is n_monomers[g] consecutive points; masses float64, one per point in that order.  Per frame and chain, in
+ * float64 with separate multiply and add (float32 coordinates are widened before any arithmetic):
+ *     c = sum m r / sum m;   S_d = sum m (r_d - c_d)^2 over the centred coordinates (two passes; the one-pass form
+ *     sum m r^2 - (sum m r)^2 / sum m is not used: it cancels for chains far from the origin);
+ *     Rg = sqrt((S_x + S_y + S_z) / sum m);   Rg_x = sqrt((S_y + S_z) / sum m), Rg_y = sqrt((S_x + S_z) / sum m),
+ *     Rg_z = sqrt((S_x + S_y) / sum m)   (the radii "around the axes" of molecule.py:529-544);
+ * the value of a group is the mean over its chains.  Every sum, across lanes and across chains, has a fixed order and
+ * no floating-point atomics are used, so the rows are bit-identical across the three input routes and across any
+ * split of the frames into calls.  Argument errors return MDX_ERR_INVALID_VALUE before any device is touched. */
+typedef struct mdx_gyr *mdx_gyr_t;
+int mdx_gyr_create(mdx_gyr_t *out, int dev, int n_groups, const int64_t *n_chains, const int64_t *n_monomers,
+                   const double *masses);
+int mdx_gyr_destroy(mdx_gyr_t h);
+/* Forgets the frames seen and the unwrap state (the next frame is again compared with `start`). */
+int mdx_gyr_reset(mdx_gyr_t h);
+/* Incoming rows become particles sorted monomer by monomer (CSR offsets[n_molecules + 1], masses per row) and the
+ * points are the float64 mass-weighted centres, summed in row order and divided once; n_molecules must equal the
+ * number of points of the groups (<= 0 removes the grouping).  Only before the first frame. */
+int mdx_gyr_set_grouping(mdx_gyr_t h, int64_t n_molecules, const int64_t *offsets, const double *masses);
+/* The reference's global unwrap (algorithm/topology.py `unwrap`) per frame and point coordinate: d = x - x_prev;
+ * |d| >= dims / 2 moves the image count by -sign(d); x_prev becomes the raw x; the point used is x + image * dims, the
+ * shift applied in float64.  Before the first frame x_prev = start (float64 [n_points][3]: the points of the first
+ * analysed frame with every chain made whole) and the image counts are 0, so the first frame recovers the make-whole
+ * images itself.  Frames must then be fed in analysis order; the result does not depend on how they are split into
+ * calls.  dims == NULL switches it off.  Only before the first frame. */
+int mdx_gyr_set_unwrap(mdx_gyr_t h, const double *dims, const double *start);
+/* Host float32 [n_frames][n][3] through the pinned ring. */
+int mdx_gyr_accumulate(mdx_gyr_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3], read where they lie; index: host int32[n_index] rows of a
+ * frame in incoming order, or NULL for all n_atoms rows.  Asynchronous (mdx_gyr_synchronize). */
+int mdx_gyr_accumulate_device(mdx_gyr_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_gyr_accumulate_traj(mdx_gyr_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_gyr_synchronize(mdx_gyr_t h);
+/* out: float64 [n_groups][frames seen][4]: the mean over the group's chains of Rg, Rg_x, Rg_y, Rg_z. */
+int mdx_gyr_result(mdx_gyr_t h, double *out);
+int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
+int mdx_gyr_enable_timing(mdx_gyr_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -588,6 +588,95 @@ class ProfileEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "replicas": rep.value}
 
 
+class GyrationEngine(_Engine):
+    """``mdx_gyr_*``: per frame and group the mean over the chains of ``Rg, Rg_x, Rg_y, Rg_z``."""
+
+    _destroy = "mdx_gyr_destroy"
+
+    def __init__(self, n_chains, n_monomers, masses, *, dev=0, timing=False):
+        self.n_chains = np.ascontiguousarray(np.atleast_1d(n_chains), dtype=np.int64)
+        self.n_monomers = np.ascontiguousarray(np.atleast_1d(n_monomers), dtype=np.int64)
+        if self.n_chains.ndim != 1 or self.n_chains.shape != self.n_monomers.shape or len(self.n_chains) == 0:
+            raise ValueError("n_chains and n_monomers must hold one entry per group.")
+        self.n_groups = len(self.n_chains)
+        self.n_points = int((self.n_chains * self.n_monomers).sum())
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if m.shape != (self.n_points,):
+            raise ValueError("masses must hold one entry per point of the groups.")
+        h = c_void_p()
+        check(lib().mdx_gyr_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers),
+                                   _ptr(m)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_gyr_enable_timing(h, 1))
+
+    def set_grouping(self, offsets, masses):
+        """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
+        groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
+        if offsets is None:
+            check(lib().mdx_gyr_set_grouping(self.handle, 0, None, None))
+            return
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if len(m) != o[-1]:
+            raise ValueError("masses must hold one entry per particle of the grouping.")
+        check(lib().mdx_gyr_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+
+    def set_unwrap(self, dims, start=None):
+        """The reference's global unwrap from frame to frame, starting from the points ``start``
+        (float64 ``[n_points, 3]``, every chain whole); ``dims=None`` switches it off.  Frames must then be
+        fed in analysis order."""
+        if dims is None:
+            check(lib().mdx_gyr_set_unwrap(self.handle, None, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        if s is None or s.shape != (self.n_points, 3):
+            raise ValueError("start must hold three coordinates per point of the groups.")
+        check(lib().mdx_gyr_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows in concatenated-group order."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_gyr_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
+        the engine's stream: ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_gyr_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                              0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_gyr_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                            0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_gyr_synchronize(self.handle))
+
+    def result(self):
+        """float64 ``[G, frames seen, 4]``: ``Rg, Rg_x, Rg_y, Rg_z`` averaged over the chains of each group."""
+        out = np.zeros((self.n_groups, self.stats()["frames"], 4), dtype=np.float64)
+        check(lib().mdx_gyr_result(self.handle, _ptr(out)))
+        return out
+
+    def reset(self):
+        check(lib().mdx_gyr_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames = c_int64(), c_double(), c_int64()
+        check(lib().mdx_gyr_stats(self.handle, byref(n), byref(ms), byref(frames)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

@@ -160,6 +160,19 @@ _SIGNATURES = {
     "mdx_prof_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int)]),
     "mdx_prof_enable_timing": (c_int, [_vp, c_int]),
     "mdx_prof_set_replicas": (c_int, [_vp, c_int]),
+    # radii of gyration
+    "mdx_gyr_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp, _vp]),
+    "mdx_gyr_destroy": (c_int, [_vp]),
+    "mdx_gyr_reset": (c_int, [_vp]),
+    "mdx_gyr_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
+    "mdx_gyr_set_unwrap": (c_int, [_vp, _vp, _vp]),
+    "mdx_gyr_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_gyr_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_gyr_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_gyr_synchronize": (c_int, [_vp]),
+    "mdx_gyr_result": (c_int, [_vp, _vp]),
+    "mdx_gyr_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
+    "mdx_gyr_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -6,8 +6,8 @@ single-chain structure factor on the reciprocal grid.
 
 Mirrors reference ``src/mdhelper/analysis/polymer.py``: ``correlation_fft`` /
 ``correlation_shift`` aliases (:30-57), ``calculate_relaxation_time`` (:59-108),
-``_PolymerAnalysisBase.__init__`` (:175-237) and ``EndToEndVector`` (:510-803) keep their
-names, arguments, defaults, result attributes and error behaviour.
+``_PolymerAnalysisBase.__init__`` (:175-237), ``Gyradius`` (:239-508) and ``EndToEndVector``
+(:510-803) keep their names, arguments, defaults, result attributes and error behaviour.
 
 Where the work goes: the reference stores ``e2e[T, N_chains, 3]`` frame by frame and calls
 ``correlation_fft(..., average=True, vector=True)`` per group (:765-781), which transforms
@@ -22,6 +22,10 @@ With ``comm=`` the chains shard across ranks (one all-reduce of the accumulators
 ``SingleChainStructureFactor`` (reference :805-1130) runs on the structure-factor engine in
 single-chain mode (``mdx_sq_set_chains``): per frame and chain the device forms
 ``rho_c(q) = sum_{j in c} exp(i q.r_j)`` and adds ``|rho_c|^2``; frames shard across ranks.
+
+``Gyradius`` runs on the gyration engine (``mdx_gyr_*``): per frame the device forms the monomer
+centres of mass, follows the points across the boundaries (``unwrap``), and computes every
+chain's centre of mass and mass-weighted second moments in float64; frames shard across ranks.
 """
 
 from __future__ import annotations
@@ -37,8 +41,8 @@ from ..algorithm import correlation
 from ..algorithm.topology import unwrap_edge
 from ..algorithm.unit import strip_unit
 from ..comm import shard_range
-from .base import (DynamicAnalysisBase, FrameBatcher, accumulate_blocks, block_frames, frame_blocks,
-                   has_frame_blocks)
+from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, accumulate_blocks, all_particles,
+                   block_frames, block_source, frame_blocks, has_frame_blocks)
 
 _GROUPINGS = {"atoms", "residues"}
 
@@ -133,6 +137,205 @@ class _PolymerAnalysisBase(DynamicAnalysisBase):
 
         self._unwrap = unwrap
         self._verbose = verbose
+
+
+class Gyradius(_PolymerAnalysisBase):
+    r"""
+    Radius of gyration of polymer chains (reference :239-508),
+
+    .. math:: R_\mathrm g=\sqrt{\frac{\sum_i m_i\|\mathbf r_i-\mathbf R_\mathrm{com}\|^2}{\sum_i m_i}}
+
+    per frame, averaged over the chains of each group; with ``components=True`` the radii around the
+    coordinate axes instead (:math:`R_{\mathrm g,x}` from the :math:`y` and :math:`z` components, ...).
+
+    Parameters (reference :337-343)
+    ----------
+    groups, groupings, n_chains, n_monomers : see ``_PolymerAnalysisBase``; a group holds
+        ``n_chains * n_monomers`` monomers, chain after chain
+    components : bool, keyword-only — the three radii around the axes instead of :math:`R_\mathrm g`
+    unwrap : bool, keyword-only — follow the monomers across the periodic boundaries from frame to
+        frame, starting from chains made whole in the first analysed frame
+    parallel : bool, keyword-only — accepted; the serial result layout is returned
+    comm, device : keyword-only (extension) — frames shard across ranks, one all-reduce at the end
+
+    Results: ``results.gyradii`` ``[N_g, N_t]`` (``[N_g, N_t, 3]`` with ``components=True``, Å),
+    ``results.units``.
+
+    Where this differs from the reference:
+
+    * A monomer's mass is the sum of its atoms' masses.  The reference reshapes the *atom* masses to
+      ``(n_chains, n_monomers)``, which only runs with one atom per monomer; there both agree.
+    * ``"residues"`` read from the topology: one chain per segment and ``n_monomers`` = residues per
+      segment, as in ``SingleChainStructureFactor``.  The reference uses atoms per chain.
+    * Image shifts are applied in float64 (the reference adds ``images * dimensions`` to the float32
+      positions, topology.py:376).
+    * ``parallel`` is accepted and returns the serial layout ``[N_g, N_t(, 3)]``.
+    * A scalar ``n_monomers`` gives one entry per group (the reference sizes that array by
+      ``n_monomers``, :226).
+    * ``unwrap=True`` with more than one rank raises ``ValueError``: the image counts run from frame to
+      frame, so the frames cannot shard.  ``unwrap=True`` without box dimensions, and groups whose size
+      does not match ``n_chains * n_monomers``, raise ``ValueError`` at construction.
+    * The chains of the first analysed frame are made whole along bonds between consecutive monomers
+      (``unwrap_edge``), for ``"residues"`` on the monomers' centres of mass; the array universes carry
+      no fragments for ``make_whole`` (:380-383).
+    * There is no CPU fallback: without a HIP device ``run()`` raises ``RuntimeError``.
+    """
+
+    def __init__(self, groups, groupings: Union[str, tuple] = "atoms", n_chains=None,
+                 n_monomers=None, *, components: bool = False, unwrap: bool = False,
+                 parallel: bool = False, verbose: bool = True, **kwargs) -> None:
+        super().__init__(groups, groupings, n_chains, n_monomers, unwrap=unwrap, parallel=parallel,
+                         verbose=verbose, **kwargs)
+        if self._internal:
+            for i, (g, gr) in enumerate(zip(self._groups, self._groupings)):
+                seg = np.asarray(g.segindices)
+                if gr == "residues":
+                    _, first = np.unique(np.asarray(g.resindices), return_index=True)
+                    _, per_seg = np.unique(seg[first], return_counts=True)      # residues per segment
+                    what = "residues"
+                else:
+                    _, per_seg = np.unique(seg, return_counts=True)
+                    what = "atoms"
+                if np.any(per_seg != per_seg[0]):
+                    raise ValueError(f"All segments of group {i} must hold the same number of {what}.")
+                self._n_monomers[i] = per_seg[0]
+        for i, (g, gr, M, N_p) in enumerate(zip(self._groups, self._groupings, self._n_chains,
+                                                self._n_monomers)):
+            N = int(M) * int(N_p)
+            if gr == "atoms" or self._internal:
+                n_have = g.n_atoms if gr == "atoms" else len(np.unique(np.asarray(g.resindices)))
+                bad = N <= 0 or n_have != N
+            else:
+                n_have = g.n_atoms
+                bad = N <= 0 or n_have == 0 or n_have % N != 0
+            if bad:
+                what = "atoms" if gr == "atoms" or not self._internal else "residues"
+                raise ValueError(f"Group {i} holds {n_have} {what}, which do not form n_chains * "
+                                 f"n_monomers = {M} * {N_p} = {N} monomers.")
+        if unwrap:
+            if self._comm.world_size > 1:
+                raise ValueError("unwrap cannot be combined with more than one rank: the image counts "
+                                 "run from frame to frame, so the frames cannot shard.  Run it on one "
+                                 "rank.")
+            if self._dimensions is None:
+                raise ValueError("No system dimensions found: unwrapping is not possible.")
+
+        self._Ns = np.fromiter((M * N_p for M, N_p in zip(self._n_chains, self._n_monomers)),
+                               dtype=int, count=self._n_groups)
+        self._N = self._Ns.sum()
+        self._slices = []
+        index = 0
+        for N in self._Ns:
+            self._slices.append(slice(index, index + N))
+            index += N
+        self._components = components
+
+    # ------------------------------------------------------------------ points
+
+    def _selection(self, g, gr, N):
+        """(particle indices monomer by monomer, monomer offsets or None, particle masses, monomer
+        masses) of a group of ``N`` monomers."""
+        idx = np.asarray(g.indices)
+        masses = np.asarray(g.masses, dtype=np.float64)
+        if gr == "atoms":
+            return idx, None, masses, masses
+        if not self._internal:
+            # a monomer is n_atoms / N consecutive atoms
+            offsets = np.arange(N + 1, dtype=np.int64) * (g.n_atoms // N)
+        else:
+            # residues of the topology, monomer by monomer; a chain is a segment
+            _, inverse = np.unique(np.asarray(g.resindices), return_inverse=True)
+            order = np.argsort(inverse, kind="stable")
+            offsets = np.concatenate(([0], np.cumsum(np.bincount(inverse)))).astype(np.int64)
+            n_chains = len(np.unique(np.asarray(g.segindices)))
+            seg = np.asarray(g.segindices)[order][offsets[:-1]].reshape(n_chains, -1)
+            if np.any(seg != seg[:, :1]) or len(np.unique(seg[:, 0])) != n_chains:
+                raise ValueError("The residues of every segment must be consecutive.")
+            idx, masses = idx[order], masses[order]
+        return idx, offsets, masses, np.add.reduceat(masses, offsets[:-1])
+
+    def _start(self, sels):
+        """float64[N, 3]: the points of the current frame with every chain made whole."""
+        pos = np.asarray(self.universe.trajectory.ts.positions, dtype=float)
+        start = np.empty((self._N, 3))
+        for (idx, off, m, pm), s, M, N_p in zip(sels, self._slices, self._n_chains, self._n_monomers):
+            points = pos[idx]
+            if off is not None:
+                points = np.add.reduceat(points * m[:, None], off[:-1], axis=0) / pm[:, None]
+            bonds = (np.arange(M)[:, None] * N_p + np.arange(N_p - 1)[None, :]).ravel()
+            start[s] = unwrap_edge(positions=points, bonds=np.stack((bonds, bonds + 1), axis=1),
+                                   dimensions=self._dimensions, masses=pm)
+        return start
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        shape = [self._n_groups, self.n_frames]
+        if self._components:
+            shape.append(3)
+        self.results.gyradii = np.empty(shape)
+        self.results.units = {"results.gyradii": "angstrom"}
+
+        # rows of every frame in concatenated-group order, sorted monomer by monomer; the monomers'
+        # centres of mass are formed on the device (plain-atom groups: monomers of one particle)
+        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
+        self._index = np.concatenate([sel[0] for sel in sels])
+        self._engine = _core.GyrationEngine(self._n_chains, self._n_monomers,
+                                            np.concatenate([sel[3] for sel in sels]), dev=self._device)
+        if any(sel[1] is not None for sel in sels):
+            sizes = [np.ones(len(idx), dtype=np.int64) if off is None else np.diff(off)
+                     for idx, off, _, _ in sels]
+            self._engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
+                                      np.concatenate([sel[2] for sel in sels]))
+        if self._unwrap:
+            st = self._sliced_trajectory
+            self.universe.trajectory[st.frames[0] if hasattr(st, "frames") else (self.start or 0)]
+            self._engine.set_unwrap(self._dimensions, self._start(sels))
+        # frames shard across ranks (unwrap, which makes them sequential, runs on one rank)
+        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
+        self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
+                                   with_box=False)
+
+    def _single_frame(self) -> None:
+        lo, hi = self._frames_mine
+        if not lo <= self._frame_index < hi:
+            return
+        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
+
+    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory
+    # file, from float32 frames in HBM (read where they lie) or from host memory
+    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
+        traj = self._trajectory
+        if not has_frame_blocks(traj):
+            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
+                               **kwargs)
+        mine = self._batched_frames(start, stop, step, frames, shard=True)
+        index = self._index
+        whole = all_particles(index, traj.n_atoms)
+        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
+                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
+        for sel in frame_blocks(mine, size):
+            route, src = block_source(traj, sel, True)
+            if route == "file":
+                self._engine.accumulate_traj(src, sel, None if whole else index)
+            elif route == "hbm":
+                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
+            else:
+                self._engine.accumulate(src if whole else src[:, index])
+        self._conclude()
+        return self
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        radii = self._engine.result()                       # [N_g, frames of this rank, 4]
+        self._engine.close()
+        radii = radii[..., 1:] if self._components else radii[..., 0]
+        if self._comm.world_size > 1:                       # this rank's rows inside the full, zero-filled array
+            lo, hi = self._frames_mine
+            full = np.zeros(self.results.gyradii.shape)
+            full[:, lo:hi] = radii
+            radii = np.asarray(self._comm.allreduce(full, op="sum"))
+        self.results.gyradii = radii
 
 
 class EndToEndVector(_PolymerAnalysisBase):

@@ -15,6 +15,8 @@
 
 #include <cstdint>
 
+#include "mdx_points_device.hpp"
+
 namespace mdx_prof_dev {
 
 constexpr int PROF_THREADS = 256;
@@ -63,11 +65,6 @@ __device__ __forceinline__ int prof_group(const int *offs, int n_groups, int p)
             hi = mid;
     }
     return lo;
-}
-
-template <typename T> __device__ __forceinline__ T prof_pick(int k, T a, T b, T c)
-{
-    return k == 0 ? a : k == 1 ? b : c;
 }
 
 // Counters of one block: uint32 in LDS, REPLICAS interleaved copies of every slot (a lane adds to copy
@@ -230,61 +227,6 @@ __global__ __launch_bounds__(PROF_THREADS) void prof_hist_points_kernel(
         }
     }
     prof_block_flush<CT, USE_LDS>(prof_lds, plan, out);
-}
-
-// out[frame][m][k] = sum_a m_a x_a / M_m over the rows a of molecule m, in row order, float64 throughout:
-// molecule_com_kernel (mdx_molecules.hpp) without its cast to float32 — the reference keeps these centres in a
-// float64 array (profile.py:778-780).
-__global__ __launch_bounds__(256) void prof_com_f64_kernel(const float *__restrict__ pos, int64_t src_rows,
-                                                           const int *__restrict__ index,
-                                                           const int64_t *__restrict__ offsets,
-                                                           const double *__restrict__ masses,
-                                                           const double *__restrict__ total_mass,
-                                                           int64_t n_molecules, double *__restrict__ out)
-{
-    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;   // (molecule, k)
-    const int64_t frame = blockIdx.y;
-    if (i >= n_molecules * 3)
-        return;
-    const int64_t m = i / 3;
-    const int k = int(i - 3 * m);
-    const float *p = pos + frame * src_rows * 3 + k;
-    double acc = 0.0;
-    for (int64_t a = offsets[m]; a < offsets[m + 1]; ++a)
-        acc = __dadd_rn(acc, __dmul_rn(masses[a], (double)p[3 * (index ? int64_t(index[a]) : a)]));
-    out[(frame * n_molecules + m) * 3 + k] = __ddiv_rn(acc, total_mass[m]);
-}
-
-// Global unwrap (topology.py `unwrap`), a scan along the frames of the call per coordinate: a displacement since
-// the previous analysed frame of |d| >= L / 2 moves the image count by -sign(d).  prev / image carry the state from
-// call to call; `first`: this is the first analysed frame, whose displacement is zero.
-template <typename SRC>
-__global__ __launch_bounds__(256) void prof_unwrap_scan_kernel(const SRC *__restrict__ pos, int64_t src_rows,
-                                                               const int *__restrict__ index, int n_points,
-                                                               int n_frames, double hx, double hy, double hz,
-                                                               int first, double *__restrict__ prev,
-                                                               int *__restrict__ image, int *__restrict__ images)
-{
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= 3 * n_points)
-        return;
-    const int p = c / 3, k = c - 3 * p;
-    const int64_t r = index ? index[p] : p;
-    const double half = prof_pick(k, hx, hy, hz);
-    double old = first ? 0.0 : prev[c];
-    int im = first ? 0 : image[c];
-    for (int f = 0; f < n_frames; ++f) {
-        const double x = (double)pos[(int64_t(f) * src_rows + r) * 3 + k];
-        if (!(first && f == 0)) {
-            const double d = __dsub_rn(x, old);
-            if (fabs(d) >= half)
-                im -= (d > 0.0) - (d < 0.0);
-        }
-        old = x;
-        images[int64_t(f) * 3 * n_points + c] = im;
-    }
-    prev[c] = old;
-    image[c] = im;
 }
 
 // shift[frame][k] = scom_k - target_k (0 where target_k is NaN), scom the mass-weighted centre of the unwrapped
