@@ -534,6 +534,45 @@ int mdx_gyr_result(mdx_gyr_t h, double *out);
 int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_gyr_enable_timing(mdx_gyr_t h, int on);
 
+/* ---- instantaneous dipole moments (reference analysis/electrostatics.py DipoleMoment) ------------------------------
+ * Rows arrive in the order of the concatenated groups: group g holds n_points[g] consecutive points; charges float64,
+ * one per point in that order, finite.  Per frame, group and component, in float64 with separate multiply and add
+ * (float32 coordinates are widened before any arithmetic):
+ *     M_gd = sum over the group's points of q_i * (r_id + image_id * L_d)          (image = 0 without unwrap).
+ * Every sum has a fixed order that depends on the group sizes alone (csrc/mdx_dipole_device.hpp: tiles of points that
+ * never span two groups, added in tile order) and no floating-point atomics are used, so the rows are bit-identical
+ * across the three input routes and across any split of the frames into calls or slabs.  The positions are read from
+ * HBM once and nothing of size frames x points is written.  Argument errors return MDX_ERR_INVALID_VALUE before any
+ * device is touched. */
+typedef struct mdx_dip *mdx_dip_t;
+int mdx_dip_create(mdx_dip_t *out, int dev, int n_groups, const int64_t *n_points, const double *charges);
+int mdx_dip_destroy(mdx_dip_t h);
+/* Forgets the frames seen and the unwrap state (the next frame is again compared with `start`). */
+int mdx_dip_reset(mdx_dip_t h);
+/* The reference's global unwrap (algorithm/topology.py `unwrap`) per frame and point coordinate: d = x - x_prev;
+ * |d| >= dims / 2 moves the image count by -sign(d); x_prev becomes the raw x; the point used is x + image * dims, the
+ * shift applied in float64.  Before the first frame x_prev = start (float64 [n_points][3]: the points of the first
+ * analysed frame with every molecule made whole) and the image counts are 0.  The state carries from slab to slab and
+ * from call to call; frames must be fed in analysis order.  dims == NULL switches it off.  Only before the first
+ * frame. */
+int mdx_dip_set_unwrap(mdx_dip_t h, const double *dims, const double *start);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the scratch of a launch).
+ * The rows do not depend on it; tests use it to make a few frames cross several slabs. */
+int mdx_dip_set_slab_frames(mdx_dip_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring. */
+int mdx_dip_accumulate(mdx_dip_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3], read where they lie; index: host int32[n_index] rows of a
+ * frame in incoming order, or NULL for all n_atoms rows.  Asynchronous (mdx_dip_synchronize). */
+int mdx_dip_accumulate_device(mdx_dip_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_dip_accumulate_traj(mdx_dip_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_dip_synchronize(mdx_dip_t h);
+/* out: float64 [n_groups][frames seen][3]: the dipole moment of every group in every frame. */
+int mdx_dip_result(mdx_dip_t h, double *out);
+int mdx_dip_stats(mdx_dip_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
+int mdx_dip_enable_timing(mdx_dip_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

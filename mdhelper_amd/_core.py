@@ -677,6 +677,86 @@ class GyrationEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
 
 
+class DipoleEngine(_Engine):
+    """``mdx_dip_*``: per frame and group the dipole moment ``sum q (r + image L)`` in float64."""
+
+    _destroy = "mdx_dip_destroy"
+    TILE = 128          # points per tile of the summation order (DIP_TILE of csrc/mdx_dipole_device.hpp)
+
+    def __init__(self, n_points, charges, *, dev=0, timing=False):
+        self.n_per_group = np.ascontiguousarray(np.atleast_1d(n_points), dtype=np.int64)
+        if self.n_per_group.ndim != 1 or len(self.n_per_group) == 0:
+            raise ValueError("n_points must hold one entry per group.")
+        self.n_groups = len(self.n_per_group)
+        self.n_points = int(self.n_per_group.sum())
+        q = np.ascontiguousarray(charges, dtype=np.float64)
+        if q.shape != (self.n_points,):
+            raise ValueError("charges must hold one entry per point of the groups.")
+        h = c_void_p()
+        check(lib().mdx_dip_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), _ptr(q)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_dip_enable_timing(h, 1))
+
+    def set_unwrap(self, dims, start=None):
+        """The reference's global unwrap from frame to frame, starting from the points ``start``
+        (float64 ``[n_points, 3]``, every molecule whole); ``dims=None`` switches it off.  Frames must then be
+        fed in analysis order."""
+        if dims is None:
+            check(lib().mdx_dip_set_unwrap(self.handle, None, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        if s is None or s.shape != (self.n_points, 3):
+            raise ValueError("start must hold three coordinates per point of the groups.")
+        check(lib().mdx_dip_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+
+    def set_slab_frames(self, frames):
+        """Frames per kernel launch at most; 0 restores the default.  The rows do not depend on it."""
+        check(lib().mdx_dip_set_slab_frames(self.handle, int(frames)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows in concatenated-group order."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_dip_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
+        the engine's stream: ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_dip_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                              0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_dip_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                            0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_dip_synchronize(self.handle))
+
+    def result(self):
+        """float64 ``[G, frames seen, 3]``: the dipole moment of every group in every frame."""
+        out = np.zeros((self.n_groups, self.stats()["frames"], 3), dtype=np.float64)
+        check(lib().mdx_dip_result(self.handle, _ptr(out)))
+        return out
+
+    def reset(self):
+        check(lib().mdx_dip_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames = c_int64(), c_double(), c_int64()
+        check(lib().mdx_dip_stats(self.handle, byref(n), byref(ms), byref(frames)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

@@ -173,6 +173,19 @@ _SIGNATURES = {
     "mdx_gyr_result": (c_int, [_vp, _vp]),
     "mdx_gyr_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_gyr_enable_timing": (c_int, [_vp, c_int]),
+    # dipole moments
+    "mdx_dip_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
+    "mdx_dip_destroy": (c_int, [_vp]),
+    "mdx_dip_reset": (c_int, [_vp]),
+    "mdx_dip_set_unwrap": (c_int, [_vp, _vp, _vp]),
+    "mdx_dip_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_dip_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_dip_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_dip_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_dip_synchronize": (c_int, [_vp]),
+    "mdx_dip_result": (c_int, [_vp, _vp]),
+    "mdx_dip_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
+    "mdx_dip_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,8 +1,9 @@
 """Analysis classes of the hot path (mirrors ``mdhelper.analysis``)."""
 
-from . import base, polymer, profile, structure, transport  # noqa: F401
+from . import base, electrostatics, polymer, profile, structure, transport  # noqa: F401
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
+from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
 from .polymer import EndToEndVector, Gyradius, SingleChainStructureFactor  # noqa: F401
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401
 from .transport import Onsager  # noqa: F401
