@@ -534,6 +534,47 @@ int mdx_gyr_result(mdx_gyr_t h, double *out);
 int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_gyr_enable_timing(mdx_gyr_t h, int on);
 
+/* ---- per-chain linear projections: Rouse mode amplitudes (analysis/polymer.py RouseModes; no counterpart in the
+ * reference) ---------------------------------------------------------------------------------------------------------
+ * Rows arrive as for the gyration engine: group g holds n_chains[g] * n_monomers[g] consecutive points, a chain is
+ * n_monomers[g] consecutive points.  weights: float64 [sum_g n_rows * n_monomers[g]], group after group, row-major
+ * (w[g][k][n]); they must be finite.  Per frame, chain c and weight row k, in float64 with separate multiply and add
+ * (float32 coordinates are widened before any arithmetic):
+ *     x_n = (double)r_n + image_n * L,    X[c][k] = sum_n w[g][k][n] * x_n,
+ * the products added one after the other in the order n = 0, 1, ... starting from +0.0 — a plain host loop gives the
+ * same bits.  No floating-point atomics: the amplitudes are bit-identical across the three input routes and across
+ * any split of the frames into calls.  They stay in HBM as double [frames][S][3], S = sum_g n_rows * n_chains[g],
+ * series series0[g] + k * n_chains[g] + c with series0[g] = sum_{g' < g} n_rows * n_chains[g']: the chains of one
+ * (group, row) are a contiguous range of a frame, the shape mdx_msd_push_device(group, d_pos, n_total = S, first,
+ * count) takes.  Argument errors return MDX_ERR_INVALID_VALUE before any device is touched. */
+typedef struct mdx_rouse *mdx_rouse_t;
+int mdx_rouse_create(mdx_rouse_t *out, int dev, int n_groups, const int64_t *n_chains, const int64_t *n_monomers,
+                     int64_t n_rows, const double *weights);
+int mdx_rouse_destroy(mdx_rouse_t h);
+/* Forgets the frames seen and the unwrap state (the next frame is again compared with `start`). */
+int mdx_rouse_reset(mdx_rouse_t h);
+/* Room for n_frames frames in all, allocated once (without it the buffer doubles as frames arrive). */
+int mdx_rouse_reserve(mdx_rouse_t h, int64_t n_frames);
+/* As mdx_gyr_set_grouping / mdx_gyr_set_unwrap: float64 centres of mass of monomers formed on the device; the global
+ * unwrap with the same rule, the same carried state and x_prev = start before the first frame. */
+int mdx_rouse_set_grouping(mdx_rouse_t h, int64_t n_molecules, const int64_t *offsets, const double *masses);
+int mdx_rouse_set_unwrap(mdx_rouse_t h, const double *dims, const double *start);
+/* The three input routes of the gyration engine: host float32 [n_frames][n][3] through the pinned ring; frames in
+ * HBM read where they lie (asynchronous: mdx_rouse_synchronize); frames of a trajectory file. */
+int mdx_rouse_accumulate(mdx_rouse_t h, const float *pos, int64_t n, int64_t n_frames);
+int mdx_rouse_accumulate_device(mdx_rouse_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                                const int32_t *index, int64_t n_index);
+int mdx_rouse_accumulate_traj(mdx_rouse_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_rouse_synchronize(mdx_rouse_t h);
+/* out: float64 [frames seen][S][3]. */
+int mdx_rouse_result(mdx_rouse_t h, double *out);
+/* Waits for the engine's stream and returns the amplitudes where they lie; the pointer is valid until the next
+ * accumulate, reset or destroy of the handle. */
+int mdx_rouse_device_result(mdx_rouse_t h, const double **d_ptr, int64_t *n_frames, int64_t *n_series);
+int mdx_rouse_stats(mdx_rouse_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
+int mdx_rouse_enable_timing(mdx_rouse_t h, int on);
+
 /* ---- instantaneous dipole moments (reference analysis/electrostatics.py DipoleMoment) ------------------------------
  * Rows arrive in the order of the concatenated groups: group g holds n_points[g] consecutive points; charges float64,
  * one per point in that order, finite.  Per frame, group and component, in float64 with separate multiply and add

@@ -677,6 +677,118 @@ class GyrationEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
 
 
+class ChainProjectionEngine(_Engine):
+    """``mdx_rouse_*``: per frame, chain and weight row ``X = sum_n w_n x_n`` in float64, kept in HBM as
+    ``[frames, S, 3]`` with series ``series0[g] + k * n_chains[g] + c`` (group g, row k, chain c)."""
+
+    _destroy = "mdx_rouse_destroy"
+
+    def __init__(self, n_chains, n_monomers, weights, *, dev=0, timing=False):
+        """weights: one float64 array ``[K, n_monomers[g]]`` per group (a single 2-D array for one group)."""
+        self.n_chains = np.ascontiguousarray(np.atleast_1d(n_chains), dtype=np.int64)
+        self.n_monomers = np.ascontiguousarray(np.atleast_1d(n_monomers), dtype=np.int64)
+        if self.n_chains.ndim != 1 or self.n_chains.shape != self.n_monomers.shape or len(self.n_chains) == 0:
+            raise ValueError("n_chains and n_monomers must hold one entry per group.")
+        self.n_groups = len(self.n_chains)
+        self.n_points = int((self.n_chains * self.n_monomers).sum())
+        if isinstance(weights, np.ndarray) and weights.ndim == 2:
+            weights = [weights]
+        w = [np.ascontiguousarray(x, dtype=np.float64) for x in weights]
+        if len(w) != self.n_groups or any(x.ndim != 2 for x in w):
+            raise ValueError("weights must hold one array [n_rows, n_monomers] per group.")
+        self.n_rows = int(w[0].shape[0])
+        if self.n_rows < 1 or any(x.shape != (self.n_rows, N) for x, N in zip(w, self.n_monomers)):
+            raise ValueError("weights must hold one array [n_rows, n_monomers] per group.")
+        self.series0 = np.concatenate(([0], np.cumsum(self.n_rows * self.n_chains)))[:-1]
+        self.n_series = int(self.n_rows * self.n_chains.sum())
+        flat = np.concatenate([x.ravel() for x in w])
+        h = c_void_p()
+        check(lib().mdx_rouse_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers),
+                                     self.n_rows, _ptr(flat)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_rouse_enable_timing(h, 1))
+
+    def set_grouping(self, offsets, masses):
+        """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
+        groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
+        if offsets is None:
+            check(lib().mdx_rouse_set_grouping(self.handle, 0, None, None))
+            return
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if len(m) != o[-1]:
+            raise ValueError("masses must hold one entry per particle of the grouping.")
+        check(lib().mdx_rouse_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+
+    def set_unwrap(self, dims, start=None):
+        """The global unwrap of ``GyrationEngine.set_unwrap``: from frame to frame, starting from the points
+        ``start`` (float64 ``[n_points, 3]``, every chain whole); ``dims=None`` switches it off."""
+        if dims is None:
+            check(lib().mdx_rouse_set_unwrap(self.handle, None, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        if s is None or s.shape != (self.n_points, 3):
+            raise ValueError("start must hold three coordinates per point of the groups.")
+        check(lib().mdx_rouse_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+
+    def reserve(self, n_frames):
+        """Room for ``n_frames`` frames in all, allocated once."""
+        check(lib().mdx_rouse_reserve(self.handle, int(n_frames)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows in concatenated-group order."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_rouse_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
+        the engine's stream: ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_rouse_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                                0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_rouse_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                              0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_rouse_synchronize(self.handle))
+
+    def result(self):
+        """float64 ``[frames seen, S, 3]`` on the host."""
+        out = np.zeros((self.stats()["frames"], self.n_series, 3), dtype=np.float64)
+        check(lib().mdx_rouse_result(self.handle, _ptr(out)))
+        return out
+
+    def device_result(self):
+        """``(pointer, frames seen, S)``: the amplitudes ``double[frames][S][3]`` where they lie in HBM, after a
+        wait for the engine's stream; valid until the next accumulate, reset or close."""
+        p, f, s = c_void_p(), c_int64(), c_int64()
+        check(lib().mdx_rouse_device_result(self.handle, byref(p), byref(f), byref(s)))
+        return p, f.value, s.value
+
+    def reset(self):
+        check(lib().mdx_rouse_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames = c_int64(), c_double(), c_int64()
+        check(lib().mdx_rouse_stats(self.handle, byref(n), byref(ms), byref(frames)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
+
+
+RouseEngine = ChainProjectionEngine
+
+
 class DipoleEngine(_Engine):
     """``mdx_dip_*``: per frame and group the dipole moment ``sum q (r + image L)`` in float64."""
 

@@ -173,6 +173,21 @@ _SIGNATURES = {
     "mdx_gyr_result": (c_int, [_vp, _vp]),
     "mdx_gyr_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_gyr_enable_timing": (c_int, [_vp, c_int]),
+    # per-chain linear projections (Rouse mode amplitudes)
+    "mdx_rouse_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp, c_int64, _vp]),
+    "mdx_rouse_destroy": (c_int, [_vp]),
+    "mdx_rouse_reset": (c_int, [_vp]),
+    "mdx_rouse_reserve": (c_int, [_vp, c_int64]),
+    "mdx_rouse_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
+    "mdx_rouse_set_unwrap": (c_int, [_vp, _vp, _vp]),
+    "mdx_rouse_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_rouse_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_rouse_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_rouse_synchronize": (c_int, [_vp]),
+    "mdx_rouse_result": (c_int, [_vp, _vp]),
+    "mdx_rouse_device_result": (c_int, [_vp, POINTER(_vp), POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_rouse_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
+    "mdx_rouse_enable_timing": (c_int, [_vp, c_int]),
     # dipole moments
     "mdx_dip_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
     "mdx_dip_destroy": (c_int, [_vp]),

@@ -4,6 +4,6 @@ from . import base, electrostatics, polymer, profile, structure, transport  # no
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
-from .polymer import EndToEndVector, Gyradius, SingleChainStructureFactor  # noqa: F401
+from .polymer import EndToEndVector, Gyradius, RouseModes, SingleChainStructureFactor  # noqa: F401
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401
 from .transport import Onsager  # noqa: F401

@@ -26,6 +26,11 @@ single-chain mode (``mdx_sq_set_chains``): per frame and chain the device forms
 ``Gyradius`` runs on the gyration engine (``mdx_gyr_*``): per frame the device forms the monomer
 centres of mass, follows the points across the boundaries (``unwrap``), and computes every
 chain's centre of mass and mass-weighted second moments in float64; frames shard across ranks.
+
+``RouseModes`` (an extension; the reference has no such analysis) runs on the chain-projection engine
+(``mdx_rouse_*``): per frame and chain the device forms ``X_p = sum_n w_pn r_n`` for every requested mode in
+float64 and keeps the amplitudes in HBM, where the correlation engine reads them (``mdx_msd_push_device``);
+the chains of each (group, mode) shard across ranks.
 """
 
 from __future__ import annotations
@@ -138,6 +143,125 @@ class _PolymerAnalysisBase(DynamicAnalysisBase):
         self._unwrap = unwrap
         self._verbose = verbose
 
+    # ---------------------------------------------------------------- points of whole chains
+    # (shared by the analyses whose engines take every monomer of every chain: Gyradius, RouseModes)
+
+    def _setup_points(self) -> None:
+        """Chain lengths read from the topology, the group-size and ``unwrap`` checks, and the groups' point
+        ranges ``_Ns`` / ``_N`` / ``_slices``."""
+        if self._internal:
+            for i, (g, gr) in enumerate(zip(self._groups, self._groupings)):
+                seg = np.asarray(g.segindices)
+                if gr == "residues":
+                    _, first = np.unique(np.asarray(g.resindices), return_index=True)
+                    _, per_seg = np.unique(seg[first], return_counts=True)      # residues per segment
+                    what = "residues"
+                else:
+                    _, per_seg = np.unique(seg, return_counts=True)
+                    what = "atoms"
+                if np.any(per_seg != per_seg[0]):
+                    raise ValueError(f"All segments of group {i} must hold the same number of {what}.")
+                self._n_monomers[i] = per_seg[0]
+        for i, (g, gr, M, N_p) in enumerate(zip(self._groups, self._groupings, self._n_chains,
+                                                self._n_monomers)):
+            N = int(M) * int(N_p)
+            if gr == "atoms" or self._internal:
+                n_have = g.n_atoms if gr == "atoms" else len(np.unique(np.asarray(g.resindices)))
+                bad = N <= 0 or n_have != N
+            else:
+                n_have = g.n_atoms
+                bad = N <= 0 or n_have == 0 or n_have % N != 0
+            if bad:
+                what = "atoms" if gr == "atoms" or not self._internal else "residues"
+                raise ValueError(f"Group {i} holds {n_have} {what}, which do not form n_chains * "
+                                 f"n_monomers = {M} * {N_p} = {N} monomers.")
+        if self._unwrap:
+            if self._comm.world_size > 1:
+                raise ValueError("unwrap cannot be combined with more than one rank: the image counts "
+                                 "run from frame to frame, so the frames cannot shard.  Run it on one "
+                                 "rank.")
+            if self._dimensions is None:
+                raise ValueError("No system dimensions found: unwrapping is not possible.")
+
+        self._Ns = np.fromiter((M * N_p for M, N_p in zip(self._n_chains, self._n_monomers)),
+                               dtype=int, count=self._n_groups)
+        self._N = self._Ns.sum()
+        self._slices = []
+        index = 0
+        for N in self._Ns:
+            self._slices.append(slice(index, index + N))
+            index += N
+
+    def _selection(self, g, gr, N):
+        """(particle indices monomer by monomer, monomer offsets or None, particle masses, monomer
+        masses) of a group of ``N`` monomers."""
+        idx = np.asarray(g.indices)
+        masses = np.asarray(g.masses, dtype=np.float64)
+        if gr == "atoms":
+            return idx, None, masses, masses
+        if not self._internal:
+            # a monomer is n_atoms / N consecutive atoms
+            offsets = np.arange(N + 1, dtype=np.int64) * (g.n_atoms // N)
+        else:
+            # residues of the topology, monomer by monomer; a chain is a segment
+            _, inverse = np.unique(np.asarray(g.resindices), return_inverse=True)
+            order = np.argsort(inverse, kind="stable")
+            offsets = np.concatenate(([0], np.cumsum(np.bincount(inverse)))).astype(np.int64)
+            n_chains = len(np.unique(np.asarray(g.segindices)))
+            seg = np.asarray(g.segindices)[order][offsets[:-1]].reshape(n_chains, -1)
+            if np.any(seg != seg[:, :1]) or len(np.unique(seg[:, 0])) != n_chains:
+                raise ValueError("The residues of every segment must be consecutive.")
+            idx, masses = idx[order], masses[order]
+        return idx, offsets, masses, np.add.reduceat(masses, offsets[:-1])
+
+    def _start(self, sels):
+        """float64[N, 3]: the points of the current frame with every chain made whole."""
+        pos = np.asarray(self.universe.trajectory.ts.positions, dtype=float)
+        start = np.empty((self._N, 3))
+        for (idx, off, m, pm), s, M, N_p in zip(sels, self._slices, self._n_chains, self._n_monomers):
+            points = pos[idx]
+            if off is not None:
+                points = np.add.reduceat(points * m[:, None], off[:-1], axis=0) / pm[:, None]
+            bonds = (np.arange(M)[:, None] * N_p + np.arange(N_p - 1)[None, :]).ravel()
+            start[s] = unwrap_edge(positions=points, bonds=np.stack((bonds, bonds + 1), axis=1),
+                                   dimensions=self._dimensions, masses=pm)
+        return start
+
+    def _point_selections(self):
+        """``_selection`` of every group; sets ``_index``, the rows of a frame in concatenated-group order."""
+        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
+        self._index = np.concatenate([sel[0] for sel in sels])
+        return sels
+
+    def _configure_points(self, engine, sels) -> None:
+        """Hands the grouping (monomers of several atoms) and the unwrap start to a chain engine."""
+        if any(sel[1] is not None for sel in sels):
+            sizes = [np.ones(len(idx), dtype=np.int64) if off is None else np.diff(off)
+                     for idx, off, _, _ in sels]
+            engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
+                                np.concatenate([sel[2] for sel in sels]))
+        if self._unwrap:
+            st = self._sliced_trajectory
+            self.universe.trajectory[st.frames[0] if hasattr(st, "frames") else (self.start or 0)]
+            engine.set_unwrap(self._dimensions, self._start(sels))
+
+    def _feed_blocks(self, mine) -> None:
+        """Whole blocks of the frames ``mine`` go to ``_engine`` from a trajectory file, from float32 frames in
+        HBM (read where they lie) or from host memory (the frame feed of base.py)."""
+        traj = self._trajectory
+        index = self._index
+        whole = all_particles(index, traj.n_atoms)
+        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
+                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
+        for sel in frame_blocks(mine, size):
+            route, src = block_source(traj, sel, True)
+            if route == "file":
+                self._engine.accumulate_traj(src, sel, None if whole else index)
+            elif route == "hbm":
+                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
+            else:
+                self._engine.accumulate(src if whole else src[:, index])
+
 
 class Gyradius(_PolymerAnalysisBase):
     r"""
@@ -186,86 +310,8 @@ class Gyradius(_PolymerAnalysisBase):
                  parallel: bool = False, verbose: bool = True, **kwargs) -> None:
         super().__init__(groups, groupings, n_chains, n_monomers, unwrap=unwrap, parallel=parallel,
                          verbose=verbose, **kwargs)
-        if self._internal:
-            for i, (g, gr) in enumerate(zip(self._groups, self._groupings)):
-                seg = np.asarray(g.segindices)
-                if gr == "residues":
-                    _, first = np.unique(np.asarray(g.resindices), return_index=True)
-                    _, per_seg = np.unique(seg[first], return_counts=True)      # residues per segment
-                    what = "residues"
-                else:
-                    _, per_seg = np.unique(seg, return_counts=True)
-                    what = "atoms"
-                if np.any(per_seg != per_seg[0]):
-                    raise ValueError(f"All segments of group {i} must hold the same number of {what}.")
-                self._n_monomers[i] = per_seg[0]
-        for i, (g, gr, M, N_p) in enumerate(zip(self._groups, self._groupings, self._n_chains,
-                                                self._n_monomers)):
-            N = int(M) * int(N_p)
-            if gr == "atoms" or self._internal:
-                n_have = g.n_atoms if gr == "atoms" else len(np.unique(np.asarray(g.resindices)))
-                bad = N <= 0 or n_have != N
-            else:
-                n_have = g.n_atoms
-                bad = N <= 0 or n_have == 0 or n_have % N != 0
-            if bad:
-                what = "atoms" if gr == "atoms" or not self._internal else "residues"
-                raise ValueError(f"Group {i} holds {n_have} {what}, which do not form n_chains * "
-                                 f"n_monomers = {M} * {N_p} = {N} monomers.")
-        if unwrap:
-            if self._comm.world_size > 1:
-                raise ValueError("unwrap cannot be combined with more than one rank: the image counts "
-                                 "run from frame to frame, so the frames cannot shard.  Run it on one "
-                                 "rank.")
-            if self._dimensions is None:
-                raise ValueError("No system dimensions found: unwrapping is not possible.")
-
-        self._Ns = np.fromiter((M * N_p for M, N_p in zip(self._n_chains, self._n_monomers)),
-                               dtype=int, count=self._n_groups)
-        self._N = self._Ns.sum()
-        self._slices = []
-        index = 0
-        for N in self._Ns:
-            self._slices.append(slice(index, index + N))
-            index += N
+        self._setup_points()
         self._components = components
-
-    # ------------------------------------------------------------------ points
-
-    def _selection(self, g, gr, N):
-        """(particle indices monomer by monomer, monomer offsets or None, particle masses, monomer
-        masses) of a group of ``N`` monomers."""
-        idx = np.asarray(g.indices)
-        masses = np.asarray(g.masses, dtype=np.float64)
-        if gr == "atoms":
-            return idx, None, masses, masses
-        if not self._internal:
-            # a monomer is n_atoms / N consecutive atoms
-            offsets = np.arange(N + 1, dtype=np.int64) * (g.n_atoms // N)
-        else:
-            # residues of the topology, monomer by monomer; a chain is a segment
-            _, inverse = np.unique(np.asarray(g.resindices), return_inverse=True)
-            order = np.argsort(inverse, kind="stable")
-            offsets = np.concatenate(([0], np.cumsum(np.bincount(inverse)))).astype(np.int64)
-            n_chains = len(np.unique(np.asarray(g.segindices)))
-            seg = np.asarray(g.segindices)[order][offsets[:-1]].reshape(n_chains, -1)
-            if np.any(seg != seg[:, :1]) or len(np.unique(seg[:, 0])) != n_chains:
-                raise ValueError("The residues of every segment must be consecutive.")
-            idx, masses = idx[order], masses[order]
-        return idx, offsets, masses, np.add.reduceat(masses, offsets[:-1])
-
-    def _start(self, sels):
-        """float64[N, 3]: the points of the current frame with every chain made whole."""
-        pos = np.asarray(self.universe.trajectory.ts.positions, dtype=float)
-        start = np.empty((self._N, 3))
-        for (idx, off, m, pm), s, M, N_p in zip(sels, self._slices, self._n_chains, self._n_monomers):
-            points = pos[idx]
-            if off is not None:
-                points = np.add.reduceat(points * m[:, None], off[:-1], axis=0) / pm[:, None]
-            bonds = (np.arange(M)[:, None] * N_p + np.arange(N_p - 1)[None, :]).ravel()
-            start[s] = unwrap_edge(positions=points, bonds=np.stack((bonds, bonds + 1), axis=1),
-                                   dimensions=self._dimensions, masses=pm)
-        return start
 
     # ------------------------------------------------------------------ protocol
 
@@ -278,19 +324,10 @@ class Gyradius(_PolymerAnalysisBase):
 
         # rows of every frame in concatenated-group order, sorted monomer by monomer; the monomers'
         # centres of mass are formed on the device (plain-atom groups: monomers of one particle)
-        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
-        self._index = np.concatenate([sel[0] for sel in sels])
+        sels = self._point_selections()
         self._engine = _core.GyrationEngine(self._n_chains, self._n_monomers,
                                             np.concatenate([sel[3] for sel in sels]), dev=self._device)
-        if any(sel[1] is not None for sel in sels):
-            sizes = [np.ones(len(idx), dtype=np.int64) if off is None else np.diff(off)
-                     for idx, off, _, _ in sels]
-            self._engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
-                                      np.concatenate([sel[2] for sel in sels]))
-        if self._unwrap:
-            st = self._sliced_trajectory
-            self.universe.trajectory[st.frames[0] if hasattr(st, "frames") else (self.start or 0)]
-            self._engine.set_unwrap(self._dimensions, self._start(sels))
+        self._configure_points(self._engine, sels)
         # frames shard across ranks (unwrap, which makes them sequential, runs on one rank)
         self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
         self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
@@ -309,19 +346,7 @@ class Gyradius(_PolymerAnalysisBase):
         if not has_frame_blocks(traj):
             return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
                                **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=True)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
+        self._feed_blocks(self._batched_frames(start, stop, step, frames, shard=True))
         self._conclude()
         return self
 
@@ -550,6 +575,195 @@ class EndToEndVector(_PolymerAnalysisBase):
                 valid = np.where(acf >= 0)[0]
                 self.results.relaxation_times[i, j] = calculate_relaxation_time(
                     self.results.times[valid], acf[valid])
+
+
+class RouseModes(_PolymerAnalysisBase):
+    r"""
+    Rouse mode amplitudes of polymer chains and their relaxation (no counterpart in the reference),
+
+    .. math:: \mathbf X_p(t)=\frac1N\sum_{n=0}^{N-1}\mathbf r_n(t)\cos\frac{p\pi(n+\frac12)}{N},
+              \qquad p=1,\dots,N-1,
+
+    their mean squares :math:`\langle X_p^2\rangle`, the normalised autocorrelations
+    :math:`C_p(t)=\langle\mathbf X_p(t)\cdot\mathbf X_p(0)\rangle/\langle X_p^2\rangle` averaged over the
+    chains of each group, and a relaxation time :math:`\tau_p` per mode.
+
+    Parameters
+    ----------
+    groups, groupings, n_chains, n_monomers : see ``_PolymerAnalysisBase``; a group holds
+        ``n_chains * n_monomers`` monomers, chain after chain (checks as in ``Gyradius``)
+    modes : int or sequence of distinct ints, keyword-only — ``P`` means :math:`p=1,\dots,P`; every
+        :math:`p` must satisfy :math:`1\le p\le\min_g N_g-1`
+    n_blocks : int, keyword-only — blocks the trajectory is split into
+    dt : float, keyword-only, optional — time between frames (ps)
+    fft : bool, keyword-only — FFT-based ACF on the GPU (``False``: direct sliding windows, NumPy, on
+        amplitudes copied from the device)
+    unwrap : bool, keyword-only — follow the monomers across the periodic boundaries from frame to
+        frame, starting from chains made whole in the first analysed frame
+    comm, device : keyword-only (extension) — every rank projects all frames; the chains of each
+        (group, mode) shard across ranks in the correlation, one all-reduce of the accumulators
+
+    Results: ``results.modes`` ``[P]``, ``results.times`` ``[T_b]`` (ps), ``results.amplitudes``
+    ``[N_g, N_b, P]`` (:math:`\langle X_p^2\rangle` in Å², the lag-0 value of the ACF after the
+    :math:`M(T_b-m)` normalisation), ``results.acf`` ``[N_g, N_b, P, T_b]`` (:math:`C_p(t)`, 1 at lag 0),
+    ``results.units``; ``results.relaxation_times`` ``[N_g, N_b, P]`` after ``calculate_relaxation_times()``.
+
+    Where the work goes: the projection engine (``mdx_rouse_*``) forms the float64 monomer centres, follows
+    them across the boundaries and computes every :math:`\mathbf X_p` of every chain and frame, in HBM; with
+    ``fft=True`` the correlation engine of ``Onsager`` reads them there (``mdx_msd_push_device``), one contiguous
+    range of series per (group, mode), and the amplitudes never visit the host.
+
+    What it restricts:
+
+    * :math:`p=0` (the centre of geometry, whose observable is an MSD, not an ACF), :math:`p\ge N`, repeated
+      modes and ``n_groups * len(modes) > 4096`` (the correlation engine's groups) raise ``ValueError`` at
+      construction.
+    * The modes are not weighted by mass (the usual definition); with ``"residues"`` the :math:`\mathbf r_n` are
+      the monomers' centres of mass.  The weights ``cos(pi p (n + 1/2) / N) / N`` are formed on the host in
+      float64; the device multiplies and adds.
+    * ``unwrap=True`` with more than one rank, or without box dimensions, and groups whose size does not match
+      ``n_chains * n_monomers`` raise ``ValueError`` at construction, as in ``Gyradius``; the chains of the first
+      analysed frame are made whole along bonds between consecutive monomers.
+    * Frames beyond ``n_blocks * (n_frames // n_blocks)`` are discarded with a warning, as in
+      ``EndToEndVector``.  Frames do not shard across ranks.
+    * Cross-correlations between different modes and the MSD of :math:`p=0` are not computed.
+    * There is no CPU fallback for the projection: without a HIP device ``run()`` raises ``RuntimeError``.
+    """
+
+    _MAX_SERIES_GROUPS = 4096          # groups of the correlation engine (mdx_msd_create)
+
+    def __init__(self, groups, groupings: Union[str, tuple] = "atoms", n_chains=None,
+                 n_monomers=None, *, modes=5, n_blocks: int = 1, dt=None, fft: bool = True,
+                 unwrap: bool = False, verbose: bool = True, **kwargs) -> None:
+        kwargs.pop("parallel", None)
+        super().__init__(groups, groupings, n_chains, n_monomers, unwrap=unwrap,
+                         verbose=verbose, **kwargs)
+        self._setup_points()
+        if isinstance(modes, (int, np.integer)):
+            modes = np.arange(1, int(modes) + 1)
+        else:
+            given = np.asarray(modes)
+            if given.ndim != 1 or (given.size and not np.issubdtype(given.dtype, np.integer)):
+                raise ValueError("'modes' must be an int or a sequence of ints.")
+            modes = given.astype(int)
+        p_max = int(self._n_monomers.min()) - 1
+        if len(modes) == 0 or modes.min() < 1 or modes.max() > p_max:
+            raise ValueError(f"Every mode p must satisfy 1 <= p <= n_monomers - 1 = {p_max}; p = 0 is the "
+                             "centre of geometry, whose observable is a mean squared displacement.")
+        if len(np.unique(modes)) != len(modes):
+            raise ValueError("The modes must be distinct.")
+        if self._n_groups * len(modes) > self._MAX_SERIES_GROUPS:
+            raise ValueError(f"n_groups * len(modes) = {self._n_groups * len(modes)} exceeds the "
+                             f"{self._MAX_SERIES_GROUPS} groups of the correlation engine.")
+        self._modes = modes
+        self._n_blocks = n_blocks
+        self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
+        self._fft = fft
+
+    def _weights(self):
+        """One float64 array ``[P, N_p]`` per group: ``cos(pi p (n + 1/2) / N_p) / N_p``."""
+        return [np.stack([np.cos(np.pi * p * (np.arange(N_p) + 0.5) / N_p) / N_p for p in self._modes])
+                for N_p in self._n_monomers]
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        self._n_frames_block = self.n_frames // self._n_blocks
+        self._n_frames = self._n_blocks * self._n_frames_block
+        extra = self.n_frames - self._n_frames
+        if extra > 0:
+            warnings.warn(f"The trajectory is not divisible into {self._n_blocks:,} blocks, so "
+                          f"the last {extra:,} frame(s) will be discarded. To maximize "
+                          "performance, set appropriate starting and ending frames in run() so "
+                          "that the number of frames to be analyzed is divisible by the number "
+                          "of blocks.")
+        P = len(self._modes)
+        step = self.step if self.step is not None else 1
+        self.results.modes = self._modes.copy()
+        self.results.times = step * self._dt * np.arange(self._n_frames_block)
+        self.results.amplitudes = np.empty((self._n_groups, self._n_blocks, P))
+        self.results.acf = np.empty((self._n_groups, self._n_blocks, P, self._n_frames_block))
+        self.results.units = {"results.times": "picosecond", "results.amplitudes": "angstrom^2"}
+
+        sels = self._point_selections()
+        self._engine = _core.ChainProjectionEngine(self._n_chains, self._n_monomers, self._weights(),
+                                                   dev=self._device)
+        self._configure_points(self._engine, sels)
+        self._engine.reserve(self.n_frames)
+        self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
+                                   with_box=False)
+
+    def _single_frame(self) -> None:
+        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
+
+    # batched run (the frame feed of base.py), the three routes of Gyradius.run; every rank sees all frames
+    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
+        if not has_frame_blocks(self._trajectory):
+            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
+                               **kwargs)
+        self._feed_blocks(self._batched_frames(start, stop, step, frames, shard=False))
+        self._conclude()
+        return self
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        B, Tb, P = self._n_blocks, self._n_frames_block, len(self._modes)
+        series0 = np.concatenate(([0], np.cumsum(P * self._n_chains)))
+        try:
+            if not self._fft:
+                X = self._engine.result()[:self._n_frames]                   # [T, S, 3]
+                for g, M in enumerate(self._n_chains):
+                    for k in range(P):
+                        lo = series0[g] + k * M
+                        raw = correlation_shift(X[:, lo:lo + M].reshape(B, Tb, M, 3), average=True,
+                                                vector=True)
+                        self.results.amplitudes[g, :, k] = raw[:, 0]
+                        self.results.acf[g, :, k] = raw / raw[:, :1]
+                return
+            rank, world = self._comm.rank, self._comm.world_size
+            d_amp, n_seen, S = self._engine.device_result()
+            if n_seen < self._n_frames:
+                raise RuntimeError(f"The projection engine holds {n_seen} frames, {self._n_frames} were "
+                                   "expected.")
+            eng = _core.MsdEngine(Tb, B, self._n_groups * P, dev=self._device)
+            try:
+                # the chains of a (group, mode) are a contiguous range of series: read where they lie
+                for g, M in enumerate(self._n_chains):
+                    lo, hi = shard_range(int(M), rank, world)
+                    if hi > lo:
+                        for k in range(P):
+                            eng.push_device(g * P + k, d_amp, S, int(series0[g] + k * M + lo), hi - lo, 0)
+                if world > 1 and getattr(self._comm, "device_collectives", False):
+                    eng.allreduce(self._comm)
+                    acf = eng.result_acf()
+                else:
+                    acf = eng.result_acf()
+                    if world > 1:
+                        acf = self._comm.allreduce(acf, op="sum")
+            finally:
+                eng.close()
+        finally:
+            self._engine.close()
+        # correlation_fft: normalise lag m by T_b - m, average over the chains
+        weights = (Tb - np.arange(Tb)).astype(float)
+        acf = np.asarray(acf).reshape(self._n_groups, P, B, Tb)
+        for g, M in enumerate(self._n_chains):
+            raw = np.swapaxes(acf[g], 0, 1) / weights / M                   # [B, P, T_b]
+            self.results.amplitudes[g] = raw[..., 0]
+            self.results.acf[g] = raw / raw[..., :1]
+
+    def calculate_relaxation_times(self) -> None:
+        """Stretched-exponential relaxation time of every (group, block, mode), fitted to the non-negative
+        part of the ACF as in ``EndToEndVector.calculate_relaxation_time``."""
+        if "acf" not in self.results:
+            raise RuntimeError("Call RouseModes.run() before RouseModes.calculate_relaxation_times().")
+        self.results.relaxation_times = np.empty(self.results.acf.shape[:3])
+        self.results.units["results.relaxation_times"] = "picosecond"
+        for idx in np.ndindex(*self.results.acf.shape[:3]):
+            acf = self.results.acf[idx]
+            valid = np.where(acf >= 0)[0]
+            self.results.relaxation_times[idx] = calculate_relaxation_time(self.results.times[valid],
+                                                                           acf[valid])
 
 
 class SingleChainStructureFactor(DynamicAnalysisBase):

@@ -23,6 +23,8 @@
 
 #include <cstdint>
 
+#include "mdx_points_device.hpp"
+
 namespace mdx_gyr_dev {
 
 constexpr int GYR_THREADS = 256;
@@ -47,27 +49,8 @@ __device__ __forceinline__ double gyr_fold(double v, int shift)
     return v;
 }
 
-template <typename SRC> struct GyrSource {
-    const SRC *__restrict__ pos;        // frame of src_rows rows
-    const int *__restrict__ index;      // row of point p, or nullptr: p
-    const int *__restrict__ images;     // int[n_points][3] of the frame, or nullptr
-    double L[3];
-
-    __device__ __forceinline__ void load(int p, double x[3]) const
-    {
-        const int64_t r = index ? index[p] : p;
-        const SRC *__restrict__ q = pos + r * 3;
-        x[0] = (double)q[0];
-        x[1] = (double)q[1];
-        x[2] = (double)q[2];
-        if (images) {
-            const int *im = images + int64_t(p) * 3;
-            x[0] = __dadd_rn(x[0], __dmul_rn((double)im[0], L[0]));
-            x[1] = __dadd_rn(x[1], __dmul_rn((double)im[1], L[1]));
-            x[2] = __dadd_rn(x[2], __dmul_rn((double)im[2], L[2]));
-        }
-    }
-};
+// the widened point of a frame (mdx_points_device.hpp), shared with the projection engine
+template <typename SRC> using GyrSource = mdx_prof_dev::PointSource<SRC>;
 
 // chain_out[frame][chain][4] = Rg, Rg_x, Rg_y, Rg_z of every chain.  Grid: x = units in fours (one per wave),
 // y = frames.  The frame is read once from HBM: the first GYR_HOLD strides of a chain stay in registers between

@@ -1,7 +1,7 @@
 // mdx_points_device.hpp — kernels that prepare the points of a frame, shared by the density-profile engine
-// (mdx_profile.hip) and the gyration engine (mdx_gyration.hip): float64 centres of mass of molecules and the image
-// scan of the reference's global unwrap (algorithm/topology.py `unwrap`).  float64 throughout, with separate
-// multiply and add.
+// (mdx_profile.hip), the gyration engine (mdx_gyration.hip) and the chain-projection engine (mdx_rouse.hip): float64
+// centres of mass of molecules, the image scan of the reference's global unwrap (algorithm/topology.py `unwrap`)
+// and the widened, image-shifted point the chain kernels read.  float64 throughout, with separate multiply and add.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +14,29 @@ template <typename T> __device__ __forceinline__ T prof_pick(int k, T a, T b, T 
 {
     return k == 0 ? a : k == 1 ? b : c;
 }
+
+// One frame as the chain kernels read it: x = (double)r + image * L, the shift applied in float64.
+template <typename SRC> struct PointSource {
+    const SRC *__restrict__ pos;        // frame of src_rows rows
+    const int *__restrict__ index;      // row of point p, or nullptr: p
+    const int *__restrict__ images;     // int[n_points][3] of the frame, or nullptr
+    double L[3];
+
+    __device__ __forceinline__ void load(int p, double x[3]) const
+    {
+        const int64_t r = index ? index[p] : p;
+        const SRC *__restrict__ q = pos + r * 3;
+        x[0] = (double)q[0];
+        x[1] = (double)q[1];
+        x[2] = (double)q[2];
+        if (images) {
+            const int *im = images + int64_t(p) * 3;
+            x[0] = __dadd_rn(x[0], __dmul_rn((double)im[0], L[0]));
+            x[1] = __dadd_rn(x[1], __dmul_rn((double)im[1], L[1]));
+            x[2] = __dadd_rn(x[2], __dmul_rn((double)im[2], L[2]));
+        }
+    }
+};
 
 namespace {   // internal linkage: compiled into several translation units
 

@@ -1,62 +1,62 @@
-// mdx_gyration.hip — per-chain radii of gyration on gfx950 (MI355X).
+// mdx_rouse.hip — per-chain linear projections (Rouse mode amplitudes) on gfx950 (MI355X).
 //
-// Carries Gyradius._single_frame (reference src/mdhelper/analysis/polymer.py:439-465): positions (atoms, or the
-// float64 centres of mass of monomers) -> optional global unwrap (topology.py `unwrap`) -> per chain the centre of
-// mass and the mass-weighted second moments about it (algorithm/molecule.py radius_of_gyration) -> square roots ->
-// mean over the chains of a group.  Contract and summation orders: mdx_gyration_device.hpp; this unit is compiled
-// with contraction off and spells its float64 operations out.
+// Carries the frame work of analysis.polymer.RouseModes: positions (atoms, or the float64 centres of mass of
+// monomers) -> optional global unwrap (topology.py `unwrap`) -> per chain and weight row X = sum_n w_n x_n.  The
+// weights come from the caller in float64 (no cos on the device), so the engine serves any per-monomer weight set.
+// Contract and summation order: mdx_rouse_device.hpp; this unit is compiled with contraction off and spells its
+// float64 operations out.
 //
-// One pass over the positions at 12 B per atom-frame: a wave takes a chain (several short ones), keeps its points in
-// registers between the centre and the moments, and folds across lanes by shuffles.  The per-chain values of a slab
-// of frames go to a scratch array that a second, small kernel averages per (frame, group).  Nothing is added with
-// atomics, so the rows repeat bit for bit whatever route the frames take and however they are split into calls.
+// One pass over the positions at 12 B per atom-frame.  The amplitudes stay in HBM as double [frames][S][3], series
+// series0[g] + k * n_chains[g] + c for group g, row k, chain c: all chains of a (group, row) are one contiguous range
+// of a frame, which is what mdx_msd_push_device takes (mdx_rouse_device_result hands the buffer over).  Nothing is
+// added with atomics and no sum is split across lanes, so the rows repeat bit for bit whatever route the frames
+// take and however they are split into calls.
 #include "mdx_common.hpp"
-#include "mdx_gyration_device.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_points_device.hpp"
+#include "mdx_rouse_device.hpp"
 #include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 using namespace mdx;
-using namespace mdx_gyr_dev;
+using namespace mdx_rouse_dev;
 using mdx_prof_dev::prof_com_f64_kernel;
 using mdx_prof_dev::prof_unwrap_scan_kernel;
 
 namespace {
 
-constexpr int64_t GYR_SLAB_FRAMES = 32768;                // frames per launch (grid y)
-constexpr int64_t GYR_SCRATCH_BYTES = int64_t(256) << 20; // centres / image counts / per-chain values of one slab
+constexpr int64_t ROUSE_SLAB_FRAMES = 32768;                // frames per launch (grid y)
+constexpr int64_t ROUSE_SCRATCH_BYTES = int64_t(256) << 20; // centres / image counts of one slab
 
 }  // namespace
 
-struct mdx_gyr {
+struct mdx_rouse {
     int dev = 0;
     hipStream_t stream = nullptr;
     int n_groups = 0;
-    int64_t n_points = 0, n_chains = 0, n_units = 0;
+    int64_t n_points = 0, n_series = 0, n_units = 0;
     int64_t frames_seen = 0, row_capacity = 0;
     bool unwrap = false;
     double dims[3] = {0, 0, 0};
     std::vector<double> start;         // [n_points][3]: x_prev before the first frame
-    DeviceBuffer d_units, d_masses, d_chain_mass, d_chain_offsets, d_rows, d_chain_out, d_stage[2], d_index,
-        d_centres, d_images, d_prev, d_image;
+    DeviceBuffer d_units, d_weights, d_rows, d_stage[2], d_index, d_centres, d_images, d_prev, d_image;
     std::vector<int32_t> index_host;   // what d_index holds
     StagePipeline pipe;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
     StreamTimer timer;
 };
 
-// capacity for `more` rows behind the ones seen.  Growing copies the rows and waits for the stream, so the host and
-// file routes ask once per call, before their copy / kernel pipeline starts.
-static int gyr_grow_rows(mdx_gyr *h, int64_t more)
+// capacity for `more` frames behind the ones seen (doubling unless `exact`).  Growing copies the rows and waits for
+// the stream, so the host and file routes ask once per call, before their copy / kernel pipeline starts.
+static int rouse_grow_rows(mdx_rouse *h, int64_t more, bool exact = false)
 {
-    const int64_t row = int64_t(32) * h->n_groups, need = h->frames_seen + more;
+    const int64_t row = int64_t(24) * h->n_series, need = h->frames_seen + more;
     if (more <= 0 || need <= h->row_capacity)
         return MDX_OK;
-    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(64, 2 * h->row_capacity));
+    const int64_t cap = exact ? need : std::max<int64_t>(need, std::max<int64_t>(64, 2 * h->row_capacity));
     DeviceBuffer grown;
     MDX_TRY(grown.ensure(size_t(row * cap)));
     if (h->frames_seen > 0)
@@ -70,21 +70,18 @@ static int gyr_grow_rows(mdx_gyr *h, int64_t more)
 }
 
 template <typename SRC>
-static void gyr_launch(mdx_gyr *h, const SRC *pos, int64_t src_rows, const int *index, int64_t nf, const int *images)
+static void rouse_launch(mdx_rouse *h, const SRC *pos, int64_t src_rows, const int *index, int64_t nf,
+                         const int *images)
 {
-    hipLaunchKernelGGL((gyr_moments_kernel<SRC>), dim3((unsigned)ceil_div(h->n_units, GYR_WAVES), (unsigned)nf),
-                       dim3(GYR_THREADS), 0, h->stream, pos, src_rows, index, (int)h->n_points,
-                       h->d_units.as<GyrUnit>(), (int)h->n_units, (int)h->n_chains, h->d_masses.as<double>(),
-                       h->d_chain_mass.as<double>(), images, h->dims[0], h->dims[1], h->dims[2],
-                       h->d_chain_out.as<double>());
-    hipLaunchKernelGGL(gyr_mean_kernel, dim3((unsigned)h->n_groups, (unsigned)nf), dim3(64), 0, h->stream,
-                       h->d_chain_out.as<double>(), (int)h->n_chains, h->d_chain_offsets.as<int>(), h->n_groups,
-                       h->d_rows.as<double>() + h->frames_seen * h->n_groups * 4);
+    hipLaunchKernelGGL((rouse_project_kernel<SRC>), dim3((unsigned)h->n_units, (unsigned)nf), dim3(ROUSE_THREADS), 0,
+                       h->stream, pos, src_rows, index, (int)h->n_points, h->d_units.as<RouseUnit>(),
+                       h->d_weights.as<double>(), images, h->dims[0], h->dims[1], h->dims[2], h->n_series,
+                       h->d_rows.as<double>() + h->frames_seen * h->n_series * 3);
 }
 
 // image counts of nf frames of points (state carried in d_prev / d_image from call to call)
 template <typename SRC>
-static int gyr_scan(mdx_gyr *h, const SRC *pos, int64_t src_rows, const int *index, int64_t nf)
+static int rouse_scan(mdx_rouse *h, const SRC *pos, int64_t src_rows, const int *index, int64_t nf)
 {
     const int n = (int)h->n_points;
     MDX_TRY(h->d_images.ensure(size_t(12) * n * nf));
@@ -95,8 +92,8 @@ static int gyr_scan(mdx_gyr *h, const SRC *pos, int64_t src_rows, const int *ind
 }
 
 // n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
-static int gyr_accumulate_rows(mdx_gyr *h, const float *d_pos, int64_t src_rows, const int *d_index, int64_t n_rows,
-                               int64_t n_frames)
+static int rouse_accumulate_rows(mdx_rouse *h, const float *d_pos, int64_t src_rows, const int *d_index,
+                                 int64_t n_rows, int64_t n_frames)
 {
     if (n_frames == 0)
         return MDX_OK;
@@ -105,20 +102,19 @@ static int gyr_accumulate_rows(mdx_gyr *h, const float *d_pos, int64_t src_rows,
     MDX_REQUIRE(n_rows == want, "%lld rows given, the groups%s hold %lld", (long long)n_rows,
                 grouped ? " (rows of the grouping)" : "", (long long)want);
     MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
-    MDX_TRY(gyr_grow_rows(h, n_frames));
+    MDX_TRY(rouse_grow_rows(h, n_frames));
     const int64_t n = h->n_points;
     if (h->unwrap && h->frames_seen == 0) {
         // before the first frame x_prev is the starting configuration and the image counts are 0
         MDX_HIP(hipMemcpyAsync(h->d_prev.ptr, h->start.data(), size_t(24) * n, hipMemcpyHostToDevice, h->stream));
         MDX_HIP(hipMemsetAsync(h->d_image.ptr, 0, size_t(12) * n, h->stream));
     }
-    const int64_t scratch = 32 * h->n_chains + (grouped ? 24 * n : 0) + (h->unwrap ? 12 * n : 0);
-    const int64_t slab = std::min(GYR_SLAB_FRAMES, std::max<int64_t>(1, GYR_SCRATCH_BYTES / scratch));
+    const int64_t scratch = std::max<int64_t>(1, (grouped ? 24 * n : 0) + (h->unwrap ? 12 * n : 0));
+    const int64_t slab = std::min(ROUSE_SLAB_FRAMES, std::max<int64_t>(1, ROUSE_SCRATCH_BYTES / scratch));
     hipEvent_t ev = h->timer.begin();
     for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
         const int64_t nf = std::min(slab, n_frames - f0);
         const float *pos = d_pos + f0 * src_rows * 3;
-        MDX_TRY(h->d_chain_out.ensure(size_t(32) * h->n_chains * nf));
         const int *images = nullptr;
         if (grouped) {
             MDX_TRY(h->d_centres.ensure(size_t(24) * n * nf));
@@ -128,16 +124,16 @@ static int gyr_accumulate_rows(mdx_gyr *h, const float *d_pos, int64_t src_rows,
                                h->d_centres.as<double>());
             const double *centres = h->d_centres.as<double>();
             if (h->unwrap) {
-                MDX_TRY(gyr_scan(h, centres, n, nullptr, nf));
+                MDX_TRY(rouse_scan(h, centres, n, nullptr, nf));
                 images = h->d_images.as<int>();
             }
-            gyr_launch(h, centres, n, nullptr, nf, images);
+            rouse_launch(h, centres, n, nullptr, nf, images);
         } else {
             if (h->unwrap) {
-                MDX_TRY(gyr_scan(h, pos, src_rows, d_index, nf));
+                MDX_TRY(rouse_scan(h, pos, src_rows, d_index, nf));
                 images = h->d_images.as<int>();
             }
-            gyr_launch(h, pos, src_rows, d_index, nf, images);
+            rouse_launch(h, pos, src_rows, d_index, nf, images);
         }
         h->frames_seen += nf;
     }
@@ -146,92 +142,76 @@ static int gyr_accumulate_rows(mdx_gyr *h, const float *d_pos, int64_t src_rows,
     return MDX_OK;
 }
 
-// host index -> d_index (kept while it does not change); *out = nullptr when index is NULL
-static int gyr_upload_index(mdx_gyr *h, const int32_t *index, int64_t n_index, int64_t n_atoms, const int **out)
-{
-    return upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, out);
-}
-
 extern "C" {
 
-int mdx_gyr_create(mdx_gyr_t *out, int dev, int n_groups, const int64_t *n_chains, const int64_t *n_monomers,
-                   const double *masses)
+int mdx_rouse_create(mdx_rouse_t *out, int dev, int n_groups, const int64_t *n_chains, const int64_t *n_monomers,
+                     int64_t n_rows, const double *weights)
 {
-    MDX_REQUIRE(out && n_chains && n_monomers && masses, "NULL argument");
+    MDX_REQUIRE(out && n_chains && n_monomers && weights, "NULL argument");
     MDX_REQUIRE(n_groups >= 1 && n_groups <= 4096, "n_groups out of range");
     const int64_t limit = (int64_t(1) << 31) / 3;
-    int64_t n_points = 0, chains = 0;
+    MDX_REQUIRE(n_rows >= 1 && n_rows < limit, "n_rows must be at least 1");
+    int64_t n_points = 0, n_series = 0, n_weights = 0;
     for (int g = 0; g < n_groups; ++g) {
         MDX_REQUIRE(n_chains[g] >= 1 && n_chains[g] < limit, "group %d: n_chains must be at least 1", g);
         MDX_REQUIRE(n_monomers[g] >= 1 && n_monomers[g] < limit, "group %d: n_monomers must be at least 1", g);
         MDX_REQUIRE(n_chains[g] * n_monomers[g] < limit - n_points,
                     "the groups must hold fewer than 2^31 / 3 points");
+        MDX_REQUIRE(n_rows * n_chains[g] < limit - n_series,
+                    "the groups must give fewer than 2^31 / 3 series (n_rows * chains)");
+        MDX_REQUIRE(n_rows * n_monomers[g] < limit, "group %d: n_rows * n_monomers must stay below 2^31 / 3", g);
         n_points += n_chains[g] * n_monomers[g];
-        chains += n_chains[g];
+        n_series += n_rows * n_chains[g];
+        n_weights += n_rows * n_monomers[g];
     }
-    // the units of the moment kernel, the chains' masses (sequential sums) and the groups' chain ranges
-    std::vector<GyrUnit> units;
-    std::vector<double> chain_mass;
-    std::vector<int32_t> chain_offsets{0};
-    chain_mass.reserve((size_t)chains);
-    int64_t point = 0;
+    for (int64_t i = 0; i < n_weights; ++i)
+        MDX_REQUIRE(std::isfinite(weights[i]), "weights must be finite");
+    // the units of the kernel and the weights transposed to wT[g][n][k]: lanes hold consecutive rows k
+    std::vector<RouseUnit> units;
+    std::vector<double> wT((size_t)n_weights);
+    int64_t point = 0, series = 0, w0 = 0;
     for (int g = 0; g < n_groups; ++g) {
         const int64_t M = n_chains[g], N = n_monomers[g];
-        int shift = 6;
-        if (N <= 32)
-            for (shift = 0; (int64_t(1) << shift) < N; ++shift) {}
-        const int64_t per_unit = int64_t(64) >> shift;
-        for (int64_t c = 0; c < M; ++c) {
-            double m = 0.0;
-            for (int64_t j = 0; j < N; ++j) {
-                const double mj = masses[point + c * N + j];
-                MDX_REQUIRE(mj >= 0.0 && std::isfinite(mj), "masses must be finite and not negative");
-                m += mj;
-            }
-            MDX_REQUIRE(m > 0.0, "chain %lld of group %d has no mass", (long long)c, g);
-            chain_mass.push_back(m);
-        }
+        for (int64_t k = 0; k < n_rows; ++k)
+            for (int64_t n = 0; n < N; ++n)
+                wT[size_t(w0 + n * n_rows + k)] = weights[w0 + k * N + n];
+        const int64_t per_unit = std::max<int64_t>(1, ROUSE_STAGE / N);
         for (int64_t c = 0; c < M; c += per_unit)
-            units.push_back(GyrUnit{int(point + c * N), int(chain_offsets.back() + c),
-                                    int(std::min(per_unit, M - c)), int(N), shift, {0, 0, 0}});
+            units.push_back(RouseUnit{int(point + c * N), int(series), int(c), int(std::min(per_unit, M - c)), int(N),
+                                      int(n_rows), int(M), 0, w0});
         point += M * N;
-        chain_offsets.push_back(int32_t(chain_offsets.back() + M));
+        series += n_rows * M;
+        w0 += n_rows * N;
     }
     MDX_TRY(set_device(dev));
-    mdx_gyr *h = new mdx_gyr();
+    mdx_rouse *h = new mdx_rouse();
     h->dev = dev;
     h->n_groups = n_groups;
     h->n_points = n_points;
-    h->n_chains = chains;
+    h->n_series = n_series;
     h->n_units = (int64_t)units.size();
     int rc = MDX_OK;
     do {
         if ((rc = stream_acquire(&h->stream)) != MDX_OK) break;
         h->timer.stream = h->stream;
-        if ((rc = h->d_units.ensure(sizeof(GyrUnit) * units.size())) != MDX_OK) break;
-        if ((rc = h->d_masses.ensure(size_t(8) * n_points)) != MDX_OK) break;
-        if ((rc = h->d_chain_mass.ensure(size_t(8) * chains)) != MDX_OK) break;
-        if ((rc = h->d_chain_offsets.ensure(size_t(4) * (n_groups + 1))) != MDX_OK) break;
-        if (hipMemcpy(h->d_units.ptr, units.data(), sizeof(GyrUnit) * units.size(), hipMemcpyHostToDevice) !=
+        if ((rc = h->d_units.ensure(sizeof(RouseUnit) * units.size())) != MDX_OK) break;
+        if ((rc = h->d_weights.ensure(size_t(8) * n_weights)) != MDX_OK) break;
+        if (hipMemcpy(h->d_units.ptr, units.data(), sizeof(RouseUnit) * units.size(), hipMemcpyHostToDevice) !=
                 hipSuccess ||
-            hipMemcpy(h->d_masses.ptr, masses, size_t(8) * n_points, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->d_chain_mass.ptr, chain_mass.data(), size_t(8) * chains, hipMemcpyHostToDevice) !=
-                hipSuccess ||
-            hipMemcpy(h->d_chain_offsets.ptr, chain_offsets.data(), size_t(4) * (n_groups + 1),
-                      hipMemcpyHostToDevice) != hipSuccess) {
+            hipMemcpy(h->d_weights.ptr, wT.data(), size_t(8) * n_weights, hipMemcpyHostToDevice) != hipSuccess) {
             rc = fail(MDX_ERR_HIP, "upload failed");
             break;
         }
     } while (0);
     if (rc != MDX_OK) {
-        mdx_gyr_destroy(h);
+        mdx_rouse_destroy(h);
         return rc;
     }
     *out = h;
     return MDX_OK;
 }
 
-int mdx_gyr_destroy(mdx_gyr_t h)
+int mdx_rouse_destroy(mdx_rouse_t h)
 {
     if (!h)
         return MDX_OK;
@@ -240,9 +220,8 @@ int mdx_gyr_destroy(mdx_gyr_t h)
         (void)hipStreamSynchronize(h->stream);
     h->timer.destroy();
     h->pipe.destroy();      // waits for its copy stream
-    for (DeviceBuffer *b : {&h->d_units, &h->d_masses, &h->d_chain_mass, &h->d_chain_offsets, &h->d_rows,
-                            &h->d_chain_out, &h->d_stage[0], &h->d_stage[1], &h->d_index, &h->d_centres,
-                            &h->d_images, &h->d_prev, &h->d_image})
+    for (DeviceBuffer *b : {&h->d_units, &h->d_weights, &h->d_rows, &h->d_stage[0], &h->d_stage[1], &h->d_index,
+                            &h->d_centres, &h->d_images, &h->d_prev, &h->d_image})
         b->recycle();
     h->mol.recycle();
     if (h->stream)
@@ -251,7 +230,7 @@ int mdx_gyr_destroy(mdx_gyr_t h)
     return MDX_OK;
 }
 
-int mdx_gyr_reset(mdx_gyr_t h)
+int mdx_rouse_reset(mdx_rouse_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(set_device(h->dev));
@@ -261,12 +240,20 @@ int mdx_gyr_reset(mdx_gyr_t h)
     return MDX_OK;
 }
 
-int mdx_gyr_set_grouping(mdx_gyr_t h, int64_t n_molecules, const int64_t *offsets, const double *masses)
+int mdx_rouse_reserve(mdx_rouse_t h, int64_t n_frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    MDX_REQUIRE(n_frames >= 0, "bad size");
+    MDX_TRY(set_device(h->dev));
+    return rouse_grow_rows(h, n_frames - h->frames_seen, true);
+}
+
+int mdx_rouse_set_grouping(mdx_rouse_t h, int64_t n_molecules, const int64_t *offsets, const double *masses)
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(set_device(h->dev));
     MDX_HIP(hipStreamSynchronize(h->stream));
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_gyr_set_grouping must be called before the first frame");
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_rouse_set_grouping must be called before the first frame");
     MDX_REQUIRE(n_molecules <= 0 || n_molecules == h->n_points, "%lld molecules given, the groups hold %lld points",
                 (long long)n_molecules, (long long)h->n_points);
     MDX_REQUIRE(n_molecules <= 0 || (offsets && offsets[n_molecules] < (int64_t(1) << 31) / 3),
@@ -274,12 +261,12 @@ int mdx_gyr_set_grouping(mdx_gyr_t h, int64_t n_molecules, const int64_t *offset
     return h->mol.set(n_molecules, offsets, masses);
 }
 
-int mdx_gyr_set_unwrap(mdx_gyr_t h, const double *dims, const double *start)
+int mdx_rouse_set_unwrap(mdx_rouse_t h, const double *dims, const double *start)
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(set_device(h->dev));
     MDX_HIP(hipStreamSynchronize(h->stream));
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_gyr_set_unwrap must be called before the first frame");
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_rouse_set_unwrap must be called before the first frame");
     if (!dims) {
         h->unwrap = false;
         return MDX_OK;
@@ -296,18 +283,18 @@ int mdx_gyr_set_unwrap(mdx_gyr_t h, const double *dims, const double *start)
     return MDX_OK;
 }
 
-int mdx_gyr_accumulate_device(mdx_gyr_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
+int mdx_rouse_accumulate_device(mdx_rouse_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                                const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     MDX_TRY(set_device(h->dev));
     const int *d_index = nullptr;
-    MDX_TRY(gyr_upload_index(h, index, n_index, n_atoms, &d_index));
-    return gyr_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    return rouse_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
 }
 
-int mdx_gyr_accumulate(mdx_gyr_t h, const float *pos, int64_t n, int64_t n_frames)
+int mdx_rouse_accumulate(mdx_rouse_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
@@ -315,7 +302,7 @@ int mdx_gyr_accumulate(mdx_gyr_t h, const float *pos, int64_t n, int64_t n_frame
     // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
     const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1),
                                            std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
-    MDX_TRY(gyr_grow_rows(h, n_frames));
+    MDX_TRY(rouse_grow_rows(h, n_frames));
     return h->pipe.run(
         h->stream, n_frames, slab,
         [&](int b, int64_t f0, int64_t nf) -> int {
@@ -324,14 +311,14 @@ int mdx_gyr_accumulate(mdx_gyr_t h, const float *pos, int64_t n, int64_t n_frame
                                                 pos + f0 * n * 3, size_t(12) * n * nf);
         },
         [&](int b, int64_t, int64_t nf) -> int {
-            return gyr_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+            return rouse_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
         });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
 // concatenated groups (rows of the grouping when one is set), or NULL for the file's first n_index particles.
-int mdx_gyr_accumulate_traj(mdx_gyr_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
+int mdx_rouse_accumulate_traj(mdx_rouse_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                              const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
@@ -343,10 +330,11 @@ int mdx_gyr_accumulate_traj(mdx_gyr_t h, mdx_traj_t traj, const int64_t *frames,
         return MDX_OK;
     MDX_TRY(h->pipe.ensure());
     const int *d_index = nullptr;
-    MDX_TRY(gyr_upload_index(h, index, n_index, t->n_atoms, &d_index));
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
+                                  &d_index));
     const int64_t slab = std::min<int64_t>(
         n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
-    MDX_TRY(gyr_grow_rows(h, n_frames));
+    MDX_TRY(rouse_grow_rows(h, n_frames));
     return h->pipe.run(
         h->stream, n_frames, slab,
         [&](int b, int64_t f0, int64_t nf) -> int {
@@ -355,11 +343,11 @@ int mdx_gyr_accumulate_traj(mdx_gyr_t h, mdx_traj_t traj, const int64_t *frames,
             return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
         },
         [&](int b, int64_t, int64_t nf) -> int {
-            return gyr_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+            return rouse_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
         });
 }
 
-int mdx_gyr_synchronize(mdx_gyr_t h)
+int mdx_rouse_synchronize(mdx_rouse_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(set_device(h->dev));
@@ -367,25 +355,31 @@ int mdx_gyr_synchronize(mdx_gyr_t h)
     return MDX_OK;
 }
 
-int mdx_gyr_result(mdx_gyr_t h, double *out)
+int mdx_rouse_result(mdx_rouse_t h, double *out)
 {
     MDX_REQUIRE(h && out, "NULL argument");
     MDX_TRY(set_device(h->dev));
     MDX_HIP(hipStreamSynchronize(h->stream));
     h->timer.collect();
-    const int64_t F = h->frames_seen, G = h->n_groups;
-    if (F == 0)
+    if (h->frames_seen == 0)
         return MDX_OK;
-    std::vector<double> rows(size_t(F * G * 4));
-    MDX_HIP(hipMemcpy(rows.data(), h->d_rows.ptr, size_t(32) * F * G, hipMemcpyDeviceToHost));
-    for (int64_t g = 0; g < G; ++g)
-        for (int64_t f = 0; f < F; ++f)
-            for (int k = 0; k < 4; ++k)
-                out[(g * F + f) * 4 + k] = rows[size_t((f * G + g) * 4 + k)];
+    MDX_HIP(hipMemcpy(out, h->d_rows.ptr, size_t(24) * h->n_series * h->frames_seen, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
-int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *frames)
+int mdx_rouse_device_result(mdx_rouse_t h, const double **d_ptr, int64_t *n_frames, int64_t *n_series)
+{
+    MDX_REQUIRE(h && d_ptr, "NULL argument");
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.collect();
+    *d_ptr = h->d_rows.as<double>();
+    if (n_frames) *n_frames = h->frames_seen;
+    if (n_series) *n_series = h->n_series;
+    return MDX_OK;
+}
+
+int mdx_rouse_stats(mdx_rouse_t h, int64_t *launches, double *kernel_ms, int64_t *frames)
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(set_device(h->dev));
@@ -397,7 +391,7 @@ int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_gyr_enable_timing(mdx_gyr_t h, int on)
+int mdx_rouse_enable_timing(mdx_rouse_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
     h->timer.enabled = on != 0;
