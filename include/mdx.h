@@ -614,6 +614,53 @@ int mdx_dip_result(mdx_dip_t h, double *out);
 int mdx_dip_stats(mdx_dip_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_dip_enable_timing(mdx_dip_t h, int on);
 
+/* ---- self van Hove function and displacement moments -----------------------------------------------------------------
+ * Rows arrive in the order of the concatenated groups: group g holds n_points[g] consecutive points (a group may be
+ * empty, all of them together may not).  Analysed frames are numbered f = 0, 1, ... in the order fed; lags: strictly
+ * increasing, non-negative frame offsets (0 allowed).  Per point, lag k and frame f >= lags[k], in float64 with
+ * separate multiply and add (float32 coordinates are widened before any arithmetic):
+ *     x(f) = r(f) + image(f) * L (image = 0 without unwrap);  d = x(f) - x(f - lag), +0.0 for a dropped component;
+ *     r2 = (dx*dx + dy*dy) + dz*dz;  r = sqrt(r2);  counts[k][g][b] += 1 where edges[b] <= r < edges[b+1] (the last
+ *     bin closed on the right; r outside the edges or not finite is not counted);  m2[k][p] += r2, m4[k][p] += r2*r2.
+ * edges: float64 [n_bins + 1], the caller's numpy.linspace(r_min, r_max, n_bins + 1) as for mdx_rdf_create; the counts
+ * then equal numpy.histogram(r, n_bins, (r_min, r_max)) count for count.  zero_dims: bit k drops component k, as for
+ * mdx_msd_push.  The accumulator of a (lag, point) receives its terms in frame order and a group's moments add the
+ * accumulators of its points in row order (csrc/mdx_vanhove_device.hpp); no floating-point atomics are used, so
+ * counts and moments are bit-identical across the three input routes, across any split of the frames into calls or
+ * slabs, and after a reset.  The engine keeps max(lags) + one slab of float64 frames in HBM (MDX_ERR_OUT_OF_MEMORY
+ * when that does not fit).  A handle touches its device with the first frame: mdx_vh_create and every argument error
+ * (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_vh *mdx_vh_t;
+int mdx_vh_create(mdx_vh_t *out, int dev, int n_groups, const int64_t *n_points, int n_bins, const double *edges,
+                  int n_lags, const int64_t *lags, int zero_dims);
+int mdx_vh_destroy(mdx_vh_t h);
+/* Forgets the frames seen, the history and the unwrap state and zeroes counts and moments. */
+int mdx_vh_reset(mdx_vh_t h);
+/* The reference's global unwrap per point coordinate, as mdx_dip_set_unwrap; the first analysed frame is its own
+ * start with image 0 (a displacement does not depend on the starting image).  dims: float64 [3] box lengths, or NULL:
+ * off.  Only before the first frame. */
+int mdx_vh_set_unwrap(mdx_vh_t h, const double *dims);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history), as
+ * mdx_dip_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
+int mdx_vh_set_slab_frames(mdx_vh_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring. */
+int mdx_vh_accumulate(mdx_vh_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_vh_synchronize). */
+int mdx_vh_accumulate_device(mdx_vh_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                             const int32_t *index, int64_t n_index);
+int mdx_vh_accumulate_traj(mdx_vh_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                           const int32_t *index, int64_t n_index);
+int mdx_vh_synchronize(mdx_vh_t h);
+/* counts: int64 [n_lags][n_groups][n_bins]; moments: float64 [n_lags][n_groups][2] = sum r2, sum r4 over the group's
+ * points and every frame pair of the lag; may be NULL. */
+int mdx_vh_result(mdx_vh_t h, int64_t *counts, double *moments);
+/* out: float64 [n_lags][n_points][2]: the accumulators of every point. */
+int mdx_vh_point_moments(mdx_vh_t h, double *out);
+/* evaluations: displacements formed so far (frame pairs x points, summed over the lags). */
+int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations);
+int mdx_vh_enable_timing(mdx_vh_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

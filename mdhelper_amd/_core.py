@@ -869,6 +869,99 @@ class DipoleEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
 
 
+class VanHoveEngine(_Engine):
+    """``mdx_vh_*``: per lag and group the histogram of the displacement magnitudes ``|x(f) - x(f - lag)|`` and the
+    sums of their second and fourth powers, in float64.  The device is first touched by the first frame, so the
+    argument errors (``ValueError``) need none."""
+
+    _destroy = "mdx_vh_destroy"
+    TILE = 64           # points per tile: a tile never spans two groups (VH_TILE of csrc/mdx_vanhove_device.hpp)
+
+    def __init__(self, n_points, edges, lags, *, zero_dims=0, dev=0, timing=False):
+        self.n_per_group = np.ascontiguousarray(np.atleast_1d(n_points), dtype=np.int64)
+        if self.n_per_group.ndim != 1 or len(self.n_per_group) == 0:
+            raise ValueError("n_points must hold one entry per group.")
+        self.n_groups = len(self.n_per_group)
+        self.n_points = int(self.n_per_group.sum())
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if self.edges.ndim != 1 or len(self.edges) < 2:
+            raise ValueError("edges must hold n_bins + 1 >= 2 bin edges.")
+        self.n_bins = len(self.edges) - 1
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        h = c_void_p()
+        check(lib().mdx_vh_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), self.n_bins,
+                                  _ptr(self.edges), self.n_lags, _ptr(self.lags), int(zero_dims)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_vh_enable_timing(h, 1))
+
+    def set_unwrap(self, dims):
+        """The reference's global unwrap from frame to frame with the box lengths ``dims``; the first frame is its
+        own start.  ``dims=None`` switches it off.  Only before the first frame."""
+        if dims is None:
+            check(lib().mdx_vh_set_unwrap(self.handle, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        check(lib().mdx_vh_set_unwrap(self.handle, _ptr(d)))
+
+    def set_slab_frames(self, frames):
+        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
+        before the first frame."""
+        check(lib().mdx_vh_set_slab_frames(self.handle, int(frames)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows in concatenated-group order."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_vh_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM (``index``: rows of a frame in incoming order).  Asynchronous on the engine's stream:
+        ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_vh_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                             0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_vh_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                           0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_vh_synchronize(self.handle))
+
+    def result(self):
+        """``(counts int64 [n_lags, G, n_bins], moments float64 [n_lags, G, 2])``: the moments are the sums of
+        ``r^2`` and ``r^4`` over the group's points and every frame pair of the lag."""
+        counts = np.zeros((self.n_lags, self.n_groups, self.n_bins), dtype=np.int64)
+        moments = np.zeros((self.n_lags, self.n_groups, 2), dtype=np.float64)
+        check(lib().mdx_vh_result(self.handle, _ptr(counts), _ptr(moments)))
+        return counts, moments
+
+    def point_moments(self):
+        """float64 ``[n_lags, n_points, 2]``: every point's own sums of ``r^2`` and ``r^4``."""
+        out = np.zeros((self.n_lags, self.n_points, 2), dtype=np.float64)
+        check(lib().mdx_vh_point_moments(self.handle, _ptr(out)))
+        return out
+
+    def reset(self):
+        check(lib().mdx_vh_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames, ev = c_int64(), c_double(), c_int64(), c_int64()
+        check(lib().mdx_vh_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

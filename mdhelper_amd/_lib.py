@@ -201,6 +201,20 @@ _SIGNATURES = {
     "mdx_dip_result": (c_int, [_vp, _vp]),
     "mdx_dip_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_dip_enable_timing": (c_int, [_vp, c_int]),
+    # self van Hove function and displacement moments
+    "mdx_vh_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int, _vp, c_int, _vp, c_int]),
+    "mdx_vh_destroy": (c_int, [_vp]),
+    "mdx_vh_reset": (c_int, [_vp]),
+    "mdx_vh_set_unwrap": (c_int, [_vp, _vp]),
+    "mdx_vh_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_vh_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_vh_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_vh_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_vh_synchronize": (c_int, [_vp]),
+    "mdx_vh_result": (c_int, [_vp, _vp, _vp]),
+    "mdx_vh_point_moments": (c_int, [_vp, _vp]),
+    "mdx_vh_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_vh_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,0 +1,230 @@
+"""
+Real-space single-particle dynamics: ``VanHove`` — the self part of the van Hove function
+``G_s(r, t)``, the distribution of displacement magnitudes after a lag and the non-Gaussian parameter —
+and ``calculate_non_gaussian_parameter``.
+
+The reference package has no counterpart; this sits next to ``IntermediateScatteringFunction(incoherent=True)``
+(``F_s(q, t)``, the Fourier transform of ``G_s``) and the mean squared displacements of the correlation
+engine (its second moment).
+
+Where the work goes: whole blocks of frames go to the van Hove engine (``mdx_vh_*``), which keeps a history of
+widened (and unwrapped) float64 points in HBM, bins ``|x(f) - x(f - lag)|`` for every point, lag and frame into
+integer histograms and adds ``r^2`` and ``r^4`` per point in frame order.  Counts equal ``numpy.histogram``
+count for count; the moments have a fixed summation order (csrc/mdx_vanhove_device.hpp).
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from .. import _core, _lib
+from ..algorithm.unit import strip_unit
+from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, all_particles, block_frames, block_source,
+                   frame_blocks, has_frame_blocks)
+
+
+def calculate_non_gaussian_parameter(m2, m4, n_dims: int = 3):
+    r"""
+    Non-Gaussian parameter of a displacement distribution in ``n_dims`` dimensions,
+
+    .. math:: \alpha_2=\frac{d\,\langle\Delta r^4\rangle}{(d+2)\,\langle\Delta r^2\rangle^2}-1
+
+    (``3 <dr^4> / (5 <dr^2>^2) - 1`` in three dimensions), which is zero for a Gaussian distribution.
+
+    m2, m4 : float or array-like — the mean second and fourth powers of the displacement magnitude
+    n_dims : int — the number of dimensions the displacements have
+
+    Returns NaN where ``m2 == 0`` (no displacement, or no data), without a warning.
+    """
+    m2 = np.asarray(m2, dtype=float)
+    m4 = np.asarray(m4, dtype=float)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = n_dims * m4 / ((n_dims + 2) * m2 ** 2) - 1
+    out = np.where(m2 == 0, np.nan, out)
+    return float(out) if out.ndim == 0 else out
+
+
+class VanHove(DynamicAnalysisBase):
+    r"""
+    Self part of the van Hove function and the moments of the displacements,
+
+    .. math:: G_s(r,t)=\frac1N\Big\langle\sum_i\delta\big(\mathbf r-[\mathbf r_i(t_0+t)-\mathbf r_i(t_0)]\big)
+              \Big\rangle_{t_0},\qquad
+              \alpha_2(t)=\frac{3\langle\Delta r^4\rangle}{5\langle\Delta r^2\rangle^2}-1
+
+    per group, averaged over every time origin ``t_0`` of the analysed frames.
+
+    Parameters
+    ----------
+    groups : AtomGroup or sequence of AtomGroups
+    n_bins : int — number of histogram bins of ``|dr|``
+    range : (float, float) — ``(r_min, r_max)`` of the histogram (Å), ``r_min < r_max``
+    lags : array-like of int, keyword-only — lag times in frames of the analysed selection, strictly increasing,
+        non-negative
+    n_lags : int, keyword-only — shorthand for ``lags=arange(n_lags)``; with neither, every analysed frame is a lag
+    dt : float, keyword-only — time between trajectory frames (ps); defaults to the trajectory's
+    dimensions : array-like ``(3,)``, keyword-only — box lengths (Å) for ``unwrap``; defaults to the universe's
+    drop_axis : {0, 1, 2, "x", "y", "z"}, keyword-only — a component that takes no part (slabs, 2-D systems)
+    unwrap : bool, keyword-only — follow the particles across the periodic boundaries from frame to frame (a step
+        of at least half a box length between analysed frames counts as a crossing); for wrapped trajectories
+    verbose : bool
+    device : keyword-only — the HIP device
+
+    Results
+    -------
+    ``results.edges`` ``[N_b + 1]``, ``results.bins`` ``[N_b]`` (bin centres, Å), ``results.times`` ``[N_t]``
+    (ps), ``results.counts`` ``[N_t, N_g, N_b]`` (int64), ``results.probability`` — the density of ``|dr|``
+    (Å⁻¹), ``counts / (N_g n_origins width)``: a row integrates to the share of displacements inside the range —
+    ``results.vanhove`` — ``G_s(r, t)``, ``counts / (N_g n_origins shell)`` with the volume of the spherical
+    shell of the bin (Å⁻³; the area of the ring, Å⁻², with ``drop_axis``) — ``results.msd`` ``[N_t, N_g]``
+    (Å²), ``results.alpha2`` ``[N_t, N_g]`` and ``results.units``.  ``n_origins = n_frames - lag``; a lag without
+    an origin has zero counts and NaN in the normalised results.
+
+    Limits: more than one rank raises ``ValueError`` (every lag needs every frame, and sharding the points would
+    change the summation order); molecule centres are not supported; the frames must be evenly spaced and go
+    forward in time; there is no CPU fallback: without a HIP device ``run()`` raises ``RuntimeError``.
+    """
+
+    def __init__(self, groups, n_bins: int = 201, range: tuple = (0.0, 15.0), *, lags=None, n_lags: int = None,
+                 dt=None, dimensions=None, drop_axis=None, unwrap: bool = False, verbose: bool = True,
+                 **kwargs) -> None:
+        self._groups = [groups] if hasattr(groups, "universe") else list(groups)
+        self._n_groups = len(self._groups)
+        self.universe = self._groups[0].universe
+        super().__init__(self.universe.trajectory, False, verbose, **kwargs)
+        if self._comm.world_size > 1:
+            raise ValueError("VanHove runs on one rank: every lag needs every frame, and sharding the points "
+                             "would change the order of the sums.")
+
+        self._n_bins = int(n_bins)
+        if self._n_bins < 1:
+            raise ValueError("'n_bins' must be at least 1.")
+        r_min, r_max = (float(x) for x in strip_unit(range, "angstrom")[0])
+        if not (np.isfinite(r_min) and np.isfinite(r_max) and r_min < r_max):
+            raise ValueError("'range' must be an increasing pair of finite numbers.")
+        self._range = (r_min, r_max)
+
+        if lags is not None and n_lags is not None:
+            raise ValueError("'lags' and 'n_lags' cannot both be given.")
+        if n_lags is not None:
+            if int(n_lags) < 1:
+                raise ValueError("'n_lags' must be at least 1.")
+            lags = np.arange(int(n_lags))
+        if lags is not None:
+            lags = np.atleast_1d(np.asarray(lags))
+            if lags.ndim != 1 or len(lags) == 0 or not np.issubdtype(lags.dtype, np.integer):
+                raise ValueError("'lags' must be a one-dimensional array of integers.")
+            if lags[0] < 0 or np.any(np.diff(lags) <= 0):
+                raise ValueError("'lags' must be non-negative and strictly increasing.")
+            lags = lags.astype(np.int64)
+        self._lags = lags
+
+        self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
+        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
+        if self._drop_axis not in {0, 1, 2, None}:
+            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
+                             "and 2 or 'z'.")
+        if dimensions is not None:
+            if len(dimensions) != 3:
+                raise ValueError("'dimensions' must have length 3.")
+            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
+        elif self.universe.dimensions is not None:
+            self._dimensions = np.asarray(self.universe.dimensions[:3], dtype=float)
+        else:
+            self._dimensions = None
+        if unwrap and self._dimensions is None:
+            raise ValueError("unwrap=True needs the box lengths: no system dimensions found or provided.")
+        self._unwrap = unwrap
+
+        self._Ns = np.fromiter((g.n_atoms for g in self._groups), dtype=int, count=self._n_groups)
+        self._N = int(self._Ns.sum())
+        self._verbose = verbose
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        st = self._sliced_trajectory
+        if hasattr(st, "frames"):
+            df = np.diff(st.frames)
+            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
+                raise ValueError("The selected frames must be evenly spaced and proceed "
+                                 "forward in time.")
+            df = df[0] if len(df) else 1
+        else:
+            if st.step is not None and st.step <= 0:
+                raise ValueError("The analysis must proceed forward in time.")
+            df = st.step if st.step is not None else 1
+        lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
+        self._lags_run = lags
+        self._index = np.concatenate([np.asarray(g.indices) for g in self._groups])
+        edges = np.linspace(*self._range, self._n_bins + 1)
+        self.results.edges = edges
+        self.results.bins = (edges[:-1] + edges[1:]) / 2
+        self.results.times = lags * df * self._dt
+        self.results.units = {"results.bins": "angstrom", "results.edges": "angstrom",
+                              "results.times": "picosecond", "results.probability": "angstrom^-1",
+                              "results.vanhove": "angstrom^-2" if self._drop_axis is not None else "angstrom^-3",
+                              "results.msd": "angstrom^2"}
+        _lib.require_device(self._device)
+        # lags without an origin never meet a frame pair: the engine gets the others
+        self._live = lags < self.n_frames
+        self._engine = None
+        if self._live.any():
+            self._engine = _core.VanHoveEngine(
+                self._Ns, edges, lags[self._live],
+                zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis, dev=self._device)
+            if self._unwrap:
+                self._engine.set_unwrap(self._dimensions)
+        self._batch = FrameBatcher(len(self._index),
+                                   lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
+                                   with_box=False)
+
+    def _single_frame(self) -> None:
+        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
+
+    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory
+    # file, from float32 frames in HBM (read where they lie) or from host memory
+    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
+        traj = self._trajectory
+        if not has_frame_blocks(traj):
+            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
+                               **kwargs)
+        mine = self._batched_frames(start, stop, step, frames, shard=False)
+        index = self._index
+        whole = all_particles(index, traj.n_atoms)
+        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
+                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
+        for sel in frame_blocks(mine, size):
+            if self._engine is None:
+                break
+            route, src = block_source(traj, sel, True)
+            if route == "file":
+                self._engine.accumulate_traj(src, sel, None if whole else index)
+            elif route == "hbm":
+                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
+            else:
+                self._engine.accumulate(src if whole else src[:, index])
+        self._conclude()
+        return self
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        n_t = len(self._lags_run)
+        counts = np.zeros((n_t, self._n_groups, self._n_bins), dtype=np.int64)
+        moments = np.zeros((n_t, self._n_groups, 2))
+        if self._engine is not None:
+            counts[self._live], moments[self._live] = self._engine.result()
+            self._engine.close()
+        edges = self.results.edges
+        n_dims = 3 if self._drop_axis is None else 2
+        if n_dims == 3:
+            shell = 4 * np.pi / 3 * (edges[1:] ** 3 - edges[:-1] ** 3)
+        else:
+            shell = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+        pairs = (np.maximum(self.n_frames - self._lags_run, 0)[:, None] * self._Ns[None, :]).astype(float)
+        pairs[pairs == 0] = np.nan          # no origin (or an empty group): NaN, without a warning
+        self.results.counts = counts
+        self.results.probability = counts / (pairs[:, :, None] * np.diff(edges))
+        self.results.vanhove = counts / (pairs[:, :, None] * shell)
+        self.results.msd = moments[:, :, 0] / pairs
+        self.results.alpha2 = calculate_non_gaussian_parameter(self.results.msd, moments[:, :, 1] / pairs, n_dims)

@@ -1,0 +1,400 @@
+// mdx_vanhove.hip — self van Hove function and displacement moments on gfx950 (MI355X).
+//
+// Per lag and group the histogram of the displacement magnitudes |x(f) - x(f - lag)| of every point and frame, and
+// per lag and point the sums of their second and fourth powers, from which the class forms G_s(r, t), the mean
+// squared displacement and the non-Gaussian parameter.  Contract, kernel shape and summation order:
+// mdx_vanhove_device.hpp; this unit is compiled with contraction off and spells its float64 operations out.
+//
+// The widened (and unwrapped) points go into a ring of max(lags) + slab frames in HBM, so that a lag reaches back
+// across slabs and calls; counts are integers, the moments have one accumulator per (lag, point) that receives its
+// terms in frame order.  Nothing is added with floating-point atomics, so counts and moments repeat bit for bit
+// whatever route the frames take and however they are split into calls or slabs.
+//
+// A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
+#include "mdx_common.hpp"
+#include "mdx_internal.hpp"
+#include "mdx_traj.hpp"
+#include "mdx_vanhove_device.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace mdx;
+using namespace mdx_vh_dev;
+
+namespace {
+
+constexpr int64_t VH_HISTORY_BYTES = int64_t(256) << 20;    // what the frames of a default slab take in the ring
+
+}  // namespace
+
+struct mdx_vh {
+    int dev = 0;
+    bool ready = false;                 // the device side exists
+    hipStream_t stream = nullptr;
+    int n_groups = 0, n_bins = 0, n_lags = 0, keep = 7;
+    int64_t n_points = 0, max_lag = 0;
+    int64_t frames_seen = 0, slab_frames = 0, evaluations = 0;      // slab_frames: 0 = the default
+    int64_t cap = 0;                    // frames the ring holds
+    bool unwrap = false;
+    double dims[3] = {0, 0, 0};
+    double inv_width = 0.0;
+    std::vector<VhTile> tiles;
+    std::vector<int64_t> offsets, lags;
+    std::vector<double> edges;
+    DeviceBuffer d_tiles, d_offsets, d_lags, d_edges, d_counts, d_acc, d_moments, d_hist, d_prev, d_image,
+        d_stage[2], d_index;
+    std::vector<int32_t> index_host;    // what d_index holds
+    StagePipeline pipe;
+    StreamTimer timer;
+};
+
+static int64_t vh_slab(const mdx_vh *h)
+{
+    if (h->slab_frames > 0)
+        return h->slab_frames;
+    return std::min(VH_SLAB_MAX, std::max<int64_t>(1, VH_HISTORY_BYTES / (24 * h->n_points)));
+}
+
+static int vh_zero(mdx_vh *h)
+{
+    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->n_lags * h->n_groups * h->n_bins, h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_acc.ptr, 0, size_t(16) * h->n_lags * h->n_points, h->stream));
+    return MDX_OK;
+}
+
+// the device side of the handle: stream, tables, counters and accumulators
+static int vh_ensure_device(mdx_vh *h)
+{
+    MDX_TRY(set_device(h->dev));
+    if (h->ready)
+        return MDX_OK;
+    if (!h->stream) {
+        MDX_TRY(stream_acquire(&h->stream));
+        h->timer.stream = h->stream;
+    }
+    const int64_t n = h->n_points;
+    MDX_TRY(h->d_tiles.ensure(sizeof(VhTile) * h->tiles.size()));
+    MDX_TRY(h->d_offsets.ensure(size_t(8) * (h->n_groups + 1)));
+    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
+    MDX_TRY(h->d_edges.ensure(size_t(8) * (h->n_bins + 1)));
+    MDX_TRY(h->d_counts.ensure(size_t(8) * h->n_lags * h->n_groups * h->n_bins));
+    MDX_TRY(h->d_acc.ensure(size_t(16) * h->n_lags * n));
+    MDX_TRY(h->d_moments.ensure(size_t(16) * h->n_lags * h->n_groups));
+    MDX_TRY(h->d_prev.ensure(size_t(24) * n));
+    MDX_TRY(h->d_image.ensure(size_t(12) * n));
+    MDX_HIP(hipMemcpy(h->d_tiles.ptr, h->tiles.data(), sizeof(VhTile) * h->tiles.size(), hipMemcpyHostToDevice));
+    MDX_HIP(hipMemcpy(h->d_offsets.ptr, h->offsets.data(), size_t(8) * (h->n_groups + 1), hipMemcpyHostToDevice));
+    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
+    MDX_HIP(hipMemcpy(h->d_edges.ptr, h->edges.data(), size_t(8) * (h->n_bins + 1), hipMemcpyHostToDevice));
+    MDX_TRY(vh_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->ready = true;
+    return MDX_OK;
+}
+
+// The ring, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.  Nothing is
+// in flight then (a reset waits for the stream), so growing it loses nothing.
+static int vh_ensure_history(mdx_vh *h)
+{
+    if (h->frames_seen > 0)
+        return MDX_OK;
+    const int64_t cap = h->max_lag + vh_slab(h);
+    MDX_REQUIRE(cap < (int64_t(1) << 40) / (24 * h->n_points),
+                "a history of %lld frames of %lld points is too large", (long long)cap, (long long)h->n_points);
+    MDX_TRY(h->d_hist.ensure(size_t(24) * h->n_points * cap));
+    h->cap = cap;
+    return MDX_OK;
+}
+
+// n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
+static int vh_accumulate_rows(mdx_vh *h, const float *d_pos, int64_t src_rows, const int *d_index, int64_t n_rows,
+                              int64_t n_frames)
+{
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_REQUIRE(n_rows == h->n_points, "%lld rows given, the groups hold %lld", (long long)n_rows,
+                (long long)h->n_points);
+    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
+    const int n = (int)h->n_points;
+    const int64_t slab = std::min(vh_slab(h), h->cap - h->max_lag);
+    const bool lds = h->n_bins <= VH_LDS_BINS;
+    const size_t lds_bytes = lds ? size_t(4) * VH_BLOCK_LAGS * h->n_bins : 0;
+    const dim3 bin_grid((unsigned)h->tiles.size(), (unsigned)ceil_div(h->n_lags, VH_BLOCK_LAGS));
+    hipEvent_t ev = h->timer.begin();
+    for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
+        const int64_t nf = std::min(slab, n_frames - s0);
+        const float *pos = d_pos + s0 * src_rows * 3;
+        const int64_t f0 = h->frames_seen;
+        if (h->unwrap)
+            hipLaunchKernelGGL(vh_prepare_kernel<true>, dim3((unsigned)ceil_div(3 * int64_t(n), 256)), dim3(256), 0,
+                               h->stream, pos, src_rows, d_index, n, (int)nf, f0, h->cap, h->dims[0], h->dims[1],
+                               h->dims[2], f0 == 0 ? 1 : 0, h->d_prev.as<double>(), h->d_image.as<int>(),
+                               h->d_hist.as<double>());
+        else
+            hipLaunchKernelGGL(vh_prepare_kernel<false>, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf),
+                               dim3(256), 0, h->stream, pos, src_rows, d_index, n, (int)nf, f0, h->cap, 0.0, 0.0,
+                               0.0, 0, (double *)nullptr, (int *)nullptr, h->d_hist.as<double>());
+        if (lds)
+            hipLaunchKernelGGL(vh_bin_kernel<true>, bin_grid, dim3(VH_THREADS), lds_bytes, h->stream,
+                               h->d_hist.as<double>(), h->cap, n, h->d_tiles.as<VhTile>(), h->d_lags.as<int64_t>(),
+                               h->n_lags, f0, f0 + nf, h->keep, h->d_edges.as<double>(), h->n_bins, h->inv_width,
+                               h->n_groups, h->d_counts.as<unsigned long long>(), h->d_acc.as<double>());
+        else
+            hipLaunchKernelGGL(vh_bin_kernel<false>, bin_grid, dim3(VH_THREADS), 0, h->stream,
+                               h->d_hist.as<double>(), h->cap, n, h->d_tiles.as<VhTile>(), h->d_lags.as<int64_t>(),
+                               h->n_lags, f0, f0 + nf, h->keep, h->d_edges.as<double>(), h->n_bins, h->inv_width,
+                               h->n_groups, h->d_counts.as<unsigned long long>(), h->d_acc.as<double>());
+        for (int64_t lag : h->lags)
+            h->evaluations += h->n_points * std::max<int64_t>(0, f0 + nf - std::max(f0, lag));
+        h->frames_seen += nf;
+    }
+    h->timer.end(ev);
+    MDX_HIP(hipGetLastError());
+    return MDX_OK;
+}
+
+extern "C" {
+
+int mdx_vh_create(mdx_vh_t *out, int dev, int n_groups, const int64_t *n_points, int n_bins, const double *edges,
+                  int n_lags, const int64_t *lags, int zero_dims)
+{
+    MDX_REQUIRE(out && n_points && edges && lags, "NULL argument");
+    MDX_REQUIRE(n_groups >= 1 && n_groups <= 4096, "n_groups out of range");
+    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 24), "n_bins out of range");
+    MDX_REQUIRE(n_lags >= 1 && n_lags <= (1 << 24), "lags must hold at least one lag");
+    MDX_REQUIRE(zero_dims >= 0 && zero_dims < 7, "zero_dims must leave at least one component");
+    const int64_t limit = (int64_t(1) << 31) / 3;
+    int64_t total = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        MDX_REQUIRE(n_points[g] >= 0 && n_points[g] < limit - total,
+                    "group %d: a group size is not negative and all groups hold fewer than 2^31 / 3 points", g);
+        total += n_points[g];
+    }
+    MDX_REQUIRE(total >= 1, "the groups hold no point");
+    for (int b = 0; b <= n_bins; ++b) {
+        MDX_REQUIRE(std::isfinite(edges[b]), "edges must be finite");
+        MDX_REQUIRE(b == 0 || edges[b] > edges[b - 1], "edges must be strictly increasing");
+    }
+    for (int k = 0; k < n_lags; ++k) {
+        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
+        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
+    }
+    MDX_REQUIRE(int64_t(n_lags) * n_groups * n_bins < (int64_t(1) << 31), "too many counters");
+    mdx_vh *h = new mdx_vh();
+    h->dev = dev;
+    h->n_groups = n_groups;
+    h->n_bins = n_bins;
+    h->n_lags = n_lags;
+    h->keep = 7 & ~zero_dims;
+    h->n_points = total;
+    h->max_lag = lags[n_lags - 1];
+    h->lags.assign(lags, lags + n_lags);
+    h->edges.assign(edges, edges + n_bins + 1);
+    h->inv_width = double(n_bins) / (edges[n_bins] - edges[0]);
+    // the tiles of every group (a tile never spans two groups) and the groups' point ranges
+    h->offsets.push_back(0);
+    int64_t point = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        for (int64_t j = 0; j < n_points[g]; j += VH_TILE)
+            h->tiles.push_back(VhTile{int(point + j), int(std::min<int64_t>(VH_TILE, n_points[g] - j)), g});
+        point += n_points[g];
+        h->offsets.push_back(point);
+    }
+    *out = h;
+    return MDX_OK;
+}
+
+int mdx_vh_destroy(mdx_vh_t h)
+{
+    if (!h)
+        return MDX_OK;
+    if (h->stream) {
+        (void)hipSetDevice(h->dev);
+        (void)hipStreamSynchronize(h->stream);
+        h->timer.destroy();
+        h->pipe.destroy();      // waits for its copy stream
+        for (DeviceBuffer *b : {&h->d_tiles, &h->d_offsets, &h->d_lags, &h->d_edges, &h->d_counts, &h->d_acc,
+                                &h->d_moments, &h->d_hist, &h->d_prev, &h->d_image, &h->d_stage[0], &h->d_stage[1],
+                                &h->d_index})
+            b->recycle();
+        stream_release(h->stream);
+    }
+    delete h;
+    return MDX_OK;
+}
+
+int mdx_vh_reset(mdx_vh_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->frames_seen = 0;         // the history and the unwrap state start over with the next frame
+    h->evaluations = 0;
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.reset();
+    MDX_TRY(vh_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
+int mdx_vh_set_unwrap(mdx_vh_t h, const double *dims)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (dims)
+        for (int k = 0; k < 3; ++k)
+            MDX_REQUIRE(dims[k] > 0.0 && std::isfinite(dims[k]), "dims[%d] must be positive and finite", k);
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_vh_set_unwrap must be called before the first frame");
+    h->unwrap = dims != nullptr;
+    for (int k = 0; k < 3; ++k)
+        h->dims[k] = dims ? dims[k] : 0.0;
+    return MDX_OK;
+}
+
+int mdx_vh_set_slab_frames(mdx_vh_t h, int64_t frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    MDX_REQUIRE(frames >= 0 && frames <= VH_SLAB_MAX, "frames must lie in [0, %lld]", (long long)VH_SLAB_MAX);
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_vh_set_slab_frames must be called before the first frame");
+    h->slab_frames = frames;
+    return MDX_OK;
+}
+
+int mdx_vh_accumulate_device(mdx_vh_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                             const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && d_pos, "NULL argument");
+    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
+    const int64_t n = index ? n_index : n_atoms;
+    MDX_REQUIRE(n == h->n_points, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_points);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(vh_ensure_device(h));
+    MDX_TRY(vh_ensure_history(h));
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    return vh_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+}
+
+int mdx_vh_accumulate(mdx_vh_t h, const float *pos, int64_t n, int64_t n_frames)
+{
+    MDX_REQUIRE(h && pos, "NULL argument");
+    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
+    MDX_REQUIRE(n == h->n_points, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_points);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(vh_ensure_device(h));
+    MDX_TRY(vh_ensure_history(h));
+    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
+                                                pos + f0 * n * 3, size_t(12) * n * nf);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return vh_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
+// concatenated groups, or NULL for the file's first n_index particles.
+int mdx_vh_accumulate_traj(mdx_vh_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                           const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && traj, "NULL handle");
+    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
+    Trajectory *t = mdx_traj_internal(traj);
+    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
+    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    MDX_REQUIRE(n == h->n_points, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n_points);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)t->n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(vh_ensure_device(h));
+    MDX_TRY(vh_ensure_history(h));
+    MDX_TRY(h->pipe.ensure());
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
+                                  &d_index));
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
+            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return vh_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+int mdx_vh_synchronize(mdx_vh_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
+int mdx_vh_result(mdx_vh_t h, int64_t *counts, double *moments)
+{
+    MDX_REQUIRE(h && counts, "NULL argument");
+    MDX_TRY(vh_ensure_device(h));
+    if (moments)
+        hipLaunchKernelGGL(vh_fold_kernel, dim3((unsigned)ceil_div(int64_t(2) * h->n_lags * h->n_groups, 256)),
+                           dim3(256), 0, h->stream, h->d_acc.as<double>(), (int)h->n_points,
+                           h->d_offsets.as<int64_t>(), h->n_groups, h->n_lags, h->d_moments.as<double>());
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.collect();
+    // uint64 counters of at most frames x points each: they fit an int64
+    MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->n_lags * h->n_groups * h->n_bins,
+                      hipMemcpyDeviceToHost));
+    if (moments)
+        MDX_HIP(hipMemcpy(moments, h->d_moments.ptr, size_t(16) * h->n_lags * h->n_groups, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_vh_point_moments(mdx_vh_t h, double *out)
+{
+    MDX_REQUIRE(h && out, "NULL argument");
+    MDX_TRY(vh_ensure_device(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    MDX_HIP(hipMemcpy(out, h->d_acc.ptr, size_t(16) * h->n_lags * h->n_points, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (h->ready) {
+        MDX_TRY(set_device(h->dev));
+        MDX_HIP(hipStreamSynchronize(h->stream));
+        h->timer.collect();
+    }
+    if (launches) *launches = h->timer.launches;
+    if (kernel_ms) *kernel_ms = h->timer.total_ms;
+    if (frames) *frames = h->frames_seen;
+    if (evaluations) *evaluations = h->evaluations;
+    return MDX_OK;
+}
+
+int mdx_vh_enable_timing(mdx_vh_t h, int on)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->timer.enabled = on != 0;
+    return MDX_OK;
+}
+
+}  // extern "C"
