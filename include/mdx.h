@@ -661,6 +661,46 @@ int mdx_vh_point_moments(mdx_vh_t h, double *out);
 int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations);
 int mdx_vh_enable_timing(mdx_vh_t h, int on);
 
+/* ---- distinct van Hove function G_d(r, t) ---------------------------------------------------------------------------
+ * Set 1 holds n1 rows, set 2 holds n2; incoming rows are set 1 then set 2, or set 1 alone with `same` (both are one
+ * set, n1 == n2, the pair i == j is left out).  dims: float64 [3] box lengths, the same for every frame.  Analysed
+ * frames are numbered f = 0, 1, ... in the order fed; lags: strictly increasing, non-negative; the frame pairs of lag k
+ * are (f0, f0 + lags[k]) with f0 % origin_step == 0.  Per frame pair and pair (i of set 1 at f0, j of set 2 at
+ * f0 + lag), in float64 with separate multiply and add (float32 coordinates are widened before any arithmetic):
+ *     d = x2_j - x1_i;  w = d - L * rint(d * (1.0 / L)), +0.0 for a dropped component;
+ *     r2 = (wx*wx + wy*wy) + wz*wz;  r = sqrt(r2);  counts[k][b] += 1 where edges[b] <= r < edges[b+1] (the last bin
+ *     closed on the right; r outside the edges or not finite is not counted).
+ * edges: float64 [n_bins + 1], the caller's numpy.linspace(r_min, r_max, n_bins + 1); the counts then equal
+ * numpy.histogram(r, n_bins, (r_min, r_max)) count for count.  edges[n_bins] may not exceed half the shortest kept box
+ * length.  zero_dims: bit k drops component k.  There is no unwrap (the minimum image of a difference needs none) and
+ * no floating-point atomic: the counts are integers and identical across the three input routes, across any split of
+ * the frames into calls or slabs, and after a reset (csrc/mdx_vanhove_distinct_device.hpp).  The engine keeps
+ * max(lags) + one slab of float32 frames in HBM.  A handle touches its device with the first frame: mdx_vhd_create and
+ * every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_vhd *mdx_vhd_t;
+int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, int n_bins, const double *edges,
+                   int n_lags, const int64_t *lags, int64_t origin_step, const double *dims, int zero_dims);
+int mdx_vhd_destroy(mdx_vhd_t h);
+/* Forgets the frames seen and the history and zeroes the counts. */
+int mdx_vhd_reset(mdx_vhd_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history).  The results do
+ * not depend on it.  Only before the first frame. */
+int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n1 + n2, or n1 with same. */
+int mdx_vhd_accumulate(mdx_vhd_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_vhd_synchronize). */
+int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_vhd_accumulate_traj(mdx_vhd_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_vhd_synchronize(mdx_vhd_t h);
+/* counts: int64 [n_lags][n_bins]. */
+int mdx_vhd_result(mdx_vhd_t h, int64_t *counts);
+/* evaluations: the contract's pair count so far, sum over the lags of origins x (n1 * n2 - (same ? n1 : 0)). */
+int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations);
+int mdx_vhd_enable_timing(mdx_vhd_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -962,6 +962,83 @@ class VanHoveEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value}
 
 
+class DistinctVanHoveEngine(_Engine):
+    """``mdx_vhd_*``: per lag the histogram of the minimum-image distances ``|x2_j(f0 + lag) - x1_i(f0)|`` over every
+    pair of points (``j != i`` with ``same``) and every frame pair whose origin ``f0`` is a multiple of
+    ``origin_step``, in float64.  Incoming rows are set 1 then set 2, or set 1 alone with ``same``.  The device is
+    first touched by the first frame, so the argument errors (``ValueError``) need none."""
+
+    _destroy = "mdx_vhd_destroy"
+    TILE = 256          # set-1 points per block (VHD_TILE of csrc/mdx_vanhove_distinct_device.hpp)
+    JCHUNK = 512        # set-2 points per block (VHD_JCHUNK)
+    LDS_BINS = 2048     # n_bins up to which the histograms live in LDS (VHD_LDS_BINS)
+
+    def __init__(self, n1, n2, edges, lags, dims, *, same=False, origin_step=1, zero_dims=0, dev=0, timing=False):
+        self.n1, self.n2, self.same = int(n1), int(n2), bool(same)
+        self.n_rows = self.n1 if self.same else self.n1 + self.n2
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if self.edges.ndim != 1 or len(self.edges) < 2:
+            raise ValueError("edges must hold n_bins + 1 >= 2 bin edges.")
+        self.n_bins = len(self.edges) - 1
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        h = c_void_p()
+        check(lib().mdx_vhd_create(byref(h), dev, self.n1, self.n2, int(self.same), self.n_bins, _ptr(self.edges),
+                                   self.n_lags, _ptr(self.lags), int(origin_step), _ptr(self.dims), int(zero_dims)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_vhd_enable_timing(h, 1))
+
+    def set_slab_frames(self, frames):
+        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
+        before the first frame."""
+        check(lib().mdx_vhd_set_slab_frames(self.handle, int(frames)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows of set 1 then set 2 (set 1 alone with ``same``)."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_vhd_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM (``index``: rows of a frame in incoming order).  Asynchronous on the engine's stream:
+        ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_vhd_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                              0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_vhd_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                            0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_vhd_synchronize(self.handle))
+
+    def result(self):
+        """``counts int64 [n_lags, n_bins]``."""
+        counts = np.zeros((self.n_lags, self.n_bins), dtype=np.int64)
+        check(lib().mdx_vhd_result(self.handle, _ptr(counts)))
+        return counts
+
+    def reset(self):
+        check(lib().mdx_vhd_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames, ev = c_int64(), c_double(), c_int64(), c_int64()
+        check(lib().mdx_vhd_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

@@ -215,6 +215,19 @@ _SIGNATURES = {
     "mdx_vh_point_moments": (c_int, [_vp, _vp]),
     "mdx_vh_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_vh_enable_timing": (c_int, [_vp, c_int]),
+    # distinct van Hove function
+    "mdx_vhd_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_int, _vp, c_int, _vp, c_int64, _vp,
+                               c_int]),
+    "mdx_vhd_destroy": (c_int, [_vp]),
+    "mdx_vhd_reset": (c_int, [_vp]),
+    "mdx_vhd_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_vhd_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_vhd_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_vhd_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_vhd_synchronize": (c_int, [_vp]),
+    "mdx_vhd_result": (c_int, [_vp, _vp]),
+    "mdx_vhd_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_vhd_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

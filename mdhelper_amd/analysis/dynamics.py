@@ -1,7 +1,7 @@
 """
-Real-space single-particle dynamics: ``VanHove`` — the self part of the van Hove function
-``G_s(r, t)``, the distribution of displacement magnitudes after a lag and the non-Gaussian parameter —
-and ``calculate_non_gaussian_parameter``.
+Real-space dynamics: ``VanHove`` — the self part of the van Hove function ``G_s(r, t)``, the distribution of
+displacement magnitudes after a lag and the non-Gaussian parameter — ``calculate_non_gaussian_parameter``, and
+``DistinctVanHove`` — the distinct part ``G_d(r, t)``, the time-dependent pair distribution.
 
 The reference package has no counterpart; this sits next to ``IntermediateScatteringFunction(incoherent=True)``
 (``F_s(q, t)``, the Fourier transform of ``G_s``) and the mean squared displacements of the correlation
@@ -10,7 +10,10 @@ engine (its second moment).
 Where the work goes: whole blocks of frames go to the van Hove engine (``mdx_vh_*``), which keeps a history of
 widened (and unwrapped) float64 points in HBM, bins ``|x(f) - x(f - lag)|`` for every point, lag and frame into
 integer histograms and adds ``r^2`` and ``r^4`` per point in frame order.  Counts equal ``numpy.histogram``
-count for count; the moments have a fixed summation order (csrc/mdx_vanhove_device.hpp).
+count for count; the moments have a fixed summation order (csrc/mdx_vanhove_device.hpp).  ``DistinctVanHove``
+feeds the same blocks to the distinct van Hove engine (``mdx_vhd_*``), which keeps a history of float32 frames in HBM
+and bins the minimum-image distance of every pair of points for every (origin, lag) frame pair into integer
+histograms (csrc/mdx_vanhove_distinct_device.hpp).
 """
 
 from __future__ import annotations
@@ -228,3 +231,204 @@ class VanHove(DynamicAnalysisBase):
         self.results.vanhove = counts / (pairs[:, :, None] * shell)
         self.results.msd = moments[:, :, 0] / pairs
         self.results.alpha2 = calculate_non_gaussian_parameter(self.results.msd, moments[:, :, 1] / pairs, n_dims)
+
+
+class DistinctVanHove(DynamicAnalysisBase):
+    r"""
+    Distinct part of the van Hove function,
+
+    .. math:: G_d(r,t)=\frac1{N_1}\Big\langle\sum_{i\in1}\sum_{j\in2,\,j\ne i}
+              \delta\big(r-|\mathbf r_j(t_0+t)-\mathbf r_i(t_0)|\big)\Big\rangle_{t_0}
+
+    with minimum-image distances, averaged over the time origins ``t_0`` of the analysed frames.  At ``t = 0`` it is
+    ``rho g(r)``; ``G_s + G_d`` is the full van Hove function.
+
+    Parameters
+    ----------
+    ag1 : AtomGroup — the points at the time origin
+    ag2 : AtomGroup, optional — the points after the lag; ``None`` (or a group of the very same atoms in the same
+        order): the pairs of ``ag1`` with itself, ``j != i``.  A group that shares only some atoms with ``ag1``, or
+        the same atoms in another order, raises ``ValueError``
+    n_bins : int — number of histogram bins of the distance
+    range : (float, float) — ``(r_min, r_max)`` of the histogram (Å), ``r_min < r_max``; ``r_max`` may not exceed
+        half the shortest box length that takes part
+    lags : array-like of int, keyword-only — lag times in frames of the analysed selection, strictly increasing,
+        non-negative
+    n_lags : int, keyword-only — shorthand for ``lags=arange(n_lags)``; with neither, every analysed frame is a lag
+    origin_step : int, keyword-only — every ``origin_step``-th analysed frame is a time origin
+    dt : float, keyword-only — time between trajectory frames (ps); defaults to the trajectory's
+    dimensions : array-like ``(3,)``, keyword-only — box lengths (Å); defaults to the universe's
+    drop_axis : {0, 1, 2, "x", "y", "z"}, keyword-only — a component that takes no part (slabs, 2-D systems)
+    verbose : bool
+    device : keyword-only — the HIP device
+
+    Results
+    -------
+    ``results.edges`` ``[N_b + 1]``, ``results.bins`` ``[N_b]`` (bin centres, Å), ``results.times`` ``[N_t]`` (ps),
+    ``results.counts`` ``[N_t, N_b]`` (int64), ``results.n_origins`` ``[N_t]``, ``results.vanhove`` —
+    ``G_d(r, t) = counts / (n_origins N_1 shell)`` with the volume of the spherical shell of the bin (Å⁻³; the area
+    of the ring, Å⁻², with ``drop_axis``) — ``results.normalized`` — ``vanhove V / N_2'`` with ``N_2' = N_2 - 1``
+    for one set and ``N_2`` for two, ``V`` the box volume (the area with ``drop_axis``): the normalisation of
+    ``RadialDistributionFunction``'s ``"rdf"`` with ``exclusion=(1, 1)``, so lag 0 is ``g(r)`` — and
+    ``results.units``.  A lag without an origin has zero counts and NaN in the normalised results.
+
+    Limits: the box is orthorhombic and taken as constant (``dimensions``, or else the universe's box): NPT
+    trajectories are outside the contract.  The coordinates are used as given; no unwrap is needed, because the
+    minimum image of a difference does not depend on the periodic images.  More than one rank raises ``ValueError``;
+    molecule centres are not supported; the frames must be evenly spaced and go forward in time; every pair of points
+    is evaluated (no cell list); there is no CPU fallback: without a HIP device ``run()`` raises ``RuntimeError``.
+    """
+
+    def __init__(self, ag1, ag2=None, n_bins: int = 201, range: tuple = (0.0, 15.0), *, lags=None,
+                 n_lags: int = None, origin_step: int = 1, dt=None, dimensions=None, drop_axis=None,
+                 verbose: bool = True, **kwargs) -> None:
+        self.universe = ag1.universe
+        super().__init__(self.universe.trajectory, False, verbose, **kwargs)
+        if self._comm.world_size > 1:
+            raise ValueError("DistinctVanHove runs on one rank: every lag needs every frame.")
+
+        self._n_bins = int(n_bins)
+        if self._n_bins < 1:
+            raise ValueError("'n_bins' must be at least 1.")
+        r_min, r_max = (float(x) for x in strip_unit(range, "angstrom")[0])
+        if not (np.isfinite(r_min) and np.isfinite(r_max) and r_min < r_max):
+            raise ValueError("'range' must be an increasing pair of finite numbers.")
+        self._range = (r_min, r_max)
+
+        if lags is not None and n_lags is not None:
+            raise ValueError("'lags' and 'n_lags' cannot both be given.")
+        if n_lags is not None:
+            if int(n_lags) < 1:
+                raise ValueError("'n_lags' must be at least 1.")
+            lags = np.arange(int(n_lags))
+        if lags is not None:
+            lags = np.atleast_1d(np.asarray(lags))
+            if lags.ndim != 1 or len(lags) == 0 or not np.issubdtype(lags.dtype, np.integer):
+                raise ValueError("'lags' must be a one-dimensional array of integers.")
+            if lags[0] < 0 or np.any(np.diff(lags) <= 0):
+                raise ValueError("'lags' must be non-negative and strictly increasing.")
+            lags = lags.astype(np.int64)
+        self._lags = lags
+        self._origin_step = int(origin_step)
+        if self._origin_step < 1:
+            raise ValueError("'origin_step' must be at least 1.")
+
+        self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
+        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
+        if self._drop_axis not in {0, 1, 2, None}:
+            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
+                             "and 2 or 'z'.")
+        if dimensions is not None:
+            if len(dimensions) != 3:
+                raise ValueError("'dimensions' must have length 3.")
+            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
+        elif self.universe.dimensions is not None:
+            box = np.asarray(self.universe.dimensions, dtype=float)
+            if len(box) > 3 and not np.all(box[3:6] == 90.0):
+                raise ValueError("DistinctVanHove needs an orthorhombic box.")
+            self._dimensions = box[:3].copy()
+        else:
+            raise ValueError("The minimum image needs the box lengths: no system dimensions found or provided.")
+        if not (np.all(np.isfinite(self._dimensions)) and np.all(self._dimensions > 0)):
+            raise ValueError("The box lengths must be positive and finite.")
+        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
+        if r_max > self._dimensions[kept].min() / 2:
+            raise ValueError("'range' reaches beyond half the shortest box length, where the minimum image is not "
+                             "the nearest image.")
+
+        i1 = np.asarray(ag1.indices)
+        i2 = i1 if ag2 is None else np.asarray(ag2.indices)
+        self._same = ag2 is None or np.array_equal(i1, i2)
+        if not self._same and len(np.intersect1d(i1, i2)):
+            raise ValueError("'ag1' and 'ag2' share some atoms: they must be disjoint, or the very same atoms in "
+                             "the same order.")
+        if len(i1) < 1 or len(i2) < 1:
+            raise ValueError("The groups must hold at least one atom.")
+        self._N1, self._N2 = len(i1), len(i2)
+        self._index = i1 if self._same else np.concatenate((i1, i2))
+        self._verbose = verbose
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        st = self._sliced_trajectory
+        if hasattr(st, "frames"):
+            df = np.diff(st.frames)
+            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
+                raise ValueError("The selected frames must be evenly spaced and proceed "
+                                 "forward in time.")
+            df = df[0] if len(df) else 1
+        else:
+            if st.step is not None and st.step <= 0:
+                raise ValueError("The analysis must proceed forward in time.")
+            df = st.step if st.step is not None else 1
+        lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
+        self._lags_run = lags
+        edges = np.linspace(*self._range, self._n_bins + 1)
+        self.results.edges = edges
+        self.results.bins = (edges[:-1] + edges[1:]) / 2
+        self.results.times = lags * df * self._dt
+        # the origins of a lag: the multiples of origin_step below n_frames - lag
+        self.results.n_origins = -(-np.maximum(self.n_frames - lags, 0) // self._origin_step)
+        per = "angstrom^-2" if self._drop_axis is not None else "angstrom^-3"
+        self.results.units = {"results.bins": "angstrom", "results.edges": "angstrom",
+                              "results.times": "picosecond", "results.vanhove": per}
+        _lib.require_device(self._device)
+        # lags without an origin never meet a frame pair: the engine gets the others
+        self._live = lags < self.n_frames
+        self._engine = None
+        if self._live.any():
+            self._engine = _core.DistinctVanHoveEngine(
+                self._N1, self._N2, edges, lags[self._live], self._dimensions, same=self._same,
+                origin_step=self._origin_step, zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis,
+                dev=self._device)
+        self._batch = FrameBatcher(len(self._index),
+                                   lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
+                                   with_box=False)
+
+    def _single_frame(self) -> None:
+        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
+
+    # batched run (the frame feed of base.py), as VanHove.run
+    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
+        traj = self._trajectory
+        if not has_frame_blocks(traj):
+            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
+                               **kwargs)
+        mine = self._batched_frames(start, stop, step, frames, shard=False)
+        index = self._index
+        whole = all_particles(index, traj.n_atoms)
+        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
+                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
+        for sel in frame_blocks(mine, size):
+            if self._engine is None:
+                break
+            route, src = block_source(traj, sel, True)
+            if route == "file":
+                self._engine.accumulate_traj(src, sel, None if whole else index)
+            elif route == "hbm":
+                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
+            else:
+                self._engine.accumulate(src if whole else src[:, index])
+        self._conclude()
+        return self
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        counts = np.zeros((len(self._lags_run), self._n_bins), dtype=np.int64)
+        if self._engine is not None:
+            counts[self._live] = self._engine.result()
+            self._engine.close()
+        edges = self.results.edges
+        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
+        if len(kept) == 3:
+            shell = 4 * np.pi / 3 * (edges[1:] ** 3 - edges[:-1] ** 3)
+        else:
+            shell = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+        origins = self.results.n_origins.astype(float)
+        origins[origins == 0] = np.nan          # no origin: NaN, without a warning
+        partners = self._N2 - 1 if self._same else self._N2
+        self.results.counts = counts
+        self.results.vanhove = counts / (origins[:, None] * self._N1 * shell)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.results.normalized = self.results.vanhove * np.prod(self._dimensions[kept]) / partners

@@ -1,0 +1,366 @@
+// mdx_vanhove_distinct.hip — distinct van Hove function G_d(r, t) on gfx950 (MI355X).
+//
+// Per lag the histogram of the minimum-image distances |x2_j(f0 + lag) - x1_i(f0)| over every pair (i of set 1,
+// j of set 2, j != i when both are one set) and every frame pair (f0, f0 + lag) with f0 a multiple of origin_step.
+// Contract, early rejection and kernel shape: mdx_vanhove_distinct_device.hpp; this unit is compiled with contraction
+// off and spells its float64 operations out.
+//
+// The gathered float32 rows go into a ring of max(lags) + slab frames in HBM, so that a lag reaches back across
+// slabs and calls.  Counts are integers added with integer atomics; nothing here adds floating-point numbers at all,
+// so the counts are the same whatever route the frames take and however they are split into calls or slabs.
+//
+// A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
+#include "mdx_common.hpp"
+#include "mdx_internal.hpp"
+#include "mdx_traj.hpp"
+#include "mdx_vanhove_distinct_device.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace mdx;
+using namespace mdx_vhd_dev;
+
+namespace {
+
+constexpr int64_t VHD_HISTORY_BYTES = int64_t(256) << 20;   // what the frames of a default slab take in the ring
+
+}  // namespace
+
+struct mdx_vhd {
+    int dev = 0;
+    bool ready = false;                 // the device side exists
+    hipStream_t stream = nullptr;
+    int n_bins = 0, n_lags = 0, keep = 7;
+    bool same = false;
+    int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
+    int64_t max_lag = 0, origin_step = 1;
+    int64_t frames_seen = 0, slab_frames = 0, evaluations = 0;      // slab_frames: 0 = the default
+    int64_t cap = 0;                    // frames the ring holds
+    VhdBox box;
+    double inv_width = 0.0, r2_lo = 0.0, r2_hi = 0.0;
+    std::vector<int64_t> lags;
+    std::vector<double> edges;
+    DeviceBuffer d_lags, d_edges, d_counts, d_ring, d_stage[2], d_index;
+    std::vector<int32_t> index_host;    // what d_index holds
+    StagePipeline pipe;
+    StreamTimer timer;
+};
+
+static int64_t vhd_slab(const mdx_vhd *h)
+{
+    if (h->slab_frames > 0)
+        return h->slab_frames;
+    return std::min(VHD_SLAB_MAX, std::max<int64_t>(1, VHD_HISTORY_BYTES / (12 * h->n_rows)));
+}
+
+static int vhd_zero(mdx_vhd *h)
+{
+    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->n_lags * h->n_bins, h->stream));
+    return MDX_OK;
+}
+
+// the device side of the handle: stream, tables and counters
+static int vhd_ensure_device(mdx_vhd *h)
+{
+    MDX_TRY(set_device(h->dev));
+    if (h->ready)
+        return MDX_OK;
+    if (!h->stream) {
+        MDX_TRY(stream_acquire(&h->stream));
+        h->timer.stream = h->stream;
+    }
+    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
+    MDX_TRY(h->d_edges.ensure(size_t(8) * (h->n_bins + 1)));
+    MDX_TRY(h->d_counts.ensure(size_t(8) * h->n_lags * h->n_bins));
+    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
+    MDX_HIP(hipMemcpy(h->d_edges.ptr, h->edges.data(), size_t(8) * (h->n_bins + 1), hipMemcpyHostToDevice));
+    MDX_TRY(vhd_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->ready = true;
+    return MDX_OK;
+}
+
+// The ring, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.  Nothing is
+// in flight then (a reset waits for the stream), so growing it loses nothing.
+static int vhd_ensure_ring(mdx_vhd *h)
+{
+    if (h->frames_seen > 0)
+        return MDX_OK;
+    const int64_t cap = h->max_lag + vhd_slab(h);
+    MDX_REQUIRE(cap < (int64_t(1) << 40) / (12 * h->n_rows), "a history of %lld frames of %lld points is too large",
+                (long long)cap, (long long)h->n_rows);
+    MDX_TRY(h->d_ring.ensure(size_t(12) * h->n_rows * cap));
+    h->cap = cap;
+    return MDX_OK;
+}
+
+// n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
+static int vhd_accumulate_rows(mdx_vhd *h, const float *d_pos, int64_t src_rows, const int *d_index, int64_t n_rows,
+                               int64_t n_frames)
+{
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n_rows, (long long)h->n_rows);
+    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
+    const int n = (int)h->n_rows;
+    const int64_t slab = std::min(vhd_slab(h), h->cap - h->max_lag);
+    const bool lds = h->n_bins <= VHD_LDS_BINS;
+    const size_t lds_bytes =
+        size_t(32) * VHD_STAGE + (lds ? size_t(8) * (h->n_bins + 1) + size_t(4) * VHD_WAVES * h->n_bins : 0);
+    const int64_t n_jchunks = ceil_div(h->n2, VHD_JCHUNK);
+    const int64_t blocks = ceil_div(h->n1, VHD_TILE) * n_jchunks;
+    const int64_t per_pair = h->n1 * h->n2 - (h->same ? h->n1 : 0);
+    hipEvent_t ev = h->timer.begin();
+    for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
+        const int64_t nf = std::min(slab, n_frames - s0);
+        const float *pos = d_pos + s0 * src_rows * 3;
+        const int64_t f0 = h->frames_seen;
+        hipLaunchKernelGGL(vhd_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
+                           0, h->stream, pos, src_rows, d_index, n, f0, h->cap, h->d_ring.as<float>());
+        const dim3 grid((unsigned)blocks, (unsigned)h->n_lags, (unsigned)nf);
+        const auto kernel = lds ? (h->keep == 7 ? vhd_pair_kernel<true, true> : vhd_pair_kernel<true, false>)
+                                : (h->keep == 7 ? vhd_pair_kernel<false, true> : vhd_pair_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(VHD_THREADS), lds_bytes, h->stream, h->d_ring.as<float>(), h->cap, n,
+                           (int)h->n1, (int)h->n2, h->same ? 0 : (int)h->n1, h->same ? 1 : 0, (int)n_jchunks,
+                           h->d_lags.as<int64_t>(), f0, h->origin_step, h->box, h->keep, h->d_edges.as<double>(),
+                           h->n_bins, h->inv_width, h->r2_lo, h->r2_hi, h->d_counts.as<unsigned long long>());
+        // the contract's pair count: origins f - lag that are multiples of origin_step, f among the new frames
+        for (int64_t lag : h->lags) {
+            const int64_t o_lo = std::max<int64_t>(0, f0 - lag), o_hi = f0 + nf - lag;      // origins [o_lo, o_hi)
+            if (o_hi > o_lo)
+                h->evaluations += per_pair * (ceil_div(o_hi, h->origin_step) - ceil_div(o_lo, h->origin_step));
+        }
+        h->frames_seen += nf;
+    }
+    h->timer.end(ev);
+    MDX_HIP(hipGetLastError());
+    return MDX_OK;
+}
+
+extern "C" {
+
+int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, int n_bins, const double *edges,
+                   int n_lags, const int64_t *lags, int64_t origin_step, const double *dims, int zero_dims)
+{
+    MDX_REQUIRE(out && edges && lags && dims, "NULL argument");
+    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 24), "n_bins out of range");
+    MDX_REQUIRE(n_lags >= 1, "lags must hold at least one lag");
+    MDX_REQUIRE(n_lags <= VHD_LAGS_MAX, "at most %d lags", VHD_LAGS_MAX);
+    MDX_REQUIRE(origin_step >= 1, "origin_step must be at least 1");
+    MDX_REQUIRE(zero_dims >= 0 && zero_dims < 7, "zero_dims must leave at least one component");
+    MDX_REQUIRE(n1 >= 1 && n2 >= 1, "both sets must hold at least one point");
+    MDX_REQUIRE(!same || n1 == n2, "same: both sets are one set, but n1 = %lld and n2 = %lld", (long long)n1,
+                (long long)n2);
+    const int64_t limit = (int64_t(1) << 31) / 3;
+    MDX_REQUIRE(n1 < limit && n2 < limit && (same ? n1 : n1 + n2) < limit,
+                "the sets must hold fewer than 2^31 / 3 points");
+    MDX_REQUIRE(ceil_div(n1, VHD_TILE) * ceil_div(n2, VHD_JCHUNK) < (int64_t(1) << 31),
+                "%lld x %lld points are too many pairs for one launch", (long long)n1, (long long)n2);
+    for (int b = 0; b <= n_bins; ++b) {
+        MDX_REQUIRE(std::isfinite(edges[b]), "edges must be finite");
+        MDX_REQUIRE(b == 0 || edges[b] > edges[b - 1], "edges must be strictly increasing");
+    }
+    for (int k = 0; k < n_lags; ++k) {
+        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
+        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
+    }
+    for (int c = 0; c < 3; ++c)
+        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
+    double shortest = HUGE_VAL;
+    for (int c = 0; c < 3; ++c)
+        if (!(zero_dims >> c & 1))
+            shortest = std::min(shortest, dims[c]);
+    // beyond half a box length the minimum image is not the nearest image
+    MDX_REQUIRE(edges[n_bins] <= shortest / 2, "edges reach %g, beyond half the shortest box length %g",
+                edges[n_bins], shortest);
+    MDX_REQUIRE(int64_t(n_lags) * n_bins < (int64_t(1) << 31), "too many counters");
+    mdx_vhd *h = new mdx_vhd();
+    h->dev = dev;
+    h->n1 = n1;
+    h->n2 = n2;
+    h->same = same != 0;
+    h->n_rows = same ? n1 : n1 + n2;
+    h->n_bins = n_bins;
+    h->n_lags = n_lags;
+    h->keep = 7 & ~zero_dims;
+    h->origin_step = origin_step;
+    h->max_lag = lags[n_lags - 1];
+    h->lags.assign(lags, lags + n_lags);
+    h->edges.assign(edges, edges + n_bins + 1);
+    h->inv_width = double(n_bins) / (edges[n_bins] - edges[0]);
+    for (int c = 0; c < 3; ++c) {
+        h->box.L[c] = dims[c];
+        h->box.inv[c] = 1.0 / dims[c];
+    }
+    // the margins of the early rejection (mdx_vanhove_distinct_device.hpp); an upper edge below 0 counts nothing
+    const double lo = edges[0], hi = edges[n_bins], margin = std::ldexp(1.0, -40);
+    h->r2_lo = lo > 0.0 ? (lo * lo) * (1.0 - margin) : 0.0;
+    h->r2_hi = hi >= 0.0 ? (hi * hi) * (1.0 + margin) : -1.0;
+    *out = h;
+    return MDX_OK;
+}
+
+int mdx_vhd_destroy(mdx_vhd_t h)
+{
+    if (!h)
+        return MDX_OK;
+    if (h->stream) {
+        (void)hipSetDevice(h->dev);
+        (void)hipStreamSynchronize(h->stream);
+        h->timer.destroy();
+        h->pipe.destroy();      // waits for its copy stream
+        for (DeviceBuffer *b : {&h->d_lags, &h->d_edges, &h->d_counts, &h->d_ring, &h->d_stage[0], &h->d_stage[1],
+                                &h->d_index})
+            b->recycle();
+        stream_release(h->stream);
+    }
+    delete h;
+    return MDX_OK;
+}
+
+int mdx_vhd_reset(mdx_vhd_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->frames_seen = 0;         // the history starts over with the next frame
+    h->evaluations = 0;
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.reset();
+    MDX_TRY(vhd_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
+int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    MDX_REQUIRE(frames >= 0 && frames <= VHD_SLAB_MAX, "frames must lie in [0, %lld]", (long long)VHD_SLAB_MAX);
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_vhd_set_slab_frames must be called before the first frame");
+    h->slab_frames = frames;
+    return MDX_OK;
+}
+
+int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && d_pos, "NULL argument");
+    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
+    const int64_t n = index ? n_index : n_atoms;
+    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(vhd_ensure_device(h));
+    MDX_TRY(vhd_ensure_ring(h));
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    return vhd_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+}
+
+int mdx_vhd_accumulate(mdx_vhd_t h, const float *pos, int64_t n, int64_t n_frames)
+{
+    MDX_REQUIRE(h && pos, "NULL argument");
+    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
+    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(vhd_ensure_device(h));
+    MDX_TRY(vhd_ensure_ring(h));
+    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
+                                                pos + f0 * n * 3, size_t(12) * n * nf);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return vhd_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+// Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
+// the file's first n_index particles.
+int mdx_vhd_accumulate_traj(mdx_vhd_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && traj, "NULL handle");
+    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
+    Trajectory *t = mdx_traj_internal(traj);
+    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
+    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the sets hold %lld", (long long)n, (long long)h->n_rows);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)t->n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(vhd_ensure_device(h));
+    MDX_TRY(vhd_ensure_ring(h));
+    MDX_TRY(h->pipe.ensure());
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
+                                  &d_index));
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
+            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return vhd_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+int mdx_vhd_synchronize(mdx_vhd_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
+int mdx_vhd_result(mdx_vhd_t h, int64_t *counts)
+{
+    MDX_REQUIRE(h && counts, "NULL argument");
+    MDX_TRY(vhd_ensure_device(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.collect();
+    // uint64 counters of at most frame pairs x n1 x n2 < 2^63 each: they fit an int64
+    MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->n_lags * h->n_bins, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (h->ready) {
+        MDX_TRY(set_device(h->dev));
+        MDX_HIP(hipStreamSynchronize(h->stream));
+        h->timer.collect();
+    }
+    if (launches) *launches = h->timer.launches;
+    if (kernel_ms) *kernel_ms = h->timer.total_ms;
+    if (frames) *frames = h->frames_seen;
+    if (evaluations) *evaluations = h->evaluations;
+    return MDX_OK;
+}
+
+int mdx_vhd_enable_timing(mdx_vhd_t h, int on)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->timer.enabled = on != 0;
+    return MDX_OK;
+}
+
+}  // extern "C"
