@@ -194,6 +194,10 @@ int mdx_rdf_debug_counters(mdx_rdf_t h, int64_t out[4]);
  * at since reset, in Hz — every block adds its span in s_memtime and in 100 MHz s_memrealtime
  * ticks; 0 when no such kernel has run. */
 int mdx_rdf_kernel_clock(mdx_rdf_t h, double *hz);
+/* Cell path: slabs since reset whose sort ran beside the pair kernel of the slab before (two sets of
+ * sorted copies, a second stream); 0 while every call took the serial route — single-slab calls,
+ * triclinic frames, more than 65 535 particles in a set, MDX_RDF_SORT_BESIDE=0. */
+int mdx_rdf_slabs_sorted_beside(mdx_rdf_t h, int64_t *out);
 /* Cell path: the sorted copies (wrapped and original float4 rows, n_pad rows) of one frame of
  * the most recent slab — for debugging the tile logic on the host.  With exclusion 0 or 1 the
  * sorted originals are not materialised: pw is filled and MDX_ERR_STATE returned. */

@@ -312,10 +312,12 @@ class RdfEngine(_Engine):
         check(lib().mdx_rdf_debug_counters(self.handle, _ptr(raw)))
         hz = c_double()
         check(lib().mdx_rdf_kernel_clock(self.handle, byref(hz)))
+        beside = c_int64()
+        check(lib().mdx_rdf_slabs_sorted_beside(self.handle, byref(beside)))
         return {"launches": n.value, "kernel_ms": ms.value, "pairs_evaluated": pe.value,
                 "pairs_exact": px.value, "pairs_computed": pc.value,
                 "cell_units": int(raw[1]), "cell_units_general": int(raw[2]),
-                "clock_hz": hz.value}
+                "slabs_sorted_beside": beside.value, "clock_hz": hz.value}
 
 
 def radial_histogram_device(pos1, pos2, n_bins, edges, dims, exclusion=None, dev=0):

@@ -34,6 +34,7 @@
 #include "mdx_rdf_cell.hpp"
 #include "mdx_traj.hpp"
 
+#include <cstring>
 #include <cmath>
 
 namespace mdx {
@@ -385,7 +386,15 @@ struct mdx_rdf {
     DeviceBuffer d_pw1, d_po1, d_bb1, d_pw2, d_po2, d_bb2;   // cell path: sorted copies + tile boxes
     DeviceBuffer d_bb16_1, d_bb16_2;                         // boxes of the CELL_CHUNK-particle chunks
     // cell path: the sort of slab k + 1 runs on its own stream beside the pair kernel of slab k (two sets of the
-    // sorted copies); events hand the sets back and forth
+    // sorted copies at offsets 0 and one slab into the buffers above); events hand the sets back and forth
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr;                  // h->stream at the entry of a call -> side
+    hipEvent_t ev_sorted[2] = {nullptr, nullptr};  // side: the set holds its slab -> h->stream
+    hipEvent_t ev_read[2] = {nullptr, nullptr};    // h->stream: the pair kernel has read the set -> side
+    hipEvent_t ev_join = nullptr;                  // side at the exit of a call -> h->stream
+    int64_t slabs_sorted_beside = 0;               // slabs whose sort ran beside a pair kernel since reset
+    size_t occ_static_lds = 0;                     // static LDS of the pair kernel asked for last
+    int occ_per_cu = 1;
     StreamTimer timer;
     int64_t pairs_evaluated = 0;    // ordered pair space covered: frames * n1 * n2
     int64_t pairs_bruteforce = 0;   // distance evaluations executed by the brute-force tiles
@@ -456,8 +465,9 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
     const int64_t per_frame = (32 + 1 + CHUNK_BOX_BYTES) * (n1p + (self ? 0 : n2p));
     // (MDX_RDF_SLAB_BYTES: test hook, so that small inputs run through several slabs and both sets)
     const char *slab_env = getenv("MDX_RDF_SLAB_BYTES");
-    // (2.5 GiB = 2 048 frames at C2: the persistent kernel ends on a tail of about one item per block and the sort
-    // between two launches is serial, so long launches pay: 1 024 frames 45.3 k, 2 048 45.6–45.8 k, 4 096 45.7 k frames/s)
+    // (2.5 GiB = 2 304 frames at C2: the persistent kernel ends on a tail of about one item per block, so long
+    // launches pay — measured while the sort between two launches was still serial: 1 024 frames 45.3 k, 2 048
+    // 45.6–45.8 k, 4 096 45.7 k frames/s)
     const int64_t slab_bytes = slab_env ? std::max<int64_t>(1, atoll(slab_env)) : (int64_t(5) << 29);
     int64_t slab = std::max<int64_t>(1, slab_bytes / per_frame);
     slab = std::min<int64_t>(slab, 32768);
@@ -466,30 +476,9 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
     if (slab >= 256)
         slab -= slab % 256;
     slab = std::min<int64_t>(slab, n_frames);
-    // One set of the sorted copies; sort and pair kernel follow each other on the handle's stream.  (The sort of
-    // slab k + 1 on a stream of its own beside the pair kernel of slab k — the form of round 2 — lost once the pair
-    // blocks became persistent: they hold every wave slot until their last items, the sort trickles in behind
-    // retiring blocks and the next pair kernel waits for it anyway: 44.1 k against 45.4 k frames/s at C2(i),
-    // NOTES.md round 3.  The second set, its stream and its events are gone.)
     // exclusion 0 or 1: a particle's tag is its row, and the exact path reads the frames as they came in —
     // no sorted copy of the original coordinates (half of the sort kernel's scattered stores)
     const bool lazy_orig = !tri && h->excl1 <= 1 && h->excl2 <= 1;
-    const size_t e_p1 = size_t(n1p) * slab, e_b1 = size_t(n1p / 64) * 2 * slab;
-    const size_t e_c1 = CELL_CHUNK >= 4 ? size_t(n1p / CELL_CHUNK) * 2 * slab : 16;
-    const size_t e_p2 = size_t(n2p) * slab, e_b2 = size_t(n2p / 64) * 2 * slab;
-    const size_t e_c2 = CELL_CHUNK >= 4 ? size_t(n2p / CELL_CHUNK) * 2 * slab : 16;
-    MDX_TRY(h->d_pw1.ensure(16 * e_p1));
-    if (!lazy_orig)
-        MDX_TRY(h->d_po1.ensure(16 * e_p1));
-    MDX_TRY(h->d_bb1.ensure(16 * e_b1));
-    MDX_TRY(h->d_bb16_1.ensure(16 * e_c1));
-    if (!self) {
-        MDX_TRY(h->d_bb16_2.ensure(16 * e_c2));
-        MDX_TRY(h->d_pw2.ensure(16 * e_p2));
-        if (!lazy_orig)
-            MDX_TRY(h->d_po2.ensure(16 * e_p2));
-        MDX_TRY(h->d_bb2.ensure(16 * e_b2));
-    }
     unsigned *d_misc = h->d_misc.as<unsigned>();
     if (!tri)
         hipLaunchKernelGGL(rdf_check_boxes_kernel, dim3((unsigned)ceil_div(n_frames, 256)), dim3(256),
@@ -523,103 +512,248 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
     // resident blocks per XCD (32 CUs each) of this kernel at this LDS size (asked once per kernel and size)
     if (h->occ_kernel != reinterpret_cast<const void *>(kern) || h->occ_lds != lds) {
         int per_cu = 0, cus = 0;
+        hipFuncAttributes fa{};
         MDX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, lds));
         MDX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->dev));
+        MDX_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)));
         h->occ_kernel = reinterpret_cast<const void *>(kern);
         h->occ_lds = lds;
+        h->occ_static_lds = fa.sharedSizeBytes;
+        h->occ_per_cu = std::max(per_cu, 1);
         h->occ_blocks_per_xcd = std::max<int64_t>(1, int64_t(std::max(per_cu, 1)) * std::max(cus, 8) / 8);
     }
     const int64_t blocks_per_xcd = h->occ_blocks_per_xcd;
 
-    hipStream_t s_sort = h->stream;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
-        const int64_t nf = std::min(slab, n_frames - f0);
-        float4 *pw1 = h->d_pw1.as<float4>();
-        float4 *po1 = lazy_orig ? nullptr : h->d_po1.as<float4>();
-        float4 *bb1 = h->d_bb1.as<float4>(), *bc1 = h->d_bb16_1.as<float4>();
-        float4 *pw2 = self ? pw1 : h->d_pw2.as<float4>();
-        float4 *po2 = self ? po1 : (lazy_orig ? nullptr : h->d_po2.as<float4>());
-        float4 *bb2 = self ? bb1 : h->d_bb2.as<float4>();
-        float4 *bc2 = self ? bc1 : h->d_bb16_2.as<float4>();
-        // the batch's largest |coordinate| (the filter's error bound grows with it) is folded by the sort
-        unsigned *d_maxabs = d_misc;
-        h->last_offset = 0;
-        h->last_frames = nf;
-        h->last_n_pad = n1p;
-        h->last_lazy = lazy_orig;
-        {
-            // (Measured and dropped, round 3: the sort as a GATHER — slots noted per particle in LDS, rows written
-            // in slot order as whole lines — 0.66 ms per 1 000 frames against 0.74–0.82, +0.5 % on the step, but its
-            // 12-byte reads scattered over frames that are no longer in L2 fetch 4.0 MB per frame where the scatter's
-            // partial-sector stores cost 1.1: 6.5 MB per frame in all against 4.4.  Neither two blocks per CU (the
-            // kernel sits at 65 VGPRs: one over), float32 cell keys, a DPP box reduction nor a two-barrier scan moved
-            // the kernel's time: all 256 blocks of a round read, then write, in step — 25 µs counting from HBM, 81 µs
-            // writing rows — and the memory system sets the pace.)
-            auto sort = tri ? rdf_cell_sort_kernel<true> : rdf_cell_sort_kernel<false>;
-            const float *cells = tri ? d_tri + f0 * 9 : d_boxes + f0 * 6;
-            hipLaunchKernelGGL(sort, dim3((unsigned)nf), dim3(SORT_THREADS), 0, s_sort,
-                               d_pos1 + f0 * n1 * 3, cells, (int)n1, (int)n1p, excl ? h->excl1 : 0,
-                               pw1, po1, bb1, bc1, d_maxabs);
-            if (!self)
-                hipLaunchKernelGGL(sort, dim3((unsigned)nf), dim3(SORT_THREADS), 0, s_sort,
-                                   d_pos2 + f0 * n2 * 3, cells, (int)n2, (int)n2p,
-                                   excl ? h->excl2 : 0, pw2, po2, bb2, bc2, d_maxabs);
-        }
-        CellArgs a{};
-        a.pw1 = pw1;
-        a.po1 = po1;
-        a.bb1 = bb1;
-        a.pw2 = pw2;
-        a.po2 = po2;
-        a.bb2 = bb2;
-        a.bb16_2 = bc2;
-        a.in1 = lazy_orig ? d_pos1 + f0 * n1 * 3 : nullptr;
-        a.in2 = lazy_orig ? d_pos2 + f0 * n2 * 3 : nullptr;
-        a.n1_in = (int)n1;
-        a.n2_in = (int)n2;
-        a.tags_everywhere = (self && h->excl1 == 1 && h->excl2 == 1) ? 0 : 1;
-        a.boxes = tri ? nullptr : d_boxes + f0 * 6;
-        a.tri = tri ? d_tri + f0 * 9 : nullptr;
-        a.thresh = h->d_thresh.as<double>();
-        a.counts = h->d_counts.as<unsigned long long>();
-        a.maxabs_bits = d_maxabs;
-        a.exact_counter = h->d_stats.as<unsigned long long>();
-        a.tilepair_counter = a.exact_counter + 1;
-        a.clock_counter = h->timer.enabled ? a.exact_counter + 3 : nullptr;
-        a.t_lo = h->t_lo;
-        a.t_hi = h->t_hi;
-        a.r0 = h->edges.front();
-        a.r1 = h->edges.back();
-        a.n1p = (int)n1p;
-        a.n2p = (int)n2p;
-        a.n_bins = h->n_bins;
-        a.n_hist = n_hist;
-        a.n_rep = h->n_rep;
-        a.self = self ? 1 : 0;
-        // persistent blocks: what the chip holds at once (blocks per CU from the kernel's own occupancy), a
-        // multiple of 8 so that every XCD gets the same number; fewer when there is less work than that
-        a.work = h->d_work.as<unsigned>();
-        {
-            const char *fu = getenv("MDX_RDF_LDS_FLUSH_UNITS");   // test hook: flush the LDS bins (much) more often
-            a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), 1 << 18) : (1u << 18);
-        }
-        const int64_t tiles = n1p / 128;
-        hipEvent_t ev = h->timer.begin();
-        // (frames per launch: the item index is 32 bits wide)
-        const int64_t launch_frames = std::max<int64_t>(8, std::min<int64_t>(32768, ((int64_t(1) << 30) / tiles) * 8));
-        for (int64_t g0 = 0; g0 < nf; g0 += launch_frames) {
-            a.frame0 = (int)g0;
-            a.n_frames = (int)std::min<int64_t>(launch_frames, nf - g0);
-            a.spread = a.n_frames < 8 ? 1 : 0;
-            const int64_t items_per_xcd = a.spread ? ceil_div(int64_t(a.n_frames) * tiles, 8)
-                                                   : ceil_div(a.n_frames, 8) * tiles;
-            const unsigned grid = 8u * (unsigned)std::min<int64_t>(blocks_per_xcd, items_per_xcd);
-            MDX_HIP(hipMemsetAsync(h->d_work.ptr, 0, CELL_WORK_BYTES, h->stream));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, h->stream, a);
-        }
-        h->timer.end(ev);
-        MDX_HIP(hipGetLastError());
+    // The sort of slab k + 1 BESIDE the pair kernel of slab k.  Round 2 put it on a second stream (+1 %); with
+    // persistent pair blocks that lost 3 % (NOTES.md round 3): they hold every wave slot and nearly every register
+    // until their last items, and a 1 024-thread sort block could enter only where four of them had retired.  Here
+    // the sort is a block of the pair block's own shape (rdf_cell_sort_small_kernel), and the pair kernel is launched
+    // with S fewer blocks than the chip holds (S a multiple of 8: every XCD gives up the same number): S persistent
+    // sort blocks on the side stream have a place from the start, and neither kernel waits for the other to retire
+    // anything.  Two sets of the sorted copies alternate.  The first slab of a call has nothing to hide behind: the
+    // big kernel sorts it on the handle's stream, and it is a quarter slab, the second a half (the shape of the host
+    // and file routes), S scaled by the ratio of the sorted slab's length to the pair launch's.
+    // Today's serial route (one set, the big kernel) remains for: triclinic frames, more than 65 535 particles in a
+    // set (packed 16-bit counters), a pair kernel whose blocks leave the sort block's 33 KB of LDS no room beside
+    // all but one of them, calls of a single slab, a device without room for the second set, and
+    // MDX_RDF_SORT_BESIDE=0.
+    // S = 16 (profiles/r06_sort_beside_S_choice.txt): 16 blocks sort a slab of 2 304 C2 frames in half the time of
+    // its pair launch; with 8 the sort would take all of it
+    constexpr int64_t S0 = 16;
+    const char *sb_env = getenv("MDX_RDF_SORT_BESIDE");
+    const size_t sort_small_lds = sort_small_lds_bytes();
+    const size_t cu_lds = size_t(160) * 1024;
+    bool beside = !tri && !(sb_env && strcmp(sb_env, "0") == 0) && n_frames > slab && n1 <= SORT_SMALL_MAX_N &&
+                  n2 <= SORT_SMALL_MAX_N && blocks_per_xcd >= 2 &&
+                  size_t(h->occ_per_cu - 1) * (h->occ_static_lds + lds) + sort_small_lds <= cu_lds;
+    if (beside && !h->ev_join) {
+        // (the last event created is the guard: after a failure half-way the next call starts over)
+        if (!h->side)
+            MDX_TRY(stream_acquire(&h->side));
+        for (hipEvent_t *e : {&h->ev_fork, &h->ev_sorted[0], &h->ev_sorted[1], &h->ev_read[0], &h->ev_read[1], &h->ev_join})
+            if (!*e)
+                MDX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
+
+    const size_t e_p1 = size_t(n1p) * slab, e_b1 = size_t(n1p / 64) * 2 * slab;
+    const size_t e_c1 = CELL_CHUNK >= 4 ? size_t(n1p / CELL_CHUNK) * 2 * slab : 16;
+    const size_t e_p2 = size_t(n2p) * slab, e_b2 = size_t(n2p / 64) * 2 * slab;
+    const size_t e_c2 = CELL_CHUNK >= 4 ? size_t(n2p / CELL_CHUNK) * 2 * slab : 16;
+    auto ensure_sets = [&](size_t n_sets) -> int {
+        MDX_TRY(h->d_pw1.ensure(16 * e_p1 * n_sets));
+        if (!lazy_orig)
+            MDX_TRY(h->d_po1.ensure(16 * e_p1 * n_sets));
+        MDX_TRY(h->d_bb1.ensure(16 * e_b1 * n_sets));
+        MDX_TRY(h->d_bb16_1.ensure(16 * e_c1 * n_sets));
+        if (!self) {
+            MDX_TRY(h->d_bb16_2.ensure(16 * e_c2 * n_sets));
+            MDX_TRY(h->d_pw2.ensure(16 * e_p2 * n_sets));
+            if (!lazy_orig)
+                MDX_TRY(h->d_po2.ensure(16 * e_p2 * n_sets));
+            MDX_TRY(h->d_bb2.ensure(16 * e_b2 * n_sets));
+        }
+        return MDX_OK;
+    };
+    // two sets are twice the memory (5 GiB at C2): a device too full for them still has the serial route's one
+    // (buffers the failed attempt had already grown stay at that size, and its message stays in mdx_last_error()
+    // although the call then succeeds: nobody reads it after MDX_OK)
+    if (beside && ensure_sets(2) == MDX_ERR_OUT_OF_MEMORY)
+        beside = false;
+    MDX_TRY(ensure_sets(beside ? 2 : 1));
+    // slab lengths of this call
+    std::vector<int64_t> lens;
+    for (int64_t f0 = 0; f0 < n_frames;) {
+        int64_t step = slab;
+        if (beside && slab >= 8 && lens.size() < 2) {   // a quarter, a half; whole rounds of the big kernel
+            step = slab >> (2 - lens.size());
+            if (step >= 256)
+                step -= step % 256;
+        }
+        step = std::min(step, n_frames - f0);
+        lens.push_back(step);
+        f0 += step;
+    }
+    // the batch's largest |coordinate| (the filter's error bound grows with it) is folded by the sort into ONE word
+    // per handle.  A pair kernel beside which the next slab is sorted may read the maximum of that slab as well:
+    // that only widens the filter's margin — more pairs take the exact path, which bins them as the contract does,
+    // so the counts cannot change (the exact-path statistics can, by a few pairs).
+    unsigned *d_maxabs = d_misc;
+
+    struct Set {
+        float4 *pw1, *po1, *bb1, *bc1, *pw2, *po2, *bb2, *bc2;
+    };
+    auto set_of = [&](int b) {
+        Set s;
+        s.pw1 = h->d_pw1.as<float4>() + b * e_p1;
+        s.po1 = lazy_orig ? nullptr : h->d_po1.as<float4>() + b * e_p1;
+        s.bb1 = h->d_bb1.as<float4>() + b * e_b1;
+        s.bc1 = h->d_bb16_1.as<float4>() + b * e_c1;
+        s.pw2 = self ? s.pw1 : h->d_pw2.as<float4>() + b * e_p2;
+        s.po2 = self ? s.po1 : (lazy_orig ? nullptr : h->d_po2.as<float4>() + b * e_p2);
+        s.bb2 = self ? s.bb1 : h->d_bb2.as<float4>() + b * e_b2;
+        s.bc2 = self ? s.bc1 : h->d_bb16_2.as<float4>() + b * e_c2;
+        return s;
+    };
+    // the sort of frames [f0, f0 + nf) into a set: the big kernel (small_grid == 0) or `small_grid` persistent
+    // blocks of the small one
+    auto launch_sort = [&](const Set &s, int64_t f0, int64_t nf, hipStream_t stream, unsigned small_grid) {
+        // (Measured and dropped, round 3: the sort as a GATHER — slots noted per particle in LDS, rows written
+        // in slot order as whole lines — 0.66 ms per 1 000 frames against 0.74–0.82, +0.5 % on the step, but its
+        // 12-byte reads scattered over frames that are no longer in L2 fetch 4.0 MB per frame where the scatter's
+        // partial-sector stores cost 1.1: 6.5 MB per frame in all against 4.4.  Neither two blocks per CU (the
+        // kernel sits at 65 VGPRs: one over), float32 cell keys, a DPP box reduction nor a two-barrier scan moved
+        // the kernel's time: all 256 blocks of a round read, then write, in step — 25 µs counting from HBM, 81 µs
+        // writing rows — and the memory system sets the pace.)
+        const float *cells = tri ? d_tri + f0 * 9 : d_boxes + f0 * 6;
+        if (small_grid) {
+            auto sort = rdf_cell_sort_small_kernel<SORT_SMALL_THREADS>;
+            hipLaunchKernelGGL(sort, dim3(small_grid), dim3(SORT_SMALL_THREADS), sort_small_lds, stream, d_pos1 + f0 * n1 * 3,
+                               cells, (int)n1, (int)n1p, excl ? h->excl1 : 0, s.pw1, s.po1, s.bb1, s.bc1, d_maxabs,
+                               (int)nf);
+            if (!self)
+                hipLaunchKernelGGL(sort, dim3(small_grid), dim3(SORT_SMALL_THREADS), sort_small_lds, stream,
+                                   d_pos2 + f0 * n2 * 3, cells, (int)n2, (int)n2p, excl ? h->excl2 : 0, s.pw2,
+                                   s.po2, s.bb2, s.bc2, d_maxabs, (int)nf);
+            return;
+        }
+        auto sort = tri ? rdf_cell_sort_kernel<true> : rdf_cell_sort_kernel<false>;
+        hipLaunchKernelGGL(sort, dim3((unsigned)nf), dim3(SORT_THREADS), 0, stream, d_pos1 + f0 * n1 * 3, cells,
+                           (int)n1, (int)n1p, excl ? h->excl1 : 0, s.pw1, s.po1, s.bb1, s.bc1, d_maxabs);
+        if (!self)
+            hipLaunchKernelGGL(sort, dim3((unsigned)nf), dim3(SORT_THREADS), 0, stream, d_pos2 + f0 * n2 * 3,
+                               cells, (int)n2, (int)n2p, excl ? h->excl2 : 0, s.pw2, s.po2, s.bb2, s.bc2,
+                               d_maxabs);
+    };
+
+    auto slabs = [&]() -> int {
+        int64_t f0 = 0;
+        for (size_t k = 0; k < lens.size(); f0 += lens[k], ++k) {
+            const int64_t nf = lens[k];
+            const int b = beside ? int(k & 1) : 0;
+            const Set s = set_of(b);
+            h->last_offset = b * e_p1;
+            h->last_frames = nf;
+            h->last_n_pad = n1p;
+            h->last_lazy = lazy_orig;
+            if (!beside || k == 0)
+                launch_sort(s, f0, nf, h->stream, 0);
+            else
+                MDX_HIP(hipStreamWaitEvent(h->stream, h->ev_sorted[b], 0));
+            // blocks the pair kernel of this slab leaves to the sort of the next
+            int64_t holes = 0;
+            if (beside && k + 1 < lens.size()) {
+                const int64_t nf_next = lens[k + 1];
+                holes = ceil_div(ceil_div(S0 * nf_next, nf), 8) * 8;
+                holes = std::min<int64_t>(holes, 8 * (blocks_per_xcd / 2));
+                // the other set: free once the pair kernel of slab k - 1 has read it (before the first slab of a
+                // call: whatever the handle's stream held at the fork)
+                if (k > 0)
+                    MDX_HIP(hipStreamWaitEvent(h->side, h->ev_read[b ^ 1], 0));
+                launch_sort(set_of(b ^ 1), f0 + nf, nf_next, h->side, (unsigned)std::min<int64_t>(holes, nf_next));
+                MDX_HIP(hipEventRecord(h->ev_sorted[b ^ 1], h->side));
+                h->slabs_sorted_beside += 1;
+            }
+            CellArgs a{};
+            a.pw1 = s.pw1;
+            a.po1 = s.po1;
+            a.bb1 = s.bb1;
+            a.pw2 = s.pw2;
+            a.po2 = s.po2;
+            a.bb2 = s.bb2;
+            a.bb16_2 = s.bc2;
+            a.in1 = lazy_orig ? d_pos1 + f0 * n1 * 3 : nullptr;
+            a.in2 = lazy_orig ? d_pos2 + f0 * n2 * 3 : nullptr;
+            a.n1_in = (int)n1;
+            a.n2_in = (int)n2;
+            a.tags_everywhere = (self && h->excl1 == 1 && h->excl2 == 1) ? 0 : 1;
+            a.boxes = tri ? nullptr : d_boxes + f0 * 6;
+            a.tri = tri ? d_tri + f0 * 9 : nullptr;
+            a.thresh = h->d_thresh.as<double>();
+            a.counts = h->d_counts.as<unsigned long long>();
+            a.maxabs_bits = d_maxabs;
+            a.exact_counter = h->d_stats.as<unsigned long long>();
+            a.tilepair_counter = a.exact_counter + 1;
+            a.clock_counter = h->timer.enabled ? a.exact_counter + 3 : nullptr;
+            a.t_lo = h->t_lo;
+            a.t_hi = h->t_hi;
+            a.r0 = h->edges.front();
+            a.r1 = h->edges.back();
+            a.n1p = (int)n1p;
+            a.n2p = (int)n2p;
+            a.n_bins = h->n_bins;
+            a.n_hist = n_hist;
+            a.n_rep = h->n_rep;
+            a.self = self ? 1 : 0;
+            // persistent blocks: what the chip holds at once (blocks per CU from the kernel's own occupancy), a
+            // multiple of 8 so that every XCD gets the same number — less the holes of a sort that runs beside
+            // this launch; fewer when there is less work than that
+            a.work = h->d_work.as<unsigned>();
+            {
+                const char *fu = getenv("MDX_RDF_LDS_FLUSH_UNITS");   // test hook: flush the LDS bins (much) more often
+                a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), 1 << 18) : (1u << 18);
+            }
+            const int64_t tiles = n1p / 128;
+            hipEvent_t ev = h->timer.begin();
+            // (frames per launch: the item index is 32 bits wide)
+            const int64_t launch_frames = std::max<int64_t>(8, std::min<int64_t>(32768, ((int64_t(1) << 30) / tiles) * 8));
+            for (int64_t g0 = 0; g0 < nf; g0 += launch_frames) {
+                a.frame0 = (int)g0;
+                a.n_frames = (int)std::min<int64_t>(launch_frames, nf - g0);
+                a.spread = a.n_frames < 8 ? 1 : 0;
+                const int64_t items_per_xcd = a.spread ? ceil_div(int64_t(a.n_frames) * tiles, 8)
+                                                       : ceil_div(a.n_frames, 8) * tiles;
+                const unsigned grid = 8u * (unsigned)std::min<int64_t>(blocks_per_xcd - holes / 8, items_per_xcd);
+                MDX_HIP(hipMemsetAsync(h->d_work.ptr, 0, CELL_WORK_BYTES, h->stream));
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, h->stream, a);
+            }
+            h->timer.end(ev);
+            MDX_HIP(hipGetLastError());
+            if (beside)
+                MDX_HIP(hipEventRecord(h->ev_read[b], h->stream));
+        }
+        return MDX_OK;
+    };
+    int rc = MDX_OK;
+    if (beside) {
+        // fork: what the caller queued on the handle's stream (the unpack kernel of the file route, an earlier
+        // call's pair kernels that still read a set) is ahead of everything on the side stream; join: the handle's
+        // stream ends behind the side stream's last kernel — on the error exits too — so that synchronize(),
+        // counts(), reset() and close() mean what they meant
+        MDX_HIP(hipEventRecord(h->ev_fork, h->stream));
+        MDX_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+        rc = slabs();
+        hipError_t e = hipEventRecord(h->ev_join, h->side);
+        if (e == hipSuccess)
+            e = hipStreamWaitEvent(h->stream, h->ev_join, 0);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(h->side);
+            if (rc == MDX_OK)
+                rc = fail(MDX_ERR_HIP, "joining the sort stream failed: %s", hipGetErrorString(e));
+        }
+    } else {
+        rc = slabs();
+    }
+    MDX_TRY(rc);
     h->pairs_evaluated += n_frames * n1 * n2;
     return MDX_OK;
 }
@@ -992,7 +1126,7 @@ static int accumulate_pipelined(mdx_rdf *h, int64_t n1, int64_t n2, bool same, c
 {
     // slabs of ~256 MiB (MDX_RDF_PIPE_MB), the first two a quarter and a half of that: each slab is one sort + one
     // pair launch on the compute stream; the persistent pair kernel ends on a tail of about one item per block
-    // (2 % of a launch of 336 frames at C2, 0.7 % of one of 1 000) and the sort cannot run beside it, so longer
+    // (2 % of a launch of 336 frames at C2, 0.7 % of one of 1 000) and a call of one slab sorts serially, so longer
     // launches are worth more than finer overlap; a multiple of 8 frames, so that every XCD gets the same number
     const char *mb_env = getenv("MDX_RDF_PIPE_MB");
     const int64_t pipe_mb = mb_env ? std::min<long long>(std::max<long long>(atoll(mb_env), 1), 4096) : 256;
@@ -1089,8 +1223,13 @@ int mdx_rdf_destroy(mdx_rdf_t h)
         (void)hipStreamSynchronize(h->stream);
     if (h->pipe.copy_stream)
         (void)hipStreamSynchronize(h->pipe.copy_stream);
+    if (h->side)
+        (void)hipStreamSynchronize(h->side);
     h->timer.destroy();
     h->pipe.destroy();
+    for (hipEvent_t e : {h->ev_fork, h->ev_join, h->ev_sorted[0], h->ev_sorted[1], h->ev_read[0], h->ev_read[1]})
+        if (e)
+            (void)hipEventDestroy(e);
     for (DeviceBuffer *b : {&h->d_thresh, &h->d_counts, &h->d_total, &h->d_pack1, &h->d_pack2,
                             &h->d_stage1[0], &h->d_stage2[0], &h->d_boxes[0], &h->d_stage1[1],
                             &h->d_stage2[1], &h->d_boxes[1], &h->d_rawslab[0], &h->d_rawslab[1], &h->d_index[0], &h->d_index[1], &h->d_tri, &h->d_misc, &h->d_stats, &h->d_work, &h->d_pw1,
@@ -1099,6 +1238,8 @@ int mdx_rdf_destroy(mdx_rdf_t h)
         b->recycle();
     h->grouping[0].recycle();
     h->grouping[1].recycle();
+    if (h->side)
+        stream_release(h->side);
     if (h->stream)
         stream_release(h->stream);
     delete h;
@@ -1118,6 +1259,7 @@ int mdx_rdf_reset(mdx_rdf_t h)
     h->timer.reset();
     h->pairs_evaluated = 0;
     h->pairs_bruteforce = 0;
+    h->slabs_sorted_beside = 0;
     h->reduced_global = false;
     return MDX_OK;
 }
@@ -1327,6 +1469,13 @@ int mdx_rdf_debug_counters(mdx_rdf_t h, int64_t out[4])
     out[1] = (int64_t)raw[1];   // (64 i) x (16 j) units evaluated by the cell kernel
     out[2] = (int64_t)raw[2];   // ... of which on the per-pair image-search path
     out[3] = h->pairs_bruteforce;
+    return MDX_OK;
+}
+
+int mdx_rdf_slabs_sorted_beside(mdx_rdf_t h, int64_t *out)
+{
+    MDX_REQUIRE(h && out, "NULL argument");
+    *out = h->slabs_sorted_beside;
     return MDX_OK;
 }
 

@@ -9,6 +9,8 @@
 //        the sorted wrapped coordinates Pw (float4, w = exclusion tag), the sorted
 //        ORIGINAL coordinates Po (the contract arithmetic needs those) and one
 //        bounding box per 64-particle tile.  Everything in LDS, no global atomics.
+//   rdf_cell_sort_small_kernel   the same sort as persistent 256-thread blocks of the pair block's
+//        footprint: sorts slab k + 1 in block slots the pair kernel of slab k leaves free.
 //   rdf_cell_pair_kernel   one 256-thread block per (frame, 128-particle i tile);
 //        each WAVE walks its share of the 64-particle j tiles on its own (no block
 //        barrier in the loop): 64 candidate j tiles are tested per instruction
@@ -187,6 +189,41 @@ struct TriCell {
     }
 };
 
+// Bounding boxes (of the float32 wrapped coordinates) of a sorted frame: one per 16-particle chunk, one per
+// 64-particle tile; each wave of the block takes every (THREADS / 64)-th tile.
+template <int THREADS>
+__device__ inline void cell_tile_boxes(const float4 *PW, float4 *bb, float4 *bb16, int frame, int n_pad, int tid)
+{
+    const int lane = tid & 63, wave = tid >> 6;
+    const int n_tiles = n_pad / 64;
+    float4 *BB = bb + int64_t(frame) * n_tiles * 2;
+    float4 *BB16 = bb16 + int64_t(frame) * n_tiles * 2 * CELL_NCHUNK;
+#pragma unroll 2
+    for (int t = wave; t < n_tiles; t += THREADS / 64) {
+        float4 v = PW[t * 64 + lane];
+        const float inf = __int_as_float(0x7f800000);
+        bool ok = v.x == v.x;
+        float lo[3] = {ok ? v.x : inf, ok ? v.y : inf, ok ? v.z : inf};
+        float hi[3] = {ok ? v.x : -inf, ok ? v.y : -inf, ok ? v.z : -inf};
+        for (int off = 1; off < 64; off <<= 1) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
+                hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
+            }
+            if (CELL_CHUNK >= 4 && off == CELL_CHUNK / 2 && (lane & (CELL_CHUNK - 1)) == 0) {
+                const int c = t * CELL_NCHUNK + lane / CELL_CHUNK;
+                BB16[c * 2] = make_float4(lo[0], lo[1], lo[2], 0.f);
+                BB16[c * 2 + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+            }
+        }
+        if (lane == 0) {
+            BB[2 * t] = make_float4(lo[0], lo[1], lo[2], 0.f);
+            BB[2 * t + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+        }
+    }
+}
+
 template <bool TRI>
 __global__ __launch_bounds__(SORT_THREADS) void rdf_cell_sort_kernel(
     const float *__restrict__ pos, const float *__restrict__ boxes, int n, int n_pad, int64_t excl,
@@ -303,36 +340,161 @@ __global__ __launch_bounds__(SORT_THREADS) void rdf_cell_sort_kernel(
     __threadfence_block();
     __syncthreads();
 
-    // bounding boxes (of the float32 wrapped coordinates): one per 16-particle chunk,
-    // one per 64-particle tile
-    const int lane = tid & 63, wave = tid >> 6;
-    const int n_tiles = n_pad / 64;
-    float4 *BB = bb + int64_t(frame) * n_tiles * 2;
-    float4 *BB16 = bb16 + int64_t(frame) * n_tiles * 2 * CELL_NCHUNK;
-#pragma unroll 2
-    for (int t = wave; t < n_tiles; t += SORT_THREADS / 64) {
-        float4 v = PW[t * 64 + lane];
-        const float inf = __int_as_float(0x7f800000);
-        bool ok = v.x == v.x;
-        float lo[3] = {ok ? v.x : inf, ok ? v.y : inf, ok ? v.z : inf};
-        float hi[3] = {ok ? v.x : -inf, ok ? v.y : -inf, ok ? v.z : -inf};
-        for (int off = 1; off < 64; off <<= 1) {
+    cell_tile_boxes<SORT_THREADS>(PW, bb, bb16, frame, n_pad, tid);
+}
+
+__device__ inline double cell_uniform_d(double v)
+{
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
+                            __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+// The sort in the shape of a PAIR block, for the slots a pair launch leaves free (mdx_rdf.hip, accumulate_cell):
+// THREADS = 256 threads at the pair kernel's register budget (seven waves per SIMD), persistent — a block takes
+// frames blockIdx.x, blockIdx.x + gridDim.x, ... of the slab — and its cell counters packed two 16-bit counts to
+// a 32-bit LDS word, so that the table of CELL_MAX cells is 32 KB and the block fits the LDS a CU has left beside
+// six pair blocks.  Same grid, keys and outputs as rdf_cell_sort_kernel.  Packed counters need n <= 65 535: a
+// count, and after the scan a cursor, never exceeds n, so the low half of a word cannot carry into the high one.
+// The order of the particles inside a cell is whatever the LDS atomics hand out, as in the big kernel.
+// Orthorhombic frames only.
+constexpr int SORT_SMALL_THREADS = 256;
+constexpr int SORT_SMALL_BATCH = 8;           // rows a thread has in flight while it counts
+constexpr int SORT_SMALL_BATCH_SCATTER = 4;   // ... and while it scatters (eight spill to scratch at 72 VGPRs)
+constexpr int64_t SORT_SMALL_MAX_N = 65535;
+constexpr size_t sort_small_lds_bytes() { return size_t(4) * (CELL_MAX / 2 + SORT_SMALL_THREADS); }
+template <int THREADS>
+__global__ __launch_bounds__(THREADS, 7) void rdf_cell_sort_small_kernel(
+    const float *__restrict__ pos, const float *__restrict__ boxes, int n, int n_pad, int64_t excl,
+    float4 *__restrict__ pw, float4 *__restrict__ po, float4 *__restrict__ bb,
+    float4 *__restrict__ bb16, unsigned *maxabs_bits, int nf)
+{
+    // (dynamic LDS, sort_small_lds_bytes(): with a static 33 KB the compiler sees four blocks per CU and spends 115
+    // VGPRs on them — the block has to fit a pair block's slot)
+    extern __shared__ __align__(16) unsigned sort_small_lds[];
+    unsigned *cnt = sort_small_lds;                 // [CELL_MAX / 2]
+    unsigned *part = sort_small_lds + CELL_MAX / 2;   // [THREADS]
+    const int tid = threadIdx.x;
+    // (a row index is below 2^16: a 32-bit division gives the tag, and any exclusion beyond 2^31 gives tag 0)
+    const unsigned excl32 = (unsigned)min(excl, (int64_t)0x7fffffff);
+    float m = 0.0f;
+    for (int frame = blockIdx.x; frame < nf; frame += gridDim.x) {
+        const float *P = pos + int64_t(frame) * n * 3;
+        float4 *PW = pw + int64_t(frame) * n_pad;
+        float4 *PO = po + int64_t(frame) * n_pad;
+        CellGrid g;
+        g.init(boxes + int64_t(frame) * 6, n);
+        // (block-uniform, but computed on the VALU: pinned into scalar registers, or the six doubles occupy twelve
+        // of the 72 VGPRs across both particle loops and the rows in flight spill)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-                hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
+        for (int k = 0; k < 3; ++k) {
+            g.Ld[k] = cell_uniform_d(g.Ld[k]);
+            g.invLd[k] = cell_uniform_d(g.invLd[k]);
+            g.nc[k] = __builtin_amdgcn_readfirstlane(g.nc[k]);
+        }
+        const int ncell = g.n_cells();
+        // (the previous frame's scatter is behind a barrier: its cursors are dead)
+        for (int c = tid; c < (ncell + 1) / 2; c += THREADS)
+            cnt[c] = 0u;
+        __syncthreads();
+
+        // A thread has n / THREADS particles and nothing but its own loads in flight hides their latency: the rows
+        // of SORT_SMALL_BATCH particles are loaded before the first is counted.  (Spelled out: behind an LDS atomic
+        // the compiler does not move the next iteration's loads of an unrolled loop, and one row was in flight.)
+        for (int a0 = tid; a0 < n; a0 += THREADS * SORT_SMALL_BATCH) {
+            float x[SORT_SMALL_BATCH], y[SORT_SMALL_BATCH], z[SORT_SMALL_BATCH];
+#pragma unroll
+            for (int u = 0; u < SORT_SMALL_BATCH; ++u) {
+                const int a = min(a0 + u * THREADS, n - 1);   // (past the end: the last row again, not counted)
+                x[u] = P[3 * a], y[u] = P[3 * a + 1], z[u] = P[3 * a + 2];
             }
-            if (CELL_CHUNK >= 4 && off == CELL_CHUNK / 2 && (lane & (CELL_CHUNK - 1)) == 0) {
-                const int c = t * CELL_NCHUNK + lane / CELL_CHUNK;
-                BB16[c * 2] = make_float4(lo[0], lo[1], lo[2], 0.f);
-                BB16[c * 2 + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+#pragma unroll
+            for (int u = 0; u < SORT_SMALL_BATCH; ++u)   // every row has arrived before the first is used
+                asm volatile("" : "+v"(x[u]), "+v"(y[u]), "+v"(z[u]));
+#pragma unroll
+            for (int u = 0; u < SORT_SMALL_BATCH; ++u) {
+                if (a0 + u * THREADS >= n)
+                    break;
+                int cx, cy, cz;
+                g.wrap(x[u], 0, cx);
+                g.wrap(y[u], 1, cy);
+                g.wrap(z[u], 2, cz);
+                const int c = g.key(cx, cy, cz);
+                atomicAdd(&cnt[c >> 1], 1u << (16 * (c & 1)));
+                float am = fmaxf(fabsf(x[u]), fmaxf(fabsf(y[u]), fabsf(z[u])));
+                m = fmaxf(m, am == am ? am : __int_as_float(0x7f800000));
             }
         }
-        if (lane == 0) {
-            BB[2 * t] = make_float4(lo[0], lo[1], lo[2], 0.f);
-            BB[2 * t + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
+        __syncthreads();
+
+        // exclusive scan of the counts: each thread owns a contiguous run of whole words
+        const int per = (((ncell + 1) / 2 + THREADS - 1) / THREADS);   // words per thread
+        const int nw = (ncell + 1) / 2;
+        const int w0 = min(tid * per, nw), w1 = min(w0 + per, nw);
+        unsigned local = 0;
+        for (int w = w0; w < w1; ++w) {
+            const unsigned v = cnt[w];
+            local += (v & 0xffffu) + (v >> 16);
         }
+        part[tid] = local;
+        __syncthreads();
+        for (int off = 1; off < THREADS; off <<= 1) {
+            unsigned v = (tid >= off) ? part[tid - off] : 0u;
+            __syncthreads();
+            part[tid] += v;
+            __syncthreads();
+        }
+        unsigned run = part[tid] - local;
+        for (int w = w0; w < w1; ++w) {
+            const unsigned v = cnt[w];
+            const unsigned lo = run, hi = run + (v & 0xffffu);
+            cnt[w] = lo | (hi << 16);   // hi <= n <= 65 535
+            run = hi + (v >> 16);
+        }
+        __syncthreads();
+
+        // scatter: the cursor of a cell hands out its slots
+        for (int a0 = tid; a0 < n; a0 += THREADS * SORT_SMALL_BATCH_SCATTER) {
+            float x[SORT_SMALL_BATCH_SCATTER], y[SORT_SMALL_BATCH_SCATTER], z[SORT_SMALL_BATCH_SCATTER];
+#pragma unroll
+            for (int u = 0; u < SORT_SMALL_BATCH_SCATTER; ++u) {
+                const int a = min(a0 + u * THREADS, n - 1);
+                x[u] = P[3 * a], y[u] = P[3 * a + 1], z[u] = P[3 * a + 2];
+            }
+#pragma unroll
+            for (int u = 0; u < SORT_SMALL_BATCH_SCATTER; ++u)   // every row has arrived before the first is used
+                asm volatile("" : "+v"(x[u]), "+v"(y[u]), "+v"(z[u]));
+#pragma unroll
+            for (int u = 0; u < SORT_SMALL_BATCH_SCATTER; ++u) {
+                const int a = a0 + u * THREADS;
+                if (a >= n)
+                    break;
+                int cx, cy, cz;
+                const float wx = g.wrap(x[u], 0, cx), wy = g.wrap(y[u], 1, cy), wz = g.wrap(z[u], 2, cz);
+                const int c = g.key(cx, cy, cz);
+                const int sh = 16 * (c & 1);
+                const unsigned slot = (atomicAdd(&cnt[c >> 1], 1u << sh) >> sh) & 0xffffu;
+                float tag = __int_as_float(excl > 0 ? int(unsigned(a) / excl32) : a);
+                PW[slot] = make_float4(wx, wy, wz, tag);
+                if (po)
+                    PO[slot] = make_float4(x[u], y[u], z[u], tag);
+            }
+        }
+        const float qnan = __int_as_float(0x7fc00000);
+        for (int a = n + tid; a < n_pad; a += THREADS) {
+            PW[a] = make_float4(qnan, qnan, qnan, __int_as_float(-1));
+            if (po)
+                PO[a] = make_float4(qnan, qnan, qnan, __int_as_float(-1));
+        }
+        __threadfence_block();
+        __syncthreads();
+        cell_tile_boxes<THREADS>(PW, bb, bb16, frame, n_pad, tid);
     }
+    // one atomicMax per wave and LAUNCH: the maximum over all the block's frames
+    unsigned bits = __float_as_uint(m);
+    for (int off = 32; off > 0; off >>= 1)
+        bits = max(bits, (unsigned)__shfl_xor((int)bits, off));
+    if ((tid & 63) == 0 && bits)
+        atomicMax(maxabs_bits, bits);
 }
 
 // Exact re-evaluation of one pair with the contract arithmetic on the ORIGINAL coordinates.
