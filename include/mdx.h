@@ -705,6 +705,53 @@ int mdx_vhd_result(mdx_vhd_t h, int64_t *counts);
 int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations);
 int mdx_vhd_enable_timing(mdx_vhd_t h, int on);
 
+/* ---- pair residence: contact survival functions --------------------------------------------------------------------
+ * Sets, rows, `same`, dims, frames, lags, origin_step and zero_dims as for mdx_vhd_*.  Per frame f and pair (i of set 1,
+ * j of set 2, both at frame f; with `same` the ordered pairs (i, j) and (j, i) both count and i == j does not), in
+ * float64 with separate multiply and add (float32 coordinates are widened before any arithmetic):
+ *     d = x2_j - x1_i;  w = d - L * rint(d * (1.0 / L)), +0.0 for a dropped component;
+ *     r2 = (wx*wx + wy*wy) + wz*wz;  the pair is a contact where r2 <= cutoff * cutoff (a NaN r2 is none).
+ * With C(f) the set of contacts of frame f:  contacts[f] = |C(f)|, and per lag k, summed over the origins f0 of the
+ * lag (f0 % origin_step == 0, f0 + lags[k] analysed):
+ *     origin_counts[k] += |C(f0)|;  intermittent[k] += |C(f0) & C(f0 + lags[k])|;
+ *     continuous[k] += |C(f0) & C(f0 + 1) & ... & C(f0 + lags[k])|  (every analysed frame in between).
+ * cutoff: positive, finite, at most half the shortest kept box length.  max_neighbors (1 ... 64): the contacts a row i
+ * may hold in one frame.  A row that would hold more is never truncated silently: mdx_prs_synchronize, mdx_prs_result
+ * and mdx_prs_contacts fail with MDX_ERR_INVALID_VALUE (the message names max_neighbors and the largest row seen)
+ * until mdx_prs_reset.  continuous == 0: only the frames a lag away from an origin are visited and continuous[] stays
+ * zero.  All results are integers and identical across the three input routes, across any split of the frames into
+ * calls or slabs, and after a reset (csrc/mdx_residence_device.hpp).  The engine keeps max(lags) + one slab of frames
+ * of contact lists in HBM, (max_neighbors + 3) * n1 * 4 bytes each.  A handle touches its device with the first frame:
+ * mdx_prs_create and every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_prs *mdx_prs_t;
+int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, double cutoff, int n_lags,
+                   const int64_t *lags, int64_t origin_step, const double *dims, int zero_dims, int max_neighbors,
+                   int continuous);
+int mdx_prs_destroy(mdx_prs_t h);
+/* Forgets the frames seen, the history and an overflowing row, and zeroes the results. */
+int mdx_prs_reset(mdx_prs_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history).  The results do
+ * not depend on it.  Only before the first frame. */
+int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n1 + n2, or n1 with same. */
+int mdx_prs_accumulate(mdx_prs_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_prs_synchronize). */
+int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_prs_accumulate_traj(mdx_prs_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_prs_synchronize(mdx_prs_t h);
+/* intermittent, continuous, origin_counts: int64 [n_lags] each. */
+int mdx_prs_result(mdx_prs_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts);
+/* out: int64 [n], the contacts of the first n frames seen. */
+int mdx_prs_contacts(mdx_prs_t h, int64_t *out, int64_t n);
+/* evaluations: the contract's pair count so far, frames x (n1 * n2 - (same ? n1 : 0)); max_row: the most contacts a
+ * row held in one frame (beyond max_neighbors: the results are refused). */
+int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *max_row);
+int mdx_prs_enable_timing(mdx_prs_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1041,6 +1041,95 @@ class DistinctVanHoveEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value}
 
 
+class PairResidenceEngine(_Engine):
+    """``mdx_prs_*``: per frame the pairs of points (``j != i`` with ``same``) whose minimum-image distance lies
+    within ``cutoff`` (``r2 <= cutoff * cutoff`` in float64), and per lag the sizes of the intersections of an origin's
+    contact set with the set a lag later (intermittent) and with every set up to there (continuous), summed over the
+    origins that are multiples of ``origin_step``.  Incoming rows are set 1 then set 2, or set 1 alone with ``same``.
+    A row may hold ``max_neighbors`` contacts in one frame; one that would hold more makes ``synchronize()``,
+    ``result()`` and ``contacts()`` raise ``ValueError`` until ``reset()``.  The device is first touched by the first
+    frame, so the argument errors (``ValueError``) need none."""
+
+    _destroy = "mdx_prs_destroy"
+    TILE = 256          # set-1 points per block (PRS_TILE of csrc/mdx_residence_device.hpp)
+    JCHUNK = 1024       # set-2 points per block (PRS_JCHUNK)
+    MAX_NEIGHBORS = 64  # slots of a row at most (PRS_MAX_NEIGHBORS)
+
+    def __init__(self, n1, n2, cutoff, lags, dims, *, same=False, origin_step=1, zero_dims=0, max_neighbors=32,
+                 continuous=True, dev=0, timing=False):
+        self.n1, self.n2, self.same = int(n1), int(n2), bool(same)
+        self.n_rows = self.n1 if self.same else self.n1 + self.n2
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.max_neighbors, self.continuous = int(max_neighbors), bool(continuous)
+        h = c_void_p()
+        check(lib().mdx_prs_create(byref(h), dev, self.n1, self.n2, int(self.same), float(cutoff), self.n_lags,
+                                   _ptr(self.lags), int(origin_step), _ptr(self.dims), int(zero_dims),
+                                   self.max_neighbors, int(self.continuous)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_prs_enable_timing(h, 1))
+
+    def set_slab_frames(self, frames):
+        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
+        before the first frame."""
+        check(lib().mdx_prs_set_slab_frames(self.handle, int(frames)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows of set 1 then set 2 (set 1 alone with ``same``)."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_prs_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM (``index``: rows of a frame in incoming order).  Asynchronous on the engine's stream:
+        ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_prs_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                              0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_prs_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                            0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_prs_synchronize(self.handle))
+
+    def result(self):
+        """``{"intermittent", "continuous", "origin_counts"}``, ``int64 [n_lags]`` each."""
+        out = {key: np.zeros(self.n_lags, dtype=np.int64) for key in ("intermittent", "continuous", "origin_counts")}
+        check(lib().mdx_prs_result(self.handle, _ptr(out["intermittent"]), _ptr(out["continuous"]),
+                                   _ptr(out["origin_counts"])))
+        return out
+
+    def contacts(self):
+        """``int64 [frames]``: the contacts of every frame seen."""
+        frames = c_int64()
+        check(lib().mdx_prs_stats(self.handle, None, None, byref(frames), None, None))
+        out = np.zeros(frames.value, dtype=np.int64)
+        check(lib().mdx_prs_contacts(self.handle, _ptr(out), len(out)))
+        return out
+
+    def reset(self):
+        check(lib().mdx_prs_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames, ev, row = c_int64(), c_double(), c_int64(), c_int64(), c_int64()
+        check(lib().mdx_prs_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev), byref(row)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value,
+                "max_row": row.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

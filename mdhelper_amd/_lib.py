@@ -229,6 +229,21 @@ _SIGNATURES = {
     "mdx_vhd_result": (c_int, [_vp, _vp]),
     "mdx_vhd_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_vhd_enable_timing": (c_int, [_vp, c_int]),
+    # pair residence (contact survival functions)
+    "mdx_prs_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_double, c_int, _vp, c_int64, _vp, c_int,
+                               c_int, c_int]),
+    "mdx_prs_destroy": (c_int, [_vp]),
+    "mdx_prs_reset": (c_int, [_vp]),
+    "mdx_prs_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_prs_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_prs_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_prs_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_prs_synchronize": (c_int, [_vp]),
+    "mdx_prs_result": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_prs_contacts": (c_int, [_vp, _vp, c_int64]),
+    "mdx_prs_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64)]),
+    "mdx_prs_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

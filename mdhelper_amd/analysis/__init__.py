@@ -3,7 +3,8 @@
 from . import base, dynamics, electrostatics, polymer, profile, structure, transport  # noqa: F401
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
-from .dynamics import DistinctVanHove, VanHove, calculate_non_gaussian_parameter  # noqa: F401
+from .dynamics import (DistinctVanHove, PairResidence, VanHove, calculate_non_gaussian_parameter,  # noqa: F401
+                       calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
 from .polymer import EndToEndVector, Gyradius, RouseModes, SingleChainStructureFactor  # noqa: F401
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401

@@ -1,7 +1,9 @@
 """
 Real-space dynamics: ``VanHove`` — the self part of the van Hove function ``G_s(r, t)``, the distribution of
 displacement magnitudes after a lag and the non-Gaussian parameter — ``calculate_non_gaussian_parameter``, and
-``DistinctVanHove`` — the distinct part ``G_d(r, t)``, the time-dependent pair distribution.
+``DistinctVanHove`` — the distinct part ``G_d(r, t)``, the time-dependent pair distribution — and ``PairResidence`` —
+the intermittent and continuous survival functions of the contacts between two groups (ion-pair lifetimes, residence
+times) with ``calculate_residence_time``.
 
 The reference package has no counterpart; this sits next to ``IntermediateScatteringFunction(incoherent=True)``
 (``F_s(q, t)``, the Fourier transform of ``G_s``) and the mean squared displacements of the correlation
@@ -13,7 +15,9 @@ integer histograms and adds ``r^2`` and ``r^4`` per point in frame order.  Count
 count for count; the moments have a fixed summation order (csrc/mdx_vanhove_device.hpp).  ``DistinctVanHove``
 feeds the same blocks to the distinct van Hove engine (``mdx_vhd_*``), which keeps a history of float32 frames in HBM
 and bins the minimum-image distance of every pair of points for every (origin, lag) frame pair into integer
-histograms (csrc/mdx_vanhove_distinct_device.hpp).
+histograms (csrc/mdx_vanhove_distinct_device.hpp).  ``PairResidence`` feeds them to the pair residence engine
+(``mdx_prs_*``), which keeps a history of capped per-atom contact lists in HBM and counts, per lag, the contacts of an
+origin that are there again, or still (csrc/mdx_residence_device.hpp).
 """
 
 from __future__ import annotations
@@ -432,3 +436,243 @@ class DistinctVanHove(DynamicAnalysisBase):
         self.results.vanhove = counts / (origins[:, None] * self._N1 * shell)
         with np.errstate(divide="ignore", invalid="ignore"):
             self.results.normalized = self.results.vanhove * np.prod(self._dimensions[kept]) / partners
+
+
+def calculate_residence_time(times, survival):
+    r"""
+    Residence time of a survival function as its time integral,
+
+    .. math:: \tau=\int_0^{t_\mathrm{max}}S(t)\,\mathrm dt
+
+    by the trapezoid rule over the finite leading part of ``survival`` (the values before the first NaN or
+    infinity).  The integral is truncated at the last lag: it is the residence time only where ``survival`` has
+    decayed to about zero by then, and a lower bound otherwise.
+
+    times : array-like ``[N_t]`` — the lag times, increasing
+    survival : array-like ``[N_t]`` — the survival function at those times (``results.continuous`` or
+        ``results.intermittent`` of ``PairResidence``)
+
+    Returns NaN where not even the first value is finite.
+    """
+    t = np.asarray(times, dtype=float)
+    s = np.asarray(survival, dtype=float)
+    if t.ndim != 1 or t.shape != s.shape:
+        raise ValueError("'times' and 'survival' must be one-dimensional and of one length.")
+    bad = np.flatnonzero(~np.isfinite(s))
+    n = bad[0] if len(bad) else len(s)
+    if n == 0:
+        return float("nan")
+    return float(((s[1:n] + s[:n - 1]) * np.diff(t[:n])).sum() / 2)
+
+
+class PairResidence(DynamicAnalysisBase):
+    r"""
+    Survival functions of the contacts between two groups: with :math:`h_{ij}(t)=1` where the minimum-image distance
+    of :math:`i\in1` and :math:`j\in2` is at most ``cutoff`` (:math:`j\ne i` for one set) and 0 otherwise,
+
+    .. math:: C_\mathrm{int}(t)=\frac{\langle\sum_{ij}h_{ij}(t_0)\,h_{ij}(t_0+t)\rangle_{t_0}}
+              {\langle\sum_{ij}h_{ij}(t_0)\rangle_{t_0}},\qquad
+              C_\mathrm{cont}(t)=\frac{\langle\sum_{ij}\prod_{t'=t_0}^{t_0+t}h_{ij}(t')\rangle_{t_0}}
+              {\langle\sum_{ij}h_{ij}(t_0)\rangle_{t_0}}
+
+    the intermittent function (the pair is together again, or still, after ``t``) and the continuous one (the pair
+    has not parted in any analysed frame up to ``t``), averaged over the time origins ``t_0`` of the analysed frames:
+    ion-pair lifetimes, residence times of ions at polymer sites.
+
+    Parameters
+    ----------
+    ag1 : AtomGroup — the rows of the contact lists (the averages are per atom of ``ag1``)
+    ag2 : AtomGroup, optional — the partners; ``None`` (or a group of the very same atoms in the same order): the
+        pairs of ``ag1`` with itself, ``j != i``, both ``(i, j)`` and ``(j, i)``.  A group that shares only some atoms
+        with ``ag1``, or the same atoms in another order, raises ``ValueError``
+    cutoff : float — the contact distance (Å), positive; it may not exceed half the shortest box length that takes
+        part
+    lags : array-like of int, keyword-only — lag times in frames of the analysed selection, strictly increasing,
+        non-negative
+    n_lags : int, keyword-only — shorthand for ``lags=arange(n_lags)``; with neither, every analysed frame is a lag
+    origin_step : int, keyword-only — every ``origin_step``-th analysed frame is a time origin
+    max_neighbors : int, keyword-only — the contacts an atom of ``ag1`` may have in one frame (1 ... 64).  A frame
+        with more raises ``ValueError`` at the end of ``run()``: nothing is truncated silently
+    continuous : bool, keyword-only — ``False`` skips the frames between the lags: ``results.continuous_counts`` is
+        then zero
+    dt : float, keyword-only — time between trajectory frames (ps); defaults to the trajectory's
+    dimensions : array-like ``(3,)``, keyword-only — box lengths (Å); defaults to the universe's
+    drop_axis : {0, 1, 2, "x", "y", "z"}, keyword-only — a component that takes no part (slabs, 2-D systems)
+    verbose : bool
+    device : keyword-only — the HIP device
+
+    Results
+    -------
+    ``results.times`` ``[N_t]`` (ps), ``results.n_origins`` ``[N_t]``, ``results.contacts`` ``[N_f]`` (int64, the
+    contacts of every analysed frame), ``results.coordination`` — ``contacts / N_1`` — ``results.intermittent_counts``,
+    ``results.continuous_counts`` and ``results.origin_counts`` ``[N_t]`` (int64), ``results.intermittent`` and
+    ``results.continuous`` — the counts over ``origin_counts``, NaN without a warning where that is 0 (a lag without
+    an origin, or no contact at any origin) — and ``results.units``.  ``calculate_residence_times()`` adds
+    ``results.residence_time`` and ``results.relaxation_time``.
+
+    Limits: as ``DistinctVanHove`` — a constant orthorhombic box, coordinates as given, one rank, no molecule
+    centres, evenly spaced frames forward in time, every pair of points evaluated (no cell list), no CPU fallback:
+    without a HIP device ``run()`` raises ``RuntimeError``.
+    """
+
+    def __init__(self, ag1, ag2=None, cutoff: float = None, *, lags=None, n_lags: int = None, origin_step: int = 1,
+                 max_neighbors: int = 32, continuous: bool = True, dt=None, dimensions=None, drop_axis=None,
+                 verbose: bool = True, **kwargs) -> None:
+        self.universe = ag1.universe
+        super().__init__(self.universe.trajectory, False, verbose, **kwargs)
+        if self._comm.world_size > 1:
+            raise ValueError("PairResidence runs on one rank: every lag needs every frame.")
+
+        if cutoff is None:
+            raise ValueError("'cutoff' must be given.")
+        self._cutoff = float(strip_unit(cutoff, "angstrom")[0])
+        if not (np.isfinite(self._cutoff) and self._cutoff > 0):
+            raise ValueError("'cutoff' must be positive and finite.")
+
+        if lags is not None and n_lags is not None:
+            raise ValueError("'lags' and 'n_lags' cannot both be given.")
+        if n_lags is not None:
+            if int(n_lags) < 1:
+                raise ValueError("'n_lags' must be at least 1.")
+            lags = np.arange(int(n_lags))
+        if lags is not None:
+            lags = np.atleast_1d(np.asarray(lags))
+            if lags.ndim != 1 or len(lags) == 0 or not np.issubdtype(lags.dtype, np.integer):
+                raise ValueError("'lags' must be a one-dimensional array of integers.")
+            if lags[0] < 0 or np.any(np.diff(lags) <= 0):
+                raise ValueError("'lags' must be non-negative and strictly increasing.")
+            lags = lags.astype(np.int64)
+        self._lags = lags
+        self._origin_step = int(origin_step)
+        if self._origin_step < 1:
+            raise ValueError("'origin_step' must be at least 1.")
+        self._max_neighbors = int(max_neighbors)
+        if not 1 <= self._max_neighbors <= _core.PairResidenceEngine.MAX_NEIGHBORS:
+            raise ValueError(f"'max_neighbors' must lie in [1, {_core.PairResidenceEngine.MAX_NEIGHBORS}].")
+        self._continuous = bool(continuous)
+
+        self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
+        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
+        if self._drop_axis not in {0, 1, 2, None}:
+            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
+                             "and 2 or 'z'.")
+        if dimensions is not None:
+            if len(dimensions) != 3:
+                raise ValueError("'dimensions' must have length 3.")
+            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
+        elif self.universe.dimensions is not None:
+            box = np.asarray(self.universe.dimensions, dtype=float)
+            if len(box) > 3 and not np.all(box[3:6] == 90.0):
+                raise ValueError("PairResidence needs an orthorhombic box.")
+            self._dimensions = box[:3].copy()
+        else:
+            raise ValueError("The minimum image needs the box lengths: no system dimensions found or provided.")
+        if not (np.all(np.isfinite(self._dimensions)) and np.all(self._dimensions > 0)):
+            raise ValueError("The box lengths must be positive and finite.")
+        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
+        if self._cutoff > self._dimensions[kept].min() / 2:
+            raise ValueError("'cutoff' reaches beyond half the shortest box length, where the minimum image is not "
+                             "the nearest image.")
+
+        i1 = np.asarray(ag1.indices)
+        i2 = i1 if ag2 is None else np.asarray(ag2.indices)
+        self._same = ag2 is None or np.array_equal(i1, i2)
+        if not self._same and len(np.intersect1d(i1, i2)):
+            raise ValueError("'ag1' and 'ag2' share some atoms: they must be disjoint, or the very same atoms in "
+                             "the same order.")
+        if len(i1) < 1 or len(i2) < 1:
+            raise ValueError("The groups must hold at least one atom.")
+        self._N1, self._N2 = len(i1), len(i2)
+        self._index = i1 if self._same else np.concatenate((i1, i2))
+        self._verbose = verbose
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        st = self._sliced_trajectory
+        if hasattr(st, "frames"):
+            df = np.diff(st.frames)
+            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
+                raise ValueError("The selected frames must be evenly spaced and proceed "
+                                 "forward in time.")
+            df = df[0] if len(df) else 1
+        else:
+            if st.step is not None and st.step <= 0:
+                raise ValueError("The analysis must proceed forward in time.")
+            df = st.step if st.step is not None else 1
+        lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
+        self._lags_run = lags
+        self.results.times = lags * df * self._dt
+        # the origins of a lag: the multiples of origin_step below n_frames - lag
+        self.results.n_origins = -(-np.maximum(self.n_frames - lags, 0) // self._origin_step)
+        self.results.units = {"results.times": "picosecond", "results.residence_time": "picosecond",
+                              "results.relaxation_time": "picosecond"}
+        _lib.require_device(self._device)
+        # lags without an origin never meet a frame pair: the engine gets the others
+        self._live = lags < self.n_frames
+        self._engine = None
+        if self._live.any():
+            self._engine = _core.PairResidenceEngine(
+                self._N1, self._N2, self._cutoff, lags[self._live], self._dimensions, same=self._same,
+                origin_step=self._origin_step, zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis,
+                max_neighbors=self._max_neighbors, continuous=self._continuous, dev=self._device)
+        self._batch = FrameBatcher(len(self._index),
+                                   lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
+                                   with_box=False)
+
+    def _single_frame(self) -> None:
+        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
+
+    # batched run (the frame feed of base.py), as VanHove.run
+    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
+        traj = self._trajectory
+        if not has_frame_blocks(traj):
+            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
+                               **kwargs)
+        mine = self._batched_frames(start, stop, step, frames, shard=False)
+        index = self._index
+        whole = all_particles(index, traj.n_atoms)
+        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
+                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
+        for sel in frame_blocks(mine, size):
+            if self._engine is None:
+                break
+            route, src = block_source(traj, sel, True)
+            if route == "file":
+                self._engine.accumulate_traj(src, sel, None if whole else index)
+            elif route == "hbm":
+                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
+            else:
+                self._engine.accumulate(src if whole else src[:, index])
+        self._conclude()
+        return self
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        n_t = len(self._lags_run)
+        counts = {key: np.zeros(n_t, dtype=np.int64) for key in ("intermittent", "continuous", "origin_counts")}
+        contacts = np.zeros(0, dtype=np.int64)
+        if self._engine is not None:
+            try:
+                for key, value in self._engine.result().items():
+                    counts[key][self._live] = value
+                contacts = self._engine.contacts()
+            finally:
+                self._engine.close()
+        self.results.contacts = contacts
+        self.results.coordination = contacts / self._N1
+        self.results.intermittent_counts = counts["intermittent"]
+        self.results.continuous_counts = counts["continuous"]
+        self.results.origin_counts = counts["origin_counts"]
+        norm = counts["origin_counts"].astype(float)
+        norm[norm == 0] = np.nan            # no origin, or no contact at any: NaN, without a warning
+        self.results.intermittent = counts["intermittent"] / norm
+        self.results.continuous = counts["continuous"] / norm
+
+    def calculate_residence_times(self) -> None:
+        """``results.residence_time`` from ``results.continuous`` and ``results.relaxation_time`` from
+        ``results.intermittent`` (``calculate_residence_time``: trapezoid integrals truncated at the last lag)."""
+        if "continuous" not in self.results:
+            raise RuntimeError("Call run() before calculate_residence_times().")
+        self.results.residence_time = calculate_residence_time(self.results.times, self.results.continuous)
+        self.results.relaxation_time = calculate_residence_time(self.results.times, self.results.intermittent)

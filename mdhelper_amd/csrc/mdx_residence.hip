@@ -1,0 +1,434 @@
+// mdx_residence.hip — pair residence (contact survival functions) on gfx950 (MI355X).
+//
+// Per frame the pairs (i of set 1, j of set 2, j != i when both are one set) whose minimum-image distance lies within
+// the cutoff, kept as capped per-row contact lists in a ring of frames in HBM; per lag the sizes of the intersections
+// of an origin's contact set with the set of the frame a lag later (intermittent) and with the sets of every frame up
+// to there (continuous).  Contract, cap and kernel shape: mdx_residence_device.hpp; this unit is compiled with
+// contraction off and spells its float64 operations out.
+//
+// Every result is an integer added with integer atomics, and set membership does not depend on the order in which a
+// row was filled, so the results are the same whatever route the frames take and however they are split into calls or
+// slabs.
+//
+// A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
+#include "mdx_common.hpp"
+#include "mdx_internal.hpp"
+#include "mdx_residence_device.hpp"
+#include "mdx_traj.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace mdx;
+using namespace mdx_prs_dev;
+
+namespace {
+
+constexpr int64_t PRS_HISTORY_BYTES = int64_t(256) << 20;   // what the frames of a default slab take in HBM
+
+}  // namespace
+
+struct mdx_prs {
+    int dev = 0;
+    bool ready = false;                 // the device side exists
+    hipStream_t stream = nullptr;
+    int n_lags = 0, keep = 7, max_nb = 32;
+    bool same = false, continuous = true;
+    int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
+    int64_t max_lag = 0, origin_step = 1;
+    int64_t frames_seen = 0, slab_frames = 0;   // slab_frames: 0 = the default
+    int64_t cap = 0;                    // frames the rings hold
+    int max_row = 0;                    // the largest row seen, as of the last look
+    PrsBox box;
+    double rc2 = 0.0;
+    std::vector<int64_t> lags;
+    // d_sums: uint64 [3][n_lags] intermittent, continuous, origin_counts; d_contacts: uint64, one per frame seen
+    DeviceBuffer d_lags, d_sums, d_contacts, d_max_row, d_slab, d_len, d_list, d_mask, d_stage[2], d_index;
+    std::vector<int32_t> index_host;    // what d_index holds
+    StagePipeline pipe;
+    StreamTimer timer;
+};
+
+// bytes a frame takes: its gathered rows while it is in flight, its lists and masks while it is in the rings
+static int64_t prs_frame_bytes(const mdx_prs *h)
+{
+    return 12 * h->n_rows + (int64_t(h->max_nb) + 1) * 4 * h->n1 + 8 * h->n1;
+}
+
+static int64_t prs_slab(const mdx_prs *h)
+{
+    if (h->slab_frames > 0)
+        return h->slab_frames;
+    return std::min(PRS_SLAB_MAX, std::max<int64_t>(1, PRS_HISTORY_BYTES / prs_frame_bytes(h)));
+}
+
+static int prs_zero(mdx_prs *h)
+{
+    MDX_HIP(hipMemsetAsync(h->d_sums.ptr, 0, size_t(24) * h->n_lags, h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_max_row.ptr, 0, 4, h->stream));
+    if (h->d_contacts.ptr)
+        MDX_HIP(hipMemsetAsync(h->d_contacts.ptr, 0, h->d_contacts.bytes, h->stream));
+    h->max_row = 0;
+    return MDX_OK;
+}
+
+// the device side of the handle: stream, tables and counters
+static int prs_ensure_device(mdx_prs *h)
+{
+    MDX_TRY(set_device(h->dev));
+    if (h->ready)
+        return MDX_OK;
+    if (!h->stream) {
+        MDX_TRY(stream_acquire(&h->stream));
+        h->timer.stream = h->stream;
+    }
+    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
+    MDX_TRY(h->d_sums.ensure(size_t(24) * h->n_lags));
+    MDX_TRY(h->d_max_row.ensure(4));
+    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
+    MDX_TRY(prs_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->ready = true;
+    return MDX_OK;
+}
+
+// The rings and the slab, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.
+// Nothing is in flight then (a reset waits for the stream), so growing them loses nothing.
+static int prs_ensure_rings(mdx_prs *h)
+{
+    if (h->frames_seen > 0)
+        return MDX_OK;
+    const int64_t slab = prs_slab(h), cap = h->max_lag + slab;
+    MDX_REQUIRE(cap < (int64_t(1) << 40) / prs_frame_bytes(h),
+                "a history of %lld frames of %lld points with %d neighbors each is too large", (long long)cap,
+                (long long)h->n1, h->max_nb);
+    MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * slab));
+    MDX_TRY(h->d_len.ensure(size_t(4) * h->n1 * cap));
+    MDX_TRY(h->d_list.ensure(size_t(4) * h->max_nb * h->n1 * cap));
+    if (h->continuous)
+        MDX_TRY(h->d_mask.ensure(size_t(8) * h->n1 * cap));
+    h->cap = cap;
+    return MDX_OK;
+}
+
+// room for the contacts of `frames` frames; what has been counted so far moves along
+static int prs_ensure_contacts(mdx_prs *h, int64_t frames)
+{
+    if (size_t(8) * frames <= h->d_contacts.bytes)
+        return MDX_OK;
+    DeviceBuffer grown;
+    MDX_TRY(grown.ensure(std::max(size_t(8) * frames, 2 * h->d_contacts.bytes)));
+    MDX_HIP(hipMemsetAsync(grown.ptr, 0, grown.bytes, h->stream));
+    if (h->frames_seen > 0)
+        MDX_HIP(hipMemcpyAsync(grown.ptr, h->d_contacts.ptr, size_t(8) * h->frames_seen, hipMemcpyDeviceToDevice,
+                               h->stream));
+    MDX_HIP(hipStreamSynchronize(h->stream));       // nobody reads the old block any more
+    h->d_contacts.recycle();
+    h->d_contacts = grown;
+    return MDX_OK;
+}
+
+// With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
+static int prs_check_rows(mdx_prs *h)
+{
+    int32_t row = 0;
+    MDX_HIP(hipMemcpy(&row, h->d_max_row.ptr, 4, hipMemcpyDeviceToHost));
+    h->max_row = row;
+    MDX_REQUIRE(row <= h->max_nb,
+                "a row held %d contacts in one frame, more than max_neighbors = %d: raise max_neighbors or lower the "
+                "cutoff (reset starts over)", row, h->max_nb);
+    return MDX_OK;
+}
+
+// n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
+static int prs_accumulate_rows(mdx_prs *h, const float *d_pos, int64_t src_rows, const int *d_index, int64_t n_rows,
+                               int64_t n_frames)
+{
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n_rows, (long long)h->n_rows);
+    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
+    MDX_TRY(prs_ensure_contacts(h, h->frames_seen + n_frames));
+    const int n = (int)h->n_rows, n1 = (int)h->n1;
+    const int64_t slab = std::min(prs_slab(h), h->cap - h->max_lag);
+    const int64_t n_jchunks = ceil_div(h->n2, PRS_JCHUNK);
+    const int64_t blocks = ceil_div(h->n1, PRS_TILE) * n_jchunks;
+    const int64_t walk_tiles = ceil_div(h->n1, PRS_WALK_THREADS);
+    hipEvent_t ev = h->timer.begin();
+    for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
+        const int64_t nf = std::min(slab, n_frames - s0);
+        const float *pos = d_pos + s0 * src_rows * 3;
+        const int64_t f_lo = h->frames_seen;
+        hipLaunchKernelGGL(prs_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
+                           0, h->stream, pos, src_rows, d_index, n, h->d_slab.as<float>());
+        // the rows of the new frames start empty: their ring slots are one range, or two where the ring wraps
+        const int64_t first = f_lo % h->cap, head = std::min(nf, h->cap - first);
+        MDX_HIP(hipMemsetAsync(h->d_len.as<int>() + first * n1, 0, size_t(4) * n1 * head, h->stream));
+        if (nf > head)
+            MDX_HIP(hipMemsetAsync(h->d_len.ptr, 0, size_t(4) * n1 * (nf - head), h->stream));
+        const auto contact = h->keep == 7 ? prs_contact_kernel<true> : prs_contact_kernel<false>;
+        hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(PRS_THREADS), 0, h->stream,
+                           h->d_slab.as<float>(), h->cap, n, n1, (int)h->n2, h->same ? 0 : n1, h->same ? 1 : 0,
+                           (int)n_jchunks, f_lo, h->box, h->keep, h->rc2, h->max_nb, h->d_len.as<int>(),
+                           h->d_list.as<int>(), h->d_contacts.as<unsigned long long>(), h->d_max_row.as<int>());
+        // the origins that meet a new frame: multiples of origin_step in [f_lo - max_lag, f_lo + nf)
+        const int64_t o_lo = ceil_div(std::max<int64_t>(0, f_lo - h->max_lag), h->origin_step);
+        const int64_t o_hi = ceil_div(f_lo + nf, h->origin_step);
+        const auto walk = h->continuous ? prs_walk_kernel<true> : prs_walk_kernel<false>;
+        for (int64_t o = o_lo; o < o_hi; o += PRS_WALK_ORIGINS) {
+            const int64_t n_o = std::min<int64_t>(PRS_WALK_ORIGINS, o_hi - o);
+            hipLaunchKernelGGL(walk, dim3((unsigned)walk_tiles, (unsigned)n_o), dim3(PRS_WALK_THREADS), 0, h->stream,
+                               h->cap, n1, h->max_nb, h->d_len.as<int>(), h->d_list.as<int>(),
+                               h->d_mask.as<unsigned long long>(), h->d_lags.as<int64_t>(), h->n_lags, h->max_lag, o,
+                               h->origin_step, f_lo, nf, h->d_sums.as<unsigned long long>());
+        }
+        h->frames_seen += nf;
+    }
+    h->timer.end(ev);
+    MDX_HIP(hipGetLastError());
+    return MDX_OK;
+}
+
+extern "C" {
+
+int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, double cutoff, int n_lags,
+                   const int64_t *lags, int64_t origin_step, const double *dims, int zero_dims, int max_neighbors,
+                   int continuous)
+{
+    MDX_REQUIRE(out && lags && dims, "NULL argument");
+    MDX_REQUIRE(n_lags >= 1, "lags must hold at least one lag");
+    MDX_REQUIRE(n_lags < (1 << 24), "at most 2^24 lags");
+    MDX_REQUIRE(origin_step >= 1, "origin_step must be at least 1");
+    MDX_REQUIRE(zero_dims >= 0 && zero_dims < 7, "zero_dims must leave at least one component");
+    MDX_REQUIRE(max_neighbors >= 1 && max_neighbors <= PRS_MAX_NEIGHBORS, "max_neighbors must lie in [1, %d]",
+                PRS_MAX_NEIGHBORS);
+    MDX_REQUIRE(n1 >= 1 && n2 >= 1, "both sets must hold at least one point");
+    MDX_REQUIRE(!same || n1 == n2, "same: both sets are one set, but n1 = %lld and n2 = %lld", (long long)n1,
+                (long long)n2);
+    const int64_t limit = (int64_t(1) << 31) / 3;
+    MDX_REQUIRE(n1 < limit && n2 < limit && (same ? n1 : n1 + n2) < limit,
+                "the sets must hold fewer than 2^31 / 3 points");
+    MDX_REQUIRE(ceil_div(n1, PRS_TILE) * ceil_div(n2, PRS_JCHUNK) < (int64_t(1) << 31),
+                "%lld x %lld points are too many pairs for one launch", (long long)n1, (long long)n2);
+    for (int k = 0; k < n_lags; ++k) {
+        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
+        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
+    }
+    for (int c = 0; c < 3; ++c)
+        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
+    MDX_REQUIRE(cutoff > 0.0 && std::isfinite(cutoff), "cutoff must be positive and finite");
+    double shortest = HUGE_VAL;
+    for (int c = 0; c < 3; ++c)
+        if (!(zero_dims >> c & 1))
+            shortest = std::min(shortest, dims[c]);
+    // beyond half a box length the minimum image is not the nearest image
+    MDX_REQUIRE(cutoff <= shortest / 2, "cutoff %g reaches beyond half the shortest box length %g", cutoff, shortest);
+    mdx_prs *h = new mdx_prs();
+    h->dev = dev;
+    h->n1 = n1;
+    h->n2 = n2;
+    h->same = same != 0;
+    h->continuous = continuous != 0;
+    h->n_rows = same ? n1 : n1 + n2;
+    h->n_lags = n_lags;
+    h->keep = 7 & ~zero_dims;
+    h->max_nb = max_neighbors;
+    h->origin_step = origin_step;
+    h->max_lag = lags[n_lags - 1];
+    h->lags.assign(lags, lags + n_lags);
+    h->rc2 = cutoff * cutoff;
+    for (int c = 0; c < 3; ++c) {
+        h->box.L[c] = dims[c];
+        h->box.inv[c] = 1.0 / dims[c];
+    }
+    *out = h;
+    return MDX_OK;
+}
+
+int mdx_prs_destroy(mdx_prs_t h)
+{
+    if (!h)
+        return MDX_OK;
+    if (h->stream) {
+        (void)hipSetDevice(h->dev);
+        (void)hipStreamSynchronize(h->stream);
+        h->timer.destroy();
+        h->pipe.destroy();      // waits for its copy stream
+        for (DeviceBuffer *b : {&h->d_lags, &h->d_sums, &h->d_contacts, &h->d_max_row, &h->d_slab, &h->d_len,
+                                &h->d_list, &h->d_mask, &h->d_stage[0], &h->d_stage[1], &h->d_index})
+            b->recycle();
+        stream_release(h->stream);
+    }
+    delete h;
+    return MDX_OK;
+}
+
+int mdx_prs_reset(mdx_prs_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->frames_seen = 0;         // the history starts over with the next frame
+    h->max_row = 0;
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.reset();
+    MDX_TRY(prs_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
+int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    MDX_REQUIRE(frames >= 0 && frames <= PRS_SLAB_MAX, "frames must lie in [0, %lld]", (long long)PRS_SLAB_MAX);
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_prs_set_slab_frames must be called before the first frame");
+    h->slab_frames = frames;
+    return MDX_OK;
+}
+
+int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && d_pos, "NULL argument");
+    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
+    const int64_t n = index ? n_index : n_atoms;
+    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(prs_ensure_device(h));
+    MDX_TRY(prs_ensure_rings(h));
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    return prs_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+}
+
+int mdx_prs_accumulate(mdx_prs_t h, const float *pos, int64_t n, int64_t n_frames)
+{
+    MDX_REQUIRE(h && pos, "NULL argument");
+    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
+    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(prs_ensure_device(h));
+    MDX_TRY(prs_ensure_rings(h));
+    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
+                                                pos + f0 * n * 3, size_t(12) * n * nf);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return prs_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+// Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
+// the file's first n_index particles.
+int mdx_prs_accumulate_traj(mdx_prs_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && traj, "NULL handle");
+    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
+    Trajectory *t = mdx_traj_internal(traj);
+    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
+    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the sets hold %lld", (long long)n, (long long)h->n_rows);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)t->n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(prs_ensure_device(h));
+    MDX_TRY(prs_ensure_rings(h));
+    MDX_TRY(h->pipe.ensure());
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
+                                  &d_index));
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
+            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return prs_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+int mdx_prs_synchronize(mdx_prs_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return prs_check_rows(h);
+}
+
+int mdx_prs_result(mdx_prs_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts)
+{
+    MDX_REQUIRE(h && intermittent && continuous && origin_counts, "NULL argument");
+    MDX_TRY(prs_ensure_device(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.collect();
+    MDX_TRY(prs_check_rows(h));
+    // uint64 sums of at most frames x n1 x max_neighbors < 2^63 each: they fit an int64
+    const size_t bytes = size_t(8) * h->n_lags;
+    const char *sums = h->d_sums.as<char>();
+    MDX_HIP(hipMemcpy(intermittent, sums, bytes, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(continuous, sums + bytes, bytes, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(origin_counts, sums + 2 * bytes, bytes, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_prs_contacts(mdx_prs_t h, int64_t *out, int64_t n)
+{
+    MDX_REQUIRE(h && (out || n == 0), "NULL argument");
+    MDX_REQUIRE(n >= 0 && n <= h->frames_seen, "%lld frames asked for, %lld seen", (long long)n,
+                (long long)h->frames_seen);
+    if (n == 0)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    MDX_TRY(prs_check_rows(h));
+    MDX_HIP(hipMemcpy(out, h->d_contacts.ptr, size_t(8) * n, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *max_row)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (h->ready) {
+        MDX_TRY(set_device(h->dev));
+        MDX_HIP(hipStreamSynchronize(h->stream));
+        h->timer.collect();
+        int32_t row = 0;
+        MDX_HIP(hipMemcpy(&row, h->d_max_row.ptr, 4, hipMemcpyDeviceToHost));
+        h->max_row = row;
+    }
+    if (launches) *launches = h->timer.launches;
+    if (kernel_ms) *kernel_ms = h->timer.total_ms;
+    if (frames) *frames = h->frames_seen;
+    if (evaluations) *evaluations = h->frames_seen * (h->n1 * h->n2 - (h->same ? h->n1 : 0));
+    if (max_row) *max_row = h->max_row;
+    return MDX_OK;
+}
+
+int mdx_prs_enable_timing(mdx_prs_t h, int on)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->timer.enabled = on != 0;
+    return MDX_OK;
+}
+
+}  // extern "C"
