@@ -453,9 +453,18 @@ static int launch_tiles(mdx_rdf *h, RdfArgs &a, int mode, int ipt, bool pbc, boo
 
 // Cell-sorted path (mdx_rdf_cell.hpp): sort + tile boxes per frame, then the culled pair kernel.
 // d_tri != nullptr: triclinic frames, d_tri = their cell matrices [n_frames][9] (d_boxes unused)
+// The pair kernel's step that leaves when none of its 64 pairs is a candidate (cell_step<..., SKIP>) pays one
+// scalar branch per step for the tail of the empty steps.  Fitted to the A/B series of round 7 (NOTES.md), a skipped
+// tail is worth 0.44 of a step and the branch costs 0.05: the step pays where more than 0.12 of the steps of the
+// shifted row loops are empty.  That share falls as the range grows against the 64-particle units — modelled at the
+// bench's density (scripts/cull_model.py): 0.17 at a range end of 0.22 L (C2(i): faster), 0.14 at 0.30 L, 0.12 at
+// 0.35 L, 0.07 at 0.5 L (C2(ii): slower) — so the launch takes the step up to 0.3 of the SHORTEST box length over its
+// frames and the unconditional tail beyond.  min_edge: that length (0 = not known: unconditional tail).
+constexpr float CELL_SKIP_MAX_RANGE = 0.3f;
+
 static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
                            int64_t n2, const float *d_boxes, int64_t n_frames, bool self, bool excl,
-                           const float *d_tri = nullptr)
+                           const float *d_tri = nullptr, float min_edge = 0.f)
 {
     const bool tri = d_tri != nullptr;
     const int64_t n1p = ceil_div(n1, 128) * 128, n2p = ceil_div(n2, 128) * 128;
@@ -501,9 +510,12 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
         lds = sizeof(float4) * 256;
     const bool lower = h->edges.front() > 0.0;
     void (*kern)(CellArgs) = nullptr;
+    // (triclinic launches keep the step: their range ends below half the smallest cell height)
+    const bool skip = tri || (float)h->edges.back() <= CELL_SKIP_MAX_RANGE * min_edge;
 #define MDX_CELL_PICK(E, L)                                                                     \
     kern = tri ? (gh ? rdf_cell_pair_kernel<E, L, 1, true> : rdf_cell_pair_kernel<E, L, 0, true>) \
-               : (gh ? rdf_cell_pair_kernel<E, L, 1> : rdf_cell_pair_kernel<E, L, 0>)
+               : (gh ? rdf_cell_pair_kernel<E, L, 1>                                             \
+                     : (skip ? rdf_cell_pair_kernel<E, L, 0, false, true> : rdf_cell_pair_kernel<E, L, 0, false, false>))
     if (excl && lower) MDX_CELL_PICK(true, true);
     else if (excl) MDX_CELL_PICK(true, false);
     else if (lower) MDX_CELL_PICK(false, true);
@@ -758,8 +770,9 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
     return MDX_OK;
 }
 
+// min_edge: the shortest box length over the frames (accumulate_cell), 0 where the caller has no boxes
 static int accumulate_ortho(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
-                            int64_t n2, const float *d_boxes, int64_t n_frames)
+                            int64_t n2, const float *d_boxes, int64_t n_frames, float min_edge = 0.f)
 {
     if (n_frames == 0 || n1 == 0 || n2 == 0)
         return MDX_OK;
@@ -786,7 +799,7 @@ static int accumulate_ortho(mdx_rdf *h, const float *d_pos1, int64_t n1, const f
     if (algo == MDX_RDF_ALGO_CELL && !d_boxes)
         algo = MDX_RDF_ALGO_FILTER_F32;   // the cell grid is defined by the periodic box
     if (algo == MDX_RDF_ALGO_CELL)
-        return accumulate_cell(h, d_pos1, n1, d_pos2, n2, d_boxes, n_frames, self, excl);
+        return accumulate_cell(h, d_pos1, n1, d_pos2, n2, d_boxes, n_frames, self, excl, nullptr, min_edge);
     const int ipt = (std::max(n1, n2) >= 2048) ? 2 : 1;
     const int T = 256 * ipt;
     const int64_t n1p = ceil_div(n1, T) * T, n2p = ceil_div(n2, T) * T;
@@ -1097,9 +1110,12 @@ static int accumulate_device_points(mdx_rdf *h, const float *d_pos1, int64_t n1,
             ++f1;
         const float *p1 = d_pos1 + f0 * n1 * 3;
         const float *p2 = d_pos2 ? d_pos2 + f0 * n2 * 3 : nullptr;
-        if (ortho)
-            MDX_TRY(accumulate_ortho(h, p1, n1, p2, n2, d_boxes + f0 * 6, f1 - f0));
-        else
+        if (ortho) {
+            float min_edge = h_boxes[6 * f0];
+            for (int64_t f = f0; f < f1; ++f)
+                min_edge = std::min(min_edge, std::min(h_boxes[6 * f], std::min(h_boxes[6 * f + 1], h_boxes[6 * f + 2])));
+            MDX_TRY(accumulate_ortho(h, p1, n1, p2, n2, d_boxes + f0 * 6, f1 - f0, min_edge));
+        } else
             MDX_TRY(accumulate_triclinic(h, p1, n1, p2, n2, h_boxes + 6 * f0, f1 - f0));
         f0 = f1;
     }

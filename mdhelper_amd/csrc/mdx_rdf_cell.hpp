@@ -626,9 +626,9 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
     cx.inv_wf = c.inv_w;
 }
 
-// One float32 distance evaluation + binning.  The bin arithmetic is unconditional (after
-// culling nearly every wave step holds a candidate, so a branch around it would always be
-// taken); only the histogram add is predicated.  An undecided pair is not evaluated here, a
+// One float32 distance evaluation + binning.  Without SKIP the bin arithmetic is unconditional
+// and only the histogram add is predicated; with SKIP (below) a step without any candidate
+// leaves before it.  An undecided pair is not evaluated here, a
 // lane or two at a time with fp64 temporaries in the middle of the hot loop: it is appended to
 // the wave's list in LDS (slot = list length + rank among the undecided lanes; the length lives
 // in a scalar register) and cell_flush evaluates the list 64 pairs at a time.  Measured at C2:
@@ -636,17 +636,85 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
 // detour with one or two lanes active) and 66 KB of code (the detour inlined ~50 times).
 // MODE: 0 per-wave LDS histograms, 1 global histogram (bin tables too large for LDS).
 // TAGS: 0 no exclusion, 1 compare exclusion tags.
-template <bool LOWER, int TAGS, int MODE, typename Hist>
+// SKIP (MODE 0 only): a step none of whose 64 pairs is a candidate leaves right after the candidate
+// test.  Rows are culled against the BOX of the 64 i particles, so a row can lie within reach of the box
+// and of none of the particles: modelled at C2(i), 0.156 of the steps of the shifted row loops are such
+// (scripts/cull_model.py, third model), and the square root, the bin arithmetic and the LDS add behind
+// the test are half of a step's issue cycles.  The steps of the straddling loops take the per-pair
+// image and keep the unconditional tail (SKIP = false), as does MODE 1.
+//
+// The tail of a SKIP step (v_sqrt_f32, v_fma_f32, v_fract_f32 and what follows) lives inside the asm
+// block, behind s_cbranch_execz; r2 is still formed in C++, so the compiler goes on hoisting the next
+// step's subtractions and fmas over this step's block.  Wait states inside the block are placed by
+// hand: one (s_nop 0) between v_sqrt_f32 and the v_fma_f32 that reads its result (transcendental
+// result read by a non-transcendental VALU instruction); none between the v_cmpx that writes EXEC and
+// s_cbranch_execz — the required-wait-state table of the CDNA ISA manuals lists EXEC written by a VALU
+// instruction only against VALU instructions that read EXECZ as a constant, DPP and v_readlane; a
+// scalar branch on EXECZ is interlocked by the hardware (the compiler's own lowering of a pixel kill
+// is v_cmpx + s_cbranch_execnz back to back).
+//
+// Invariant the skipped step relies on: the mask of undecided lanes is ZERO after a skipped step
+// although the v_cmp that computes it did not run.  On this ISA family V_CMPX writes its result to
+// EXEC AND to its scalar destination; in the VOP3 encoding that destination is any SGPR pair.  The
+// last candidate test therefore names the mask register as its destination: when it leaves EXEC = 0
+// it has left mask = 0 as well, and the cold append branch below is not taken.  No scalar instruction
+// per step, no register live across steps.  (The redo of an overflowed unit, cell_slow_unit,
+// classifies with the same float32 operations in C++ and looks at candidates only: a step skipped
+// here is a step without undecided lanes there.  It needs no counterpart of the skip.)
+#define MDX_CELL_SKIP_TAIL                                                                          \
+    "s_cbranch_execz .Lmdx_cell_skip%=\n\t"                                                          \
+    "v_sqrt_f32_e32 %[tmp], %[r2]\n\ts_nop 0\n\tv_fma_f32 %[tmp], %[tmp], %[iw], %[p0]\n\t"          \
+    "v_fract_f32_e32 %[t], %[tmp]\n\t"                                                              \
+    "v_cmp_le_f32_e64 %[mt], %[sw], %[t]\n\tv_cvt_i32_f32_e32 %[tmp], %[tmp]\n\t"                   \
+    "s_andn2_b64 exec, exec, %[mt]\n\tv_lshl_add_u32 %[tmp], %[tmp], %[sh], %[hb]\n\t"              \
+    "ds_add_u32 %[tmp], %[w]\n"                                                                     \
+    ".Lmdx_cell_skip%=:\n\ts_mov_b64 exec, -1"
+template <bool LOWER, int TAGS, int MODE, bool SKIP, typename Hist>
 __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist &hist, float fx,
                                  float fy, float fz, int tag_i, int tag_j, unsigned i_base,
                                  unsigned j_idx, unsigned w, CellWave &wv)
 {
     float r2 = __fmaf_rn(fz, fz, __fmaf_rn(fy, fy, fx * fx));
+    unsigned long long m_todo;
+    if (MODE == 0 && SKIP) {
+        const unsigned hbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)hist.h;
+        const int hshift = cell_hist_shift(hist) + 2;   // byte offset of a bin = bin << (2 + log2 R)
+        unsigned tmp;
+        float t;
+        // the candidate tests of the block below; the LAST one in its VOP3 form, writing the mask register too
+        if (LOWER && TAGS)
+            asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_le_f32_e32 %[lo], %[r2]\n\tv_cmpx_ne_u32_e64 %[mt], %[ti], %[tj]\n\t"
+                         MDX_CELL_SKIP_TAIL
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
+                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w),
+                           [p0] "v"(c.pos0), [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift), [ti] "v"(tag_i), [tj] "v"(tag_j)
+                         : "memory");
+        else if (LOWER)
+            asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_le_f32_e64 %[mt], %[lo], %[r2]\n\t"
+                         MDX_CELL_SKIP_TAIL
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
+                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w),
+                           [p0] "v"(c.pos0), [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
+                         : "memory");
+        else if (TAGS)
+            asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_ne_u32_e64 %[mt], %[ti], %[tj]\n\t"
+                         MDX_CELL_SKIP_TAIL
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
+                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w), [p0] "v"(c.pos0),
+                           [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift), [ti] "v"(tag_i), [tj] "v"(tag_j)
+                         : "memory");
+        else
+            asm volatile("v_cmpx_gt_f32_e64 %[mt], %[hi], %[r2]\n\t"
+                         MDX_CELL_SKIP_TAIL
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
+                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w), [p0] "v"(c.pos0),
+                           [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
+                         : "memory");
+    } else {
     // pos = (sqrt(r2) - r0) / width - eta; raw v_sqrt_f32 (a denormal r2 ends on the exact path).
     // "Farther than eta from both neighbouring bin edges" is fract(pos) < 1 - 2 eta (see cell_filter).
     const float pos = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.inv_w, c.pos0);
     const float t = __builtin_amdgcn_fractf(pos);
-    unsigned long long m_todo;
     if (MODE == 1) {   // global histogram (bin tables too large for LDS): compiler-generated masks
         bool cand = LOWER ? (r2 < c.cand_hi && r2 >= c.cand_lo) : (r2 < c.cand_hi);
         if (TAGS)
@@ -702,6 +770,7 @@ __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist
                            [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
                          : "memory");
     }
+    }
     // An undecided pair is not evaluated here, a lane or two at a time with fp64 temporaries in the
     // middle of the hot loop: it is appended to the wave's list in LDS (slot = list length + rank
     // among the undecided lanes; the length lives in a scalar register) and cell_flush evaluates the
@@ -724,6 +793,7 @@ __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist
         }
     }
 }
+#undef MDX_CELL_SKIP_TAIL
 
 // Exact arithmetic for the listed pairs, 64 at a time, one per lane (the list is wave-private).
 template <typename Hist>
@@ -800,7 +870,9 @@ __device__ inline void cell_slow_unit(const CellHot &c, const CellArgs &a, const
     }
 }
 
-template <bool EXCL, bool LOWER, int MODE, bool TRI = false>
+// SKIP: the steps of the shifted row loops leave behind their candidate test when no lane holds a candidate
+// (cell_step); chosen per launch by the host (mdx_rdf.hip, CELL_SKIP_MAX_RANGE), ignored by MODE 1.
+template <bool EXCL, bool LOWER, int MODE, bool TRI = false, bool SKIP = true>
 // (seven waves per SIMD: 72 VGPRs with 12 more bytes of scratch in the prologue than at six and 80 — +4 % at C2(i);
 // eight do not fit the LDS of seven blocks and lose to their spills)
 //
@@ -1217,8 +1289,8 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                 const unsigned mark = wv.n_todo;
                 n_units += (unsigned)__popcll(sub) + (CELL_CHUNK == 1 ? (unsigned)__popcll(sub1) : 0u);
 #define MDX_CELL_HALF(TG, P, IB, Q, JJ)                                                            \
-    if (GH) cell_step<LOWER, TG, MODE>(hot, a, hg, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), IB, (JJ), w, wv); \
-    else cell_step<LOWER, TG, MODE>(hot, a, hl, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), IB, (JJ), w, wv);
+    if (GH) cell_step<LOWER, TG, MODE, false>(hot, a, hg, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), IB, (JJ), w, wv); \
+    else cell_step<LOWER, TG, MODE, SKIP>(hot, a, hl, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), IB, (JJ), w, wv);
 // one unit: CELL_CHUNK slab rows (whole 16-byte reads: ds_read_b96 costs 8 LDS cycles,
 // ds_read_b128 4) against the i halves that survived; the global j index is scalar
 #define MDX_CELL_UNITS_CHUNKS(TG)                                                                         \
@@ -1349,8 +1421,8 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
             if ((GM) & 1) fx = fminf(fabsf(fx), hot.L[0] - fabsf(fx));                             \
             if ((GM) & 2) fy = fminf(fabsf(fy), hot.L[1] - fabsf(fy));                             \
             if ((GM) & 4) fz = fminf(fabsf(fz), hot.L[2] - fabsf(fz));                             \
-            if (GH) cell_step<LOWER, EXCL ? 1 : 0, MODE>(hot, a, hg, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0 + 64u * u, jbase + jj, w, wv); \
-            else cell_step<LOWER, EXCL ? 1 : 0, MODE>(hot, a, hl, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0 + 64u * u, jbase + jj, w, wv); \
+            if (GH) cell_step<LOWER, EXCL ? 1 : 0, MODE, false>(hot, a, hg, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0 + 64u * u, jbase + jj, w, wv); \
+            else cell_step<LOWER, EXCL ? 1 : 0, MODE, false>(hot, a, hl, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0 + 64u * u, jbase + jj, w, wv); \
         }                                                                                          \
     }
                 switch (gen) {

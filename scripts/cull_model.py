@@ -107,3 +107,55 @@ def quarter_model():
 
 
 quarter_model()
+
+
+# ---------------------------------------------------------------------------------------------
+# Third model: candidates per wave step.  A step is one j row against the 64 particles of an i unit; the row
+# loops run the rows within R of the unit's BOX.  How many of the 64 lanes (and of each 32-lane half) then hold a
+# pair within R — and how many steps hold none, which cell_step<..., SKIP> leaves behind its candidate test?
+def step_model(units=40):
+    rng = np.random.default_rng(2)
+    N, L, R = 32768, 68.94, 15.0
+    pos = rng.random((N, 3)) * L
+    a = (64 * L**3 / N) ** (1 / 3)
+    nc0 = nc1 = max(int(round(L / a)), 1); nc2 = max(int(round(16 * L / a)), 1)
+    c = np.minimum((pos / L * [nc0, nc1, nc2]).astype(int), [nc0 - 1, nc1 - 1, nc2 - 1])
+    cx, cy, cz = c[:, 0], c[:, 1].copy(), c[:, 2].copy()
+    cy = np.where(cx & 1, nc1 - 1 - cy, cy); col = cx * nc1 + cy
+    cz = np.where(col & 1, nc2 - 1 - cz, cz)
+    P = pos[np.argsort(col * nc2 + cz, kind="stable")]
+
+    def reach(I, pts):
+        """points within R of the box of the particles I, minimum image per component"""
+        lo, hi = I.min(0), I.max(0)
+        d = pts - 0.5 * (lo + hi); d -= L * np.rint(d / L)
+        g = np.maximum(0.0, np.abs(d) - 0.5 * (hi - lo))
+        return (g * g).sum(-1) <= R * R
+
+    hist = np.zeros(65, dtype=np.int64)
+    half_empty = halves = 0
+    kept = {2: 0, 8: 0}          # empty steps a finer box test (2 x 32, 8 x 8 particles) would still run
+    for t in rng.choice(N // 64, units, replace=False):
+        I = P[t * 64:(t + 1) * 64]
+        rows = P[reach(I, P)]
+        d = rows[:, None, :] - I[None]
+        d -= L * np.rint(d / L)
+        cand = (d * d).sum(-1) < R * R                       # [rows, 64 lanes]
+        hist += np.bincount(cand.sum(1), minlength=65)
+        h = cand.reshape(len(rows), 2, 32).sum(2)
+        half_empty += (h == 0).sum(); halves += h.size
+        empty = rows[cand.sum(1) == 0]
+        for parts in kept:
+            g = 64 // parts
+            kept[parts] += np.logical_or.reduce([reach(I[k * g:(k + 1) * g], empty) for k in range(parts)]).sum()
+    steps = hist.sum()
+    print("--- candidates per wave step (64-particle unit x rows within R of its box)")
+    print(f"units {units}, steps {steps}, candidate lanes {(hist * np.arange(65)).sum() / (64 * steps):.3f} of all lanes")
+    print(f"steps with no candidate: {hist[0] / steps:.3f} per 64 lanes, {half_empty / halves:.3f} per 32-lane half")
+    for k in (1, 2, 4, 8, 16, 32):
+        print(f"steps with at most {k:2d} candidates: {hist[:k + 1].sum() / steps:.3f}")
+    for parts, n in kept.items():
+        print(f"empty steps kept by a test against {parts} boxes of {64 // parts} particles: {n / max(hist[0], 1):.3f}")
+
+
+step_model()

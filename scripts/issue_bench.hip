@@ -3,13 +3,30 @@
 //     inside the kernel, printed next to the HIP-event time; run under
 //     `rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace` to get the counter-based clock as well;
 //   * SALU issue rate (independent s_add_u32 / s_and_b32 / s_lshr_b32), alone and beside VALU;
-//   * the hot step's mix: 10 plain VALU + v_sqrt_f32 + 2 v_cmp + 10 SALU per 13 VALU.
+//   * the hot step's mix: 10 plain VALU + v_sqrt_f32 + 2 v_cmp + 10 SALU per 13 VALU;
+//   * the same 13 VALU with v_cmpx + s_cbranch_execz around the seven behind the candidate test (round 7), at
+//     0, 5 of 32 and all steps empty — the price of the branch alone and what a skipped tail gives back — after a
+//     check that a skipped step leaves the mask register zero and its temporaries untouched.
 // hipcc -O2 --offload-arch=gfx950 scripts/issue_bench.hip -o /tmp/issue_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #define REP16(x) x x x x x x x x x x x x x x x x
 typedef float v2f __attribute__((ext_vector_type(2)));
-template <int MODE>
+// One step with the skip, as cell_step<..., SKIP> writes it: lanes whose r2 is below `hi` are candidates.
+__global__ void skip_check(const float *r2_in, float hi, unsigned long long *mask, float *pos)
+{
+    const float r2 = r2_in[threadIdx.x];
+    unsigned long long m;
+    float tmp = -7.f, t = 0.f;
+    asm volatile("v_cmpx_gt_f32_e64 %[mt], %[hi], %[r2]\n\ts_cbranch_execz .Lskip_check%=\n\t"
+                 "v_sqrt_f32_e32 %[tmp], %[r2]\n\ts_nop 0\n\tv_fma_f32 %[tmp], %[tmp], 1.0, 0\n\tv_fract_f32_e32 %[t], %[tmp]\n\t"
+                 "v_cmp_le_f32_e64 %[mt], 0.5, %[t]\n"
+                 ".Lskip_check%=:\n\ts_mov_b64 exec, -1"
+                 : [mt] "=&s"(m), [tmp] "+v"(tmp), [t] "+v"(t) : [hi] "s"(hi), [r2] "v"(r2) : "memory");
+    pos[threadIdx.x] = tmp;
+    if (threadIdx.x == 0) *mask = m;
+}
+template <int MODE, unsigned EMPTY = 0u>
 __global__ void kern(float *out, long long *clk, int iters)
 {
     float a0 = threadIdx.x, a1 = 1.f, a2 = 2.f, a3 = 3.f, a4 = 4.f, a5 = 5.f, a6 = 6.f, a7 = 7.f;
@@ -59,6 +76,17 @@ __global__ void kern(float *out, long long *clk, int iters)
             REP16(asm volatile("v_sub_u32 %0, %0, %8\n v_cvt_f32_i32 %1, %0\n v_sub_u32 %2, %2, %8\n v_cvt_f32_i32 %3, %2\n"
                                "v_sub_u32 %4, %4, %8\n v_cvt_f32_i32 %5, %4\n v_sub_u32 %6, %6, %8\n v_cvt_f32_i32 %7, %6\n"
                                : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7) : "v"(b), "v"(c));)
+        } else if (MODE == 8) {   // the hot step with the skip: 32 steps per turn, bit k of EMPTY = step k has no candidate
+            const float pass = 3e38f, fail = -1.f;   // r2 stays finite and positive: every lane passes or none
+#pragma unroll
+            for (int k = 0; k < 32; ++k)
+                asm volatile("v_sub_f32 %0, %0, %8\n v_sub_f32 %1, %1, %8\n v_sub_f32 %2, %2, %8\n v_mul_f32 %3, %0, %0\n"
+                             "v_fma_f32 %3, %1, %1, %3\n v_fma_f32 %3, %2, %2, %3\n v_cmpx_gt_f32_e64 vcc, %10, %3\n"
+                             "s_cbranch_execz .Lbench_skip%=\n v_sqrt_f32 %4, %3\n s_nop 0\n v_fma_f32 %4, %4, %8, %9\n"
+                             "v_fract_f32 %5, %4\n v_cmp_gt_f32 vcc, %5, %9\n v_cvt_i32_f32 %6, %4\n v_lshlrev_b32 %7, 2, %6\n"
+                             ".Lbench_skip%=:\n s_mov_b64 exec, -1\n"
+                             : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
+                             : "v"(b), "v"(c), "s"(((EMPTY >> k) & 1u) ? fail : pass) : "vcc");
         }
     }
     const long long t1 = clock64(), w1 = wall_clock64();
@@ -69,7 +97,7 @@ __global__ void kern(float *out, long long *clk, int iters)
     out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + float(s0 + s1 + s2 + s3) +
         (p0 + p1 + p2 + p3 + p4 + p5 + p6 + p7).x + (p0 + p1 + p2 + p3 + p4 + p5 + p6 + p7).y;
 }
-template <int MODE> void run(const char *name, int n_valu, int n_salu)
+template <int MODE, unsigned EMPTY = 0u> void run(const char *name, int n_valu, int n_salu, int groups = 16)
 {
     float *d; hipMalloc(&d, 256 * 64 * 64 * 4 * 8);
     long long *clk; hipMalloc(&clk, 16);
@@ -78,22 +106,53 @@ template <int MODE> void run(const char *name, int n_valu, int n_salu)
         dim3 grid(256), block(64 * 4 * (waves > 4 ? 4 : waves));
         if (waves == 6) { grid = dim3(512); block = dim3(64 * 4 * 3); }   // 2 blocks of 12 waves per CU
         const int iters = 4000;
-        kern<MODE><<<grid, block>>>(d, clk, 10);
+        kern<MODE, EMPTY><<<grid, block>>>(d, clk, 10);
         hipDeviceSynchronize();
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
         hipEventRecord(e0);
-        kern<MODE><<<grid, block>>>(d, clk, iters);
+        kern<MODE, EMPTY><<<grid, block>>>(d, clk, iters);
         hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
         long long h[2]; hipMemcpy(h, clk, 16, hipMemcpyDeviceToHost);
         const double mhz_memtime = double(h[0]) / double(h[1]) * 100.0;
-        const double steps_per_simd = double(iters) * 16 * waves;
+        const double steps_per_simd = double(iters) * groups * waves;
         printf("%-22s waves/SIMD=%d  %.3f ms  per 16-instr group and SIMD: %.1f ns = %.1f cycles at 2.4 GHz  "
                "(VALU %d SALU %d per group; s_memtime/s_memrealtime -> %.0f MHz)\n",
                name, waves, ms, ms * 1e6 / steps_per_simd, ms * 1e-3 * 2.4e9 / steps_per_simd, n_valu, n_salu, mhz_memtime);
         if (waves == 6) break;
     }
     hipFree(d); hipFree(clk);
+}
+// Every lane a candidate, none, the odd lanes: the mask must hold the undecided candidates (fract >= 0.5) — zero
+// after a skipped step, whose temporaries stay untouched.
+static bool check_skip()
+{
+    float *r2, *pos, h_r2[64], h_pos[64], h_want[64];
+    unsigned long long *mask, h_mask;
+    hipMalloc(&r2, 256); hipMalloc(&pos, 256); hipMalloc(&mask, 8);
+    bool ok = true;
+    const char *names[3] = {"every lane a candidate", "no candidate (step skipped)", "odd lanes candidates"};
+    for (int variant = 0; variant < 3; ++variant) {
+        unsigned long long want = 0;
+        for (int l = 0; l < 64; ++l) {
+            const bool cand = variant == 0 || (variant == 2 && (l & 1));
+            const float r = (l & 2) ? 2.75f : 2.f;      // fract 0.75: undecided; fract 0: decided
+            h_r2[l] = cand ? r * r : 100.f;             // the candidate test is r2 < 50
+            h_want[l] = cand ? r : -7.f;
+            if (cand && (l & 2)) want |= 1ull << l;
+        }
+        hipMemcpy(r2, h_r2, 256, hipMemcpyHostToDevice);
+        skip_check<<<1, 64>>>(r2, 50.f, mask, pos);
+        hipMemcpy(&h_mask, mask, 8, hipMemcpyDeviceToHost);
+        hipMemcpy(h_pos, pos, 256, hipMemcpyDeviceToHost);
+        bool good = h_mask == want;
+        for (int l = 0; l < 64; ++l)
+            good = good && h_pos[l] == h_want[l];
+        printf("skip check, %s: mask %016llx (want %016llx) %s\n", names[variant], h_mask, want, good ? "ok" : "WRONG");
+        ok = ok && good;
+    }
+    hipFree(r2); hipFree(pos); hipFree(mask);
+    return ok;
 }
 int main()
 {
@@ -105,5 +164,9 @@ int main()
     run<5>("8 v_pk_fma_f32", 8, 0);
     run<6>("4 pk_add + 4 pk_mul f32", 8, 0);
     run<7>("4 v_sub_u32+4 cvt_f32_i32", 8, 0);
+    if (!check_skip()) return 1;
+    run<8, 0u>("skip step, 0/32 empty", 13, 1, 32);
+    run<8, 0x04082082u>("skip step, 5/32 empty", 13, 1, 32);
+    run<8, ~0u>("skip step, 32/32 empty", 13, 1, 32);
     return 0;
 }
