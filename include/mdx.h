@@ -43,6 +43,7 @@ extern "C" {
 #define MDX_ERR_OUT_OF_MEMORY (-7) /* -> MemoryError         */
 #define MDX_ERR_STATE (-8)         /* -> RuntimeError        */
 #define MDX_ERR_IO (-9)            /* -> OSError             */
+#define MDX_ERR_INTERNAL (-10)     /* -> RuntimeError        */
 
 /* ------------------------------------------------------------------ runtime
  * Loading the library sets GPU_PINNED_MIN_XFER_SIZE=1048576 (MiB) in the process unless the variable is set already:
@@ -751,6 +752,57 @@ int mdx_prs_contacts(mdx_prs_t h, int64_t *out, int64_t n);
 int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
                   int64_t *max_row);
 int mdx_prs_enable_timing(mdx_prs_t h, int on);
+
+/* ------------------------------------------------------------------ ion clusters
+ * Per analysed frame the connected components of the bond graph of n rows: the atoms of group 0, then group 1, ...;
+ * species[n] (int32, 0 ... n_species - 1, n_species <= 8) names the group of a row.  Box, minimum image and r2 are
+ * those of mdx_prs_*: float32 rows, one constant orthorhombic box dims[3], zero_dims (bit c set: component c takes no
+ * part), everything in float64, one operation at a time.  cutoff[n_species * n_species] is a symmetric table of
+ * non-negative finite values with at least one positive entry, the largest at most half the shortest kept box length;
+ * rows i != j are bonded iff r2 <= cutoff[a][b]^2 with a, b their species, and never where cutoff[a][b] == 0.
+ * label[f][i] is the smallest row of the component of i.  Results, all integers:
+ *     per frame: bonds (unordered pairs), n_clusters, largest (rows of the largest component), sum_squares
+ *                (sum over the components of size^2);
+ *     over the frames seen: size_counts[s], s = 0 ... n (components of s rows), species_counts[g][s] (rows of species
+ *                g in a component of s rows; sum_g species_counts[g][s] == s * size_counts[s]).
+ * max_neighbors (1 ... 64): the bonds a row may hold in one frame, both directions counted.  A row that would hold
+ * more is never truncated silently: mdx_clu_synchronize and every result call fail with MDX_ERR_INVALID_VALUE (the
+ * message names max_neighbors and the largest row seen) until mdx_clu_reset.  The components are found on the device
+ * from the bond lists by sweeps of hooking and pointer jumping (csrc/mdx_cluster_device.hpp); a slab that has not
+ * settled after n + 1 sweeps is MDX_ERR_INTERNAL.  All results are identical across the three input routes, across
+ * any split of the frames into calls or slabs, and after a reset.  Frames are independent: nothing but the results
+ * outlives a slab.  A handle touches its device with the first frame: mdx_clu_create and every argument error
+ * (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_clu *mdx_clu_t;
+int mdx_clu_create(mdx_clu_t *out, int dev, int64_t n, const int32_t *species, int n_species, const double *cutoff,
+                   const double *dims, int zero_dims, int max_neighbors, int keep_labels);
+int mdx_clu_destroy(mdx_clu_t h);
+/* Forgets the frames seen and an overflowing row, and zeroes the results. */
+int mdx_clu_reset(mdx_clu_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the lists in HBM).  The results
+ * do not depend on it.  Only before the first frame. */
+int mdx_clu_set_slab_frames(mdx_clu_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring. */
+int mdx_clu_accumulate(mdx_clu_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows. */
+int mdx_clu_accumulate_device(mdx_clu_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_clu_accumulate_traj(mdx_clu_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_clu_synchronize(mdx_clu_t h);
+/* size_counts: int64 [n + 1]; species_counts: int64 [n_species][n + 1]. */
+int mdx_clu_result(mdx_clu_t h, int64_t *size_counts, int64_t *species_counts);
+/* bonds, n_clusters, largest, sum_squares: int64 [n] each, the first n frames seen. */
+int mdx_clu_frames(mdx_clu_t h, int64_t *bonds, int64_t *n_clusters, int64_t *largest, int64_t *sum_squares,
+                   int64_t n);
+/* out: int32 [n][points], the labels of the first n frames seen; only with keep_labels. */
+int mdx_clu_labels(mdx_clu_t h, int32_t *out, int64_t n);
+/* evaluations: the contract's pair count so far, frames x n (n - 1) / 2; max_row: the most bonds a row held in one
+ * frame (beyond max_neighbors: the results are refused); sweeps: the labelling sweeps so far. */
+int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *max_row, int64_t *sweeps);
+int mdx_clu_enable_timing(mdx_clu_t h, int on);
 
 #ifdef __cplusplus
 }

@@ -1130,6 +1130,115 @@ class PairResidenceEngine(_Engine):
                 "max_row": row.value}
 
 
+class ClusterEngine(_Engine):
+    """``mdx_clu_*``: per frame the connected components of the bond graph of ``n`` rows.  ``species`` (``int [n]``,
+    ``0 ... G - 1``, ``G <= 8``) names the group of a row; ``cutoff`` is a float or a symmetric ``G x G`` table of
+    non-negative values (0: that pair of species never bonds); rows ``i != j`` are bonded where the minimum-image
+    ``r2 <= cutoff[a][b] ** 2`` in float64.  ``label[f][i]`` is the smallest row of the component of ``i``.  A row
+    may hold ``max_neighbors`` bonds in one frame; one that would hold more makes ``synchronize()`` and every result
+    call raise ``ValueError`` until ``reset()``.  The device is first touched by the first frame, so the argument
+    errors (``ValueError``) need none."""
+
+    _destroy = "mdx_clu_destroy"
+    TILE = 256          # rows per block (CLU_TILE of csrc/mdx_cluster_device.hpp)
+    JCHUNK = 1024       # partners per block (CLU_JCHUNK)
+    MAX_NEIGHBORS = 64  # slots of a row at most (CLU_MAX_NEIGHBORS)
+    MAX_SPECIES = 8     # CLU_MAX_SPECIES
+
+    def __init__(self, species, cutoff, dims, *, n_species=None, zero_dims=0, max_neighbors=32, keep_labels=False,
+                 dev=0, timing=False):
+        self.species = np.ascontiguousarray(np.atleast_1d(species), dtype=np.int32)
+        if self.species.ndim != 1:
+            raise ValueError("species must be one-dimensional.")
+        self.n = len(self.species)
+        table = np.asarray(cutoff, dtype=np.float64)
+        if n_species is None:
+            n_species = len(table) if table.ndim == 2 else (int(self.species.max()) + 1 if self.n else 1)
+        self.n_species = int(n_species)
+        if not 1 <= self.n_species <= self.MAX_SPECIES:
+            raise ValueError(f"n_species must lie in [1, {self.MAX_SPECIES}].")
+        if table.ndim == 0:
+            table = np.full((self.n_species, self.n_species), float(table))
+        if table.shape != (self.n_species, self.n_species):
+            raise ValueError(f"cutoff must be a number or a {self.n_species} x {self.n_species} table.")
+        self.cutoff = np.ascontiguousarray(table)
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.max_neighbors, self.keep_labels = int(max_neighbors), bool(keep_labels)
+        h = c_void_p()
+        check(lib().mdx_clu_create(byref(h), dev, self.n, _ptr(self.species), self.n_species, _ptr(self.cutoff),
+                                   _ptr(self.dims), int(zero_dims), self.max_neighbors, int(self.keep_labels)))
+        self.handle = h
+        self.dev = dev
+        if timing:
+            check(lib().mdx_clu_enable_timing(h, 1))
+
+    def set_slab_frames(self, frames):
+        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
+        before the first frame."""
+        check(lib().mdx_clu_set_slab_frames(self.handle, int(frames)))
+
+    def accumulate(self, pos):
+        """pos: float32[F, n, 3], rows of group 0, then group 1, ..."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(lib().mdx_clu_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM (``index``: rows of a frame in incoming order)."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_clu_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                              0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(lib().mdx_clu_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                            0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(lib().mdx_clu_synchronize(self.handle))
+
+    def result(self):
+        """``{"size_counts": int64 [n + 1], "species_counts": int64 [G, n + 1]}`` over the frames seen."""
+        out = {"size_counts": np.zeros(self.n + 1, dtype=np.int64),
+               "species_counts": np.zeros((self.n_species, self.n + 1), dtype=np.int64)}
+        check(lib().mdx_clu_result(self.handle, _ptr(out["size_counts"]), _ptr(out["species_counts"])))
+        return out
+
+    def _frames_seen(self):
+        frames = c_int64()
+        check(lib().mdx_clu_stats(self.handle, None, None, byref(frames), None, None, None))
+        return frames.value
+
+    def frames(self):
+        """``{"bonds", "n_clusters", "largest", "sum_squares"}``, ``int64 [frames]`` each: every frame seen."""
+        n = self._frames_seen()
+        out = {key: np.zeros(n, dtype=np.int64) for key in ("bonds", "n_clusters", "largest", "sum_squares")}
+        check(lib().mdx_clu_frames(self.handle, _ptr(out["bonds"]), _ptr(out["n_clusters"]), _ptr(out["largest"]),
+                                   _ptr(out["sum_squares"]), n))
+        return out
+
+    def labels(self):
+        """``int32 [frames, n]``: the smallest row of every row's cluster (``keep_labels``)."""
+        out = np.zeros((self._frames_seen(), self.n), dtype=np.int32)
+        check(lib().mdx_clu_labels(self.handle, _ptr(out), len(out)))
+        return out
+
+    def reset(self):
+        check(lib().mdx_clu_reset(self.handle))
+
+    def stats(self):
+        n, ms, frames, ev, row, sweeps = c_int64(), c_double(), c_int64(), c_int64(), c_int64(), c_int64()
+        check(lib().mdx_clu_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev), byref(row),
+                                  byref(sweeps)))
+        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value,
+                "max_row": row.value, "sweeps": sweeps.value}
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

@@ -26,6 +26,7 @@ _EXC = {
     -7: MemoryError,           # MDX_ERR_OUT_OF_MEMORY
     -8: RuntimeError,          # MDX_ERR_STATE
     -9: OSError,               # MDX_ERR_IO
+    -10: RuntimeError,         # MDX_ERR_INTERNAL
 }
 
 RDF_ALGO = {"auto": 0, "exact": 1, "filter": 2, "cell": 3}
@@ -244,6 +245,21 @@ _SIGNATURES = {
     "mdx_prs_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
     "mdx_prs_enable_timing": (c_int, [_vp, c_int]),
+    # ion clusters (connected components of a contact graph)
+    "mdx_clu_create": (c_int, [POINTER(_vp), c_int, c_int64, _vp, c_int, _vp, _vp, c_int, c_int, c_int]),
+    "mdx_clu_destroy": (c_int, [_vp]),
+    "mdx_clu_reset": (c_int, [_vp]),
+    "mdx_clu_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_clu_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_clu_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_clu_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_clu_synchronize": (c_int, [_vp]),
+    "mdx_clu_result": (c_int, [_vp, _vp, _vp]),
+    "mdx_clu_frames": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64]),
+    "mdx_clu_labels": (c_int, [_vp, _vp, c_int64]),
+    "mdx_clu_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_clu_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -2,9 +2,14 @@
 Small numeric utilities (reference ``src/mdhelper/algorithm/utility.py``).
 Only ``get_closest_factors`` (:15-72) touches the hot path (spherical wavevector
 surfaces of ``StructureFactor``, reference analysis/structure.py:1383).
+``find_connected_nodes`` / ``depth_first_search`` (:158-210) are host helpers for
+graphs a user builds by hand; ``analysis.Clusters`` finds the clusters of a
+trajectory on the GPU.
 """
 
 from __future__ import annotations
+
+from typing import Any
 
 import numpy as np
 
@@ -43,3 +48,42 @@ def get_closest_factors(value: int, n_factors: int, reverse: bool = False) -> np
     search(value, n_factors, 1, [])
     factors = np.array(best[1], dtype=int)
     return factors[::-1] if reverse else factors
+
+
+def depth_first_search(graph: dict[Any, list[Any]], start: Any, visited: dict[Any, bool],
+                       group: list[Any]) -> None:
+    """
+    Appends to ``group`` every node of ``graph`` (``{node: [neighbors]}``) that can be reached from ``start``
+    without passing a node already marked in ``visited``, in depth-first preorder, and marks them; ``visited`` and
+    ``group`` are updated in place.
+
+    Iterative, with an explicit stack of neighbor iterators: the order is that of the reference's recursive search,
+    and a chain of any length is walked without touching Python's recursion limit.
+    """
+    visited[start] = True
+    group.append(start)
+    stack = [iter(graph[start])]
+    while stack:
+        for neighbor in stack[-1]:
+            if not visited[neighbor]:
+                visited[neighbor] = True
+                group.append(neighbor)
+                stack.append(iter(graph[neighbor]))
+                break
+        else:
+            stack.pop()
+
+
+def find_connected_nodes(graph: dict[Any, list[Any]]) -> list[list[Any]]:
+    """
+    Connected components of ``graph`` (``{node: [neighbors]}``, every neighbor a key): a list of lists of nodes,
+    the components in the order of their first node in ``graph``, the nodes of one in depth-first preorder.
+    """
+    visited = {node: False for node in graph}
+    results = []
+    for start in graph:
+        if not visited[start]:
+            group = []
+            depth_first_search(graph, start, visited, group)
+            results.append(group)
+    return results

@@ -1,0 +1,521 @@
+// mdx_cluster.hip — ion clusters (connected components of a contact graph) on gfx950 (MI355X).
+//
+// Per frame the bonds between the rows of one or several species (minimum-image distance within the cutoff of the
+// two species), kept as capped per-row lists in HBM; from the lists the connected components (label = the smallest
+// row of the component) and from the labels the cluster-size distribution, the per-species membership by cluster
+// size and per-frame cluster counts.  Contract, cap, kernel shapes and why the labelling ends with the minimum:
+// mdx_cluster_device.hpp; this unit is compiled with contraction off and spells its float64 operations out.
+//
+// Every result is an integer added with integer atomics, so the results are the same whatever route the frames take
+// and however they are split into calls or slabs.
+//
+// A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
+#include "mdx_common.hpp"
+#include "mdx_internal.hpp"
+#include "mdx_cluster_device.hpp"
+#include "mdx_traj.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+using namespace mdx;
+using namespace mdx_clu_dev;
+
+namespace {
+
+constexpr int64_t CLU_SLAB_BYTES = int64_t(256) << 20;  // what the frames of a default slab take in HBM
+constexpr int CLU_SWEEP_BATCH = 4;                      // sweeps queued between two looks at their "lowered" words
+
+}  // namespace
+
+struct mdx_clu {
+    int dev = 0;
+    bool ready = false;                 // the device side exists
+    hipStream_t stream = nullptr;
+    int n_species = 1, keep = 7, max_nb = 32;
+    bool uniform = true, keep_labels = false;
+    int64_t n = 0;
+    int64_t frames_seen = 0, slab_frames = 0;   // slab_frames: 0 = the default
+    int64_t sweeps = 0;
+    int max_row = 0;                    // the largest row seen, as of the last look
+    CluBox box;
+    double rc2 = 0.0;                   // the one squared cutoff of a uniform table
+    double table[CLU_MAX_SPECIES * CLU_MAX_SPECIES];    // rc2 at [8 * b + a], -1.0 where the species never bond
+    std::vector<int32_t> species;
+    // d_counts: uint64 [1 + G][n + 1], size_counts then species_counts; d_frames: uint64 [frames][CLU_FRAME_WORDS];
+    // d_labels: int32 [frames][n] (keep_labels); d_ctl: int32 max_row, then the "lowered" words of a batch of sweeps
+    DeviceBuffer d_species, d_table, d_counts, d_frames, d_labels, d_ctl, d_slab, d_len, d_list, d_label, d_size,
+        d_stage[2], d_index;
+    std::vector<int32_t> index_host;    // what d_index holds
+    StagePipeline pipe;
+    StreamTimer timer;
+};
+
+// bytes a frame of a slab takes: its gathered rows, its lists and lengths, its labels and sizes
+static int64_t clu_frame_bytes(const mdx_clu *h)
+{
+    return 12 * h->n + (int64_t(h->max_nb) + 1) * 4 * h->n + 8 * h->n;
+}
+
+static int64_t clu_slab(const mdx_clu *h)
+{
+    if (h->slab_frames > 0)
+        return h->slab_frames;
+    return std::min(CLU_SLAB_MAX, std::max<int64_t>(1, CLU_SLAB_BYTES / clu_frame_bytes(h)));
+}
+
+static int clu_zero(mdx_clu *h)
+{
+    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * (1 + h->n_species) * (h->n + 1), h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_ctl.ptr, 0, size_t(4) * (1 + CLU_SWEEP_BATCH), h->stream));
+    if (h->d_frames.ptr)
+        MDX_HIP(hipMemsetAsync(h->d_frames.ptr, 0, h->d_frames.bytes, h->stream));
+    h->max_row = 0;
+    return MDX_OK;
+}
+
+// the device side of the handle: stream, tables and counters
+static int clu_ensure_device(mdx_clu *h)
+{
+    MDX_TRY(set_device(h->dev));
+    if (h->ready)
+        return MDX_OK;
+    if (!h->stream) {
+        MDX_TRY(stream_acquire(&h->stream));
+        h->timer.stream = h->stream;
+    }
+    MDX_TRY(h->d_species.ensure(size_t(4) * h->n));
+    MDX_TRY(h->d_table.ensure(sizeof(h->table)));
+    MDX_TRY(h->d_counts.ensure(size_t(8) * (1 + h->n_species) * (h->n + 1)));
+    MDX_TRY(h->d_ctl.ensure(size_t(4) * (1 + CLU_SWEEP_BATCH)));
+    MDX_HIP(hipMemcpy(h->d_species.ptr, h->species.data(), size_t(4) * h->n, hipMemcpyHostToDevice));
+    MDX_HIP(hipMemcpy(h->d_table.ptr, h->table, sizeof(h->table), hipMemcpyHostToDevice));
+    MDX_TRY(clu_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->ready = true;
+    return MDX_OK;
+}
+
+// The buffers of a slab, sized before the first frame of a pass.  Nothing is in flight then (a reset waits for the
+// stream), so growing them loses nothing.
+static int clu_ensure_slab(mdx_clu *h)
+{
+    if (h->frames_seen > 0)
+        return MDX_OK;
+    const int64_t slab = clu_slab(h);
+    MDX_REQUIRE(slab < (int64_t(1) << 40) / clu_frame_bytes(h),
+                "a slab of %lld frames of %lld points with %d neighbors each is too large", (long long)slab,
+                (long long)h->n, h->max_nb);
+    MDX_TRY(h->d_slab.ensure(size_t(12) * h->n * slab));
+    MDX_TRY(h->d_len.ensure(size_t(4) * h->n * slab));
+    MDX_TRY(h->d_list.ensure(size_t(4) * h->max_nb * h->n * slab));
+    MDX_TRY(h->d_label.ensure(size_t(4) * h->n * slab));
+    MDX_TRY(h->d_size.ensure(size_t(4) * h->n * slab));
+    return MDX_OK;
+}
+
+// room in `buf` for `frames` frames of `frame_bytes` each; what the frames seen so far hold moves along
+static int clu_grow(mdx_clu *h, DeviceBuffer &buf, size_t frame_bytes, int64_t frames)
+{
+    if (frame_bytes * frames <= buf.bytes)
+        return MDX_OK;
+    DeviceBuffer grown;
+    MDX_TRY(grown.ensure(std::max(frame_bytes * frames, 2 * buf.bytes)));
+    MDX_HIP(hipMemsetAsync(grown.ptr, 0, grown.bytes, h->stream));
+    if (h->frames_seen > 0)
+        MDX_HIP(hipMemcpyAsync(grown.ptr, buf.ptr, frame_bytes * h->frames_seen, hipMemcpyDeviceToDevice,
+                               h->stream));
+    MDX_HIP(hipStreamSynchronize(h->stream));       // nobody reads the old block any more
+    buf.recycle();
+    buf = grown;
+    return MDX_OK;
+}
+
+static int clu_refuse_rows(const mdx_clu *h)
+{
+    MDX_REQUIRE(h->max_row <= h->max_nb,
+                "a row held %d bonds in one frame, more than max_neighbors = %d: raise max_neighbors or lower the "
+                "cutoff (reset starts over)", h->max_row, h->max_nb);
+    return MDX_OK;
+}
+
+// With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
+static int clu_check_rows(mdx_clu *h)
+{
+    int32_t row = 0;
+    MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
+    h->max_row = row;
+    return clu_refuse_rows(h);
+}
+
+// Labels the nf frames of the slab whose lists are queued on the stream: sweeps in batches, until one lowered
+// nothing.  *labelled = false where a row of the slab (or an earlier one) went beyond the cap: the lists are then
+// truncated, the results refused, and nothing more is done with the slab.  Returns with the stream idle.
+static int clu_label_slab(mdx_clu *h, int64_t nf, hipEvent_t *ev, bool *labelled)
+{
+    const int n = (int)h->n;
+    const dim3 grid((unsigned)ceil_div(h->n, CLU_ROW_THREADS), (unsigned)nf);
+    int *ctl = h->d_ctl.as<int>();
+    int32_t seen[1 + CLU_SWEEP_BATCH];
+    *labelled = false;
+    for (int64_t done = 0;;) {
+        MDX_HIP(hipMemsetAsync(ctl + 1, 0, size_t(4) * CLU_SWEEP_BATCH, h->stream));
+        for (int b = 0; b < CLU_SWEEP_BATCH; ++b)
+            hipLaunchKernelGGL(clu_sweep_kernel, grid, dim3(CLU_ROW_THREADS), 0, h->stream, n, h->max_nb,
+                               h->d_len.as<int>(), h->d_list.as<int>(), h->d_label.as<int>(), ctl + 1 + b);
+        h->timer.end(*ev);
+        MDX_HIP(hipGetLastError());
+        MDX_HIP(hipStreamSynchronize(h->stream));
+        MDX_HIP(hipMemcpy(seen, ctl, sizeof(seen), hipMemcpyDeviceToHost));
+        *ev = h->timer.begin();
+        h->max_row = seen[0];
+        if (seen[0] > h->max_nb)
+            return MDX_OK;
+        for (int b = 0; b < CLU_SWEEP_BATCH; ++b) {
+            ++done;
+            ++h->sweeps;
+            if (!seen[1 + b]) {
+                *labelled = true;       // a whole sweep lowered nothing
+                return MDX_OK;
+            }
+            if (done > h->n)
+                return fail(MDX_ERR_INTERNAL, "the labelling of %lld points did not settle in %lld sweeps",
+                            (long long)h->n, (long long)done);
+        }
+    }
+}
+
+// n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
+static int clu_accumulate_rows(mdx_clu *h, const float *d_pos, int64_t src_rows, const int *d_index, int64_t n_rows,
+                               int64_t n_frames)
+{
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_REQUIRE(n_rows == h->n, "%lld rows given, the groups hold %lld", (long long)n_rows, (long long)h->n);
+    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
+    MDX_TRY(clu_grow(h, h->d_frames, size_t(8) * CLU_FRAME_WORDS, h->frames_seen + n_frames));
+    if (h->keep_labels)
+        MDX_TRY(clu_grow(h, h->d_labels, size_t(4) * h->n, h->frames_seen + n_frames));
+    const int n = (int)h->n;
+    const int64_t slab = clu_slab(h);       // what clu_ensure_slab sized the buffers for
+    const int64_t n_jchunks = ceil_div(h->n, CLU_JCHUNK);
+    const int64_t blocks = ceil_div(h->n, CLU_TILE) * n_jchunks;
+    const int64_t row_tiles = ceil_div(h->n, CLU_ROW_THREADS);
+    unsigned long long *counts = h->d_counts.as<unsigned long long>();
+    for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
+        const int64_t nf = std::min(slab, n_frames - s0);
+        const float *pos = d_pos + s0 * src_rows * 3;
+        const int64_t f_lo = h->frames_seen;
+        hipEvent_t ev = h->timer.begin();
+        hipLaunchKernelGGL(clu_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
+                           0, h->stream, pos, src_rows, d_index, n, h->d_slab.as<float>(), h->d_label.as<int>(),
+                           h->d_size.as<int>());
+        MDX_HIP(hipMemsetAsync(h->d_len.ptr, 0, size_t(4) * n * nf, h->stream));
+        const auto contact = h->uniform
+                                 ? (h->keep == 7 ? clu_contact_kernel<true, true> : clu_contact_kernel<false, true>)
+                                 : (h->keep == 7 ? clu_contact_kernel<true, false> : clu_contact_kernel<false, false>);
+        hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(CLU_THREADS), 0, h->stream,
+                           h->d_slab.as<float>(), n, (int)n_jchunks, f_lo, h->box, h->keep, h->rc2,
+                           h->d_table.as<double>(), h->d_species.as<int>(), h->max_nb, h->d_len.as<int>(),
+                           h->d_list.as<int>(), h->d_frames.as<unsigned long long>(), h->d_ctl.as<int>());
+        h->frames_seen += nf;
+        bool labelled = false;
+        if (h->max_row <= h->max_nb) {      // else: the results are refused until a reset; only max_row goes on
+            const int rc = clu_label_slab(h, nf, &ev, &labelled);
+            if (rc != MDX_OK) {
+                h->timer.end(ev);
+                return rc;
+            }
+        }
+        if (labelled) {
+            const dim3 grid((unsigned)row_tiles, (unsigned)nf);
+            hipLaunchKernelGGL(clu_size_kernel, grid, dim3(CLU_ROW_THREADS), 0, h->stream, n, h->d_label.as<int>(),
+                               h->d_size.as<int>());
+            hipLaunchKernelGGL(clu_tally_kernel, grid, dim3(CLU_ROW_THREADS), 0, h->stream, n, f_lo,
+                               h->d_label.as<int>(), h->d_size.as<int>(), h->d_species.as<int>(), counts,
+                               counts + (h->n + 1), h->d_frames.as<unsigned long long>());
+            if (h->keep_labels)
+                MDX_HIP(hipMemcpyAsync(h->d_labels.as<int>() + f_lo * h->n, h->d_label.ptr, size_t(4) * n * nf,
+                                       hipMemcpyDeviceToDevice, h->stream));
+        }
+        h->timer.end(ev);
+        MDX_HIP(hipGetLastError());
+    }
+    return MDX_OK;
+}
+
+extern "C" {
+
+int mdx_clu_create(mdx_clu_t *out, int dev, int64_t n, const int32_t *species, int n_species, const double *cutoff,
+                   const double *dims, int zero_dims, int max_neighbors, int keep_labels)
+{
+    MDX_REQUIRE(out && species && cutoff && dims, "NULL argument");
+    MDX_REQUIRE(n_species >= 1 && n_species <= CLU_MAX_SPECIES, "n_species must lie in [1, %d]", CLU_MAX_SPECIES);
+    MDX_REQUIRE(zero_dims >= 0 && zero_dims < 7, "zero_dims must leave at least one component");
+    MDX_REQUIRE(max_neighbors >= 1 && max_neighbors <= CLU_MAX_NEIGHBORS, "max_neighbors must lie in [1, %d]",
+                CLU_MAX_NEIGHBORS);
+    MDX_REQUIRE(n >= 1, "the groups must hold at least one point");
+    MDX_REQUIRE(n < (int64_t(1) << 31) / 3, "the groups must hold fewer than 2^31 / 3 points");
+    MDX_REQUIRE(ceil_div(n, CLU_TILE) * ceil_div(n, CLU_JCHUNK) < (int64_t(1) << 31),
+                "%lld points are too many pairs for one launch", (long long)n);
+    for (int64_t i = 0; i < n; ++i)
+        MDX_REQUIRE(species[i] >= 0 && species[i] < n_species, "species[%lld] = %d out of range [0, %d)",
+                    (long long)i, species[i], n_species);
+    for (int c = 0; c < 3; ++c)
+        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
+    const int G = n_species;
+    double largest = 0.0;
+    bool uniform = true;
+    for (int a = 0; a < G; ++a)
+        for (int b = 0; b < G; ++b) {
+            const double c = cutoff[a * G + b];
+            MDX_REQUIRE(c >= 0.0 && std::isfinite(c), "cutoff[%d][%d] must be finite and not negative", a, b);
+            MDX_REQUIRE(c == cutoff[b * G + a], "the cutoff table must be symmetric: [%d][%d] = %g, [%d][%d] = %g", a,
+                        b, c, b, a, cutoff[b * G + a]);
+            largest = std::max(largest, c);
+            uniform = uniform && c == cutoff[0];
+        }
+    MDX_REQUIRE(largest > 0.0, "the cutoff table must hold at least one positive entry");
+    double shortest = HUGE_VAL;
+    for (int c = 0; c < 3; ++c)
+        if (!(zero_dims >> c & 1))
+            shortest = std::min(shortest, dims[c]);
+    // beyond half a box length the minimum image is not the nearest image
+    MDX_REQUIRE(largest <= shortest / 2, "cutoff %g reaches beyond half the shortest box length %g", largest,
+                shortest);
+    mdx_clu *h = new mdx_clu();
+    h->dev = dev;
+    h->n = n;
+    h->n_species = G;
+    h->keep = 7 & ~zero_dims;
+    h->max_nb = max_neighbors;
+    h->keep_labels = keep_labels != 0;
+    h->species.assign(species, species + n);
+    h->uniform = uniform;               // every entry is the one positive value
+    h->rc2 = cutoff[0] * cutoff[0];
+    for (double &t : h->table)
+        t = -1.0;
+    for (int a = 0; a < G; ++a)
+        for (int b = 0; b < G; ++b)
+            if (cutoff[a * G + b] > 0.0)
+                h->table[CLU_MAX_SPECIES * b + a] = cutoff[a * G + b] * cutoff[a * G + b];
+    for (int c = 0; c < 3; ++c) {
+        h->box.L[c] = dims[c];
+        h->box.inv[c] = 1.0 / dims[c];
+    }
+    *out = h;
+    return MDX_OK;
+}
+
+int mdx_clu_destroy(mdx_clu_t h)
+{
+    if (!h)
+        return MDX_OK;
+    if (h->stream) {
+        (void)hipSetDevice(h->dev);
+        (void)hipStreamSynchronize(h->stream);
+        h->timer.destroy();
+        h->pipe.destroy();      // waits for its copy stream
+        for (DeviceBuffer *b : {&h->d_species, &h->d_table, &h->d_counts, &h->d_frames, &h->d_labels, &h->d_ctl,
+                                &h->d_slab, &h->d_len, &h->d_list, &h->d_label, &h->d_size, &h->d_stage[0],
+                                &h->d_stage[1], &h->d_index})
+            b->recycle();
+        stream_release(h->stream);
+    }
+    delete h;
+    return MDX_OK;
+}
+
+int mdx_clu_reset(mdx_clu_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->frames_seen = 0;
+    h->sweeps = 0;
+    h->max_row = 0;
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.reset();
+    MDX_TRY(clu_zero(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return MDX_OK;
+}
+
+int mdx_clu_set_slab_frames(mdx_clu_t h, int64_t frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    MDX_REQUIRE(frames >= 0 && frames <= CLU_SLAB_MAX, "frames must lie in [0, %lld]", (long long)CLU_SLAB_MAX);
+    MDX_REQUIRE(h->frames_seen == 0, "mdx_clu_set_slab_frames must be called before the first frame");
+    h->slab_frames = frames;
+    return MDX_OK;
+}
+
+int mdx_clu_accumulate_device(mdx_clu_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && d_pos, "NULL argument");
+    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
+    const int64_t n = index ? n_index : n_atoms;
+    MDX_REQUIRE(n == h->n, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(clu_ensure_device(h));
+    MDX_TRY(clu_ensure_slab(h));
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    return clu_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+}
+
+int mdx_clu_accumulate(mdx_clu_t h, const float *pos, int64_t n, int64_t n_frames)
+{
+    MDX_REQUIRE(h && pos, "NULL argument");
+    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
+    MDX_REQUIRE(n == h->n, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(clu_ensure_device(h));
+    MDX_TRY(clu_ensure_slab(h));
+    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
+                                                pos + f0 * n * 3, size_t(12) * n * nf);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return clu_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
+// the file's first n_index particles.
+int mdx_clu_accumulate_traj(mdx_clu_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index)
+{
+    MDX_REQUIRE(h && traj, "NULL handle");
+    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
+    Trajectory *t = mdx_traj_internal(traj);
+    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
+    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    MDX_REQUIRE(n == h->n, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n);
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)t->n_atoms);
+    if (n_frames == 0)
+        return MDX_OK;
+    MDX_TRY(clu_ensure_device(h));
+    MDX_TRY(clu_ensure_slab(h));
+    MDX_TRY(h->pipe.ensure());
+    const int *d_index = nullptr;
+    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
+                                  &d_index));
+    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    return h->pipe.run(
+        h->stream, n_frames, slab,
+        [&](int b, int64_t f0, int64_t nf) -> int {
+            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
+            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
+            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
+        },
+        [&](int b, int64_t, int64_t nf) -> int {
+            return clu_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
+        });
+}
+
+int mdx_clu_synchronize(mdx_clu_t h)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (!h->ready)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    return clu_check_rows(h);
+}
+
+int mdx_clu_result(mdx_clu_t h, int64_t *size_counts, int64_t *species_counts)
+{
+    MDX_REQUIRE(h && size_counts && species_counts, "NULL argument");
+    MDX_TRY(clu_ensure_device(h));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    h->timer.collect();
+    MDX_TRY(clu_check_rows(h));
+    // uint64 counts of at most frames x n < 2^63 each: they fit an int64
+    const size_t bytes = size_t(8) * (h->n + 1);
+    MDX_HIP(hipMemcpy(size_counts, h->d_counts.ptr, bytes, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(species_counts, h->d_counts.as<char>() + bytes, bytes * h->n_species, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_clu_frames(mdx_clu_t h, int64_t *bonds, int64_t *n_clusters, int64_t *largest, int64_t *sum_squares,
+                   int64_t n)
+{
+    MDX_REQUIRE(h && ((bonds && n_clusters && largest && sum_squares) || n == 0), "NULL argument");
+    MDX_REQUIRE(n >= 0 && n <= h->frames_seen, "%lld frames asked for, %lld seen", (long long)n,
+                (long long)h->frames_seen);
+    if (n == 0)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    MDX_TRY(clu_check_rows(h));
+    std::vector<uint64_t> words(size_t(CLU_FRAME_WORDS) * n);
+    MDX_HIP(hipMemcpy(words.data(), h->d_frames.ptr, size_t(8) * words.size(), hipMemcpyDeviceToHost));
+    for (int64_t f = 0; f < n; ++f) {
+        const uint64_t *w = words.data() + CLU_FRAME_WORDS * f;
+        bonds[f] = int64_t(w[0] / 2);       // the kernel counts a bond from both ends
+        n_clusters[f] = int64_t(w[1]);
+        largest[f] = int64_t(w[2]);
+        sum_squares[f] = int64_t(w[3]);
+    }
+    return MDX_OK;
+}
+
+int mdx_clu_labels(mdx_clu_t h, int32_t *out, int64_t n)
+{
+    MDX_REQUIRE(h && (out || n == 0), "NULL argument");
+    MDX_REQUIRE(h->keep_labels, "the handle was created without keep_labels");
+    MDX_REQUIRE(n >= 0 && n <= h->frames_seen, "%lld frames asked for, %lld seen", (long long)n,
+                (long long)h->frames_seen);
+    if (n == 0)
+        return MDX_OK;
+    MDX_TRY(set_device(h->dev));
+    MDX_HIP(hipStreamSynchronize(h->stream));
+    MDX_TRY(clu_check_rows(h));
+    MDX_HIP(hipMemcpy(out, h->d_labels.ptr, size_t(4) * h->n * n, hipMemcpyDeviceToHost));
+    return MDX_OK;
+}
+
+int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *max_row, int64_t *sweeps)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    if (h->ready) {
+        MDX_TRY(set_device(h->dev));
+        MDX_HIP(hipStreamSynchronize(h->stream));
+        h->timer.collect();
+        int32_t row = 0;
+        MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
+        h->max_row = row;
+    }
+    if (launches) *launches = h->timer.launches;
+    if (kernel_ms) *kernel_ms = h->timer.total_ms;
+    if (frames) *frames = h->frames_seen;
+    if (evaluations) *evaluations = h->frames_seen * (h->n * (h->n - 1) / 2);
+    if (max_row) *max_row = h->max_row;
+    if (sweeps) *sweeps = h->sweeps;
+    return MDX_OK;
+}
+
+int mdx_clu_enable_timing(mdx_clu_t h, int on)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    h->timer.enabled = on != 0;
+    return MDX_OK;
+}
+
+}  // extern "C"
