@@ -672,7 +672,8 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
 template <bool LOWER, int TAGS, int MODE, bool SKIP, typename Hist>
 __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist &hist, float fx,
                                  float fy, float fz, int tag_i, int tag_j, unsigned i_base,
-                                 unsigned j_idx, unsigned w, CellWave &wv)
+                                 unsigned i_half, unsigned j_base, unsigned j_row, unsigned j_off,
+                                 unsigned w, CellWave &wv)
 {
     float r2 = __fmaf_rn(fz, fz, __fmaf_rn(fy, fy, fx * fx));
     unsigned long long m_todo;
@@ -775,16 +776,32 @@ __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist
     // middle of the hot loop: it is appended to the wave's list in LDS (slot = list length + rank
     // among the undecided lanes; the length lives in a scalar register) and cell_flush evaluates the
     // list 64 pairs at a time.
+    //
+    // Everything the entry is made of is formed HERE, behind the branch that 4.5 % of the steps take:
+    // the callers hand over the pieces (the item's i base and which half; the tile's j base, the row
+    // of the turn and the row's offset in the turn), not the sums — a sum formed at the call site is
+    // formed on every turn of a row loop, for the one turn in twenty that reads it.  The opaque copy
+    // of the row keeps the optimiser from moving the sums back up.
+    // The store runs under EXEC = the mask itself (a scalar register pair already: no per-lane test of
+    // "is my bit set", no branch around the store); rank and address are computed by all lanes, which
+    // costs nothing.  EXEC is all ones at every call site (see above), so that is what it is restored to.
     if (__builtin_expect(m_todo != 0ull, 0)) {
         const unsigned cnt = (unsigned)__popcll(m_todo);
         if (wv.n_todo + cnt <= (unsigned)CELL_TODO) {
-            if ((m_todo >> (threadIdx.x & 63u)) & 1ull) {
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi(
-                    (unsigned)(m_todo >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_todo, 0u));
-                // i index = (wave-uniform base of the half tile) + lane, formed only here
-                wv.todo[wv.n_todo + rank] =
-                    make_uint2(i_base + (threadIdx.x & 63u), j_idx);   // j_idx carries the weight flag (bit 31)
-            }
+            unsigned row = j_row + j_off;
+            asm volatile("" : "+s"(row));
+            // slot = list length + rank: the length is the count's starting value
+            const unsigned slot = __builtin_amdgcn_mbcnt_hi(
+                (unsigned)(m_todo >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_todo, wv.n_todo));
+            const unsigned addr =
+                (unsigned)(size_t)(__attribute__((address_space(3))) uint2 *)wv.todo + slot * 8u;
+            // i index = (wave-uniform base of the half tile) + lane; j index carries the weight flag (bit 31)
+            const uint2 e = make_uint2((i_base + 64u * i_half) | (threadIdx.x & 63u), j_base + row);
+            const unsigned long long ev = (unsigned long long)e.x | ((unsigned long long)e.y << 32);
+            asm volatile("s_mov_b64 exec, %[m]\n\tds_write_b64 %[ad], %[ev]\n\ts_mov_b64 exec, -1"
+                         :
+                         : [m] "s"(m_todo), [ad] "v"(addr), [ev] "v"(ev)
+                         : "memory");
             wv.n_todo += cnt;
         } else {
             // the list is full (adversarial input: everything on a bin edge): the caller rolls
@@ -1288,9 +1305,11 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                 // unit: one roll-back mark, one overflow test, one popcount for the statistics.
                 const unsigned mark = wv.n_todo;
                 n_units += (unsigned)__popcll(sub) + (CELL_CHUNK == 1 ? (unsigned)__popcll(sub1) : 0u);
-#define MDX_CELL_HALF(TG, P, IB, Q, JJ)                                                            \
-    if (GH) cell_step<LOWER, TG, MODE, false>(hot, a, hg, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), IB, (JJ), w, wv); \
-    else cell_step<LOWER, TG, MODE, SKIP>(hot, a, hl, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), IB, (JJ), w, wv);
+// (H: the i half, R: the slab row of the turn, O: the row's offset in the turn — the pieces of the indices an
+// undecided pair is listed under; cell_step puts them together where it lists one)
+#define MDX_CELL_HALF(TG, P, H, Q, R, O)                                                           \
+    if (GH) cell_step<LOWER, TG, MODE, false>(hot, a, hg, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), i_base0, H, jbase, unsigned(R), O, w, wv); \
+    else cell_step<LOWER, TG, MODE, SKIP>(hot, a, hl, Q.x - P.x, Q.y - P.y, Q.z - P.z, __float_as_int(P.w), __float_as_int(Q.w), i_base0, H, jbase, unsigned(R), O, w, wv);
 // one unit: CELL_CHUNK slab rows (whole 16-byte reads: ds_read_b96 costs 8 LDS cycles,
 // ds_read_b128 4) against the i halves that survived; the global j index is scalar
 #define MDX_CELL_UNITS_CHUNKS(TG)                                                                         \
@@ -1298,7 +1317,6 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
         const int s = __builtin_ctzll(rem) >> 1;                                                   \
         const unsigned bits = unsigned(rem >> (2 * s)) & 3u;                                       \
         rem &= ~(3ull << (2 * s));                                                                 \
-        const unsigned jg = jbase + unsigned(CELL_CHUNK * s);                                      \
         float4 q[CELL_CHUNK];                                                                      \
         _Pragma("unroll") for (int c = 0; c < CELL_CHUNK; ++c) q[c] = sJw[CELL_CHUNK * s + c];     \
         /* all reads issued before any is waited for; .w kept alive = whole 16-byte reads */       \
@@ -1307,13 +1325,13 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
         if (bits & 1u) {                                                                           \
             _Pragma("unroll") for (int c = 0; c < CELL_CHUNK; ++c)                                 \
             {                                                                                      \
-                MDX_CELL_HALF(TG, p0, i_base0, q[c], jg + unsigned(c))                             \
+                MDX_CELL_HALF(TG, p0, 0u, q[c], CELL_CHUNK * s, unsigned(c))                      \
             }                                                                                      \
         }                                                                                          \
         if (bits & 2u) {                                                                           \
             _Pragma("unroll") for (int c = 0; c < CELL_CHUNK; ++c)                                 \
             {                                                                                      \
-                MDX_CELL_HALF(TG, p1, i_base0 + 64u, q[c], jg + unsigned(c))                       \
+                MDX_CELL_HALF(TG, p1, 1u, q[c], CELL_CHUNK * s, unsigned(c))                      \
             }                                                                                      \
         }                                                                                          \
     }
@@ -1344,27 +1362,27 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
         const unsigned long long pairs = both & (both >> 1) & 0x5555555555555555ull;               \
         const unsigned long long paired = pairs | (pairs << 1);                                    \
         MDX_CELL_ROW2_LOOP(TG, pairs,                                                              \
-                          MDX_CELL_HALF(TG, p0, i_base0, q, jbase + unsigned(r))                   \
-                          MDX_CELL_HALF(TG, p0, i_base0, q1, jbase + unsigned(r) + 1u)             \
-                          MDX_CELL_HALF(TG, p1, i_base0 + 64u, q, jbase + unsigned(r))             \
-                          MDX_CELL_HALF(TG, p1, i_base0 + 64u, q1, jbase + unsigned(r) + 1u))      \
+                          MDX_CELL_HALF(TG, p0, 0u, q, r, 0u)                                      \
+                          MDX_CELL_HALF(TG, p0, 0u, q1, r, 1u)                                     \
+                          MDX_CELL_HALF(TG, p1, 1u, q, r, 0u)                                      \
+                          MDX_CELL_HALF(TG, p1, 1u, q1, r, 1u))                                    \
         MDX_CELL_ROW_LOOP(TG, both & ~paired,                                                      \
-                          MDX_CELL_HALF(TG, p0, i_base0, q, jbase + unsigned(r))                   \
-                          MDX_CELL_HALF(TG, p1, i_base0 + 64u, q, jbase + unsigned(r)))            \
+                          MDX_CELL_HALF(TG, p0, 0u, q, r, 0u)                                      \
+                          MDX_CELL_HALF(TG, p1, 1u, q, r, 0u))                                     \
         /* rows of one half only, adjacent pairs first */                                          \
         const unsigned long long only0 = sub & ~sub1, only1 = sub1 & ~sub;                         \
         const unsigned long long pairs0 = only0 & (only0 >> 1) & 0x5555555555555555ull;            \
         const unsigned long long pairs1 = only1 & (only1 >> 1) & 0x5555555555555555ull;            \
         MDX_CELL_ROW2_LOOP(TG, pairs0,                                                             \
-                          MDX_CELL_HALF(TG, p0, i_base0, q, jbase + unsigned(r))                   \
-                          MDX_CELL_HALF(TG, p0, i_base0, q1, jbase + unsigned(r) + 1u))            \
+                          MDX_CELL_HALF(TG, p0, 0u, q, r, 0u)                                      \
+                          MDX_CELL_HALF(TG, p0, 0u, q1, r, 1u))                                    \
         MDX_CELL_ROW2_LOOP(TG, pairs1,                                                             \
-                          MDX_CELL_HALF(TG, p1, i_base0 + 64u, q, jbase + unsigned(r))             \
-                          MDX_CELL_HALF(TG, p1, i_base0 + 64u, q1, jbase + unsigned(r) + 1u))      \
+                          MDX_CELL_HALF(TG, p1, 1u, q, r, 0u)                                      \
+                          MDX_CELL_HALF(TG, p1, 1u, q1, r, 1u))                                    \
         MDX_CELL_ROW_LOOP(TG, only0 & ~(pairs0 | (pairs0 << 1)),                                   \
-                          MDX_CELL_HALF(TG, p0, i_base0, q, jbase + unsigned(r)))                  \
+                          MDX_CELL_HALF(TG, p0, 0u, q, r, 0u))                                     \
         MDX_CELL_ROW_LOOP(TG, only1 & ~(pairs1 | (pairs1 << 1)),                                   \
-                          MDX_CELL_HALF(TG, p1, i_base0 + 64u, q, jbase + unsigned(r)))            \
+                          MDX_CELL_HALF(TG, p1, 1u, q, r, 0u))                                     \
     }
 #define MDX_CELL_UNITS(TG)                                                                         \
     if (CELL_CHUNK == 1) {                                                                         \
@@ -1410,19 +1428,22 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                 n_general += 2 * CELL_NCHUNK;
                 const unsigned mark = wv.n_todo;
 #define MDX_CELL_GENERAL(GM)                                                                       \
-    _Pragma("unroll 2") for (int jj = 0; jj < 64; ++jj)                                            \
+    _Pragma("unroll 1") for (int jj = 0; jj < 64; jj += 2)                                         \
     {                                                                                              \
-        float4 q = sJw[jj];                                                                        \
-        asm volatile("" ::"v"(q.w)); /* whole 16-byte read (ds_read_b96 costs twice the cycles) */ \
-        _Pragma("unroll") for (int u = 0; u < 2; ++u)                                              \
+        _Pragma("unroll") for (int c = 0; c < 2; ++c)   /* two rows per turn, each read when it is due */ \
         {                                                                                          \
-            const float4 &p = u ? p1 : p0;                                                         \
-            float fx = q.x - p.x, fy = q.y - p.y, fz = q.z - p.z;                                  \
-            if ((GM) & 1) fx = fminf(fabsf(fx), hot.L[0] - fabsf(fx));                             \
-            if ((GM) & 2) fy = fminf(fabsf(fy), hot.L[1] - fabsf(fy));                             \
-            if ((GM) & 4) fz = fminf(fabsf(fz), hot.L[2] - fabsf(fz));                             \
-            if (GH) cell_step<LOWER, EXCL ? 1 : 0, MODE, false>(hot, a, hg, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0 + 64u * u, jbase + jj, w, wv); \
-            else cell_step<LOWER, EXCL ? 1 : 0, MODE, false>(hot, a, hl, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0 + 64u * u, jbase + jj, w, wv); \
+            float4 q = sJw[jj + c];                                                                \
+            asm volatile("" ::"v"(q.w)); /* whole 16-byte read (ds_read_b96 costs twice the cycles) */ \
+            _Pragma("unroll") for (int u = 0; u < 2; ++u)                                          \
+            {                                                                                      \
+                const float4 &p = u ? p1 : p0;                                                     \
+                float fx = q.x - p.x, fy = q.y - p.y, fz = q.z - p.z;                              \
+                if ((GM) & 1) fx = fminf(fabsf(fx), hot.L[0] - fabsf(fx));                         \
+                if ((GM) & 2) fy = fminf(fabsf(fy), hot.L[1] - fabsf(fy));                         \
+                if ((GM) & 4) fz = fminf(fabsf(fz), hot.L[2] - fabsf(fz));                         \
+                if (GH) cell_step<LOWER, EXCL ? 1 : 0, MODE, false>(hot, a, hg, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0, unsigned(u), jbase, unsigned(jj), unsigned(c), w, wv); \
+                else cell_step<LOWER, EXCL ? 1 : 0, MODE, false>(hot, a, hl, fx, fy, fz, __float_as_int(p.w), __float_as_int(q.w), i_base0, unsigned(u), jbase, unsigned(jj), unsigned(c), w, wv); \
+            }                                                                                      \
         }                                                                                          \
     }
                 switch (gen) {

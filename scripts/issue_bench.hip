@@ -6,7 +6,10 @@
 //   * the hot step's mix: 10 plain VALU + v_sqrt_f32 + 2 v_cmp + 10 SALU per 13 VALU;
 //   * the same 13 VALU with v_cmpx + s_cbranch_execz around the seven behind the candidate test (round 7), at
 //     0, 5 of 32 and all steps empty — the price of the branch alone and what a skipped tail gives back — after a
-//     check that a skipped step leaves the mask register zero and its temporaries untouched.
+//     check that a skipped step leaves the mask register zero and its temporaries untouched;
+//   * the price of what a trip issues AROUND the step (round 8), at the pair kernel's seven waves per SIMD: the
+//     skip step with no empty step, then with 1, 2, 4 and 8 independent s_add_i32 spread through it, with a
+//     compare and a not-taken s_cbranch_scc0 behind it, and with one and two more VALU instructions.
 // hipcc -O2 --offload-arch=gfx950 scripts/issue_bench.hip -o /tmp/issue_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -26,6 +29,9 @@ __global__ void skip_check(const float *r2_in, float hi, unsigned long long *mas
     pos[threadIdx.x] = tmp;
     if (threadIdx.x == 0) *mask = m;
 }
+// MODE 9: the skip step of MODE 8 with EMPTY reused as the extra scalar work per step: 0, 1, 2, 4 = that many
+// s_add_i32 (8 as well, for a longer lever); 100 = s_cmp_eq_u32 (SCC = 1) + s_cbranch_scc0 that is never taken;
+// 201, 202 = one, two extra VALU instructions (v_max_f32 of a register with itself), the other yardstick.
 template <int MODE, unsigned EMPTY = 0u>
 __global__ void kern(float *out, long long *clk, int iters)
 {
@@ -87,6 +93,32 @@ __global__ void kern(float *out, long long *clk, int iters)
                              ".Lbench_skip%=:\n s_mov_b64 exec, -1\n"
                              : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
                              : "v"(b), "v"(c), "s"(((EMPTY >> k) & 1u) ? fail : pass) : "vcc");
+        } else if (MODE == 9) {
+            // (operands %8 and %9 are b and c in MODE 8; here the four scalar counters sit at %8..%11, so the
+            // strings below are written with their own numbering: b = %12, c = %13, pass = %14)
+            const float pass = 3e38f;
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+#define MDX_B9_STEP(S1, S2, S3)                                                                                      \
+    asm volatile("v_sub_f32 %0, %0, %12\n v_sub_f32 %1, %1, %12\n" S1 "v_sub_f32 %2, %2, %12\n v_mul_f32 %3, %0, %0\n"      \
+                 "v_fma_f32 %3, %1, %1, %3\n" S2 "v_fma_f32 %3, %2, %2, %3\n v_cmpx_gt_f32_e64 vcc, %14, %3\n"               \
+                 "s_cbranch_execz .Lbench9_skip%=\n v_sqrt_f32 %4, %3\n s_nop 0\n v_fma_f32 %4, %4, %12, %13\n"              \
+                 "v_fract_f32 %5, %4\n v_cmp_gt_f32 vcc, %5, %13\n v_cvt_i32_f32 %6, %4\n v_lshlrev_b32 %7, 2, %6\n"          \
+                 ".Lbench9_skip%=:\n s_mov_b64 exec, -1\n" S3                                                            \
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7), "+s"(s0), "+s"(s1),  \
+                   "+s"(s2), "+s"(s3)                                                                                \
+                 : "v"(b), "v"(c), "s"(pass)                                                                         \
+                 : "vcc", "scc")
+                if (EMPTY == 0u) MDX_B9_STEP("", "", "");
+                else if (EMPTY == 1u) MDX_B9_STEP("", "s_add_i32 %8, %8, 3\n", "");
+                else if (EMPTY == 2u) MDX_B9_STEP("s_add_i32 %8, %8, 3\n", "", "s_add_i32 %9, %9, 5\n");
+                else if (EMPTY == 4u) MDX_B9_STEP("s_add_i32 %8, %8, 3\n s_add_i32 %10, %10, 1\n", "s_add_i32 %11, %11, 7\n", "s_add_i32 %9, %9, 5\n");
+                else if (EMPTY == 8u) MDX_B9_STEP("s_add_i32 %8, %8, 3\n s_add_i32 %10, %10, 1\n s_add_i32 %9, %9, 1\n", "s_add_i32 %11, %11, 7\n s_add_i32 %8, %8, 1\n s_add_i32 %10, %10, 3\n", "s_add_i32 %9, %9, 5\n s_add_i32 %11, %11, 5\n");
+                else if (EMPTY == 201u) MDX_B9_STEP("", "v_max_f32 %7, %7, %7\n", "");
+                else if (EMPTY == 202u) MDX_B9_STEP("v_max_f32 %7, %7, %7\n", "", "v_max_f32 %6, %6, %6\n");
+                else MDX_B9_STEP("", "", "s_cmp_eq_u32 %8, %8\n s_cbranch_scc0 .Lbench9_skip%=\n");
+#undef MDX_B9_STEP
+            }
         }
     }
     const long long t1 = clock64(), w1 = wall_clock64();
@@ -121,6 +153,28 @@ template <int MODE, unsigned EMPTY = 0u> void run(const char *name, int n_valu, 
                name, waves, ms, ms * 1e6 / steps_per_simd, ms * 1e-3 * 2.4e9 / steps_per_simd, n_valu, n_salu, mhz_memtime);
         if (waves == 6) break;
     }
+    hipFree(d); hipFree(clk);
+}
+// The pair kernel's occupancy: seven blocks of 256 threads per CU = seven waves per SIMD.
+template <int MODE, unsigned EXTRA> void run7(const char *name, int n_valu, int n_salu)
+{
+    float *d; hipMalloc(&d, size_t(256) * 7 * 256 * 4);
+    long long *clk; hipMalloc(&clk, 16);
+    const int waves = 7, groups = 32, iters = 4000;
+    dim3 grid(256 * 7), block(256);
+    kern<MODE, EXTRA><<<grid, block>>>(d, clk, 10);
+    hipDeviceSynchronize();
+    hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0);
+    kern<MODE, EXTRA><<<grid, block>>>(d, clk, iters);
+    hipEventRecord(e1); hipEventSynchronize(e1);
+    float ms; hipEventElapsedTime(&ms, e0, e1);
+    long long h[2]; hipMemcpy(h, clk, 16, hipMemcpyDeviceToHost);
+    const double mhz = double(h[0]) / double(h[1]) * 100.0;
+    const double steps_per_simd = double(iters) * groups * waves;
+    printf("%-30s waves/SIMD=%d  %.3f ms  per step and SIMD: %.2f ns = %.2f cycles at the measured %.0f MHz  "
+           "(VALU %d, scalar/branch %d per step)\n",
+           name, waves, ms, ms * 1e6 / steps_per_simd, ms * 1e-3 * mhz * 1e6 / steps_per_simd, mhz, n_valu, n_salu);
     hipFree(d); hipFree(clk);
 }
 // Every lane a candidate, none, the odd lanes: the mask must hold the undecided candidates (fract >= 0.5) — zero
@@ -168,5 +222,16 @@ int main()
     run<8, 0u>("skip step, 0/32 empty", 13, 1, 32);
     run<8, 0x04082082u>("skip step, 5/32 empty", 13, 1, 32);
     run<8, ~0u>("skip step, 32/32 empty", 13, 1, 32);
+    // three passes: they show how far two runs of one row differ
+    for (int pass = 0; pass < 3; ++pass) {
+        run7<9, 0u>("skip step bare", 13, 2);
+        run7<9, 1u>("skip step + 1 s_add_i32", 13, 3);
+        run7<9, 2u>("skip step + 2 s_add_i32", 13, 4);
+        run7<9, 4u>("skip step + 4 s_add_i32", 13, 6);
+        run7<9, 8u>("skip step + 8 s_add_i32", 13, 10);
+        run7<9, 100u>("skip step + s_cmp + s_cbranch", 13, 4);
+        run7<9, 201u>("skip step + 1 VALU", 14, 2);
+        run7<9, 202u>("skip step + 2 VALU", 15, 2);
+    }
     return 0;
 }
