@@ -486,10 +486,77 @@ class IsfEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": fr.value}
 
 
-class ProfileEngine(_Engine):
+class _FrameEngine(_Engine):
+    """What the per-frame engines share: the three routes frames take (host memory, HBM, a trajectory file),
+    ``synchronize``, ``reset``, ``stats`` and the ``timing=`` switch.  A subclass names the prefix of its symbols and
+    what its ``mdx_X_stats`` reports behind launches, kernel time and frames."""
+
+    _prefix = None
+    _stats_extra = ()       # (key, ctype) of every further field of mdx_X_stats, in its order
+
+    @property
+    def _destroy(self):
+        return f"{self._prefix}_destroy"
+
+    def _fn(self, name):
+        return getattr(lib(), f"{self._prefix}_{name}")
+
+    def _adopt(self, handle, dev, timing):
+        """The tail of every constructor: keeps the created handle and switches the event timers on."""
+        self.handle = handle
+        self.dev = dev
+        if timing:
+            check(self._fn("enable_timing")(handle, 1))
+
+    def accumulate(self, pos):
+        """pos: float32[F, N, 3], rows in the engine's incoming order (concatenated groups unless its class says
+        otherwise)."""
+        p = np.ascontiguousarray(pos, dtype=np.float32)
+        if p.ndim == 2:
+            p = p[None]
+        check(self._fn("accumulate")(self.handle, _ptr(p), p.shape[1], p.shape[0]))
+
+    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
+        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
+        the engine's stream: ``synchronize()`` before the frames are overwritten."""
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(self._fn("accumulate_device")(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
+                                            0 if i is None else len(i)))
+
+    def accumulate_traj(self, traj_file, frames, index=None):
+        """Frames of a native trajectory file; ``index``: particles in incoming order."""
+        f = np.ascontiguousarray(frames, dtype=np.int64)
+        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        check(self._fn("accumulate_traj")(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
+                                          0 if i is None else len(i)))
+
+    def synchronize(self):
+        check(self._fn("synchronize")(self.handle))
+
+    def reset(self):
+        check(self._fn("reset")(self.handle))
+
+    def stats(self):
+        keys = ("launches", "kernel_ms", "frames") + tuple(key for key, _ in self._stats_extra)
+        out = [c_int64(), c_double(), c_int64()] + [ctype() for _, ctype in self._stats_extra]
+        check(self._fn("stats")(self.handle, *map(byref, out)))
+        return {key: value.value for key, value in zip(keys, out)}
+
+
+class _SlabbedFrameEngine(_FrameEngine):
+    """... of which these export ``mdx_X_set_slab_frames``."""
+
+    def set_slab_frames(self, frames):
+        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Every
+        engine but the dipole one takes it only before the first frame."""
+        check(self._fn("set_slab_frames")(self.handle, int(frames)))
+
+
+class ProfileEngine(_FrameEngine):
     """``mdx_prof_*``: per-axis, per-group position histograms with ``numpy.histogram``'s counts."""
 
-    _destroy = "mdx_prof_destroy"
+    _prefix = "mdx_prof"
+    _stats_extra = (("replicas", c_int),)
 
     def __init__(self, group_sizes, axes, n_bins, dims, *, per_frame=False, dev=0, timing=False, replicas=None):
         self.offsets = np.concatenate(([0], np.cumsum(group_sizes))).astype(np.int64)
@@ -503,10 +570,7 @@ class ProfileEngine(_Engine):
         h = c_void_p()
         check(lib().mdx_prof_create(byref(h), dev, self.n_groups, _ptr(self.offsets), len(self.axes),
                                     _ptr(self.axes), _ptr(self.n_bins), _ptr(self.dims), int(self.per_frame)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_prof_enable_timing(h, 1))
+        self._adopt(h, dev, timing)
         if replicas is not None:
             self.set_replicas(replicas)
 
@@ -546,30 +610,6 @@ class ProfileEngine(_Engine):
             raise ValueError("target must hold three coordinates.")
         check(lib().mdx_prof_set_recenter(self.handle, group, _ptr(m), _ptr(t)))
 
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows in concatenated-group order."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_prof_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
-        the engine's stream: ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_prof_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                               0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_prof_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                             0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_prof_synchronize(self.handle))
-
     def counts(self):
         """One int64 array per axis: ``[G, n_bins]``, or ``[G, frames seen, n_bins]`` for per-frame engines."""
         frames = self.stats()["frames"]
@@ -581,19 +621,11 @@ class ProfileEngine(_Engine):
             out.append(c)
         return out
 
-    def reset(self):
-        check(lib().mdx_prof_reset(self.handle))
 
-    def stats(self):
-        n, ms, frames, rep = c_int64(), c_double(), c_int64(), c_int()
-        check(lib().mdx_prof_stats(self.handle, byref(n), byref(ms), byref(frames), byref(rep)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "replicas": rep.value}
-
-
-class GyrationEngine(_Engine):
+class GyrationEngine(_FrameEngine):
     """``mdx_gyr_*``: per frame and group the mean over the chains of ``Rg, Rg_x, Rg_y, Rg_z``."""
 
-    _destroy = "mdx_gyr_destroy"
+    _prefix = "mdx_gyr"
 
     def __init__(self, n_chains, n_monomers, masses, *, dev=0, timing=False):
         self.n_chains = np.ascontiguousarray(np.atleast_1d(n_chains), dtype=np.int64)
@@ -608,10 +640,7 @@ class GyrationEngine(_Engine):
         h = c_void_p()
         check(lib().mdx_gyr_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers),
                                    _ptr(m)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_gyr_enable_timing(h, 1))
+        self._adopt(h, dev, timing)
 
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
@@ -640,50 +669,18 @@ class GyrationEngine(_Engine):
             raise ValueError("start must hold three coordinates per point of the groups.")
         check(lib().mdx_gyr_set_unwrap(self.handle, _ptr(d), _ptr(s)))
 
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows in concatenated-group order."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_gyr_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
-        the engine's stream: ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_gyr_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                              0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_gyr_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                            0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_gyr_synchronize(self.handle))
-
     def result(self):
         """float64 ``[G, frames seen, 4]``: ``Rg, Rg_x, Rg_y, Rg_z`` averaged over the chains of each group."""
         out = np.zeros((self.n_groups, self.stats()["frames"], 4), dtype=np.float64)
         check(lib().mdx_gyr_result(self.handle, _ptr(out)))
         return out
 
-    def reset(self):
-        check(lib().mdx_gyr_reset(self.handle))
 
-    def stats(self):
-        n, ms, frames = c_int64(), c_double(), c_int64()
-        check(lib().mdx_gyr_stats(self.handle, byref(n), byref(ms), byref(frames)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
-
-
-class ChainProjectionEngine(_Engine):
+class ChainProjectionEngine(_FrameEngine):
     """``mdx_rouse_*``: per frame, chain and weight row ``X = sum_n w_n x_n`` in float64, kept in HBM as
     ``[frames, S, 3]`` with series ``series0[g] + k * n_chains[g] + c`` (group g, row k, chain c)."""
 
-    _destroy = "mdx_rouse_destroy"
+    _prefix = "mdx_rouse"
 
     def __init__(self, n_chains, n_monomers, weights, *, dev=0, timing=False):
         """weights: one float64 array ``[K, n_monomers[g]]`` per group (a single 2-D array for one group)."""
@@ -707,10 +704,7 @@ class ChainProjectionEngine(_Engine):
         h = c_void_p()
         check(lib().mdx_rouse_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers),
                                      self.n_rows, _ptr(flat)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_rouse_enable_timing(h, 1))
+        self._adopt(h, dev, timing)
 
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
@@ -742,30 +736,6 @@ class ChainProjectionEngine(_Engine):
         """Room for ``n_frames`` frames in all, allocated once."""
         check(lib().mdx_rouse_reserve(self.handle, int(n_frames)))
 
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows in concatenated-group order."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_rouse_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
-        the engine's stream: ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_rouse_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                                0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_rouse_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                              0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_rouse_synchronize(self.handle))
-
     def result(self):
         """float64 ``[frames seen, S, 3]`` on the host."""
         out = np.zeros((self.stats()["frames"], self.n_series, 3), dtype=np.float64)
@@ -779,22 +749,14 @@ class ChainProjectionEngine(_Engine):
         check(lib().mdx_rouse_device_result(self.handle, byref(p), byref(f), byref(s)))
         return p, f.value, s.value
 
-    def reset(self):
-        check(lib().mdx_rouse_reset(self.handle))
-
-    def stats(self):
-        n, ms, frames = c_int64(), c_double(), c_int64()
-        check(lib().mdx_rouse_stats(self.handle, byref(n), byref(ms), byref(frames)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
-
 
 RouseEngine = ChainProjectionEngine
 
 
-class DipoleEngine(_Engine):
+class DipoleEngine(_SlabbedFrameEngine):
     """``mdx_dip_*``: per frame and group the dipole moment ``sum q (r + image L)`` in float64."""
 
-    _destroy = "mdx_dip_destroy"
+    _prefix = "mdx_dip"
     TILE = 128          # points per tile of the summation order (DIP_TILE of csrc/mdx_dipole_device.hpp)
 
     def __init__(self, n_points, charges, *, dev=0, timing=False):
@@ -808,10 +770,7 @@ class DipoleEngine(_Engine):
             raise ValueError("charges must hold one entry per point of the groups.")
         h = c_void_p()
         check(lib().mdx_dip_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), _ptr(q)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_dip_enable_timing(h, 1))
+        self._adopt(h, dev, timing)
 
     def set_unwrap(self, dims, start=None):
         """The reference's global unwrap from frame to frame, starting from the points ``start``
@@ -828,55 +787,20 @@ class DipoleEngine(_Engine):
             raise ValueError("start must hold three coordinates per point of the groups.")
         check(lib().mdx_dip_set_unwrap(self.handle, _ptr(d), _ptr(s)))
 
-    def set_slab_frames(self, frames):
-        """Frames per kernel launch at most; 0 restores the default.  The rows do not depend on it."""
-        check(lib().mdx_dip_set_slab_frames(self.handle, int(frames)))
-
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows in concatenated-group order."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_dip_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM, read where they lie (``index``: rows of a frame in incoming order).  Asynchronous on
-        the engine's stream: ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_dip_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                              0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_dip_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                            0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_dip_synchronize(self.handle))
-
     def result(self):
         """float64 ``[G, frames seen, 3]``: the dipole moment of every group in every frame."""
         out = np.zeros((self.n_groups, self.stats()["frames"], 3), dtype=np.float64)
         check(lib().mdx_dip_result(self.handle, _ptr(out)))
         return out
 
-    def reset(self):
-        check(lib().mdx_dip_reset(self.handle))
 
-    def stats(self):
-        n, ms, frames = c_int64(), c_double(), c_int64()
-        check(lib().mdx_dip_stats(self.handle, byref(n), byref(ms), byref(frames)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value}
-
-
-class VanHoveEngine(_Engine):
+class VanHoveEngine(_SlabbedFrameEngine):
     """``mdx_vh_*``: per lag and group the histogram of the displacement magnitudes ``|x(f) - x(f - lag)|`` and the
     sums of their second and fourth powers, in float64.  The device is first touched by the first frame, so the
     argument errors (``ValueError``) need none."""
 
-    _destroy = "mdx_vh_destroy"
+    _prefix = "mdx_vh"
+    _stats_extra = (("evaluations", c_int64),)
     TILE = 64           # points per tile: a tile never spans two groups (VH_TILE of csrc/mdx_vanhove_device.hpp)
 
     def __init__(self, n_points, edges, lags, *, zero_dims=0, dev=0, timing=False):
@@ -896,10 +820,7 @@ class VanHoveEngine(_Engine):
         h = c_void_p()
         check(lib().mdx_vh_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), self.n_bins,
                                   _ptr(self.edges), self.n_lags, _ptr(self.lags), int(zero_dims)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_vh_enable_timing(h, 1))
+        self._adopt(h, dev, timing)
 
     def set_unwrap(self, dims):
         """The reference's global unwrap from frame to frame with the box lengths ``dims``; the first frame is its
@@ -911,35 +832,6 @@ class VanHoveEngine(_Engine):
         if d.shape != (3,):
             raise ValueError("dims must hold the three box lengths.")
         check(lib().mdx_vh_set_unwrap(self.handle, _ptr(d)))
-
-    def set_slab_frames(self, frames):
-        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
-        before the first frame."""
-        check(lib().mdx_vh_set_slab_frames(self.handle, int(frames)))
-
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows in concatenated-group order."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_vh_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM (``index``: rows of a frame in incoming order).  Asynchronous on the engine's stream:
-        ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_vh_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                             0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_vh_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                           0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_vh_synchronize(self.handle))
 
     def result(self):
         """``(counts int64 [n_lags, G, n_bins], moments float64 [n_lags, G, 2])``: the moments are the sums of
@@ -955,22 +847,15 @@ class VanHoveEngine(_Engine):
         check(lib().mdx_vh_point_moments(self.handle, _ptr(out)))
         return out
 
-    def reset(self):
-        check(lib().mdx_vh_reset(self.handle))
 
-    def stats(self):
-        n, ms, frames, ev = c_int64(), c_double(), c_int64(), c_int64()
-        check(lib().mdx_vh_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value}
-
-
-class DistinctVanHoveEngine(_Engine):
+class DistinctVanHoveEngine(_SlabbedFrameEngine):
     """``mdx_vhd_*``: per lag the histogram of the minimum-image distances ``|x2_j(f0 + lag) - x1_i(f0)|`` over every
     pair of points (``j != i`` with ``same``) and every frame pair whose origin ``f0`` is a multiple of
     ``origin_step``, in float64.  Incoming rows are set 1 then set 2, or set 1 alone with ``same``.  The device is
     first touched by the first frame, so the argument errors (``ValueError``) need none."""
 
-    _destroy = "mdx_vhd_destroy"
+    _prefix = "mdx_vhd"
+    _stats_extra = (("evaluations", c_int64),)
     TILE = 256          # set-1 points per block (VHD_TILE of csrc/mdx_vanhove_distinct_device.hpp)
     JCHUNK = 512        # set-2 points per block (VHD_JCHUNK)
     LDS_BINS = 2048     # n_bins up to which the histograms live in LDS (VHD_LDS_BINS)
@@ -992,39 +877,7 @@ class DistinctVanHoveEngine(_Engine):
         h = c_void_p()
         check(lib().mdx_vhd_create(byref(h), dev, self.n1, self.n2, int(self.same), self.n_bins, _ptr(self.edges),
                                    self.n_lags, _ptr(self.lags), int(origin_step), _ptr(self.dims), int(zero_dims)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_vhd_enable_timing(h, 1))
-
-    def set_slab_frames(self, frames):
-        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
-        before the first frame."""
-        check(lib().mdx_vhd_set_slab_frames(self.handle, int(frames)))
-
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows of set 1 then set 2 (set 1 alone with ``same``)."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_vhd_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM (``index``: rows of a frame in incoming order).  Asynchronous on the engine's stream:
-        ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_vhd_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                              0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_vhd_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                            0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_vhd_synchronize(self.handle))
+        self._adopt(h, dev, timing)
 
     def result(self):
         """``counts int64 [n_lags, n_bins]``."""
@@ -1032,16 +885,8 @@ class DistinctVanHoveEngine(_Engine):
         check(lib().mdx_vhd_result(self.handle, _ptr(counts)))
         return counts
 
-    def reset(self):
-        check(lib().mdx_vhd_reset(self.handle))
 
-    def stats(self):
-        n, ms, frames, ev = c_int64(), c_double(), c_int64(), c_int64()
-        check(lib().mdx_vhd_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value}
-
-
-class PairResidenceEngine(_Engine):
+class PairResidenceEngine(_SlabbedFrameEngine):
     """``mdx_prs_*``: per frame the pairs of points (``j != i`` with ``same``) whose minimum-image distance lies
     within ``cutoff`` (``r2 <= cutoff * cutoff`` in float64), and per lag the sizes of the intersections of an origin's
     contact set with the set a lag later (intermittent) and with every set up to there (continuous), summed over the
@@ -1050,7 +895,8 @@ class PairResidenceEngine(_Engine):
     ``result()`` and ``contacts()`` raise ``ValueError`` until ``reset()``.  The device is first touched by the first
     frame, so the argument errors (``ValueError``) need none."""
 
-    _destroy = "mdx_prs_destroy"
+    _prefix = "mdx_prs"
+    _stats_extra = (("evaluations", c_int64), ("max_row", c_int64))
     TILE = 256          # set-1 points per block (PRS_TILE of csrc/mdx_residence_device.hpp)
     JCHUNK = 1024       # set-2 points per block (PRS_JCHUNK)
     MAX_NEIGHBORS = 64  # slots of a row at most (PRS_MAX_NEIGHBORS)
@@ -1071,39 +917,7 @@ class PairResidenceEngine(_Engine):
         check(lib().mdx_prs_create(byref(h), dev, self.n1, self.n2, int(self.same), float(cutoff), self.n_lags,
                                    _ptr(self.lags), int(origin_step), _ptr(self.dims), int(zero_dims),
                                    self.max_neighbors, int(self.continuous)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_prs_enable_timing(h, 1))
-
-    def set_slab_frames(self, frames):
-        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
-        before the first frame."""
-        check(lib().mdx_prs_set_slab_frames(self.handle, int(frames)))
-
-    def accumulate(self, pos):
-        """pos: float32[F, N, 3], rows of set 1 then set 2 (set 1 alone with ``same``)."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_prs_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM (``index``: rows of a frame in incoming order).  Asynchronous on the engine's stream:
-        ``synchronize()`` before the frames are overwritten."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_prs_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                              0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_prs_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                            0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_prs_synchronize(self.handle))
+        self._adopt(h, dev, timing)
 
     def result(self):
         """``{"intermittent", "continuous", "origin_counts"}``, ``int64 [n_lags]`` each."""
@@ -1120,26 +934,18 @@ class PairResidenceEngine(_Engine):
         check(lib().mdx_prs_contacts(self.handle, _ptr(out), len(out)))
         return out
 
-    def reset(self):
-        check(lib().mdx_prs_reset(self.handle))
 
-    def stats(self):
-        n, ms, frames, ev, row = c_int64(), c_double(), c_int64(), c_int64(), c_int64()
-        check(lib().mdx_prs_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev), byref(row)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value,
-                "max_row": row.value}
-
-
-class ClusterEngine(_Engine):
+class ClusterEngine(_SlabbedFrameEngine):
     """``mdx_clu_*``: per frame the connected components of the bond graph of ``n`` rows.  ``species`` (``int [n]``,
     ``0 ... G - 1``, ``G <= 8``) names the group of a row; ``cutoff`` is a float or a symmetric ``G x G`` table of
     non-negative values (0: that pair of species never bonds); rows ``i != j`` are bonded where the minimum-image
     ``r2 <= cutoff[a][b] ** 2`` in float64.  ``label[f][i]`` is the smallest row of the component of ``i``.  A row
     may hold ``max_neighbors`` bonds in one frame; one that would hold more makes ``synchronize()`` and every result
-    call raise ``ValueError`` until ``reset()``.  The device is first touched by the first frame, so the argument
-    errors (``ValueError``) need none."""
+    call raise ``ValueError`` until ``reset()``.  Incoming rows are those of group 0, then group 1, ...  The device is
+    first touched by the first frame, so the argument errors (``ValueError``) need none."""
 
-    _destroy = "mdx_clu_destroy"
+    _prefix = "mdx_clu"
+    _stats_extra = (("evaluations", c_int64), ("max_row", c_int64), ("sweeps", c_int64))
     TILE = 256          # rows per block (CLU_TILE of csrc/mdx_cluster_device.hpp)
     JCHUNK = 1024       # partners per block (CLU_JCHUNK)
     MAX_NEIGHBORS = 64  # slots of a row at most (CLU_MAX_NEIGHBORS)
@@ -1169,38 +975,7 @@ class ClusterEngine(_Engine):
         h = c_void_p()
         check(lib().mdx_clu_create(byref(h), dev, self.n, _ptr(self.species), self.n_species, _ptr(self.cutoff),
                                    _ptr(self.dims), int(zero_dims), self.max_neighbors, int(self.keep_labels)))
-        self.handle = h
-        self.dev = dev
-        if timing:
-            check(lib().mdx_clu_enable_timing(h, 1))
-
-    def set_slab_frames(self, frames):
-        """Frames per kernel launch at most; 0 restores the default.  The results do not depend on it.  Only
-        before the first frame."""
-        check(lib().mdx_clu_set_slab_frames(self.handle, int(frames)))
-
-    def accumulate(self, pos):
-        """pos: float32[F, n, 3], rows of group 0, then group 1, ..."""
-        p = np.ascontiguousarray(pos, dtype=np.float32)
-        if p.ndim == 2:
-            p = p[None]
-        check(lib().mdx_clu_accumulate(self.handle, _ptr(p), p.shape[1], p.shape[0]))
-
-    def accumulate_device(self, d_pos, n_atoms, n_frames, index=None):
-        """Frames in HBM (``index``: rows of a frame in incoming order)."""
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_clu_accumulate_device(self.handle, d_pos, n_atoms, n_frames, _ptr(i),
-                                              0 if i is None else len(i)))
-
-    def accumulate_traj(self, traj_file, frames, index=None):
-        """Frames of a native trajectory file; ``index``: particles in incoming order."""
-        f = np.ascontiguousarray(frames, dtype=np.int64)
-        i = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
-        check(lib().mdx_clu_accumulate_traj(self.handle, traj_file.handle, _ptr(f), len(f), _ptr(i),
-                                            0 if i is None else len(i)))
-
-    def synchronize(self):
-        check(lib().mdx_clu_synchronize(self.handle))
+        self._adopt(h, dev, timing)
 
     def result(self):
         """``{"size_counts": int64 [n + 1], "species_counts": int64 [G, n + 1]}`` over the frames seen."""
@@ -1227,16 +1002,6 @@ class ClusterEngine(_Engine):
         out = np.zeros((self._frames_seen(), self.n), dtype=np.int32)
         check(lib().mdx_clu_labels(self.handle, _ptr(out), len(out)))
         return out
-
-    def reset(self):
-        check(lib().mdx_clu_reset(self.handle))
-
-    def stats(self):
-        n, ms, frames, ev, row, sweeps = c_int64(), c_double(), c_int64(), c_int64(), c_int64(), c_int64()
-        check(lib().mdx_clu_stats(self.handle, byref(n), byref(ms), byref(frames), byref(ev), byref(row),
-                                  byref(sweeps)))
-        return {"launches": n.value, "kernel_ms": ms.value, "frames": frames.value, "evaluations": ev.value,
-                "max_row": row.value, "sweeps": sweeps.value}
 
 
 def fourier_sum_device(wavevectors, positions, dev=0):

@@ -11,9 +11,9 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_cluster_device.hpp"
-#include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,14 +28,11 @@ constexpr int CLU_SWEEP_BATCH = 4;                      // sweeps queued between
 
 }  // namespace
 
-struct mdx_clu {
-    int dev = 0;
+struct mdx_clu : FrameEngine {
     bool ready = false;                 // the device side exists
-    hipStream_t stream = nullptr;
     int n_species = 1, keep = 7, max_nb = 32;
     bool uniform = true, keep_labels = false;
     int64_t n = 0;
-    int64_t frames_seen = 0, slab_frames = 0;   // slab_frames: 0 = the default
     int64_t sweeps = 0;
     int max_row = 0;                    // the largest row seen, as of the last look
     CluBox box;
@@ -44,11 +41,7 @@ struct mdx_clu {
     std::vector<int32_t> species;
     // d_counts: uint64 [1 + G][n + 1], size_counts then species_counts; d_frames: uint64 [frames][CLU_FRAME_WORDS];
     // d_labels: int32 [frames][n] (keep_labels); d_ctl: int32 max_row, then the "lowered" words of a batch of sweeps
-    DeviceBuffer d_species, d_table, d_counts, d_frames, d_labels, d_ctl, d_slab, d_len, d_list, d_label, d_size,
-        d_stage[2], d_index;
-    std::vector<int32_t> index_host;    // what d_index holds
-    StagePipeline pipe;
-    StreamTimer timer;
+    DeviceBuffer d_species, d_table, d_counts, d_frames, d_labels, d_ctl, d_slab, d_len, d_list, d_label, d_size;
 };
 
 // bytes a frame of a slab takes: its gathered rows, its lists and lengths, its labels and sizes
@@ -311,17 +304,9 @@ int mdx_clu_destroy(mdx_clu_t h)
 {
     if (!h)
         return MDX_OK;
-    if (h->stream) {
-        (void)hipSetDevice(h->dev);
-        (void)hipStreamSynchronize(h->stream);
-        h->timer.destroy();
-        h->pipe.destroy();      // waits for its copy stream
-        for (DeviceBuffer *b : {&h->d_species, &h->d_table, &h->d_counts, &h->d_frames, &h->d_labels, &h->d_ctl,
-                                &h->d_slab, &h->d_len, &h->d_list, &h->d_label, &h->d_size, &h->d_stage[0],
-                                &h->d_stage[1], &h->d_index})
-            b->recycle();
-        stream_release(h->stream);
-    }
+    if (h->stream)
+        h->release({&h->d_species, &h->d_table, &h->d_counts, &h->d_frames, &h->d_labels, &h->d_ctl, &h->d_slab,
+                    &h->d_len, &h->d_list, &h->d_label, &h->d_size});
     delete h;
     return MDX_OK;
 }
@@ -358,15 +343,13 @@ int mdx_clu_accumulate_device(mdx_clu_t h, const float *d_pos, int64_t n_atoms, 
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     const int64_t n = index ? n_index : n_atoms;
     MDX_REQUIRE(n == h->n, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(clu_ensure_device(h));
     MDX_TRY(clu_ensure_slab(h));
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return clu_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
 }
 
@@ -379,18 +362,10 @@ int mdx_clu_accumulate(mdx_clu_t h, const float *pos, int64_t n, int64_t n_frame
         return MDX_OK;
     MDX_TRY(clu_ensure_device(h));
     MDX_TRY(clu_ensure_slab(h));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return clu_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return clu_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
@@ -401,31 +376,20 @@ int mdx_clu_accumulate_traj(mdx_clu_t h, mdx_traj_t traj, const int64_t *frames,
     MDX_REQUIRE(h && traj, "NULL handle");
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     MDX_REQUIRE(n == h->n, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)t->n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(clu_ensure_device(h));
     MDX_TRY(clu_ensure_slab(h));
-    MDX_TRY(h->pipe.ensure());
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
-                                  &d_index));
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return clu_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return clu_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_clu_synchronize(mdx_clu_t h)
@@ -494,17 +458,12 @@ int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *max_row, int64_t *sweeps)
 {
     MDX_REQUIRE(h, "NULL handle");
+    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
     if (h->ready) {
-        MDX_TRY(set_device(h->dev));
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        h->timer.collect();
         int32_t row = 0;
         MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
         h->max_row = row;
     }
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
     if (evaluations) *evaluations = h->frames_seen * (h->n * (h->n - 1) / 2);
     if (max_row) *max_row = h->max_row;
     if (sweeps) *sweeps = h->sweeps;
@@ -514,8 +473,7 @@ int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *fr
 int mdx_clu_enable_timing(mdx_clu_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

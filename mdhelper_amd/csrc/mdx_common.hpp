@@ -223,31 +223,4 @@ struct StagePipeline {
     }
 };
 
-// A host particle index in HBM for the kernels of a handle: checked against [0, n_atoms) and uploaded to d_index,
-// which is kept while the index does not change (index_host: what d_index holds).  *out = nullptr when index is
-// NULL.  `compute` and the pipeline's copy stream are waited for before the buffer is rewritten.
-inline int upload_particle_index(hipStream_t compute, StagePipeline &pipe, DeviceBuffer &d_index,
-                                 std::vector<int32_t> &index_host, const int32_t *index, int64_t n_index,
-                                 int64_t n_atoms, const int **out)
-{
-    *out = nullptr;
-    if (!index)
-        return MDX_OK;
-    for (int64_t i = 0; i < n_index; ++i)
-        if (index[i] < 0 || index[i] >= n_atoms)
-            return fail(MDX_ERR_INVALID_VALUE, "particle index %d out of range [0, %lld)", index[i],
-                        (long long)n_atoms);
-    if (int64_t(index_host.size()) != n_index || memcmp(index_host.data(), index, size_t(4) * n_index) != 0) {
-        // kernels and staging copies of earlier calls may still read the old one
-        MDX_HIP(hipStreamSynchronize(compute));
-        if (pipe.copy_stream)
-            MDX_HIP(hipStreamSynchronize(pipe.copy_stream));
-        MDX_TRY(d_index.ensure(size_t(4) * (n_index > 1 ? n_index : 1)));
-        MDX_HIP(hipMemcpy(d_index.ptr, index, size_t(4) * n_index, hipMemcpyHostToDevice));
-        index_host.assign(index, index + n_index);
-    }
-    *out = d_index.as<int>();
-    return MDX_OK;
-}
-
 }  // namespace mdx

@@ -12,8 +12,8 @@
 // slabs.
 #include "mdx_common.hpp"
 #include "mdx_dipole_device.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
-#include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,39 +28,19 @@ constexpr int64_t DIP_SCRATCH_BYTES = int64_t(256) << 20; // tile sums of one sl
 
 }  // namespace
 
-struct mdx_dip {
-    int dev = 0;
-    hipStream_t stream = nullptr;
+struct mdx_dip : FrameEngine {
     int n_groups = 0;
     int64_t n_points = 0, n_tiles = 0;
-    int64_t frames_seen = 0, row_capacity = 0, slab_frames = 0;   // slab_frames: 0 = the default
+    int64_t row_capacity = 0;
     bool unwrap = false;
     double dims[3] = {0, 0, 0};
     std::vector<double> start;         // [n_points][3]: x_prev before the first frame
-    DeviceBuffer d_tiles, d_tile_offsets, d_charges, d_rows, d_partial, d_stage[2], d_index, d_prev, d_image;
-    std::vector<int32_t> index_host;   // what d_index holds
-    StagePipeline pipe;
-    StreamTimer timer;
+    DeviceBuffer d_tiles, d_tile_offsets, d_charges, d_rows, d_partial, d_prev, d_image;
 };
 
-// capacity for `more` rows behind the ones seen.  Growing copies the rows and waits for the stream, so the host and
-// file routes ask once per call, before their copy / kernel pipeline starts.
 static int dip_grow_rows(mdx_dip *h, int64_t more)
 {
-    const int64_t row = int64_t(24) * h->n_groups, need = h->frames_seen + more;
-    if (more <= 0 || need <= h->row_capacity)
-        return MDX_OK;
-    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(64, 2 * h->row_capacity));
-    DeviceBuffer grown;
-    MDX_TRY(grown.ensure(size_t(row * cap)));
-    if (h->frames_seen > 0)
-        MDX_HIP(hipMemcpyAsync(grown.ptr, h->d_rows.ptr, size_t(row * h->frames_seen), hipMemcpyDeviceToDevice,
-                               h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->d_rows.recycle();
-    h->d_rows = grown;
-    h->row_capacity = cap;
-    return MDX_OK;
+    return grow_rows(h->d_rows, h->stream, int64_t(24) * h->n_groups, h->frames_seen, more, &h->row_capacity);
 }
 
 template <bool UNWRAP>
@@ -108,30 +88,6 @@ static int dip_accumulate_rows(mdx_dip *h, const float *d_pos, int64_t src_rows,
     }
     h->timer.end(ev);
     MDX_HIP(hipGetLastError());
-    return MDX_OK;
-}
-
-// host index -> d_index (kept while it does not change); *out = nullptr when index is NULL
-static int dip_upload_index(mdx_dip *h, const int32_t *index, int64_t n_index, int64_t n_atoms, const int **out)
-{
-    *out = nullptr;
-    if (!index)
-        return MDX_OK;
-    for (int64_t i = 0; i < n_index; ++i)
-        if (index[i] < 0 || index[i] >= n_atoms)
-            return fail(MDX_ERR_INVALID_VALUE, "particle index %d out of range [0, %lld)", index[i],
-                        (long long)n_atoms);
-    if (int64_t(h->index_host.size()) != n_index ||
-        memcmp(h->index_host.data(), index, size_t(4) * n_index) != 0) {
-        // kernels and staging copies of earlier calls may still read the old one
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        if (h->pipe.copy_stream)
-            MDX_HIP(hipStreamSynchronize(h->pipe.copy_stream));
-        MDX_TRY(h->d_index.ensure(size_t(4) * std::max<int64_t>(n_index, 1)));
-        MDX_HIP(hipMemcpy(h->d_index.ptr, index, size_t(4) * n_index, hipMemcpyHostToDevice));
-        h->index_host.assign(index, index + n_index);
-    }
-    *out = h->d_index.as<int>();
     return MDX_OK;
 }
 
@@ -194,16 +150,7 @@ int mdx_dip_destroy(mdx_dip_t h)
 {
     if (!h)
         return MDX_OK;
-    (void)hipSetDevice(h->dev);
-    if (h->stream)
-        (void)hipStreamSynchronize(h->stream);
-    h->timer.destroy();
-    h->pipe.destroy();      // waits for its copy stream
-    for (DeviceBuffer *b : {&h->d_tiles, &h->d_tile_offsets, &h->d_charges, &h->d_rows, &h->d_partial,
-                            &h->d_stage[0], &h->d_stage[1], &h->d_index, &h->d_prev, &h->d_image})
-        b->recycle();
-    if (h->stream)
-        stream_release(h->stream);
+    h->release({&h->d_tiles, &h->d_tile_offsets, &h->d_charges, &h->d_rows, &h->d_partial, &h->d_prev, &h->d_image});
     delete h;
     return MDX_OK;
 }
@@ -257,8 +204,9 @@ int mdx_dip_accumulate_device(mdx_dip_t h, const float *d_pos, int64_t n_atoms, 
     MDX_REQUIRE(h && d_pos, "NULL argument");
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     MDX_TRY(set_device(h->dev));
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(dip_upload_index(h, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return dip_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
 }
 
@@ -268,20 +216,11 @@ int mdx_dip_accumulate(mdx_dip_t h, const float *pos, int64_t n, int64_t n_frame
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
     MDX_REQUIRE(n == h->n_points, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_points);
     MDX_TRY(set_device(h->dev));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1),
-                                           std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
     MDX_TRY(dip_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return dip_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return dip_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -293,27 +232,19 @@ int mdx_dip_accumulate_traj(mdx_dip_t h, mdx_traj_t traj, const int64_t *frames,
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     MDX_TRY(set_device(h->dev));
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     MDX_REQUIRE(n == h->n_points, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n_points);
     if (n_frames == 0)
         return MDX_OK;
-    MDX_TRY(h->pipe.ensure());
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(dip_upload_index(h, index, n_index, t->n_atoms, &d_index));
-    const int64_t slab = std::min<int64_t>(
-        n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     MDX_TRY(dip_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return dip_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return dip_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_dip_synchronize(mdx_dip_t h)
@@ -345,20 +276,13 @@ int mdx_dip_result(mdx_dip_t h, double *out)
 int mdx_dip_stats(mdx_dip_t h, int64_t *launches, double *kernel_ms, int64_t *frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
-    return MDX_OK;
+    return h->stats(true, launches, kernel_ms, frames);
 }
 
 int mdx_dip_enable_timing(mdx_dip_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

@@ -1,0 +1,169 @@
+// mdx_frame_feed.hpp — what the per-frame engines share between their C entry points and their
+// X_accumulate_rows(h, d_pos, src_rows, d_index, n_rows, n_frames): the staged host-memory and trajectory-file routes,
+// the particle index in HBM, the growing per-frame rows and the common part of a handle.  Host code only.
+//
+// An engine writes its own argument checks, its preparation (set_device + grow_rows, or its ensure_device /
+// ensure_history) and X_accumulate_rows; the rest of a route is one call into the feed.
+#pragma once
+
+#include "mdx_common.hpp"
+#include "mdx_traj.hpp"
+
+#include <algorithm>
+#include <initializer_list>
+
+namespace mdx {
+
+// frames per staged slab: ~64 MB of coordinates of frames of `rows` rows (the caller's n on the host route, the
+// file's n_atoms on the file route)
+inline int64_t feed_slab_frames(int64_t n_frames, int64_t rows)
+{
+    return std::min<int64_t>(std::max<int64_t>(n_frames, 1), std::max<int64_t>(1, (int64_t(64) << 20) / (12 * rows)));
+}
+
+// the rows a file call selects: the index's, else the file's first n_index (all of them when n_index <= 0)
+inline int traj_selection(const Trajectory *t, const int32_t *index, int64_t n_index, int64_t *n)
+{
+    *n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
+    MDX_REQUIRE(*n > 0 && (index || *n <= t->n_atoms), "selection larger than the trajectory");
+    return MDX_OK;
+}
+
+// a host particle index (or NULL) against [0, n_atoms): needs no device
+inline int check_particle_index(const int32_t *index, int64_t n_index, int64_t n_atoms)
+{
+    for (int64_t i = 0; index && i < n_index; ++i)
+        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
+                    (long long)n_atoms);
+    return MDX_OK;
+}
+
+struct FrameFeed {
+    StagePipeline pipe;
+    DeviceBuffer d_stage[2], d_index;
+    std::vector<int32_t> index_host;   // what d_index holds
+
+    // A checked host index in HBM for the kernels on `compute`: d_index is kept while the index does not change.
+    // *out = nullptr when index is NULL.  `compute` and the copy stream are waited for before the buffer is rewritten.
+    int upload_index(hipStream_t compute, const int32_t *index, int64_t n_index, const int **out)
+    {
+        *out = nullptr;
+        if (!index)
+            return MDX_OK;
+        if (int64_t(index_host.size()) != n_index || memcmp(index_host.data(), index, size_t(4) * n_index) != 0) {
+            // kernels and staging copies of earlier calls may still read the old one
+            MDX_HIP(hipStreamSynchronize(compute));
+            if (pipe.copy_stream)
+                MDX_HIP(hipStreamSynchronize(pipe.copy_stream));
+            MDX_TRY(d_index.ensure(size_t(4) * std::max<int64_t>(n_index, 1)));
+            MDX_HIP(hipMemcpy(d_index.ptr, index, size_t(4) * n_index, hipMemcpyHostToDevice));
+            index_host.assign(index, index + n_index);
+        }
+        *out = d_index.as<int>();
+        return MDX_OK;
+    }
+
+    // pos float32[n_frames][n][3] in host memory, `slab` frames at a time: the copies of slab k+1 overlap what
+    // rows_fn(d_pos, nf) queues on `compute` for slab k (StagePipeline)
+    template <typename Rows>
+    int host(int dev, hipStream_t compute, const float *pos, int64_t n, int64_t n_frames, int64_t slab, Rows rows_fn)
+    {
+        return pipe.run(
+            compute, n_frames, slab,
+            [&](int b, int64_t f0, int64_t nf) -> int {
+                MDX_TRY(d_stage[b].ensure(size_t(12) * n * slab));
+                return device_stager(dev).upload(dev, pipe.copy_stream, d_stage[b].ptr, pos + f0 * n * 3,
+                                                 size_t(12) * n * nf);
+            },
+            [&](int b, int64_t, int64_t nf) -> int { return rows_fn(d_stage[b].as<float>(), nf); });
+    }
+
+    // the same for the listed frames of a trajectory file, gathered to the n rows of d_index (nullptr: the first n)
+    template <typename Rows>
+    int traj(int dev, hipStream_t compute, Trajectory *t, const int64_t *frames, int64_t n_frames, const int *d_index,
+             int64_t n, int64_t slab, Rows rows_fn)
+    {
+        return pipe.run(
+            compute, n_frames, slab,
+            [&](int b, int64_t f0, int64_t nf) -> int {
+                MDX_TRY(d_stage[b].ensure(size_t(12) * n * slab));
+                TrajSelection sel{d_index, n, d_stage[b].as<float>()};
+                return t->stage_async(dev, pipe.copy_stream, frames + f0, nf, &sel, 1);
+            },
+            [&](int b, int64_t, int64_t nf) -> int { return rows_fn(d_stage[b].as<float>(), nf); });
+    }
+
+    // destroy paths, after the compute stream has been synchronised
+    void destroy()
+    {
+        pipe.destroy();     // waits for its copy stream
+        for (DeviceBuffer *b : {&d_stage[0], &d_stage[1], &d_index})
+            b->recycle();
+    }
+};
+
+// Per-frame result rows of row_bytes each: capacity for `more` rows behind the frames_seen ones (doubling unless
+// `exact`).  Growing copies the rows and waits for the stream, so the host and file routes ask once per call, before
+// their copy / kernel pipeline starts.
+inline int grow_rows(DeviceBuffer &rows, hipStream_t stream, int64_t row_bytes, int64_t frames_seen, int64_t more,
+                     int64_t *capacity, bool exact = false)
+{
+    const int64_t need = frames_seen + more;
+    if (more <= 0 || need <= *capacity)
+        return MDX_OK;
+    const int64_t cap = exact ? need : std::max<int64_t>(need, std::max<int64_t>(64, 2 * *capacity));
+    DeviceBuffer grown;
+    MDX_TRY(grown.ensure(size_t(row_bytes * cap)));
+    if (frames_seen > 0)
+        MDX_HIP(hipMemcpyAsync(grown.ptr, rows.ptr, size_t(row_bytes * frames_seen), hipMemcpyDeviceToDevice, stream));
+    MDX_HIP(hipStreamSynchronize(stream));
+    rows.recycle();
+    rows = grown;
+    *capacity = cap;
+    return MDX_OK;
+}
+
+// what every per-frame engine handle starts with
+struct FrameEngine {
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    int64_t frames_seen = 0, slab_frames = 0;   // slab_frames: 0 = the default
+    StreamTimer timer;
+    FrameFeed feed;
+
+    int enable_timing(int on)
+    {
+        timer.enabled = on != 0;
+        return MDX_OK;
+    }
+
+    // the head of X_stats; live = false: the handle has not touched its device yet
+    int stats(bool live, int64_t *launches, double *kernel_ms, int64_t *frames)
+    {
+        if (live) {
+            MDX_TRY(set_device(dev));
+            MDX_HIP(hipStreamSynchronize(stream));
+            timer.collect();
+        }
+        if (launches) *launches = timer.launches;
+        if (kernel_ms) *kernel_ms = timer.total_ms;
+        if (frames) *frames = frames_seen;
+        return MDX_OK;
+    }
+
+    // the device side of X_destroy: everything idle, then blocks and stream back to the per-device pools
+    void release(std::initializer_list<DeviceBuffer *> own)
+    {
+        (void)hipSetDevice(dev);
+        if (stream)
+            (void)hipStreamSynchronize(stream);
+        timer.destroy();
+        feed.destroy();
+        for (DeviceBuffer *b : own)
+            b->recycle();
+        if (stream)
+            stream_release(stream);
+    }
+};
+
+}  // namespace mdx

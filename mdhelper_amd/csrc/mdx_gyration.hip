@@ -11,11 +11,11 @@
 // of frames go to a scratch array that a second, small kernel averages per (frame, group).  Nothing is added with
 // atomics, so the rows repeat bit for bit whatever route the frames take and however they are split into calls.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_gyration_device.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_points_device.hpp"
-#include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -32,41 +32,21 @@ constexpr int64_t GYR_SCRATCH_BYTES = int64_t(256) << 20; // centres / image cou
 
 }  // namespace
 
-struct mdx_gyr {
-    int dev = 0;
-    hipStream_t stream = nullptr;
+struct mdx_gyr : FrameEngine {
     int n_groups = 0;
     int64_t n_points = 0, n_chains = 0, n_units = 0;
-    int64_t frames_seen = 0, row_capacity = 0;
+    int64_t row_capacity = 0;
     bool unwrap = false;
     double dims[3] = {0, 0, 0};
     std::vector<double> start;         // [n_points][3]: x_prev before the first frame
-    DeviceBuffer d_units, d_masses, d_chain_mass, d_chain_offsets, d_rows, d_chain_out, d_stage[2], d_index,
-        d_centres, d_images, d_prev, d_image;
-    std::vector<int32_t> index_host;   // what d_index holds
-    StagePipeline pipe;
+    DeviceBuffer d_units, d_masses, d_chain_mass, d_chain_offsets, d_rows, d_chain_out, d_centres, d_images, d_prev,
+        d_image;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
-    StreamTimer timer;
 };
 
-// capacity for `more` rows behind the ones seen.  Growing copies the rows and waits for the stream, so the host and
-// file routes ask once per call, before their copy / kernel pipeline starts.
 static int gyr_grow_rows(mdx_gyr *h, int64_t more)
 {
-    const int64_t row = int64_t(32) * h->n_groups, need = h->frames_seen + more;
-    if (more <= 0 || need <= h->row_capacity)
-        return MDX_OK;
-    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(64, 2 * h->row_capacity));
-    DeviceBuffer grown;
-    MDX_TRY(grown.ensure(size_t(row * cap)));
-    if (h->frames_seen > 0)
-        MDX_HIP(hipMemcpyAsync(grown.ptr, h->d_rows.ptr, size_t(row * h->frames_seen), hipMemcpyDeviceToDevice,
-                               h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->d_rows.recycle();
-    h->d_rows = grown;
-    h->row_capacity = cap;
-    return MDX_OK;
+    return grow_rows(h->d_rows, h->stream, int64_t(32) * h->n_groups, h->frames_seen, more, &h->row_capacity);
 }
 
 template <typename SRC>
@@ -144,12 +124,6 @@ static int gyr_accumulate_rows(mdx_gyr *h, const float *d_pos, int64_t src_rows,
     h->timer.end(ev);
     MDX_HIP(hipGetLastError());
     return MDX_OK;
-}
-
-// host index -> d_index (kept while it does not change); *out = nullptr when index is NULL
-static int gyr_upload_index(mdx_gyr *h, const int32_t *index, int64_t n_index, int64_t n_atoms, const int **out)
-{
-    return upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, out);
 }
 
 extern "C" {
@@ -235,18 +209,9 @@ int mdx_gyr_destroy(mdx_gyr_t h)
 {
     if (!h)
         return MDX_OK;
-    (void)hipSetDevice(h->dev);
-    if (h->stream)
-        (void)hipStreamSynchronize(h->stream);
-    h->timer.destroy();
-    h->pipe.destroy();      // waits for its copy stream
-    for (DeviceBuffer *b : {&h->d_units, &h->d_masses, &h->d_chain_mass, &h->d_chain_offsets, &h->d_rows,
-                            &h->d_chain_out, &h->d_stage[0], &h->d_stage[1], &h->d_index, &h->d_centres,
-                            &h->d_images, &h->d_prev, &h->d_image})
-        b->recycle();
+    h->release({&h->d_units, &h->d_masses, &h->d_chain_mass, &h->d_chain_offsets, &h->d_rows, &h->d_chain_out,
+                &h->d_centres, &h->d_images, &h->d_prev, &h->d_image});
     h->mol.recycle();
-    if (h->stream)
-        stream_release(h->stream);
     delete h;
     return MDX_OK;
 }
@@ -302,8 +267,9 @@ int mdx_gyr_accumulate_device(mdx_gyr_t h, const float *d_pos, int64_t n_atoms, 
     MDX_REQUIRE(h && d_pos, "NULL argument");
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     MDX_TRY(set_device(h->dev));
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(gyr_upload_index(h, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return gyr_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
 }
 
@@ -312,20 +278,11 @@ int mdx_gyr_accumulate(mdx_gyr_t h, const float *pos, int64_t n, int64_t n_frame
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
     MDX_TRY(set_device(h->dev));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1),
-                                           std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
     MDX_TRY(gyr_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return gyr_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return gyr_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -337,26 +294,18 @@ int mdx_gyr_accumulate_traj(mdx_gyr_t h, mdx_traj_t traj, const int64_t *frames,
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     MDX_TRY(set_device(h->dev));
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     if (n_frames == 0)
         return MDX_OK;
-    MDX_TRY(h->pipe.ensure());
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(gyr_upload_index(h, index, n_index, t->n_atoms, &d_index));
-    const int64_t slab = std::min<int64_t>(
-        n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     MDX_TRY(gyr_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return gyr_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return gyr_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_gyr_synchronize(mdx_gyr_t h)
@@ -388,20 +337,13 @@ int mdx_gyr_result(mdx_gyr_t h, double *out)
 int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
-    return MDX_OK;
+    return h->stats(true, launches, kernel_ms, frames);
 }
 
 int mdx_gyr_enable_timing(mdx_gyr_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

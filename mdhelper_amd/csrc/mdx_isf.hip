@@ -18,13 +18,13 @@
 // (wavevector block, group x particle split, lag) with the frames of a chunk
 // looped inside, so sums are formed in a fixed order (run-to-run reproducible).
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 
 using namespace mdx;
 
 #include "mdx_sq_device.hpp"
-#include "mdx_traj.hpp"
 
 using namespace mdx_sq_dev;
 
@@ -251,7 +251,7 @@ struct mdx_isf {
     std::vector<int64_t> offsets;
     std::vector<int64_t> ranges;      // particle range of every incoherent slot
     DeviceBuffer d_q, d_offsets, d_pairs, d_ranges, d_rho_ring, d_pos_ring, d_cisf, d_iisf, d_part,
-        d_pos_stage, d_index, d_mtrip, d_row_stage, d_rho_parts;
+        d_pos_stage, d_mtrip, d_row_stage, d_rho_parts;
     MoleculeStage mol;      // optional centre-of-mass stage (groupings other than "atoms")
     bool lattice = false;   // grid wavevectors: separable phase tables (mdx_sq_device.hpp)
     SqLattice lat{};
@@ -261,8 +261,7 @@ struct mdx_isf {
     SqQuadShape quad{};
     DeviceBuffer d_qitems;
     StreamTimer timer;
-    StagePipeline pipe;             // host-buffer / trajectory-file entry points: slab k+1 is staged while slab k runs
-    DeviceBuffer d_stage[2];
+    FrameFeed feed;                 // host-buffer / trajectory-file entry points: slab k+1 is staged while slab k runs
 };
 
 // Frames must arrive in analysis order; consecutive calls continue the same series.
@@ -422,6 +421,15 @@ static int64_t isf_slab_frames(const mdx_isf *h, int64_t n_rows)
     return std::max<int64_t>(1, by_bytes / h->n_lags) * h->n_lags;
 }
 
+// n_frames frames of n rows in HBM enter the position / rho rings by a device copy on the compute stream
+static int isf_accumulate_staged(mdx_isf *h, const float *d_pos, int64_t n, int64_t n_frames)
+{
+    return isf_accumulate(h, n, n_frames, [&](float *d_dst, int64_t done, int64_t nf) -> int {
+        MDX_HIP(hipMemcpyAsync(d_dst, d_pos + done * n * 3, size_t(12) * n * nf, hipMemcpyDeviceToDevice, h->stream));
+        return MDX_OK;
+    });
+}
+
 int mdx_isf_accumulate(mdx_isf_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
@@ -434,31 +442,14 @@ int mdx_isf_accumulate(mdx_isf_t h, const float *pos, int64_t n, int64_t n_frame
     // (whole multiples of n_lags: the kernels take the frames in chunks of n_lags, and a ragged last chunk per
     // slab is a launch of its own over a fraction of the work)
     const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1), isf_slab_frames(h, n));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            const float *d_pos = h->d_stage[b].as<float>();
-            return isf_accumulate(h, n, nf, [&](float *d_dst, int64_t done, int64_t m) -> int {
-                MDX_HIP(hipMemcpyAsync(d_dst, d_pos + done * n * 3, size_t(12) * n * m, hipMemcpyDeviceToDevice,
-                                       h->stream));
-                return MDX_OK;
-            });
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, slab,
+                        [&](const float *d_pos, int64_t nf) -> int { return isf_accumulate_staged(h, d_pos, n, nf); });
 }
 
 int mdx_isf_accumulate_device(mdx_isf_t h, const float *d_pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    return isf_accumulate(h, n, n_frames, [&](float *d_dst, int64_t done, int64_t nf) -> int {
-        MDX_HIP(hipMemcpyAsync(d_dst, d_pos + done * n * 3, size_t(12) * n * nf,
-                               hipMemcpyDeviceToDevice, h->stream));
-        return MDX_OK;
-    });
+    return isf_accumulate_staged(h, d_pos, n, n_frames);
 }
 
 // Frames straight from a trajectory file, in the order listed; index as for
@@ -479,29 +470,16 @@ int mdx_isf_accumulate_traj(mdx_isf_t h, mdx_traj_t traj, const int64_t *frames,
                 return fail(MDX_ERR_INVALID_VALUE, "particle index %d out of range [0, %lld)",
                             index[i], (long long)t->n_atoms);
         MDX_HIP(hipStreamSynchronize(h->stream));
-        MDX_TRY(h->d_index.ensure(size_t(4) * n));
-        MDX_HIP(hipMemcpy(h->d_index.ptr, index, size_t(4) * n, hipMemcpyHostToDevice));
-        d_index = h->d_index.as<int>();
+        MDX_TRY(h->feed.d_index.ensure(size_t(4) * n));
+        MDX_HIP(hipMemcpy(h->feed.d_index.ptr, index, size_t(4) * n, hipMemcpyHostToDevice));
+        d_index = h->feed.d_index.as<int>();
     }
     if (n_frames == 0)
         return MDX_OK;
     // file -> pinned ring -> HBM on the copy stream, a slab ahead of the kernels
     const int64_t slab = std::min<int64_t>(n_frames, isf_slab_frames(h, t->n_atoms));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            const float *d_pos = h->d_stage[b].as<float>();
-            return isf_accumulate(h, n, nf, [&](float *d_dst, int64_t done, int64_t m) -> int {
-                MDX_HIP(hipMemcpyAsync(d_dst, d_pos + done * n * 3, size_t(12) * n * m, hipMemcpyDeviceToDevice,
-                                       h->stream));
-                return MDX_OK;
-            });
-        });
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, slab,
+                        [&](const float *d_pos, int64_t nf) -> int { return isf_accumulate_staged(h, d_pos, n, nf); });
 }
 
 int mdx_isf_create(mdx_isf_t *out, int dev, const double *wavevectors, int64_t n_q,
@@ -614,11 +592,10 @@ int mdx_isf_destroy(mdx_isf_t h)
     if (h->stream)
         (void)hipStreamSynchronize(h->stream);
     h->timer.destroy();
-    h->pipe.destroy();      // waits for its copy stream
+    h->feed.destroy();      // waits for its copy stream
     for (DeviceBuffer *b : {&h->d_q, &h->d_offsets, &h->d_pairs, &h->d_ranges, &h->d_rho_ring,
                             &h->d_pos_ring, &h->d_cisf, &h->d_iisf, &h->d_part, &h->d_pos_stage,
-                            &h->d_index, &h->d_mtrip, &h->d_row_stage, &h->d_qitems, &h->d_rho_parts,
-                            &h->d_stage[0], &h->d_stage[1]})
+                            &h->d_mtrip, &h->d_row_stage, &h->d_qitems, &h->d_rho_parts})
         b->recycle();
     h->mol.recycle();
     if (h->stream)

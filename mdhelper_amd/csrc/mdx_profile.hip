@@ -11,10 +11,10 @@
 // atomics (uint64 totals when averaging, a uint32 row per frame otherwise), so results repeat bit for bit.  When
 // the slots do not fit, the replica count steps down and finally the kernels bin straight into global memory.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_profile_device.hpp"
-#include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -31,9 +31,7 @@ constexpr int64_t PROF_SCRATCH_BYTES = int64_t(256) << 20; // centres / image co
 
 }  // namespace
 
-struct mdx_prof {
-    int dev = 0;
-    hipStream_t stream = nullptr;
+struct mdx_prof : FrameEngine {
     int n_groups = 0, n_axes = 0;
     bool per_frame = false;
     int64_t n_points = 0;
@@ -43,13 +41,9 @@ struct mdx_prof {
     ProfPlan plan{};
     bool use_lds = true;
     size_t lds_bytes = 0;
-    int64_t frames_seen = 0, row_capacity = 0;
-    DeviceBuffer d_offsets, d_total, d_rows, d_stage[2], d_index, d_centres, d_images, d_shift, d_prev, d_image,
-        d_rmass;
-    std::vector<int32_t> index_host;   // what d_index holds
-    StagePipeline pipe;
+    int64_t row_capacity = 0;
+    DeviceBuffer d_offsets, d_total, d_rows, d_centres, d_images, d_shift, d_prev, d_image, d_rmass;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
-    StreamTimer timer;
     // recentring
     int rc_group = -1;
     int64_t rc_lo = 0, rc_hi = 0;
@@ -78,26 +72,12 @@ static void prof_plan_counters(mdx_prof *h, int limit)
     h->lds_bytes = (h->use_lds ? (size_t(plan.n_slots) << plan.rep_shift) * 4 : 0) + size_t(4) * (h->n_groups + 1);
 }
 
-// per-frame rows: capacity for `more` frames behind the ones seen.  Growing copies the rows and waits for the
-// stream, so the host and file routes ask once per call, before their copy / kernel pipeline starts.
+// per-frame rows: capacity for `more` frames behind the ones seen
 static int prof_grow_rows(mdx_prof *h, int64_t more)
 {
-    if (!h->per_frame || more <= 0)
+    if (!h->per_frame)
         return MDX_OK;
-    const int64_t S = h->plan.n_slots, need = h->frames_seen + more;
-    if (need <= h->row_capacity)
-        return MDX_OK;
-    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(64, 2 * h->row_capacity));
-    DeviceBuffer grown;
-    MDX_TRY(grown.ensure(size_t(4) * S * cap));
-    if (h->frames_seen > 0)
-        MDX_HIP(hipMemcpyAsync(grown.ptr, h->d_rows.ptr, size_t(4) * S * h->frames_seen, hipMemcpyDeviceToDevice,
-                               h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->d_rows.recycle();
-    h->d_rows = grown;
-    h->row_capacity = cap;
-    return MDX_OK;
+    return grow_rows(h->d_rows, h->stream, int64_t(4) * h->plan.n_slots, h->frames_seen, more, &h->row_capacity);
 }
 
 // ... and the rows of the next `more` frames zeroed
@@ -225,30 +205,6 @@ static int prof_accumulate_rows(mdx_prof *h, const float *d_pos, int64_t src_row
     return MDX_OK;
 }
 
-// host index -> d_index (kept while it does not change); *out = nullptr when index is NULL
-static int prof_upload_index(mdx_prof *h, const int32_t *index, int64_t n_index, int64_t n_atoms, const int **out)
-{
-    *out = nullptr;
-    if (!index)
-        return MDX_OK;
-    for (int64_t i = 0; i < n_index; ++i)
-        if (index[i] < 0 || index[i] >= n_atoms)
-            return fail(MDX_ERR_INVALID_VALUE, "particle index %d out of range [0, %lld)", index[i],
-                        (long long)n_atoms);
-    if (int64_t(h->index_host.size()) != n_index ||
-        memcmp(h->index_host.data(), index, size_t(4) * n_index) != 0) {
-        // kernels and staging copies of earlier calls may still read the old one
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        if (h->pipe.copy_stream)
-            MDX_HIP(hipStreamSynchronize(h->pipe.copy_stream));
-        MDX_TRY(h->d_index.ensure(size_t(4) * std::max<int64_t>(n_index, 1)));
-        MDX_HIP(hipMemcpy(h->d_index.ptr, index, size_t(4) * n_index, hipMemcpyHostToDevice));
-        h->index_host.assign(index, index + n_index);
-    }
-    *out = h->d_index.as<int>();
-    return MDX_OK;
-}
-
 extern "C" {
 
 int mdx_prof_create(mdx_prof_t *out, int dev, int n_groups, const int64_t *group_offsets, int n_axes,
@@ -325,17 +281,9 @@ int mdx_prof_destroy(mdx_prof_t h)
 {
     if (!h)
         return MDX_OK;
-    (void)hipSetDevice(h->dev);
-    if (h->stream)
-        (void)hipStreamSynchronize(h->stream);
-    h->timer.destroy();
-    h->pipe.destroy();      // waits for its copy stream
-    for (DeviceBuffer *b : {&h->d_offsets, &h->d_total, &h->d_rows, &h->d_stage[0], &h->d_stage[1], &h->d_index,
-                            &h->d_centres, &h->d_images, &h->d_shift, &h->d_prev, &h->d_image, &h->d_rmass})
-        b->recycle();
+    h->release({&h->d_offsets, &h->d_total, &h->d_rows, &h->d_centres, &h->d_images, &h->d_shift, &h->d_prev,
+                &h->d_image, &h->d_rmass});
     h->mol.recycle();
-    if (h->stream)
-        stream_release(h->stream);
     delete h;
     return MDX_OK;
 }
@@ -415,8 +363,9 @@ int mdx_prof_accumulate_device(mdx_prof_t h, const float *d_pos, int64_t n_atoms
     MDX_REQUIRE(h && d_pos, "NULL argument");
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     MDX_TRY(set_device(h->dev));
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(prof_upload_index(h, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return prof_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
 }
 
@@ -425,20 +374,11 @@ int mdx_prof_accumulate(mdx_prof_t h, const float *pos, int64_t n, int64_t n_fra
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
     MDX_TRY(set_device(h->dev));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1),
-                                           std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
     MDX_TRY(prof_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return prof_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return prof_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -450,26 +390,18 @@ int mdx_prof_accumulate_traj(mdx_prof_t h, mdx_traj_t traj, const int64_t *frame
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     MDX_TRY(set_device(h->dev));
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     if (n_frames == 0)
         return MDX_OK;
-    MDX_TRY(h->pipe.ensure());
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(prof_upload_index(h, index, n_index, t->n_atoms, &d_index));
-    const int64_t slab = std::min<int64_t>(
-        n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     MDX_TRY(prof_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return prof_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return prof_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_prof_synchronize(mdx_prof_t h)
@@ -511,12 +443,7 @@ int mdx_prof_counts(mdx_prof_t h, int axis_slot, int64_t *out)
 int mdx_prof_stats(mdx_prof_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int *replicas)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
+    MDX_TRY(h->stats(true, launches, kernel_ms, frames));
     if (replicas) *replicas = h->use_lds ? 1 << h->plan.rep_shift : 0;
     return MDX_OK;
 }
@@ -524,8 +451,7 @@ int mdx_prof_stats(mdx_prof_t h, int64_t *launches, double *kernel_ms, int64_t *
 int mdx_prof_enable_timing(mdx_prof_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

@@ -12,9 +12,9 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_residence_device.hpp"
-#include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -28,25 +28,19 @@ constexpr int64_t PRS_HISTORY_BYTES = int64_t(256) << 20;   // what the frames o
 
 }  // namespace
 
-struct mdx_prs {
-    int dev = 0;
+struct mdx_prs : FrameEngine {
     bool ready = false;                 // the device side exists
-    hipStream_t stream = nullptr;
     int n_lags = 0, keep = 7, max_nb = 32;
     bool same = false, continuous = true;
     int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
     int64_t max_lag = 0, origin_step = 1;
-    int64_t frames_seen = 0, slab_frames = 0;   // slab_frames: 0 = the default
     int64_t cap = 0;                    // frames the rings hold
     int max_row = 0;                    // the largest row seen, as of the last look
     PrsBox box;
     double rc2 = 0.0;
     std::vector<int64_t> lags;
     // d_sums: uint64 [3][n_lags] intermittent, continuous, origin_counts; d_contacts: uint64, one per frame seen
-    DeviceBuffer d_lags, d_sums, d_contacts, d_max_row, d_slab, d_len, d_list, d_mask, d_stage[2], d_index;
-    std::vector<int32_t> index_host;    // what d_index holds
-    StagePipeline pipe;
-    StreamTimer timer;
+    DeviceBuffer d_lags, d_sums, d_contacts, d_max_row, d_slab, d_len, d_list, d_mask;
 };
 
 // bytes a frame takes: its gathered rows while it is in flight, its lists and masks while it is in the rings
@@ -249,16 +243,9 @@ int mdx_prs_destroy(mdx_prs_t h)
 {
     if (!h)
         return MDX_OK;
-    if (h->stream) {
-        (void)hipSetDevice(h->dev);
-        (void)hipStreamSynchronize(h->stream);
-        h->timer.destroy();
-        h->pipe.destroy();      // waits for its copy stream
-        for (DeviceBuffer *b : {&h->d_lags, &h->d_sums, &h->d_contacts, &h->d_max_row, &h->d_slab, &h->d_len,
-                                &h->d_list, &h->d_mask, &h->d_stage[0], &h->d_stage[1], &h->d_index})
-            b->recycle();
-        stream_release(h->stream);
-    }
+    if (h->stream)
+        h->release({&h->d_lags, &h->d_sums, &h->d_contacts, &h->d_max_row, &h->d_slab, &h->d_len, &h->d_list,
+                    &h->d_mask});
     delete h;
     return MDX_OK;
 }
@@ -294,15 +281,13 @@ int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, 
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     const int64_t n = index ? n_index : n_atoms;
     MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(prs_ensure_device(h));
     MDX_TRY(prs_ensure_rings(h));
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return prs_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
 }
 
@@ -315,18 +300,10 @@ int mdx_prs_accumulate(mdx_prs_t h, const float *pos, int64_t n, int64_t n_frame
         return MDX_OK;
     MDX_TRY(prs_ensure_device(h));
     MDX_TRY(prs_ensure_rings(h));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return prs_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return prs_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
@@ -337,31 +314,20 @@ int mdx_prs_accumulate_traj(mdx_prs_t h, mdx_traj_t traj, const int64_t *frames,
     MDX_REQUIRE(h && traj, "NULL handle");
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)t->n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(prs_ensure_device(h));
     MDX_TRY(prs_ensure_rings(h));
-    MDX_TRY(h->pipe.ensure());
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
-                                  &d_index));
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return prs_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return prs_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_prs_synchronize(mdx_prs_t h)
@@ -408,17 +374,12 @@ int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *max_row)
 {
     MDX_REQUIRE(h, "NULL handle");
+    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
     if (h->ready) {
-        MDX_TRY(set_device(h->dev));
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        h->timer.collect();
         int32_t row = 0;
         MDX_HIP(hipMemcpy(&row, h->d_max_row.ptr, 4, hipMemcpyDeviceToHost));
         h->max_row = row;
     }
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
     if (evaluations) *evaluations = h->frames_seen * (h->n1 * h->n2 - (h->same ? h->n1 : 0));
     if (max_row) *max_row = h->max_row;
     return MDX_OK;
@@ -427,8 +388,7 @@ int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *fr
 int mdx_prs_enable_timing(mdx_prs_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

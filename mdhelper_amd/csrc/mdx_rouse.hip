@@ -12,11 +12,11 @@
 // added with atomics and no sum is split across lanes, so the rows repeat bit for bit whatever route the frames
 // take and however they are split into calls.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_points_device.hpp"
 #include "mdx_rouse_device.hpp"
-#include "mdx_traj.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -33,40 +33,20 @@ constexpr int64_t ROUSE_SCRATCH_BYTES = int64_t(256) << 20; // centres / image c
 
 }  // namespace
 
-struct mdx_rouse {
-    int dev = 0;
-    hipStream_t stream = nullptr;
+struct mdx_rouse : FrameEngine {
     int n_groups = 0;
     int64_t n_points = 0, n_series = 0, n_units = 0;
-    int64_t frames_seen = 0, row_capacity = 0;
+    int64_t row_capacity = 0;
     bool unwrap = false;
     double dims[3] = {0, 0, 0};
     std::vector<double> start;         // [n_points][3]: x_prev before the first frame
-    DeviceBuffer d_units, d_weights, d_rows, d_stage[2], d_index, d_centres, d_images, d_prev, d_image;
-    std::vector<int32_t> index_host;   // what d_index holds
-    StagePipeline pipe;
+    DeviceBuffer d_units, d_weights, d_rows, d_centres, d_images, d_prev, d_image;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
-    StreamTimer timer;
 };
 
-// capacity for `more` frames behind the ones seen (doubling unless `exact`).  Growing copies the rows and waits for
-// the stream, so the host and file routes ask once per call, before their copy / kernel pipeline starts.
 static int rouse_grow_rows(mdx_rouse *h, int64_t more, bool exact = false)
 {
-    const int64_t row = int64_t(24) * h->n_series, need = h->frames_seen + more;
-    if (more <= 0 || need <= h->row_capacity)
-        return MDX_OK;
-    const int64_t cap = exact ? need : std::max<int64_t>(need, std::max<int64_t>(64, 2 * h->row_capacity));
-    DeviceBuffer grown;
-    MDX_TRY(grown.ensure(size_t(row * cap)));
-    if (h->frames_seen > 0)
-        MDX_HIP(hipMemcpyAsync(grown.ptr, h->d_rows.ptr, size_t(row * h->frames_seen), hipMemcpyDeviceToDevice,
-                               h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->d_rows.recycle();
-    h->d_rows = grown;
-    h->row_capacity = cap;
-    return MDX_OK;
+    return grow_rows(h->d_rows, h->stream, int64_t(24) * h->n_series, h->frames_seen, more, &h->row_capacity, exact);
 }
 
 template <typename SRC>
@@ -215,17 +195,8 @@ int mdx_rouse_destroy(mdx_rouse_t h)
 {
     if (!h)
         return MDX_OK;
-    (void)hipSetDevice(h->dev);
-    if (h->stream)
-        (void)hipStreamSynchronize(h->stream);
-    h->timer.destroy();
-    h->pipe.destroy();      // waits for its copy stream
-    for (DeviceBuffer *b : {&h->d_units, &h->d_weights, &h->d_rows, &h->d_stage[0], &h->d_stage[1], &h->d_index,
-                            &h->d_centres, &h->d_images, &h->d_prev, &h->d_image})
-        b->recycle();
+    h->release({&h->d_units, &h->d_weights, &h->d_rows, &h->d_centres, &h->d_images, &h->d_prev, &h->d_image});
     h->mol.recycle();
-    if (h->stream)
-        stream_release(h->stream);
     delete h;
     return MDX_OK;
 }
@@ -289,8 +260,9 @@ int mdx_rouse_accumulate_device(mdx_rouse_t h, const float *d_pos, int64_t n_ato
     MDX_REQUIRE(h && d_pos, "NULL argument");
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     MDX_TRY(set_device(h->dev));
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return rouse_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
 }
 
@@ -299,20 +271,11 @@ int mdx_rouse_accumulate(mdx_rouse_t h, const float *pos, int64_t n, int64_t n_f
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
     MDX_TRY(set_device(h->dev));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1),
-                                           std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
     MDX_TRY(rouse_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return rouse_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return rouse_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -324,27 +287,18 @@ int mdx_rouse_accumulate_traj(mdx_rouse_t h, mdx_traj_t traj, const int64_t *fra
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     MDX_TRY(set_device(h->dev));
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     if (n_frames == 0)
         return MDX_OK;
-    MDX_TRY(h->pipe.ensure());
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
-                                  &d_index));
-    const int64_t slab = std::min<int64_t>(
-        n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     MDX_TRY(rouse_grow_rows(h, n_frames));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return rouse_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return rouse_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_rouse_synchronize(mdx_rouse_t h)
@@ -382,20 +336,13 @@ int mdx_rouse_device_result(mdx_rouse_t h, const double **d_ptr, int64_t *n_fram
 int mdx_rouse_stats(mdx_rouse_t h, int64_t *launches, double *kernel_ms, int64_t *frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
-    return MDX_OK;
+    return h->stats(true, launches, kernel_ms, frames);
 }
 
 int mdx_rouse_enable_timing(mdx_rouse_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

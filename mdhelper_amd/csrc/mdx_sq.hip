@@ -22,13 +22,13 @@
 // pair products and accumulates over the frames of the slab in frame order, so
 // results are run-to-run reproducible.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 
 using namespace mdx;
 
 #include "mdx_sq_device.hpp"
-#include "mdx_traj.hpp"
 
 using namespace mdx_sq_dev;
 
@@ -228,8 +228,8 @@ struct mdx_sq {
     int n_groups = 0, n_pairs = 0;
     int64_t n_total = 0;
     std::vector<int64_t> offsets;
-    DeviceBuffer d_q, d_offsets, d_pairs, d_acc, d_rho, d_stage[2], d_index, d_mtrip;
-    StagePipeline pipe;   // host-buffer / trajectory-file entry points
+    DeviceBuffer d_q, d_offsets, d_pairs, d_acc, d_rho, d_mtrip;
+    FrameFeed feed;       // host-buffer / trajectory-file entry points
     MoleculeStage mol;    // optional centre-of-mass stage (groupings other than "atoms")
     StreamTimer timer;
     bool lattice = false;        // wavevectors are integer multiples of one base per axis
@@ -536,12 +536,11 @@ int mdx_sq_destroy(mdx_sq_t h)
     if (h->stream)
         (void)hipStreamSynchronize(h->stream);
     h->timer.destroy();
-    h->pipe.destroy();      // waits for its copy stream
+    h->feed.destroy();      // waits for its copy stream
     // (every stream that touched them is idle: blocks and stream go back to the per-device pools, so that an
     // analysis object per call does not pay hipMalloc / hipFree / stream creation each time)
-    for (DeviceBuffer *b : {&h->d_q, &h->d_offsets, &h->d_pairs, &h->d_acc, &h->d_rho, &h->d_stage[0],
-                            &h->d_stage[1], &h->d_index, &h->d_mtrip, &h->d_items, &h->d_qitems,
-                            &h->d_chain_items, &h->d_chain_qmap})
+    for (DeviceBuffer *b : {&h->d_q, &h->d_offsets, &h->d_pairs, &h->d_acc, &h->d_rho, &h->d_mtrip, &h->d_items,
+                            &h->d_qitems, &h->d_chain_items, &h->d_chain_qmap})
         b->recycle();
     h->mol.recycle();
     if (h->stream)
@@ -606,19 +605,8 @@ int mdx_sq_accumulate(mdx_sq_t h, const float *pos, int64_t n, int64_t n_frames)
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
     MDX_TRY(set_device(h->dev));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(std::max<int64_t>(n_frames, 1),
-                                           std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                         pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return sq_accumulate_device(h, h->d_stage[b].as<float>(), n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int { return sq_accumulate_device(h, d_pos, n, nf); });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the
@@ -637,30 +625,20 @@ int mdx_sq_accumulate_traj(mdx_sq_t h, mdx_traj_t traj, const int64_t *frames, i
     MDX_REQUIRE(index || n <= t->n_atoms, "selection larger than the trajectory");
     if (n_frames == 0)
         return MDX_OK;
-    MDX_TRY(h->pipe.ensure());
+    MDX_TRY(h->feed.pipe.ensure());
     const int *d_index = nullptr;
     if (index) {
         for (int64_t i = 0; i < n; ++i)
             if (index[i] < 0 || index[i] >= t->n_atoms)
                 return fail(MDX_ERR_INVALID_VALUE, "particle index %d out of range [0, %lld)",
                             index[i], (long long)t->n_atoms);
-        MDX_HIP(hipStreamSynchronize(h->pipe.copy_stream));
-        MDX_TRY(h->d_index.ensure(size_t(4) * n));
-        MDX_HIP(hipMemcpy(h->d_index.ptr, index, size_t(4) * n, hipMemcpyHostToDevice));
-        d_index = h->d_index.as<int>();
+        MDX_HIP(hipStreamSynchronize(h->feed.pipe.copy_stream));
+        MDX_TRY(h->feed.d_index.ensure(size_t(4) * n));
+        MDX_HIP(hipMemcpy(h->feed.d_index.ptr, index, size_t(4) * n, hipMemcpyHostToDevice));
+        d_index = h->feed.d_index.as<int>();
     }
-    const int64_t slab = std::min<int64_t>(
-        n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return sq_accumulate_device(h, h->d_stage[b].as<float>(), n, nf);
-        });
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int { return sq_accumulate_device(h, d_pos, n, nf); });
 }
 
 int mdx_sq_result(mdx_sq_t h, double *ssf)

@@ -12,8 +12,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
-#include "mdx_traj.hpp"
 #include "mdx_vanhove_device.hpp"
 
 #include <algorithm>
@@ -28,13 +28,11 @@ constexpr int64_t VH_HISTORY_BYTES = int64_t(256) << 20;    // what the frames o
 
 }  // namespace
 
-struct mdx_vh {
-    int dev = 0;
+struct mdx_vh : FrameEngine {
     bool ready = false;                 // the device side exists
-    hipStream_t stream = nullptr;
     int n_groups = 0, n_bins = 0, n_lags = 0, keep = 7;
     int64_t n_points = 0, max_lag = 0;
-    int64_t frames_seen = 0, slab_frames = 0, evaluations = 0;      // slab_frames: 0 = the default
+    int64_t evaluations = 0;
     int64_t cap = 0;                    // frames the ring holds
     bool unwrap = false;
     double dims[3] = {0, 0, 0};
@@ -42,11 +40,7 @@ struct mdx_vh {
     std::vector<VhTile> tiles;
     std::vector<int64_t> offsets, lags;
     std::vector<double> edges;
-    DeviceBuffer d_tiles, d_offsets, d_lags, d_edges, d_counts, d_acc, d_moments, d_hist, d_prev, d_image,
-        d_stage[2], d_index;
-    std::vector<int32_t> index_host;    // what d_index holds
-    StagePipeline pipe;
-    StreamTimer timer;
+    DeviceBuffer d_tiles, d_offsets, d_lags, d_edges, d_counts, d_acc, d_moments, d_hist, d_prev, d_image;
 };
 
 static int64_t vh_slab(const mdx_vh *h)
@@ -209,17 +203,9 @@ int mdx_vh_destroy(mdx_vh_t h)
 {
     if (!h)
         return MDX_OK;
-    if (h->stream) {
-        (void)hipSetDevice(h->dev);
-        (void)hipStreamSynchronize(h->stream);
-        h->timer.destroy();
-        h->pipe.destroy();      // waits for its copy stream
-        for (DeviceBuffer *b : {&h->d_tiles, &h->d_offsets, &h->d_lags, &h->d_edges, &h->d_counts, &h->d_acc,
-                                &h->d_moments, &h->d_hist, &h->d_prev, &h->d_image, &h->d_stage[0], &h->d_stage[1],
-                                &h->d_index})
-            b->recycle();
-        stream_release(h->stream);
-    }
+    if (h->stream)
+        h->release({&h->d_tiles, &h->d_offsets, &h->d_lags, &h->d_edges, &h->d_counts, &h->d_acc, &h->d_moments,
+                    &h->d_hist, &h->d_prev, &h->d_image});
     delete h;
     return MDX_OK;
 }
@@ -268,15 +254,13 @@ int mdx_vh_accumulate_device(mdx_vh_t h, const float *d_pos, int64_t n_atoms, in
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     const int64_t n = index ? n_index : n_atoms;
     MDX_REQUIRE(n == h->n_points, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_points);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(vh_ensure_device(h));
     MDX_TRY(vh_ensure_history(h));
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return vh_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
 }
 
@@ -289,18 +273,10 @@ int mdx_vh_accumulate(mdx_vh_t h, const float *pos, int64_t n, int64_t n_frames)
         return MDX_OK;
     MDX_TRY(vh_ensure_device(h));
     MDX_TRY(vh_ensure_history(h));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return vh_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return vh_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -311,31 +287,20 @@ int mdx_vh_accumulate_traj(mdx_vh_t h, mdx_traj_t traj, const int64_t *frames, i
     MDX_REQUIRE(h && traj, "NULL handle");
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     MDX_REQUIRE(n == h->n_points, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n_points);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)t->n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(vh_ensure_device(h));
     MDX_TRY(vh_ensure_history(h));
-    MDX_TRY(h->pipe.ensure());
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
-                                  &d_index));
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return vh_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return vh_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_vh_synchronize(mdx_vh_t h)
@@ -378,14 +343,7 @@ int mdx_vh_point_moments(mdx_vh_t h, double *out)
 int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (h->ready) {
-        MDX_TRY(set_device(h->dev));
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        h->timer.collect();
-    }
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
+    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
     if (evaluations) *evaluations = h->evaluations;
     return MDX_OK;
 }
@@ -393,8 +351,7 @@ int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *fram
 int mdx_vh_enable_timing(mdx_vh_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"

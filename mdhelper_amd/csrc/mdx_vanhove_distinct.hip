@@ -11,8 +11,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
-#include "mdx_traj.hpp"
 #include "mdx_vanhove_distinct_device.hpp"
 
 #include <algorithm>
@@ -27,24 +27,19 @@ constexpr int64_t VHD_HISTORY_BYTES = int64_t(256) << 20;   // what the frames o
 
 }  // namespace
 
-struct mdx_vhd {
-    int dev = 0;
+struct mdx_vhd : FrameEngine {
     bool ready = false;                 // the device side exists
-    hipStream_t stream = nullptr;
     int n_bins = 0, n_lags = 0, keep = 7;
     bool same = false;
     int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
     int64_t max_lag = 0, origin_step = 1;
-    int64_t frames_seen = 0, slab_frames = 0, evaluations = 0;      // slab_frames: 0 = the default
+    int64_t evaluations = 0;
     int64_t cap = 0;                    // frames the ring holds
     VhdBox box;
     double inv_width = 0.0, r2_lo = 0.0, r2_hi = 0.0;
     std::vector<int64_t> lags;
     std::vector<double> edges;
-    DeviceBuffer d_lags, d_edges, d_counts, d_ring, d_stage[2], d_index;
-    std::vector<int32_t> index_host;    // what d_index holds
-    StagePipeline pipe;
-    StreamTimer timer;
+    DeviceBuffer d_lags, d_edges, d_counts, d_ring;
 };
 
 static int64_t vhd_slab(const mdx_vhd *h)
@@ -205,16 +200,8 @@ int mdx_vhd_destroy(mdx_vhd_t h)
 {
     if (!h)
         return MDX_OK;
-    if (h->stream) {
-        (void)hipSetDevice(h->dev);
-        (void)hipStreamSynchronize(h->stream);
-        h->timer.destroy();
-        h->pipe.destroy();      // waits for its copy stream
-        for (DeviceBuffer *b : {&h->d_lags, &h->d_edges, &h->d_counts, &h->d_ring, &h->d_stage[0], &h->d_stage[1],
-                                &h->d_index})
-            b->recycle();
-        stream_release(h->stream);
-    }
+    if (h->stream)
+        h->release({&h->d_lags, &h->d_edges, &h->d_counts, &h->d_ring});
     delete h;
     return MDX_OK;
 }
@@ -250,15 +237,13 @@ int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, 
     MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
     const int64_t n = index ? n_index : n_atoms;
     MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(vhd_ensure_device(h));
     MDX_TRY(vhd_ensure_ring(h));
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, n_atoms, &d_index));
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
     return vhd_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
 }
 
@@ -271,18 +256,10 @@ int mdx_vhd_accumulate(mdx_vhd_t h, const float *pos, int64_t n, int64_t n_frame
         return MDX_OK;
     MDX_TRY(vhd_ensure_device(h));
     MDX_TRY(vhd_ensure_ring(h));
-    // copies of slab k+1 overlap the kernels of slab k (StagePipeline)
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * n)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            return device_stager(h->dev).upload(h->dev, h->pipe.copy_stream, h->d_stage[b].ptr,
-                                                pos + f0 * n * 3, size_t(12) * n * nf);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return vhd_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return vhd_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
@@ -293,31 +270,20 @@ int mdx_vhd_accumulate_traj(mdx_vhd_t h, mdx_traj_t traj, const int64_t *frames,
     MDX_REQUIRE(h && traj, "NULL handle");
     MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
     Trajectory *t = mdx_traj_internal(traj);
-    const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
-    MDX_REQUIRE(n > 0 && (index || n <= t->n_atoms), "selection larger than the trajectory");
+    int64_t n = 0;
+    MDX_TRY(traj_selection(t, index, n_index, &n));
     MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    for (int64_t i = 0; index && i < n_index; ++i)
-        MDX_REQUIRE(index[i] >= 0 && index[i] < t->n_atoms, "particle index %d out of range [0, %lld)", index[i],
-                    (long long)t->n_atoms);
+    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
     if (n_frames == 0)
         return MDX_OK;
     MDX_TRY(vhd_ensure_device(h));
     MDX_TRY(vhd_ensure_ring(h));
-    MDX_TRY(h->pipe.ensure());
     const int *d_index = nullptr;
-    MDX_TRY(upload_particle_index(h->stream, h->pipe, h->d_index, h->index_host, index, n_index, t->n_atoms,
-                                  &d_index));
-    const int64_t slab = std::min<int64_t>(n_frames, std::max<int64_t>(1, (int64_t(64) << 20) / (12 * t->n_atoms)));
-    return h->pipe.run(
-        h->stream, n_frames, slab,
-        [&](int b, int64_t f0, int64_t nf) -> int {
-            MDX_TRY(h->d_stage[b].ensure(size_t(12) * n * slab));
-            TrajSelection sel{d_index, n, h->d_stage[b].as<float>()};
-            return t->stage_async(h->dev, h->pipe.copy_stream, frames + f0, nf, &sel, 1);
-        },
-        [&](int b, int64_t, int64_t nf) -> int {
-            return vhd_accumulate_rows(h, h->d_stage[b].as<float>(), n, nullptr, n, nf);
-        });
+    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
+    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                        [&](const float *d_pos, int64_t nf) -> int {
+                            return vhd_accumulate_rows(h, d_pos, n, nullptr, n, nf);
+                        });
 }
 
 int mdx_vhd_synchronize(mdx_vhd_t h)
@@ -344,14 +310,7 @@ int mdx_vhd_result(mdx_vhd_t h, int64_t *counts)
 int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (h->ready) {
-        MDX_TRY(set_device(h->dev));
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        h->timer.collect();
-    }
-    if (launches) *launches = h->timer.launches;
-    if (kernel_ms) *kernel_ms = h->timer.total_ms;
-    if (frames) *frames = h->frames_seen;
+    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
     if (evaluations) *evaluations = h->evaluations;
     return MDX_OK;
 }
@@ -359,8 +318,7 @@ int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *fr
 int mdx_vhd_enable_timing(mdx_vhd_t h, int on)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->timer.enabled = on != 0;
-    return MDX_OK;
+    return h->enable_timing(on);
 }
 
 }  // extern "C"
