@@ -17,12 +17,10 @@ import numpy as np
 
 from .. import _core, _lib
 from ..algorithm.unit import strip_unit
-from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, all_particles, block_frames, block_source,
-                   frame_blocks, has_frame_blocks)
-from ..comm import shard_range
+from .base import DynamicAnalysisBase, EngineFedAnalysis, parse_drop_axis, zero_dims
 
 
-class Clusters(DynamicAnalysisBase):
+class Clusters(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Connected components of the contact graph of ``groups``: two atoms are bonded in a frame where their
     minimum-image distance is at most the cutoff of their two groups, and a cluster is a set of atoms connected by
@@ -106,74 +104,21 @@ class Clusters(DynamicAnalysisBase):
             raise ValueError(f"'max_neighbors' must lie in [1, {_core.ClusterEngine.MAX_NEIGHBORS}].")
         self._store_labels = bool(store_labels)
 
-        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
-        if self._drop_axis not in {0, 1, 2, None}:
-            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
-                             "and 2 or 'z'.")
-        if dimensions is not None:
-            if len(dimensions) != 3:
-                raise ValueError("'dimensions' must have length 3.")
-            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
-        elif self.universe.dimensions is not None:
-            box = np.asarray(self.universe.dimensions, dtype=float)
-            if len(box) > 3 and not np.all(box[3:6] == 90.0):
-                raise ValueError("Clusters needs an orthorhombic box.")
-            self._dimensions = box[:3].copy()
-        else:
-            raise ValueError("The minimum image needs the box lengths: no system dimensions found or provided.")
-        if not (np.all(np.isfinite(self._dimensions)) and np.all(self._dimensions > 0)):
-            raise ValueError("The box lengths must be positive and finite.")
-        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
-        if self._cutoff.max() > self._dimensions[kept].min() / 2:
-            raise ValueError("'cutoff' reaches beyond half the shortest box length, where the minimum image is not "
-                             "the nearest image.")
+        self._drop_axis = parse_drop_axis(drop_axis)
+        self._dimensions = self._box_lengths(dimensions, self._cutoff.max(), "cutoff")
         self._verbose = verbose
 
     # ------------------------------------------------------------------ protocol
 
+    _shard_frames = True        # a frame needs no other frame
+
     def _prepare(self) -> None:
         self.results.units = {"results.sizes": "atoms"}
         _lib.require_device(self._device)
-        self._engine = _core.ClusterEngine(
+        self._feed_engine(_core.ClusterEngine(
             self._species, self._cutoff, self._dimensions, n_species=len(self._groups),
-            zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis, max_neighbors=self._max_neighbors,
-            keep_labels=self._store_labels, dev=self._device)
-        # frames shard across ranks: a frame needs no other frame
-        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
-        self._batch = FrameBatcher(self._N, lambda p, b: self._engine.accumulate(p[0]), with_box=False)
-
-    def _single_frame(self) -> None:
-        lo, hi = self._frames_mine
-        if not lo <= self._frame_index < hi:
-            return
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory file, from
-    # float32 frames in HBM (read where they lie) or from host memory
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=True)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        try:
-            for sel in frame_blocks(mine, size):
-                route, src = block_source(traj, sel, True)
-                if route == "file":
-                    self._engine.accumulate_traj(src, sel, None if whole else index)
-                elif route == "hbm":
-                    self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-                else:
-                    self._engine.accumulate(src if whole else src[:, index])
-        except BaseException:
-            self._engine.close()
-            raise
-        self._conclude()
-        return self
+            zero_dims=zero_dims(self._drop_axis), max_neighbors=self._max_neighbors,
+            keep_labels=self._store_labels, dev=self._device), self._index)
 
     def _conclude(self) -> None:
         try:
@@ -186,19 +131,13 @@ class Clusters(DynamicAnalysisBase):
         F, n = self.n_frames, self._N
         size_counts, species_counts = counts["size_counts"], counts["species_counts"]
         if self._comm.world_size > 1:
-            # the counts add up at their full length n + 1; the per-frame arrays (and the labels) travel as this
-            # rank's rows inside a zero-filled array over all frames
+            # the counts add up at their full length n + 1; the per-frame arrays (and the labels) are gathered
             size_counts = np.asarray(self._comm.allreduce(size_counts, op="sum"))
             species_counts = np.asarray(self._comm.allreduce(species_counts, op="sum"))
-            lo, hi = self._frames_mine
             for key, rows in per_frame.items():
-                full = np.zeros(F, dtype=np.int64)
-                full[lo:hi] = rows
-                per_frame[key] = np.asarray(self._comm.allreduce(full, op="sum"))
+                per_frame[key] = self._gather_frame_rows(rows)
             if labels is not None:
-                full = np.zeros((F, n), dtype=np.int32)
-                full[lo:hi] = labels
-                labels = np.asarray(self._comm.allreduce(full, op="sum"))
+                labels = self._gather_frame_rows(labels)
         seen = np.flatnonzero(size_counts)
         s_max = int(seen[-1]) if len(seen) else 0
         res = self.results

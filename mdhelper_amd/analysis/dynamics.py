@@ -26,8 +26,8 @@ import numpy as np
 
 from .. import _core, _lib
 from ..algorithm.unit import strip_unit
-from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, all_particles, block_frames, block_source,
-                   frame_blocks, has_frame_blocks)
+from .base import (DynamicAnalysisBase, EngineFedAnalysis, kept_components, pair_selection, parse_drop_axis,
+                   parse_lags, shell_volumes, zero_dims)
 
 
 def calculate_non_gaussian_parameter(m2, m4, n_dims: int = 3):
@@ -51,7 +51,7 @@ def calculate_non_gaussian_parameter(m2, m4, n_dims: int = 3):
     return float(out) if out.ndim == 0 else out
 
 
-class VanHove(DynamicAnalysisBase):
+class VanHove(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Self part of the van Hove function and the moments of the displacements,
 
@@ -111,26 +111,10 @@ class VanHove(DynamicAnalysisBase):
             raise ValueError("'range' must be an increasing pair of finite numbers.")
         self._range = (r_min, r_max)
 
-        if lags is not None and n_lags is not None:
-            raise ValueError("'lags' and 'n_lags' cannot both be given.")
-        if n_lags is not None:
-            if int(n_lags) < 1:
-                raise ValueError("'n_lags' must be at least 1.")
-            lags = np.arange(int(n_lags))
-        if lags is not None:
-            lags = np.atleast_1d(np.asarray(lags))
-            if lags.ndim != 1 or len(lags) == 0 or not np.issubdtype(lags.dtype, np.integer):
-                raise ValueError("'lags' must be a one-dimensional array of integers.")
-            if lags[0] < 0 or np.any(np.diff(lags) <= 0):
-                raise ValueError("'lags' must be non-negative and strictly increasing.")
-            lags = lags.astype(np.int64)
-        self._lags = lags
+        self._lags = parse_lags(lags, n_lags)
 
         self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
-        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
-        if self._drop_axis not in {0, 1, 2, None}:
-            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
-                             "and 2 or 'z'.")
+        self._drop_axis = parse_drop_axis(drop_axis)
         if dimensions is not None:
             if len(dimensions) != 3:
                 raise ValueError("'dimensions' must have length 3.")
@@ -150,20 +134,9 @@ class VanHove(DynamicAnalysisBase):
     # ------------------------------------------------------------------ protocol
 
     def _prepare(self) -> None:
-        st = self._sliced_trajectory
-        if hasattr(st, "frames"):
-            df = np.diff(st.frames)
-            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
-                raise ValueError("The selected frames must be evenly spaced and proceed "
-                                 "forward in time.")
-            df = df[0] if len(df) else 1
-        else:
-            if st.step is not None and st.step <= 0:
-                raise ValueError("The analysis must proceed forward in time.")
-            df = st.step if st.step is not None else 1
+        df = self._frame_stride()
         lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
         self._lags_run = lags
-        self._index = np.concatenate([np.asarray(g.indices) for g in self._groups])
         edges = np.linspace(*self._range, self._n_bins + 1)
         self.results.edges = edges
         self.results.bins = (edges[:-1] + edges[1:]) / 2
@@ -175,44 +148,13 @@ class VanHove(DynamicAnalysisBase):
         _lib.require_device(self._device)
         # lags without an origin never meet a frame pair: the engine gets the others
         self._live = lags < self.n_frames
-        self._engine = None
+        engine = None
         if self._live.any():
-            self._engine = _core.VanHoveEngine(
-                self._Ns, edges, lags[self._live],
-                zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis, dev=self._device)
+            engine = _core.VanHoveEngine(self._Ns, edges, lags[self._live], zero_dims=zero_dims(self._drop_axis),
+                                         dev=self._device)
             if self._unwrap:
-                self._engine.set_unwrap(self._dimensions)
-        self._batch = FrameBatcher(len(self._index),
-                                   lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
-                                   with_box=False)
-
-    def _single_frame(self) -> None:
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory
-    # file, from float32 frames in HBM (read where they lie) or from host memory
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=False)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            if self._engine is None:
-                break
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
-        self._conclude()
-        return self
+                engine.set_unwrap(self._dimensions)
+        self._feed_engine(engine, np.concatenate([np.asarray(g.indices) for g in self._groups]))
 
     def _conclude(self) -> None:
         self._batch.flush()
@@ -224,10 +166,7 @@ class VanHove(DynamicAnalysisBase):
             self._engine.close()
         edges = self.results.edges
         n_dims = 3 if self._drop_axis is None else 2
-        if n_dims == 3:
-            shell = 4 * np.pi / 3 * (edges[1:] ** 3 - edges[:-1] ** 3)
-        else:
-            shell = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+        shell = shell_volumes(edges, n_dims)
         pairs = (np.maximum(self.n_frames - self._lags_run, 0)[:, None] * self._Ns[None, :]).astype(float)
         pairs[pairs == 0] = np.nan          # no origin (or an empty group): NaN, without a warning
         self.results.counts = counts
@@ -237,7 +176,7 @@ class VanHove(DynamicAnalysisBase):
         self.results.alpha2 = calculate_non_gaussian_parameter(self.results.msd, moments[:, :, 1] / pairs, n_dims)
 
 
-class DistinctVanHove(DynamicAnalysisBase):
+class DistinctVanHove(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Distinct part of the van Hove function,
 
@@ -299,73 +238,22 @@ class DistinctVanHove(DynamicAnalysisBase):
             raise ValueError("'range' must be an increasing pair of finite numbers.")
         self._range = (r_min, r_max)
 
-        if lags is not None and n_lags is not None:
-            raise ValueError("'lags' and 'n_lags' cannot both be given.")
-        if n_lags is not None:
-            if int(n_lags) < 1:
-                raise ValueError("'n_lags' must be at least 1.")
-            lags = np.arange(int(n_lags))
-        if lags is not None:
-            lags = np.atleast_1d(np.asarray(lags))
-            if lags.ndim != 1 or len(lags) == 0 or not np.issubdtype(lags.dtype, np.integer):
-                raise ValueError("'lags' must be a one-dimensional array of integers.")
-            if lags[0] < 0 or np.any(np.diff(lags) <= 0):
-                raise ValueError("'lags' must be non-negative and strictly increasing.")
-            lags = lags.astype(np.int64)
-        self._lags = lags
+        self._lags = parse_lags(lags, n_lags)
         self._origin_step = int(origin_step)
         if self._origin_step < 1:
             raise ValueError("'origin_step' must be at least 1.")
 
         self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
-        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
-        if self._drop_axis not in {0, 1, 2, None}:
-            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
-                             "and 2 or 'z'.")
-        if dimensions is not None:
-            if len(dimensions) != 3:
-                raise ValueError("'dimensions' must have length 3.")
-            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
-        elif self.universe.dimensions is not None:
-            box = np.asarray(self.universe.dimensions, dtype=float)
-            if len(box) > 3 and not np.all(box[3:6] == 90.0):
-                raise ValueError("DistinctVanHove needs an orthorhombic box.")
-            self._dimensions = box[:3].copy()
-        else:
-            raise ValueError("The minimum image needs the box lengths: no system dimensions found or provided.")
-        if not (np.all(np.isfinite(self._dimensions)) and np.all(self._dimensions > 0)):
-            raise ValueError("The box lengths must be positive and finite.")
-        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
-        if r_max > self._dimensions[kept].min() / 2:
-            raise ValueError("'range' reaches beyond half the shortest box length, where the minimum image is not "
-                             "the nearest image.")
+        self._drop_axis = parse_drop_axis(drop_axis)
+        self._dimensions = self._box_lengths(dimensions, r_max, "range")
 
-        i1 = np.asarray(ag1.indices)
-        i2 = i1 if ag2 is None else np.asarray(ag2.indices)
-        self._same = ag2 is None or np.array_equal(i1, i2)
-        if not self._same and len(np.intersect1d(i1, i2)):
-            raise ValueError("'ag1' and 'ag2' share some atoms: they must be disjoint, or the very same atoms in "
-                             "the same order.")
-        if len(i1) < 1 or len(i2) < 1:
-            raise ValueError("The groups must hold at least one atom.")
-        self._N1, self._N2 = len(i1), len(i2)
-        self._index = i1 if self._same else np.concatenate((i1, i2))
+        self._same, self._N1, self._N2, self._index = pair_selection(ag1, ag2)
         self._verbose = verbose
 
     # ------------------------------------------------------------------ protocol
 
     def _prepare(self) -> None:
-        st = self._sliced_trajectory
-        if hasattr(st, "frames"):
-            df = np.diff(st.frames)
-            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
-                raise ValueError("The selected frames must be evenly spaced and proceed "
-                                 "forward in time.")
-            df = df[0] if len(df) else 1
-        else:
-            if st.step is not None and st.step <= 0:
-                raise ValueError("The analysis must proceed forward in time.")
-            df = st.step if st.step is not None else 1
+        df = self._frame_stride()
         lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
         self._lags_run = lags
         edges = np.linspace(*self._range, self._n_bins + 1)
@@ -380,42 +268,12 @@ class DistinctVanHove(DynamicAnalysisBase):
         _lib.require_device(self._device)
         # lags without an origin never meet a frame pair: the engine gets the others
         self._live = lags < self.n_frames
-        self._engine = None
+        engine = None
         if self._live.any():
-            self._engine = _core.DistinctVanHoveEngine(
+            engine = _core.DistinctVanHoveEngine(
                 self._N1, self._N2, edges, lags[self._live], self._dimensions, same=self._same,
-                origin_step=self._origin_step, zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis,
-                dev=self._device)
-        self._batch = FrameBatcher(len(self._index),
-                                   lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
-                                   with_box=False)
-
-    def _single_frame(self) -> None:
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py), as VanHove.run
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=False)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            if self._engine is None:
-                break
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
-        self._conclude()
-        return self
+                origin_step=self._origin_step, zero_dims=zero_dims(self._drop_axis), dev=self._device)
+        self._feed_engine(engine, self._index)
 
     def _conclude(self) -> None:
         self._batch.flush()
@@ -424,11 +282,8 @@ class DistinctVanHove(DynamicAnalysisBase):
             counts[self._live] = self._engine.result()
             self._engine.close()
         edges = self.results.edges
-        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
-        if len(kept) == 3:
-            shell = 4 * np.pi / 3 * (edges[1:] ** 3 - edges[:-1] ** 3)
-        else:
-            shell = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+        kept = kept_components(self._drop_axis)
+        shell = shell_volumes(edges, len(kept))
         origins = self.results.n_origins.astype(float)
         origins[origins == 0] = np.nan          # no origin: NaN, without a warning
         partners = self._N2 - 1 if self._same else self._N2
@@ -465,7 +320,7 @@ def calculate_residence_time(times, survival):
     return float(((s[1:n] + s[:n - 1]) * np.diff(t[:n])).sum() / 2)
 
 
-class PairResidence(DynamicAnalysisBase):
+class PairResidence(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Survival functions of the contacts between two groups: with :math:`h_{ij}(t)=1` where the minimum-image distance
     of :math:`i\in1` and :math:`j\in2` is at most ``cutoff`` (:math:`j\ne i` for one set) and 0 otherwise,
@@ -529,20 +384,7 @@ class PairResidence(DynamicAnalysisBase):
         if not (np.isfinite(self._cutoff) and self._cutoff > 0):
             raise ValueError("'cutoff' must be positive and finite.")
 
-        if lags is not None and n_lags is not None:
-            raise ValueError("'lags' and 'n_lags' cannot both be given.")
-        if n_lags is not None:
-            if int(n_lags) < 1:
-                raise ValueError("'n_lags' must be at least 1.")
-            lags = np.arange(int(n_lags))
-        if lags is not None:
-            lags = np.atleast_1d(np.asarray(lags))
-            if lags.ndim != 1 or len(lags) == 0 or not np.issubdtype(lags.dtype, np.integer):
-                raise ValueError("'lags' must be a one-dimensional array of integers.")
-            if lags[0] < 0 or np.any(np.diff(lags) <= 0):
-                raise ValueError("'lags' must be non-negative and strictly increasing.")
-            lags = lags.astype(np.int64)
-        self._lags = lags
+        self._lags = parse_lags(lags, n_lags)
         self._origin_step = int(origin_step)
         if self._origin_step < 1:
             raise ValueError("'origin_step' must be at least 1.")
@@ -552,54 +394,16 @@ class PairResidence(DynamicAnalysisBase):
         self._continuous = bool(continuous)
 
         self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
-        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
-        if self._drop_axis not in {0, 1, 2, None}:
-            raise ValueError("Invalid value passed to 'drop_axis'. The valid values are 0 or 'x', 1 or 'y', "
-                             "and 2 or 'z'.")
-        if dimensions is not None:
-            if len(dimensions) != 3:
-                raise ValueError("'dimensions' must have length 3.")
-            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
-        elif self.universe.dimensions is not None:
-            box = np.asarray(self.universe.dimensions, dtype=float)
-            if len(box) > 3 and not np.all(box[3:6] == 90.0):
-                raise ValueError("PairResidence needs an orthorhombic box.")
-            self._dimensions = box[:3].copy()
-        else:
-            raise ValueError("The minimum image needs the box lengths: no system dimensions found or provided.")
-        if not (np.all(np.isfinite(self._dimensions)) and np.all(self._dimensions > 0)):
-            raise ValueError("The box lengths must be positive and finite.")
-        kept = [c for c in (0, 1, 2) if c != self._drop_axis]
-        if self._cutoff > self._dimensions[kept].min() / 2:
-            raise ValueError("'cutoff' reaches beyond half the shortest box length, where the minimum image is not "
-                             "the nearest image.")
+        self._drop_axis = parse_drop_axis(drop_axis)
+        self._dimensions = self._box_lengths(dimensions, self._cutoff, "cutoff")
 
-        i1 = np.asarray(ag1.indices)
-        i2 = i1 if ag2 is None else np.asarray(ag2.indices)
-        self._same = ag2 is None or np.array_equal(i1, i2)
-        if not self._same and len(np.intersect1d(i1, i2)):
-            raise ValueError("'ag1' and 'ag2' share some atoms: they must be disjoint, or the very same atoms in "
-                             "the same order.")
-        if len(i1) < 1 or len(i2) < 1:
-            raise ValueError("The groups must hold at least one atom.")
-        self._N1, self._N2 = len(i1), len(i2)
-        self._index = i1 if self._same else np.concatenate((i1, i2))
+        self._same, self._N1, self._N2, self._index = pair_selection(ag1, ag2)
         self._verbose = verbose
 
     # ------------------------------------------------------------------ protocol
 
     def _prepare(self) -> None:
-        st = self._sliced_trajectory
-        if hasattr(st, "frames"):
-            df = np.diff(st.frames)
-            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
-                raise ValueError("The selected frames must be evenly spaced and proceed "
-                                 "forward in time.")
-            df = df[0] if len(df) else 1
-        else:
-            if st.step is not None and st.step <= 0:
-                raise ValueError("The analysis must proceed forward in time.")
-            df = st.step if st.step is not None else 1
+        df = self._frame_stride()
         lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
         self._lags_run = lags
         self.results.times = lags * df * self._dt
@@ -610,42 +414,13 @@ class PairResidence(DynamicAnalysisBase):
         _lib.require_device(self._device)
         # lags without an origin never meet a frame pair: the engine gets the others
         self._live = lags < self.n_frames
-        self._engine = None
+        engine = None
         if self._live.any():
-            self._engine = _core.PairResidenceEngine(
+            engine = _core.PairResidenceEngine(
                 self._N1, self._N2, self._cutoff, lags[self._live], self._dimensions, same=self._same,
-                origin_step=self._origin_step, zero_dims=0 if self._drop_axis is None else 1 << self._drop_axis,
+                origin_step=self._origin_step, zero_dims=zero_dims(self._drop_axis),
                 max_neighbors=self._max_neighbors, continuous=self._continuous, dev=self._device)
-        self._batch = FrameBatcher(len(self._index),
-                                   lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
-                                   with_box=False)
-
-    def _single_frame(self) -> None:
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py), as VanHove.run
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=False)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            if self._engine is None:
-                break
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
-        self._conclude()
-        return self
+        self._feed_engine(engine, self._index)
 
     def _conclude(self) -> None:
         self._batch.flush()

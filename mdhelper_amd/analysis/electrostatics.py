@@ -22,10 +22,8 @@ import numpy as np
 from .. import _core
 from ..algorithm.topology import make_whole_images
 from ..algorithm.unit import strip_unit
-from ..comm import shard_range
 from ..universe import box_volumes
-from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, all_particles, block_frames, block_source,
-                   frame_blocks, has_frame_blocks)
+from .base import DynamicAnalysisBase, EngineFedAnalysis
 from .profile import ELEMENTARY_CHARGE, VACUUM_PERMITTIVITY
 
 # CODATA 2018 (exact)
@@ -60,7 +58,7 @@ def calculate_relative_permittivity(M, temperature: float, volume, *, reduced: b
     return float(1 + PERMITTIVITY_FACTOR * fluctuation / (V * temperature))
 
 
-class DipoleMoment(DynamicAnalysisBase):
+class DipoleMoment(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Instantaneous dipole moment vectors (reference :105-482),
 
@@ -206,17 +204,18 @@ class DipoleMoment(DynamicAnalysisBase):
 
     # ------------------------------------------------------------------ protocol
 
+    _shard_frames = True        # (unwrap, which makes the frames sequential, runs on one rank)
+
     def _prepare(self) -> None:
-        self._index = np.concatenate([np.asarray(g.indices) for g in self._groups])
-        self._engine = _core.DipoleEngine(self._Ns, self._effective_charges(), dev=self._device)
+        index = np.concatenate([np.asarray(g.indices) for g in self._groups])
+        engine = _core.DipoleEngine(self._Ns, self._effective_charges(), dev=self._device)
         if self._unwrap:
             st = self._sliced_trajectory
             self.universe.trajectory[st.frames[0] if hasattr(st, "frames") else (self.start or 0)]
             # the first analysed frame with every molecule whole, in float64
             positions = np.asarray(self.universe.trajectory.ts.positions, dtype=np.float64)
             images = make_whole_images(self.universe, self._dimensions)
-            self._engine.set_unwrap(self._dimensions,
-                                    positions[self._index] + images[self._index] * self._dimensions)
+            engine.set_unwrap(self._dimensions, positions[index] + images[index] * self._dimensions)
 
         self.results.dipoles = np.zeros((self.n_frames, self._n_groups, 3))
         self.results.volumes = np.zeros(self.n_frames)
@@ -224,55 +223,22 @@ class DipoleMoment(DynamicAnalysisBase):
         if not self._average:
             self.results.times = (self.step or 1) * self._trajectory.dt * np.arange(self.n_frames)
             self.results.units["results.times"] = "picosecond"
-        # frames shard across ranks (unwrap, which makes them sequential, runs on one rank)
-        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
-        self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
-                                   with_box=False)
+        self._feed_engine(engine, index)
 
     def _single_frame(self) -> None:
         self.results.volumes[self._frame_index] = self._ts.volume
-        lo, hi = self._frames_mine
-        if not lo <= self._frame_index < hi:
-            return
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
+        super()._single_frame()
 
-    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory
-    # file, from float32 frames in HBM (read where they lie) or from host memory
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=True)
-        boxes = traj.box_block(self._frame_numbers())
+    def _before_blocks(self) -> None:
+        boxes = self._trajectory.box_block(self._frame_numbers())
         if boxes is not None:
             self.results.volumes = box_volumes(boxes)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
-        self._conclude()
-        return self
 
     def _conclude(self) -> None:
         self._batch.flush()
         rows = self._engine.result()                        # [N_g, frames of this rank, 3]
         self._engine.close()
-        dipoles = np.ascontiguousarray(rows.transpose(1, 0, 2))
-        if self._comm.world_size > 1:                       # this rank's rows inside the full, zero-filled array
-            lo, hi = self._frames_mine
-            full = np.zeros((self.n_frames, self._n_groups, 3))
-            full[lo:hi] = dipoles
-            dipoles = np.asarray(self._comm.allreduce(full, op="sum"))
-        self.results.dipoles = dipoles
+        self.results.dipoles = self._gather_frame_rows(np.ascontiguousarray(rows.transpose(1, 0, 2)))
         if self._average:
             self.results.dipoles = self.results.dipoles.mean(axis=0)
             self.results.volumes = self.results.volumes.mean()

@@ -46,8 +46,7 @@ from ..algorithm import correlation
 from ..algorithm.topology import unwrap_edge
 from ..algorithm.unit import strip_unit
 from ..comm import shard_range
-from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, accumulate_blocks, all_particles,
-                   block_frames, block_source, frame_blocks, has_frame_blocks)
+from .base import DynamicAnalysisBase, EngineFedAnalysis, block_frames, grouping_of, has_frame_blocks
 
 _GROUPINGS = {"atoms", "residues"}
 
@@ -227,43 +226,20 @@ class _PolymerAnalysisBase(DynamicAnalysisBase):
                                    dimensions=self._dimensions, masses=pm)
         return start
 
-    def _point_selections(self):
-        """``_selection`` of every group; sets ``_index``, the rows of a frame in concatenated-group order."""
-        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
-        self._index = np.concatenate([sel[0] for sel in sels])
-        return sels
-
-    def _configure_points(self, engine, sels) -> None:
-        """Hands the grouping (monomers of several atoms) and the unwrap start to a chain engine."""
-        if any(sel[1] is not None for sel in sels):
-            sizes = [np.ones(len(idx), dtype=np.int64) if off is None else np.diff(off)
-                     for idx, off, _, _ in sels]
-            engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
-                                np.concatenate([sel[2] for sel in sels]))
+    def _feed_points(self, engine, sels) -> None:
+        """Hands the grouping (monomers of several atoms), the unwrap start and the rows of a frame — those of
+        ``sels``, the ``_selection`` of every group, in concatenated-group order — to a chain engine."""
+        grouping = grouping_of([sel[:3] for sel in sels])
+        if grouping is not None:
+            engine.set_grouping(*grouping)
         if self._unwrap:
             st = self._sliced_trajectory
             self.universe.trajectory[st.frames[0] if hasattr(st, "frames") else (self.start or 0)]
             engine.set_unwrap(self._dimensions, self._start(sels))
-
-    def _feed_blocks(self, mine) -> None:
-        """Whole blocks of the frames ``mine`` go to ``_engine`` from a trajectory file, from float32 frames in
-        HBM (read where they lie) or from host memory (the frame feed of base.py)."""
-        traj = self._trajectory
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
+        self._feed_engine(engine, np.concatenate([sel[0] for sel in sels]))
 
 
-class Gyradius(_PolymerAnalysisBase):
+class Gyradius(EngineFedAnalysis, _PolymerAnalysisBase):
     r"""
     Radius of gyration of polymer chains (reference :239-508),
 
@@ -315,6 +291,8 @@ class Gyradius(_PolymerAnalysisBase):
 
     # ------------------------------------------------------------------ protocol
 
+    _shard_frames = True        # (unwrap, which makes the frames sequential, runs on one rank)
+
     def _prepare(self) -> None:
         shape = [self._n_groups, self.n_frames]
         if self._components:
@@ -324,43 +302,15 @@ class Gyradius(_PolymerAnalysisBase):
 
         # rows of every frame in concatenated-group order, sorted monomer by monomer; the monomers'
         # centres of mass are formed on the device (plain-atom groups: monomers of one particle)
-        sels = self._point_selections()
-        self._engine = _core.GyrationEngine(self._n_chains, self._n_monomers,
-                                            np.concatenate([sel[3] for sel in sels]), dev=self._device)
-        self._configure_points(self._engine, sels)
-        # frames shard across ranks (unwrap, which makes them sequential, runs on one rank)
-        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
-        self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
-                                   with_box=False)
-
-    def _single_frame(self) -> None:
-        lo, hi = self._frames_mine
-        if not lo <= self._frame_index < hi:
-            return
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory
-    # file, from float32 frames in HBM (read where they lie) or from host memory
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        self._feed_blocks(self._batched_frames(start, stop, step, frames, shard=True))
-        self._conclude()
-        return self
+        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
+        self._feed_points(_core.GyrationEngine(self._n_chains, self._n_monomers,
+                                               np.concatenate([sel[3] for sel in sels]), dev=self._device), sels)
 
     def _conclude(self) -> None:
         self._batch.flush()
         radii = self._engine.result()                       # [N_g, frames of this rank, 4]
         self._engine.close()
-        radii = radii[..., 1:] if self._components else radii[..., 0]
-        if self._comm.world_size > 1:                       # this rank's rows inside the full, zero-filled array
-            lo, hi = self._frames_mine
-            full = np.zeros(self.results.gyradii.shape)
-            full[:, lo:hi] = radii
-            radii = np.asarray(self._comm.allreduce(full, op="sum"))
-        self.results.gyradii = radii
+        self.results.gyradii = self._gather_frame_rows(radii[..., 1:] if self._components else radii[..., 0], 1)
 
 
 class EndToEndVector(_PolymerAnalysisBase):
@@ -521,13 +471,12 @@ class EndToEndVector(_PolymerAnalysisBase):
             return super().run(start=start, stop=stop, step=step, frames=frames, n_jobs=n_jobs,
                                verbose=verbose, **kwargs)
         # trajectories with block access: the end monomers of ~256 MiB of frames at a time
-        first = 0
-        for chunk in frame_blocks(self._batched_frames(start, stop, step, frames, shard=False),
-                                  block_frames(self.universe.atoms.n_atoms, 1, 1 << 28)):
-            block = traj.frame_block(chunk)
+        mine = self._batched_frames(start, stop, step, frames, shard=False)
+        size = block_frames(self.universe.atoms.n_atoms, 1, 1 << 28)
+        for first in range(0, len(mine), size):
+            block = traj.frame_block(mine[first:first + size])
             for sel, s in zip(self._selections, self._slices):
                 self._store(first, self._ends_of_block(block[:, sel[0]], sel), s)
-            first += len(chunk)
         self._conclude()
         return self
 
@@ -577,7 +526,7 @@ class EndToEndVector(_PolymerAnalysisBase):
                     self.results.times[valid], acf[valid])
 
 
-class RouseModes(_PolymerAnalysisBase):
+class RouseModes(EngineFedAnalysis, _PolymerAnalysisBase):
     r"""
     Rouse mode amplitudes of polymer chains and their relaxation (no counterpart in the reference),
 
@@ -685,25 +634,11 @@ class RouseModes(_PolymerAnalysisBase):
         self.results.acf = np.empty((self._n_groups, self._n_blocks, P, self._n_frames_block))
         self.results.units = {"results.times": "picosecond", "results.amplitudes": "angstrom^2"}
 
-        sels = self._point_selections()
-        self._engine = _core.ChainProjectionEngine(self._n_chains, self._n_monomers, self._weights(),
-                                                   dev=self._device)
-        self._configure_points(self._engine, sels)
+        # every rank projects all frames: the chains shard in the correlation
+        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
+        self._feed_points(_core.ChainProjectionEngine(self._n_chains, self._n_monomers, self._weights(),
+                                                      dev=self._device), sels)
         self._engine.reserve(self.n_frames)
-        self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
-                                   with_box=False)
-
-    def _single_frame(self) -> None:
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py), the three routes of Gyradius.run; every rank sees all frames
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        if not has_frame_blocks(self._trajectory):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        self._feed_blocks(self._batched_frames(start, stop, step, frames, shard=False))
-        self._conclude()
-        return self
 
     def _conclude(self) -> None:
         self._batch.flush()
@@ -766,7 +701,7 @@ class RouseModes(_PolymerAnalysisBase):
                                                                            acf[valid])
 
 
-class SingleChainStructureFactor(DynamicAnalysisBase):
+class SingleChainStructureFactor(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Single-chain structure factor of a homopolymer (reference :805-1130):
 
@@ -903,36 +838,26 @@ class SingleChainStructureFactor(DynamicAnalysisBase):
 
     # ------------------------------------------------------------------ protocol
 
+    _shard_frames = True
+    _device_index = False       # SqEngine.accumulate_device takes every particle in order
+
     def _prepare(self) -> None:
         self.results.wavenumbers = np.unique(self._wavenumbers.round(11))
         self.results.units = {"results.wavenumbers": "angstrom^-1"}
         self._sel = self._selection()
-        self._engine = _core.SqEngine(self._wavevectors, [self._N], ((None, None),), dev=self._device)
-        self._engine.set_chains(self._n_monomers)
-        self._batch = FrameBatcher(int(self._N), lambda p, b: self._engine.accumulate(p[0]),
-                                   with_box=False)
-        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
+        engine = _core.SqEngine(self._wavevectors, [self._N], ((None, None),), dev=self._device)
+        engine.set_chains(self._n_monomers)
+        self._feed_engine(engine, self._sel[0], rows=int(self._N))
 
-    def _single_frame(self) -> None:
-        lo, hi = self._frames_mine
-        if not lo <= self._frame_index < hi:
-            return
-        self._batch.add([self._points(self._sel)])
+    def _frame_rows(self):
+        return self._points(self._sel)
 
-    # batched run (the frame feed of base.py), as in StructureFactor.run; monomer centres of mass are
-    # formed on the device
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        if not has_frame_blocks(self._trajectory):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=True)
-        index, offsets, masses = self._sel
+    # the batched route forms the monomer centres of mass on the device, which then cannot read the frames in HBM
+    def _before_blocks(self) -> None:
+        _, offsets, masses = self._sel
         if offsets is not None:
             self._engine.set_grouping(offsets, masses)
-        accumulate_blocks(self._engine, self._trajectory, mine, index, self._batch.capacity,
-                          hbm=offsets is None)
-        self._conclude()
-        return self
+            self._hbm = False
 
     def _conclude(self) -> None:
         from .structure import _mean_over_equal_wavenumbers

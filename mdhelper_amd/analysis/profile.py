@@ -27,9 +27,7 @@ from scipy.sparse.linalg import spsolve
 from .. import _core
 from ..algorithm.molecule import molecule_rows
 from ..algorithm.unit import strip_unit
-from ..comm import shard_range
-from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, all_particles, block_frames, block_source,
-                   frame_blocks, has_frame_blocks)
+from .base import DynamicAnalysisBase, EngineFedAnalysis, grouping_of
 
 # CODATA 2018: elementary charge (C, exact) and vacuum permittivity (F/m)
 ELEMENTARY_CHARGE = 1.602176634e-19
@@ -146,7 +144,7 @@ def _parse_axes(axes) -> np.ndarray:
                        count=len(axes), dtype=int)
 
 
-class DensityProfile(DynamicAnalysisBase):
+class DensityProfile(EngineFedAnalysis, DynamicAnalysisBase):
     r"""
     Number and charge density profiles :math:`\rho_i(z)` and :math:`\rho_q(z)=\sum_i z_ie\rho_i(z)`
     along the given axes (reference profile.py:287-996): particle positions are binned along each axis,
@@ -336,8 +334,9 @@ class DensityProfile(DynamicAnalysisBase):
 
     # ------------------------------------------------------------------ protocol
 
+    _shard_frames = True        # (recenter, which makes the frames sequential, runs on one rank)
+
     def _prepare(self) -> None:
-        world = self._comm.world_size
         self.results.bins = [
             np.linspace(self._dimensions[a] / (2 * self._n_bins[i]),
                         self._dimensions[a] - self._dimensions[a] / (2 * self._n_bins[i]), self._n_bins[i])
@@ -354,63 +353,24 @@ class DensityProfile(DynamicAnalysisBase):
         # rows of every frame in concatenated-group order; residue / segment centres of mass are formed on
         # the device from rows sorted molecule by molecule (plain-atom groups: molecules of one particle)
         rows = [molecule_rows(g, gr) for g, gr in zip(self._groups, self._groupings)]
-        self._index = np.concatenate([r[0] for r in rows])
-        self._engine = _core.ProfileEngine(self._Ns, self._axes, self._n_bins, self._dimensions,
-                                           per_frame=not self._average, dev=self._device)
-        if any(gr != "atoms" for gr in self._groupings):
-            sizes = [np.ones(len(i), dtype=np.int64) if off is None else np.diff(off) for i, off, _ in rows]
-            masses = [np.ones(len(i)) if m is None else m for i, _, m in rows]
-            self._engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
-                                      np.concatenate(masses))
+        engine = _core.ProfileEngine(self._Ns, self._axes, self._n_bins, self._dimensions,
+                                     per_frame=not self._average, dev=self._device)
+        grouping = grouping_of(rows)
+        if grouping is not None:
+            engine.set_grouping(*grouping)
         if self._recenter is not None:
             k, target = self._recenter
-            self._engine.set_recenter(k, getattr(self._groups[k], self._groupings[k]).masses, target)
-        # frames shard across ranks unless the recentring makes them sequential
-        self._frames_mine = shard_range(self.n_frames, self._comm.rank, world)
-        self._batch = FrameBatcher(len(self._index), lambda p, b: self._engine.accumulate(p[0]),
-                                   with_box=False)
-
-    def _single_frame(self) -> None:
-        lo, hi = self._frames_mine
-        if not lo <= self._frame_index < hi:
-            return
-        self._batch.add([np.asarray(self._ts.positions, dtype=np.float32)[self._index]])
-
-    # batched run (the frame feed of base.py): whole blocks of frames go to the engine from a trajectory
-    # file, from float32 frames in HBM (read where they lie) or from host memory
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        traj = self._trajectory
-        if not has_frame_blocks(traj):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=self._recenter is None)
-        index = self._index
-        whole = all_particles(index, traj.n_atoms)
-        size = (FILE_BLOCK if getattr(traj, "native", None) is not None
-                else block_frames(traj.n_atoms, self._batch.capacity, 1 << 30))
-        for sel in frame_blocks(mine, size):
-            route, src = block_source(traj, sel, True)
-            if route == "file":
-                self._engine.accumulate_traj(src, sel, None if whole else index)
-            elif route == "hbm":
-                self._engine.accumulate_device(src.ptr, traj.n_atoms, len(sel), None if whole else index)
-            else:
-                self._engine.accumulate(src if whole else src[:, index])
-        self._conclude()
-        return self
+            engine.set_recenter(k, getattr(self._groups[k], self._groupings[k]).masses, target)
+        self._feed_engine(engine, np.concatenate([r[0] for r in rows]))
 
     def _conclude(self) -> None:
         self._batch.flush()
         counts = self._engine.counts()
         self._engine.close()
         if self._comm.world_size > 1:
-            lo, hi = self._frames_mine
             for a, c in enumerate(counts):
-                if not self._average:      # this rank's rows inside the full, zero-filled array
-                    full = np.zeros((self._n_groups, self.n_frames, c.shape[-1]), dtype=np.int64)
-                    full[:, lo:hi] = c
-                    c = full
-                counts[a] = np.asarray(self._comm.allreduce(np.ascontiguousarray(c, dtype=np.int64)))
+                c = np.ascontiguousarray(c, dtype=np.int64)
+                counts[a] = np.asarray(self._comm.allreduce(c)) if self._average else self._gather_frame_rows(c, 1)
         V = np.prod(self._dimensions)
         self.results.number_densities = []
         for a, c in enumerate(counts):

@@ -34,8 +34,8 @@ from ..algorithm.unit import strip_unit
 from ..algorithm.utility import get_closest_factors
 from ..comm import shard_range
 from ..universe import box_volumes
-from .base import (FILE_BLOCK, DynamicAnalysisBase, FrameBatcher, NumbaAnalysisBase, accumulate_blocks,
-                   all_particles, block_frames, block_source, frame_blocks, has_frame_blocks)
+from .base import (FILE_BLOCK, DynamicAnalysisBase, EngineFedAnalysis, FrameBatcher, NumbaAnalysisBase, all_particles,
+                   block_frames, grouping_of, has_frame_blocks, parse_drop_axis, source_blocks)
 
 _GROUPINGS_RDF = {"atoms", "residues", "segments"}
 _KB_KJ_PER_MOL_K = 8.31446261815324e-3   # N_A * k_B in kJ/(mol K)
@@ -200,9 +200,7 @@ class RadialDistributionFunction(DynamicAnalysisBase):
                                      "'atoms', 'residues', and 'segments'.")
             self._groupings = list(2 * tuple(groupings) if len(groupings) == 1 else groupings)
 
-        self._drop_axis = ord(drop_axis) - 120 if isinstance(drop_axis, str) else drop_axis
-        if self._drop_axis not in {0, 1, 2, None}:
-            raise ValueError("Invalid axis to drop.")
+        self._drop_axis = parse_drop_axis(drop_axis, "Invalid axis to drop.")
         if norm not in {"rdf", "density", None}:
             raise ValueError("Invalid normalization.")
 
@@ -313,7 +311,8 @@ class RadialDistributionFunction(DynamicAnalysisBase):
             # k + 1 beside the kernels of slab k), every call boundary drains that pipeline once
             contiguous = len(mine) < 2 or bool(np.all(np.diff(mine) == 1))
             size = block_frames(traj.n_atoms, self._batch.capacity, (4 if contiguous else 1) << 30)
-        for sel in frame_blocks(mine, size):
+        # frames in HBM are read where they lie for one group of every particle
+        for sel, route, src in source_blocks(traj, mine, size, all1 and self._same and off1 is None):
             boxes = traj.box_block(sel)
             if self._drop_axis is None:
                 self._area_or_volume += float(box_volumes(boxes).sum())
@@ -321,8 +320,6 @@ class RadialDistributionFunction(DynamicAnalysisBase):
                 self._area_or_volume += float(
                     np.delete(np.asarray(boxes, dtype=np.float32)[:, :3], self._drop_axis, axis=1)
                     .prod(axis=1, dtype=np.float32).astype(float).sum())
-            # frames in HBM are read where they lie for one group of every particle
-            route, src = block_source(traj, sel, all1 and self._same and off1 is None)
             if route == "file":
                 self._engine.accumulate_traj(src, sel, boxes, None if all1 else i1,
                                              None if self._same else i2, same=self._same)
@@ -414,7 +411,7 @@ def _mean_over_equal_wavenumbers(x, wavenumbers, unique) -> np.ndarray:
     return np.stack([x[..., np.isclose(v, w)].mean(axis=-1) for v in q], axis=-1)
 
 
-class StructureFactor(NumbaAnalysisBase):
+class StructureFactor(EngineFedAnalysis, NumbaAnalysisBase):
     r"""
     Static / partial structure factor from particle positions (reference
     structure.py:1034-1550):
@@ -547,6 +544,9 @@ class StructureFactor(NumbaAnalysisBase):
         self._unique = unique
         self._verbose = verbose
 
+    _shard_frames = True        # frames shard across ranks (IntermediateScatteringFunction shards wavevectors)
+    _device_index = False       # SqEngine / IsfEngine.accumulate_device take every particle in order
+
     def _prepare(self) -> None:
         self.results.pairs = (
             tuple(combinations_with_replacement(range(self._n_groups), 2))
@@ -557,44 +557,25 @@ class StructureFactor(NumbaAnalysisBase):
         self.results.wavenumbers = (np.unique(self._wavenumbers.round(11))
                                     if self._unique else self._wavenumbers)
         self.results.units = {"results.wavenumbers": "angstrom^-1"}
-        self._engine = _core.SqEngine(self._wavevectors, self._Ns, self.results.pairs,
-                                      dev=self._device)
-        self._batch = FrameBatcher(int(self._N), lambda p, b: self._engine.accumulate(p[0]),
-                                   with_box=False)
         self._positions = np.empty((self._N, 3), dtype=np.float32)
-        self._frames_mine = shard_range(self.n_frames, self._comm.rank, self._comm.world_size)
+        self._feed_engine(_core.SqEngine(self._wavevectors, self._Ns, self.results.pairs, dev=self._device),
+                          rows=int(self._N))
 
-    def _single_frame(self) -> None:
-        lo, hi = self._frames_mine
-        if not lo <= self._frame_index < hi:
-            return
+    # the per-frame route forms residue centres of mass on the host ...
+    def _frame_rows(self):
         for g, gr, s in zip(self._groups, self._groupings, self._slices):
             self._positions[s] = _group_positions(g, gr)
-        self._batch.add([self._positions])
+        return self._positions
 
-    _shard_frames = True     # frames shard across ranks (IntermediateScatteringFunction shards wavevectors)
-
-    # batched run (the frame feed of base.py), shared with IntermediateScatteringFunction: whole blocks of
-    # frames go to the engine, gathered in concatenated-group order, instead of one Python iteration per frame
-    def run(self, start=None, stop=None, step=None, frames=None, verbose=None, **kwargs):
-        if not has_frame_blocks(self._trajectory):
-            return super().run(start=start, stop=stop, step=step, frames=frames, verbose=verbose,
-                               **kwargs)
-        mine = self._batched_frames(start, stop, step, frames, shard=self._shard_frames)
-        if self._engine is not None:        # (an ISF rank without wavevectors of its own adds nothing)
-            grouped = any(g != "atoms" for g in self._groupings)
-            rows = [molecule_rows(g, gr) for g, gr in zip(self._groups, self._groupings)]
-            if grouped:
-                # residue / segment centres of mass are formed on the device: rows sorted molecule
-                # by molecule; plain-atom groups enter as molecules of one particle and unit mass
-                sizes = [np.ones(len(i), dtype=np.int64) if off is None else np.diff(off) for i, off, _ in rows]
-                masses = [np.ones(len(i)) if m is None else m for i, _, m in rows]
-                self._engine.set_grouping(np.concatenate(([0], np.cumsum(np.concatenate(sizes)))),
-                                          np.concatenate(masses))
-            accumulate_blocks(self._engine, self._trajectory, mine, np.concatenate([r[0] for r in rows]),
-                              self._batch.capacity, hbm=not grouped)
-        self._conclude()
-        return self
+    # ... the batched one (shared with IntermediateScatteringFunction) on the device, from rows sorted molecule by
+    # molecule, and then cannot read the frames in HBM
+    def _before_blocks(self) -> None:
+        rows = [molecule_rows(g, gr) for g, gr in zip(self._groups, self._groupings)]
+        self._index = np.concatenate([r[0] for r in rows])
+        grouping = grouping_of(rows)
+        if grouping is not None:
+            self._engine.set_grouping(*grouping)
+            self._hbm = False
 
     def _conclude(self) -> None:
         self._batch.flush()
@@ -659,17 +640,7 @@ class IntermediateScatteringFunction(StructureFactor):
 
     def _prepare(self) -> None:
         self._n_lags = self._n_lags or self.n_frames
-        st = self._sliced_trajectory
-        if hasattr(st, "frames"):
-            df = np.diff(st.frames)
-            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
-                raise ValueError("The selected frames must be evenly spaced and proceed "
-                                 "forward in time.")
-            df = df[0] if len(df) else 1
-        else:
-            if st.step is not None and st.step <= 0:
-                raise ValueError("The analysis must proceed forward in time.")
-            df = st.step if st.step is not None else 1
+        df = self._frame_stride()
         self.results.pairs = (
             tuple(combinations_with_replacement(range(self._n_groups), 2))
             if self._mode == "partial"
@@ -683,19 +654,12 @@ class IntermediateScatteringFunction(StructureFactor):
         # frames and owns a contiguous block of wavevectors (frames cannot shard: every lag is needed)
         self._q_mine = shard_range(len(self._wavevectors), self._comm.rank, self._comm.world_size)
         lo, hi = self._q_mine
-        self._engine = None
+        engine = None
         if hi > lo:
-            self._engine = _core.IsfEngine(self._wavevectors[lo:hi], self._Ns, self.results.pairs,
-                                           self._n_lags, self._incoherent, dev=self._device)
-        self._batch = FrameBatcher(
-            int(self._N), lambda p, b: self._engine.accumulate(p[0]) if self._engine else None,
-            with_box=False, max_bytes=64 << 20)
+            engine = _core.IsfEngine(self._wavevectors[lo:hi], self._Ns, self.results.pairs,
+                                     self._n_lags, self._incoherent, dev=self._device)
         self._positions = np.empty((self._N, 3), dtype=np.float32)
-
-    def _single_frame(self) -> None:
-        for g, gr, s in zip(self._groups, self._groupings, self._slices):
-            self._positions[s] = _group_positions(g, gr)
-        self._batch.add([self._positions])
+        self._feed_engine(engine, rows=int(self._N), max_bytes=64 << 20)
 
     def _conclude(self) -> None:
         self._batch.flush()

@@ -301,14 +301,7 @@ class Onsager(SerialAnalysisBase):
     # ------------------------------------------------------------------ protocol
 
     def _prepare(self) -> None:
-        st = self._sliced_trajectory
-        if hasattr(st, "frames"):
-            df = np.diff(st.frames)
-            if len(df) and (df[0] <= 0 or not np.allclose(df, df[0])):
-                raise ValueError("The selected frames must be evenly spaced and proceed "
-                                 "forward in time.")
-        elif hasattr(st, "step") and st.step is not None and st.step <= 0:
-            raise ValueError("The analysis must proceed forward in time.")
+        self._frame_stride()          # evenly spaced frames, forward in time
 
         self.results.pairs = tuple(
             itertools.combinations_with_replacement(range(self._n_groups), 2))
@@ -328,8 +321,8 @@ class Onsager(SerialAnalysisBase):
         if self._unwrap:
             # every fragment of the first analysed frame is made whole before the starting positions
             # are stored (reference :936-941); universes without bonds have nothing to make whole
-            first = st.frames[0] if hasattr(st, "frames") else (self.start or 0)
-            self.universe.trajectory[first]
+            st = self._sliced_trajectory
+            self.universe.trajectory[st.frames[0] if hasattr(st, "frames") else (self.start or 0)]
             images0 = make_whole_images(self.universe, self._dimensions)
             if images0.any():
                 self._images0 = images0

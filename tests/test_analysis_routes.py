@@ -17,15 +17,18 @@ import numpy as np
 import pytest
 
 import mdhelper_amd
-from mdhelper_amd import _core
-from mdhelper_amd.analysis import (EndToEndVector, IntermediateScatteringFunction, Onsager,
-                                   RadialDistributionFunction, SingleChainStructureFactor, StructureFactor)
+from mdhelper_amd import _core, _lib
+from mdhelper_amd.analysis import (Clusters, DensityProfile, DipoleMoment, DistinctVanHove, EndToEndVector, Gyradius,
+                                   IntermediateScatteringFunction, Onsager, PairResidence,
+                                   RadialDistributionFunction, RouseModes, SingleChainStructureFactor, StructureFactor,
+                                   VanHove)
 
 F, N, L = 10, 120, 50.0
 BIG_N = 1 << 20          # particles of the zero-stride trajectories whose frames split into several blocks
 
 _trace = []
 _tokens = [0]
+_failing = set()         # names of the recorders whose accumulate raises
 
 
 # ----------------------------------------------------------------------------------------------- formatting
@@ -182,6 +185,125 @@ class MsdRecorder(_Recorder):
         return np.zeros((len(pairs),) + self._shape[1:])
 
 
+class _FrameRecorder(_Recorder):
+    """The per-frame engines hold one row per frame seen: the three routes count the frames they are handed.  A
+    recorder named in ``_failing`` raises in ``accumulate``."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._kwargs = kwargs
+        self._seen = 0
+
+    def accumulate(self, *args, **kwargs):
+        _record(f"{self.name}.accumulate", args, kwargs)
+        if self.name in _failing:
+            raise RuntimeError(f"{self.name}.accumulate fails")
+        self._seen += np.shape(args[0])[0]
+
+    def accumulate_device(self, *args, **kwargs):
+        _record(f"{self.name}.accumulate_device", args, kwargs)
+        self._seen += int(args[2])
+
+    def accumulate_traj(self, *args, **kwargs):
+        _record(f"{self.name}.accumulate_traj", args, kwargs)
+        self._seen += len(args[1])
+
+
+class VanHoveRecorder(_FrameRecorder):
+    name = "VanHove"
+
+    def result(self):
+        _record("VanHove.result")
+        sizes, edges, lags = self._args[:3]
+        return (np.zeros((len(lags), len(sizes), len(edges) - 1), dtype=np.int64),
+                np.zeros((len(lags), len(sizes), 2)))
+
+
+class DistinctVanHoveRecorder(_FrameRecorder):
+    name = "DistinctVanHove"
+
+    def result(self):
+        _record("DistinctVanHove.result")
+        return np.zeros((len(self._args[3]), len(self._args[2]) - 1), dtype=np.int64)
+
+
+class ResidenceRecorder(_FrameRecorder):
+    name = "Residence"
+    MAX_NEIGHBORS = 64
+
+    def result(self):
+        _record("Residence.result")
+        return {key: np.zeros(len(self._args[3]), dtype=np.int64)
+                for key in ("intermittent", "continuous", "origin_counts")}
+
+    def contacts(self):
+        _record("Residence.contacts")
+        return np.zeros(self._seen, dtype=np.int64)
+
+
+class ClusterRecorder(_FrameRecorder):
+    name = "Cluster"
+    MAX_NEIGHBORS = 64
+    MAX_SPECIES = 8
+
+    def result(self):
+        _record("Cluster.result")
+        n = len(self._args[0])
+        return {"size_counts": np.zeros(n + 1, dtype=np.int64),
+                "species_counts": np.zeros((self._kwargs["n_species"], n + 1), dtype=np.int64)}
+
+    def frames(self):
+        _record("Cluster.frames")
+        return {key: np.zeros(self._seen, dtype=np.int64)
+                for key in ("bonds", "n_clusters", "largest", "sum_squares")}
+
+    def labels(self):
+        _record("Cluster.labels")
+        return np.zeros((self._seen, len(self._args[0])), dtype=np.int32)
+
+
+class DipoleRecorder(_FrameRecorder):
+    name = "Dipole"
+
+    def result(self):
+        _record("Dipole.result")
+        return np.zeros((len(self._args[0]), self._seen, 3))
+
+
+class ProfileRecorder(_FrameRecorder):
+    name = "Profile"
+
+    def counts(self):
+        _record("Profile.counts")
+        sizes, axes, n_bins = self._args[:3]
+        frames = (self._seen,) if self._kwargs.get("per_frame") else ()
+        return [np.zeros((len(sizes),) + frames + (int(nb),), dtype=np.int64)
+                for nb in np.broadcast_to(n_bins, np.shape(axes))]
+
+
+class GyrationRecorder(_FrameRecorder):
+    name = "Gyration"
+
+    def result(self):
+        _record("Gyration.result")
+        return np.zeros((len(self._args[0]), self._seen, 4))
+
+
+class ProjectionRecorder(_FrameRecorder):
+    name = "Projection"
+
+    def _series(self):
+        return int(len(self._args[2][0]) * np.sum(self._args[0]))
+
+    def result(self):
+        _record("Projection.result")
+        return np.zeros((self._seen, self._series(), 3))
+
+    def device_result(self):
+        _record("Projection.device_result")
+        return "amplitudes", self._seen, self._series()
+
+
 class DeviceArrayRecorder:
     """``_core.DeviceArray``: allocations are named d0, d1, ... in the order they are made."""
 
@@ -264,6 +386,15 @@ def install_recorders(monkeypatch):
     monkeypatch.setattr(_core, "SqEngine", SqRecorder)
     monkeypatch.setattr(_core, "IsfEngine", IsfRecorder)
     monkeypatch.setattr(_core, "MsdEngine", MsdRecorder)
+    monkeypatch.setattr(_core, "VanHoveEngine", VanHoveRecorder)
+    monkeypatch.setattr(_core, "DistinctVanHoveEngine", DistinctVanHoveRecorder)
+    monkeypatch.setattr(_core, "PairResidenceEngine", ResidenceRecorder)
+    monkeypatch.setattr(_core, "ClusterEngine", ClusterRecorder)
+    monkeypatch.setattr(_core, "DipoleEngine", DipoleRecorder)
+    monkeypatch.setattr(_core, "ProfileEngine", ProfileRecorder)
+    monkeypatch.setattr(_core, "GyrationEngine", GyrationRecorder)
+    monkeypatch.setattr(_core, "ChainProjectionEngine", ProjectionRecorder)
+    monkeypatch.setattr(_lib, "require_device", lambda dev=0: None)
     monkeypatch.setattr(_core, "DeviceArray", DeviceArrayRecorder)
     monkeypatch.setattr(_core, "device_info", lambda dev=0: _record("device_info") or {"hbm_available_bytes": 1 << 40})
     monkeypatch.setattr(_core, "synchronize", lambda dev=0: _record("synchronize"))
@@ -272,6 +403,7 @@ def install_recorders(monkeypatch):
                         lambda self, frames, d_out, dev=0, **kw: _record("file.load_device", (frames, d_out)))
     _trace.clear()
     _tokens[0] = 0
+    _failing.clear()
 
 
 @pytest.fixture(autouse=True)
@@ -279,6 +411,7 @@ def recorders(monkeypatch):
     install_recorders(monkeypatch)
     yield
     _trace.clear()
+    _failing.clear()
 
 
 # ---------------------------------------------------------------------------------------------- trajectories
@@ -319,7 +452,9 @@ def _universe(kind, tmp_path):
     return u
 
 
-BIG_FRAMES = {"rdf": 400, "sq": 100, "isf": 100, "scsf": 100, "e2e": 50}
+BIG_FRAMES = {"rdf": 400, "sq": 100, "isf": 100, "scsf": 100, "e2e": 50,
+              # the engine-fed classes: 85 frames of BIG_N particles make a block of 1 GiB
+              "vh": 100, "vhd": 100, "prs": 100, "clu": 100, "dip": 100, "prof": 100, "gyr": 100, "rouse": 100}
 
 
 def _per_frame(analysis):
@@ -367,6 +502,54 @@ def _ons(groups, groupings="atoms", *, hbm_share=None, columns=None, **kw):
     if columns is not None:
         o._stream_columns = columns
     return o
+
+
+def _vh(groups, **kw):
+    return VanHove(groups, n_bins=4, range=(0.0, 5.0), verbose=False, **{"n_lags": 3, **kw})
+
+
+def _vhd(*groups, **kw):
+    return DistinctVanHove(*groups, n_bins=4, range=(0.0, 5.0), verbose=False, **{"n_lags": 3, **kw})
+
+
+def _prs(*groups, **kw):
+    return PairResidence(*groups, cutoff=4.0, verbose=False, **{"n_lags": 3, **kw})
+
+
+UNLIKE = [[0, 3.5], [3.5, 0]]          # a cutoff table of two species: bonds between unlike atoms only
+
+
+def _clu(groups, cutoff=4.0, **kw):
+    return Clusters(groups, cutoff, verbose=False, **kw)
+
+
+def _dip(groups, **kw):
+    n_groups = 1 if hasattr(groups, "universe") else len(groups)
+    return DipoleMoment(groups, charges=[0.5 * (g + 1) for g in range(n_groups)], verbose=False, **kw)
+
+
+def _prof(groups, groupings="atoms", **kw):
+    return DensityProfile(groups, groupings, axes="z", n_bins=4, verbose=False, **kw)
+
+
+def _gyr(groups, groupings="atoms", **kw):
+    return Gyradius(groups, groupings, verbose=False, **kw)
+
+
+def _rouse(groups, groupings="atoms", **kw):
+    return RouseModes(groups, groupings, verbose=False, **{"modes": 2, **kw})
+
+
+def _volumes(analysis):
+    """Record ``results.volumes`` of a finished DipoleMoment (the batched route reads them from ``box_block``)."""
+    _record("results.volumes", (analysis.results.volumes,))
+
+
+def _fails(name, analysis):
+    """Run ``analysis`` with the recorder ``name`` raising in ``accumulate``."""
+    _failing.add(name)
+    with pytest.raises(RuntimeError, match=f"{name}.accumulate fails"):
+        analysis.run()
 
 
 CASES = {
@@ -463,6 +646,118 @@ CASES = {
         center_wrap=True).run()),
     "ons-file-hbm": ("file", lambda u: _ons((u.atoms[:60], u.atoms[60:]), unwrap=True).run(step=2)),
     "ons-per-frame": ("memory", lambda u: _per_frame(_ons((u.atoms[:60], u.atoms[60:]))).run()),
+    # self van Hove function
+    "vh-memory": ("memory", lambda u: _vh(u.atoms).run()),
+    "vh-memory-gather": ("memory", lambda u: _vh((u.atoms[60:], u.atoms[:60])).run(step=2)),
+    "vh-hbm32": ("hbm32", lambda u: _vh(u.atoms).run()),
+    "vh-hbm32-subset": ("hbm32", lambda u: _vh(u.atoms[30:90]).run(start=1, stop=9)),
+    "vh-hbm32-frames": ("hbm32", lambda u: _vh(u.atoms[30:90]).run(frames=[0, 2, 4, 6])),
+    "vh-hbm64": ("hbm64", lambda u: _vh(u.atoms).run()),
+    "vh-file-subset": ("file", lambda u: _vh(u.atoms[30:90]).run(start=2)),
+    "vh-file": ("file", lambda u: _vh(u.atoms).run(stop=6)),
+    "vh-per-frame": ("memory", lambda u: _per_frame(_vh(u.atoms[30:90])).run()),
+    "vh-blocks": ("big-vh", lambda u: _vh(u.atoms, n_lags=2).run()),
+    "vh-memory-unwrap-drop": ("memory", lambda u: _vh(u.atoms, unwrap=True, drop_axis="y").run()),
+    "vh-memory-lags-beyond": ("memory", lambda u: _vh(u.atoms[30:90], n_lags=None, lags=[20, 25]).run()),
+    # distinct van Hove function
+    "vhd-memory": ("memory", lambda u: _vhd(u.atoms).run()),
+    "vhd-memory-gather": ("memory", lambda u: _vhd(u.atoms[60:], u.atoms[:60]).run(step=2)),
+    "vhd-hbm32": ("hbm32", lambda u: _vhd(u.atoms).run()),
+    "vhd-hbm32-subset": ("hbm32", lambda u: _vhd(u.atoms[30:60], u.atoms[90:]).run(start=1, stop=9)),
+    "vhd-hbm32-frames": ("hbm32", lambda u: _vhd(u.atoms[30:60], u.atoms[90:]).run(frames=[0, 2, 4, 6])),
+    "vhd-hbm64": ("hbm64", lambda u: _vhd(u.atoms).run()),
+    "vhd-file-subset": ("file", lambda u: _vhd(u.atoms[30:60], u.atoms[90:]).run(start=2)),
+    "vhd-file": ("file", lambda u: _vhd(u.atoms).run(stop=6)),
+    "vhd-per-frame": ("memory", lambda u: _per_frame(_vhd(u.atoms[30:60], u.atoms[90:])).run()),
+    "vhd-blocks": ("big-vhd", lambda u: _vhd(u.atoms, n_lags=2).run()),
+    "vhd-memory-lags-beyond": ("memory", lambda u: _vhd(u.atoms[30:90], n_lags=None, lags=[10]).run()),
+    # pair residence
+    "prs-memory": ("memory", lambda u: _prs(u.atoms).run()),
+    "prs-memory-gather": ("memory", lambda u: _prs(u.atoms[60:], u.atoms[:60]).run(step=2)),
+    "prs-hbm32": ("hbm32", lambda u: _prs(u.atoms).run()),
+    "prs-hbm32-subset": ("hbm32", lambda u: _prs(u.atoms[30:60], u.atoms[90:]).run(start=1, stop=9)),
+    "prs-hbm32-frames": ("hbm32", lambda u: _prs(u.atoms[30:60], u.atoms[90:]).run(frames=[0, 2, 4, 6])),
+    "prs-hbm64": ("hbm64", lambda u: _prs(u.atoms).run()),
+    "prs-file-subset": ("file", lambda u: _prs(u.atoms[30:60], u.atoms[90:]).run(start=2)),
+    "prs-file": ("file", lambda u: _prs(u.atoms).run(stop=6)),
+    "prs-per-frame": ("memory", lambda u: _per_frame(_prs(u.atoms[30:60], u.atoms[90:])).run()),
+    "prs-blocks": ("big-prs", lambda u: _prs(u.atoms, n_lags=2).run()),
+    "prs-memory-lags-beyond": ("memory", lambda u: _prs(u.atoms[30:90], n_lags=None, lags=[12]).run()),
+    # clusters
+    "clu-memory": ("memory", lambda u: _clu(u.atoms).run()),
+    "clu-memory-gather": ("memory", lambda u: _clu((u.atoms[60:], u.atoms[:60]), store_labels=True).run(step=2)),
+    "clu-hbm32": ("hbm32", lambda u: _clu(u.atoms).run()),
+    "clu-hbm32-subset": ("hbm32", lambda u: _clu((u.atoms[30:60], u.atoms[90:]), UNLIKE).run(start=1, stop=9)),
+    "clu-hbm32-frames": ("hbm32", lambda u: _clu(
+        (u.atoms[30:60], u.atoms[90:]), UNLIKE).run(frames=[0, 2, 3, 7])),
+    "clu-hbm64": ("hbm64", lambda u: _clu(u.atoms).run()),
+    "clu-file-subset": ("file", lambda u: _clu((u.atoms[30:60], u.atoms[90:]), UNLIKE).run(start=2)),
+    "clu-file": ("file", lambda u: _clu(u.atoms).run(stop=6)),
+    "clu-per-frame": ("memory", lambda u: _per_frame(_clu((u.atoms[30:60], u.atoms[90:]), UNLIKE)).run()),
+    "clu-blocks": ("big-clu", lambda u: _clu(u.atoms).run()),
+    "clu-memory-rank1": ("memory", lambda u: _clu(u.atoms, store_labels=True, comm=_Comm(1, 2)).run()),
+    "clu-per-frame-rank1": ("memory", lambda u: _per_frame(_clu(u.atoms[30:90], comm=_Comm(1, 2))).run()),
+    "clu-memory-accumulate-raises": ("memory", lambda u: _fails("Cluster", _clu(u.atoms[30:90]))),
+    # dipole moments
+    "dip-memory": ("memory", lambda u: _volumes(_dip(u.atoms).run())),
+    "dip-memory-gather": ("memory", lambda u: _dip((u.atoms[60:], u.atoms[:60])).run(step=2)),
+    "dip-hbm32": ("hbm32", lambda u: _volumes(_dip(u.atoms).run())),
+    "dip-hbm32-subset": ("hbm32", lambda u: _volumes(_dip((u.atoms[30:60], u.atoms[90:])).run(start=1, stop=9))),
+    "dip-hbm32-frames": ("hbm32", lambda u: _volumes(
+        _dip((u.atoms[30:60], u.atoms[90:])).run(frames=[0, 2, 3, 7]))),
+    "dip-hbm64": ("hbm64", lambda u: _volumes(_dip(u.atoms).run())),
+    "dip-file-subset": ("file", lambda u: _volumes(_dip((u.atoms[30:60], u.atoms[90:])).run(start=2))),
+    "dip-file": ("file", lambda u: _volumes(_dip(u.atoms).run(stop=6))),
+    "dip-per-frame": ("memory", lambda u: _volumes(_per_frame(_dip((u.atoms[30:60], u.atoms[90:]))).run())),
+    "dip-blocks": ("big-dip", lambda u: _dip(u.atoms).run()),
+    "dip-memory-unwrap": ("bonds", lambda u: _dip(u.atoms, unwrap=True).run(start=3)),
+    "dip-memory-rank1": ("memory", lambda u: _volumes(_dip(u.atoms, comm=_Comm(1, 2)).run())),
+    "dip-per-frame-rank1": ("memory", lambda u: _volumes(_per_frame(_dip(u.atoms[30:90], comm=_Comm(1, 2))).run())),
+    # density profiles
+    "prof-memory": ("memory", lambda u: _prof(u.atoms).run()),
+    "prof-memory-gather": ("memory", lambda u: _prof((u.atoms[60:], u.atoms[:60]), average=False).run(step=2)),
+    "prof-hbm32": ("hbm32", lambda u: _prof(u.atoms).run()),
+    "prof-hbm32-subset": ("hbm32", lambda u: _prof((u.atoms[30:60], u.atoms[90:])).run(start=1, stop=9)),
+    "prof-hbm32-frames": ("hbm32", lambda u: _prof((u.atoms[30:60], u.atoms[90:])).run(frames=[0, 2, 3, 7])),
+    "prof-hbm64": ("hbm64", lambda u: _prof(u.atoms).run()),
+    "prof-file-subset": ("file", lambda u: _prof((u.atoms[30:60], u.atoms[90:])).run(start=2)),
+    "prof-file": ("file", lambda u: _prof(u.atoms).run(stop=6)),
+    "prof-per-frame": ("memory", lambda u: _per_frame(_prof((u.atoms[30:60], u.atoms[90:]))).run()),
+    "prof-blocks": ("big-prof", lambda u: _prof(u.atoms).run()),
+    "prof-memory-residues": ("memory", lambda u: _prof((u.atoms[60:], u.atoms[:60]), ("residues", "atoms")).run()),
+    "prof-file-residues-recenter": ("file", lambda u: _prof(u.atoms, "residues", recenter=0).run()),
+    "prof-memory-rank1": ("memory", lambda u: _prof(u.atoms, average=False, comm=_Comm(1, 2)).run()),
+    "prof-per-frame-rank1": ("memory", lambda u: _per_frame(_prof(u.atoms[30:90], comm=_Comm(1, 2))).run()),
+    # radii of gyration
+    "gyr-memory": ("memory", lambda u: _gyr(u.atoms).run()),
+    "gyr-memory-gather": ("memory", lambda u: _gyr((u.atoms[60:], u.atoms[:60]), components=True).run(step=2)),
+    "gyr-hbm32": ("hbm32", lambda u: _gyr(u.atoms).run()),
+    "gyr-hbm32-subset": ("hbm32", lambda u: _gyr((u.atoms[24:60], u.atoms[96:])).run(start=1, stop=9)),
+    "gyr-hbm32-frames": ("hbm32", lambda u: _gyr((u.atoms[24:60], u.atoms[96:])).run(frames=[0, 2, 3, 7])),
+    "gyr-hbm64": ("hbm64", lambda u: _gyr(u.atoms).run()),
+    "gyr-file-subset": ("file", lambda u: _gyr((u.atoms[24:60], u.atoms[96:])).run(start=2)),
+    "gyr-file": ("file", lambda u: _gyr(u.atoms).run(stop=6)),
+    "gyr-per-frame": ("memory", lambda u: _per_frame(_gyr((u.atoms[24:60], u.atoms[96:]))).run()),
+    "gyr-blocks": ("big-gyr", lambda u: _gyr(u.atoms, n_chains=2, n_monomers=BIG_N // 2).run()),
+    "gyr-memory-residues-unwrap": ("bonds", lambda u: _gyr(u.atoms, "residues", unwrap=True).run(start=2)),
+    "gyr-file-explicit-residues": ("file", lambda u: _gyr(u.atoms[:60], "residues", n_chains=5, n_monomers=4).run()),
+    "gyr-memory-rank1": ("memory", lambda u: _gyr(u.atoms, comm=_Comm(1, 2)).run()),
+    "gyr-per-frame-rank1": ("memory", lambda u: _per_frame(_gyr(u.atoms[24:60], comm=_Comm(1, 2))).run()),
+    # Rouse modes
+    "rouse-memory": ("memory", lambda u: _rouse(u.atoms).run()),
+    "rouse-memory-gather": ("memory", lambda u: _rouse((u.atoms[60:], u.atoms[:60]), n_blocks=2).run(step=2)),
+    "rouse-hbm32": ("hbm32", lambda u: _rouse(u.atoms).run()),
+    "rouse-hbm32-subset": ("hbm32", lambda u: _rouse((u.atoms[24:60], u.atoms[96:])).run(start=1, stop=9)),
+    "rouse-hbm32-frames": ("hbm32", lambda u: _rouse((u.atoms[24:60], u.atoms[96:])).run(frames=[0, 2, 3, 7])),
+    "rouse-hbm64": ("hbm64", lambda u: _rouse(u.atoms).run()),
+    "rouse-file-subset": ("file", lambda u: _rouse((u.atoms[24:60], u.atoms[96:])).run(start=2)),
+    "rouse-file": ("file", lambda u: _rouse(u.atoms).run(stop=6)),
+    "rouse-per-frame": ("memory", lambda u: _per_frame(_rouse((u.atoms[24:60], u.atoms[96:]))).run()),
+    "rouse-blocks": ("big-rouse", lambda u: _rouse(u.atoms, modes=1, n_chains=2, n_monomers=BIG_N // 2).run()),
+    "rouse-memory-residues-unwrap": ("bonds", lambda u: _rouse(u.atoms, "residues", unwrap=True).run(start=2)),
+    "rouse-memory-no-fft": ("memory", lambda u: _rouse(u.atoms[:60], fft=False).run()),
+    "rouse-memory-rank1": ("memory", lambda u: _rouse(u.atoms, comm=_Comm(1, 2)).run()),
+    "rouse-per-frame-rank1": ("memory", lambda u: _per_frame(_rouse(u.atoms[24:60], comm=_Comm(1, 2))).run()),
 }
 
 
@@ -478,6 +773,25 @@ def trace_of(case, tmp_path):
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_engine_calls(case, tmp_path):
     assert trace_of(case, tmp_path) == EXPECTED[case]
+
+
+# a block that raises: the shared run() closes the engine (its stream and HBM) before the error leaves
+FAILING = {
+    "VanHove": (lambda u: _vh(u.atoms[30:90]), "30..89"),
+    "DistinctVanHove": (lambda u: _vhd(u.atoms[30:60], u.atoms[90:]), "30..59,90..119"),
+    "Residence": (lambda u: _prs(u.atoms[30:60], u.atoms[90:]), "30..59,90..119"),
+    "Dipole": (lambda u: _dip(u.atoms[30:90]), "30..89"),
+    "Profile": (lambda u: _prof(u.atoms[30:90]), "30..89"),
+    "Gyration": (lambda u: _gyr(u.atoms[24:60]), "24..59"),
+    "Projection": (lambda u: _rouse(u.atoms[24:60]), "24..59"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FAILING))
+def test_engine_closed_when_a_block_raises(name, tmp_path):
+    make, atoms = FAILING[name]
+    _fails(name, make(_universe("memory", tmp_path)))
+    assert _trace[-2:] == [f"{name}.accumulate(pos32[0..9 | {atoms}])", f"{name}.close()"]
 
 
 # the engine calls of every case
@@ -1001,3 +1315,632 @@ EXPECTED = {'e2e-blocks': ['frame_block(0..20)',
                   'Sq.accumulate(pos32[0..9 | 0..119])',
                   'Sq.result()',
                   'Sq.close()']}
+
+
+# ... and those of the engine-fed classes (VanHove, DistinctVanHove, PairResidence, Clusters, DipoleMoment,
+# DensityProfile, Gyradius, RouseModes), recorded while each class still had a run() of its own
+EXPECTED.update(
+{'clu-blocks': ['Cluster(0x1048576, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, n_species=1, '
+                'zero_dims=0)',
+                'Cluster.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                'Cluster.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                'Cluster.result()',
+                'Cluster.frames()',
+                'Cluster.close()'],
+ 'clu-file': ['Cluster(0x120, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, n_species=1, zero_dims=0)',
+              'Cluster.accumulate_traj(file, 0..5, None)',
+              'Cluster.result()',
+              'Cluster.frames()',
+              'Cluster.close()'],
+ 'clu-file-subset': ['Cluster(<60 ints #0f7eb7b687>, [0 3.5 3.5 0], [50 50 50], dev=0, keep_labels=False, '
+                     'max_neighbors=32, n_species=2, zero_dims=0)',
+                     'Cluster.accumulate_traj(file, 2..9, 30..59,90..119)',
+                     'Cluster.result()',
+                     'Cluster.frames()',
+                     'Cluster.close()'],
+ 'clu-hbm32': ['Cluster(0x120, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, n_species=1, zero_dims=0)',
+               'rows(0, 10)',
+               "Cluster.accumulate_device('rows0+10', 120, 10, None)",
+               'Cluster.result()',
+               'Cluster.frames()',
+               'Cluster.close()'],
+ 'clu-hbm32-frames': ['Cluster(<60 ints #0f7eb7b687>, [0 3.5 3.5 0], [50 50 50], dev=0, keep_labels=False, '
+                      'max_neighbors=32, n_species=2, zero_dims=0)',
+                      'to_host(0, 1)',
+                      'to_host(2, 1)',
+                      'to_host(3, 1)',
+                      'to_host(7, 1)',
+                      'Cluster.accumulate(pos32[0,2..3,7 | 30..59,90..119])',
+                      'Cluster.result()',
+                      'Cluster.frames()',
+                      'Cluster.close()'],
+ 'clu-hbm32-subset': ['Cluster(<60 ints #0f7eb7b687>, [0 3.5 3.5 0], [50 50 50], dev=0, keep_labels=False, '
+                      'max_neighbors=32, n_species=2, zero_dims=0)',
+                      'rows(1, 8)',
+                      "Cluster.accumulate_device('rows1+8', 120, 8, 30..59,90..119)",
+                      'Cluster.result()',
+                      'Cluster.frames()',
+                      'Cluster.close()'],
+ 'clu-hbm64': ['Cluster(0x120, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, n_species=1, zero_dims=0)',
+               'to_host(0, 10)',
+               'Cluster.accumulate(pos64[0..9 | 0..119])',
+               'Cluster.result()',
+               'Cluster.frames()',
+               'Cluster.close()'],
+ 'clu-memory': ['Cluster(0x120, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, n_species=1, zero_dims=0)',
+                'Cluster.accumulate(pos32[0..9 | 0..119])',
+                'Cluster.result()',
+                'Cluster.frames()',
+                'Cluster.close()'],
+ 'clu-memory-accumulate-raises': ['Cluster(0x60, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, '
+                                  'n_species=1, zero_dims=0)',
+                                  'Cluster.accumulate(pos32[0..9 | 30..89])',
+                                  'Cluster.close()'],
+ 'clu-memory-gather': ['Cluster(<120 ints #ffb434c782>, [4 4 4 4], [50 50 50], dev=0, keep_labels=True, '
+                       'max_neighbors=32, n_species=2, zero_dims=0)',
+                       'Cluster.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                       'Cluster.result()',
+                       'Cluster.frames()',
+                       'Cluster.labels()',
+                       'Cluster.close()'],
+ 'clu-memory-rank1': ['Cluster(0x120, [4], [50 50 50], dev=0, keep_labels=True, max_neighbors=32, n_species=1, '
+                      'zero_dims=0)',
+                      'Cluster.accumulate(pos32[5..9 | 0..119])',
+                      'Cluster.result()',
+                      'Cluster.frames()',
+                      'Cluster.labels()',
+                      'Cluster.close()'],
+ 'clu-per-frame': ['Cluster(<60 ints #0f7eb7b687>, [0 3.5 3.5 0], [50 50 50], dev=0, keep_labels=False, '
+                   'max_neighbors=32, n_species=2, zero_dims=0)',
+                   'Cluster.accumulate(pos32[0..9 | 30..59,90..119])',
+                   'Cluster.result()',
+                   'Cluster.frames()',
+                   'Cluster.close()'],
+ 'clu-per-frame-rank1': ['Cluster(0x60, [4], [50 50 50], dev=0, keep_labels=False, max_neighbors=32, n_species=1, '
+                         'zero_dims=0)',
+                         'Cluster.accumulate(pos32[5..9 | 30..89])',
+                         'Cluster.result()',
+                         'Cluster.frames()',
+                         'Cluster.close()'],
+ 'dip-blocks': ['Dipole(1048576, <(1048576,) #14c194b18a>, dev=0)',
+                'Dipole.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                'Dipole.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                'Dipole.result()',
+                'Dipole.close()'],
+ 'dip-file': ['Dipole(120, <(120,) #fd59dbb533>, dev=0)',
+              'Dipole.accumulate_traj(file, 0..5, None)',
+              'Dipole.result()',
+              'Dipole.close()',
+              'results.volumes([125000 125312 125625 125938 126250 126562])'],
+ 'dip-file-subset': ['Dipole(30x2, <(60,) #12b5303bb1>, dev=0)',
+                     'Dipole.accumulate_traj(file, 2..9, 30..59,90..119)',
+                     'Dipole.result()',
+                     'Dipole.close()',
+                     'results.volumes([125625 125938 126250 126562 126875 127188 127500 127812])'],
+ 'dip-hbm32': ['Dipole(120, <(120,) #fd59dbb533>, dev=0)',
+               'rows(0, 10)',
+               "Dipole.accumulate_device('rows0+10', 120, 10, None)",
+               'Dipole.result()',
+               'Dipole.close()',
+               'results.volumes(<(10,) #e82c6627dc>)'],
+ 'dip-hbm32-frames': ['Dipole(30x2, <(60,) #12b5303bb1>, dev=0)',
+                      'to_host(0, 1)',
+                      'to_host(2, 1)',
+                      'to_host(3, 1)',
+                      'to_host(7, 1)',
+                      'Dipole.accumulate(pos32[0,2..3,7 | 30..59,90..119])',
+                      'Dipole.result()',
+                      'Dipole.close()',
+                      'results.volumes([125000 125625 125938 127188])'],
+ 'dip-hbm32-subset': ['Dipole(30x2, <(60,) #12b5303bb1>, dev=0)',
+                      'rows(1, 8)',
+                      "Dipole.accumulate_device('rows1+8', 120, 8, 30..59,90..119)",
+                      'Dipole.result()',
+                      'Dipole.close()',
+                      'results.volumes([125312 125625 125938 126250 126562 126875 127188 127500])'],
+ 'dip-hbm64': ['Dipole(120, <(120,) #fd59dbb533>, dev=0)',
+               'to_host(0, 10)',
+               'Dipole.accumulate(pos64[0..9 | 0..119])',
+               'Dipole.result()',
+               'Dipole.close()',
+               'results.volumes(<(10,) #e82c6627dc>)'],
+ 'dip-memory': ['Dipole(120, <(120,) #fd59dbb533>, dev=0)',
+                'Dipole.accumulate(pos32[0..9 | 0..119])',
+                'Dipole.result()',
+                'Dipole.close()',
+                'results.volumes(<(10,) #e82c6627dc>)'],
+ 'dip-memory-gather': ['Dipole(60x2, <(120,) #5e7d5d6bf0>, dev=0)',
+                       'Dipole.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                       'Dipole.result()',
+                       'Dipole.close()'],
+ 'dip-memory-rank1': ['Dipole(120, <(120,) #fd59dbb533>, dev=0)',
+                      'Dipole.accumulate(pos32[5..9 | 0..119])',
+                      'Dipole.result()',
+                      'Dipole.close()',
+                      'results.volumes(<(10,) #e82c6627dc>)'],
+ 'dip-memory-unwrap': ['Dipole(120, <(120,) #fd59dbb533>, dev=0)',
+                       'Dipole.set_unwrap([50 50 50], <(120, 3) #66606d5eaa>)',
+                       'Dipole.accumulate(pos32[3..9 | 0..119])',
+                       'Dipole.result()',
+                       'Dipole.close()'],
+ 'dip-per-frame': ['Dipole(30x2, <(60,) #12b5303bb1>, dev=0)',
+                   'Dipole.accumulate(pos32[0..9 | 30..59,90..119])',
+                   'Dipole.result()',
+                   'Dipole.close()',
+                   'results.volumes(<(10,) #e82c6627dc>)'],
+ 'dip-per-frame-rank1': ['Dipole(60, <(60,) #e0bdd5f931>, dev=0)',
+                         'Dipole.accumulate(pos32[5..9 | 30..89])',
+                         'Dipole.result()',
+                         'Dipole.close()',
+                         'results.volumes(<(10,) #e82c6627dc>)'],
+ 'gyr-blocks': ['Gyration(2, 524288, <(1048576,) #01dfa447da>, dev=0)',
+                'Gyration.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                'Gyration.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                'Gyration.result()',
+                'Gyration.close()'],
+ 'gyr-file': ['Gyration(10, 12, <(120,) #2a35702bbc>, dev=0)',
+              'Gyration.accumulate_traj(file, 0..5, None)',
+              'Gyration.result()',
+              'Gyration.close()'],
+ 'gyr-file-explicit-residues': ['Gyration(5, 4, <(20,) #08c8d5ab2e>, dev=0)',
+                                'Gyration.set_grouping(0..60/3, <(60,) #b2c88767f2>)',
+                                'Gyration.accumulate_traj(file, 0..9, 0..59)',
+                                'Gyration.result()',
+                                'Gyration.close()'],
+ 'gyr-file-subset': ['Gyration(3,2, 12x2, <(60,) #9848ddd21b>, dev=0)',
+                     'Gyration.accumulate_traj(file, 2..9, 24..59,96..119)',
+                     'Gyration.result()',
+                     'Gyration.close()'],
+ 'gyr-hbm32': ['Gyration(10, 12, <(120,) #2a35702bbc>, dev=0)',
+               'rows(0, 10)',
+               "Gyration.accumulate_device('rows0+10', 120, 10, None)",
+               'Gyration.result()',
+               'Gyration.close()'],
+ 'gyr-hbm32-frames': ['Gyration(3,2, 12x2, <(60,) #9848ddd21b>, dev=0)',
+                      'to_host(0, 1)',
+                      'to_host(2, 1)',
+                      'to_host(3, 1)',
+                      'to_host(7, 1)',
+                      'Gyration.accumulate(pos32[0,2..3,7 | 24..59,96..119])',
+                      'Gyration.result()',
+                      'Gyration.close()'],
+ 'gyr-hbm32-subset': ['Gyration(3,2, 12x2, <(60,) #9848ddd21b>, dev=0)',
+                      'rows(1, 8)',
+                      "Gyration.accumulate_device('rows1+8', 120, 8, 24..59,96..119)",
+                      'Gyration.result()',
+                      'Gyration.close()'],
+ 'gyr-hbm64': ['Gyration(10, 12, <(120,) #2a35702bbc>, dev=0)',
+               'to_host(0, 10)',
+               'Gyration.accumulate(pos64[0..9 | 0..119])',
+               'Gyration.result()',
+               'Gyration.close()'],
+ 'gyr-memory': ['Gyration(10, 12, <(120,) #2a35702bbc>, dev=0)',
+                'Gyration.accumulate(pos32[0..9 | 0..119])',
+                'Gyration.result()',
+                'Gyration.close()'],
+ 'gyr-memory-gather': ['Gyration(5x2, 12x2, <(120,) #f985569a2d>, dev=0)',
+                       'Gyration.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                       'Gyration.result()',
+                       'Gyration.close()'],
+ 'gyr-memory-rank1': ['Gyration(10, 12, <(120,) #2a35702bbc>, dev=0)',
+                      'Gyration.accumulate(pos32[5..9 | 0..119])',
+                      'Gyration.result()',
+                      'Gyration.close()'],
+ 'gyr-memory-residues-unwrap': ['Gyration(10, 4, <(40,) #94036cb298>, dev=0)',
+                                'Gyration.set_grouping(0..120/3, <(120,) #2a35702bbc>)',
+                                'Gyration.set_unwrap([50 50 50], <(40, 3) #fb5db8ad72>)',
+                                'Gyration.accumulate(pos32[2..9 | 0..119])',
+                                'Gyration.result()',
+                                'Gyration.close()'],
+ 'gyr-per-frame': ['Gyration(3,2, 12x2, <(60,) #9848ddd21b>, dev=0)',
+                   'Gyration.accumulate(pos32[0..9 | 24..59,96..119])',
+                   'Gyration.result()',
+                   'Gyration.close()'],
+ 'gyr-per-frame-rank1': ['Gyration(3, 12, <(36,) #17ac4c3d94>, dev=0)',
+                         'Gyration.accumulate(pos32[5..9 | 24..59])',
+                         'Gyration.result()',
+                         'Gyration.close()'],
+ 'prof-blocks': ['Profile(1048576, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                 'Profile.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                 'Profile.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                 'Profile.counts()',
+                 'Profile.close()'],
+ 'prof-file': ['Profile(120, 2, 4, [50 50 50], dev=0, per_frame=False)',
+               'Profile.accumulate_traj(file, 0..5, None)',
+               'Profile.counts()',
+               'Profile.close()'],
+ 'prof-file-residues-recenter': ['Profile(40, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                                 'Profile.set_grouping(0..120/3, <(120,) #2a35702bbc>)',
+                                 'Profile.set_recenter(0, <(40,) #94036cb298>, [25 25 25])',
+                                 'Profile.accumulate_traj(file, 0..9, None)',
+                                 'Profile.counts()',
+                                 'Profile.close()'],
+ 'prof-file-subset': ['Profile(30x2, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                      'Profile.accumulate_traj(file, 2..9, 30..59,90..119)',
+                      'Profile.counts()',
+                      'Profile.close()'],
+ 'prof-hbm32': ['Profile(120, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                'rows(0, 10)',
+                "Profile.accumulate_device('rows0+10', 120, 10, None)",
+                'Profile.counts()',
+                'Profile.close()'],
+ 'prof-hbm32-frames': ['Profile(30x2, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                       'to_host(0, 1)',
+                       'to_host(2, 1)',
+                       'to_host(3, 1)',
+                       'to_host(7, 1)',
+                       'Profile.accumulate(pos32[0,2..3,7 | 30..59,90..119])',
+                       'Profile.counts()',
+                       'Profile.close()'],
+ 'prof-hbm32-subset': ['Profile(30x2, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                       'rows(1, 8)',
+                       "Profile.accumulate_device('rows1+8', 120, 8, 30..59,90..119)",
+                       'Profile.counts()',
+                       'Profile.close()'],
+ 'prof-hbm64': ['Profile(120, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                'to_host(0, 10)',
+                'Profile.accumulate(pos64[0..9 | 0..119])',
+                'Profile.counts()',
+                'Profile.close()'],
+ 'prof-memory': ['Profile(120, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                 'Profile.accumulate(pos32[0..9 | 0..119])',
+                 'Profile.counts()',
+                 'Profile.close()'],
+ 'prof-memory-gather': ['Profile(60x2, 2, 4, [50 50 50], dev=0, per_frame=True)',
+                        'Profile.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                        'Profile.counts()',
+                        'Profile.close()'],
+ 'prof-memory-rank1': ['Profile(120, 2, 4, [50 50 50], dev=0, per_frame=True)',
+                       'Profile.accumulate(pos32[5..9 | 0..119])',
+                       'Profile.counts()',
+                       'Profile.close()'],
+ 'prof-memory-residues': ['Profile(20,60, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                          'Profile.set_grouping(<81 ints #95475c9bc2>, <(120,) #7f4d5a97af>)',
+                          'Profile.accumulate(pos32[0..9 | 60..119,0..59])',
+                          'Profile.counts()',
+                          'Profile.close()'],
+ 'prof-per-frame': ['Profile(30x2, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                    'Profile.accumulate(pos32[0..9 | 30..59,90..119])',
+                    'Profile.counts()',
+                    'Profile.close()'],
+ 'prof-per-frame-rank1': ['Profile(60, 2, 4, [50 50 50], dev=0, per_frame=False)',
+                          'Profile.accumulate(pos32[5..9 | 30..89])',
+                          'Profile.counts()',
+                          'Profile.close()'],
+ 'prs-blocks': ['Residence(1048576, 1048576, 4, 0..1, [50 50 50], continuous=True, dev=0, max_neighbors=32, '
+                'origin_step=1, same=True, zero_dims=0)',
+                'Residence.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                'Residence.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                'Residence.result()',
+                'Residence.contacts()',
+                'Residence.close()'],
+ 'prs-file': ['Residence(120, 120, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+              'same=True, zero_dims=0)',
+              'Residence.accumulate_traj(file, 0..5, None)',
+              'Residence.result()',
+              'Residence.contacts()',
+              'Residence.close()'],
+ 'prs-file-subset': ['Residence(30, 30, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+                     'same=False, zero_dims=0)',
+                     'Residence.accumulate_traj(file, 2..9, 30..59,90..119)',
+                     'Residence.result()',
+                     'Residence.contacts()',
+                     'Residence.close()'],
+ 'prs-hbm32': ['Residence(120, 120, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+               'same=True, zero_dims=0)',
+               'rows(0, 10)',
+               "Residence.accumulate_device('rows0+10', 120, 10, None)",
+               'Residence.result()',
+               'Residence.contacts()',
+               'Residence.close()'],
+ 'prs-hbm32-frames': ['Residence(30, 30, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+                      'same=False, zero_dims=0)',
+                      'to_host(0, 1)',
+                      'to_host(2, 1)',
+                      'to_host(4, 1)',
+                      'to_host(6, 1)',
+                      'Residence.accumulate(pos32[0,2,4,6 | 30..59,90..119])',
+                      'Residence.result()',
+                      'Residence.contacts()',
+                      'Residence.close()'],
+ 'prs-hbm32-subset': ['Residence(30, 30, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+                      'same=False, zero_dims=0)',
+                      'rows(1, 8)',
+                      "Residence.accumulate_device('rows1+8', 120, 8, 30..59,90..119)",
+                      'Residence.result()',
+                      'Residence.contacts()',
+                      'Residence.close()'],
+ 'prs-hbm64': ['Residence(120, 120, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+               'same=True, zero_dims=0)',
+               'to_host(0, 10)',
+               'Residence.accumulate(pos64[0..9 | 0..119])',
+               'Residence.result()',
+               'Residence.contacts()',
+               'Residence.close()'],
+ 'prs-memory': ['Residence(120, 120, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+                'same=True, zero_dims=0)',
+                'Residence.accumulate(pos32[0..9 | 0..119])',
+                'Residence.result()',
+                'Residence.contacts()',
+                'Residence.close()'],
+ 'prs-memory-gather': ['Residence(60, 60, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, '
+                       'origin_step=1, same=False, zero_dims=0)',
+                       'Residence.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                       'Residence.result()',
+                       'Residence.contacts()',
+                       'Residence.close()'],
+ 'prs-memory-lags-beyond': [],
+ 'prs-per-frame': ['Residence(30, 30, 4, 0..2, [50 50 50], continuous=True, dev=0, max_neighbors=32, origin_step=1, '
+                   'same=False, zero_dims=0)',
+                   'Residence.accumulate(pos32[0..9 | 30..59,90..119])',
+                   'Residence.result()',
+                   'Residence.contacts()',
+                   'Residence.close()'],
+ 'rouse-blocks': ['Projection(2, 524288, (<(1, 524288) #e75350f232>), dev=0)',
+                  'Projection.reserve(100)',
+                  'Projection.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                  'Projection.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                  'Projection.device_result()',
+                  'Msd(100, 1, 1, dev=0)',
+                  "Msd.push_device(0, 'amplitudes', 2, 0, 2, 0)",
+                  'Msd.result_acf()',
+                  'Msd.close()',
+                  'Projection.close()'],
+ 'rouse-file': ['Projection(10, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                'Projection.reserve(6)',
+                'Projection.accumulate_traj(file, 0..5, None)',
+                'Projection.device_result()',
+                'Msd(6, 1, 2, dev=0)',
+                "Msd.push_device(0, 'amplitudes', 20, 0, 10, 0)",
+                "Msd.push_device(1, 'amplitudes', 20, 10, 10, 0)",
+                'Msd.result_acf()',
+                'Msd.close()',
+                'Projection.close()'],
+ 'rouse-file-subset': ['Projection(3,2, 12x2, (<(2, 12) #2ea9fc7d31>, <(2, 12) #2ea9fc7d31>), dev=0)',
+                       'Projection.reserve(8)',
+                       'Projection.accumulate_traj(file, 2..9, 24..59,96..119)',
+                       'Projection.device_result()',
+                       'Msd(8, 1, 4, dev=0)',
+                       "Msd.push_device(0, 'amplitudes', 10, 0, 3, 0)",
+                       "Msd.push_device(1, 'amplitudes', 10, 3, 3, 0)",
+                       "Msd.push_device(2, 'amplitudes', 10, 6, 2, 0)",
+                       "Msd.push_device(3, 'amplitudes', 10, 8, 2, 0)",
+                       'Msd.result_acf()',
+                       'Msd.close()',
+                       'Projection.close()'],
+ 'rouse-hbm32': ['Projection(10, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                 'Projection.reserve(10)',
+                 'rows(0, 10)',
+                 "Projection.accumulate_device('rows0+10', 120, 10, None)",
+                 'Projection.device_result()',
+                 'Msd(10, 1, 2, dev=0)',
+                 "Msd.push_device(0, 'amplitudes', 20, 0, 10, 0)",
+                 "Msd.push_device(1, 'amplitudes', 20, 10, 10, 0)",
+                 'Msd.result_acf()',
+                 'Msd.close()',
+                 'Projection.close()'],
+ 'rouse-hbm32-frames': ['Projection(3,2, 12x2, (<(2, 12) #2ea9fc7d31>, <(2, 12) #2ea9fc7d31>), dev=0)',
+                        'Projection.reserve(4)',
+                        'to_host(0, 1)',
+                        'to_host(2, 1)',
+                        'to_host(3, 1)',
+                        'to_host(7, 1)',
+                        'Projection.accumulate(pos32[0,2..3,7 | 24..59,96..119])',
+                        'Projection.device_result()',
+                        'Msd(4, 1, 4, dev=0)',
+                        "Msd.push_device(0, 'amplitudes', 10, 0, 3, 0)",
+                        "Msd.push_device(1, 'amplitudes', 10, 3, 3, 0)",
+                        "Msd.push_device(2, 'amplitudes', 10, 6, 2, 0)",
+                        "Msd.push_device(3, 'amplitudes', 10, 8, 2, 0)",
+                        'Msd.result_acf()',
+                        'Msd.close()',
+                        'Projection.close()'],
+ 'rouse-hbm32-subset': ['Projection(3,2, 12x2, (<(2, 12) #2ea9fc7d31>, <(2, 12) #2ea9fc7d31>), dev=0)',
+                        'Projection.reserve(8)',
+                        'rows(1, 8)',
+                        "Projection.accumulate_device('rows1+8', 120, 8, 24..59,96..119)",
+                        'Projection.device_result()',
+                        'Msd(8, 1, 4, dev=0)',
+                        "Msd.push_device(0, 'amplitudes', 10, 0, 3, 0)",
+                        "Msd.push_device(1, 'amplitudes', 10, 3, 3, 0)",
+                        "Msd.push_device(2, 'amplitudes', 10, 6, 2, 0)",
+                        "Msd.push_device(3, 'amplitudes', 10, 8, 2, 0)",
+                        'Msd.result_acf()',
+                        'Msd.close()',
+                        'Projection.close()'],
+ 'rouse-hbm64': ['Projection(10, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                 'Projection.reserve(10)',
+                 'to_host(0, 10)',
+                 'Projection.accumulate(pos64[0..9 | 0..119])',
+                 'Projection.device_result()',
+                 'Msd(10, 1, 2, dev=0)',
+                 "Msd.push_device(0, 'amplitudes', 20, 0, 10, 0)",
+                 "Msd.push_device(1, 'amplitudes', 20, 10, 10, 0)",
+                 'Msd.result_acf()',
+                 'Msd.close()',
+                 'Projection.close()'],
+ 'rouse-memory': ['Projection(10, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                  'Projection.reserve(10)',
+                  'Projection.accumulate(pos32[0..9 | 0..119])',
+                  'Projection.device_result()',
+                  'Msd(10, 1, 2, dev=0)',
+                  "Msd.push_device(0, 'amplitudes', 20, 0, 10, 0)",
+                  "Msd.push_device(1, 'amplitudes', 20, 10, 10, 0)",
+                  'Msd.result_acf()',
+                  'Msd.close()',
+                  'Projection.close()'],
+ 'rouse-memory-gather': ['Projection(5x2, 12x2, (<(2, 12) #2ea9fc7d31>, <(2, 12) #2ea9fc7d31>), dev=0)',
+                         'Projection.reserve(5)',
+                         'Projection.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                         'Projection.device_result()',
+                         'Msd(2, 2, 4, dev=0)',
+                         "Msd.push_device(0, 'amplitudes', 20, 0, 5, 0)",
+                         "Msd.push_device(1, 'amplitudes', 20, 5, 5, 0)",
+                         "Msd.push_device(2, 'amplitudes', 20, 10, 5, 0)",
+                         "Msd.push_device(3, 'amplitudes', 20, 15, 5, 0)",
+                         'Msd.result_acf()',
+                         'Msd.close()',
+                         'Projection.close()'],
+ 'rouse-memory-no-fft': ['Projection(5, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                         'Projection.reserve(10)',
+                         'Projection.accumulate(pos32[0..9 | 0..59])',
+                         'Projection.result()',
+                         'Projection.close()'],
+ 'rouse-memory-rank1': ['Projection(10, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                        'Projection.reserve(10)',
+                        'Projection.accumulate(pos32[0..9 | 0..119])',
+                        'Projection.device_result()',
+                        'Msd(10, 1, 2, dev=0)',
+                        "Msd.push_device(0, 'amplitudes', 20, 5, 5, 0)",
+                        "Msd.push_device(1, 'amplitudes', 20, 15, 5, 0)",
+                        'Msd.result_acf()',
+                        'Msd.close()',
+                        'Projection.close()'],
+ 'rouse-memory-residues-unwrap': ['Projection(10, 4, ([0.23097 0.0956709 -0.0956709 -0.23097 0.176777 -0.176777 '
+                                  '-0.176777 0.176777]), dev=0)',
+                                  'Projection.set_grouping(0..120/3, <(120,) #2a35702bbc>)',
+                                  'Projection.set_unwrap([50 50 50], <(40, 3) #fb5db8ad72>)',
+                                  'Projection.reserve(8)',
+                                  'Projection.accumulate(pos32[2..9 | 0..119])',
+                                  'Projection.device_result()',
+                                  'Msd(8, 1, 2, dev=0)',
+                                  "Msd.push_device(0, 'amplitudes', 20, 0, 10, 0)",
+                                  "Msd.push_device(1, 'amplitudes', 20, 10, 10, 0)",
+                                  'Msd.result_acf()',
+                                  'Msd.close()',
+                                  'Projection.close()'],
+ 'rouse-per-frame': ['Projection(3,2, 12x2, (<(2, 12) #2ea9fc7d31>, <(2, 12) #2ea9fc7d31>), dev=0)',
+                     'Projection.reserve(10)',
+                     'Projection.accumulate(pos32[0..9 | 24..59,96..119])',
+                     'Projection.device_result()',
+                     'Msd(10, 1, 4, dev=0)',
+                     "Msd.push_device(0, 'amplitudes', 10, 0, 3, 0)",
+                     "Msd.push_device(1, 'amplitudes', 10, 3, 3, 0)",
+                     "Msd.push_device(2, 'amplitudes', 10, 6, 2, 0)",
+                     "Msd.push_device(3, 'amplitudes', 10, 8, 2, 0)",
+                     'Msd.result_acf()',
+                     'Msd.close()',
+                     'Projection.close()'],
+ 'rouse-per-frame-rank1': ['Projection(3, 12, (<(2, 12) #2ea9fc7d31>), dev=0)',
+                           'Projection.reserve(10)',
+                           'Projection.accumulate(pos32[0..9 | 24..59])',
+                           'Projection.device_result()',
+                           'Msd(10, 1, 2, dev=0)',
+                           "Msd.push_device(0, 'amplitudes', 6, 2, 1, 0)",
+                           "Msd.push_device(1, 'amplitudes', 6, 5, 1, 0)",
+                           'Msd.result_acf()',
+                           'Msd.close()',
+                           'Projection.close()'],
+ 'vh-blocks': ['VanHove(1048576, [0 1.25 2.5 3.75 5], 0..1, dev=0, zero_dims=0)',
+               'VanHove.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+               'VanHove.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+               'VanHove.result()',
+               'VanHove.close()'],
+ 'vh-file': ['VanHove(120, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+             'VanHove.accumulate_traj(file, 0..5, None)',
+             'VanHove.result()',
+             'VanHove.close()'],
+ 'vh-file-subset': ['VanHove(60, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+                    'VanHove.accumulate_traj(file, 2..9, 30..89)',
+                    'VanHove.result()',
+                    'VanHove.close()'],
+ 'vh-hbm32': ['VanHove(120, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+              'rows(0, 10)',
+              "VanHove.accumulate_device('rows0+10', 120, 10, None)",
+              'VanHove.result()',
+              'VanHove.close()'],
+ 'vh-hbm32-frames': ['VanHove(60, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+                     'to_host(0, 1)',
+                     'to_host(2, 1)',
+                     'to_host(4, 1)',
+                     'to_host(6, 1)',
+                     'VanHove.accumulate(pos32[0,2,4,6 | 30..89])',
+                     'VanHove.result()',
+                     'VanHove.close()'],
+ 'vh-hbm32-subset': ['VanHove(60, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+                     'rows(1, 8)',
+                     "VanHove.accumulate_device('rows1+8', 120, 8, 30..89)",
+                     'VanHove.result()',
+                     'VanHove.close()'],
+ 'vh-hbm64': ['VanHove(120, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+              'to_host(0, 10)',
+              'VanHove.accumulate(pos64[0..9 | 0..119])',
+              'VanHove.result()',
+              'VanHove.close()'],
+ 'vh-memory': ['VanHove(120, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+               'VanHove.accumulate(pos32[0..9 | 0..119])',
+               'VanHove.result()',
+               'VanHove.close()'],
+ 'vh-memory-gather': ['VanHove(60x2, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+                      'VanHove.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                      'VanHove.result()',
+                      'VanHove.close()'],
+ 'vh-memory-lags-beyond': [],
+ 'vh-memory-unwrap-drop': ['VanHove(120, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=2)',
+                           'VanHove.set_unwrap([50 50 50])',
+                           'VanHove.accumulate(pos32[0..9 | 0..119])',
+                           'VanHove.result()',
+                           'VanHove.close()'],
+ 'vh-per-frame': ['VanHove(60, [0 1.25 2.5 3.75 5], 0..2, dev=0, zero_dims=0)',
+                  'VanHove.accumulate(pos32[0..9 | 30..89])',
+                  'VanHove.result()',
+                  'VanHove.close()'],
+ 'vhd-blocks': ['DistinctVanHove(1048576, 1048576, [0 1.25 2.5 3.75 5], 0..1, [50 50 50], dev=0, origin_step=1, '
+                'same=True, zero_dims=0)',
+                'DistinctVanHove.accumulate(pos32<zero-stride (85, 1048576, 3)>)',
+                'DistinctVanHove.accumulate(pos32<zero-stride (15, 1048576, 3)>)',
+                'DistinctVanHove.result()',
+                'DistinctVanHove.close()'],
+ 'vhd-file': ['DistinctVanHove(120, 120, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, same=True, '
+              'zero_dims=0)',
+              'DistinctVanHove.accumulate_traj(file, 0..5, None)',
+              'DistinctVanHove.result()',
+              'DistinctVanHove.close()'],
+ 'vhd-file-subset': ['DistinctVanHove(30, 30, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, same=False, '
+                     'zero_dims=0)',
+                     'DistinctVanHove.accumulate_traj(file, 2..9, 30..59,90..119)',
+                     'DistinctVanHove.result()',
+                     'DistinctVanHove.close()'],
+ 'vhd-hbm32': ['DistinctVanHove(120, 120, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, same=True, '
+               'zero_dims=0)',
+               'rows(0, 10)',
+               "DistinctVanHove.accumulate_device('rows0+10', 120, 10, None)",
+               'DistinctVanHove.result()',
+               'DistinctVanHove.close()'],
+ 'vhd-hbm32-frames': ['DistinctVanHove(30, 30, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, '
+                      'same=False, zero_dims=0)',
+                      'to_host(0, 1)',
+                      'to_host(2, 1)',
+                      'to_host(4, 1)',
+                      'to_host(6, 1)',
+                      'DistinctVanHove.accumulate(pos32[0,2,4,6 | 30..59,90..119])',
+                      'DistinctVanHove.result()',
+                      'DistinctVanHove.close()'],
+ 'vhd-hbm32-subset': ['DistinctVanHove(30, 30, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, '
+                      'same=False, zero_dims=0)',
+                      'rows(1, 8)',
+                      "DistinctVanHove.accumulate_device('rows1+8', 120, 8, 30..59,90..119)",
+                      'DistinctVanHove.result()',
+                      'DistinctVanHove.close()'],
+ 'vhd-hbm64': ['DistinctVanHove(120, 120, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, same=True, '
+               'zero_dims=0)',
+               'to_host(0, 10)',
+               'DistinctVanHove.accumulate(pos64[0..9 | 0..119])',
+               'DistinctVanHove.result()',
+               'DistinctVanHove.close()'],
+ 'vhd-memory': ['DistinctVanHove(120, 120, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, same=True, '
+                'zero_dims=0)',
+                'DistinctVanHove.accumulate(pos32[0..9 | 0..119])',
+                'DistinctVanHove.result()',
+                'DistinctVanHove.close()'],
+ 'vhd-memory-gather': ['DistinctVanHove(60, 60, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, '
+                       'same=False, zero_dims=0)',
+                       'DistinctVanHove.accumulate(pos32[0,2,4,6,8 | 60..119,0..59])',
+                       'DistinctVanHove.result()',
+                       'DistinctVanHove.close()'],
+ 'vhd-memory-lags-beyond': [],
+ 'vhd-per-frame': ['DistinctVanHove(30, 30, [0 1.25 2.5 3.75 5], 0..2, [50 50 50], dev=0, origin_step=1, same=False, '
+                   'zero_dims=0)',
+                   'DistinctVanHove.accumulate(pos32[0..9 | 30..59,90..119])',
+                   'DistinctVanHove.result()',
+                   'DistinctVanHove.close()']})
