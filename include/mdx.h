@@ -280,6 +280,9 @@ int mdx_isf_create(mdx_isf_t *out, int dev, const double *wavevectors, int64_t n
                    int n_lags, int incoherent);
 int mdx_isf_destroy(mdx_isf_t h);
 int mdx_isf_reset(mdx_isf_t h);
+/* Every call of a series gives the same n (with a grouping: the grouping's particles): another n after the first
+ * frame is MDX_ERR_INVALID_VALUE and leaves the sums as they were, with or without the incoherent part;
+ * mdx_isf_reset starts a new series, which may have another n. */
 int mdx_isf_accumulate(mdx_isf_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Same, positions already in HBM on the engine's device (float32[n_frames][n][3]).  ASYNCHRONOUS on the
  * handle's stream: the frames are copied into the engine's position ring by a device-to-device copy queued on
@@ -294,6 +297,16 @@ int mdx_isf_set_grouping(mdx_isf_t h, int64_t n_molecules, const int64_t *offset
 int mdx_isf_result(mdx_isf_t h, double *cisf, double *iisf);
 int mdx_isf_stats(mdx_isf_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_isf_enable_timing(mdx_isf_t h, int on);
+/* The launch plan of an engine created with these wavevectors, n_groups groups (the largest of max_group
+ * particles), n_slots incoherent slots (the largest of max_range particles) and n_lags lags, for a chunk of n_new
+ * new frames (an accumulate call is cut into chunks of at most n_lags frames).  Touches no device; honours
+ * MDX_SQ_NO_LATTICE and MDX_ISF_NO_QUADS as mdx_isf_create does.  out: 0 route (0 general sincos, 1 per-wavevector
+ * lattice tables, 2 register-blocked quads), 1 row stride of the regular quad form (0: general items, or no quads),
+ * 2 particles per table tile of the incoherent kernel, 3 copies per quad item (1 without quads), 4 quad items
+ * (without quads: wavevectors) per block, 5 blocks along the wavevectors, 6 particle parts of rho, 7 particle parts
+ * of the incoherent sums. */
+int mdx_isf_plan(const double *wavevectors, int64_t n_q, int n_groups, int n_slots, int n_lags, int64_t max_group,
+                 int64_t max_range, int64_t n_new, int32_t out[8]);
 
 /* ------------------------------------------------------------- time correlation
  * Replaces algorithm.correlation.correlation_fft / msd_fft

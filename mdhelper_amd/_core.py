@@ -434,6 +434,27 @@ class IsfEngine(_Engine):
         if timing:
             check(lib().mdx_isf_enable_timing(h, 1))
 
+    PLAN_FIELDS = ("route", "regular_stride", "tile", "n_sub", "items_per_block", "blocks", "rho_split",
+                   "incoherent_split")
+    ROUTES = ("general", "tables", "quads")
+
+    @staticmethod
+    def plan(wavevectors, group_sizes, pairs, n_lags, n_new=None):
+        """``mdx_isf_plan``: the kernels an engine built from these arguments launches for a chunk of ``n_new`` new
+        frames (default: ``n_lags``, a full chunk), as a dict of ``PLAN_FIELDS`` — ``route`` indexes ``ROUTES``.
+        Needs no device; reads ``MDX_SQ_NO_LATTICE`` / ``MDX_ISF_NO_QUADS`` as the constructor does."""
+        q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)
+        sizes = [int(s) for s in group_sizes]
+        if pairs[0][0] is None:
+            ranges = [sum(sizes)]
+        else:
+            diagonal = {int(j) for j, k in pairs if int(j) == int(k)}
+            ranges = [s if g in diagonal else 0 for g, s in enumerate(sizes)]
+        out = np.zeros(8, dtype=np.int32)
+        check(lib().mdx_isf_plan(_ptr(q), q.shape[0], len(sizes), len(ranges), int(n_lags), max(sizes),
+                                 max(ranges), int(n_lags if n_new is None else n_new), _ptr(out)))
+        return dict(zip(IsfEngine.PLAN_FIELDS, (int(v) for v in out)))
+
     _set_grouping = "mdx_isf_set_grouping"
 
     def set_grouping(self, offsets, masses):

@@ -99,6 +99,7 @@ _SIGNATURES = {
     "mdx_isf_result": (c_int, [_vp, _vp, _vp]),
     "mdx_isf_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_isf_enable_timing": (c_int, [_vp, c_int]),
+    "mdx_isf_plan": (c_int, [_vp, c_int64, c_int, c_int, c_int, c_int64, c_int64, c_int64, _vp]),
     # time correlation
     "mdx_msd_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int, c_int]),
     "mdx_msd_destroy": (c_int, [_vp]),

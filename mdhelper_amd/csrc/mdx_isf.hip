@@ -17,6 +17,10 @@
 // factor per frame and dominates; it runs as one fused kernel over
 // (wavevector block, group x particle split, lag) with the frames of a chunk
 // looped inside, so sums are formed in a fixed order (run-to-run reproducible).
+//
+// Every frame of a series has the same number of points, n: the position ring is laid out with stride n.  A call
+// with another n after the first frame is refused (isf_series_points), by an engine without the incoherent part as
+// well — one rule; mdx_isf_reset starts a new series.
 #include "mdx_common.hpp"
 #include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
@@ -241,6 +245,53 @@ __global__ __launch_bounds__(256) void isf_rho_merge_kernel(const double2 *__res
     ring[i] = r;
 }
 
+// ---------------------------------------------------------------------------------------
+// Host planning, shared by the engine and by mdx_isf_plan (which touches no device).
+
+// The kernels a wavevector set goes through: general sincos, per-q lattice tables, or register-blocked quads
+// (MDX_SQ_NO_LATTICE / MDX_ISF_NO_QUADS switch the latter two off).
+struct IsfRoute {
+    bool lattice = false, quads = false;
+    SqLattice lat{};
+    SqQuadShape quad{};
+    std::vector<short> trip;
+    std::vector<SqQuadItem> qitems;
+    int rho_blocks(int qblocks) const { return quads ? quad.blocks() : qblocks; }
+};
+
+static void isf_plan_route(const double *wavevectors, int64_t n_q, IsfRoute &r)
+{
+    r.lattice = sq_detect_lattice(wavevectors, n_q, r.lat, r.trip);
+    r.quads = r.lattice && !getenv("MDX_ISF_NO_QUADS") && sq_quad_plan(r.trip, n_q, r.lat, r.qitems, r.quad);
+}
+
+// Particle parts of rho for a chunk of nf frames: a chunk holds at most n_lags frames, so the particles of a group
+// are split (and the parts summed in a fixed order) until the grid fills the chip.
+static int isf_rho_split(int rblocks, int n_groups, int64_t nf, int64_t max_group)
+{
+    int rs = 1;
+    while (int64_t(rblocks) * 4 * n_groups * rs * nf < 4096 && rs < 64 && max_group / (rs * 2) >= 1024)
+        rs *= 2;
+    return rs;
+}
+
+// Particle parts of the incoherent kernel's slots (quads: 4 waves per block, parts of at least four table tiles)
+static int isf_incoherent_split(const IsfRoute &r, int qblocks, int n_slots, int n_lags, int64_t max_range)
+{
+    int n_split = 1;
+    if (r.quads) {
+        const int iblocks = r.quad.blocks();
+        while (int64_t(iblocks) * 4 * n_slots * n_split * n_lags < 4096 && n_split < 64 &&
+               max_range / (n_split * 2) >= 4 * r.quad.lat.tile)
+            n_split *= 2;
+    } else {
+        while (int64_t(qblocks) * n_slots * n_split * n_lags < 1024 && n_split < 64 &&
+               max_range / (n_split * 2) >= SQ_TILE)
+            n_split *= 2;
+    }
+    return n_split;
+}
+
 struct mdx_isf {
     int dev = 0;
     hipStream_t stream = nullptr;
@@ -248,21 +299,40 @@ struct mdx_isf {
     int n_groups = 0, n_pairs = 0, n_lags = 0, n_slots = 0, ring_slots = 0;
     bool incoherent = false;
     long long frames_seen = 0;
+    int64_t n_series = 0;             // points per frame of the series in progress (the stride of the position ring)
     std::vector<int64_t> offsets;
     std::vector<int64_t> ranges;      // particle range of every incoherent slot
     DeviceBuffer d_q, d_offsets, d_pairs, d_ranges, d_rho_ring, d_pos_ring, d_cisf, d_iisf, d_part,
         d_pos_stage, d_mtrip, d_row_stage, d_rho_parts;
     MoleculeStage mol;      // optional centre-of-mass stage (groupings other than "atoms")
-    bool lattice = false;   // grid wavevectors: separable phase tables (mdx_sq_device.hpp)
-    SqLattice lat{};
+    IsfRoute route;         // lattice: grid wavevectors through separable phase tables (mdx_sq_device.hpp); quads: the
+                            // register-blocked column form of those (sq_rho_quads_kernel, isf_incoherent_quads_kernel)
     size_t lat_lds = 0;
-    // incoherent part through the register-blocked column form (isf_incoherent_quads_kernel)
-    bool quads = false;
-    SqQuadShape quad{};
     DeviceBuffer d_qitems;
+    int64_t max_group = 0, max_range = 0;   // largest group / incoherent slot: what the particle splits go by
     StreamTimer timer;
     FrameFeed feed;                 // host-buffer / trajectory-file entry points: slab k+1 is staged while slab k runs
 };
+
+// The points per frame that frames of n_rows rows give the rings and kernels: with a grouping set the incoming rows
+// are particles sorted molecule by molecule and the points are the float32 centres of mass.  Every frame of a series
+// has the same number of points — it is the stride of the position ring, whose history a call with another count
+// would misread (and lose, where the ring had to grow) — whether or not the engine has the incoherent part: one
+// rule for both.  mdx_isf_reset starts a new series.
+static int isf_series_points(const mdx_isf *h, int64_t n_rows, int64_t *n)
+{
+    *n = n_rows;
+    if (h->mol.active()) {
+        MDX_REQUIRE(n_rows == h->mol.n_atoms, "%lld particles given, the grouping was defined for %lld",
+                    (long long)n_rows, (long long)h->mol.n_atoms);
+        *n = h->mol.n_groups;
+    }
+    MDX_REQUIRE(*n >= h->n_total, "bad size");
+    MDX_REQUIRE(h->frames_seen == 0 || *n == h->n_series,
+                "%lld points per frame given, the frames of this series so far had %lld (mdx_isf_reset starts a new one)",
+                (long long)*n, (long long)h->n_series);
+    return MDX_OK;
+}
 
 // Frames must arrive in analysis order; consecutive calls continue the same series.
 // source(d_dst, done, nf) queues on h->stream whatever brings frames [done, done+nf) of the
@@ -271,15 +341,10 @@ template <typename Source>
 static int isf_accumulate(mdx_isf *h, int64_t n, int64_t n_frames, Source source)
 {
     MDX_TRY(set_device(h->dev));
-    // with a grouping set the incoming rows are particles sorted molecule by molecule; the rings
-    // and kernels below see the float32 centres of mass
     const int64_t n_rows = n;
-    if (h->mol.active()) {
-        MDX_REQUIRE(n == h->mol.n_atoms, "%lld particles given, the grouping was defined for %lld",
-                    (long long)n, (long long)h->mol.n_atoms);
-        n = h->mol.n_groups;
-    }
-    MDX_REQUIRE(n >= h->n_total && n_frames >= 0, "bad size");
+    MDX_TRY(isf_series_points(h, n_rows, &n));
+    MDX_REQUIRE(n_frames >= 0, "bad size");
+    h->n_series = n;
     if (h->incoherent)
         MDX_TRY(h->d_pos_ring.ensure(size_t(12) * n * h->ring_slots));
     const int qblocks = (int)ceil_div(h->n_q, SQ_QPB);
@@ -306,33 +371,25 @@ static int isf_accumulate(mdx_isf *h, int64_t n, int64_t n_frames, Source source
         }
         hipEvent_t ev = h->timer.begin();
         {
-            // rho_g(q) of the new frames -> ring.  A chunk holds at most n_lags frames, so the
-            // particles of a group are split (and the parts summed in a fixed order) until the
-            // grid fills the chip.
-            int64_t max_group = 0;
-            for (int g = 0; g < h->n_groups; ++g)
-                max_group = std::max(max_group, h->offsets[g + 1] - h->offsets[g]);
-            const int rblocks = h->quads ? h->quad.blocks() : qblocks;
-            int rs = 1;
-            while (int64_t(rblocks) * 4 * h->n_groups * rs * nf < 4096 && rs < 64 &&
-                   max_group / (rs * 2) >= 1024)
-                rs *= 2;
+            // rho_g(q) of the new frames -> ring, the particles of a group in rs parts (isf_rho_split)
+            const int rblocks = h->route.rho_blocks(qblocks);
+            const int rs = isf_rho_split(rblocks, h->n_groups, nf, h->max_group);
             double2 *ring = h->d_rho_ring.as<double2>() + int64_t(slot0) * h->n_groups * h->n_q;
             double2 *dst = ring;
             if (rs > 1) {
                 MDX_TRY(h->d_rho_parts.ensure(size_t(16) * nf * h->n_groups * rs * h->n_q));
                 dst = h->d_rho_parts.as<double2>();
             }
-            if (h->quads)
-                hipLaunchKernelGGL(sq_rho_quads_pick(h->quad.regular_stride), dim3(rblocks, h->n_groups * rs, (unsigned)nf),
-                                   dim3(SQ_QUAD_THREADS), h->quad.lds, h->stream, d_new, n,
-                                   h->d_qitems.as<SqQuadItem>(), h->quad.n_items, h->quad.ipb,
-                                   h->quad.n_sub, (int)h->n_q, h->quad.lat, h->d_offsets.as<int64_t>(),
+            if (h->route.quads)
+                hipLaunchKernelGGL(sq_rho_quads_pick(h->route.quad.regular_stride), dim3(rblocks, h->n_groups * rs, (unsigned)nf),
+                                   dim3(SQ_QUAD_THREADS), h->route.quad.lds, h->stream, d_new, n,
+                                   h->d_qitems.as<SqQuadItem>(), h->route.quad.n_items, h->route.quad.ipb,
+                                   h->route.quad.n_sub, (int)h->n_q, h->route.quad.lat, h->d_offsets.as<int64_t>(),
                                    h->n_groups, rs, dst);
-            else if (h->lattice)
+            else if (h->route.lattice)
                 hipLaunchKernelGGL(sq_rho_lattice_kernel, dim3(qblocks, h->n_groups * rs, (unsigned)nf),
                                    dim3(SQ_THREADS), h->lat_lds, h->stream, d_new, n,
-                                   h->d_mtrip.as<short4>(), (int)h->n_q, h->lat,
+                                   h->d_mtrip.as<short4>(), (int)h->n_q, h->route.lat,
                                    h->d_offsets.as<int64_t>(), h->n_groups, rs, dst);
             else
                 hipLaunchKernelGGL(sq_rho_kernel, dim3(qblocks, h->n_groups * rs, (unsigned)nf),
@@ -350,33 +407,22 @@ static int isf_accumulate(mdx_isf *h, int64_t n, int64_t n_frames, Source source
                            (int)h->n_q, h->d_pairs.as<int>(), h->n_pairs, h->n_lags, f0, (int)nf,
                            h->d_cisf.as<double>());
         if (h->incoherent) {
-            int64_t max_range = 0;
-            for (int s = 0; s < h->n_slots; ++s)
-                max_range = std::max(max_range, h->ranges[2 * s + 1] - h->ranges[2 * s]);
-            int n_split = 1;
-            while (int64_t(qblocks) * h->n_slots * n_split * h->n_lags < 1024 && n_split < 64 &&
-                   max_range / (n_split * 2) >= SQ_TILE)
-                n_split *= 2;
+            const int n_split = isf_incoherent_split(h->route, qblocks, h->n_slots, h->n_lags, h->max_range);
             const int64_t n_out = int64_t(h->n_lags) * h->n_slots * h->n_q;
             MDX_TRY(h->d_part.ensure(size_t(8) * n_out * n_split));
-            if (h->quads) {
-                const int iblocks = h->quad.blocks();
-                n_split = 1;   // 4 waves per block here
-                while (int64_t(iblocks) * 4 * h->n_slots * n_split * h->n_lags < 4096 && n_split < 64 &&
-                       max_range / (n_split * 2) >= 4 * h->quad.lat.tile)
-                    n_split *= 2;
-                MDX_TRY(h->d_part.ensure(size_t(8) * n_out * n_split));
-                hipLaunchKernelGGL(isf_incoherent_quads_pick(h->quad.regular_stride),
+            if (h->route.quads) {
+                const int iblocks = h->route.quad.blocks();
+                hipLaunchKernelGGL(isf_incoherent_quads_pick(h->route.quad.regular_stride),
                                    dim3(iblocks, h->n_slots * n_split, h->n_lags), dim3(SQ_QUAD_THREADS),
-                                   h->quad.lds, h->stream, h->d_pos_ring.as<float>(), h->ring_slots, n,
-                                   h->d_qitems.as<SqQuadItem>(), h->quad.n_items, h->quad.ipb,
-                                   h->quad.n_sub, (int)h->n_q, h->quad.lat, h->d_ranges.as<int64_t>(),
+                                   h->route.quad.lds, h->stream, h->d_pos_ring.as<float>(), h->ring_slots, n,
+                                   h->d_qitems.as<SqQuadItem>(), h->route.quad.n_items, h->route.quad.ipb,
+                                   h->route.quad.n_sub, (int)h->n_q, h->route.quad.lat, h->d_ranges.as<int64_t>(),
                                    h->n_slots, n_split, h->n_lags, f0, (int)nf, h->d_part.as<double>());
-            } else if (h->lattice)
+            } else if (h->route.lattice)
                 hipLaunchKernelGGL(isf_incoherent_lattice_kernel,
                                    dim3(qblocks, h->n_slots * n_split, h->n_lags), dim3(SQ_THREADS),
                                    h->lat_lds, h->stream, h->d_pos_ring.as<float>(), h->ring_slots, n,
-                                   h->d_mtrip.as<short4>(), (int)h->n_q, h->lat,
+                                   h->d_mtrip.as<short4>(), (int)h->n_q, h->route.lat,
                                    h->d_ranges.as<int64_t>(), h->n_slots, n_split, h->n_lags, f0,
                                    (int)nf, h->d_part.as<double>());
             else
@@ -434,6 +480,8 @@ int mdx_isf_accumulate(mdx_isf_t h, const float *pos, int64_t n, int64_t n_frame
 {
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
+    int64_t n_points = 0;
+    MDX_TRY(isf_series_points(h, n, &n_points));   // before the pipeline starts
     MDX_TRY(set_device(h->dev));
     // Slabs of frames travel host -> pinned ring -> HBM on the pipeline's copy stream while the kernels of the
     // slab before run (a pageable hipMemcpyAsync on the compute stream, the first form of this entry point, sat
@@ -463,6 +511,8 @@ int mdx_isf_accumulate_traj(mdx_isf_t h, mdx_traj_t traj, const int64_t *frames,
     Trajectory *t = mdx_traj_internal(traj);
     const int64_t n = index ? n_index : (n_index > 0 ? n_index : t->n_atoms);
     MDX_REQUIRE(index || n <= t->n_atoms, "selection larger than the trajectory");
+    int64_t n_points = 0;
+    MDX_TRY(isf_series_points(h, n, &n_points));   // before the pipeline starts
     const int *d_index = nullptr;
     if (index) {
         for (int64_t i = 0; i < n; ++i)
@@ -526,6 +576,10 @@ int mdx_isf_create(mdx_isf_t *out, int dev, const double *wavevectors, int64_t n
                 h->ranges[2 * g + 1] = group_offsets[g + 1];
             }
     }
+    for (int g = 0; g < n_groups; ++g)
+        h->max_group = std::max(h->max_group, group_offsets[g + 1] - group_offsets[g]);
+    for (int s = 0; s < h->n_slots; ++s)
+        h->max_range = std::max(h->max_range, h->ranges[2 * s + 1] - h->ranges[2 * s]);
     int rc = MDX_OK;
     do {
         if ((rc = stream_acquire(&h->stream)) != MDX_OK)
@@ -548,31 +602,30 @@ int mdx_isf_create(mdx_isf_t *out, int dev, const double *wavevectors, int64_t n
             rc = fail(MDX_ERR_HIP, "upload failed");
             break;
         }
-        std::vector<short> trip;
-        h->lattice = sq_detect_lattice(wavevectors, n_q, h->lat, trip);
-        if (h->lattice) {
-            h->lat_lds = size_t(16) * h->lat.tile * (h->lat.R[0] + h->lat.R[1] + h->lat.R[2]);
+        isf_plan_route(wavevectors, n_q, h->route);
+        const std::vector<short> &trip = h->route.trip;
+        if (h->route.lattice) {
+            h->lat_lds = size_t(16) * h->route.lat.tile * (h->route.lat.R[0] + h->route.lat.R[1] + h->route.lat.R[2]);
             if ((rc = h->d_mtrip.ensure(size_t(8) * n_q)) != MDX_OK) break;
             if (hipMemcpy(h->d_mtrip.ptr, trip.data(), size_t(8) * n_q, hipMemcpyHostToDevice) !=
                 hipSuccess) {
                 rc = fail(MDX_ERR_HIP, "lattice table setup failed");
                 break;
             }
-            std::vector<SqQuadItem> qitems;
-            if (!getenv("MDX_ISF_NO_QUADS") && sq_quad_plan(trip, n_q, h->lat, qitems, h->quad)) {
+            const std::vector<SqQuadItem> &qitems = h->route.qitems;
+            if (h->route.quads) {
                 if ((rc = h->d_qitems.ensure(sizeof(SqQuadItem) * qitems.size())) != MDX_OK) break;
                 if (hipMemcpy(h->d_qitems.ptr, qitems.data(), sizeof(SqQuadItem) * qitems.size(),
                               hipMemcpyHostToDevice) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(isf_incoherent_quads_pick(h->quad.regular_stride)),
+                    hipFuncSetAttribute(reinterpret_cast<const void *>(isf_incoherent_quads_pick(h->route.quad.regular_stride)),
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)h->quad.lds) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(sq_rho_quads_pick(h->quad.regular_stride)),
+                                        (int)h->route.quad.lds) != hipSuccess ||
+                    hipFuncSetAttribute(reinterpret_cast<const void *>(sq_rho_quads_pick(h->route.quad.regular_stride)),
                                         hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)h->quad.lds) != hipSuccess) {
+                                        (int)h->route.quad.lds) != hipSuccess) {
                     rc = fail(MDX_ERR_HIP, "quad table setup failed");
                     break;
                 }
-                h->quads = true;
             }
         }
     } while (0);
@@ -582,6 +635,30 @@ int mdx_isf_create(mdx_isf_t *out, int dev, const double *wavevectors, int64_t n
     }
     *out = h;
     return mdx_isf_reset(h);
+}
+
+// What an engine created with these wavevectors would launch; touches no device.
+int mdx_isf_plan(const double *wavevectors, int64_t n_q, int n_groups, int n_slots, int n_lags,
+                 int64_t max_group, int64_t max_range, int64_t n_new, int32_t out[8])
+{
+    MDX_REQUIRE(wavevectors && out, "NULL argument");
+    MDX_REQUIRE(n_q >= 1 && n_q < (int64_t(1) << 30), "n_q out of range");
+    MDX_REQUIRE(n_groups >= 1 && n_groups <= 1024, "n_groups out of range");
+    MDX_REQUIRE(n_slots >= 1 && n_slots <= n_groups, "n_slots out of range");
+    MDX_REQUIRE(n_lags >= 1 && n_lags <= 32768, "n_lags out of range");
+    MDX_REQUIRE(max_group >= 0 && max_range >= 0 && n_new >= 1, "bad size");
+    IsfRoute r;
+    isf_plan_route(wavevectors, n_q, r);
+    const int qblocks = (int)ceil_div(n_q, SQ_QPB);
+    out[0] = r.quads ? 2 : r.lattice ? 1 : 0;
+    out[1] = r.quads ? r.quad.regular_stride : 0;
+    out[2] = r.quads ? r.quad.lat.tile : r.lattice ? r.lat.tile : SQ_TILE / 2;
+    out[3] = r.quads ? r.quad.n_sub : 1;
+    out[4] = r.quads ? r.quad.ipb : SQ_QPB;
+    out[5] = r.rho_blocks(qblocks);
+    out[6] = isf_rho_split(out[5], n_groups, std::min<int64_t>(n_new, n_lags), max_group);
+    out[7] = isf_incoherent_split(r, qblocks, n_slots, n_lags, max_range);
+    return MDX_OK;
 }
 
 int mdx_isf_destroy(mdx_isf_t h)

@@ -195,3 +195,122 @@ def isf_run_ref(frames, group_sizes, wavevectors, n_lags=None, *, mode=None, inc
         if incoherent:
             iisf = iisf[:, :, order]
     return {"pairs": pairs, "wavenumbers": out_q, "cisf": cisf, "iisf": iisf}
+
+
+# --------------------------------------------------------------------------------------------------
+# The ISF engine's outputs straight from their definition (header comment of csrc/mdx_isf.hip): no ring, frames
+# f and f - lag indexed directly, every phase, sine, cosine and sum in extended precision.
+
+_WIDE = np.longdouble if np.finfo(np.longdouble).eps < np.finfo(np.float64).eps else None
+
+
+def _wide(a):
+    return np.asarray(a, dtype=np.float64).astype(_WIDE or np.float64)
+
+
+def _sum_rows(terms):
+    """Sum over the last axis: in extended precision as it stands, else exactly rounded (math.fsum)."""
+    if _WIDE is not None:
+        return terms.sum(axis=-1)
+    import math
+    flat = terms.reshape(-1, terms.shape[-1])
+    return np.array([math.fsum(row) for row in flat]).reshape(terms.shape[:-1])
+
+
+def molecule_centres_ref(frames, mol_offsets, masses):
+    """float32[F, n_molecules, 3]: the centres of mass as ``molecule_com_kernel`` (csrc/mdx_molecules.hpp) states
+    them — a float64 sum of ``m * x`` over the rows of a molecule in row order with separate multiply and add, one
+    division by the sequentially summed mass, cast to float32."""
+    x = np.asarray(frames, dtype=np.float32).astype(np.float64)
+    o = np.asarray(mol_offsets, dtype=np.int64)
+    m = np.asarray(masses, dtype=np.float64)
+    lens = np.diff(o)
+    acc = np.zeros((x.shape[0], len(lens), 3))
+    total = np.zeros(len(lens))
+    for k in range(int(lens.max())):
+        has = np.flatnonzero(lens > k)
+        rows = o[has] + k
+        acc[:, has] = acc[:, has] + m[rows][None, :, None] * x[:, rows]
+        total[has] = total[has] + m[rows]
+    return (acc / total[None, :, None]).astype(np.float32)
+
+
+def isf_definition_ref(frames, group_offsets, pairs, wavevectors, n_lags):
+    """
+    Un-normalised ``cisf[lag][p][q]`` and ``iisf[lag][slot][q]`` of ``IsfEngine.result()``:
+
+        rho_g(q, f) = sum_{j in g} exp(i q . r_j(f))
+        cisf[lag][p] = sum_{f >= lag} Re rho_j(f - lag) rho_j(f)^*                                      p = (j, j)
+                       sum_{f >= lag} Re rho_j(f - lag) rho_k(f)^* + Re rho_k(f - lag) rho_j(f)^*       p = (j, k)
+                       sum_{f >= lag} Re rho(f - lag) rho(f)^*,  rho = sum_g rho_g                      p = (None, None)
+        iisf[lag][g] = sum_{f >= lag} sum_{j in g} cos(q . (r_j(f) - r_j(f - lag)))
+
+    frames : float32[F, n >= group_offsets[-1], 3] (rows beyond the groups' span are ignored); ``pairs``: ANY list
+    of pairs of groups, or ``((None, None),)`` for the total mode.  The ``iisf`` slots are the engine's: one for the
+    total mode, else one per group, zero for a group without a ``(g, g)`` pair.  Lags >= F are zero.
+
+    The float32 coordinates are widened exactly; phases, sines, cosines and sums are formed in ``numpy.longdouble``
+    where that is wider than float64 (x86), else in float64 with exactly rounded sums.
+
+    Also returned, for error bounds: ``S_cisf`` = sum_f |rho_a(f - lag)| |rho_b(f)| (both orderings for a cross
+    pair), ``S_iisf`` = slot size x number of frame pairs at the lag, ``phi_max`` = the largest |q . r| of a particle
+    of a group in any frame.  All outputs float64.
+    """
+    x = _wide(np.asarray(frames, dtype=np.float32))
+    q = _wide(np.asarray(wavevectors, dtype=np.float64).reshape(-1, 3))
+    o = [int(v) for v in group_offsets]
+    n_groups, n_q, n_frames = len(o) - 1, len(q), len(x)
+    total_mode = pairs[0][0] is None
+    dtype = x.dtype
+
+    def phases(r):          # [..., n, 3] -> [..., n_q, n]
+        return (q[:, None, 0] * r[..., None, :, 0] + q[:, None, 1] * r[..., None, :, 1]) + q[:, None, 2] * r[..., None, :, 2]
+
+    # rho[f][g][q], cos and sin parts
+    rc = np.zeros((n_frames, n_groups, n_q), dtype=dtype)
+    rs = np.zeros((n_frames, n_groups, n_q), dtype=dtype)
+    phi_max = 0.0
+    for g in range(n_groups):
+        if o[g + 1] == o[g]:
+            continue
+        for f in range(n_frames):
+            ph = phases(x[f, o[g]:o[g + 1]])
+            phi_max = max(phi_max, float(np.abs(ph).max()))
+            rc[f, g] = _sum_rows(np.cos(ph))
+            rs[f, g] = _sum_rows(np.sin(ph))
+    if total_mode:
+        rc = rc.sum(axis=1, keepdims=True)
+        rs = rs.sum(axis=1, keepdims=True)
+        use = [(0, 0)]
+        slots = [(o[0], o[n_groups])]
+    else:
+        use = [(int(j), int(k)) for j, k in pairs]
+        diagonal = {j for j, k in use if j == k}
+        slots = [(o[g], o[g + 1]) if g in diagonal else (0, 0) for g in range(n_groups)]
+    mod = np.sqrt(rc * rc + rs * rs)
+
+    cisf = np.zeros((n_lags, len(use), n_q), dtype=dtype)
+    s_cisf = np.zeros((n_lags, len(use), n_q), dtype=dtype)
+    iisf = np.zeros((n_lags, len(slots), n_q), dtype=dtype)
+    s_iisf = np.zeros((n_lags, len(slots), n_q))
+    for lag in range(min(n_lags, n_frames)):
+        old, new = slice(0, n_frames - lag), slice(lag, n_frames)
+        for p, (j, k) in enumerate(use):
+            re = rc[old, j] * rc[new, k] + rs[old, j] * rs[new, k]
+            s = mod[old, j] * mod[new, k]
+            if j != k:
+                re = re + (rc[old, k] * rc[new, j] + rs[old, k] * rs[new, j])
+                s = s + mod[old, k] * mod[new, j]
+            cisf[lag, p] = re.sum(axis=0)
+            s_cisf[lag, p] = s.sum(axis=0)
+        for slot, (lo, hi) in enumerate(slots):
+            if hi == lo:
+                continue
+            d = x[new, lo:hi] - x[old, lo:hi]                  # exact: float32 differences fit the wide type
+            acc = np.zeros(n_q, dtype=dtype)
+            for f in range(n_frames - lag):
+                acc = acc + _sum_rows(np.cos(phases(d[f])))
+            iisf[lag, slot] = acc
+            s_iisf[lag, slot] = float(hi - lo) * (n_frames - lag)
+    return {"cisf": cisf.astype(np.float64), "iisf": iisf.astype(np.float64),
+            "S_cisf": s_cisf.astype(np.float64), "S_iisf": s_iisf, "phi_max": phi_max}
