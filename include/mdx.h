@@ -817,6 +817,61 @@ int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *max_row, int64_t *sweeps);
 int mdx_clu_enable_timing(mdx_clu_t h, int on);
 
+/* ------------------------------------------------------------------ angular distributions
+ * Per analysed frame the angles ligand-center-ligand in the first shell of every center.  The rows of a frame are the
+ * n_centers centers, then the ligands group by group: n_species groups (1 ... 4) of ligand_sizes[g] rows; species(j)
+ * of a ligand follows from the sizes.  With same, n_species == 1, ligand_sizes[0] == n_centers, the ligands are the
+ * centers themselves, the rows arrive once and j == i never counts.  Box, minimum image and r2 are those of
+ * mdx_prs_*: float32 rows, one constant orthorhombic box dims[3], zero_dims (bit c set: component c takes no part),
+ * everything in float64, one operation at a time.  For center i and ligand j:
+ *     d = x_j - x_i;  w = d - L * rint(d * (1.0 / L)), +0.0 for a dropped component;  r2 = (wx*wx + wy*wy) + wz*wz;
+ *     j is a neighbour of i iff r2 <= cutoff[species(j)]^2 (a NaN r2 is none).
+ * cutoff[n_species]: positive, finite, the largest at most half the shortest kept box length.  For every center and
+ * every unordered pair {j, k}, j != k, of its neighbours:
+ *     dot = (w_ijx*w_ikx + w_ijy*w_iky) + w_ijz*w_ikz;  c = dot / sqrt(r2_ij * r2_ik)
+ * (one multiply, one correctly rounded sqrt, one correctly rounded divide; symmetric in j and k).  thresholds is
+ * t[0 ... n_bins], strictly decreasing (anything else is MDX_ERR_INVALID_VALUE); the bin of a triplet is
+ * b = #{m in 1 ... n_bins - 1 : c <= t[m]}, so bin b holds t[b + 1] < c <= t[b], the first bin also takes c > t[0] and
+ * the last also c <= t[n_bins]; only the inner thresholds are compared.  A NaN c (a ligand on its center, r2 == 0)
+ * goes into no bin and adds 1 to degenerate[p].  Results, all integers:
+ *     counts[p][b] and degenerate[p], p = a*G - a*(a-1)/2 + (b-a) the unordered pair of ligand species a <= b of the
+ *                two ligands, P = G (G + 1) / 2 of them (G = n_species);
+ *     coordination[g][m], m = 0 ... max_neighbors: the (frame, center) cases with exactly m neighbours of species g.
+ * max_neighbors (1 ... 64): the neighbours of all species a center may hold in one frame; exactly full is no error.
+ * A center that would hold more is never truncated silently: mdx_ang_synchronize and mdx_ang_result fail with
+ * MDX_ERR_INVALID_VALUE (the message names max_neighbors and the largest row seen) until mdx_ang_reset.  All results
+ * are identical across the three input routes, across any split of the frames into calls or slabs, and after a reset
+ * (csrc/mdx_angle_device.hpp).  Frames are independent: nothing but the results outlives a slab.  Every (center,
+ * ligand) pair is evaluated, there is no cell list.  A handle touches its device with the first frame: mdx_ang_create
+ * and every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_ang *mdx_ang_t;
+int mdx_ang_create(mdx_ang_t *out, int dev, int64_t n_centers, int n_species, const int64_t *ligand_sizes, int same,
+                   const double *cutoff, int64_t n_bins, const double *thresholds, const double *dims, int zero_dims,
+                   int max_neighbors);
+int mdx_ang_destroy(mdx_ang_t h);
+/* Forgets the frames seen and an overflowing row, and zeroes the results. */
+int mdx_ang_reset(mdx_ang_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the lists in HBM).  The results
+ * do not depend on it.  Only before the first frame. */
+int mdx_ang_set_slab_frames(mdx_ang_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n_centers + the ligands, or n_centers with same. */
+int mdx_ang_accumulate(mdx_ang_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows. */
+int mdx_ang_accumulate_device(mdx_ang_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_ang_accumulate_traj(mdx_ang_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_ang_synchronize(mdx_ang_t h);
+/* counts: int64 [P][n_bins]; degenerate: int64 [P]; coordination: int64 [n_species][max_neighbors + 1]. */
+int mdx_ang_result(mdx_ang_t h, int64_t *counts, int64_t *degenerate, int64_t *coordination);
+/* evaluations: the contract's pair count so far, frames x (n_centers * ligands - (same ? n_centers : 0)); triplets:
+ * sum counts + sum degenerate; max_row: the most neighbours a center held in one frame (beyond max_neighbors: the
+ * results are refused). */
+int mdx_ang_stats(mdx_ang_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *triplets, int64_t *max_row);
+int mdx_ang_enable_timing(mdx_ang_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

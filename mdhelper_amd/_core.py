@@ -1025,6 +1025,72 @@ class ClusterEngine(_SlabbedFrameEngine):
         return out
 
 
+class AngleEngine(_SlabbedFrameEngine):
+    """``mdx_ang_*``: per frame the neighbours of each of ``n_centers`` centres among ``G <= 4`` ligand groups of
+    ``ligand_sizes`` rows (minimum-image ``r2 <= cutoff[g] ** 2`` in float64 for a ligand of group ``g``), and for
+    every unordered pair of neighbours of a centre ``c = dot / sqrt(r2_ij * r2_ik)``, counted in bin
+    ``#{m in 1 ... n_bins - 1 : c <= thresholds[m]}`` of the unordered pair ``p = a*G - a*(a-1)/2 + (b-a)`` of the two
+    ligands' species; a NaN ``c`` (a ligand on its centre) counts in ``degenerate[p]``.  ``thresholds`` is
+    ``float64 [n_bins + 1]``, strictly decreasing.  Incoming rows are the centres, then the ligands group by group;
+    with ``same`` the one ligand group is the centres themselves, the rows arrive once and ``j == i`` never counts.
+    A centre may hold ``max_neighbors`` neighbours in one frame; one that would hold more makes ``synchronize()`` and
+    ``result()`` raise ``ValueError`` until ``reset()``.  The device is first touched by the first frame, so the
+    argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_ang"
+    _stats_extra = (("evaluations", c_int64), ("triplets", c_int64), ("max_row", c_int64))
+    TILE = 256          # centres per block of the list kernel (ANG_TILE of csrc/mdx_angle_device.hpp)
+    STAGE = 256         # ligands per LDS stage (ANG_STAGE)
+    JCHUNK = 1024       # ligands per block (ANG_JCHUNK)
+    MAX_NEIGHBORS = 64  # slots of a row at most (ANG_MAX_NEIGHBORS)
+    MAX_SPECIES = 4     # ANG_MAX_SPECIES
+
+    @staticmethod
+    def pair_index(a, b, n_species):
+        """The number ``p`` of the unordered pair of ligand species ``(a, b)``."""
+        a, b = min(a, b), max(a, b)
+        return a * n_species - a * (a - 1) // 2 + (b - a)
+
+    def __init__(self, n_centers, ligand_sizes, cutoff, thresholds, dims, *, same=False, zero_dims=0,
+                 max_neighbors=32, dev=0, timing=False):
+        self.n_centers, self.same = int(n_centers), bool(same)
+        self.ligand_sizes = np.ascontiguousarray(np.atleast_1d(ligand_sizes), dtype=np.int64)
+        if self.ligand_sizes.ndim != 1 or not 1 <= len(self.ligand_sizes) <= self.MAX_SPECIES:
+            raise ValueError(f"ligand_sizes must hold between 1 and {self.MAX_SPECIES} sizes.")
+        self.n_species = len(self.ligand_sizes)
+        self.n_pairs = self.n_species * (self.n_species + 1) // 2
+        self.n_rows = self.n_centers if self.same else self.n_centers + int(self.ligand_sizes.sum())
+        cut = np.asarray(cutoff, dtype=np.float64)
+        if cut.ndim == 0:
+            cut = np.full(self.n_species, float(cut))
+        if cut.shape != (self.n_species,):
+            raise ValueError(f"cutoff must be a number or {self.n_species} values, one per ligand group.")
+        self.cutoff = np.ascontiguousarray(cut)
+        self.thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if self.thresholds.ndim != 1 or len(self.thresholds) < 2:
+            raise ValueError("thresholds must hold n_bins + 1 values, at least two.")
+        self.n_bins = len(self.thresholds) - 1
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.max_neighbors = int(max_neighbors)
+        h = c_void_p()
+        check(lib().mdx_ang_create(byref(h), dev, self.n_centers, self.n_species, _ptr(self.ligand_sizes),
+                                   int(self.same), _ptr(self.cutoff), self.n_bins, _ptr(self.thresholds),
+                                   _ptr(self.dims), int(zero_dims), self.max_neighbors))
+        self._adopt(h, dev, timing)
+
+    def result(self):
+        """``{"counts": int64 [P, n_bins], "degenerate": int64 [P], "coordination": int64 [G, max_neighbors + 1]}``
+        over the frames seen."""
+        out = {"counts": np.zeros((self.n_pairs, self.n_bins), dtype=np.int64),
+               "degenerate": np.zeros(self.n_pairs, dtype=np.int64),
+               "coordination": np.zeros((self.n_species, self.max_neighbors + 1), dtype=np.int64)}
+        check(lib().mdx_ang_result(self.handle, _ptr(out["counts"]), _ptr(out["degenerate"]),
+                                   _ptr(out["coordination"])))
+        return out
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

@@ -261,6 +261,20 @@ _SIGNATURES = {
     "mdx_clu_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64), POINTER(c_int64)]),
     "mdx_clu_enable_timing": (c_int, [_vp, c_int]),
+    # angular distributions (ligand-center-ligand angles in the first shell)
+    "mdx_ang_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int, _vp, c_int, _vp, c_int64, _vp, _vp, c_int,
+                               c_int]),
+    "mdx_ang_destroy": (c_int, [_vp]),
+    "mdx_ang_reset": (c_int, [_vp]),
+    "mdx_ang_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_ang_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_ang_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_ang_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_ang_synchronize": (c_int, [_vp]),
+    "mdx_ang_result": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_ang_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_ang_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

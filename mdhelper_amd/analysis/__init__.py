@@ -1,8 +1,9 @@
 """Analysis classes of the hot path (mirrors ``mdhelper.analysis``)."""
 
-from . import base, cluster, dynamics, electrostatics, polymer, profile, structure, transport  # noqa: F401
+from . import angle, base, cluster, dynamics, electrostatics, polymer, profile, structure, transport  # noqa: F401
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
+from .angle import AngularDistribution  # noqa: F401
 from .cluster import Clusters  # noqa: F401
 from .dynamics import (DistinctVanHove, PairResidence, VanHove, calculate_non_gaussian_parameter,  # noqa: F401
                        calculate_residence_time)
