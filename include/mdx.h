@@ -593,6 +593,47 @@ int mdx_rouse_device_result(mdx_rouse_t h, const double **d_ptr, int64_t *n_fram
 int mdx_rouse_stats(mdx_rouse_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_rouse_enable_timing(mdx_rouse_t h, int on);
 
+/* ---- chain internal distances and bond-orientation correlations (analysis/polymer.py InternalDistances; no
+ * counterpart in the reference) --------------------------------------------------------------------------------------
+ * Rows arrive as for the gyration engine: group g holds n_chains[g] * n_monomers[g] consecutive points, a chain is
+ * n_monomers[g] >= 2 consecutive points.  Per frame and group of M chains of N points, in float64 with separate
+ * multiply and add (float32 coordinates are widened before any arithmetic):
+ *     R2(s) = sum_c sum_i |x_{c,i+s} - x_{c,i}|^2 / (M (N - s)),        s = 1 ... N-1,   |d|^2 = (dx dx + dy dy) + dz dz
+ *     u_i   = (x_{i+1} - x_i) / sqrt(|x_{i+1} - x_i|^2)                 (0 for a bond of no length)
+ *     C(s)  = sum_c sum_i u_{c,i} . u_{c,i+s} / (M (N - 1 - s)),        s = 0 ... N-2.
+ * Every sum has a fixed order that depends on (M, N) alone (csrc/mdx_msid_device.hpp: i ascending per chain and
+ * separation, chains ascending within a unit, units ascending, one division) and no floating-point atomics are used,
+ * so the rows are bit-identical across the three input routes and across any split of the frames into calls or
+ * slabs.  A frame's rows: for group g at offset 2 sum_{h<g} (N_h - 1), first the N_g - 1 values R2(1 ... N-1), then
+ * the N_g - 1 values C(0 ... N-2).  Argument errors return MDX_ERR_INVALID_VALUE before any device is touched. */
+typedef struct mdx_msid *mdx_msid_t;
+int mdx_msid_create(mdx_msid_t *out, int dev, int n_groups, const int64_t *n_chains, const int64_t *n_monomers);
+int mdx_msid_destroy(mdx_msid_t h);
+/* Forgets the frames seen and the unwrap state (the next frame is again compared with `start`). */
+int mdx_msid_reset(mdx_msid_t h);
+/* Room for n_frames frames in all, allocated once (without it the buffer doubles as frames arrive). */
+int mdx_msid_reserve(mdx_msid_t h, int64_t n_frames);
+/* As mdx_gyr_set_grouping / mdx_gyr_set_unwrap.  mdx_msid_set_unwrap excludes mdx_msid_set_whole. */
+int mdx_msid_set_grouping(mdx_msid_t h, int64_t n_molecules, const int64_t *offsets, const double *masses);
+int mdx_msid_set_unwrap(mdx_msid_t h, const double *dims, const double *start);
+/* Every chain made whole in every frame by itself, in float64 on the points (the monomer centres under a grouping):
+ * x_0 = r_0;  d = r_{n+1} - r_n per component;  |d| >= dims / 2 moves d by -sign(d) * dims;  x_{n+1} = x_n + d.
+ * Bonds must be shorter than half the shortest box length.  No state is carried between frames, so frames may be
+ * fed in any order and shard across ranks.  dims == NULL switches it off.  Only before the first frame; excludes
+ * mdx_msid_set_unwrap. */
+int mdx_msid_set_whole(mdx_msid_t h, const double *dims);
+/* The three input routes of the gyration engine. */
+int mdx_msid_accumulate(mdx_msid_t h, const float *pos, int64_t n, int64_t n_frames);
+int mdx_msid_accumulate_device(mdx_msid_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                               const int32_t *index, int64_t n_index);
+int mdx_msid_accumulate_traj(mdx_msid_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                             const int32_t *index, int64_t n_index);
+int mdx_msid_synchronize(mdx_msid_t h);
+/* out: float64 [frames seen][2 sum_g (N_g - 1)]. */
+int mdx_msid_result(mdx_msid_t h, double *out);
+int mdx_msid_stats(mdx_msid_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
+int mdx_msid_enable_timing(mdx_msid_t h, int on);
+
 /* ---- instantaneous dipole moments (reference analysis/electrostatics.py DipoleMoment) ------------------------------
  * Rows arrive in the order of the concatenated groups: group g holds n_points[g] consecutive points; charges float64,
  * one per point in that order, finite.  Per frame, group and component, in float64 with separate multiply and add

@@ -774,6 +774,76 @@ class ChainProjectionEngine(_FrameEngine):
 RouseEngine = ChainProjectionEngine
 
 
+class InternalDistanceEngine(_FrameEngine):
+    """``mdx_msid_*``: per frame and group the mean-square internal distances ``R2(s)``, ``s = 1 ... N - 1``, and the
+    bond-orientation correlations ``C(s)``, ``s = 0 ... N - 2``, of chains of ``N`` points, in float64."""
+
+    _prefix = "mdx_msid"
+
+    def __init__(self, n_chains, n_monomers, *, dev=0, timing=False):
+        self.n_chains = np.ascontiguousarray(np.atleast_1d(n_chains), dtype=np.int64)
+        self.n_monomers = np.ascontiguousarray(np.atleast_1d(n_monomers), dtype=np.int64)
+        if self.n_chains.ndim != 1 or self.n_chains.shape != self.n_monomers.shape or len(self.n_chains) == 0:
+            raise ValueError("n_chains and n_monomers must hold one entry per group.")
+        self.n_groups = len(self.n_chains)
+        self.n_points = int((self.n_chains * self.n_monomers).sum())
+        self.row0 = np.concatenate(([0], np.cumsum(2 * (self.n_monomers - 1))))
+        h = c_void_p()
+        check(lib().mdx_msid_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers)))
+        self._adopt(h, dev, timing)
+
+    def set_grouping(self, offsets, masses):
+        """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
+        groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
+        if offsets is None:
+            check(lib().mdx_msid_set_grouping(self.handle, 0, None, None))
+            return
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if len(m) != o[-1]:
+            raise ValueError("masses must hold one entry per particle of the grouping.")
+        check(lib().mdx_msid_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+
+    def set_unwrap(self, dims, start=None):
+        """The global unwrap of ``GyrationEngine.set_unwrap``: from frame to frame, starting from the points
+        ``start`` (float64 ``[n_points, 3]``, every chain whole); ``dims=None`` switches it off.  Excludes
+        ``set_whole``."""
+        if dims is None:
+            check(lib().mdx_msid_set_unwrap(self.handle, None, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        if s is None or s.shape != (self.n_points, 3):
+            raise ValueError("start must hold three coordinates per point of the groups.")
+        check(lib().mdx_msid_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+
+    def set_whole(self, dims):
+        """Every chain is made whole in every frame by itself, bond after bond from its first point, by the
+        minimum image of each bond in the box ``dims``; ``dims=None`` switches it off.  Bonds must be shorter than
+        half the shortest box length.  Frames may come in any order.  Excludes ``set_unwrap``."""
+        if dims is None:
+            check(lib().mdx_msid_set_whole(self.handle, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        check(lib().mdx_msid_set_whole(self.handle, _ptr(d)))
+
+    def reserve(self, n_frames):
+        """Room for ``n_frames`` frames in all, allocated once."""
+        check(lib().mdx_msid_reserve(self.handle, int(n_frames)))
+
+    def result(self):
+        """One float64 array ``[frames seen, 2, N_g - 1]`` per group: ``[:, 0]`` is ``R2(1 ... N_g - 1)``,
+        ``[:, 1]`` is ``C(0 ... N_g - 2)``."""
+        rows = np.zeros((self.stats()["frames"], int(self.row0[-1])), dtype=np.float64)
+        check(lib().mdx_msid_result(self.handle, _ptr(rows)))
+        return [rows[:, lo:lo + 2 * (N - 1)].reshape(len(rows), 2, N - 1).copy()
+                for lo, N in zip(self.row0[:-1], self.n_monomers)]
+
+
 class DipoleEngine(_SlabbedFrameEngine):
     """``mdx_dip_*``: per frame and group the dipole moment ``sum q (r + image L)`` in float64."""
 

@@ -191,6 +191,21 @@ _SIGNATURES = {
     "mdx_rouse_device_result": (c_int, [_vp, POINTER(_vp), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_rouse_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_rouse_enable_timing": (c_int, [_vp, c_int]),
+    # chain internal distances and bond-orientation correlations
+    "mdx_msid_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
+    "mdx_msid_destroy": (c_int, [_vp]),
+    "mdx_msid_reset": (c_int, [_vp]),
+    "mdx_msid_reserve": (c_int, [_vp, c_int64]),
+    "mdx_msid_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
+    "mdx_msid_set_unwrap": (c_int, [_vp, _vp, _vp]),
+    "mdx_msid_set_whole": (c_int, [_vp, _vp]),
+    "mdx_msid_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_msid_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_msid_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_msid_synchronize": (c_int, [_vp]),
+    "mdx_msid_result": (c_int, [_vp, _vp]),
+    "mdx_msid_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
+    "mdx_msid_enable_timing": (c_int, [_vp, c_int]),
     # dipole moments
     "mdx_dip_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
     "mdx_dip_destroy": (c_int, [_vp]),

@@ -8,6 +8,7 @@ from .cluster import Clusters  # noqa: F401
 from .dynamics import (DistinctVanHove, PairResidence, VanHove, calculate_non_gaussian_parameter,  # noqa: F401
                        calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
-from .polymer import EndToEndVector, Gyradius, RouseModes, SingleChainStructureFactor  # noqa: F401
+from .polymer import (EndToEndVector, Gyradius, InternalDistances, RouseModes,  # noqa: F401
+                      SingleChainStructureFactor)
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401
 from .transport import Onsager  # noqa: F401

@@ -31,6 +31,11 @@ chain's centre of mass and mass-weighted second moments in float64; frames shard
 (``mdx_rouse_*``): per frame and chain the device forms ``X_p = sum_n w_pn r_n`` for every requested mode in
 float64 and keeps the amplitudes in HBM, where the correlation engine reads them (``mdx_msd_push_device``);
 the chains of each (group, mode) shard across ranks.
+
+``InternalDistances`` (an extension; the reference has no such analysis) runs on the internal-distance engine
+(``mdx_msid_*``): per frame and group the device sums ``|r_{i+s} - r_i|^2`` and ``b_i . b_{i+s}`` over every pair of
+monomers and of bonds of every chain, in float64 out of LDS; ``whole=True`` makes the chains whole per frame on the
+device, so wrapped trajectories still shard by frame across ranks.
 """
 
 from __future__ import annotations
@@ -143,7 +148,7 @@ class _PolymerAnalysisBase(DynamicAnalysisBase):
         self._verbose = verbose
 
     # ---------------------------------------------------------------- points of whole chains
-    # (shared by the analyses whose engines take every monomer of every chain: Gyradius, RouseModes)
+    # (shared by the analyses whose engines take every monomer of every chain: Gyradius, RouseModes, InternalDistances)
 
     def _setup_points(self) -> None:
         """Chain lengths read from the topology, the group-size and ``unwrap`` checks, and the groups' point
@@ -699,6 +704,146 @@ class RouseModes(EngineFedAnalysis, _PolymerAnalysisBase):
             valid = np.where(acf >= 0)[0]
             self.results.relaxation_times[idx] = calculate_relaxation_time(self.results.times[valid],
                                                                            acf[valid])
+
+
+def calculate_characteristic_ratio(r2: np.ndarray) -> np.ndarray:
+    r"""
+    :math:`C(s)=\langle R^2(s)\rangle/(s\,\langle R^2(1)\rangle)` from the mean-square internal distances
+    ``r2[..., s - 1]``, :math:`s=1,\dots,N-1`; its plateau is the characteristic ratio :math:`C_\infty`.
+    """
+    r2 = np.asarray(r2, dtype=float)
+    return r2 / (np.arange(1, r2.shape[-1] + 1) * r2[..., :1])
+
+
+def calculate_persistence_length(cosines: np.ndarray, bond_length: float, n_fit: int = None) -> float:
+    r"""
+    Persistence length :math:`l_\mathrm p=-b/m` from the bond-orientation correlation ``cosines[s]``,
+    :math:`s=0,1,\dots`, with :math:`m` the least-squares slope through the origin of :math:`\ln C(s)` against
+    :math:`s` over :math:`s=0,\dots,` ``n_fit`` (:math:`C(s)=e^{-sb/l_\mathrm p}`).  ``n_fit`` defaults to the last
+    :math:`s` before :math:`C` first falls to :math:`1/e` or below, at least 1.  A correlation that is not positive
+    inside the window raises ``ValueError``.
+    """
+    c = np.asarray(cosines, dtype=float)
+    if c.ndim != 1 or len(c) < 2:
+        raise ValueError("'cosines' must hold C(s) for s = 0, 1, ...: at least two separations.")
+    if n_fit is None:
+        below = np.flatnonzero(c <= np.exp(-1.0))
+        n_fit = max(1, (below[0] if len(below) else len(c)) - 1)
+    n_fit = int(n_fit)
+    if not 1 <= n_fit < len(c):
+        raise ValueError(f"'n_fit' must satisfy 1 <= n_fit <= {len(c) - 1}.")
+    window = c[:n_fit + 1]
+    if np.any(window <= 0) or not np.all(np.isfinite(window)):
+        raise ValueError("The bond-orientation correlation must be positive inside the fit window.")
+    s = np.arange(n_fit + 1, dtype=float)
+    slope = (s * np.log(window)).sum() / (s * s).sum()
+    return np.inf if slope == 0 else -bond_length / slope
+
+
+class InternalDistances(EngineFedAnalysis, _PolymerAnalysisBase):
+    r"""
+    Mean-square internal distances and bond-orientation correlations of polymer chains (no counterpart in the
+    reference),
+
+    .. math:: \langle R^2(s)\rangle=\frac{1}{M(N-s)}\sum_c\sum_{i=0}^{N-1-s}|\mathbf r_{c,i+s}-\mathbf r_{c,i}|^2,
+              \qquad C(s)=\frac{1}{M(N-1-s)}\sum_c\sum_{i=0}^{N-2-s}\hat{\mathbf b}_{c,i}\cdot\hat{\mathbf b}_{c,i+s},
+
+    with :math:`\hat{\mathbf b}_i` the unit vector of the bond from monomer :math:`i` to :math:`i+1`, per frame and
+    group.  :math:`\langle R^2(s)\rangle/s` against :math:`s` shows whether a melt is equilibrated; from the two
+    follow the characteristic ratio and the persistence length.
+
+    Parameters
+    ----------
+    groups, groupings, n_chains, n_monomers : see ``_PolymerAnalysisBase``; a group holds
+        ``n_chains * n_monomers`` monomers, chain after chain (checks as in ``Gyradius``), ``n_monomers >= 2``
+    unwrap : bool, keyword-only — follow the monomers across the periodic boundaries from frame to frame,
+        starting from chains made whole in the first analysed frame (one rank only)
+    whole : bool, keyword-only — make every chain whole in every frame by itself, on the device: bond after
+        bond from the chain's first monomer, each bond by its minimum image.  **Every bond must be shorter than half
+        the shortest box length.**  Needs a constant orthorhombic box; the frames still shard across ranks.
+        Excludes ``unwrap``.
+    dimensions : array-like (3,), keyword-only, optional — box lengths (Å) for ``whole``; default: the universe's
+    parallel : bool, keyword-only — accepted; the serial result layout is returned
+    comm, device : keyword-only (extension) — frames shard across ranks, one all-reduce at the end
+
+    Results, one entry per group (the chain lengths differ between groups): ``results.separations[g]`` ``[N-1]``
+    (:math:`s=1,\dots,N-1`), ``results.squared_distances[g]`` ``[N_t, N-1]`` (Å², per frame),
+    ``results.bond_cosines[g]`` ``[N_t, N-1]`` (:math:`s=0,\dots,N-2`), ``results.mean_squared_distances[g]`` and
+    ``results.mean_bond_cosines[g]`` ``[N-1]`` (means over the frames), ``results.units``;
+    ``results.characteristic_ratio[g]`` ``[N-1]`` after ``calculate_characteristic_ratio()`` and
+    ``results.persistence_length[g]`` (Å) after ``calculate_persistence_length()``.
+
+    Where the work goes: the internal-distance engine (``mdx_msid_*``) forms the float64 monomer centres, makes
+    the chains whole (or follows them), and sums every pair term of every chain in float64 out of LDS; the host
+    sees ``2 (N - 1)`` numbers per frame and group.  With ``"residues"`` the points are the monomers' centres of
+    mass; a bond of no length has the unit vector 0.  There is no CPU fallback: without a HIP device ``run()``
+    raises ``RuntimeError``.
+    """
+
+    def __init__(self, groups, groupings: Union[str, tuple] = "atoms", n_chains=None,
+                 n_monomers=None, *, unwrap: bool = False, whole: bool = False, dimensions=None,
+                 parallel: bool = False, verbose: bool = True, **kwargs) -> None:
+        super().__init__(groups, groupings, n_chains, n_monomers, unwrap=unwrap, parallel=parallel,
+                         verbose=verbose, **kwargs)
+        if unwrap and whole:
+            raise ValueError("'unwrap' and 'whole' cannot be combined: either follow the monomers from frame to "
+                             "frame or make the chains whole in every frame.")
+        self._setup_points()
+        for i, N_p in enumerate(self._n_monomers):
+            if N_p < 2:
+                raise ValueError(f"Group {i} has chains of {N_p} monomer(s): internal distances need n_monomers "
+                                 ">= 2.")
+        self._whole = bool(whole)
+        self._drop_axis = None
+        self._whole_dimensions = self._box_lengths(dimensions, 0.0, "whole") if whole else None
+
+    # ------------------------------------------------------------------ protocol
+
+    _shard_frames = True        # (unwrap, which makes the frames sequential, runs on one rank)
+
+    def _prepare(self) -> None:
+        self.results.separations = [np.arange(1, N_p) for N_p in self._n_monomers]
+        self.results.units = {"results.squared_distances": "angstrom^2",
+                              "results.mean_squared_distances": "angstrom^2"}
+        sels = [self._selection(g, gr, int(N)) for g, gr, N in zip(self._groups, self._groupings, self._Ns)]
+        engine = _core.InternalDistanceEngine(self._n_chains, self._n_monomers, dev=self._device)
+        if self._whole:
+            engine.set_whole(self._whole_dimensions)
+        self._feed_points(engine, sels)
+        lo, hi = self._frames_mine
+        self._engine.reserve(hi - lo)
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        per_group = self._engine.result()                   # [frames of this rank, 2, N - 1] per group
+        self._engine.close()
+        rows = self._gather_frame_rows(np.concatenate([r.reshape(len(r), -1) for r in per_group], axis=1))
+        row0 = np.concatenate(([0], np.cumsum(2 * (self._n_monomers - 1))))
+        both = [rows[:, lo:lo + 2 * (N_p - 1)].reshape(len(rows), 2, N_p - 1)
+                for lo, N_p in zip(row0[:-1], self._n_monomers)]
+        self.results.squared_distances = [b[:, 0].copy() for b in both]
+        self.results.bond_cosines = [b[:, 1].copy() for b in both]
+        self.results.mean_squared_distances = [r2.mean(axis=0) for r2 in self.results.squared_distances]
+        self.results.mean_bond_cosines = [c.mean(axis=0) for c in self.results.bond_cosines]
+
+    def calculate_characteristic_ratio(self) -> None:
+        r""":math:`\langle R^2(s)\rangle/(s\langle R^2(1)\rangle)` of every group, from the means over the frames."""
+        if "mean_squared_distances" not in self.results:
+            raise RuntimeError("Call InternalDistances.run() before "
+                               "InternalDistances.calculate_characteristic_ratio().")
+        self.results.characteristic_ratio = [calculate_characteristic_ratio(r2)
+                                             for r2 in self.results.mean_squared_distances]
+
+    def calculate_persistence_length(self, n_fit: int = None) -> None:
+        r"""Persistence length (Å) of every group from the mean bond-orientation correlation, with the bond length
+        :math:`b=\sqrt{\langle R^2(1)\rangle}` (``calculate_persistence_length``)."""
+        if "mean_bond_cosines" not in self.results:
+            raise RuntimeError("Call InternalDistances.run() before "
+                               "InternalDistances.calculate_persistence_length().")
+        self.results.persistence_length = [
+            calculate_persistence_length(c, np.sqrt(r2[0]), n_fit)
+            for c, r2 in zip(self.results.mean_bond_cosines, self.results.mean_squared_distances)]
+        self.results.units["results.persistence_length"] = "angstrom"
 
 
 class SingleChainStructureFactor(EngineFedAnalysis, DynamicAnalysisBase):
