@@ -252,6 +252,18 @@ int mdx_sq_result(mdx_sq_t h, double *ssf);
 int mdx_sq_allreduce(mdx_sq_t h, mdx_comm_t comm);
 int mdx_sq_stats(mdx_sq_t h, int64_t *launches, double *kernel_ms);
 int mdx_sq_enable_timing(mdx_sq_t h, int on);
+/* The launch plan of an engine created with these wavevectors and n_groups groups (the largest of max_group points,
+ * together spanning n_total points) for ONE accumulate call of n_frames frames; chain_length > 0: in the single-chain
+ * mode of mdx_sq_set_chains (n_groups = 1, n_total a multiple of chain_length), else the normal mode.  Touches no
+ * device; honours MDX_SQ_NO_LATTICE, MDX_SQ_NO_COLUMNS and MDX_SQ_NO_QUADS as mdx_sq_create and mdx_sq_set_chains
+ * do.  out: 0 route (0 general sincos, 1 per-wavevector lattice tables, 2 column items, 3 register-blocked quads;
+ * chain mode: 0 sincos or 3 quads), 1 row stride of the regular quad form (0: general items, or no quads),
+ * 2 particles per LDS stage (the table tile of the lattice routes), 3 copies per quad item (1 without quads),
+ * 4 items per block (quad or column items; general and tables: wavevectors), 5 blocks along the wavevectors,
+ * 6 threads per block, 7 particle parts per group (chain mode: parts of whole chains, none empty), 8 frames per slab
+ * (the call is cut at 32 768 frames or 512 MiB of partial sums), 9 chain mode: chains per part, else 0. */
+int mdx_sq_plan(const double *wavevectors, int64_t n_q, int n_groups, int64_t max_group, int64_t n_total,
+                int64_t chain_length, int64_t n_frames, int32_t out[10]);
 /* Function-level drop-in for accelerated.delta_fourier_transform_sum_2d_2d
  * (accelerated.py:81-122): out = complex128[n_q] as (re, im) pairs; float64 positions. */
 int mdx_fourier_sum(int dev, const double *wavevectors, int64_t n_q, const double *positions,

@@ -353,6 +353,23 @@ class SqEngine(_Engine):
         if timing:
             check(lib().mdx_sq_enable_timing(h, 1))
 
+    PLAN_FIELDS = ("route", "regular_stride", "tile", "n_sub", "items_per_block", "blocks", "threads", "n_split",
+                   "slab_frames", "chains_per_part")
+    ROUTES = ("general", "tables", "columns", "quads")
+
+    @staticmethod
+    def plan(wavevectors, group_sizes, n_frames, chain_length=0):
+        """``mdx_sq_plan``: the kernels an engine built from these arguments launches for ONE accumulate call of
+        ``n_frames`` frames, as a dict of ``PLAN_FIELDS`` — ``route`` indexes ``ROUTES`` (in the single-chain mode,
+        ``chain_length > 0``: ``general`` is the sincos kernel, ``quads`` the quad kernel).  Needs no device; reads
+        ``MDX_SQ_NO_LATTICE`` / ``MDX_SQ_NO_COLUMNS`` / ``MDX_SQ_NO_QUADS`` as the constructor does."""
+        q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)
+        sizes = [int(s) for s in group_sizes]
+        out = np.zeros(10, dtype=np.int32)
+        check(lib().mdx_sq_plan(_ptr(q), q.shape[0], len(sizes), max(sizes), sum(sizes), int(chain_length),
+                                int(n_frames), _ptr(out)))
+        return dict(zip(SqEngine.PLAN_FIELDS, (int(v) for v in out)))
+
     _set_grouping = "mdx_sq_set_grouping"
 
     def set_grouping(self, offsets, masses):

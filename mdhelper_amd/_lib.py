@@ -90,6 +90,7 @@ _SIGNATURES = {
     "mdx_sq_allreduce": (c_int, [_vp, _vp]),
     "mdx_sq_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double)]),
     "mdx_sq_enable_timing": (c_int, [_vp, c_int]),
+    "mdx_sq_plan": (c_int, [_vp, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, _vp]),
     "mdx_fourier_sum": (c_int, [c_int, _vp, c_int64, _vp, c_int64, _vp]),
     # intermediate scattering function
     "mdx_isf_create": (c_int, [POINTER(_vp), c_int, _vp, c_int64, _vp, c_int, _vp, c_int, c_int, c_int]),

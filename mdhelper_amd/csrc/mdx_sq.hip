@@ -221,6 +221,111 @@ __global__ void inner_kernel(const double *__restrict__ q, int64_t n_q, const do
 
 }  // namespace
 
+// ---------------------------------------------------------------------------------------
+// Host planning, shared by the engine and by mdx_sq_plan (which touches no device).
+
+// The density kernel a wavevector set goes through in the normal mode: general sincos, per-wavevector lattice tables,
+// column items or register-blocked quads.  MDX_SQ_NO_LATTICE switches the three lattice forms off, MDX_SQ_NO_COLUMNS
+// quads and columns, MDX_SQ_NO_QUADS the quads alone.
+struct SqRoute {
+    bool lattice = false, quads = false, columns = false;
+    SqLattice lat{};
+    size_t lat_lds = 0;
+    std::vector<short> trip;
+    SqQuadShape quad{};
+    std::vector<SqQuadItem> qitems;
+    int col_threads = 0;
+    SqLattice col_lat{};
+    size_t col_lds = 0;
+    std::vector<SqColumnItem> items;
+    int kind() const { return quads ? 3 : columns ? 2 : lattice ? 1 : 0; }
+    int threads() const { return quads ? SQ_QUAD_THREADS : columns ? col_threads : SQ_THREADS; }
+    int blocks(int64_t n_q) const
+    {
+        return quads     ? quad.blocks()
+               : columns ? (int)ceil_div((int)items.size(), col_threads)
+                         : (int)ceil_div(n_q, SQ_QPB);
+    }
+};
+
+static void sq_plan_route(const double *wavevectors, int64_t n_q, SqRoute &r)
+{
+    r.lattice = sq_detect_lattice(wavevectors, n_q, r.lat, r.trip);
+    if (!r.lattice)
+        return;
+    r.lat_lds = size_t(16) * r.lat.tile * (r.lat.R[0] + r.lat.R[1] + r.lat.R[2]);
+    r.quads = !getenv("MDX_SQ_NO_COLUMNS") && !getenv("MDX_SQ_NO_QUADS") &&
+              sq_quad_plan(r.trip, n_q, r.lat, r.qitems, r.quad);
+    if (!r.quads && !getenv("MDX_SQ_NO_COLUMNS") && sq_build_columns(r.trip, n_q, r.lat, r.items)) {
+        const int n_items = (int)r.items.size();
+        const int waves = (int)std::min<int64_t>(4, ceil_div(n_items, 64));
+        // tables sized for ~24 waves per CU: 150 KB / (24 / waves) per block
+        const int total_r = r.lat.R[0] + r.lat.R[1] + r.lat.R[2];
+        const size_t budget = size_t(150) * 1024 * waves / 24;
+        const int tile = (int)std::min<size_t>(64, budget / (size_t(16) * total_r));
+        if (tile >= 4) {
+            r.col_threads = 64 * waves;
+            r.col_lat = r.lat;
+            r.col_lat.tile = tile;
+            r.col_lds = size_t(16) * tile * total_r;
+            r.columns = true;
+        }
+    }
+}
+
+// The chain kernel's plan: quad items with one copy each when the wavevectors form a lattice the quad planner takes
+// (and neither MDX_SQ_NO_QUADS nor MDX_SQ_NO_COLUMNS is set), else the plain sincos kernel.
+struct SqChainRoute {
+    bool quads = false;
+    SqQuadShape quad{};
+    std::vector<SqQuadItem> items;
+    int blocks(int64_t n_q) const { return quads ? quad.blocks() : (int)ceil_div(n_q, SQ_QPB); }
+    int64_t cols(int64_t n_q) const { return quads ? int64_t(SQ_QCOLS * SQ_ZPT) * quad.n_items : n_q; }
+};
+
+static void sq_plan_chain_route(const double *wavevectors, int64_t n_q, SqChainRoute &r)
+{
+    SqLattice lat{};
+    std::vector<short> trip;
+    r.quads = !getenv("MDX_SQ_NO_COLUMNS") && !getenv("MDX_SQ_NO_QUADS") &&
+              sq_detect_lattice(wavevectors, n_q, lat, trip) &&
+              sq_quad_plan(trip, n_q, lat, r.items, r.quad, true, 1) && r.quad.n_sub == 1;
+}
+
+// Particle parts of a group: the particles are split when frames x q-blocks x groups alone would not fill 256 CUs,
+// counted in waves (256 CUs x 4 SIMDs x ~8 resident waves), down to parts of two LDS stages
+static int sq_points_split(int qblocks, int block_threads, int n_groups, int64_t n_frames, int64_t max_group)
+{
+    const int block_waves = block_threads / 64;
+    constexpr int64_t want_waves = 4096;
+    int n_split = 1;
+    while (int64_t(qblocks) * block_waves * n_groups * n_split * std::min<int64_t>(n_frames, 4096) < want_waves &&
+           n_split < 64 && max_group / (n_split * 2) >= 2 * SQ_TILE)
+        n_split *= 2;
+    return n_split;
+}
+
+// Chain parts (whole chains) by the rule of sq_points_split; *per: chains per part, no part empty
+static int sq_chains_split(int qblocks, int64_t n_frames, int64_t n_chains, int64_t n_total, int64_t *per)
+{
+    constexpr int block_waves = SQ_QUAD_THREADS / 64;
+    static_assert(SQ_QUAD_THREADS == SQ_THREADS, "both chain kernels run 256-thread blocks");
+    constexpr int64_t want_waves = 4096;
+    int n_split = 1;
+    while (int64_t(qblocks) * block_waves * n_split * std::min<int64_t>(n_frames, 4096) < want_waves &&
+           n_split < 64 && n_chains >= 2 * int64_t(n_split) && n_total / (n_split * 2) >= 2 * SQ_TILE)
+        n_split *= 2;
+    *per = ceil_div(n_chains, int64_t(n_split));
+    return (int)ceil_div(n_chains, *per);
+}
+
+// Frames per slab of a call of n_frames frames: at most 32 768 frames and 512 MiB of partial sums
+static int64_t sq_slab_frames(int64_t bytes_per_frame, int64_t n_frames)
+{
+    const int64_t slab = std::max<int64_t>(1, (int64_t(512) << 20) / bytes_per_frame);
+    return std::min<int64_t>(std::min<int64_t>(slab, 32768), n_frames);
+}
+
 struct mdx_sq {
     int dev = 0;
     hipStream_t stream = nullptr;
@@ -236,6 +341,7 @@ struct mdx_sq {
     SqLattice lat{};
     size_t lat_lds = 0;
     // column form of the lattice path (mdx_sq_device.hpp): items, block size, its own tile
+    int rho_blocks = 0, rho_threads = 0;   // the density kernel's blocks along the wavevectors and threads per block
     bool quads = false;          // register-blocked columns (sq_rho_quads_kernel)
     int n_qitems = 0, ipb = 1, n_sub = 1;
     SqLattice quad_lat{};
@@ -253,6 +359,8 @@ struct mdx_sq {
     bool fed = false;            // a frame has been accumulated since creation / the last reset
     int64_t chain_len = 0;
     bool chain_planned = false, chain_quads = false;
+    int chain_blocks = 0;        // the chain kernel's blocks along the wavevectors
+    int64_t chain_cols = 0;      // partial sums per frame and chain part
     int chain_items = 0, chain_ipb = 1, chain_regular = 0;
     SqLattice chain_lat{};
     size_t chain_lds = 0;
@@ -285,24 +393,13 @@ static int sq_accumulate_points(mdx_sq *h, const float *d_pos, int64_t n, int64_
     h->fed = true;
     if (h->chain_len > 0)
         return sq_accumulate_chains(h, d_pos, n, n_frames);
-    const int qblocks = h->quads     ? (int)ceil_div(int64_t(h->n_qitems), int64_t(h->ipb))
-                        : h->columns ? (int)ceil_div(h->n_items, h->col_threads)
-                                     : (int)ceil_div(h->n_q, SQ_QPB);
-    // split the particles when frames x q-blocks x groups alone would not fill 256 CUs
+    const int qblocks = h->rho_blocks;
     int64_t max_group = 0;
     for (int g = 0; g < h->n_groups; ++g)
         max_group = std::max(max_group, h->offsets[g + 1] - h->offsets[g]);
-    // ... counted in waves: 256 CUs x 4 SIMDs x ~8 resident waves
-    const int block_waves = (h->quads ? SQ_QUAD_THREADS : h->columns ? h->col_threads : SQ_THREADS) / 64;
-    constexpr int64_t want_waves = 4096;
-    int n_split = 1;
-    while (int64_t(qblocks) * block_waves * h->n_groups * n_split * std::min<int64_t>(n_frames, 4096) <
-               want_waves &&
-           n_split < 64 && max_group / (n_split * 2) >= 2 * SQ_TILE)
-        n_split *= 2;
+    const int n_split = sq_points_split(qblocks, h->rho_threads, h->n_groups, n_frames, max_group);
     const int64_t rho_per_frame = int64_t(h->n_groups) * n_split * h->n_q * 16;
-    int64_t slab = std::max<int64_t>(1, (int64_t(512) << 20) / rho_per_frame);
-    slab = std::min<int64_t>(std::min<int64_t>(slab, 32768), n_frames);
+    const int64_t slab = sq_slab_frames(rho_per_frame, n_frames);
     MDX_TRY(h->d_rho.ensure(size_t(rho_per_frame) * slab));
     MDX_REQUIRE(int64_t(h->n_groups) * n_split <= 65535, "too many groups");
     hipEvent_t ev = h->timer.begin();
@@ -345,22 +442,12 @@ static int sq_accumulate_points(mdx_sq *h, const float *d_pos, int64_t n, int64_
 static int sq_accumulate_chains(mdx_sq *h, const float *d_pos, int64_t n, int64_t n_frames)
 {
     const int64_t n_chains = h->n_total / h->chain_len;
-    const int qblocks = h->chain_quads ? (int)ceil_div(int64_t(h->chain_items), int64_t(h->chain_ipb))
-                                       : (int)ceil_div(h->n_q, SQ_QPB);
-    // split the chains when frames x q-blocks alone would not fill the chip (the rule of sq_accumulate_points)
-    constexpr int block_waves = SQ_QUAD_THREADS / 64;
-    static_assert(SQ_QUAD_THREADS == SQ_THREADS, "both chain kernels run 256-thread blocks");
-    constexpr int64_t want_waves = 4096;
-    int n_split = 1;
-    while (int64_t(qblocks) * block_waves * n_split * std::min<int64_t>(n_frames, 4096) < want_waves &&
-           n_split < 64 && n_chains >= 2 * int64_t(n_split) && h->n_total / (n_split * 2) >= 2 * SQ_TILE)
-        n_split *= 2;
-    const int64_t per = ceil_div(n_chains, int64_t(n_split));   // chains per split
-    n_split = (int)ceil_div(n_chains, per);                     // no empty split
-    const int64_t n_cols = h->chain_quads ? int64_t(SQ_QCOLS * SQ_ZPT) * h->chain_items : h->n_q;
+    const int qblocks = h->chain_blocks;
+    int64_t per = 0;   // chains per split
+    const int n_split = sq_chains_split(qblocks, n_frames, n_chains, h->n_total, &per);
+    const int64_t n_cols = h->chain_cols;
     const int64_t part_per_frame = int64_t(n_split) * n_cols * 8;
-    int64_t slab = std::max<int64_t>(1, (int64_t(512) << 20) / part_per_frame);
-    slab = std::min<int64_t>(std::min<int64_t>(slab, 32768), n_frames);
+    const int64_t slab = sq_slab_frames(part_per_frame, n_frames);
     MDX_TRY(h->d_rho.ensure(size_t(part_per_frame) * slab));
     double *part = h->d_rho.as<double>();
     hipEvent_t ev = h->timer.begin();
@@ -384,19 +471,18 @@ static int sq_accumulate_chains(mdx_sq *h, const float *d_pos, int64_t n, int64_
     return MDX_OK;
 }
 
-// The chain kernel's plan: quad items with one copy each when the wavevectors form a lattice the quad planner takes
-// (and neither MDX_SQ_NO_QUADS nor MDX_SQ_NO_COLUMNS is set), else the plain sincos kernel.
+// Uploads the chain kernel's plan (sq_plan_chain_route)
 static int sq_plan_chains(mdx_sq *h)
 {
     h->chain_quads = false;
-    SqLattice lat{};
-    std::vector<short> trip;
-    std::vector<SqQuadItem> items;
-    SqQuadShape shape;
-    if (getenv("MDX_SQ_NO_COLUMNS") || getenv("MDX_SQ_NO_QUADS") ||
-        !sq_detect_lattice(h->q_host.data(), h->n_q, lat, trip) ||
-        !sq_quad_plan(trip, h->n_q, lat, items, shape, true, 1) || shape.n_sub != 1)
+    SqChainRoute route;
+    sq_plan_chain_route(h->q_host.data(), h->n_q, route);
+    h->chain_blocks = route.blocks(h->n_q);
+    h->chain_cols = route.cols(h->n_q);
+    if (!route.quads)
         return MDX_OK;
+    const std::vector<SqQuadItem> &items = route.items;
+    const SqQuadShape &shape = route.quad;
     const int n_items = shape.n_items;
     std::vector<int> qmap(size_t(SQ_QCOLS) * SQ_ZPT * n_items);
     for (int k = 0; k < n_items; ++k)
@@ -461,12 +547,16 @@ int mdx_sq_create(mdx_sq_t *out, int dev, const double *wavevectors, int64_t n_q
             rc = fail(MDX_ERR_HIP, "upload failed");
             break;
         }
-        std::vector<short> trip;
-        h->lattice = sq_detect_lattice(wavevectors, n_q, h->lat, trip);
+        SqRoute route;
+        sq_plan_route(wavevectors, n_q, route);
+        h->lattice = route.lattice;
+        h->rho_blocks = route.blocks(n_q);
+        h->rho_threads = route.threads();
         if (h->lattice) {
-            h->lat_lds = size_t(16) * h->lat.tile * (h->lat.R[0] + h->lat.R[1] + h->lat.R[2]);
+            h->lat = route.lat;
+            h->lat_lds = route.lat_lds;
             if ((rc = h->d_mtrip.ensure(size_t(8) * n_q)) != MDX_OK) break;
-            if (hipMemcpy(h->d_mtrip.ptr, trip.data(), size_t(8) * n_q, hipMemcpyHostToDevice) !=
+            if (hipMemcpy(h->d_mtrip.ptr, route.trip.data(), size_t(8) * n_q, hipMemcpyHostToDevice) !=
                     hipSuccess ||
                 (h->lat_lds > 48 * 1024 &&
                  hipFuncSetAttribute(reinterpret_cast<const void *>(sq_rho_lattice_kernel),
@@ -475,10 +565,9 @@ int mdx_sq_create(mdx_sq_t *out, int dev, const double *wavevectors, int64_t n_q
                 rc = fail(MDX_ERR_HIP, "lattice table setup failed");
                 break;
             }
-            std::vector<SqQuadItem> qitems;
-            SqQuadShape shape;
-            if (!getenv("MDX_SQ_NO_COLUMNS") && !getenv("MDX_SQ_NO_QUADS") &&
-                sq_quad_plan(trip, n_q, h->lat, qitems, shape)) {
+            if (route.quads) {
+                const SqQuadShape &shape = route.quad;
+                const std::vector<SqQuadItem> &qitems = route.qitems;
                 h->n_qitems = shape.n_items;
                 h->ipb = shape.ipb;
                 h->n_sub = shape.n_sub;
@@ -496,27 +585,19 @@ int mdx_sq_create(mdx_sq_t *out, int dev, const double *wavevectors, int64_t n_q
                 }
                 h->quads = true;
             }
-            std::vector<SqColumnItem> items;
-            if (!h->quads && !getenv("MDX_SQ_NO_COLUMNS") && sq_build_columns(trip, n_q, h->lat, items)) {
+            if (route.columns) {
+                const std::vector<SqColumnItem> &items = route.items;
                 h->n_items = (int)items.size();
-                const int waves = (int)std::min<int64_t>(4, ceil_div(h->n_items, 64));
-                h->col_threads = 64 * waves;
-                // tables sized for ~24 waves per CU: 150 KB / (24 / waves) per block
-                const int total_r = h->lat.R[0] + h->lat.R[1] + h->lat.R[2];
-                const size_t budget = size_t(150) * 1024 * waves / 24;
-                const int tile = (int)std::min<size_t>(64, budget / (size_t(16) * total_r));
-                if (tile >= 4) {
-                    h->col_lat = h->lat;
-                    h->col_lat.tile = tile;
-                    h->col_lds = size_t(16) * tile * total_r;
-                    if ((rc = h->d_items.ensure(sizeof(SqColumnItem) * items.size())) != MDX_OK) break;
-                    if (hipMemcpy(h->d_items.ptr, items.data(), sizeof(SqColumnItem) * items.size(),
-                                  hipMemcpyHostToDevice) != hipSuccess) {
-                        rc = fail(MDX_ERR_HIP, "column table upload failed");
-                        break;
-                    }
-                    h->columns = true;
+                h->col_threads = route.col_threads;
+                h->col_lat = route.col_lat;
+                h->col_lds = route.col_lds;
+                if ((rc = h->d_items.ensure(sizeof(SqColumnItem) * items.size())) != MDX_OK) break;
+                if (hipMemcpy(h->d_items.ptr, items.data(), sizeof(SqColumnItem) * items.size(),
+                              hipMemcpyHostToDevice) != hipSuccess) {
+                    rc = fail(MDX_ERR_HIP, "column table upload failed");
+                    break;
                 }
+                h->columns = true;
             }
         }
     } while (0);
@@ -526,6 +607,48 @@ int mdx_sq_create(mdx_sq_t *out, int dev, const double *wavevectors, int64_t n_q
     }
     *out = h;
     return mdx_sq_reset(h);
+}
+
+// What an engine created with these wavevectors would launch for one call of n_frames frames; touches no device.
+int mdx_sq_plan(const double *wavevectors, int64_t n_q, int n_groups, int64_t max_group, int64_t n_total,
+                int64_t chain_length, int64_t n_frames, int32_t out[10])
+{
+    MDX_REQUIRE(wavevectors && out, "NULL argument");
+    MDX_REQUIRE(n_q >= 1 && n_q < (int64_t(1) << 30), "n_q out of range");
+    MDX_REQUIRE(n_groups >= 1 && n_groups <= 1024, "n_groups out of range");
+    MDX_REQUIRE(max_group >= 0 && n_total >= max_group && n_frames >= 1, "bad size");
+    if (chain_length > 0) {
+        MDX_REQUIRE(n_groups == 1 && n_total >= chain_length && n_total % chain_length == 0,
+                    "%lld points are not a whole number of chains of %lld", (long long)n_total,
+                    (long long)chain_length);
+        SqChainRoute r;
+        sq_plan_chain_route(wavevectors, n_q, r);
+        int64_t per = 0;
+        out[0] = r.quads ? 3 : 0;
+        out[1] = r.quads ? r.quad.regular_stride : 0;
+        out[2] = r.quads ? r.quad.lat.tile : SQ_TILE;
+        out[3] = 1;
+        out[4] = r.quads ? r.quad.ipb : SQ_QPB;
+        out[5] = r.blocks(n_q);
+        out[6] = SQ_QUAD_THREADS;
+        out[7] = sq_chains_split(out[5], n_frames, n_total / chain_length, n_total, &per);
+        out[8] = (int32_t)sq_slab_frames(int64_t(out[7]) * r.cols(n_q) * 8, n_frames);
+        out[9] = (int32_t)std::min<int64_t>(per, INT32_MAX);
+        return MDX_OK;
+    }
+    SqRoute r;
+    sq_plan_route(wavevectors, n_q, r);
+    out[0] = r.kind();
+    out[1] = r.quads ? r.quad.regular_stride : 0;
+    out[2] = r.quads ? r.quad.lat.tile : r.columns ? r.col_lat.tile : r.lattice ? r.lat.tile : SQ_TILE;
+    out[3] = r.quads ? r.quad.n_sub : 1;
+    out[4] = r.quads ? r.quad.ipb : r.columns ? r.col_threads : SQ_QPB;
+    out[5] = r.blocks(n_q);
+    out[6] = r.threads();
+    out[7] = sq_points_split(out[5], out[6], n_groups, n_frames, max_group);
+    out[8] = (int32_t)sq_slab_frames(int64_t(n_groups) * out[7] * n_q * 16, n_frames);
+    out[9] = 0;
+    return MDX_OK;
 }
 
 int mdx_sq_destroy(mdx_sq_t h)

@@ -314,3 +314,77 @@ def isf_definition_ref(frames, group_offsets, pairs, wavevectors, n_lags):
             s_iisf[lag, slot] = float(hi - lo) * (n_frames - lag)
     return {"cisf": cisf.astype(np.float64), "iisf": iisf.astype(np.float64),
             "S_cisf": s_cisf.astype(np.float64), "S_iisf": s_iisf, "phi_max": phi_max}
+
+
+def ssf_definition_ref(frames, group_offsets, pairs, wavevectors, chain_length=0):
+    """
+    Un-normalised ``ssf[p][q]`` of ``SqEngine.result()`` straight from the definition (header comment of
+    csrc/mdx_sq.hip):
+
+        rho_g(q, f) = sum_{j in g} exp(i q . r_j(f))
+        ssf[p] = sum_f |rho_j(f)|^2                                    p = (j, j)
+                 sum_f 2 Re rho_j(f) rho_k(f)^*                        p = (j, k), j != k, in either order
+                 sum_f |sum_g rho_g(f)|^2                              p = (None, None)
+        ssf[0] = sum_f sum_c |rho_c(f)|^2, chain c = points [c L, (c + 1) L)      chain_length = L > 0
+
+    frames : float32[F, n >= group_offsets[-1], 3] (rows beyond the groups' span are ignored); ``pairs``: ANY list
+    of pairs of groups, or ``((None, None),)`` for the total mode (which the chain mode requires, with one group).
+
+    The float32 coordinates are widened exactly; phases, sines, cosines and sums are formed in ``numpy.longdouble``
+    where that is wider than float64 (x86), else in float64 with exactly rounded sums.
+
+    Also returned, for error bounds: ``S[p][q]`` = sum_f (n_j |rho_k| + n_k |rho_j|) with n the group sizes (total
+    mode: 2 N |rho|; chains: sum_f sum_c 2 L |rho_c|) — the first-order effect on ssf of errors of n eps in every
+    rho, whatever the configuration — and ``phi_max``, the largest |q . r| of a particle of a group in any frame.
+    All outputs float64.
+    """
+    x = _wide(np.asarray(frames, dtype=np.float32))
+    q = _wide(np.asarray(wavevectors, dtype=np.float64).reshape(-1, 3))
+    o = [int(v) for v in group_offsets]
+    n_groups, n_q, n_frames = len(o) - 1, len(q), len(x)
+    dtype = x.dtype
+    phi_max = 0.0
+
+    def rho(r):
+        """[F, ..., n, 3] -> cos and sin sums [F, ..., n_q], a slab of frames at a time (bounded memory)."""
+        nonlocal phi_max
+        rc = np.zeros(r.shape[:-2] + (n_q,), dtype=dtype)
+        rs = np.zeros_like(rc)
+        per_frame = max(1, int(np.prod(r.shape[1:-1])) * n_q)
+        step = max(1, (1 << 21) // per_frame)
+        for f0 in range(0, len(r), step):
+            s = r[f0:f0 + step]
+            ph = (q[:, None, 0] * s[..., None, :, 0] + q[:, None, 1] * s[..., None, :, 1]) + q[:, None, 2] * s[..., None, :, 2]
+            if ph.size:
+                phi_max = max(phi_max, float(np.abs(ph).max()))
+            rc[f0:f0 + step] = _sum_rows(np.cos(ph))
+            rs[f0:f0 + step] = _sum_rows(np.sin(ph))
+        return rc, rs
+
+    if chain_length > 0:
+        n_total = o[n_groups]
+        assert n_groups == 1 and pairs[0][0] is None and n_total % chain_length == 0
+        rc, rs = rho(x[:, o[0]:n_total].reshape(n_frames, n_total // chain_length, chain_length, 3))
+        ssf = (rc * rc + rs * rs).sum(axis=(0, 1))[None]
+        scale = (2 * chain_length * np.sqrt(rc * rc + rs * rs)).sum(axis=(0, 1))[None]
+        return {"ssf": ssf.astype(np.float64), "S": scale.astype(np.float64), "phi_max": phi_max}
+
+    rc = np.zeros((n_groups, n_frames, n_q), dtype=dtype)
+    rs = np.zeros((n_groups, n_frames, n_q), dtype=dtype)
+    for g in range(n_groups):
+        if o[g + 1] > o[g]:
+            rc[g], rs[g] = rho(x[:, o[g]:o[g + 1]])
+    sizes = [o[g + 1] - o[g] for g in range(n_groups)]
+    if pairs[0][0] is None:
+        rc, rs = rc.sum(axis=0, keepdims=True), rs.sum(axis=0, keepdims=True)
+        sizes, use = [o[n_groups] - o[0]], [(0, 0)]
+    else:
+        use = [(int(j), int(k)) for j, k in pairs]
+    mod = np.sqrt(rc * rc + rs * rs)
+    ssf = np.zeros((len(use), n_q), dtype=dtype)
+    scale = np.zeros((len(use), n_q), dtype=dtype)
+    for p, (j, k) in enumerate(use):
+        re = rc[j] * rc[k] + rs[j] * rs[k]
+        ssf[p] = (re if j == k else 2 * re).sum(axis=0)
+        scale[p] = (sizes[j] * mod[k] + sizes[k] * mod[j]).sum(axis=0)
+    return {"ssf": ssf.astype(np.float64), "S": scale.astype(np.float64), "phi_max": phi_max}

@@ -476,8 +476,9 @@ def test_sq_lattice_and_general_paths_agree(monkeypatch):
     sizes = [1800, 1200]
     slices = [slice(0, 1800), slice(1800, 3000)]
     pairs = of.ssf_pairs(2, "partial")
-    for q in (q_lat, q_gen):
+    for q, route in ((q_lat, "tables"), (q_gen, "general")):      # 300 scattered triples: neither item form takes them
         want = sum(of.ssf_frame_ref(q, pos[f].astype(np.float64), slices, pairs, "partial") for f in range(2))
+        assert _core.SqEngine.ROUTES[_core.SqEngine.plan(q, sizes, 2)["route"]] == route
         eng = _core.SqEngine(q, sizes, pairs)
         eng.accumulate(pos)
         got = eng.result()
@@ -489,6 +490,7 @@ def test_sq_lattice_and_general_paths_agree(monkeypatch):
     fast = eng.result()
     eng.close()
     monkeypatch.setenv("MDX_SQ_NO_LATTICE", "1")
+    assert _core.SqEngine.plan(q_lat, sizes, 2)["route"] == 0
     eng = _core.SqEngine(q_lat, sizes, pairs)
     eng.accumulate(pos)
     slow = eng.result()
@@ -499,6 +501,8 @@ def test_sq_lattice_and_general_paths_agree(monkeypatch):
     L = 30.0
     p = (rng.random((1, 500, 3)) * L).astype(np.float32)
     q = of.grid_wavevectors([L, L, L], 32)
+    plan = _core.SqEngine.plan(q, [500], 1)
+    assert (plan["route"], plan["regular_stride"], plan["n_sub"]) == (3, 17, 1)      # regular quads, one copy per item
     eng = _core.SqEngine(q, [500], ((None, None),))
     eng.accumulate(p)
     got = eng.result()[0]
@@ -731,7 +735,9 @@ def test_isf_lattice_tables_equal_general_sincos_path(mode, monkeypatch):
 def test_sq_column_form_equals_lattice_and_general_kernels(monkeypatch):
     """Grid wavevector sets through the four S(q) kernels: register-blocked columns (default),
     column form (MDX_SQ_NO_QUADS), per-q lattice tables (MDX_SQ_NO_COLUMNS) and general fp64
-    sincos (MDX_SQ_NO_LATTICE)."""
+    sincos (MDX_SQ_NO_LATTICE) — where the planner takes the set: every run first asserts through
+    SqEngine.plan the kernel it is labelled with (``routes``: a set the quad planner or sq_build_columns declines
+    runs the next form down, and the label says so)."""
     rng = np.random.default_rng(81)
     F, sizes, L = 5, (1700, 1301), np.array([31.0, 29.5, 33.25])
     N = sum(sizes)
@@ -743,10 +749,17 @@ def test_sq_column_form_equals_lattice_and_general_kernels(monkeypatch):
 
     grid = grid_of(-3, 4)
     big = grid_of(-6, 7)
+    four = ("quads", "columns", "tables", "general")       # the kernel under: no switch, NO_QUADS, NO_COLUMNS, NO_LATTICE
+    routes = {"21 x 21 x 9 grid (56 % of the quad accumulators: columns, 882 items in several blocks)":
+                  ("columns", "columns", "tables", "general"),
+              "grid from m = 2 (no m = 1: the lattice detector declines, general kernel throughout)": ("general",) * 4,
+              "sphere |q| < 0.5 (both item builders decline: tables)": ("tables", "tables", "tables", "general"),
+              "sphere of the 13^3 grid (the quad planner declines: columns)": ("columns", "columns", "tables", "general"),
+              "ragged columns (the quad planner declines: columns)": ("columns", "columns", "tables", "general")}
     sets = {"full 7^3 grid": grid,
             "positive octant 8^3 (one item copy per 16 threads)": grid_of(0, 8),
             "13^3 grid (two m_z chunks, 86 items)": big,
-            "21 x 21 x 9 grid (more than 256 items: several blocks)":
+            "21 x 21 x 9 grid (56 % of the quad accumulators: columns, 882 items in several blocks)":
                 np.stack(np.meshgrid(2 * np.pi * np.arange(-10, 11) / L[0], 2 * np.pi * np.arange(-10, 11) / L[1],
                                      2 * np.pi * np.arange(0, 9) / L[2], indexing="ij"), -1).reshape(-1, 3),
             # the reference's grids and their q_max subsets (m >= 0: structure.py:1376-1381, 1412-1414): regular quad
@@ -755,23 +768,25 @@ def test_sq_column_form_equals_lattice_and_general_kernels(monkeypatch):
             "octant sphere of the 12^3 grid (q_max)": (lambda g: g[np.linalg.norm(g, axis=1) <= 2.2])(grid_of(0, 12)),
             "octant sphere of the 20^3 grid (several blocks)":
                 (lambda g: g[np.linalg.norm(g, axis=1) <= 3.4])(grid_of(0, 20)),
-            "grid from m = 2 (tables start at m = 0)": grid_of(2, 9),
+            "grid from m = 2 (no m = 1: the lattice detector declines, general kernel throughout)": grid_of(2, 9),
             "5 x 9 x 17 grid (95 items, unequal axes)":
                 np.stack(np.meshgrid(2 * np.pi * np.arange(0, 5) / L[0], 2 * np.pi * np.arange(0, 9) / L[1],
                                      2 * np.pi * np.arange(0, 17) / L[2], indexing="ij"), -1).reshape(-1, 3),
-            "sphere |q| < 0.5": grid[np.linalg.norm(grid, axis=1) < 0.5],
-            "sphere of the 13^3 grid": big[np.linalg.norm(big, axis=1) < 1.1],
-            "ragged columns": grid[rng.random(len(grid)) < 0.6]}
+            "sphere |q| < 0.5 (both item builders decline: tables)": grid[np.linalg.norm(grid, axis=1) < 0.5],
+            "sphere of the 13^3 grid (the quad planner declines: columns)": big[np.linalg.norm(big, axis=1) < 1.1],
+            "ragged columns (the quad planner declines: columns)": grid[rng.random(len(grid)) < 0.6]}
     pairs = of.ssf_pairs(2, "partial")
     envs = ("MDX_SQ_NO_QUADS", "MDX_SQ_NO_COLUMNS", "MDX_SQ_NO_LATTICE")
     for name, q in sets.items():
         out = {}
-        for kind, env in (("quads", {}), ("columns", {"MDX_SQ_NO_QUADS": "1"}),
-                          ("lattice", {"MDX_SQ_NO_COLUMNS": "1"}), ("general", {"MDX_SQ_NO_LATTICE": "1"})):
+        for (kind, env), route in zip((("quads", {}), ("columns", {"MDX_SQ_NO_QUADS": "1"}),
+                                       ("lattice", {"MDX_SQ_NO_COLUMNS": "1"}), ("general", {"MDX_SQ_NO_LATTICE": "1"})),
+                                      routes.get(name, four)):
             for k in envs:
                 monkeypatch.delenv(k, raising=False)
             for k, v in env.items():
                 monkeypatch.setenv(k, v)
+            assert _core.SqEngine.ROUTES[_core.SqEngine.plan(q, sizes, F)["route"]] == route, (name, kind)
             eng = _core.SqEngine(q, sizes, pairs)
             eng.accumulate(pos)
             out[kind] = eng.result()
@@ -787,6 +802,7 @@ def test_sq_column_form_equals_lattice_and_general_kernels(monkeypatch):
     # groups smaller than one table tile, and a single particle
     for tiny in ((3, 1), (50, 17)):
         n = sum(tiny)
+        assert _core.SqEngine.plan(grid, tiny, F)["route"] == 3
         eng = _core.SqEngine(grid, tiny, pairs)
         eng.accumulate(pos[:, :n])
         got = eng.result()

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import mdhelper_amd
+from mdhelper_amd import _core
 from mdhelper_amd.analysis import SingleChainStructureFactor
 
 sys.path.insert(0, str(pathlib.Path(__file__).parent))
@@ -197,8 +198,11 @@ def test_quad_and_plain_kernels_agree(monkeypatch, n_points):
     dims = (15.0, 15.0, 15.0)
     u = mdhelper_amd.ArrayUniverse(_melt(9, 37, 3, dims, seed=14), [*dims, 90, 90, 90])
     kw = dict(n_points=n_points, n_chains=9, n_monomers=37)
+    plan = lambda: _core.SqEngine.plan(_grid(dims, n_points), (9 * 37,), 3, 37)["route"]      # noqa: E731
+    assert plan() == 3                                  # sq_chain_quads_kernel
     quad = SingleChainStructureFactor(u.atoms, **kw).run()
     monkeypatch.setenv("MDX_SQ_NO_QUADS", "1")
+    assert plan() == 0                                  # sq_chain_sincos_kernel
     plain = SingleChainStructureFactor(u.atoms, **kw).run()
     np.testing.assert_allclose(quad.results.scsf, plain.results.scsf, rtol=1e-10, atol=0)
 
