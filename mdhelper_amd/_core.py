@@ -574,6 +574,31 @@ class _FrameEngine(_Engine):
     def reset(self):
         check(self._fn("reset")(self.handle))
 
+    def _set_grouping(self, name, offsets, masses):
+        """``mdx_X_<name>(handle, n_groups, offsets, masses)``; ``offsets=None`` removes the grouping."""
+        if offsets is None:
+            check(self._fn(name)(self.handle, 0, None, None))
+            return
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        m = np.ascontiguousarray(masses, dtype=np.float64)
+        if len(m) != o[-1]:
+            raise ValueError("masses must hold one entry per particle of the grouping.")
+        check(self._fn(name)(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+
+    def _set_unwrap(self, name, dims, start):
+        """``mdx_X_<name>(handle, dims, start)`` with ``start`` float64 ``[n_points, 3]``; ``dims=None`` switches the
+        unwrap off."""
+        if dims is None:
+            check(self._fn(name)(self.handle, None, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        if s is None or s.shape != (self.n_points, 3):
+            raise ValueError("start must hold three coordinates per point of the groups.")
+        check(self._fn(name)(self.handle, _ptr(d), _ptr(s)))
+
     def stats(self):
         keys = ("launches", "kernel_ms", "frames") + tuple(key for key, _ in self._stats_extra)
         out = [c_int64(), c_double(), c_int64()] + [ctype() for _, ctype in self._stats_extra]
@@ -620,14 +645,7 @@ class ProfileEngine(_FrameEngine):
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of molecules ``[offsets[m], offsets[m+1])`` — one per point of the
         groups — whose float64 centres of mass are binned; ``offsets=None`` removes the grouping."""
-        if offsets is None:
-            check(lib().mdx_prof_set_grouping(self.handle, 0, None, None))
-            return
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        m = np.ascontiguousarray(masses, dtype=np.float64)
-        if len(m) != o[-1]:
-            raise ValueError("masses must hold one entry per particle of the grouping.")
-        check(lib().mdx_prof_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+        self._set_grouping("set_grouping", offsets, masses)
 
     def set_recenter(self, group, masses=None, target=None):
         """Every frame is shifted so that the mass-weighted centre of the globally unwrapped points of
@@ -683,29 +701,13 @@ class GyrationEngine(_FrameEngine):
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
         groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
-        if offsets is None:
-            check(lib().mdx_gyr_set_grouping(self.handle, 0, None, None))
-            return
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        m = np.ascontiguousarray(masses, dtype=np.float64)
-        if len(m) != o[-1]:
-            raise ValueError("masses must hold one entry per particle of the grouping.")
-        check(lib().mdx_gyr_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+        self._set_grouping("set_grouping", offsets, masses)
 
     def set_unwrap(self, dims, start=None):
         """The reference's global unwrap from frame to frame, starting from the points ``start``
         (float64 ``[n_points, 3]``, every chain whole); ``dims=None`` switches it off.  Frames must then be
         fed in analysis order."""
-        if dims is None:
-            check(lib().mdx_gyr_set_unwrap(self.handle, None, None))
-            return
-        d = np.ascontiguousarray(dims, dtype=np.float64)
-        if d.shape != (3,):
-            raise ValueError("dims must hold the three box lengths.")
-        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
-        if s is None or s.shape != (self.n_points, 3):
-            raise ValueError("start must hold three coordinates per point of the groups.")
-        check(lib().mdx_gyr_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+        self._set_unwrap("set_unwrap", dims, start)
 
     def result(self):
         """float64 ``[G, frames seen, 4]``: ``Rg, Rg_x, Rg_y, Rg_z`` averaged over the chains of each group."""
@@ -747,28 +749,12 @@ class ChainProjectionEngine(_FrameEngine):
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
         groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
-        if offsets is None:
-            check(lib().mdx_rouse_set_grouping(self.handle, 0, None, None))
-            return
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        m = np.ascontiguousarray(masses, dtype=np.float64)
-        if len(m) != o[-1]:
-            raise ValueError("masses must hold one entry per particle of the grouping.")
-        check(lib().mdx_rouse_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+        self._set_grouping("set_grouping", offsets, masses)
 
     def set_unwrap(self, dims, start=None):
         """The global unwrap of ``GyrationEngine.set_unwrap``: from frame to frame, starting from the points
         ``start`` (float64 ``[n_points, 3]``, every chain whole); ``dims=None`` switches it off."""
-        if dims is None:
-            check(lib().mdx_rouse_set_unwrap(self.handle, None, None))
-            return
-        d = np.ascontiguousarray(dims, dtype=np.float64)
-        if d.shape != (3,):
-            raise ValueError("dims must hold the three box lengths.")
-        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
-        if s is None or s.shape != (self.n_points, 3):
-            raise ValueError("start must hold three coordinates per point of the groups.")
-        check(lib().mdx_rouse_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+        self._set_unwrap("set_unwrap", dims, start)
 
     def reserve(self, n_frames):
         """Room for ``n_frames`` frames in all, allocated once."""
@@ -812,29 +798,13 @@ class InternalDistanceEngine(_FrameEngine):
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
         groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
-        if offsets is None:
-            check(lib().mdx_msid_set_grouping(self.handle, 0, None, None))
-            return
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        m = np.ascontiguousarray(masses, dtype=np.float64)
-        if len(m) != o[-1]:
-            raise ValueError("masses must hold one entry per particle of the grouping.")
-        check(lib().mdx_msid_set_grouping(self.handle, len(o) - 1, _ptr(o), _ptr(m)))
+        self._set_grouping("set_grouping", offsets, masses)
 
     def set_unwrap(self, dims, start=None):
         """The global unwrap of ``GyrationEngine.set_unwrap``: from frame to frame, starting from the points
         ``start`` (float64 ``[n_points, 3]``, every chain whole); ``dims=None`` switches it off.  Excludes
         ``set_whole``."""
-        if dims is None:
-            check(lib().mdx_msid_set_unwrap(self.handle, None, None))
-            return
-        d = np.ascontiguousarray(dims, dtype=np.float64)
-        if d.shape != (3,):
-            raise ValueError("dims must hold the three box lengths.")
-        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
-        if s is None or s.shape != (self.n_points, 3):
-            raise ValueError("start must hold three coordinates per point of the groups.")
-        check(lib().mdx_msid_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+        self._set_unwrap("set_unwrap", dims, start)
 
     def set_whole(self, dims):
         """Every chain is made whole in every frame by itself, bond after bond from its first point, by the
@@ -884,16 +854,7 @@ class DipoleEngine(_SlabbedFrameEngine):
         """The reference's global unwrap from frame to frame, starting from the points ``start``
         (float64 ``[n_points, 3]``, every molecule whole); ``dims=None`` switches it off.  Frames must then be
         fed in analysis order."""
-        if dims is None:
-            check(lib().mdx_dip_set_unwrap(self.handle, None, None))
-            return
-        d = np.ascontiguousarray(dims, dtype=np.float64)
-        if d.shape != (3,):
-            raise ValueError("dims must hold the three box lengths.")
-        s = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
-        if s is None or s.shape != (self.n_points, 3):
-            raise ValueError("start must hold three coordinates per point of the groups.")
-        check(lib().mdx_dip_set_unwrap(self.handle, _ptr(d), _ptr(s)))
+        self._set_unwrap("set_unwrap", dims, start)
 
     def result(self):
         """float64 ``[G, frames seen, 3]``: the dipole moment of every group in every frame."""

@@ -14,6 +14,7 @@
 #include "mdx_common.hpp"
 #include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_pairs_host.hpp"
 #include "mdx_angle_device.hpp"
 
 #include <algorithm>
@@ -32,54 +33,46 @@ constexpr int64_t ANG_MAX_BINS = int64_t(1) << 20;
 
 struct mdx_ang : FrameEngine {
     bool ready = false;                 // the device side exists
-    int n_species = 1, keep = 7, max_nb = 32;
+    int n_species = 1, keep = 7;
     bool same = false, uniform = true, lds_hist = true;
     int64_t n0 = 0, n_lig = 0, n_rows = 0, n_bins = 0;
-    int max_row = 0;                    // the largest row seen, as of the last look
-    AngBox box;
+    PairBox box;
+    CappedLists lists;                  // the centres' neighbour lists of a slab
     AngGroups groups;
     std::vector<double> inner;          // thresholds[1 ... n_bins - 1]
-    // d_counts: uint64 counts [P][n_bins], degenerate [P], coordination [G][max_nb + 1]; d_ctl: int32 max_row
-    DeviceBuffer d_inner, d_counts, d_ctl, d_slab, d_len, d_list;
+    // d_counts: uint64 counts [P][n_bins], degenerate [P], coordination [G][max_nb + 1]
+    DeviceBuffer d_inner, d_counts, d_slab;
 
     int64_t pairs() const { return int64_t(n_species) * (n_species + 1) / 2; }
-    int64_t words() const { return pairs() * n_bins + pairs() + int64_t(n_species) * (max_nb + 1); }
+    int64_t words() const { return pairs() * n_bins + pairs() + int64_t(n_species) * (lists.max_nb + 1); }
 };
 
 // bytes a frame of a slab takes: its gathered rows, its lists and lengths
 static int64_t ang_frame_bytes(const mdx_ang *h)
 {
-    return 12 * h->n_rows + (int64_t(h->max_nb) + 1) * 4 * h->n0;
+    return 12 * h->n_rows + (int64_t(h->lists.max_nb) + 1) * 4 * h->n0;
 }
 
 static int64_t ang_slab(const mdx_ang *h)
 {
-    if (h->slab_frames > 0)
-        return h->slab_frames;
-    return std::min(ANG_SLAB_MAX, std::max<int64_t>(1, ANG_SLAB_BYTES / ang_frame_bytes(h)));
+    return pair_slab_frames(h->slab_frames, ANG_SLAB_BYTES, ang_frame_bytes(h));
 }
 
 static int ang_zero(mdx_ang *h)
 {
     MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->words(), h->stream));
-    MDX_HIP(hipMemsetAsync(h->d_ctl.ptr, 0, 4, h->stream));
-    h->max_row = 0;
-    return MDX_OK;
+    return h->lists.zero(h->stream);
 }
 
 // the device side of the handle: stream, thresholds and counters
 static int ang_ensure_device(mdx_ang *h)
 {
-    MDX_TRY(set_device(h->dev));
     if (h->ready)
-        return MDX_OK;
-    if (!h->stream) {
-        MDX_TRY(stream_acquire(&h->stream));
-        h->timer.stream = h->stream;
-    }
+        return set_device(h->dev);
+    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_inner.ensure(size_t(8) * std::max<size_t>(h->inner.size(), 1)));
     MDX_TRY(h->d_counts.ensure(size_t(8) * h->words()));
-    MDX_TRY(h->d_ctl.ensure(4));
+    MDX_TRY(h->lists.ensure_ctl());
     if (!h->inner.empty())
         MDX_HIP(hipMemcpy(h->d_inner.ptr, h->inner.data(), size_t(8) * h->inner.size(), hipMemcpyHostToDevice));
     MDX_TRY(ang_zero(h));
@@ -97,28 +90,16 @@ static int ang_ensure_slab(mdx_ang *h)
     const int64_t slab = ang_slab(h);
     MDX_REQUIRE(slab < (int64_t(1) << 40) / ang_frame_bytes(h),
                 "a slab of %lld frames of %lld rows with %d neighbors each is too large", (long long)slab,
-                (long long)h->n_rows, h->max_nb);
+                (long long)h->n_rows, h->lists.max_nb);
     MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * slab));
-    MDX_TRY(h->d_len.ensure(size_t(4) * h->n0 * slab));
-    MDX_TRY(h->d_list.ensure(size_t(4) * h->max_nb * h->n0 * slab));
-    return MDX_OK;
-}
-
-static int ang_refuse_rows(const mdx_ang *h)
-{
-    MDX_REQUIRE(h->max_row <= h->max_nb,
-                "a center held %d neighbors in one frame, more than max_neighbors = %d: raise max_neighbors or lower "
-                "the cutoff (reset starts over)", h->max_row, h->max_nb);
+    MDX_TRY(h->lists.ensure(h->n0, slab));
     return MDX_OK;
 }
 
 // With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
 static int ang_check_rows(mdx_ang *h)
 {
-    int32_t row = 0;
-    MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
-    h->max_row = row;
-    return ang_refuse_rows(h);
+    return h->lists.check("center", "neighbors");
 }
 
 // n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
@@ -131,6 +112,8 @@ static int ang_accumulate_rows(mdx_ang *h, const float *d_pos, int64_t src_rows,
                 (long long)h->n_rows);
     MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     const int n = (int)h->n_rows, n0 = (int)h->n0, n_lig = (int)h->n_lig, off = h->same ? 0 : n0;
+    const int max_nb = h->lists.max_nb;
+    int *len = h->lists.d_len.as<int>(), *list = h->lists.d_list.as<int>();
     const int64_t slab = ang_slab(h);       // what ang_ensure_slab sized the buffers for
     const int64_t n_jchunks = ceil_div(h->n_lig, ANG_JCHUNK);
     const int64_t blocks = ceil_div(h->n0, ANG_TILE) * n_jchunks;
@@ -147,20 +130,17 @@ static int ang_accumulate_rows(mdx_ang *h, const float *d_pos, int64_t src_rows,
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         hipEvent_t ev = h->timer.begin();
-        hipLaunchKernelGGL(ang_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
-                           0, h->stream, pos, src_rows, d_index, n, h->d_slab.as<float>());
-        MDX_HIP(hipMemsetAsync(h->d_len.ptr, 0, size_t(4) * n0 * nf, h->stream));
+        launch_gather<false>(h->stream, pos, src_rows, d_index, n, nf, h->d_slab.as<float>());
+        MDX_HIP(hipMemsetAsync(len, 0, size_t(4) * n0 * nf, h->stream));
         hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(ANG_THREADS), 0, h->stream,
                            h->d_slab.as<float>(), n, n0, n_lig, off, int(h->same), (int)n_jchunks, h->box, h->keep,
-                           h->groups.rc2[0], h->groups, h->max_nb, h->d_len.as<int>(), h->d_list.as<int>(),
-                           h->d_ctl.as<int>());
+                           h->groups.rc2[0], h->groups, max_nb, len, list, h->lists.d_ctl.as<int>());
         // a block walks at most ANG_BLOCK_TILES tiles: the bound of its uint32 counters (mdx_angle_device.hpp)
         const int64_t n_tiles = c_tiles * nf;
         const int64_t grid = std::max(std::min<int64_t>(n_tiles, ANG_GRID), ceil_div(n_tiles, ANG_BLOCK_TILES));
         hipLaunchKernelGGL(triplet, dim3((unsigned)grid), dim3(ANG_THREADS), 0, h->stream, h->d_slab.as<float>(), n,
-                           n0, off, n_tiles, (int)c_tiles, h->box, h->keep, h->groups, h->n_species, h->max_nb,
-                           h->d_len.as<int>(), h->d_list.as<int>(), h->d_inner.as<double>(), (int)h->n_bins, counts,
-                           degenerate, coordination);
+                           n0, off, n_tiles, (int)c_tiles, h->box, h->keep, h->groups, h->n_species, max_nb, len, list,
+                           h->d_inner.as<double>(), (int)h->n_bins, counts, degenerate, coordination);
         h->frames_seen += nf;
         h->timer.end(ev);
         MDX_HIP(hipGetLastError());
@@ -195,8 +175,6 @@ int mdx_ang_create(mdx_ang_t *out, int dev, int64_t n_centers, int n_species, co
     MDX_REQUIRE(ceil_div(n_centers, ANG_TILE) * ceil_div(n_lig, ANG_JCHUNK) < (int64_t(1) << 31),
                 "%lld centers and %lld ligands are too many pairs for one launch", (long long)n_centers,
                 (long long)n_lig);
-    for (int c = 0; c < 3; ++c)
-        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
     double largest = 0.0;
     bool uniform = true;
     for (int g = 0; g < G; ++g) {
@@ -204,13 +182,9 @@ int mdx_ang_create(mdx_ang_t *out, int dev, int64_t n_centers, int n_species, co
         largest = std::max(largest, cutoff[g]);
         uniform = uniform && cutoff[g] == cutoff[0];
     }
-    double shortest = HUGE_VAL;
-    for (int c = 0; c < 3; ++c)
-        if (!(zero_dims >> c & 1))
-            shortest = std::min(shortest, dims[c]);
-    // beyond half a box length the minimum image is not the nearest image
-    MDX_REQUIRE(largest <= shortest / 2, "cutoff %g reaches beyond half the shortest box length %g", largest,
-                shortest);
+    PairBox box;
+    int keep = 7;
+    MDX_TRY(check_box_cutoff(dims, zero_dims, largest, &box, &keep));
     MDX_REQUIRE(n_bins >= 1 && n_bins <= ANG_MAX_BINS, "n_bins must lie in [1, %lld]", (long long)ANG_MAX_BINS);
     for (int64_t m = 0; m < n_bins; ++m)
         MDX_REQUIRE(thresholds[m] > thresholds[m + 1],
@@ -223,8 +197,9 @@ int mdx_ang_create(mdx_ang_t *out, int dev, int64_t n_centers, int n_species, co
     h->n_rows = n_rows;
     h->n_species = G;
     h->same = same != 0;
-    h->keep = 7 & ~zero_dims;
-    h->max_nb = max_neighbors;
+    h->keep = keep;
+    h->box = box;
+    h->lists.max_nb = max_neighbors;
     h->uniform = uniform;
     h->n_bins = n_bins;
     h->lds_hist = h->pairs() * n_bins <= ANG_HIST_WORDS && n_bins <= ANG_LDS_BINS;
@@ -235,10 +210,6 @@ int mdx_ang_create(mdx_ang_t *out, int dev, int64_t n_centers, int n_species, co
         h->groups.end[g] = g < G ? (int)end : INT_MAX;
         h->groups.rc2[g] = g < G ? cutoff[g] * cutoff[g] : 0.0;
     }
-    for (int c = 0; c < 3; ++c) {
-        h->box.L[c] = dims[c];
-        h->box.inv[c] = 1.0 / dims[c];
-    }
     *out = h;
     return MDX_OK;
 }
@@ -248,7 +219,7 @@ int mdx_ang_destroy(mdx_ang_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_inner, &h->d_counts, &h->d_ctl, &h->d_slab, &h->d_len, &h->d_list});
+        h->release({&h->d_inner, &h->d_counts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len, &h->lists.d_list});
     delete h;
     return MDX_OK;
 }
@@ -257,7 +228,7 @@ int mdx_ang_reset(mdx_ang_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
     h->frames_seen = 0;
-    h->max_row = 0;
+    h->lists.max_row = 0;
     if (!h->ready)
         return MDX_OK;
     MDX_TRY(set_device(h->dev));
@@ -277,36 +248,25 @@ int mdx_ang_set_slab_frames(mdx_ang_t h, int64_t frames)
     return MDX_OK;
 }
 
+// what a route prepares before the first kernel
+static int ang_prepare(mdx_ang *h, int64_t)
+{
+    MDX_TRY(ang_ensure_device(h));
+    return ang_ensure_slab(h);
+}
+
 int mdx_ang_accumulate_device(mdx_ang_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
-    const int64_t n = index ? n_index : n_atoms;
-    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_rows);
-    MDX_TRY(check_particle_index(index, n_index, n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(ang_ensure_device(h));
-    MDX_TRY(ang_ensure_slab(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return ang_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "groups", ang_prepare,
+                                ang_accumulate_rows);
 }
 
 int mdx_ang_accumulate(mdx_ang_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
-    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
-    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_rows);
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(ang_ensure_device(h));
-    MDX_TRY(ang_ensure_slab(h));
-    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return ang_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_host(pos, n, n_frames, h->n_rows, "groups", ang_prepare, ang_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
@@ -315,22 +275,8 @@ int mdx_ang_accumulate_traj(mdx_ang_t h, mdx_traj_t traj, const int64_t *frames,
                             const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
-    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
-    Trajectory *t = mdx_traj_internal(traj);
-    int64_t n = 0;
-    MDX_TRY(traj_selection(t, index, n_index, &n));
-    MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n_rows);
-    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(ang_ensure_device(h));
-    MDX_TRY(ang_ensure_slab(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return ang_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "groups",
+                              ang_prepare, ang_accumulate_rows);
 }
 
 int mdx_ang_synchronize(mdx_ang_t h)
@@ -355,7 +301,7 @@ int mdx_ang_result(mdx_ang_t h, int64_t *counts, int64_t *degenerate, int64_t *c
     const char *src = h->d_counts.as<char>();
     MDX_HIP(hipMemcpy(counts, src, n_counts, hipMemcpyDeviceToHost));
     MDX_HIP(hipMemcpy(degenerate, src + n_counts, n_degenerate, hipMemcpyDeviceToHost));
-    MDX_HIP(hipMemcpy(coordination, src + n_counts + n_degenerate, size_t(8) * h->n_species * (h->max_nb + 1),
+    MDX_HIP(hipMemcpy(coordination, src + n_counts + n_degenerate, size_t(8) * h->n_species * (h->lists.max_nb + 1),
                       hipMemcpyDeviceToHost));
     return MDX_OK;
 }
@@ -367,9 +313,7 @@ int mdx_ang_stats(mdx_ang_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
     int64_t sum = 0;
     if (h->ready) {
-        int32_t row = 0;
-        MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
-        h->max_row = row;
+        MDX_TRY(h->lists.look());
         if (triplets) {
             std::vector<uint64_t> words(size_t(h->pairs() * (h->n_bins + 1)));      // counts, then degenerate
             MDX_HIP(hipMemcpy(words.data(), h->d_counts.ptr, size_t(8) * words.size(), hipMemcpyDeviceToHost));
@@ -379,7 +323,7 @@ int mdx_ang_stats(mdx_ang_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     }
     if (evaluations) *evaluations = h->frames_seen * (h->n0 * h->n_lig - (h->same ? h->n0 : 0));
     if (triplets) *triplets = sum;
-    if (max_row) *max_row = h->max_row;
+    if (max_row) *max_row = h->lists.max_row;
     return MDX_OK;
 }
 

@@ -8,14 +8,8 @@
 // of them, ligand j is row j, and j == i never counts.  Otherwise the centres and all ligand groups are pairwise
 // disjoint sets of atoms.
 //
-// Box and pair arithmetic: those of mdx_residence_device.hpp.  One constant orthorhombic box, lengths L_c;
-// inv_c = 1.0 / L_c is formed once on the host in float64.  Everything is float64, one operation at a time (the unit
-// is built with contraction off); float32 coordinates are widened before any arithmetic.  For centre i and ligand j
-// of frame f:
+// Box and pair arithmetic: those of mdx_pairs_device.hpp, for centre i and ligand j of frame f, with r2_ij its r2:
 //
-//     d_c = x_jc(f) - x_ic(f) ;  s = d_c * inv_c ;  w_c = d_c - L_c * rint(s)       (rint: ties to even, as numpy.rint;
-//                                                                                   w_c = +0.0 for a dropped component)
-//     r2_ij = (w_x*w_x + w_y*w_y) + w_z*w_z
 //     j is a neighbour of i  iff  r2_ij <= rc2[species(j)],  rc2[g] = cutoff[g] * cutoff[g] formed once on the host
 //
 // A NaN r2 is never a neighbour (the comparison fails).
@@ -46,11 +40,9 @@
 //     coordination[g][m]   m = 0 ... max_neighbors: the (frame, centre) cases in which the centre had exactly m
 //                          neighbours of species g, so that sum_m coordination[g][m] == F * n0
 //
-// Capped lists.  A centre holds at most max_neighbors (1 ... 64) neighbours of all species together in one frame.  A
-// row that would hold more is an error, never a silent truncation: the contact kernel stores only into the row's
-// max_neighbors slots but keeps counting, the largest row seen is kept in HBM, and the host refuses to hand out
-// results (MDX_ERR_INVALID_VALUE, naming max_neighbors and the largest row) from the next synchronize / result on
-// until a reset.  Exactly full is no error.
+// Capped lists (mdx_pairs_device.hpp).  A centre holds at most max_neighbors (1 ... 64) neighbours of all species
+// together in one frame; a row that would hold more refuses the results (MDX_ERR_INVALID_VALUE, naming max_neighbors
+// and the largest row).  Exactly full is no error.
 //
 // evaluations is the contract's count F * (n0 * n_lig - (same ? n0 : 0)); triplets = sum counts + sum degenerate.
 //
@@ -61,17 +53,15 @@
 //
 // Shape.  Two phases per slab of frames; a frame never needs another, so there is no history.
 //
-// Phase 1, neighbour lists (the hot path, F * n0 * n_lig evaluations).  ang_prepare_kernel gathers the rows of a slab
-// component-major float32.  ang_contact_kernel has the shape of prs_contact_kernel: grid x = i tiles x j chunks,
-// z = frames; a block holds ANG_TILE centres in registers, one per lane, widened, and walks its chunk of at most
-// ANG_JCHUNK ligands in stages of ANG_STAGE through LDS (widened once when staged; every lane reads the same j at
-// once, a broadcast).  The thread that stages ligand j puts rc2[species(j)] into the fourth word of its stage entry.
+// Phase 1, neighbour lists (the hot path, F * n0 * n_lig evaluations).  gather_kernel gathers the rows of a slab
+// component-major float32.  ang_contact_kernel is the walk of mdx_pairs_device.hpp with z = frames and ANG_JCHUNK
+// ligands per block.  The thread that stages ligand j puts rc2[species(j)] into the fourth word of its stage entry.
 // Ligands arrive group by group, so a stage holds one species where species(first) == species(last): the lane then
 // takes its bound once for the stage, and only a stage that spans two groups reads the bound beside each partner, as
 // clu_contact_kernel does.  UNIFORM (every cutoff is one value): rc2 is a kernel argument.  A neighbour takes
 // slot = atomicAdd(&len[f][i], 1) and is stored at list[f][slot][i] when slot < max_neighbors (slot-major: the angle
 // kernel's lanes read consecutive i); several j chunks append to one row.  Each block adds its largest row to max_row
-// with one atomicMax.
+// with one atomicMax (the max-only block_tally).
 //
 // Phase 2, angles (ang_triplet_kernel).  A centre with m neighbours has m (m - 1) / 2 pairs, 6 ... 28 in a real first
 // shell and 2016 at the cap, so neither a lane nor a wave per centre keeps the lanes busy.  A block walks tiles of
@@ -101,46 +91,27 @@
 // (DESIGN.md §10).
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "mdx_pairs_device.hpp"
 
 namespace mdx_ang_dev {
 
-constexpr int ANG_TILE = 256;                 // centres per block of phase 1, one per lane
-constexpr int ANG_THREADS = ANG_TILE;
-constexpr int ANG_WAVES = ANG_THREADS / 64;
-constexpr int ANG_STAGE = ANG_THREADS;        // ligands per LDS stage, one staged per thread
+using namespace mdx_pairs_dev;
+
+constexpr int ANG_TILE = PAIR_TILE;           // centres per block of phase 1, one per lane
+constexpr int ANG_THREADS = PAIR_THREADS;
+constexpr int ANG_WAVES = PAIR_WAVES;
+constexpr int ANG_STAGE = PAIR_STAGE;         // ligands per LDS stage, one staged per thread
 constexpr int ANG_JCHUNK = 4 * ANG_STAGE;     // ligands per block
-constexpr int ANG_MAX_NEIGHBORS = 64;         // slots of a row at most
+constexpr int ANG_MAX_NEIGHBORS = PAIR_MAX_NEIGHBORS;   // slots of a row at most
 constexpr int ANG_MAX_SPECIES = 4;
 constexpr int ANG_MAX_PAIRS = ANG_MAX_SPECIES * (ANG_MAX_SPECIES + 1) / 2;
-constexpr int64_t ANG_SLAB_MAX = 32768;       // frames per launch, at most (grid z)
+constexpr int64_t ANG_SLAB_MAX = PAIR_SLAB_MAX;         // frames per launch, at most (grid z)
 constexpr int ANG_CTILE = 16;                 // centres per tile of phase 2
 constexpr int ANG_ENTRIES = ANG_CTILE * ANG_MAX_NEIGHBORS;
 constexpr int ANG_HIST_WORDS = 1920;          // uint32 words of a wave's histogram in LDS: P * n_bins at most
 constexpr int ANG_LDS_BINS = 512;             // n_bins at most for thresholds in LDS
 constexpr int64_t ANG_BLOCK_TILES = 65536;    // tiles a block of phase 2 walks in one launch, at most
 constexpr int ANG_GRID = 2048;                // blocks of phase 2 unless ANG_BLOCK_TILES asks for more
-
-// Row index[p] (or p) of n_frames float32 frames of src_rows rows into the slab: slab[(f * 3 + c) * n_rows + p].  One
-// thread per coordinate (t = c * n_rows + p: a wave writes consecutive floats); grid y = frames.
-__global__ __launch_bounds__(256) void ang_prepare_kernel(const float *__restrict__ pos, int64_t src_rows,
-                                                          const int *__restrict__ index, int n_rows,
-                                                          float *__restrict__ slab)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 3 * n_rows)
-        return;
-    const int c = t / n_rows, p = t - c * n_rows;
-    const int64_t r = index ? index[p] : p;
-    const int64_t f = blockIdx.y;
-    slab[(f * 3 + c) * n_rows + p] = pos[(f * src_rows + r) * 3 + c];
-}
-
-struct AngBox {
-    double L[3], inv[3];
-};
 
 // end[g]: one past the last ligand j of species g (INT_MAX for g >= G); rc2[g] = cutoff[g]^2
 struct AngGroups {
@@ -167,51 +138,13 @@ __device__ __forceinline__ int ang_pair(int a, int b, int G)
     return lo * G - lo * (lo - 1) / 2 + (hi - lo);
 }
 
-// w = d - L * rint(d * inv), one operation at a time
-__device__ __forceinline__ double ang_min_image(double d, double L, double inv)
-{
-    return __dsub_rn(d, __dmul_rn(L, rint(__dmul_rn(d, inv))));
-}
-
-// r2 = (wx*wx + wy*wy) + wz*wz
-__device__ __forceinline__ double ang_r2(double wx, double wy, double wz)
-{
-    return __dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz));
-}
-
-// The staged ligands js ... js + nj - 1 against this lane's centre (xi, yi, zi).  LOOKUP: the bound of a partner is
-// the fourth word of its stage entry; else it is `bound` for every partner of the stage.
-template <bool ALL, bool LOOKUP>
-__device__ __forceinline__ void ang_stage_pairs(const double *__restrict__ stage, double bound, int nj, int js,
-                                                int skip, double xi, double yi, double zi, const AngBox &box, int keep,
-                                                int n0, int max_nb, int *__restrict__ my_len,
-                                                int *__restrict__ my_list, unsigned int &row)
-{
-#pragma unroll 4
-    for (int jj = 0; jj < nj; ++jj) {
-        const double dx = __dsub_rn(stage[4 * jj + 0], xi), dy = __dsub_rn(stage[4 * jj + 1], yi),
-                     dz = __dsub_rn(stage[4 * jj + 2], zi);
-        const double wx = ALL || keep & 1 ? ang_min_image(dx, box.L[0], box.inv[0]) : 0.0;
-        const double wy = ALL || keep & 2 ? ang_min_image(dy, box.L[1], box.inv[1]) : 0.0;
-        const double wz = ALL || keep & 4 ? ang_min_image(dz, box.L[2], box.inv[2]) : 0.0;
-        const double r2 = ang_r2(wx, wy, wz);
-        const double rc2 = LOOKUP ? stage[4 * jj + 3] : bound;
-        if (r2 <= rc2 && jj != skip) {
-            const int slot = atomicAdd(my_len, 1);          // other j chunks append to the same row
-            if (slot < max_nb)
-                my_list[int64_t(slot) * n0] = js + jj;
-            row = (unsigned int)slot + 1u > row ? (unsigned int)slot + 1u : row;
-        }
-    }
-}
-
 // The neighbour lists of slab frame blockIdx.z.  n_rows: rows of a slab frame; the n_lig ligands start at row off
 // (0 with same).  keep: bit c set -> component c takes part; ALL: keep == 7, known when compiled.  UNIFORM: every
 // species has the bound rc2; else groups names the species of a ligand and its bound.  len: int32 [slab][n0], zero;
 // list: int32 [slab][max_nb][n0], ligand numbers j.
 template <bool ALL, bool UNIFORM>
 __global__ __launch_bounds__(ANG_THREADS) void ang_contact_kernel(
-    const float *__restrict__ slab, int n_rows, int n0, int n_lig, int off, int same, int n_jchunks, AngBox box,
+    const float *__restrict__ slab, int n_rows, int n0, int n_lig, int off, int same, int n_jchunks, PairBox box,
     int keep, double rc2, AngGroups groups, int max_nb, int *__restrict__ len, int *__restrict__ list,
     int *__restrict__ max_row)
 {
@@ -235,11 +168,8 @@ __global__ __launch_bounds__(ANG_THREADS) void ang_contact_kernel(
         const int nj = j_end - js < ANG_STAGE ? j_end - js : ANG_STAGE;
         __syncthreads();                    // the stage is free
         if ((int)threadIdx.x < nj) {
-            const float *__restrict__ src = b + js + threadIdx.x;
-            stage[4 * threadIdx.x + 0] = (double)src[0];
-            stage[4 * threadIdx.x + 1] = (double)src[n_rows];
-            stage[4 * threadIdx.x + 2] = (double)src[2 * int64_t(n_rows)];
-            if (!UNIFORM)
+            stage_partners(stage, b, n_rows, js);
+            if (!UNIFORM)                   // the bound of a ligand lies beside it
                 stage[4 * threadIdx.x + 3] = ang_bound(groups, js + threadIdx.x);
         }
         __syncthreads();
@@ -247,24 +177,23 @@ __global__ __launch_bounds__(ANG_THREADS) void ang_contact_kernel(
             continue;
         const int skip = same ? i - js : -1;        // the stage entry that is this lane's own row
         // groups are ranges of j: a stage holds one species where its first and last ligand are of one
-        if (UNIFORM || ang_species(groups, js) == ang_species(groups, js + nj - 1))
-            ang_stage_pairs<ALL, false>(stage, UNIFORM ? rc2 : stage[3], nj, js, skip, xi, yi, zi, box, keep, n0,
-                                        max_nb, my_len, my_list, row);
-        else
-            ang_stage_pairs<ALL, true>(stage, 0.0, nj, js, skip, xi, yi, zi, box, keep, n0, max_nb, my_len, my_list,
-                                       row);
-    }
-    // one integer atomic per block for the largest row: max commutes
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned int other = __shfl_down(row, o);
-        row = other > row ? other : row;
+        if (UNIFORM || ang_species(groups, js) == ang_species(groups, js + nj - 1)) {
+            const double bound = UNIFORM ? rc2 : stage[3];
+            stage_pairs<ALL>(stage, nj, js, skip, xi, yi, zi, box, keep,
+                             [&](int, int j, double, double, double, double r2, bool other) {
+                                 if (r2 <= bound && other)
+                                     append_capped(my_len, my_list, n0, max_nb, j, row);
+                             });
+        } else {
+            stage_pairs<ALL>(stage, nj, js, skip, xi, yi, zi, box, keep,
+                             [&](int jj, int j, double, double, double, double r2, bool other) {
+                                 if (r2 <= stage[4 * jj + 3] && other)
+                                     append_capped(my_len, my_list, n0, max_nb, j, row);
+                             });
+        }
     }
     __syncthreads();                        // block_row is zero (no stage at all: the barrier above never ran)
-    if ((threadIdx.x & 63) == 0 && row)
-        atomicMax(&block_row, row);
-    __syncthreads();
-    if (threadIdx.x == 0 && block_row)
-        atomicMax(max_row, (int)block_row);
+    block_tally<false>(0u, row, nullptr, &block_row, nullptr, max_row);
 }
 
 // The pair (a, b), a < b, with q = b (b - 1) / 2 + a.  q < 2016, so the float root is off by one at most.
@@ -284,7 +213,7 @@ __device__ __forceinline__ void ang_unrank(int q, int &a, int &b)
 // counts: uint64 [P][n_bins]; degenerate: uint64 [P]; coordination: uint64 [G][max_nb + 1].
 template <bool ALL, bool LDS_HIST>
 __global__ __launch_bounds__(ANG_THREADS) void ang_triplet_kernel(
-    const float *__restrict__ slab, int n_rows, int n0, int off, int64_t n_tiles, int c_tiles, AngBox box, int keep,
+    const float *__restrict__ slab, int n_rows, int n0, int off, int64_t n_tiles, int c_tiles, PairBox box, int keep,
     AngGroups groups, int G, int max_nb, const int *__restrict__ len, const int *__restrict__ list,
     const double *__restrict__ inner, int n_bins, unsigned long long *__restrict__ counts,
     unsigned long long *__restrict__ degenerate, unsigned long long *__restrict__ coordination)
@@ -354,9 +283,9 @@ __global__ __launch_bounds__(ANG_THREADS) void ang_triplet_kernel(
             const double dx = __dsub_rn((double)src[0], centre[0][c]), dy = __dsub_rn((double)src[n_rows], centre[1][c]),
                          dz = __dsub_rn((double)src[2 * int64_t(n_rows)], centre[2][c]);
             const int at = c * ANG_MAX_NEIGHBORS + s;
-            ent_w[0][at] = ALL || keep & 1 ? ang_min_image(dx, box.L[0], box.inv[0]) : 0.0;
-            ent_w[1][at] = ALL || keep & 2 ? ang_min_image(dy, box.L[1], box.inv[1]) : 0.0;
-            ent_w[2][at] = ALL || keep & 4 ? ang_min_image(dz, box.L[2], box.inv[2]) : 0.0;
+            ent_w[0][at] = ALL || keep & 1 ? min_image(dx, box.L[0], box.inv[0]) : 0.0;
+            ent_w[1][at] = ALL || keep & 2 ? min_image(dy, box.L[1], box.inv[1]) : 0.0;
+            ent_w[2][at] = ALL || keep & 4 ? min_image(dz, box.L[2], box.inv[2]) : 0.0;
             ent_species[at] = (unsigned char)ang_species(groups, j);
         }
         __syncthreads();
@@ -388,7 +317,7 @@ __global__ __launch_bounds__(ANG_THREADS) void ang_triplet_kernel(
             const double ax = ent_w[0][ea], ay = ent_w[1][ea], az = ent_w[2][ea];
             const double bx = ent_w[0][eb], by = ent_w[1][eb], bz = ent_w[2][eb];
             const double dot = __dadd_rn(__dadd_rn(__dmul_rn(ax, bx), __dmul_rn(ay, by)), __dmul_rn(az, bz));
-            const double cosine = __ddiv_rn(dot, __dsqrt_rn(__dmul_rn(ang_r2(ax, ay, az), ang_r2(bx, by, bz))));
+            const double cosine = __ddiv_rn(dot, __dsqrt_rn(__dmul_rn(r2_of(ax, ay, az), r2_of(bx, by, bz))));
             const int p = ang_pair(ent_species[ea], ent_species[eb], G);
             if (cosine != cosine) {
                 atomicAdd(&degen[p], 1u);

@@ -13,6 +13,7 @@
 #include "mdx_common.hpp"
 #include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_pairs_host.hpp"
 #include "mdx_cluster_device.hpp"
 
 #include <algorithm>
@@ -30,57 +31,49 @@ constexpr int CLU_SWEEP_BATCH = 4;                      // sweeps queued between
 
 struct mdx_clu : FrameEngine {
     bool ready = false;                 // the device side exists
-    int n_species = 1, keep = 7, max_nb = 32;
+    int n_species = 1, keep = 7;
     bool uniform = true, keep_labels = false;
     int64_t n = 0;
     int64_t sweeps = 0;
-    int max_row = 0;                    // the largest row seen, as of the last look
-    CluBox box;
+    PairBox box;
+    CappedLists lists;                  // d_ctl: int32 max_row, then the "lowered" words of a batch of sweeps
     double rc2 = 0.0;                   // the one squared cutoff of a uniform table
     double table[CLU_MAX_SPECIES * CLU_MAX_SPECIES];    // rc2 at [8 * b + a], -1.0 where the species never bond
     std::vector<int32_t> species;
     // d_counts: uint64 [1 + G][n + 1], size_counts then species_counts; d_frames: uint64 [frames][CLU_FRAME_WORDS];
-    // d_labels: int32 [frames][n] (keep_labels); d_ctl: int32 max_row, then the "lowered" words of a batch of sweeps
-    DeviceBuffer d_species, d_table, d_counts, d_frames, d_labels, d_ctl, d_slab, d_len, d_list, d_label, d_size;
+    // d_labels: int32 [frames][n] (keep_labels)
+    DeviceBuffer d_species, d_table, d_counts, d_frames, d_labels, d_slab, d_label, d_size;
 };
 
 // bytes a frame of a slab takes: its gathered rows, its lists and lengths, its labels and sizes
 static int64_t clu_frame_bytes(const mdx_clu *h)
 {
-    return 12 * h->n + (int64_t(h->max_nb) + 1) * 4 * h->n + 8 * h->n;
+    return 12 * h->n + (int64_t(h->lists.max_nb) + 1) * 4 * h->n + 8 * h->n;
 }
 
 static int64_t clu_slab(const mdx_clu *h)
 {
-    if (h->slab_frames > 0)
-        return h->slab_frames;
-    return std::min(CLU_SLAB_MAX, std::max<int64_t>(1, CLU_SLAB_BYTES / clu_frame_bytes(h)));
+    return pair_slab_frames(h->slab_frames, CLU_SLAB_BYTES, clu_frame_bytes(h));
 }
 
 static int clu_zero(mdx_clu *h)
 {
     MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * (1 + h->n_species) * (h->n + 1), h->stream));
-    MDX_HIP(hipMemsetAsync(h->d_ctl.ptr, 0, size_t(4) * (1 + CLU_SWEEP_BATCH), h->stream));
     if (h->d_frames.ptr)
         MDX_HIP(hipMemsetAsync(h->d_frames.ptr, 0, h->d_frames.bytes, h->stream));
-    h->max_row = 0;
-    return MDX_OK;
+    return h->lists.zero(h->stream);
 }
 
 // the device side of the handle: stream, tables and counters
 static int clu_ensure_device(mdx_clu *h)
 {
-    MDX_TRY(set_device(h->dev));
     if (h->ready)
-        return MDX_OK;
-    if (!h->stream) {
-        MDX_TRY(stream_acquire(&h->stream));
-        h->timer.stream = h->stream;
-    }
+        return set_device(h->dev);
+    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_species.ensure(size_t(4) * h->n));
     MDX_TRY(h->d_table.ensure(sizeof(h->table)));
     MDX_TRY(h->d_counts.ensure(size_t(8) * (1 + h->n_species) * (h->n + 1)));
-    MDX_TRY(h->d_ctl.ensure(size_t(4) * (1 + CLU_SWEEP_BATCH)));
+    MDX_TRY(h->lists.ensure_ctl());
     MDX_HIP(hipMemcpy(h->d_species.ptr, h->species.data(), size_t(4) * h->n, hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_table.ptr, h->table, sizeof(h->table), hipMemcpyHostToDevice));
     MDX_TRY(clu_zero(h));
@@ -98,47 +91,18 @@ static int clu_ensure_slab(mdx_clu *h)
     const int64_t slab = clu_slab(h);
     MDX_REQUIRE(slab < (int64_t(1) << 40) / clu_frame_bytes(h),
                 "a slab of %lld frames of %lld points with %d neighbors each is too large", (long long)slab,
-                (long long)h->n, h->max_nb);
+                (long long)h->n, h->lists.max_nb);
     MDX_TRY(h->d_slab.ensure(size_t(12) * h->n * slab));
-    MDX_TRY(h->d_len.ensure(size_t(4) * h->n * slab));
-    MDX_TRY(h->d_list.ensure(size_t(4) * h->max_nb * h->n * slab));
+    MDX_TRY(h->lists.ensure(h->n, slab));
     MDX_TRY(h->d_label.ensure(size_t(4) * h->n * slab));
     MDX_TRY(h->d_size.ensure(size_t(4) * h->n * slab));
-    return MDX_OK;
-}
-
-// room in `buf` for `frames` frames of `frame_bytes` each; what the frames seen so far hold moves along
-static int clu_grow(mdx_clu *h, DeviceBuffer &buf, size_t frame_bytes, int64_t frames)
-{
-    if (frame_bytes * frames <= buf.bytes)
-        return MDX_OK;
-    DeviceBuffer grown;
-    MDX_TRY(grown.ensure(std::max(frame_bytes * frames, 2 * buf.bytes)));
-    MDX_HIP(hipMemsetAsync(grown.ptr, 0, grown.bytes, h->stream));
-    if (h->frames_seen > 0)
-        MDX_HIP(hipMemcpyAsync(grown.ptr, buf.ptr, frame_bytes * h->frames_seen, hipMemcpyDeviceToDevice,
-                               h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));       // nobody reads the old block any more
-    buf.recycle();
-    buf = grown;
-    return MDX_OK;
-}
-
-static int clu_refuse_rows(const mdx_clu *h)
-{
-    MDX_REQUIRE(h->max_row <= h->max_nb,
-                "a row held %d bonds in one frame, more than max_neighbors = %d: raise max_neighbors or lower the "
-                "cutoff (reset starts over)", h->max_row, h->max_nb);
     return MDX_OK;
 }
 
 // With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
 static int clu_check_rows(mdx_clu *h)
 {
-    int32_t row = 0;
-    MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
-    h->max_row = row;
-    return clu_refuse_rows(h);
+    return h->lists.check("row", "bonds");
 }
 
 // Labels the nf frames of the slab whose lists are queued on the stream: sweeps in batches, until one lowered
@@ -148,21 +112,22 @@ static int clu_label_slab(mdx_clu *h, int64_t nf, hipEvent_t *ev, bool *labelled
 {
     const int n = (int)h->n;
     const dim3 grid((unsigned)ceil_div(h->n, CLU_ROW_THREADS), (unsigned)nf);
-    int *ctl = h->d_ctl.as<int>();
+    int *ctl = h->lists.d_ctl.as<int>();
     int32_t seen[1 + CLU_SWEEP_BATCH];
     *labelled = false;
     for (int64_t done = 0;;) {
         MDX_HIP(hipMemsetAsync(ctl + 1, 0, size_t(4) * CLU_SWEEP_BATCH, h->stream));
         for (int b = 0; b < CLU_SWEEP_BATCH; ++b)
-            hipLaunchKernelGGL(clu_sweep_kernel, grid, dim3(CLU_ROW_THREADS), 0, h->stream, n, h->max_nb,
-                               h->d_len.as<int>(), h->d_list.as<int>(), h->d_label.as<int>(), ctl + 1 + b);
+            hipLaunchKernelGGL(clu_sweep_kernel, grid, dim3(CLU_ROW_THREADS), 0, h->stream, n, h->lists.max_nb,
+                               h->lists.d_len.as<int>(), h->lists.d_list.as<int>(), h->d_label.as<int>(),
+                               ctl + 1 + b);
         h->timer.end(*ev);
         MDX_HIP(hipGetLastError());
         MDX_HIP(hipStreamSynchronize(h->stream));
         MDX_HIP(hipMemcpy(seen, ctl, sizeof(seen), hipMemcpyDeviceToHost));
         *ev = h->timer.begin();
-        h->max_row = seen[0];
-        if (seen[0] > h->max_nb)
+        h->lists.max_row = seen[0];
+        if (seen[0] > h->lists.max_nb)
             return MDX_OK;
         for (int b = 0; b < CLU_SWEEP_BATCH; ++b) {
             ++done;
@@ -186,9 +151,10 @@ static int clu_accumulate_rows(mdx_clu *h, const float *d_pos, int64_t src_rows,
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n, "%lld rows given, the groups hold %lld", (long long)n_rows, (long long)h->n);
     MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
-    MDX_TRY(clu_grow(h, h->d_frames, size_t(8) * CLU_FRAME_WORDS, h->frames_seen + n_frames));
+    MDX_TRY(grow_frames(h->d_frames, h->stream, size_t(8) * CLU_FRAME_WORDS, h->frames_seen,
+                        h->frames_seen + n_frames));
     if (h->keep_labels)
-        MDX_TRY(clu_grow(h, h->d_labels, size_t(4) * h->n, h->frames_seen + n_frames));
+        MDX_TRY(grow_frames(h->d_labels, h->stream, size_t(4) * h->n, h->frames_seen, h->frames_seen + n_frames));
     const int n = (int)h->n;
     const int64_t slab = clu_slab(h);       // what clu_ensure_slab sized the buffers for
     const int64_t n_jchunks = ceil_div(h->n, CLU_JCHUNK);
@@ -200,20 +166,21 @@ static int clu_accumulate_rows(mdx_clu *h, const float *d_pos, int64_t src_rows,
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f_lo = h->frames_seen;
         hipEvent_t ev = h->timer.begin();
-        hipLaunchKernelGGL(clu_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
-                           0, h->stream, pos, src_rows, d_index, n, h->d_slab.as<float>(), h->d_label.as<int>(),
-                           h->d_size.as<int>());
-        MDX_HIP(hipMemsetAsync(h->d_len.ptr, 0, size_t(4) * n * nf, h->stream));
+        launch_gather<false>(h->stream, pos, src_rows, d_index, n, nf, h->d_slab.as<float>(), 0, 1,
+                             CluStart{h->d_label.as<int>(), h->d_size.as<int>()});
+        MDX_HIP(hipMemsetAsync(h->lists.d_len.ptr, 0, size_t(4) * n * nf, h->stream));
         const auto contact = h->uniform
                                  ? (h->keep == 7 ? clu_contact_kernel<true, true> : clu_contact_kernel<false, true>)
                                  : (h->keep == 7 ? clu_contact_kernel<true, false> : clu_contact_kernel<false, false>);
         hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(CLU_THREADS), 0, h->stream,
                            h->d_slab.as<float>(), n, (int)n_jchunks, f_lo, h->box, h->keep, h->rc2,
-                           h->d_table.as<double>(), h->d_species.as<int>(), h->max_nb, h->d_len.as<int>(),
-                           h->d_list.as<int>(), h->d_frames.as<unsigned long long>(), h->d_ctl.as<int>());
+                           h->d_table.as<double>(), h->d_species.as<int>(), h->lists.max_nb,
+                           h->lists.d_len.as<int>(), h->lists.d_list.as<int>(),
+                           h->d_frames.as<unsigned long long>(), h->lists.d_ctl.as<int>());
         h->frames_seen += nf;
         bool labelled = false;
-        if (h->max_row <= h->max_nb) {      // else: the results are refused until a reset; only max_row goes on
+        // a row beyond the cap: the results are refused until a reset; only max_row goes on
+        if (h->lists.max_row <= h->lists.max_nb) {
             const int rc = clu_label_slab(h, nf, &ev, &labelled);
             if (rc != MDX_OK) {
                 h->timer.end(ev);
@@ -254,8 +221,6 @@ int mdx_clu_create(mdx_clu_t *out, int dev, int64_t n, const int32_t *species, i
     for (int64_t i = 0; i < n; ++i)
         MDX_REQUIRE(species[i] >= 0 && species[i] < n_species, "species[%lld] = %d out of range [0, %d)",
                     (long long)i, species[i], n_species);
-    for (int c = 0; c < 3; ++c)
-        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
     const int G = n_species;
     double largest = 0.0;
     bool uniform = true;
@@ -269,19 +234,17 @@ int mdx_clu_create(mdx_clu_t *out, int dev, int64_t n, const int32_t *species, i
             uniform = uniform && c == cutoff[0];
         }
     MDX_REQUIRE(largest > 0.0, "the cutoff table must hold at least one positive entry");
-    double shortest = HUGE_VAL;
-    for (int c = 0; c < 3; ++c)
-        if (!(zero_dims >> c & 1))
-            shortest = std::min(shortest, dims[c]);
-    // beyond half a box length the minimum image is not the nearest image
-    MDX_REQUIRE(largest <= shortest / 2, "cutoff %g reaches beyond half the shortest box length %g", largest,
-                shortest);
+    PairBox box;
+    int keep = 7;
+    MDX_TRY(check_box_cutoff(dims, zero_dims, largest, &box, &keep));
     mdx_clu *h = new mdx_clu();
     h->dev = dev;
     h->n = n;
     h->n_species = G;
-    h->keep = 7 & ~zero_dims;
-    h->max_nb = max_neighbors;
+    h->keep = keep;
+    h->box = box;
+    h->lists.max_nb = max_neighbors;
+    h->lists.ctl_words = 1 + CLU_SWEEP_BATCH;
     h->keep_labels = keep_labels != 0;
     h->species.assign(species, species + n);
     h->uniform = uniform;               // every entry is the one positive value
@@ -292,10 +255,6 @@ int mdx_clu_create(mdx_clu_t *out, int dev, int64_t n, const int32_t *species, i
         for (int b = 0; b < G; ++b)
             if (cutoff[a * G + b] > 0.0)
                 h->table[CLU_MAX_SPECIES * b + a] = cutoff[a * G + b] * cutoff[a * G + b];
-    for (int c = 0; c < 3; ++c) {
-        h->box.L[c] = dims[c];
-        h->box.inv[c] = 1.0 / dims[c];
-    }
     *out = h;
     return MDX_OK;
 }
@@ -305,8 +264,8 @@ int mdx_clu_destroy(mdx_clu_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_species, &h->d_table, &h->d_counts, &h->d_frames, &h->d_labels, &h->d_ctl, &h->d_slab,
-                    &h->d_len, &h->d_list, &h->d_label, &h->d_size});
+        h->release({&h->d_species, &h->d_table, &h->d_counts, &h->d_frames, &h->d_labels, &h->lists.d_ctl, &h->d_slab,
+                    &h->lists.d_len, &h->lists.d_list, &h->d_label, &h->d_size});
     delete h;
     return MDX_OK;
 }
@@ -316,7 +275,7 @@ int mdx_clu_reset(mdx_clu_t h)
     MDX_REQUIRE(h, "NULL handle");
     h->frames_seen = 0;
     h->sweeps = 0;
-    h->max_row = 0;
+    h->lists.max_row = 0;
     if (!h->ready)
         return MDX_OK;
     MDX_TRY(set_device(h->dev));
@@ -336,36 +295,25 @@ int mdx_clu_set_slab_frames(mdx_clu_t h, int64_t frames)
     return MDX_OK;
 }
 
+// what a route prepares before the first kernel
+static int clu_prepare(mdx_clu *h, int64_t)
+{
+    MDX_TRY(clu_ensure_device(h));
+    return clu_ensure_slab(h);
+}
+
 int mdx_clu_accumulate_device(mdx_clu_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
-    const int64_t n = index ? n_index : n_atoms;
-    MDX_REQUIRE(n == h->n, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n);
-    MDX_TRY(check_particle_index(index, n_index, n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(clu_ensure_device(h));
-    MDX_TRY(clu_ensure_slab(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return clu_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n, "groups", clu_prepare,
+                                clu_accumulate_rows);
 }
 
 int mdx_clu_accumulate(mdx_clu_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
-    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
-    MDX_REQUIRE(n == h->n, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n);
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(clu_ensure_device(h));
-    MDX_TRY(clu_ensure_slab(h));
-    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return clu_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_host(pos, n, n_frames, h->n, "groups", clu_prepare, clu_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
@@ -374,22 +322,8 @@ int mdx_clu_accumulate_traj(mdx_clu_t h, mdx_traj_t traj, const int64_t *frames,
                             const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
-    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
-    Trajectory *t = mdx_traj_internal(traj);
-    int64_t n = 0;
-    MDX_TRY(traj_selection(t, index, n_index, &n));
-    MDX_REQUIRE(n == h->n, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n);
-    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(clu_ensure_device(h));
-    MDX_TRY(clu_ensure_slab(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return clu_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n, "groups", clu_prepare,
+                              clu_accumulate_rows);
 }
 
 int mdx_clu_synchronize(mdx_clu_t h)
@@ -459,13 +393,10 @@ int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *fr
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
-    if (h->ready) {
-        int32_t row = 0;
-        MDX_HIP(hipMemcpy(&row, h->d_ctl.ptr, 4, hipMemcpyDeviceToHost));
-        h->max_row = row;
-    }
+    if (h->ready)
+        MDX_TRY(h->lists.look());
     if (evaluations) *evaluations = h->frames_seen * (h->n * (h->n - 1) / 2);
-    if (max_row) *max_row = h->max_row;
+    if (max_row) *max_row = h->lists.max_row;
     if (sweeps) *sweeps = h->sweeps;
     return MDX_OK;
 }

@@ -5,13 +5,7 @@
 // Nodes.  The n incoming rows of a frame are the atoms of group 0, then group 1, and so on; species[i] in 0 ... G-1 is
 // the group of row i, 1 <= G <= 8.
 //
-// Box and pair arithmetic: those of mdx_residence_device.hpp.  One constant orthorhombic box, lengths L_c;
-// inv_c = 1.0 / L_c is formed once on the host in float64.  Everything is float64, one operation at a time (the unit
-// is built with contraction off); float32 coordinates are widened before any arithmetic.  For rows i != j of frame f:
-//
-//     d_c = x_jc(f) - x_ic(f) ;  s = d_c * inv_c ;  w_c = d_c - L_c * rint(s)       (rint: ties to even, as numpy.rint;
-//                                                                                   w_c = +0.0 for a dropped component)
-//     r2  = (w_x*w_x + w_y*w_y) + w_z*w_z
+// Box and pair arithmetic: those of mdx_pairs_device.hpp, for rows i != j of frame f.
 //
 // Bond rule.  cutoff is a symmetric G x G table of non-negative finite values, at least one of them positive.
 // rc2[a][b] = cutoff[a][b] * cutoff[a][b], formed once on the host in float64, where the entry is positive, and -1.0
@@ -32,11 +26,9 @@
 //                           sum_g species_counts[g][s] == s * size_counts[s]
 // With keep_labels the engine also hands out label, int32 [F][n].
 //
-// Capped lists.  A row holds at most max_neighbors (1 ... 64) bonds in one frame, both directions counted (every bond
-// is in the rows of both its ends).  A row that would hold more is an error, never a silent truncation: the contact
-// kernel stores only into the row's max_neighbors slots but keeps counting, the largest row seen is kept in HBM, and
-// the host refuses to hand out results (MDX_ERR_INVALID_VALUE, naming max_neighbors and the largest row) from the
-// next synchronize / result on until a reset.  The slab that holds such a row is not labelled.
+// Capped lists (mdx_pairs_device.hpp).  A row holds at most max_neighbors (1 ... 64) bonds in one frame, both
+// directions counted (every bond is in the rows of both its ends); a row that would hold more refuses the results
+// (MDX_ERR_INVALID_VALUE, naming max_neighbors and the largest row).  The slab that holds such a row is not labelled.
 //
 // The bonds are a function of the frame alone, the labels a function of the bonds alone, and every tally is an integer
 // add or max (atomics on integers commute): the numbers are the same whatever the input route, the split into calls
@@ -46,20 +38,19 @@
 //
 // Shape.  Three phases per slab of frames; a frame never needs another, so there is no history.
 //
-// Phase 1, contact lists (the hot path, F * n * (n - 1) ordered evaluations).  clu_prepare_kernel gathers the rows of
-// a slab component-major float32, sets label[f][i] = i and size[f][i] = 0.  clu_contact_kernel has the shape of
-// prs_contact_kernel: grid x = i tiles x j chunks, z = frames; a block holds CLU_TILE rows in registers, one per
-// lane, widened, and walks its chunk of at most CLU_JCHUNK partners in stages of CLU_STAGE through LDS (widened once
-// when staged; every lane reads the same j at once, a broadcast).  The species of a staged partner lies beside its
-// coordinates in LDS, and the lane picks rc2 from the table in LDS at [species_j][species_i]: one row of 8 doubles per
-// partner, so the lanes of a wave read at most 8 neighbouring words.  Rows arrive group by group, so the partners of
-// nearly every stage are of one species: the block finds that out while it stages (one barrier with a vote), the lane
-// then takes its bound once for the stage, and only a stage that spans two groups looks it up pair by pair.  UNIFORM
-// (one species, or a table whose entries are all one positive value): rc2 is a kernel argument and neither species
-// nor table is touched.  Ordered pairs are evaluated, so that a row is filled by its own lane: a bond takes
-// slot = atomicAdd(&len[f][i], 1) and is stored at list[f][slot][i] when slot < max_neighbors (slot-major: the
-// labelling's lanes read consecutive i).  Each block adds its ordered bonds to the frame's count with one integer
-// atomic (bonds[f] is half of that count) and its largest row to max_row with one atomicMax.
+// Phase 1, contact lists (the hot path, F * n * (n - 1) ordered evaluations).  gather_kernel gathers the rows of a
+// slab component-major float32 and, through CluStart, sets label[f][i] = i and size[f][i] = 0.  clu_contact_kernel is
+// the walk of mdx_pairs_device.hpp with z = frames and CLU_JCHUNK partners per block.  The species of a staged
+// partner lies beside its coordinates in LDS, and the lane picks rc2 from the table in LDS at [species_j][species_i]:
+// one row of 8 doubles per partner, so the lanes of a wave read at most 8 neighbouring words.  Rows arrive group by
+// group, so the partners of nearly every stage are of one species: the block finds that out while it stages (one
+// barrier with a vote), the lane then takes its bound once for the stage, and only a stage that spans two groups
+// looks it up pair by pair.  UNIFORM (one species, or a table whose entries are all one positive value): rc2 is a
+// kernel argument and neither species nor table is touched.  Ordered pairs are evaluated, so that a row is filled by
+// its own lane: a bond takes slot = atomicAdd(&len[f][i], 1) and is stored at list[f][slot][i] when
+// slot < max_neighbors (slot-major: the labelling's lanes read consecutive i).  Each block adds its ordered bonds to
+// the frame's count with one integer atomic (bonds[f] is half of that count) and its largest row to max_row with one
+// atomicMax.
 //
 // Phase 2, labelling, from the lists only: in place, hooking plus pointer jumping.  A sweep (clu_sweep_kernel, one
 // thread per (frame, row i)) reads li = label[i], takes m = min(li, label[j] over the row's list), jumps once,
@@ -91,82 +82,31 @@
 // pairs, a labelling in LDS for small n and culling by cells are follow-ups.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "mdx_pairs_device.hpp"
 
 namespace mdx_clu_dev {
 
-constexpr int CLU_TILE = 256;                 // rows per block, one per lane
-constexpr int CLU_THREADS = CLU_TILE;
-constexpr int CLU_STAGE = CLU_THREADS;        // partners per LDS stage, one staged per thread
+using namespace mdx_pairs_dev;
+
+constexpr int CLU_TILE = PAIR_TILE;           // rows per block, one per lane
+constexpr int CLU_THREADS = PAIR_THREADS;
+constexpr int CLU_STAGE = PAIR_STAGE;         // partners per LDS stage, one staged per thread
 constexpr int CLU_JCHUNK = 4 * CLU_STAGE;     // partners per block
-constexpr int CLU_MAX_NEIGHBORS = 64;         // slots of a row at most
+constexpr int CLU_MAX_NEIGHBORS = PAIR_MAX_NEIGHBORS;   // slots of a row at most
 constexpr int CLU_MAX_SPECIES = 8;
-constexpr int64_t CLU_SLAB_MAX = 32768;       // frames per launch, at most (grid y / z)
+constexpr int64_t CLU_SLAB_MAX = PAIR_SLAB_MAX;         // frames per launch, at most (grid y / z)
 constexpr int CLU_ROW_THREADS = 256;          // threads of the per-row kernels (sweep, size, tally)
 constexpr int CLU_FRAME_WORDS = 4;            // uint64 per frame: ordered bonds, n_clusters, largest, sum_squares
 
-// Row index[p] (or p) of n_frames float32 frames of src_rows rows into the slab: slab[(f * 3 + c) * n + p].  One
-// thread per coordinate (t = c * n + p: a wave writes consecutive floats); grid y = frames.  The threads of component
-// 0 also start the labels (label[f][p] = p) and zero the sizes.
-__global__ __launch_bounds__(256) void clu_prepare_kernel(const float *__restrict__ pos, int64_t src_rows,
-                                                          const int *__restrict__ index, int n,
-                                                          float *__restrict__ slab, int *__restrict__ label,
-                                                          int *__restrict__ size)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 3 * n)
-        return;
-    const int c = t / n, p = t - c * n;
-    const int64_t r = index ? index[p] : p;
-    const int64_t f = blockIdx.y;
-    slab[(f * 3 + c) * n + p] = pos[(f * src_rows + r) * 3 + c];
-    if (c == 0) {
+// what gather_kernel does per row beyond the gather: the labels start (label[f][p] = p) and the sizes are zero
+struct CluStart {
+    int *__restrict__ label, *__restrict__ size;
+    __device__ __forceinline__ void operator()(int64_t f, int p, int n) const
+    {
         label[f * n + p] = p;
         size[f * n + p] = 0;
     }
-}
-
-struct CluBox {
-    double L[3], inv[3];
 };
-
-// w = d - L * rint(d * inv), one operation at a time
-__device__ __forceinline__ double clu_min_image(double d, double L, double inv)
-{
-    return __dsub_rn(d, __dmul_rn(L, rint(__dmul_rn(d, inv))));
-}
-
-// The staged partners js ... js + nj - 1 against this lane's row (xi, yi, zi).  LOOKUP: the bound of a pair is
-// table[8 * species_j + my_species] from LDS; else it is `bound` for every partner of the stage.
-template <bool ALL, bool LOOKUP>
-__device__ __forceinline__ void clu_stage_pairs(const double *__restrict__ stage,
-                                                const int *__restrict__ stage_species,
-                                                const double *__restrict__ lds_table, int my_species, double bound,
-                                                int nj, int js, int skip, double xi, double yi, double zi,
-                                                const CluBox &box, int keep, int n, int max_nb,
-                                                int *__restrict__ my_len, int *__restrict__ my_list,
-                                                unsigned int &found, unsigned int &row)
-{
-#pragma unroll 4
-    for (int jj = 0; jj < nj; ++jj) {
-        const double dx = __dsub_rn(stage[4 * jj + 0], xi), dy = __dsub_rn(stage[4 * jj + 1], yi),
-                     dz = __dsub_rn(stage[4 * jj + 2], zi);
-        const double wx = ALL || keep & 1 ? clu_min_image(dx, box.L[0], box.inv[0]) : 0.0;
-        const double wy = ALL || keep & 2 ? clu_min_image(dy, box.L[1], box.inv[1]) : 0.0;
-        const double wz = ALL || keep & 4 ? clu_min_image(dz, box.L[2], box.inv[2]) : 0.0;
-        const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz));
-        const double rc2 = LOOKUP ? lds_table[CLU_MAX_SPECIES * stage_species[jj] + my_species] : bound;
-        if (r2 <= rc2 && jj != skip) {
-            const int slot = atomicAdd(my_len, 1);          // other j chunks append to the same row
-            if (slot < max_nb)
-                my_list[int64_t(slot) * n] = js + jj;
-            ++found;
-            row = (unsigned int)slot + 1u > row ? (unsigned int)slot + 1u : row;
-        }
-    }
-}
 
 // The bonds of frame f_lo + blockIdx.z among the n rows of slab frame blockIdx.z.  keep: bit c set -> component c
 // takes part; ALL: keep == 7, known when compiled.  UNIFORM: every pair of species bonds within rc2; else
@@ -176,7 +116,7 @@ __device__ __forceinline__ void clu_stage_pairs(const double *__restrict__ stage
 // list: int32 [slab][max_nb][n]; frames: uint64 [F][CLU_FRAME_WORDS].
 template <bool ALL, bool UNIFORM>
 __global__ __launch_bounds__(CLU_THREADS) void clu_contact_kernel(
-    const float *__restrict__ slab, int n, int n_jchunks, int64_t f_lo, CluBox box, int keep, double rc2,
+    const float *__restrict__ slab, int n, int n_jchunks, int64_t f_lo, PairBox box, int keep, double rc2,
     const double *__restrict__ table, const int *__restrict__ species, int max_nb, int *__restrict__ len,
     int *__restrict__ list, unsigned long long *__restrict__ frames, int *__restrict__ max_row)
 {
@@ -212,10 +152,7 @@ __global__ __launch_bounds__(CLU_THREADS) void clu_contact_kernel(
         __syncthreads();                    // the stage is free
         int mixed = 0;                      // a partner of another species than the stage's first
         if ((int)threadIdx.x < nj) {
-            const float *__restrict__ src = b + js + threadIdx.x;
-            stage[4 * threadIdx.x + 0] = (double)src[0];
-            stage[4 * threadIdx.x + 1] = (double)src[n];
-            stage[4 * threadIdx.x + 2] = (double)src[2 * int64_t(n)];
+            stage_partners(stage, b, n, js);
             if (!UNIFORM) {
                 const int sj = species[js + threadIdx.x];
                 stage_species[threadIdx.x] = sj;
@@ -229,30 +166,26 @@ __global__ __launch_bounds__(CLU_THREADS) void clu_contact_kernel(
         if (!live)
             continue;
         const int skip = i - js;            // the stage entry that is this lane's own row
+        const auto bond = [&](int j) {
+            append_capped(my_len, my_list, n, max_nb, j, row);
+            ++found;
+        };
         if (UNIFORM || !mixed) {
             const double bound = UNIFORM ? rc2 : lds_table[CLU_MAX_SPECIES * stage_species[0] + my_species];
-            clu_stage_pairs<ALL, false>(stage, stage_species, lds_table, my_species, bound, nj, js, skip, xi, yi, zi,
-                                        box, keep, n, max_nb, my_len, my_list, found, row);
+            stage_pairs<ALL>(stage, nj, js, skip, xi, yi, zi, box, keep,
+                             [&](int, int j, double, double, double, double r2, bool other) {
+                                 if (r2 <= bound && other)
+                                     bond(j);
+                             });
         } else {
-            clu_stage_pairs<ALL, true>(stage, stage_species, lds_table, my_species, 0.0, nj, js, skip, xi, yi, zi, box,
-                                       keep, n, max_nb, my_len, my_list, found, row);
+            stage_pairs<ALL>(stage, nj, js, skip, xi, yi, zi, box, keep,
+                             [&](int jj, int j, double, double, double, double r2, bool other) {
+                                 if (r2 <= lds_table[CLU_MAX_SPECIES * stage_species[jj] + my_species] && other)
+                                     bond(j);
+                             });
         }
     }
-    // one integer atomic per block for the frame's ordered bonds, one for the largest row: integer adds and max commute
-    for (int off = 32; off > 0; off >>= 1) {
-        found += __shfl_down(found, off);
-        const unsigned int other = __shfl_down(row, off);
-        row = other > row ? other : row;
-    }
-    if ((threadIdx.x & 63) == 0 && (found | row)) {
-        atomicAdd(&block_found, found);
-        atomicMax(&block_row, row);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && block_found) {
-        atomicAdd(&frames[(f_lo + fs) * CLU_FRAME_WORDS], (unsigned long long)block_found);
-        atomicMax(max_row, (int)block_row);
-    }
+    block_tally<true>(found, row, &block_found, &block_row, &frames[(f_lo + fs) * CLU_FRAME_WORDS], max_row);
 }
 
 // One labelling sweep over the slab: grid x = row tiles, y = frames.  label: int32 [slab][n]; *lowered becomes 1 where

@@ -2,8 +2,9 @@
 // X_accumulate_rows(h, d_pos, src_rows, d_index, n_rows, n_frames): the staged host-memory and trajectory-file routes,
 // the particle index in HBM, the growing per-frame rows and the common part of a handle.  Host code only.
 //
-// An engine writes its own argument checks, its preparation (set_device + grow_rows, or its ensure_device /
-// ensure_history) and X_accumulate_rows; the rest of a route is one call into the feed.
+// An engine writes its own NULL checks, its preparation (set_device + grow_rows, or its ensure_device /
+// ensure_history) and X_accumulate_rows; the rest of a route is one call of FrameEngine::accumulate_device / _host /
+// _traj.
 #pragma once
 
 #include "mdx_common.hpp"
@@ -123,6 +124,23 @@ inline int grow_rows(DeviceBuffer &rows, hipStream_t stream, int64_t row_bytes, 
     return MDX_OK;
 }
 
+// Per-frame words of frame_bytes each that start at zero: room for `frames` frames (doubling); what the frames_seen
+// frames hold moves along.  Growing waits for the stream.
+inline int grow_frames(DeviceBuffer &buf, hipStream_t stream, size_t frame_bytes, int64_t frames_seen, int64_t frames)
+{
+    if (frame_bytes * frames <= buf.bytes)
+        return MDX_OK;
+    DeviceBuffer grown;
+    MDX_TRY(grown.ensure(std::max(frame_bytes * frames, 2 * buf.bytes)));
+    MDX_HIP(hipMemsetAsync(grown.ptr, 0, grown.bytes, stream));
+    if (frames_seen > 0)
+        MDX_HIP(hipMemcpyAsync(grown.ptr, buf.ptr, frame_bytes * frames_seen, hipMemcpyDeviceToDevice, stream));
+    MDX_HIP(hipStreamSynchronize(stream));          // nobody reads the old block any more
+    buf.recycle();
+    buf = grown;
+    return MDX_OK;
+}
+
 // what every per-frame engine handle starts with
 struct FrameEngine {
     int dev = 0;
@@ -149,6 +167,79 @@ struct FrameEngine {
         if (kernel_ms) *kernel_ms = timer.total_ms;
         if (frames) *frames = frames_seen;
         return MDX_OK;
+    }
+
+    // the head of a lazy X_ensure_device: the handle's device is current and its stream exists
+    int acquire_stream()
+    {
+        MDX_TRY(set_device(dev));
+        if (!stream) {
+            MDX_TRY(stream_acquire(&stream));
+            timer.stream = stream;
+        }
+        return MDX_OK;
+    }
+
+    // The three input routes of the engine H (its handle derives from FrameEngine), after the entry point's NULL
+    // checks.  want: the rows a frame must hold, `noun` holds them ("groups", "sets").  prepare(h, n_frames): what
+    // has to exist before the first kernel (the device side of a lazy handle, room for the frames' rows);
+    // rows_fn: the engine's X_accumulate_rows(h, d_pos, src_rows, d_index, n_rows, nf).  Argument errors come before
+    // anything touches the device, and no frames touch nothing.
+    template <typename H> using PrepareFn = int (*)(H *, int64_t);
+    template <typename H> using RowsFn = int (*)(H *, const float *, int64_t, const int *, int64_t, int64_t);
+
+    // d_pos float32[n_frames][n_atoms][3] in HBM; index: host int32[n_index] rows of a frame, or NULL for all
+    template <typename H>
+    int accumulate_device(const float *d_pos, int64_t n_atoms, int64_t n_frames, const int32_t *index, int64_t n_index,
+                          int64_t want, const char *noun, PrepareFn<H> prepare, RowsFn<H> rows_fn)
+    {
+        H *h = static_cast<H *>(this);
+        MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
+        const int64_t n = index ? n_index : n_atoms;
+        MDX_REQUIRE(n == want, "%lld rows given, the %s hold %lld", (long long)n, noun, (long long)want);
+        MDX_TRY(check_particle_index(index, n_index, n_atoms));
+        if (n_frames == 0)
+            return MDX_OK;
+        MDX_TRY(prepare(h, n_frames));
+        const int *d_index = nullptr;
+        MDX_TRY(feed.upload_index(stream, index, n_index, &d_index));
+        return rows_fn(h, d_pos, n_atoms, d_index, n, n_frames);
+    }
+
+    // pos float32[n_frames][n][3] in host memory, staged in slabs sized by n
+    template <typename H>
+    int accumulate_host(const float *pos, int64_t n, int64_t n_frames, int64_t want, const char *noun,
+                        PrepareFn<H> prepare, RowsFn<H> rows_fn)
+    {
+        H *h = static_cast<H *>(this);
+        MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
+        MDX_REQUIRE(n == want, "%lld rows given, the %s hold %lld", (long long)n, noun, (long long)want);
+        if (n_frames == 0)
+            return MDX_OK;
+        MDX_TRY(prepare(h, n_frames));
+        return feed.host(dev, stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
+                         [&](const float *d_pos, int64_t nf) -> int { return rows_fn(h, d_pos, n, nullptr, n, nf); });
+    }
+
+    // the listed frames of a trajectory file, gathered to the index's rows (NULL: the file's first n_index) while
+    // they are staged, in slabs sized by the file's n_atoms
+    template <typename H>
+    int accumulate_traj(Trajectory *t, const int64_t *frames, int64_t n_frames, const int32_t *index, int64_t n_index,
+                        int64_t want, const char *noun, PrepareFn<H> prepare, RowsFn<H> rows_fn)
+    {
+        H *h = static_cast<H *>(this);
+        MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
+        int64_t n = 0;
+        MDX_TRY(traj_selection(t, index, n_index, &n));
+        MDX_REQUIRE(n == want, "%lld rows selected, the %s hold %lld", (long long)n, noun, (long long)want);
+        MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
+        if (n_frames == 0)
+            return MDX_OK;
+        MDX_TRY(prepare(h, n_frames));
+        const int *d_index = nullptr;
+        MDX_TRY(feed.upload_index(stream, index, n_index, &d_index));
+        return feed.traj(dev, stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
+                         [&](const float *d_pos, int64_t nf) -> int { return rows_fn(h, d_pos, n, nullptr, n, nf); });
     }
 
     // the device side of X_destroy: everything idle, then blocks and stream back to the per-device pools

@@ -42,6 +42,9 @@ struct MoleculeStage {
     DeviceBuffer d_offsets, d_masses, d_total, d_com;
 
     bool active() const { return n_groups > 0; }
+    // the rows an incoming frame must hold for an engine of n_points points, and what holds them in its messages
+    int64_t rows_wanted(int64_t n_points) const { return active() ? n_atoms : n_points; }
+    const char *rows_noun() const { return active() ? "groups (rows of the grouping)" : "groups"; }
 
     // offsets int64[n_groups + 1] (CSR over the incoming rows), masses float64[offsets[n_groups]];
     // n_groups <= 0 switches the stage off.  The caller has synchronised the consuming stream.

@@ -14,6 +14,7 @@
 #include "mdx_common.hpp"
 #include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_pairs_host.hpp"
 #include "mdx_residence_device.hpp"
 
 #include <algorithm>
@@ -30,55 +31,47 @@ constexpr int64_t PRS_HISTORY_BYTES = int64_t(256) << 20;   // what the frames o
 
 struct mdx_prs : FrameEngine {
     bool ready = false;                 // the device side exists
-    int n_lags = 0, keep = 7, max_nb = 32;
+    int n_lags = 0, keep = 7;
     bool same = false, continuous = true;
     int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
     int64_t max_lag = 0, origin_step = 1;
     int64_t cap = 0;                    // frames the rings hold
-    int max_row = 0;                    // the largest row seen, as of the last look
-    PrsBox box;
+    PairBox box;
+    CappedLists lists;                  // the rings of contact lists
     double rc2 = 0.0;
     std::vector<int64_t> lags;
     // d_sums: uint64 [3][n_lags] intermittent, continuous, origin_counts; d_contacts: uint64, one per frame seen
-    DeviceBuffer d_lags, d_sums, d_contacts, d_max_row, d_slab, d_len, d_list, d_mask;
+    DeviceBuffer d_lags, d_sums, d_contacts, d_slab, d_mask;
 };
 
 // bytes a frame takes: its gathered rows while it is in flight, its lists and masks while it is in the rings
 static int64_t prs_frame_bytes(const mdx_prs *h)
 {
-    return 12 * h->n_rows + (int64_t(h->max_nb) + 1) * 4 * h->n1 + 8 * h->n1;
+    return 12 * h->n_rows + (int64_t(h->lists.max_nb) + 1) * 4 * h->n1 + 8 * h->n1;
 }
 
 static int64_t prs_slab(const mdx_prs *h)
 {
-    if (h->slab_frames > 0)
-        return h->slab_frames;
-    return std::min(PRS_SLAB_MAX, std::max<int64_t>(1, PRS_HISTORY_BYTES / prs_frame_bytes(h)));
+    return pair_slab_frames(h->slab_frames, PRS_HISTORY_BYTES, prs_frame_bytes(h));
 }
 
 static int prs_zero(mdx_prs *h)
 {
     MDX_HIP(hipMemsetAsync(h->d_sums.ptr, 0, size_t(24) * h->n_lags, h->stream));
-    MDX_HIP(hipMemsetAsync(h->d_max_row.ptr, 0, 4, h->stream));
     if (h->d_contacts.ptr)
         MDX_HIP(hipMemsetAsync(h->d_contacts.ptr, 0, h->d_contacts.bytes, h->stream));
-    h->max_row = 0;
-    return MDX_OK;
+    return h->lists.zero(h->stream);
 }
 
 // the device side of the handle: stream, tables and counters
 static int prs_ensure_device(mdx_prs *h)
 {
-    MDX_TRY(set_device(h->dev));
     if (h->ready)
-        return MDX_OK;
-    if (!h->stream) {
-        MDX_TRY(stream_acquire(&h->stream));
-        h->timer.stream = h->stream;
-    }
+        return set_device(h->dev);
+    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
     MDX_TRY(h->d_sums.ensure(size_t(24) * h->n_lags));
-    MDX_TRY(h->d_max_row.ensure(4));
+    MDX_TRY(h->lists.ensure_ctl());
     MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
     MDX_TRY(prs_zero(h));
     MDX_HIP(hipStreamSynchronize(h->stream));
@@ -95,43 +88,19 @@ static int prs_ensure_rings(mdx_prs *h)
     const int64_t slab = prs_slab(h), cap = h->max_lag + slab;
     MDX_REQUIRE(cap < (int64_t(1) << 40) / prs_frame_bytes(h),
                 "a history of %lld frames of %lld points with %d neighbors each is too large", (long long)cap,
-                (long long)h->n1, h->max_nb);
+                (long long)h->n1, h->lists.max_nb);
     MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * slab));
-    MDX_TRY(h->d_len.ensure(size_t(4) * h->n1 * cap));
-    MDX_TRY(h->d_list.ensure(size_t(4) * h->max_nb * h->n1 * cap));
+    MDX_TRY(h->lists.ensure(h->n1, cap));
     if (h->continuous)
         MDX_TRY(h->d_mask.ensure(size_t(8) * h->n1 * cap));
     h->cap = cap;
     return MDX_OK;
 }
 
-// room for the contacts of `frames` frames; what has been counted so far moves along
-static int prs_ensure_contacts(mdx_prs *h, int64_t frames)
-{
-    if (size_t(8) * frames <= h->d_contacts.bytes)
-        return MDX_OK;
-    DeviceBuffer grown;
-    MDX_TRY(grown.ensure(std::max(size_t(8) * frames, 2 * h->d_contacts.bytes)));
-    MDX_HIP(hipMemsetAsync(grown.ptr, 0, grown.bytes, h->stream));
-    if (h->frames_seen > 0)
-        MDX_HIP(hipMemcpyAsync(grown.ptr, h->d_contacts.ptr, size_t(8) * h->frames_seen, hipMemcpyDeviceToDevice,
-                               h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));       // nobody reads the old block any more
-    h->d_contacts.recycle();
-    h->d_contacts = grown;
-    return MDX_OK;
-}
-
 // With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
 static int prs_check_rows(mdx_prs *h)
 {
-    int32_t row = 0;
-    MDX_HIP(hipMemcpy(&row, h->d_max_row.ptr, 4, hipMemcpyDeviceToHost));
-    h->max_row = row;
-    MDX_REQUIRE(row <= h->max_nb,
-                "a row held %d contacts in one frame, more than max_neighbors = %d: raise max_neighbors or lower the "
-                "cutoff (reset starts over)", row, h->max_nb);
-    return MDX_OK;
+    return h->lists.check("row", "contacts");
 }
 
 // n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
@@ -142,8 +111,9 @@ static int prs_accumulate_rows(mdx_prs *h, const float *d_pos, int64_t src_rows,
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n_rows, (long long)h->n_rows);
     MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
-    MDX_TRY(prs_ensure_contacts(h, h->frames_seen + n_frames));
-    const int n = (int)h->n_rows, n1 = (int)h->n1;
+    MDX_TRY(grow_frames(h->d_contacts, h->stream, 8, h->frames_seen, h->frames_seen + n_frames));
+    const int n = (int)h->n_rows, n1 = (int)h->n1, max_nb = h->lists.max_nb;
+    int *len = h->lists.d_len.as<int>(), *list = h->lists.d_list.as<int>();
     const int64_t slab = std::min(prs_slab(h), h->cap - h->max_lag);
     const int64_t n_jchunks = ceil_div(h->n2, PRS_JCHUNK);
     const int64_t blocks = ceil_div(h->n1, PRS_TILE) * n_jchunks;
@@ -153,18 +123,17 @@ static int prs_accumulate_rows(mdx_prs *h, const float *d_pos, int64_t src_rows,
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f_lo = h->frames_seen;
-        hipLaunchKernelGGL(prs_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
-                           0, h->stream, pos, src_rows, d_index, n, h->d_slab.as<float>());
+        launch_gather<false>(h->stream, pos, src_rows, d_index, n, nf, h->d_slab.as<float>());
         // the rows of the new frames start empty: their ring slots are one range, or two where the ring wraps
         const int64_t first = f_lo % h->cap, head = std::min(nf, h->cap - first);
-        MDX_HIP(hipMemsetAsync(h->d_len.as<int>() + first * n1, 0, size_t(4) * n1 * head, h->stream));
+        MDX_HIP(hipMemsetAsync(len + first * n1, 0, size_t(4) * n1 * head, h->stream));
         if (nf > head)
-            MDX_HIP(hipMemsetAsync(h->d_len.ptr, 0, size_t(4) * n1 * (nf - head), h->stream));
+            MDX_HIP(hipMemsetAsync(len, 0, size_t(4) * n1 * (nf - head), h->stream));
         const auto contact = h->keep == 7 ? prs_contact_kernel<true> : prs_contact_kernel<false>;
         hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(PRS_THREADS), 0, h->stream,
                            h->d_slab.as<float>(), h->cap, n, n1, (int)h->n2, h->same ? 0 : n1, h->same ? 1 : 0,
-                           (int)n_jchunks, f_lo, h->box, h->keep, h->rc2, h->max_nb, h->d_len.as<int>(),
-                           h->d_list.as<int>(), h->d_contacts.as<unsigned long long>(), h->d_max_row.as<int>());
+                           (int)n_jchunks, f_lo, h->box, h->keep, h->rc2, max_nb, len, list,
+                           h->d_contacts.as<unsigned long long>(), h->lists.d_ctl.as<int>());
         // the origins that meet a new frame: multiples of origin_step in [f_lo - max_lag, f_lo + nf)
         const int64_t o_lo = ceil_div(std::max<int64_t>(0, f_lo - h->max_lag), h->origin_step);
         const int64_t o_hi = ceil_div(f_lo + nf, h->origin_step);
@@ -172,7 +141,7 @@ static int prs_accumulate_rows(mdx_prs *h, const float *d_pos, int64_t src_rows,
         for (int64_t o = o_lo; o < o_hi; o += PRS_WALK_ORIGINS) {
             const int64_t n_o = std::min<int64_t>(PRS_WALK_ORIGINS, o_hi - o);
             hipLaunchKernelGGL(walk, dim3((unsigned)walk_tiles, (unsigned)n_o), dim3(PRS_WALK_THREADS), 0, h->stream,
-                               h->cap, n1, h->max_nb, h->d_len.as<int>(), h->d_list.as<int>(),
+                               h->cap, n1, max_nb, len, list,
                                h->d_mask.as<unsigned long long>(), h->d_lags.as<int64_t>(), h->n_lags, h->max_lag, o,
                                h->origin_step, f_lo, nf, h->d_sums.as<unsigned long long>());
         }
@@ -208,15 +177,10 @@ int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, do
         MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
         MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
     }
-    for (int c = 0; c < 3; ++c)
-        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
     MDX_REQUIRE(cutoff > 0.0 && std::isfinite(cutoff), "cutoff must be positive and finite");
-    double shortest = HUGE_VAL;
-    for (int c = 0; c < 3; ++c)
-        if (!(zero_dims >> c & 1))
-            shortest = std::min(shortest, dims[c]);
-    // beyond half a box length the minimum image is not the nearest image
-    MDX_REQUIRE(cutoff <= shortest / 2, "cutoff %g reaches beyond half the shortest box length %g", cutoff, shortest);
+    PairBox box;
+    int keep = 7;
+    MDX_TRY(check_box_cutoff(dims, zero_dims, cutoff, &box, &keep));
     mdx_prs *h = new mdx_prs();
     h->dev = dev;
     h->n1 = n1;
@@ -225,16 +189,13 @@ int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, do
     h->continuous = continuous != 0;
     h->n_rows = same ? n1 : n1 + n2;
     h->n_lags = n_lags;
-    h->keep = 7 & ~zero_dims;
-    h->max_nb = max_neighbors;
+    h->keep = keep;
+    h->box = box;
+    h->lists.max_nb = max_neighbors;
     h->origin_step = origin_step;
     h->max_lag = lags[n_lags - 1];
     h->lags.assign(lags, lags + n_lags);
     h->rc2 = cutoff * cutoff;
-    for (int c = 0; c < 3; ++c) {
-        h->box.L[c] = dims[c];
-        h->box.inv[c] = 1.0 / dims[c];
-    }
     *out = h;
     return MDX_OK;
 }
@@ -244,8 +205,8 @@ int mdx_prs_destroy(mdx_prs_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_lags, &h->d_sums, &h->d_contacts, &h->d_max_row, &h->d_slab, &h->d_len, &h->d_list,
-                    &h->d_mask});
+        h->release({&h->d_lags, &h->d_sums, &h->d_contacts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
+                    &h->lists.d_list, &h->d_mask});
     delete h;
     return MDX_OK;
 }
@@ -254,7 +215,7 @@ int mdx_prs_reset(mdx_prs_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
     h->frames_seen = 0;         // the history starts over with the next frame
-    h->max_row = 0;
+    h->lists.max_row = 0;
     if (!h->ready)
         return MDX_OK;
     MDX_TRY(set_device(h->dev));
@@ -274,36 +235,25 @@ int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames)
     return MDX_OK;
 }
 
+// what a route prepares before the first kernel
+static int prs_prepare(mdx_prs *h, int64_t)
+{
+    MDX_TRY(prs_ensure_device(h));
+    return prs_ensure_rings(h);
+}
+
 int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
-    const int64_t n = index ? n_index : n_atoms;
-    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    MDX_TRY(check_particle_index(index, n_index, n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(prs_ensure_device(h));
-    MDX_TRY(prs_ensure_rings(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return prs_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "sets", prs_prepare,
+                                prs_accumulate_rows);
 }
 
 int mdx_prs_accumulate(mdx_prs_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
-    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
-    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(prs_ensure_device(h));
-    MDX_TRY(prs_ensure_rings(h));
-    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return prs_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_host(pos, n, n_frames, h->n_rows, "sets", prs_prepare, prs_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
@@ -312,22 +262,8 @@ int mdx_prs_accumulate_traj(mdx_prs_t h, mdx_traj_t traj, const int64_t *frames,
                             const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
-    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
-    Trajectory *t = mdx_traj_internal(traj);
-    int64_t n = 0;
-    MDX_TRY(traj_selection(t, index, n_index, &n));
-    MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(prs_ensure_device(h));
-    MDX_TRY(prs_ensure_rings(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return prs_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "sets",
+                              prs_prepare, prs_accumulate_rows);
 }
 
 int mdx_prs_synchronize(mdx_prs_t h)
@@ -375,13 +311,10 @@ int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *fr
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
-    if (h->ready) {
-        int32_t row = 0;
-        MDX_HIP(hipMemcpy(&row, h->d_max_row.ptr, 4, hipMemcpyDeviceToHost));
-        h->max_row = row;
-    }
+    if (h->ready)
+        MDX_TRY(h->lists.look());
     if (evaluations) *evaluations = h->frames_seen * (h->n1 * h->n2 - (h->same ? h->n1 : 0));
-    if (max_row) *max_row = h->max_row;
+    if (max_row) *max_row = h->lists.max_row;
     return MDX_OK;
 }
 

@@ -3,14 +3,10 @@
 // Result contract.  The sets, the box, the frames, lags, origin_step, zero_dims and `same` mean what they mean in
 // mdx_vanhove_distinct_device.hpp: set 1 holds n1 rows, set 2 holds n2 rows, incoming rows are set 1 then set 2; with
 // `same` both are one set (n1 == n2, the rows arrive once), the ordered pairs (i, j) and (j, i) both count and i == j
-// does not.  One constant orthorhombic box, lengths L_c; inv_c = 1.0 / L_c is formed once on the host in float64.
-// Analysed frames are numbered f = 0, 1, ... in the order fed; `lags` is strictly increasing and non-negative;
-// origin_step >= 1.  Everything is float64, one operation at a time (the unit is built with contraction off); float32
-// coordinates are widened before any arithmetic.  For frame f and pair (i of set 1, j of set 2), both at frame f:
+// does not.  Analysed frames are numbered f = 0, 1, ... in the order fed; `lags` is strictly increasing and
+// non-negative; origin_step >= 1.  Box and pair arithmetic: those of mdx_pairs_device.hpp, for the pair (i of set 1,
+// j of set 2), both at frame f:
 //
-//     d_c = x2_jc(f) - x1_ic(f) ;  s = d_c * inv_c ;  w_c = d_c - L_c * rint(s)      (rint: ties to even, as numpy.rint;
-//                                                                                    w_c = +0.0 for a dropped component)
-//     r2  = (w_x*w_x + w_y*w_y) + w_z*w_z
 //     h_ij(f) = 1  where  r2 <= rc2 ,  rc2 = cutoff * cutoff formed once on the host in float64
 //
 // A NaN r2 is never a contact (the comparison fails); no square root is taken.  C(f) is the set of pairs with h = 1.
@@ -23,10 +19,8 @@
 //     continuous[k]    += |C(f0) & C(f0 + 1) & ... & C(f0 + lags[k])|    over every analysed frame in between, not only
 //                                                                        those that are lags
 //
-// Capped lists.  A row i holds at most max_neighbors (1 ... 64) contacts in one frame.  A row that would hold more is
-// an error, never a silent truncation: the contact kernel stores only into the row's max_neighbors slots but keeps
-// counting, the largest row seen is kept in HBM, and the host refuses to hand out results (MDX_ERR_INVALID_VALUE,
-// naming max_neighbors and the largest row) from the next synchronize / result on until a reset.
+// Capped lists (mdx_pairs_device.hpp).  A row i holds at most max_neighbors (1 ... 64) contacts in one frame; a row
+// that would hold more refuses the results (MDX_ERR_INVALID_VALUE, naming max_neighbors and the largest row).
 //
 // All accumulation is integer adds (atomics on integers commute), set membership does not depend on the order in
 // which a row's contacts were appended, and popcounts do not either: the numbers are the same whatever the input
@@ -34,15 +28,13 @@
 //
 // evaluations is the contract's count F * (n1*n2 - (same ? n1 : 0)).
 //
-// Shape.  prs_prepare_kernel gathers the rows of a slab of incoming frames, component-major float32 (widening is
-// exact and happens in registers); positions live only as long as the slab in flight: the history is contact lists.
-// prs_contact_kernel (the hot path, F * n1 * n2 evaluations): grid x = i tiles x j chunks, z = the new frames.  A
-// block holds PRS_TILE points of set 1 in registers, one per lane, widened, and walks its chunk of at most PRS_JCHUNK
-// points of set 2 in stages of PRS_STAGE points through LDS (widened once when staged; every lane reads the same j at
-// once, a broadcast).  14 float64 operations to r2 and one compare per pair.  A contact takes
-// slot = atomicAdd(&len[f % cap][i], 1) and is stored at list[f % cap][slot][i] when slot < max_neighbors (slot-major:
-// the walk kernel's lanes read consecutive i).  Each block adds its contacts to contacts[f] with one integer atomic
-// and its largest row to max_row with one atomicMax.
+// Shape.  gather_kernel gathers the rows of a slab of incoming frames, component-major float32 (widening is exact
+// and happens in registers); positions live only as long as the slab in flight: the history is contact lists.
+// prs_contact_kernel (the hot path, F * n1 * n2 evaluations) is the walk of mdx_pairs_device.hpp with z = the new
+// frames and PRS_JCHUNK points of set 2 per block; its rule is one compare per pair against a kernel argument.  A
+// contact takes slot = atomicAdd(&len[f % cap][i], 1) and is stored at list[f % cap][slot][i] when
+// slot < max_neighbors (slot-major: the walk kernel's lanes read consecutive i).  Each block adds its contacts to
+// contacts[f] with one integer atomic and its largest row to max_row with one atomicMax.
 // prs_walk_kernel: one thread per (origin f0, point i); its state is a 64-bit alive mask over the slots of
 // list[f0 % cap][.][i], kept in HBM and ring-indexed by f0, so that an origin survives slab and call boundaries.  For
 // every new frame f of the launch in order, f0 <= f <= f0 + max(lags): member = the origin's slots whose j is also in
@@ -56,46 +48,20 @@
 // No cell list and no spatial culling: every pair is evaluated.  Culling by cells is the follow-up.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "mdx_pairs_device.hpp"
 
 namespace mdx_prs_dev {
 
-constexpr int PRS_TILE = 256;                 // set-1 points per block, one per lane
-constexpr int PRS_THREADS = PRS_TILE;
-constexpr int PRS_WAVES = PRS_THREADS / 64;
-constexpr int PRS_STAGE = PRS_THREADS;        // set-2 points per LDS stage, one staged per thread
+using namespace mdx_pairs_dev;
+
+constexpr int PRS_TILE = PAIR_TILE;           // set-1 points per block, one per lane
+constexpr int PRS_THREADS = PAIR_THREADS;
+constexpr int PRS_STAGE = PAIR_STAGE;         // set-2 points per LDS stage, one staged per thread
 constexpr int PRS_JCHUNK = 4 * PRS_STAGE;     // set-2 points per block
-constexpr int PRS_MAX_NEIGHBORS = 64;         // slots of a row at most: one bit each in the alive mask
-constexpr int64_t PRS_SLAB_MAX = 32768;       // frames per launch, at most (grid z)
+constexpr int PRS_MAX_NEIGHBORS = PAIR_MAX_NEIGHBORS;   // slots of a row at most: one bit each in the alive mask
+constexpr int64_t PRS_SLAB_MAX = PAIR_SLAB_MAX;         // frames per launch, at most (grid z)
 constexpr int PRS_WALK_THREADS = 256;
 constexpr int PRS_WALK_ORIGINS = 65535;       // origins per walk launch, at most (grid y)
-
-// Row index[p] (or p) of n_frames float32 frames of src_rows rows into the slab: slab[(f * 3 + c) * n_points + p].
-// One thread per coordinate (t = c * n_points + p: a wave writes consecutive floats); grid y = frames.
-__global__ __launch_bounds__(256) void prs_prepare_kernel(const float *__restrict__ pos, int64_t src_rows,
-                                                          const int *__restrict__ index, int n_points,
-                                                          float *__restrict__ slab)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 3 * n_points)
-        return;
-    const int c = t / n_points, p = t - c * n_points;
-    const int64_t r = index ? index[p] : p;
-    const int64_t f = blockIdx.y;
-    slab[(f * 3 + c) * n_points + p] = pos[(f * src_rows + r) * 3 + c];
-}
-
-struct PrsBox {
-    double L[3], inv[3];
-};
-
-// w = d - L * rint(d * inv), one operation at a time
-__device__ __forceinline__ double prs_min_image(double d, double L, double inv)
-{
-    return __dsub_rn(d, __dmul_rn(L, rint(__dmul_rn(d, inv))));
-}
 
 // The contacts of frame f = f_lo + blockIdx.z among the rows of slab frame blockIdx.z.  n_points: rows of a slab
 // frame; set 2 starts at row off2 (0 with same).  keep: bit c set -> component c takes part; ALL: keep == 7, known
@@ -103,7 +69,7 @@ __device__ __forceinline__ double prs_min_image(double d, double L, double inv)
 template <bool ALL>
 __global__ __launch_bounds__(PRS_THREADS) void prs_contact_kernel(
     const float *__restrict__ slab, int64_t cap, int n_points, int n1, int n2, int off2, int same, int n_jchunks,
-    int64_t f_lo, PrsBox box, int keep, double rc2, int max_nb, int *__restrict__ len, int *__restrict__ list,
+    int64_t f_lo, PairBox box, int keep, double rc2, int max_nb, int *__restrict__ len, int *__restrict__ list,
     unsigned long long *__restrict__ contacts, int *__restrict__ max_row)
 {
     __shared__ __attribute__((aligned(16))) double stage[4 * PRS_STAGE];
@@ -129,48 +95,21 @@ __global__ __launch_bounds__(PRS_THREADS) void prs_contact_kernel(
     for (int js = j_begin; js < j_end; js += PRS_STAGE) {
         const int nj = j_end - js < PRS_STAGE ? j_end - js : PRS_STAGE;
         __syncthreads();                    // the stage is free
-        if ((int)threadIdx.x < nj) {
-            const float *__restrict__ src = b + js + threadIdx.x;
-            stage[4 * threadIdx.x + 0] = (double)src[0];
-            stage[4 * threadIdx.x + 1] = (double)src[n_points];
-            stage[4 * threadIdx.x + 2] = (double)src[2 * int64_t(n_points)];
-        }
+        if ((int)threadIdx.x < nj)
+            stage_partners(stage, b, n_points, js);
         __syncthreads();
         if (!live)
             continue;
         const int skip = same ? i - js : -1;        // the stage entry that is this lane's own point
-#pragma unroll 4
-        for (int jj = 0; jj < nj; ++jj) {
-            const double dx = __dsub_rn(stage[4 * jj + 0], xi), dy = __dsub_rn(stage[4 * jj + 1], yi),
-                         dz = __dsub_rn(stage[4 * jj + 2], zi);
-            const double wx = ALL || keep & 1 ? prs_min_image(dx, box.L[0], box.inv[0]) : 0.0;
-            const double wy = ALL || keep & 2 ? prs_min_image(dy, box.L[1], box.inv[1]) : 0.0;
-            const double wz = ALL || keep & 4 ? prs_min_image(dz, box.L[2], box.inv[2]) : 0.0;
-            const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz));
-            if (r2 <= rc2 && jj != skip) {
-                const int slot = atomicAdd(my_len, 1);          // other j chunks append to the same row
-                if (slot < max_nb)
-                    my_list[int64_t(slot) * n1] = js + jj;
-                ++found;
-                row = (unsigned int)slot + 1u > row ? (unsigned int)slot + 1u : row;
-            }
-        }
+        stage_pairs<ALL>(stage, nj, js, skip, xi, yi, zi, box, keep,
+                         [&](int, int j, double, double, double, double r2, bool other) {
+                             if (r2 <= rc2 && other) {
+                                 append_capped(my_len, my_list, n1, max_nb, j, row);
+                                 ++found;
+                             }
+                         });
     }
-    // one integer atomic per block for the frame's contacts, one for the largest row: integer adds and max commute
-    for (int off = 32; off > 0; off >>= 1) {
-        found += __shfl_down(found, off);
-        const unsigned int other = __shfl_down(row, off);
-        row = other > row ? other : row;
-    }
-    if ((threadIdx.x & 63) == 0 && (found | row)) {
-        atomicAdd(&block_found, found);
-        atomicMax(&block_row, row);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && block_found) {
-        atomicAdd(&contacts[f], (unsigned long long)block_found);
-        atomicMax(max_row, (int)block_row);
-    }
+    block_tally<true>(found, row, &block_found, &block_row, &contacts[f], max_row);
 }
 
 // bits 0 ... n - 1

@@ -254,28 +254,26 @@ int mdx_rouse_set_unwrap(mdx_rouse_t h, const double *dims, const double *start)
     return MDX_OK;
 }
 
+// what a route prepares before the first kernel
+static int rouse_prepare(mdx_rouse *h, int64_t n_frames)
+{
+    MDX_TRY(set_device(h->dev));
+    return rouse_grow_rows(h, n_frames);
+}
+
 int mdx_rouse_accumulate_device(mdx_rouse_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                                 const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
-    MDX_TRY(set_device(h->dev));
-    MDX_TRY(check_particle_index(index, n_index, n_atoms));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return rouse_accumulate_rows(h, d_pos, n_atoms, d_index, index ? n_index : n_atoms, n_frames);
+    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->mol.rows_wanted(h->n_points),
+                                h->mol.rows_noun(), rouse_prepare, rouse_accumulate_rows);
 }
 
 int mdx_rouse_accumulate(mdx_rouse_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
-    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
-    MDX_TRY(set_device(h->dev));
-    MDX_TRY(rouse_grow_rows(h, n_frames));
-    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return rouse_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_host(pos, n, n_frames, h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), rouse_prepare,
+                              rouse_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -284,21 +282,9 @@ int mdx_rouse_accumulate_traj(mdx_rouse_t h, mdx_traj_t traj, const int64_t *fra
                               const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
-    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
-    MDX_TRY(set_device(h->dev));
-    Trajectory *t = mdx_traj_internal(traj);
-    int64_t n = 0;
-    MDX_TRY(traj_selection(t, index, n_index, &n));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    MDX_TRY(rouse_grow_rows(h, n_frames));
-    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return rouse_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index,
+                              h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), rouse_prepare,
+                              rouse_accumulate_rows);
 }
 
 int mdx_rouse_synchronize(mdx_rouse_t h)

@@ -60,13 +60,9 @@ static int vh_zero(mdx_vh *h)
 // the device side of the handle: stream, tables, counters and accumulators
 static int vh_ensure_device(mdx_vh *h)
 {
-    MDX_TRY(set_device(h->dev));
     if (h->ready)
-        return MDX_OK;
-    if (!h->stream) {
-        MDX_TRY(stream_acquire(&h->stream));
-        h->timer.stream = h->stream;
-    }
+        return set_device(h->dev);
+    MDX_TRY(h->acquire_stream());
     const int64_t n = h->n_points;
     MDX_TRY(h->d_tiles.ensure(sizeof(VhTile) * h->tiles.size()));
     MDX_TRY(h->d_offsets.ensure(size_t(8) * (h->n_groups + 1)));
@@ -247,36 +243,25 @@ int mdx_vh_set_slab_frames(mdx_vh_t h, int64_t frames)
     return MDX_OK;
 }
 
+// what a route prepares before the first kernel
+static int vh_prepare(mdx_vh *h, int64_t)
+{
+    MDX_TRY(vh_ensure_device(h));
+    return vh_ensure_history(h);
+}
+
 int mdx_vh_accumulate_device(mdx_vh_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                              const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
-    const int64_t n = index ? n_index : n_atoms;
-    MDX_REQUIRE(n == h->n_points, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_points);
-    MDX_TRY(check_particle_index(index, n_index, n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(vh_ensure_device(h));
-    MDX_TRY(vh_ensure_history(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return vh_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_points, "groups",
+                                vh_prepare, vh_accumulate_rows);
 }
 
 int mdx_vh_accumulate(mdx_vh_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
-    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
-    MDX_REQUIRE(n == h->n_points, "%lld rows given, the groups hold %lld", (long long)n, (long long)h->n_points);
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(vh_ensure_device(h));
-    MDX_TRY(vh_ensure_history(h));
-    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return vh_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_host(pos, n, n_frames, h->n_points, "groups", vh_prepare, vh_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -285,22 +270,8 @@ int mdx_vh_accumulate_traj(mdx_vh_t h, mdx_traj_t traj, const int64_t *frames, i
                            const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
-    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
-    Trajectory *t = mdx_traj_internal(traj);
-    int64_t n = 0;
-    MDX_TRY(traj_selection(t, index, n_index, &n));
-    MDX_REQUIRE(n == h->n_points, "%lld rows selected, the groups hold %lld", (long long)n, (long long)h->n_points);
-    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(vh_ensure_device(h));
-    MDX_TRY(vh_ensure_history(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return vh_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_points,
+                              "groups", vh_prepare, vh_accumulate_rows);
 }
 
 int mdx_vh_synchronize(mdx_vh_t h)

@@ -13,6 +13,7 @@
 #include "mdx_common.hpp"
 #include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_pairs_host.hpp"
 #include "mdx_vanhove_distinct_device.hpp"
 
 #include <algorithm>
@@ -35,7 +36,7 @@ struct mdx_vhd : FrameEngine {
     int64_t max_lag = 0, origin_step = 1;
     int64_t evaluations = 0;
     int64_t cap = 0;                    // frames the ring holds
-    VhdBox box;
+    PairBox box;
     double inv_width = 0.0, r2_lo = 0.0, r2_hi = 0.0;
     std::vector<int64_t> lags;
     std::vector<double> edges;
@@ -44,9 +45,7 @@ struct mdx_vhd : FrameEngine {
 
 static int64_t vhd_slab(const mdx_vhd *h)
 {
-    if (h->slab_frames > 0)
-        return h->slab_frames;
-    return std::min(VHD_SLAB_MAX, std::max<int64_t>(1, VHD_HISTORY_BYTES / (12 * h->n_rows)));
+    return pair_slab_frames(h->slab_frames, VHD_HISTORY_BYTES, 12 * h->n_rows);
 }
 
 static int vhd_zero(mdx_vhd *h)
@@ -58,13 +57,9 @@ static int vhd_zero(mdx_vhd *h)
 // the device side of the handle: stream, tables and counters
 static int vhd_ensure_device(mdx_vhd *h)
 {
-    MDX_TRY(set_device(h->dev));
     if (h->ready)
-        return MDX_OK;
-    if (!h->stream) {
-        MDX_TRY(stream_acquire(&h->stream));
-        h->timer.stream = h->stream;
-    }
+        return set_device(h->dev);
+    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
     MDX_TRY(h->d_edges.ensure(size_t(8) * (h->n_bins + 1)));
     MDX_TRY(h->d_counts.ensure(size_t(8) * h->n_lags * h->n_bins));
@@ -111,8 +106,7 @@ static int vhd_accumulate_rows(mdx_vhd *h, const float *d_pos, int64_t src_rows,
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f0 = h->frames_seen;
-        hipLaunchKernelGGL(vhd_prepare_kernel, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf), dim3(256),
-                           0, h->stream, pos, src_rows, d_index, n, f0, h->cap, h->d_ring.as<float>());
+        launch_gather<true>(h->stream, pos, src_rows, d_index, n, nf, h->d_ring.as<float>(), f0, h->cap);
         const dim3 grid((unsigned)blocks, (unsigned)h->n_lags, (unsigned)nf);
         const auto kernel = lds ? (h->keep == 7 ? vhd_pair_kernel<true, true> : vhd_pair_kernel<true, false>)
                                 : (h->keep == 7 ? vhd_pair_kernel<false, true> : vhd_pair_kernel<false, false>);
@@ -160,15 +154,10 @@ int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, in
         MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
         MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
     }
-    for (int c = 0; c < 3; ++c)
-        MDX_REQUIRE(dims[c] > 0.0 && std::isfinite(dims[c]), "dims[%d] must be positive and finite", c);
-    double shortest = HUGE_VAL;
-    for (int c = 0; c < 3; ++c)
-        if (!(zero_dims >> c & 1))
-            shortest = std::min(shortest, dims[c]);
-    // beyond half a box length the minimum image is not the nearest image
-    MDX_REQUIRE(edges[n_bins] <= shortest / 2, "edges reach %g, beyond half the shortest box length %g",
-                edges[n_bins], shortest);
+    PairBox box;
+    int keep = 7;
+    MDX_TRY(check_box_cutoff(dims, zero_dims, edges[n_bins], &box, &keep,
+                             "edges reach %g, beyond half the shortest box length %g"));
     MDX_REQUIRE(int64_t(n_lags) * n_bins < (int64_t(1) << 31), "too many counters");
     mdx_vhd *h = new mdx_vhd();
     h->dev = dev;
@@ -178,16 +167,13 @@ int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, in
     h->n_rows = same ? n1 : n1 + n2;
     h->n_bins = n_bins;
     h->n_lags = n_lags;
-    h->keep = 7 & ~zero_dims;
+    h->keep = keep;
+    h->box = box;
     h->origin_step = origin_step;
     h->max_lag = lags[n_lags - 1];
     h->lags.assign(lags, lags + n_lags);
     h->edges.assign(edges, edges + n_bins + 1);
     h->inv_width = double(n_bins) / (edges[n_bins] - edges[0]);
-    for (int c = 0; c < 3; ++c) {
-        h->box.L[c] = dims[c];
-        h->box.inv[c] = 1.0 / dims[c];
-    }
     // the margins of the early rejection (mdx_vanhove_distinct_device.hpp); an upper edge below 0 counts nothing
     const double lo = edges[0], hi = edges[n_bins], margin = std::ldexp(1.0, -40);
     h->r2_lo = lo > 0.0 ? (lo * lo) * (1.0 - margin) : 0.0;
@@ -230,36 +216,25 @@ int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames)
     return MDX_OK;
 }
 
+// what a route prepares before the first kernel
+static int vhd_prepare(mdx_vhd *h, int64_t)
+{
+    MDX_TRY(vhd_ensure_device(h));
+    return vhd_ensure_ring(h);
+}
+
 int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
-    MDX_REQUIRE(n_atoms > 0 && n_frames >= 0 && (!index || n_index > 0), "bad size");
-    const int64_t n = index ? n_index : n_atoms;
-    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    MDX_TRY(check_particle_index(index, n_index, n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(vhd_ensure_device(h));
-    MDX_TRY(vhd_ensure_ring(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return vhd_accumulate_rows(h, d_pos, n_atoms, d_index, n, n_frames);
+    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "sets", vhd_prepare,
+                                vhd_accumulate_rows);
 }
 
 int mdx_vhd_accumulate(mdx_vhd_t h, const float *pos, int64_t n, int64_t n_frames)
 {
     MDX_REQUIRE(h && pos, "NULL argument");
-    MDX_REQUIRE(n > 0 && n_frames >= 0, "bad size");
-    MDX_REQUIRE(n == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(vhd_ensure_device(h));
-    MDX_TRY(vhd_ensure_ring(h));
-    return h->feed.host(h->dev, h->stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return vhd_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_host(pos, n, n_frames, h->n_rows, "sets", vhd_prepare, vhd_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
@@ -268,22 +243,8 @@ int mdx_vhd_accumulate_traj(mdx_vhd_t h, mdx_traj_t traj, const int64_t *frames,
                             const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && traj, "NULL handle");
-    MDX_REQUIRE(n_frames >= 0 && (n_frames == 0 || frames), "bad frame list");
-    Trajectory *t = mdx_traj_internal(traj);
-    int64_t n = 0;
-    MDX_TRY(traj_selection(t, index, n_index, &n));
-    MDX_REQUIRE(n == h->n_rows, "%lld rows selected, the sets hold %lld", (long long)n, (long long)h->n_rows);
-    MDX_TRY(check_particle_index(index, n_index, t->n_atoms));
-    if (n_frames == 0)
-        return MDX_OK;
-    MDX_TRY(vhd_ensure_device(h));
-    MDX_TRY(vhd_ensure_ring(h));
-    const int *d_index = nullptr;
-    MDX_TRY(h->feed.upload_index(h->stream, index, n_index, &d_index));
-    return h->feed.traj(h->dev, h->stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
-                        [&](const float *d_pos, int64_t nf) -> int {
-                            return vhd_accumulate_rows(h, d_pos, n, nullptr, n, nf);
-                        });
+    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "sets",
+                              vhd_prepare, vhd_accumulate_rows);
 }
 
 int mdx_vhd_synchronize(mdx_vhd_t h)

@@ -1,17 +1,12 @@
 // mdx_vanhove_distinct_device.hpp — device side of the distinct van Hove engine (mdx_vanhove_distinct.hip).
 //
 // Result contract.  Set 1 holds n1 rows, set 2 holds n2 rows; incoming rows are set 1 then set 2.  With `same` both
-// are one set (n1 == n2, the rows arrive once) and the pair i == j is left out.  Box lengths L_c; inv_c = 1.0 / L_c
-// is formed once on the host in float64 and handed to the device.  Analysed frames are numbered f = 0, 1, ... in the
-// order fed; `lags` is strictly increasing and non-negative; origin_step >= 1.  The frame pairs of lag k are
-// (f0, f0 + lags[k]) with f0 % origin_step == 0 and f0 + lags[k] < F.  Everything is float64, one operation at a time
-// (the unit is built with contraction off); float32 coordinates are widened before any arithmetic.  For every such
-// frame pair and every pair (i of set 1 at f0, j of set 2 at f0 + lag):
+// are one set (n1 == n2, the rows arrive once) and the pair i == j is left out.  Analysed frames are numbered
+// f = 0, 1, ... in the order fed; `lags` is strictly increasing and non-negative; origin_step >= 1.  The frame pairs
+// of lag k are (f0, f0 + lags[k]) with f0 % origin_step == 0 and f0 + lags[k] < F.  Box and pair arithmetic: those of
+// mdx_pairs_device.hpp, for every such frame pair and every pair (i of set 1 at f0, j of set 2 at f0 + lag):
 //
-//     d_c = x2_jc(f0 + lag) - x1_ic(f0)
-//     s   = d_c * inv_c ;  w_c = d_c - L_c * rint(s)          (rint: ties to even, as numpy.rint;
-//                                                              w_c = +0.0 for a component zero_dims drops)
-//     r2  = (w_x*w_x + w_y*w_y) + w_z*w_z ;  r = sqrt(r2), correctly rounded
+//     d_c = x2_jc(f0 + lag) - x1_ic(f0) ;  w_c and r2 as stated there ;  r = sqrt(r2), correctly rounded
 //     counts[k][b] += 1   where  edges[b] <= r < edges[b+1]    (the last bin also takes r == edges[n_bins];
 //                                                              r outside the edges or not finite: not counted)
 //
@@ -34,13 +29,12 @@
 // correctly rounded r is greater than hi and would not have been counted.  The lower side is the mirror image.  A
 // NaN r2 fails both comparisons of the keep test and is dropped, as the contract says.
 //
-// Shape.  vhd_prepare_kernel gathers the rows of each incoming frame into a ring of frames in HBM,
+// Shape.  gather_kernel (its ring form) gathers the rows of each incoming frame into a ring of frames in HBM,
 // ring[f % cap][c][p] (component-major float32: widening is exact and happens in registers), cap = max(lags) + the
-// frames of a slab, so that a lag reaches back across slabs and calls.  vhd_pair_kernel: grid x = i tiles x j chunks,
-// y = lags, z = the new frames f of the launch; the block of (f, k) is the frame pair (f - lags[k], f) and leaves at
-// once when that is no pair of the contract.  A block holds VHD_TILE points of set 1 at f0 in registers, one per
-// lane, widened, and walks its chunk of at most VHD_JCHUNK points of set 2 at f0 + lag in stages of VHD_STAGE
-// points through LDS (widened once when staged: all lanes read the same j at once, a broadcast).  The edges are
+// frames of a slab, so that a lag reaches back across slabs and calls.  vhd_pair_kernel is the walk of
+// mdx_pairs_device.hpp with y = lags, z = the new frames f of the launch and VHD_JCHUNK points of set 2 per block;
+// the block of (f, k) is the frame pair (f - lags[k], f) and leaves at once when that is no pair of the contract:
+// the lanes hold set 1 at f0 and the stages set 2 at f0 + lag.  The edges are
 // copied to LDS once per block, so the bin rule's fix-up reads no global memory.  Every wave counts
 // into its own uint32 histogram in LDS; at the end the block adds the waves' histograms bin by bin and sends the
 // non-zero sums to the global uint64 counts with one integer atomic each.  A wave's LDS counter receives at most
@@ -51,43 +45,23 @@
 // the range, so the early rejection rarely spares a whole wave.  Culling by cells is the follow-up.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "mdx_pairs_device.hpp"
 
 namespace mdx_vhd_dev {
 
-constexpr int VHD_TILE = 256;                 // set-1 points per block, one per lane
-constexpr int VHD_THREADS = VHD_TILE;
-constexpr int VHD_WAVES = VHD_THREADS / 64;
-constexpr int VHD_STAGE = VHD_THREADS;        // set-2 points per LDS stage, one staged per thread
+using namespace mdx_pairs_dev;
+
+constexpr int VHD_TILE = PAIR_TILE;           // set-1 points per block, one per lane
+constexpr int VHD_THREADS = PAIR_THREADS;
+constexpr int VHD_WAVES = PAIR_WAVES;
+constexpr int VHD_STAGE = PAIR_STAGE;         // set-2 points per LDS stage, one staged per thread
 constexpr int VHD_JCHUNK = 2 * VHD_STAGE;     // set-2 points per block; 64 lanes x VHD_JCHUNK = 2^15 < 2^32 counts
                                               // per wave's uint32 LDS counter and launch
 // n_bins up to which the edges and the waves' histograms live in LDS: 2049 x 8 B + 4 waves x 2048 x 4 B = 48 KiB next
 // to the 8 KiB stage: inside the 64 KiB a launch gets without asking for more
 constexpr int VHD_LDS_BINS = 2048;
-constexpr int64_t VHD_SLAB_MAX = 32768;       // frames per launch, at most (grid z)
+constexpr int64_t VHD_SLAB_MAX = PAIR_SLAB_MAX;         // frames per launch, at most (grid z)
 constexpr int VHD_LAGS_MAX = 65535;           // lags, at most (grid y)
-
-// Row index[p] (or p) of n_frames float32 frames of src_rows rows into the ring: ring[(((f0 + f) % cap) * 3 + c) *
-// n_points + p].  One thread per coordinate (t = c * n_points + p: a wave writes consecutive floats); grid y = frames.
-__global__ __launch_bounds__(256) void vhd_prepare_kernel(const float *__restrict__ pos, int64_t src_rows,
-                                                          const int *__restrict__ index, int n_points, int64_t f0,
-                                                          int64_t cap, float *__restrict__ ring)
-{
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= 3 * n_points)
-        return;
-    const int c = t / n_points, p = t - c * n_points;
-    const int64_t r = index ? index[p] : p;
-    const int64_t f = blockIdx.y;
-    const int64_t slot = (f0 + f) % cap;
-    ring[(slot * 3 + c) * n_points + p] = pos[(f * src_rows + r) * 3 + c];
-}
-
-struct VhdBox {
-    double L[3], inv[3];
-};
 
 // The b with edges[b] <= r < edges[b + 1] (the last bin closed on the right), or -1: vh_bin of mdx_vanhove_device.hpp,
 // copied because that header also defines the self engine's kernels and belongs in one unit only.
@@ -105,19 +79,13 @@ __device__ __forceinline__ int vhd_bin(double r, const double *__restrict__ edge
     return b;
 }
 
-// w = d - L * rint(d * inv), one operation at a time
-__device__ __forceinline__ double vhd_min_image(double d, double L, double inv)
-{
-    return __dsub_rn(d, __dmul_rn(L, rint(__dmul_rn(d, inv))));
-}
-
 // The frame pairs (f - lags[k], f), f = f_lo + blockIdx.z, k = blockIdx.y.  n_points: rows of a ring frame; set 2
 // starts at row off2 (0 with same).  keep: bit c set -> component c takes part; ALL: keep == 7, known when compiled,
 // so that the loop over j has no branch before the range test.  counts: uint64 [n_lags][n_bins].
 template <bool USE_LDS, bool ALL>
 __global__ __launch_bounds__(VHD_THREADS) void vhd_pair_kernel(
     const float *__restrict__ ring, int64_t cap, int n_points, int n1, int n2, int off2, int same, int n_jchunks,
-    const int64_t *__restrict__ lags, int64_t f_lo, int64_t origin_step, VhdBox box, int keep,
+    const int64_t *__restrict__ lags, int64_t f_lo, int64_t origin_step, PairBox box, int keep,
     const double *__restrict__ edges, int n_bins, double inv_width, double r2_lo, double r2_hi,
     unsigned long long *__restrict__ counts)
 {
@@ -152,34 +120,24 @@ __global__ __launch_bounds__(VHD_THREADS) void vhd_pair_kernel(
     for (int js = j_begin; js < j_end; js += VHD_STAGE) {
         const int nj = j_end - js < VHD_STAGE ? j_end - js : VHD_STAGE;
         __syncthreads();                    // the stage is free (and, the first time, histograms and edges are set)
-        if ((int)threadIdx.x < nj) {
-            const float *__restrict__ src = b + js + threadIdx.x;
-            stage[4 * threadIdx.x + 0] = (double)src[0];
-            stage[4 * threadIdx.x + 1] = (double)src[n_points];
-            stage[4 * threadIdx.x + 2] = (double)src[2 * int64_t(n_points)];
-        }
+        if ((int)threadIdx.x < nj)
+            stage_partners(stage, b, n_points, js);
         __syncthreads();
         if (!live)
             continue;
         const int skip = same ? i - js : -1;        // the stage entry that is this lane's own point
-#pragma unroll 4
-        for (int jj = 0; jj < nj; ++jj) {
-            const double dx = __dsub_rn(stage[4 * jj + 0], xi), dy = __dsub_rn(stage[4 * jj + 1], yi),
-                         dz = __dsub_rn(stage[4 * jj + 2], zi);
-            const double wx = ALL || keep & 1 ? vhd_min_image(dx, box.L[0], box.inv[0]) : 0.0;
-            const double wy = ALL || keep & 2 ? vhd_min_image(dy, box.L[1], box.inv[1]) : 0.0;
-            const double wz = ALL || keep & 4 ? vhd_min_image(dz, box.L[2], box.inv[2]) : 0.0;
-            const double r2 = __dadd_rn(__dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy)), __dmul_rn(wz, wz));
-            if (r2 >= r2_lo && r2 <= r2_hi && jj != skip) {
-                const int bin = vhd_bin(__dsqrt_rn(r2), bin_edges, n_bins, inv_width);
-                if (bin >= 0) {
-                    if (USE_LDS)
-                        atomicAdd(&mine[bin], 1u);
-                    else
-                        atomicAdd(&row[bin], 1ull);
-                }
-            }
-        }
+        stage_pairs<ALL>(stage, nj, js, skip, xi, yi, zi, box, keep,
+                         [&](int, int, double, double, double, double r2, bool other) {
+                             if (r2 >= r2_lo && r2 <= r2_hi && other) {
+                                 const int bin = vhd_bin(__dsqrt_rn(r2), bin_edges, n_bins, inv_width);
+                                 if (bin >= 0) {
+                                     if (USE_LDS)
+                                         atomicAdd(&mine[bin], 1u);
+                                     else
+                                         atomicAdd(&row[bin], 1ull);
+                                 }
+                             }
+                         });
     }
     if (USE_LDS) {
         __syncthreads();

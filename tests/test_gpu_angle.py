@@ -177,6 +177,18 @@ def test_more_ligands_than_one_chunk():
     assert_same(engine_run(pos, n0, [300, 725], [6.0, 4.0], ANGLE180, BOX), two, n0)
 
 
+@pytest.mark.parametrize("n_lig", [_core.AngleEngine.JCHUNK - 1, _core.AngleEngine.JCHUNK])
+def test_ligands_just_inside_one_chunk(n_lig):
+    """T + 1 centres (a second tile of one live lane) and JCHUNK - 1 and JCHUNK ligands: the last stage of the one
+    chunk is one ligand short, and full.  Two groups with two cutoffs whose border lies inside the second stage."""
+    n0 = T + 1
+    pos = walk(600 + n_lig, 2, n0 + n_lig, step=0.25)
+    sizes = [300, n_lig - 300]
+    want = restate(pos, n0, sizes, [6.0, 4.0], ANGLE180, BOX)
+    assert 2 <= want["max_row"] <= 32 and want["counts"].any(axis=1).all()
+    assert_same(engine_run(pos, n0, sizes, [6.0, 4.0], ANGLE180, BOX), want, n0)
+
+
 @pytest.fixture(scope="module")
 def two_species():
     """Frames of 130 centres + 100 + 91 ligands, shared and left unchanged."""

@@ -24,6 +24,7 @@ from mdhelper_amd.analysis import Clusters
 pytestmark = pytest.mark.gpu
 
 T = _core.ClusterEngine.TILE
+J = _core.ClusterEngine.JCHUNK
 BOX = np.array([31.0, 44.5, 57.25])
 ARRAYS = ("size_counts", "species_counts", "bonds", "n_clusters", "largest", "sum_squares", "labels")
 SCALARS = ("evaluations", "frames", "max_row")
@@ -165,6 +166,19 @@ def test_one_species_sizes(n):
             np.testing.assert_array_equal(want["n_clusters"], [1, 1, 1])            # one percolating cluster
             np.testing.assert_array_equal(want["largest"], [n, n, n])
             assert want["size_counts"][n] == 3
+
+
+@pytest.mark.parametrize("n", [J - 1, J, J + 1])
+def test_partners_around_one_chunk(n):
+    """JCHUNK - 1, JCHUNK and JCHUNK + 1 rows: the last is a second chunk of one partner that appends to the same
+    rows, and that partner is the own row of the one live lane of the last tile.  One species (the bound is a kernel
+    argument), then two whose border lies inside a stage (the bound of that stage is looked up pair by pair)."""
+    pos = walk(500 + n, 2, n, step=0.25)
+    for species, cutoff in ((np.zeros(n, dtype=np.int32), 4.5),
+                            ((np.arange(n) >= 3 * T + 7).astype(np.int32), [[4.5, 5.0], [5.0, 0.0]])):
+        want = restate(pos, species, cutoff, BOX)
+        assert 1 <= want["max_row"] <= 32 and want["bonds"].all()
+        assert_same(engine_run(pos, species, cutoff, BOX), want)
 
 
 @pytest.fixture(scope="module")

@@ -23,6 +23,7 @@ from mdhelper_amd.analysis import PairResidence, calculate_residence_time
 pytestmark = pytest.mark.gpu
 
 T = _core.PairResidenceEngine.TILE
+J = _core.PairResidenceEngine.JCHUNK
 LAGS = [0, 1, 2, 5, 8, 11, 13]          # lag 13 never has an origin in 12 frames
 BOX = np.array([31.0, 44.5, 57.25])
 CUTOFF = 6.0
@@ -150,6 +151,24 @@ def test_two_sets_sizes_and_frame_counts(n1, n2):
             assert got[key][6] == 0
     with pytest.raises(ValueError, match="rows given"):
         engine_run(x1, x2, CUTOFF, LAGS, BOX, setup=lambda e: e.accumulate(pos[:, :-1]))      # wrong row count
+
+
+@pytest.mark.parametrize("n2", [J - 1, J, J + 1])
+def test_partners_around_one_chunk_and_rings_that_wrap_inside_one_call(n2):
+    """JCHUNK - 1, JCHUNK and JCHUNK + 1 partners (the last: a second chunk of one partner appends to the same rows)
+    against T + 1 points (a second tile of one live lane).  Lags 0 and 1 with slabs of one frame: the rings hold two
+    frames, so the third frame of the one call goes into the slot of the first."""
+    n1 = T + 1
+    pos = walk(300 + n2, 3, n1 + n2, step=0.25)
+    x1, x2 = pos[:, :n1], pos[:, n1:]
+    want = restate(x1, x2, 4.0, [0, 1], BOX)
+    assert 1 <= want["max_row"] <= 32 and want["intermittent"].all()
+    assert_same(engine_run(x1, x2, 4.0, [0, 1], BOX, setup=lambda e: e.set_slab_frames(1)), want)
+    if n2 == J + 1:
+        # one set: the second chunk's only partner is the own point of the one live lane of the last tile
+        one = pos[:, :n2]
+        assert_same(engine_run(one, None, 4.0, [0, 1], BOX, setup=lambda e: e.set_slab_frames(1)),
+                    restate(one, None, 4.0, [0, 1], BOX))
 
 
 def test_the_issue_figures_for_321_points():

@@ -20,6 +20,7 @@ from mdhelper_amd.analysis import DistinctVanHove
 pytestmark = pytest.mark.gpu
 
 T = _core.DistinctVanHoveEngine.TILE
+J = _core.DistinctVanHoveEngine.JCHUNK
 LAGS = [0, 1, 2, 5, 8, 10]             # lag 10 never has an origin in 9 frames
 BOX = np.array([31.0, 44.5, 57.25])
 EDGES = np.linspace(0.0, 15.0, 202)    # 15 <= 15.5, half the shortest length
@@ -132,6 +133,24 @@ def test_two_sets_sizes_and_frame_counts(n1, n2):
         assert not got[0][5].any()
     with pytest.raises(ValueError, match="rows given"):
         engine_run(x1, x2, EDGES, LAGS, BOX, setup=lambda e: e.accumulate(pos[:, :-1]))       # wrong row count
+
+
+@pytest.mark.parametrize("n2", [J - 1, J, J + 1])
+def test_partners_around_one_chunk_and_a_ring_that_wraps_inside_one_call(n2):
+    """JCHUNK - 1, JCHUNK and JCHUNK + 1 partners (the last: a second chunk of one partner counts into the same bins)
+    against T + 1 points (a second tile of one live lane).  Lags 0 and 1 with slabs of one frame: the ring holds two
+    frames, so the third frame of the one call goes into the slot of the first."""
+    n1 = T + 1
+    pos = walk(300 + n2, 3, n1 + n2)
+    x1, x2 = pos[:, :n1], pos[:, n1:]
+    want = restate(x1, x2, EDGES, [0, 1], BOX)
+    assert want[0].sum(axis=-1).all()
+    assert_same(engine_run(x1, x2, EDGES, [0, 1], BOX, setup=lambda e: e.set_slab_frames(1)), want, 3)
+    if n2 == J + 1:
+        # one set: the second chunk's only partner is the own point of the one live lane of the last tile
+        one = pos[:, :n2]
+        assert_same(engine_run(one, None, EDGES, [0, 1], BOX, setup=lambda e: e.set_slab_frames(1)),
+                    restate(one, None, EDGES, [0, 1], BOX), 3)
 
 
 @pytest.mark.parametrize("n", [65, T + 1])
