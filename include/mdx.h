@@ -925,6 +925,59 @@ int mdx_ang_stats(mdx_ang_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *triplets, int64_t *max_row);
 int mdx_ang_enable_timing(mdx_ang_t h, int on);
 
+/* ---- orientational relaxation: P1 / P2 reorientation of unit vectors and their order tensor ----------------------------
+ * A frame delivers n_rows points; pairs: int32 [V][2] row numbers (tail, head) of the V vectors, tail != head; group g
+ * holds n_vectors[g] consecutive vectors (a group may be empty, all of them together may not).  Analysed frames are
+ * numbered f = 0, 1, ... in the order fed; lags: strictly increasing, non-negative frame offsets (0 allowed).  In
+ * float64 with separate multiply and add (float32 coordinates are widened before any arithmetic), per vector and frame:
+ *     d = x_head - x_tail;  w = d - L * rint(d * (1.0 / L)) with a box (mdx_ori_set_box), else w = d; +0.0 for a
+ *     dropped component;  n2 = (wx*wx + wy*wy) + wz*wz;  u = w / sqrt(n2)  (sqrt and divide correctly rounded);
+ * per vector v, lag k and frame f >= lags[k]:
+ *     c = (ux(f)*ux(f-lag) + uy(f)*uy(f-lag)) + uz(f)*uz(f-lag);  acc[k][v][0] += c;  acc[k][v][1] += 1.5*(c*c) - 0.5;
+ * and per frame f, group g and product ab = xx, xy, xz, yy, yz, zz:  frame_sums[f][g][ab] = sum of ua*ub.
+ * zero_dims: bit k drops component k.  The accumulator of a (lag, vector) receives its terms in frame order, a group's
+ * sums add the accumulators of its vectors in row order, and the products are added per tile of 64 vectors in row
+ * order and then per group in tile order (csrc/mdx_orient_device.hpp); no floating-point atomics are used, so every
+ * result is bit-identical across the three input routes, across any split of the frames into calls or slabs, and
+ * after a reset.  A vector with n2 == 0 or n2 not finite has no direction: it is never averaged silently, and
+ * mdx_ori_synchronize, mdx_ori_result, mdx_ori_vector_sums and mdx_ori_frame_sums fail with MDX_ERR_INVALID_VALUE
+ * (the message counts such vectors) until mdx_ori_reset.  The engine keeps max(lags) + one slab of float64 frames of
+ * unit vectors in HBM (MDX_ERR_OUT_OF_MEMORY when that does not fit).  A handle touches its device with the first
+ * frame: mdx_ori_create and every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_ori *mdx_ori_t;
+int mdx_ori_create(mdx_ori_t *out, int dev, int n_groups, const int64_t *n_vectors, int64_t n_rows,
+                   const int32_t *pairs, int n_lags, const int64_t *lags, int zero_dims);
+int mdx_ori_destroy(mdx_ori_t h);
+/* Forgets the frames seen, the history and the degenerate vectors and zeroes the sums. */
+int mdx_ori_reset(mdx_ori_t h);
+/* One constant orthorhombic box for the minimum image of head - tail.  dims: float64 [3] box lengths, or NULL: none
+ * (molecules that are whole already).  Only before the first frame. */
+int mdx_ori_set_box(mdx_ori_t h, const double *dims);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history), as
+ * mdx_vh_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
+int mdx_ori_set_slab_frames(mdx_ori_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n_rows. */
+int mdx_ori_accumulate(mdx_ori_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in the order the
+ * pairs name them, or NULL for all n_atoms rows.  Asynchronous (mdx_ori_synchronize). */
+int mdx_ori_accumulate_device(mdx_ori_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_ori_accumulate_traj(mdx_ori_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_ori_synchronize(mdx_ori_t h);
+/* sums: float64 [n_lags][n_groups][2] = sum c, sum 1.5*c*c - 0.5 over the group's vectors and every frame pair of the
+ * lag. */
+int mdx_ori_result(mdx_ori_t h, double *sums);
+/* out: float64 [n_lags][V][2]: the accumulators of every vector. */
+int mdx_ori_vector_sums(mdx_ori_t h, double *out);
+/* out: float64 [n][n_groups][6], the product sums of the first n frames seen. */
+int mdx_ori_frame_sums(mdx_ori_t h, double *out, int64_t n);
+/* evaluations: dot products formed so far (frame pairs x vectors, summed over the lags); degenerate: vectors without
+ * a direction seen since the last reset (not zero: the results are refused). */
+int mdx_ori_stats(mdx_ori_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *degenerate);
+int mdx_ori_enable_timing(mdx_ori_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1139,6 +1139,72 @@ class AngleEngine(_SlabbedFrameEngine):
         return out
 
 
+class OrientationEngine(_SlabbedFrameEngine):
+    """``mdx_ori_*``: per frame the unit vectors ``u`` from row ``pairs[v, 0]`` to row ``pairs[v, 1]`` of the ``n_rows``
+    incoming rows (with the minimum image where ``set_box`` gave a box), per lag and vector the sums of
+    ``c = u(f) . u(f - lag)`` and of ``1.5 c^2 - 0.5`` over the frames, and per frame and group the sums of the six
+    products ``u_a u_b``, in float64.  Group ``g`` holds ``n_vectors[g]`` consecutive vectors.  A vector without a
+    direction (head on its tail, or a length that is not finite) makes ``synchronize()``, ``result()``,
+    ``vector_sums()`` and ``frame_sums()`` raise ``ValueError`` until ``reset()``.  The device is first touched by the
+    first frame, so the argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_ori"
+    _stats_extra = (("evaluations", c_int64), ("degenerate", c_int64))
+    TILE = 64           # vectors per tile: a tile never spans two groups (ORI_TILE of csrc/mdx_orient_device.hpp)
+
+    def __init__(self, n_vectors, pairs, n_rows, lags, *, zero_dims=0, dev=0, timing=False):
+        self.n_per_group = np.ascontiguousarray(np.atleast_1d(n_vectors), dtype=np.int64)
+        if self.n_per_group.ndim != 1 or len(self.n_per_group) == 0:
+            raise ValueError("n_vectors must hold one entry per group.")
+        self.n_groups = len(self.n_per_group)
+        self.n_vectors = int(self.n_per_group.sum())
+        self.pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+        if self.pairs.ndim != 2 or self.pairs.shape[1] != 2 or len(self.pairs) != max(self.n_vectors, 0):
+            raise ValueError("pairs must hold one (tail, head) row per vector of the groups.")
+        self.n_rows = int(n_rows)
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        h = c_void_p()
+        check(lib().mdx_ori_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), self.n_rows,
+                                   _ptr(self.pairs), self.n_lags, _ptr(self.lags), int(zero_dims)))
+        self._adopt(h, dev, timing)
+
+    def set_box(self, dims):
+        """The box lengths ``dims`` of one constant orthorhombic box: ``head - tail`` is then the minimum image.
+        ``dims=None``: no box, for molecules that are whole already.  Only before the first frame."""
+        if dims is None:
+            check(lib().mdx_ori_set_box(self.handle, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        check(lib().mdx_ori_set_box(self.handle, _ptr(d)))
+
+    def result(self):
+        """float64 ``[n_lags, G, 2]``: the sums of ``c`` and of ``1.5 c^2 - 0.5`` over the group's vectors and every
+        frame pair of the lag."""
+        sums = np.zeros((self.n_lags, self.n_groups, 2), dtype=np.float64)
+        check(lib().mdx_ori_result(self.handle, _ptr(sums)))
+        return sums
+
+    def vector_sums(self):
+        """float64 ``[n_lags, V, 2]``: every vector's own sums."""
+        out = np.zeros((self.n_lags, self.n_vectors, 2), dtype=np.float64)
+        check(lib().mdx_ori_vector_sums(self.handle, _ptr(out)))
+        return out
+
+    def frame_sums(self):
+        """float64 ``[frames seen, G, 6]``: the sums of ``u_a u_b`` over the group's vectors, ``ab = xx, xy, xz, yy,
+        yz, zz``, of every frame seen."""
+        frames = c_int64()
+        check(lib().mdx_ori_stats(self.handle, None, None, byref(frames), None, None))
+        out = np.zeros((frames.value, self.n_groups, 6), dtype=np.float64)
+        check(lib().mdx_ori_frame_sums(self.handle, _ptr(out), len(out)))
+        return out
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

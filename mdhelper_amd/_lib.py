@@ -291,6 +291,22 @@ _SIGNATURES = {
     "mdx_ang_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64), POINTER(c_int64)]),
     "mdx_ang_enable_timing": (c_int, [_vp, c_int]),
+    # orientational relaxation (P1 / P2 of unit vectors, order tensor)
+    "mdx_ori_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int64, _vp, c_int, _vp, c_int]),
+    "mdx_ori_destroy": (c_int, [_vp]),
+    "mdx_ori_reset": (c_int, [_vp]),
+    "mdx_ori_set_box": (c_int, [_vp, _vp]),
+    "mdx_ori_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_ori_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_ori_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_ori_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_ori_synchronize": (c_int, [_vp]),
+    "mdx_ori_result": (c_int, [_vp, _vp]),
+    "mdx_ori_vector_sums": (c_int, [_vp, _vp]),
+    "mdx_ori_frame_sums": (c_int, [_vp, _vp, c_int64]),
+    "mdx_ori_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64)]),
+    "mdx_ori_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

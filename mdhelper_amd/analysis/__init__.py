@@ -5,8 +5,8 @@ from .structure import (IntermediateScatteringFunction, RadialDistributionFuncti
                         StructureFactor)
 from .angle import AngularDistribution  # noqa: F401
 from .cluster import Clusters  # noqa: F401
-from .dynamics import (DistinctVanHove, PairResidence, VanHove, calculate_non_gaussian_parameter,  # noqa: F401
-                       calculate_residence_time)
+from .dynamics import (DistinctVanHove, OrientationalRelaxation, PairResidence, VanHove,  # noqa: F401
+                       calculate_non_gaussian_parameter, calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
 from .polymer import (EndToEndVector, Gyradius, InternalDistances, RouseModes,  # noqa: F401
                       SingleChainStructureFactor)

@@ -3,7 +3,8 @@ Real-space dynamics: ``VanHove`` — the self part of the van Hove function ``G_
 displacement magnitudes after a lag and the non-Gaussian parameter — ``calculate_non_gaussian_parameter``, and
 ``DistinctVanHove`` — the distinct part ``G_d(r, t)``, the time-dependent pair distribution — and ``PairResidence`` —
 the intermittent and continuous survival functions of the contacts between two groups (ion-pair lifetimes, residence
-times) with ``calculate_residence_time``.
+times) with ``calculate_residence_time`` — and ``OrientationalRelaxation`` — the reorientation functions ``C_1(t)`` and
+``C_2(t)`` of unit vectors (bonds, segments, molecular axes) and their nematic order tensor.
 
 The reference package has no counterpart; this sits next to ``IntermediateScatteringFunction(incoherent=True)``
 (``F_s(q, t)``, the Fourier transform of ``G_s``) and the mean squared displacements of the correlation
@@ -17,7 +18,10 @@ feeds the same blocks to the distinct van Hove engine (``mdx_vhd_*``), which kee
 and bins the minimum-image distance of every pair of points for every (origin, lag) frame pair into integer
 histograms (csrc/mdx_vanhove_distinct_device.hpp).  ``PairResidence`` feeds them to the pair residence engine
 (``mdx_prs_*``), which keeps a history of capped per-atom contact lists in HBM and counts, per lag, the contacts of an
-origin that are there again, or still (csrc/mdx_residence_device.hpp).
+origin that are there again, or still (csrc/mdx_residence_device.hpp).  ``OrientationalRelaxation`` feeds the distinct
+atoms of its vectors to the orientation engine (``mdx_ori_*``), which keeps a history of float64 unit vectors in HBM,
+adds the first and second Legendre polynomials of ``u(f) . u(f - lag)`` per vector in frame order and the products
+``u_a u_b`` of every frame per group (csrc/mdx_orient_device.hpp).
 """
 
 from __future__ import annotations
@@ -451,3 +455,175 @@ class PairResidence(EngineFedAnalysis, DynamicAnalysisBase):
             raise RuntimeError("Call run() before calculate_residence_times().")
         self.results.residence_time = calculate_residence_time(self.results.times, self.results.continuous)
         self.results.relaxation_time = calculate_residence_time(self.results.times, self.results.intermittent)
+
+
+class OrientationalRelaxation(EngineFedAnalysis, DynamicAnalysisBase):
+    r"""
+    Reorientation of unit vectors (bonds, chain segments, molecular axes): with :math:`\mathbf u_v(t)` the unit
+    vector from ``tails[v]`` to ``heads[v]``,
+
+    .. math:: C_1(t)=\big\langle\mathbf u_v(t_0+t)\cdot\mathbf u_v(t_0)\big\rangle_{v,t_0},\qquad
+              C_2(t)=\big\langle\tfrac32\,[\mathbf u_v(t_0+t)\cdot\mathbf u_v(t_0)]^2-\tfrac12\big\rangle_{v,t_0}
+
+    per group of vectors, averaged over every time origin ``t_0`` of the analysed frames — the first and second
+    Legendre polynomials of the angle a vector turns through in ``t``, the quantities behind dielectric (``C_1``) and
+    NMR / depolarised light scattering (``C_2``) relaxation times — and per frame the nematic order tensor
+
+    .. math:: \mathbf Q=\tfrac32\,\langle\mathbf u\,\mathbf u^{\mathsf T}\rangle_v-\tfrac12\,\mathbf I
+
+    with its largest eigenvalue (the order parameter ``S``) and the eigenvector that goes with it (the director).
+
+    Parameters
+    ----------
+    tails, heads : AtomGroup, or two equally long sequences of AtomGroups — vector ``v`` of a group points from
+        ``tails[v]`` to ``heads[v]``; the two groups must be of one length, and no vector may start where it ends.  An
+        atom may sit in many vectors (the bonds along a chain): every distinct atom is read once per frame
+    lags : array-like of int, keyword-only — lag times in frames of the analysed selection, strictly increasing,
+        non-negative
+    n_lags : int, keyword-only — shorthand for ``lags=arange(n_lags)``; with neither, every analysed frame is a lag
+    dt : float, keyword-only — time between trajectory frames (ps); defaults to the trajectory's
+    dimensions : array-like ``(3,)``, keyword-only — box lengths (Å) for the minimum image; defaults to the universe's
+    minimum_image : bool, keyword-only — take ``head - tail`` as its minimum image in one constant orthorhombic box
+        (wrapped trajectories); ``False`` needs no box and suits molecules that are whole already
+    drop_axis : {0, 1, 2, "x", "y", "z"}, keyword-only — a component that takes no part: the vectors are the unit
+        vectors of the projections onto the remaining plane
+    verbose : bool
+    device : keyword-only — the HIP device
+
+    Results
+    -------
+    ``results.times`` ``[N_t]`` (ps), ``results.c1`` and ``results.c2`` ``[N_t, N_g]`` — the engine's sums over
+    ``n_origins V_g`` with ``n_origins = n_frames - lag``; NaN without a warning for a lag without an origin or an empty
+    group — ``results.order_tensor`` ``[N_f, N_g, 3, 3]``, ``results.order_parameter`` ``[N_f, N_g]`` (the largest
+    eigenvalue of ``Q``, ``numpy.linalg.eigvalsh``), ``results.director`` ``[N_f, N_g, 3]`` (a unit vector; its sign
+    means nothing) and ``results.units``.  With ``drop_axis`` the tensor is the two-dimensional form
+    ``Q = 2 <u u^T> - I`` on the kept components (its eigenvalues are ``+S`` and ``-S``); the row and the column of
+    the dropped component are zero, and so is that component of the director.  ``calculate_relaxation_times()`` adds
+    ``results.relaxation_times``.
+
+    Limits: the box is orthorhombic and taken as constant (``dimensions``, or else the universe's box): NPT
+    trajectories are outside the contract.  A vector whose head lies on its tail in some frame has no direction:
+    ``run()`` then raises ``ValueError`` instead of averaging it.  More than one rank raises ``ValueError``; the
+    frames must be evenly spaced and go forward in time; there is no CPU fallback: without a HIP device ``run()``
+    raises ``RuntimeError``.
+    """
+
+    _shard_frames = False
+
+    def __init__(self, tails, heads, *, lags=None, n_lags: int = None, dt=None, dimensions=None,
+                 minimum_image: bool = True, drop_axis=None, verbose: bool = True, **kwargs) -> None:
+        tails = [tails] if hasattr(tails, "universe") else list(tails)
+        heads = [heads] if hasattr(heads, "universe") else list(heads)
+        if len(tails) != len(heads) or len(tails) == 0:
+            raise ValueError("'tails' and 'heads' must hold the same number of groups, at least one.")
+        self._n_groups = len(tails)
+        self.universe = tails[0].universe
+        super().__init__(self.universe.trajectory, False, verbose, **kwargs)
+        if self._comm.world_size > 1:
+            raise ValueError("OrientationalRelaxation runs on one rank: every lag needs every frame, and sharding "
+                             "the vectors would change the order of the sums.")
+
+        for g, (t, h) in enumerate(zip(tails, heads)):
+            if t.n_atoms != h.n_atoms:
+                raise ValueError(f"group {g}: 'tails' holds {t.n_atoms} atoms and 'heads' {h.n_atoms}: a vector "
+                                 "needs one of each.")
+            if np.any(np.asarray(t.indices) == np.asarray(h.indices)):
+                raise ValueError(f"group {g}: a vector starts and ends on the same atom.")
+        self._Ns = np.fromiter((t.n_atoms for t in tails), dtype=int, count=self._n_groups)
+        self._V = int(self._Ns.sum())
+        if self._V < 1:
+            raise ValueError("The groups must hold at least one vector.")
+        # the distinct atoms are fed once; the pairs name them by their place in that feed
+        atoms = np.concatenate([np.asarray(t.indices) for t in tails] + [np.asarray(h.indices) for h in heads])
+        self._index, inverse = np.unique(atoms, return_inverse=True)
+        self._pairs = np.stack((inverse[:self._V], inverse[self._V:]), axis=1).astype(np.int32)
+
+        self._lags = parse_lags(lags, n_lags)
+        self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
+        self._drop_axis = parse_drop_axis(drop_axis)
+        self._dimensions = self._box_lengths(dimensions, 0.0, "minimum_image") if minimum_image else None
+        self._verbose = verbose
+
+    @classmethod
+    def from_chains(cls, ag, n_chains: int, n_monomers: int, *, stride: int = 1, **kwargs):
+        """The polymer case: ``ag`` holds ``n_chains`` chains of ``n_monomers`` consecutive atoms each, and the
+        vectors go from monomer ``n`` to monomer ``n + stride`` of every chain, ``n = 0 ... n_monomers - stride - 1``,
+        in one group (``stride=1``: the bonds)."""
+        n_chains, n_monomers, stride = int(n_chains), int(n_monomers), int(stride)
+        if n_chains < 1 or n_monomers < 2 or ag.n_atoms != n_chains * n_monomers:
+            raise ValueError("'ag' must hold n_chains * n_monomers atoms, n_monomers >= 2.")
+        if not 1 <= stride < n_monomers:
+            raise ValueError("'stride' must lie in [1, n_monomers).")
+        place = np.arange(n_chains * n_monomers).reshape(n_chains, n_monomers)
+        return cls(ag[place[:, :-stride].ravel()], ag[place[:, stride:].ravel()], **kwargs)
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        df = self._frame_stride()
+        lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
+        self._lags_run = lags
+        self.results.times = lags * df * self._dt
+        self.results.units = {"results.times": "picosecond", "results.relaxation_times": "picosecond"}
+        _lib.require_device(self._device)
+        # lags without an origin never meet a frame pair: the engine gets the others
+        self._live = lags < self.n_frames
+        engine = None
+        if self._live.any():
+            engine = _core.OrientationEngine(self._Ns, self._pairs, len(self._index), lags[self._live],
+                                             zero_dims=zero_dims(self._drop_axis), dev=self._device)
+            if self._dimensions is not None:
+                engine.set_box(self._dimensions)
+        self._feed_engine(engine, self._index)
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        sums = np.zeros((len(self._lags_run), self._n_groups, 2))
+        products = np.full((self.n_frames, self._n_groups, 6), np.nan)     # no lag with an origin: no engine ran
+        if self._engine is not None:
+            try:
+                sums[self._live] = self._engine.result()
+                products = self._engine.frame_sums()
+            finally:
+                self._engine.close()
+        terms = (np.maximum(self.n_frames - self._lags_run, 0)[:, None] * self._Ns[None, :]).astype(float)
+        terms[terms == 0] = np.nan          # no origin (or an empty group): NaN, without a warning
+        self.results.c1 = sums[:, :, 0] / terms
+        self.results.c2 = sums[:, :, 1] / terms
+
+        kept = kept_components(self._drop_axis)
+        filled = self._Ns > 0
+        mean = np.full((len(products), self._n_groups, 3, 3), np.nan)
+        for q, (a, b) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+            mean[:, filled, a, b] = mean[:, filled, b, a] = products[:, filled, q] / self._Ns[filled]
+        tensor = np.zeros_like(mean)
+        block = np.ix_(kept, kept)
+        if len(kept) == 3:
+            tensor = 1.5 * mean - 0.5 * np.eye(3)
+        else:
+            tensor[(..., *block)] = 2.0 * mean[(..., *block)] - np.eye(2)
+            tensor[:, ~filled] = np.nan
+        order = np.full(mean.shape[:2], np.nan)
+        director = np.full(mean.shape[:2] + (3,), np.nan)
+        if filled.any() and len(products) and self._engine is not None:
+            q_kept = tensor[:, filled][(..., *block)]
+            order[:, filled] = np.linalg.eigvalsh(q_kept)[..., -1]
+            axis = np.zeros(q_kept.shape[:2] + (3,))
+            axis[..., kept] = np.linalg.eigh(q_kept)[1][..., -1]
+            director[:, filled] = axis
+        self.results.order_tensor = tensor
+        self.results.order_parameter = order
+        self.results.director = director
+
+    def calculate_relaxation_times(self) -> None:
+        r"""``results.relaxation_times`` ``[2, N_g]``: :math:`\tau_l=\int_0^{t_\mathrm{max}}C_l(t)\,\mathrm dt` of
+        ``results.c1`` (row 0) and ``results.c2`` (row 1) for every group (``calculate_residence_time``: the trapezoid
+        rule).  The integral is truncated at the last lag: it is the relaxation time only where ``C_l`` has decayed
+        to about zero by then, and a lower bound otherwise.  In a nematic sample ``C_2`` does not decay to 0: it
+        levels off near ``<S>^2``, the square of ``results.order_parameter``, so read its long-time value against
+        that plateau before trusting ``tau_2``."""
+        if "c1" not in self.results:
+            raise RuntimeError("Call run() before calculate_relaxation_times().")
+        self.results.relaxation_times = np.array(
+            [[calculate_residence_time(self.results.times, c[:, g]) for g in range(self._n_groups)]
+             for c in (self.results.c1, self.results.c2)])
