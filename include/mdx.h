@@ -978,6 +978,65 @@ int mdx_ori_stats(mdx_ori_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *degenerate);
 int mdx_ori_enable_timing(mdx_ori_t h, int on);
 
+/* ---- bond-orientational order: Steinhardt q_l and the neighbour-averaged qbar_l of every center -----------------
+ * Incoming rows of a frame: the n_centers centers, then the n_neighbors neighbour candidates (two disjoint sets); with
+ * same the candidates are the centers themselves, the rows arrive once (n_neighbors == n_centers) and j == i never
+ * counts.  In float64 with separate multiply and add, per frame, center i and candidate j:
+ *     d = x_j - x_i;  w = d - L * rint(d * (1.0 / L));  r2 = (wx*wx + wy*wy) + wz*wz;  neighbour iff r2 <= cutoff^2
+ * and per bond and degree l = degrees[d] (1 ... 12, at most 4 distinct ones) Y_lm(w / sqrt(r2)), m = 0 ... l, by the
+ * recurrences and host tables of csrc/mdx_bond_order_device.hpp (Condon-Shortley phase).  Per center with m_i >= 1
+ * neighbours: q_lm = (sum of Y_lm over its neighbours in ascending j) / m_i and
+ * q_l = sqrt(4 pi / (2l + 1) * sum_m |q_lm|^2);
+ * with averaged (same only): qbar_lm = (q_lm(i) + sum of q_lm(j) over the neighbours in ascending j) / (m_i + 1) and
+ * qbar_l from it alike.  K = 2 with averaged, else 1; k = 0 is q_l, k = 1 is qbar_l.  A center without a neighbour is
+ * isolated: its values are NaN, it is not binned and adds nothing to the sums.  edges: float64 [n_bins + 1], strictly
+ * increasing; a value q is counted in bin #{m in 1 ... n_bins - 1 : q >= edges[m]} iff edges[0] <= q <= edges[n_bins]
+ * (numpy.histogram's counts), else in outside.  dims: float64 [3] lengths of one constant orthorhombic box; the
+ * cutoff may not exceed half the shortest.  A center holds at most max_neighbors (1 ... 64) neighbours in one frame:
+ * one that would hold more is never truncated silently, and a neighbour on top of its center (r2 == 0) has no
+ * direction; after either, mdx_boo_synchronize, mdx_boo_result, mdx_boo_frames and mdx_boo_values fail with
+ * MDX_ERR_INVALID_VALUE (the message names max_neighbors and the largest row, or counts the bonds that had no
+ * direction) until mdx_boo_reset.  The rows are sorted before they are summed, the frame sums run per tile of 64
+ * centers in row order and then in tile order, and no floating-point atomics are used, so every result is
+ * bit-identical across the three input routes, across any split of the frames into calls or slabs, and after a
+ * reset.  Every (center, candidate) pair is evaluated, there is no cell list.  A handle touches its device with the
+ * first frame: mdx_boo_create and every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_boo *mdx_boo_t;
+int mdx_boo_create(mdx_boo_t *out, int dev, int64_t n_centers, int64_t n_neighbors, int same, double cutoff,
+                   int n_degrees, const int32_t *degrees, int averaged, int64_t n_bins, const double *edges,
+                   const double *dims, int max_neighbors, int keep_values);
+int mdx_boo_destroy(mdx_boo_t h);
+/* Forgets the frames seen, the largest row, the bonds without a direction and the kept values, and zeroes the
+ * results. */
+int mdx_boo_reset(mdx_boo_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the slab's buffers in HBM), as
+ * mdx_ang_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
+int mdx_boo_set_slab_frames(mdx_boo_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = the rows of a frame. */
+int mdx_boo_accumulate(mdx_boo_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_boo_synchronize). */
+int mdx_boo_accumulate_device(mdx_boo_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_boo_accumulate_traj(mdx_boo_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_boo_synchronize(mdx_boo_t h);
+/* counts: int64 [D][K][n_bins]; outside: int64 [D][K]; coordination: int64 [max_neighbors + 1], the (frame, center)
+ * cases with exactly m neighbours. */
+int mdx_boo_result(mdx_boo_t h, int64_t *counts, int64_t *outside, int64_t *coordination);
+/* Of the first n frames seen: sums float64 [n][D][K], the sum of the values of the frame's centers that are not
+ * isolated; counted int64 [n], how many those are. */
+int mdx_boo_frames(mdx_boo_t h, double *sums, int64_t *counted, int64_t n);
+/* values: float64 [n][D][K][n_centers] of the first n frames seen, NaN for an isolated center; only with
+ * keep_values. */
+int mdx_boo_values(mdx_boo_t h, double *values, int64_t n);
+/* evaluations: frames * (n_centers * n_neighbors - (same ? n_centers : 0)); bonds: the list entries; degenerate: the
+ * bonds without a direction seen since the last reset (not zero: the results are refused); max_row: the most
+ * neighbours a center held in one frame. */
+int mdx_boo_stats(mdx_boo_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *bonds, int64_t *degenerate, int64_t *max_row);
+int mdx_boo_enable_timing(mdx_boo_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1205,6 +1205,85 @@ class OrientationEngine(_SlabbedFrameEngine):
         return out
 
 
+class BondOrderEngine(_SlabbedFrameEngine):
+    """``mdx_boo_*``: per frame the neighbours of each of ``n_centers`` centres among ``n_neighbors`` candidates
+    (minimum-image ``r2 <= cutoff ** 2`` in float64), and per centre ``i`` with ``m_i >= 1`` neighbours and degree
+    ``l`` of ``degrees`` (``1 ... 12``, at most 4 distinct ones) ``q_lm = sum_j Y_lm(w_ij / r_ij) / m_i`` over the
+    neighbours in ascending ``j`` and ``q_l = sqrt(4 pi / (2l + 1) * sum_m |q_lm|^2)``; with ``averaged`` also
+    ``qbar_l`` from ``qbar_lm = (q_lm(i) + sum_j q_lm(j)) / (m_i + 1)``.  Recurrences, host tables and summation
+    orders: csrc/mdx_bond_order_device.hpp.  ``K = 2`` with ``averaged``, else 1.  A value ``q`` is counted in bin
+    ``#{m in 1 ... n_bins - 1 : q >= edges[m]}`` iff ``edges[0] <= q <= edges[n_bins]`` (``numpy.histogram``), else in
+    ``outside``; a centre without a neighbour has NaN values and is counted nowhere.  Incoming rows are the centres,
+    then the candidates; with ``same`` the candidates are the centres themselves, the rows arrive once and ``j == i``
+    never counts; ``averaged`` needs ``same``.  A centre may hold ``max_neighbors`` neighbours in one frame; one that
+    would hold more, or a neighbour on top of its centre (a bond without a direction), makes ``synchronize()``,
+    ``result()``, ``frames()`` and ``values()`` raise ``ValueError`` until ``reset()``.  Every result is the same bits
+    whatever the route, the split into calls or the slab.  The device is first touched by the first frame, so the
+    argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_boo"
+    _stats_extra = (("evaluations", c_int64), ("bonds", c_int64), ("degenerate", c_int64), ("max_row", c_int64))
+    TILE = 256          # centres per block of the list kernel (BOO_TILE of csrc/mdx_bond_order_device.hpp)
+    JCHUNK = 1024       # candidates per block (BOO_JCHUNK)
+    MAX_NEIGHBORS = 64  # slots of a row at most (BOO_MAX_NEIGHBORS)
+    MAX_DEGREE = 12     # the largest l (BOO_MAX_DEGREE)
+    MAX_DEGREES = 4     # degrees per engine at most (BOO_MAX_DEGREES)
+    SUM_TILE = 64       # centres per tile of the frame sums (BOO_SUM_TILE)
+    LDS_BINS = 1024     # n_bins at most for the histogram in LDS (BOO_LDS_BINS)
+
+    def __init__(self, n_centers, n_neighbors, cutoff, degrees, edges, dims, *, same=False, averaged=False,
+                 max_neighbors=32, keep_values=False, dev=0, timing=False):
+        self.n_centers, self.same, self.averaged = int(n_centers), bool(same), bool(averaged)
+        self.n_neighbors = self.n_centers if n_neighbors is None else int(n_neighbors)
+        self.n_rows = self.n_centers if self.same else self.n_centers + self.n_neighbors
+        self.degrees = np.ascontiguousarray(np.atleast_1d(degrees), dtype=np.int32)
+        if self.degrees.ndim != 1 or not 1 <= len(self.degrees) <= self.MAX_DEGREES:
+            raise ValueError(f"degrees must hold between 1 and {self.MAX_DEGREES} degrees.")
+        self.n_degrees, self.n_kinds = len(self.degrees), 2 if self.averaged else 1
+        self.edges = np.ascontiguousarray(edges, dtype=np.float64)
+        if self.edges.ndim != 1 or len(self.edges) < 2:
+            raise ValueError("edges must hold n_bins + 1 values, at least two.")
+        self.n_bins = len(self.edges) - 1
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.cutoff, self.max_neighbors, self.keep_values = float(cutoff), int(max_neighbors), bool(keep_values)
+        h = c_void_p()
+        check(lib().mdx_boo_create(byref(h), dev, self.n_centers, self.n_neighbors, int(self.same), self.cutoff,
+                                   self.n_degrees, _ptr(self.degrees), int(self.averaged), self.n_bins,
+                                   _ptr(self.edges), _ptr(self.dims), self.max_neighbors, int(self.keep_values)))
+        self._adopt(h, dev, timing)
+
+    def _frames_seen(self):
+        frames = c_int64()
+        check(lib().mdx_boo_stats(self.handle, None, None, byref(frames), None, None, None, None))
+        return frames.value
+
+    def result(self):
+        """``{"counts": int64 [D, K, n_bins], "outside": int64 [D, K], "coordination": int64 [max_neighbors + 1]}``
+        over the frames seen."""
+        out = {"counts": np.zeros((self.n_degrees, self.n_kinds, self.n_bins), dtype=np.int64),
+               "outside": np.zeros((self.n_degrees, self.n_kinds), dtype=np.int64),
+               "coordination": np.zeros(self.max_neighbors + 1, dtype=np.int64)}
+        check(lib().mdx_boo_result(self.handle, _ptr(out["counts"]), _ptr(out["outside"]), _ptr(out["coordination"])))
+        return out
+
+    def frames(self):
+        """``{"sums": float64 [frames, D, K], "counted": int64 [frames]}`` of every frame seen: the sum of the values
+        of the centres that have a neighbour, and how many those are."""
+        n = self._frames_seen()
+        out = {"sums": np.zeros((n, self.n_degrees, self.n_kinds), dtype=np.float64),
+               "counted": np.zeros(n, dtype=np.int64)}
+        check(lib().mdx_boo_frames(self.handle, _ptr(out["sums"]), _ptr(out["counted"]), n))
+        return out
+
+    def values(self):
+        """float64 ``[frames, D, K, n_centers]``: every centre's values, NaN for an isolated one (``keep_values``)."""
+        out = np.zeros((self._frames_seen(), self.n_degrees, self.n_kinds, self.n_centers), dtype=np.float64)
+        check(lib().mdx_boo_values(self.handle, _ptr(out), len(out)))
+        return out
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

@@ -307,6 +307,22 @@ _SIGNATURES = {
     "mdx_ori_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
     "mdx_ori_enable_timing": (c_int, [_vp, c_int]),
+    # bond-orientational order (Steinhardt q_l, neighbour-averaged qbar_l)
+    "mdx_boo_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_double, c_int, _vp, c_int, c_int64, _vp,
+                               _vp, c_int, c_int]),
+    "mdx_boo_destroy": (c_int, [_vp]),
+    "mdx_boo_reset": (c_int, [_vp]),
+    "mdx_boo_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_boo_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_boo_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_boo_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_boo_synchronize": (c_int, [_vp]),
+    "mdx_boo_result": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_boo_frames": (c_int, [_vp, _vp, _vp, c_int64]),
+    "mdx_boo_values": (c_int, [_vp, _vp, c_int64]),
+    "mdx_boo_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_boo_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,6 +1,7 @@
 """Analysis classes of the hot path (mirrors ``mdhelper.analysis``)."""
 
-from . import angle, base, cluster, dynamics, electrostatics, polymer, profile, structure, transport  # noqa: F401
+from . import (angle, base, cluster, dynamics, electrostatics, order, polymer, profile, structure,  # noqa: F401
+               transport)
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
 from .angle import AngularDistribution  # noqa: F401
@@ -8,6 +9,7 @@ from .cluster import Clusters  # noqa: F401
 from .dynamics import (DistinctVanHove, OrientationalRelaxation, PairResidence, VanHove,  # noqa: F401
                        calculate_non_gaussian_parameter, calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
+from .order import BondOrientationalOrder  # noqa: F401
 from .polymer import (EndToEndVector, Gyradius, InternalDistances, RouseModes,  # noqa: F401
                       SingleChainStructureFactor)
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401
