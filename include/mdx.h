@@ -340,6 +340,26 @@ int mdx_msd_n_fft(mdx_msd_t h, int64_t *n_fft);
  * (csrc/mdx_msd_fft.hpp), *own = 0 (r1 = r2 = 0) for the rocFFT pipeline.  No reference counterpart: the
  * reference has one path (scipy.fft, correlation.py:176-197); benchmarks and tests name the path they measured. */
 int mdx_msd_transform(mdx_msd_t h, int *own, int *r1, int *r2);
+/* The launch plan of an engine created with (n_frames_block, n_blocks) for ONE push of particles [first, first+count)
+ * of an array of n_total particles per frame, elem_bytes 8 (mdx_msd_push_device) or 4 (mdx_msd_push_device_f32:
+ * MDX_ERR_UNSUPPORTED where the engine does not read float32 in place), base_aligned != 0: the array starts on a
+ * 128-byte boundary (anything from hipMalloc).  Touches no device; honours MDX_MSD_ROCFFT and MDX_MSD_TWO_PASS as
+ * mdx_msd_create does.  The push is described as ONE chunk: the engine cuts a push into equal chunks only when the
+ * half-transformed block of the whole push does not fit ~40 % of the free HBM, which no host-only query can know.
+ * mdx_msd_push stages the selection first, so its pushes are (n_total = count, first = 0, base_aligned = 1).
+ * out: 0 n_fft, 1 own transform (else rocFFT), 2 r1, 3 r2 (0 without own transform), 4 single pass, 5 pass A forms
+ * the per-frame sums, 6 float32 read in place,
+ * 7 pass A: 0 msd_gather_kernel + rocFFT, 1 msd_fft_single400_kernel<r2>, 2 msd_fft_cols400_fused_kernel<r2>,
+ *   3 msd_fft_cols_small_fused_kernel<64, r2>, 4 msd_fft_cols_kernel<r1, r2> (sums: msd_sums_kernel),
+ * 8 pass B: 0 none (single pass, rocFFT), 1 msd_fft_rows_tiny_power_kernel, 2 msd_fft_rows_short_power_kernel,
+ *   3 msd_fft_rows_mid_power_kernel, 4 msd_fft_rows512_power_kernel, 5 msd_fft_rows1024_power_kernel,
+ *   6 msd_fft_rows_power_kernel (the general rows kernel: no length of the engine's takes it),
+ * 9 head: coordinates by which pass A enters the chunk early to read whole 128-byte lines, 10 n_elem = 3 count + head,
+ * 11 p_pad: coordinate pairs padded to whole pair groups, 12 super groups of the fused pass A (0: not fused),
+ * 13 the split of pass A's grid: blockIdx.x of the single-pass kernel, blockIdx.y of the others (0: rocFFT),
+ * 14 parts of pass B (blockIdx.z; 0: no pass B), 15 Y is laid out pair-group-major. */
+int mdx_msd_plan(int64_t n_frames_block, int n_blocks, int64_t n_total, int64_t first, int64_t count, int elem_bytes,
+                 int base_aligned, int64_t out[16]);
 /* Feed particles of one group: pos float64[n_blocks*n_frames_block][n_total][3]
  * (transport.py:932 layout), of which particles [first, first+count) belong to
  * `group`.  Accumulates sum_particles of the per-particle self MSD numerators

@@ -1347,6 +1347,24 @@ class MsdEngine(_Engine):
         check(lib().mdx_msd_transform(self.handle, byref(own), byref(r1), byref(r2)))
         return bool(own.value), r1.value, r2.value
 
+    PLAN_FIELDS = ("n_fft", "own", "r1", "r2", "single", "fused_sums", "reads_f32", "pass_a", "pass_b", "head", "n_elem",
+                   "p_pad", "super_groups", "split", "rows_parts", "pg_major")
+    PASS_A = ("rocfft", "single400", "cols400_fused", "cols_small_fused", "cols")
+    PASS_B = ("none", "tiny", "short", "mid", "rows512", "rows1024", "general")
+
+    @staticmethod
+    def plan(n_frames_block, n_blocks, n_total, first, count, elem_bytes=8, base_aligned=True):
+        """``mdx_msd_plan``: the kernels an engine ``MsdEngine(n_frames_block, n_blocks, ...)`` launches for ONE
+        ``push_device`` (``elem_bytes=8``) or ``push_device_f32`` (``4``) of particles ``[first, first + count)`` of
+        an array of ``n_total`` particles per frame, as a dict of ``PLAN_FIELDS`` — ``pass_a`` indexes ``PASS_A``,
+        ``pass_b`` indexes ``PASS_B``; the push is described as one chunk.  ``push`` stages its selection first:
+        ``plan(T_b, B, count, 0, count)``.  Needs no device; reads ``MDX_MSD_ROCFFT`` / ``MDX_MSD_TWO_PASS`` as the
+        constructor does."""
+        out = np.zeros(16, dtype=np.int64)
+        check(lib().mdx_msd_plan(int(n_frames_block), int(n_blocks), int(n_total), int(first), int(count),
+                                 int(elem_bytes), 1 if base_aligned else 0, _ptr(out)))
+        return dict(zip(MsdEngine.PLAN_FIELDS, (int(v) for v in out)))
+
     def push(self, group, positions, first, count, zero_dims=0):
         """positions: float64[T, N_total, 3] on the host."""
         p = np.ascontiguousarray(positions, dtype=np.float64)

@@ -468,6 +468,84 @@ __global__ void cross_product_kernel(const double2 *__restrict__ F, const int *_
 
 }  // namespace
 
+// ------------------------------------------------------------------------------------------------------------
+// Host planning, shared by the engine and by mdx_msd_plan (which touches no device).
+
+// What mdx_msd_create decides from the block length and the environment.
+struct MsdRoute {
+    int64_t n_fft = 0;
+    msdfft::Shape shape;
+    bool own_fft = false;      // n_fft is one of the shapes of mdx_msd_fft.hpp
+    bool fused_sums = false;   // pass A of this shape also forms the per-frame sums
+    bool single = false;       // <= 800 frames per block: one pass, no Y (msd_fft_single400_kernel)
+};
+
+static MsdRoute msd_plan_route(int64_t n_frames_block)
+{
+    MsdRoute r;
+    // Any length >= 2 N_t - 1 gives the same linear correlation up to rounding.  The reference pads to
+    // 2 * next_fast_len(N_t) (correlation.py:176-178).  Here:
+    //   * blocks of more than 200 frames take the shortest length of the engine's own two-pass transform
+    //     (mdx_msd_fft.hpp) that covers 2 N_t: 800 = 400 x 2, 1 600 = 400 x 4, 3 200 = 400 x 8, 6 400 = 400 x 16, 2^13, 12 800 = 400 x 32, 2^14, 25 600 = 400 x 64, 2^15, 51 200 = 400 x 128, 2^16,
+    //     102 400 = 400 x 256, 204 800 = 400 x 512, 2^18, 409 600 = 400 x 1024, 2^19, 2^20 (2^17 is served by 204 800 / 2^18).  It never materialises the padding and moves
+    //     ~4.3 MB per series at 2^18 whatever N_t is, where the rocFFT pipeline moves ~17.7 MB;
+    //   * everything else goes through rocFFT at the reference's length, or at the next power of two when that is
+    //     at most 1.5 x longer (fewer rocFFT passes: measured 15 % faster end to end at N_t = 1e5).
+    // MDX_MSD_ROCFFT=1 (test hook: tests/test_gpu_engines.py compares the two pipelines) keeps rocFFT throughout.
+    r.n_fft = 2 * next_fast_len_real(n_frames_block);
+    int64_t p = 1;
+    while (p < 2 * n_frames_block)
+        p <<= 1;
+    int64_t own_len = 0;
+    if (!getenv("MDX_MSD_ROCFFT")) {
+        // the shortest own length that covers 2 N_t
+        static const int64_t lengths[] = {400, 800, 1600, 3200, 6400, int64_t(1) << 13, 12800, int64_t(1) << 14, 25600, int64_t(1) << 15, 51200,
+                                          int64_t(1) << 16, 102400, 204800, int64_t(1) << 18, 409600, int64_t(1) << 19,
+                                          int64_t(1) << 20};
+        for (int64_t len : lengths)
+            if (len >= 2 * n_frames_block) {
+                own_len = len;
+                break;
+            }
+    }
+    if (own_len && msdfft::shape_for(own_len).r1)
+        r.n_fft = own_len;
+    else if (2 * p <= 3 * r.n_fft)
+        r.n_fft = p;
+    // the shapes of mdx_msd_fft.hpp run through the engine's own two-pass kernels (MDX_MSD_ROCFFT=1: rocFFT)
+    r.shape = msdfft::shape_for(r.n_fft);
+    r.own_fft = r.shape.r1 != 0 && !getenv("MDX_MSD_ROCFFT");
+    r.fused_sums = r.own_fft && msdfft::fuses_sums(r.shape);
+    // blocks of <= 800 frames: the single-pass kernel (MDX_MSD_TWO_PASS=1, test hook: the two-pass pipeline for
+    // 800 and 1 600 points; 400 points has no two-pass form)
+    r.single = r.own_fft && msdfft::single_pass(r.shape) && (r.shape.r2 == 1 || !getenv("MDX_MSD_TWO_PASS"));
+    return r;
+}
+
+// float32 positions are read where they lie by these engines only (mdx_msd_push_device_f32)
+static bool msd_reads_f32(bool own_fft, bool single, bool fused_sums, const msdfft::Shape &shape)
+{
+    return own_fft && (single || fused_sums) && msdfft::cols_read_f32(shape);
+}
+
+// One chunk of `count` particles from `first` of an array of n_total per frame, as the transforms of the engine's
+// own pipeline see it.
+struct MsdChunk {
+    int head = 0;         // coordinates the chunk is entered early (msdfft::chunk_head)
+    int64_t n_elem = 0;   // coordinates pass A counts: 3 count + head
+    int p_pad = 0;        // pairs of coordinates, padded to whole pair groups
+};
+
+static MsdChunk msd_plan_chunk(const msdfft::Shape &shape, bool single, bool fused_sums, int64_t n_total, int64_t first,
+                               int64_t count, bool base_aligned)
+{
+    MsdChunk c;
+    c.head = msdfft::chunk_head(shape, single, fused_sums, n_total, first, base_aligned);
+    c.n_elem = msdfft::chunk_elems(count, c.head);
+    c.p_pad = msdfft::chunk_p_pad(shape, c.n_elem);
+    return c;
+}
+
 struct mdx_msd {
     int dev = 0;
     hipStream_t stream = nullptr;
@@ -509,7 +587,7 @@ struct mdx_msd {
 static int msd_push_device(mdx_msd *h, int group, const double *d_pos, int64_t n_total, int64_t first,
                            int64_t count, int zero_dims, const float *d_pos32 = nullptr)
 {
-    if (d_pos32 && !(h->own_fft && (h->single || h->fused_sums) && msdfft::cols_read_f32(h->shape)))
+    if (d_pos32 && !msd_reads_f32(h->own_fft, h->single, h->fused_sums, h->shape))
         return fail(MDX_ERR_UNSUPPORTED, "float32 positions are read in place by the transforms with a 400- or 64-point first factor only "
                     "(this engine: n_fft = %lld)", (long long)h->n_fft);
     if (count == 0)
@@ -536,8 +614,7 @@ static int msd_push_device(mdx_msd *h, int group, const double *d_pos, int64_t n
     if (h->single) {
         MDX_TRY(h->d_part.ensure(msdfft::single_part_bytes(h->shape, B)));
     } else if (h->own_fft) {
-        const int64_t pmul = int64_t(msdfft::PG) * msdfft::pair_group_multiple(h->shape);
-        const int64_t p_pad_max = ceil_div(ceil_div(chunk * 3 + 15, 2), pmul) * pmul;   // (+ 15: head)
+        const int64_t p_pad_max = msdfft::chunk_p_pad(h->shape, msdfft::chunk_elems(chunk, 15));   // (15: the largest head)
         MDX_TRY(h->d_spec.ensure(size_t(B) * h->n_fft * p_pad_max * 16));
         if (h->fused_sums)
             MDX_TRY(h->d_part.ensure(msdfft::fused_part_bytes(h->shape, (int)p_pad_max, B)));
@@ -558,17 +635,12 @@ static int msd_push_device(mdx_msd *h, int group, const double *d_pos, int64_t n
                           *twN = tw_r2 + h->shape.r2 / 2;
             // (batches of particles whose half-transformed block fits the 256 MB memory-side cache were measured in
             // rounds 1 and 2: small launches lose more than the cache returns — NOTES.md — so a chunk is one launch)
-            // rows whose length is a multiple of 128 bytes (and positions from hipMalloc): a chunk that starts
-            // in the middle of a line is entered `head` coordinates early, so that pass A's 128-byte pieces
-            // are whole lines (msd_fft_cols400_fused_kernel); the head is staged as zeros
-            const int head = ((h->single || (h->fused_sums && msdfft::aligns_head(h->shape))) && (n_total * 3) % 16 == 0 &&
-                              (reinterpret_cast<uintptr_t>(d_pos32 ? static_cast<const void *>(d_pos32)
-                                                                   : static_cast<const void *>(d_pos)) & 127u) == 0)
-                                 ? int(((first + a0) * 3) % 16)
-                                 : 0;
-            const int64_t ne = c * 3 + head;
-            const int64_t pmul = int64_t(msdfft::PG) * msdfft::pair_group_multiple(h->shape);
-            const int p_pad = (int)(ceil_div(ceil_div(ne, 2), pmul) * pmul);
+            // a chunk that starts in the middle of a 128-byte line is entered `head` coordinates early (msdfft::chunk_head)
+            const bool base_aligned = (reinterpret_cast<uintptr_t>(d_pos32 ? static_cast<const void *>(d_pos32)
+                                                                           : static_cast<const void *>(d_pos)) & 127u) == 0;
+            const MsdChunk ck = msd_plan_chunk(h->shape, h->single, h->fused_sums, n_total, first + a0, c, base_aligned);
+            const int head = ck.head, p_pad = ck.p_pad;
+            const int64_t ne = ck.n_elem;
             if (h->single) {
                 // one pass: positions -> |F|^2 sums and per-frame sums, nothing written in between
                 const int parts = msdfft::launch_single(h->shape, h->stream, d_pos, n_total, first + a0, ne, h->t_block, B,
@@ -1109,37 +1181,9 @@ int mdx_msd_create(mdx_msd_t *out, int dev, int64_t n_frames_block, int n_blocks
     h->t_block = n_frames_block;
     h->n_blocks = n_blocks;
     h->n_groups = n_groups;
-    // Any length >= 2 N_t - 1 gives the same linear correlation up to rounding.  The reference pads to
-    // 2 * next_fast_len(N_t) (correlation.py:176-178).  Here:
-    //   * blocks of more than 200 frames take the shortest length of the engine's own two-pass transform
-    //     (mdx_msd_fft.hpp) that covers 2 N_t: 800 = 400 x 2, 1 600 = 400 x 4, 3 200 = 400 x 8, 6 400 = 400 x 16, 2^13, 12 800 = 400 x 32, 2^14, 25 600 = 400 x 64, 2^15, 51 200 = 400 x 128, 2^16,
-    //     102 400 = 400 x 256, 204 800 = 400 x 512, 2^18, 409 600 = 400 x 1024, 2^19, 2^20 (2^17 is served by 204 800 / 2^18).  It never materialises the padding and moves
-    //     ~4.3 MB per series at 2^18 whatever N_t is, where the rocFFT pipeline moves ~17.7 MB;
-    //   * everything else goes through rocFFT at the reference's length, or at the next power of two when that is
-    //     at most 1.5 x longer (fewer rocFFT passes: measured 15 % faster end to end at N_t = 1e5).
-    // MDX_MSD_ROCFFT=1 (test hook: tests/test_gpu_engines.py compares the two pipelines) keeps rocFFT throughout.
-    h->n_fft = 2 * next_fast_len_real(n_frames_block);
-    {
-        int64_t p = 1;
-        while (p < 2 * n_frames_block)
-            p <<= 1;
-        int64_t own_len = 0;
-        if (!getenv("MDX_MSD_ROCFFT")) {
-            // the shortest own length that covers 2 N_t
-            static const int64_t lengths[] = {400, 800, 1600, 3200, 6400, int64_t(1) << 13, 12800, int64_t(1) << 14, 25600, int64_t(1) << 15, 51200,
-                                              int64_t(1) << 16, 102400, 204800, int64_t(1) << 18, 409600, int64_t(1) << 19,
-                                              int64_t(1) << 20};
-            for (int64_t len : lengths)
-                if (len >= 2 * n_frames_block) {
-                    own_len = len;
-                    break;
-                }
-        }
-        if (own_len && msdfft::shape_for(own_len).r1)
-            h->n_fft = own_len;
-        else if (2 * p <= 3 * h->n_fft)
-            h->n_fft = p;
-    }
+    // the transform length and the pipeline: msd_plan_route
+    const MsdRoute route = msd_plan_route(n_frames_block);
+    h->n_fft = route.n_fft;
     h->nc = h->n_fft / 2 + 1;
     h->fft.n_fft = h->n_fft;
     int rc = MDX_OK;
@@ -1148,13 +1192,10 @@ int mdx_msd_create(mdx_msd_t *out, int dev, int64_t n_frames_block, int n_blocks
         h->timer.stream = h->stream;
         if ((rc = h->d_acc.ensure(size_t(8) * h->acc_len())) != MDX_OK) break;
         if ((rc = h->d_traj.ensure(size_t(8) * h->traj_len())) != MDX_OK) break;
-        // the shapes of mdx_msd_fft.hpp run through the engine's own two-pass kernels (MDX_MSD_ROCFFT=1: rocFFT)
-        h->shape = msdfft::shape_for(h->n_fft);
-        h->own_fft = h->shape.r1 != 0 && !getenv("MDX_MSD_ROCFFT");
-        h->fused_sums = h->own_fft && msdfft::fuses_sums(h->shape);
-        // blocks of <= 800 frames: the single-pass kernel (MDX_MSD_TWO_PASS=1, test hook: the two-pass pipeline for
-        // 800 and 1 600 points; 400 points has no two-pass form)
-        h->single = h->own_fft && msdfft::single_pass(h->shape) && (h->shape.r2 == 1 || !getenv("MDX_MSD_TWO_PASS"));
+        h->shape = route.shape;
+        h->own_fft = route.own_fft;
+        h->fused_sums = route.fused_sums;
+        h->single = route.single;
         if (h->own_fft) {
             const int r1 = h->shape.r1, r2 = h->shape.r2;
             std::vector<double> tw;
@@ -1233,6 +1274,63 @@ int mdx_msd_transform(mdx_msd_t h, int *own, int *r1, int *r2)
     *own = h->own_fft ? 1 : 0;
     *r1 = h->own_fft ? h->shape.r1 : 0;
     *r2 = h->own_fft ? h->shape.r2 : 0;
+    return MDX_OK;
+}
+
+int mdx_msd_plan(int64_t n_frames_block, int n_blocks, int64_t n_total, int64_t first, int64_t count, int elem_bytes,
+                 int base_aligned, int64_t out[16])
+{
+    MDX_REQUIRE(out, "NULL argument");
+    MDX_REQUIRE(n_frames_block >= 1 && n_frames_block < (int64_t(1) << 30), "n_frames_block out of range");
+    MDX_REQUIRE(n_blocks >= 1 && n_blocks <= 65535, "n_blocks out of range");
+    MDX_REQUIRE(first >= 0 && count >= 1 && first + count <= n_total, "particle range out of bounds");
+    MDX_REQUIRE(elem_bytes == 4 || elem_bytes == 8, "elem_bytes must be 4 (float32) or 8 (float64)");
+    const MsdRoute r = msd_plan_route(n_frames_block);
+    const bool reads_f32 = msd_reads_f32(r.own_fft, r.single, r.fused_sums, r.shape);
+    if (elem_bytes == 4 && !reads_f32)
+        return fail(MDX_ERR_UNSUPPORTED, "float32 positions are read in place by the transforms with a 400- or 64-point first factor only "
+                    "(this engine: n_fft = %lld)", (long long)r.n_fft);
+    for (int i = 0; i < 16; ++i)
+        out[i] = 0;
+    out[0] = r.n_fft;
+    out[1] = r.own_fft ? 1 : 0;
+    out[4] = r.single ? 1 : 0;
+    out[5] = r.fused_sums ? 1 : 0;
+    out[6] = reads_f32 ? 1 : 0;
+    out[10] = count * 3;
+    if (!r.own_fft)
+        return MDX_OK;     // msd_gather_kernel + rocFFT: no head, no pairs
+    // (msd_push_device cuts a push into equal chunks when Y of the whole push does not fit ~40 % of the free HBM:
+    // that depends on the device's state, so the query describes the push as ONE chunk)
+    const MsdChunk ck = msd_plan_chunk(r.shape, r.single, r.fused_sums, n_total, first, count, base_aligned != 0);
+    const int pass_a = msdfft::pass_a_kernel(r.shape, r.single, r.fused_sums);
+    out[2] = r.shape.r1;
+    out[3] = r.shape.r2;
+    out[7] = pass_a;
+    out[8] = r.single ? msdfft::PASS_B_NONE : msdfft::pass_b_kernel(r.shape.r1, r.shape.r2);
+    out[9] = ck.head;
+    out[10] = ck.n_elem;
+    out[11] = ck.p_pad;
+    const int n_sg = msdfft::fused_super_groups(ck.p_pad);
+    switch (pass_a) {
+    case msdfft::PASS_A_SINGLE400:
+        out[13] = msdfft::single_grid_splits(n_blocks, ck.p_pad);
+        break;
+    case msdfft::PASS_A_COLS400_FUSED:
+        out[12] = n_sg;
+        out[13] = msdfft::cols400_fused_split(r.shape, n_sg, n_blocks);
+        break;
+    case msdfft::PASS_A_COLS_SMALL_FUSED:
+        out[12] = n_sg;
+        out[13] = msdfft::small_fused_split(r.shape, n_sg, n_blocks);
+        break;
+    default:
+        out[13] = msdfft::cols_split(r.shape, ck.p_pad, n_blocks);
+    }
+    if (!r.single) {
+        out[14] = msdfft::rows_parts(r.shape, n_blocks);
+        out[15] = msdfft::y_pg_major(r.shape, pass_a);
+    }
     return MDX_OK;
 }
 

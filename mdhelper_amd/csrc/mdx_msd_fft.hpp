@@ -15,7 +15,7 @@
 //         W_N^(n2 k1), writes Y[k1][pair group][n2][pair] (8 pairs = 128 B contiguous) — the 400-, 512- and 1024-point
 //         first factors with rows of >= 32 points Y[pair group][k1][n2][pair]: the lines an iteration stores then lie R2 x 128 B
 //         apart inside one pair group's block instead of a whole k1 row apart (`pg_major`);
-//       pass B (msd_fft_rows512_power_kernel; msd_fft_rows_power_kernel for 1024-point rows): streams
+//       pass B (msd_fft_rows512_power_kernel; msd_fft_rows1024_power_kernel for 1024-point rows): streams
 //         Y once (R2 x 128 B contiguous per step), R2-point transforms over n2 — first stage on the
 //         registers the loads land in, middle stage in LDS, last stage back in registers —
 //         accumulates |Z|^2 over all pairs in registers: the spectrum itself is never written;
@@ -26,7 +26,7 @@
 // no barrier inside a transform).  Shapes: 400 x R2 — pass A msd_fft_cols400_fused_kernel<R2> (in-place DIF stages
 // 10, 10, 4 of the 400-point columns, the per-frame sums fused in), pass B msd_fft_rows_tiny_power_kernel (R2 = 2, 4), msd_fft_rows_short_power_kernel (8,
 // 16, 32, 64), msd_fft_rows_mid_power_kernel (128, 256), msd_fft_rows512_power_kernel (512),
-// msd_fft_rows_power_kernel (1024) —, 2^13 = 64 x 128,
+// msd_fft_rows1024_power_kernel (1024; pass_b_kernel below names the kernel of every shape) —, 2^13 = 64 x 128,
 // 2^14 = 64 x 256, 2^15 = 64 x 512, 2^16 = 64 x 1024 (8 short column transforms per wave at a time, the rows as above),
 // 2^18 = 512 x 512, 2^19 = 1024 x 512, 2^20 = 1024 x 1024.
 #pragma once
@@ -1804,13 +1804,108 @@ inline size_t single_part_bytes(const Shape &sh, int n_blocks)
     return size_t(single_splits(n_blocks)) * n_blocks * single_live(sh.r2) * 32;
 }
 
+// ---- the launch arithmetic of one chunk: called by the launches below, by msd_push_device and by mdx_msd_plan
+// (mdx_msd.hip), which reports what these functions return and touches no device.
+
+// Kernel ids as mdx_msd_plan reports them (include/mdx.h).
+enum PassA {
+    PASS_A_ROCFFT = 0,            // no own transform: msd_gather_kernel + rocFFT + msd_power_kernel
+    PASS_A_SINGLE400 = 1,         // msd_fft_single400_kernel<R2>, R2 = 1, 2, 4: the whole transform, no pass B
+    PASS_A_COLS400_FUSED = 2,     // msd_fft_cols400_fused_kernel<R2>
+    PASS_A_COLS_SMALL_FUSED = 3,  // msd_fft_cols_small_fused_kernel<64, R2>
+    PASS_A_COLS = 4               // msd_fft_cols_kernel<R1, R2> (per-frame sums: msd_sums_kernel)
+};
+enum PassB {
+    PASS_B_NONE = 0,              // single pass, or the rocFFT pipeline
+    PASS_B_TINY = 1,              // msd_fft_rows_tiny_power_kernel
+    PASS_B_SHORT = 2,             // msd_fft_rows_short_power_kernel
+    PASS_B_MID = 3,               // msd_fft_rows_mid_power_kernel
+    PASS_B_ROWS512 = 4,           // msd_fft_rows512_power_kernel
+    PASS_B_ROWS1024 = 5,          // msd_fft_rows1024_power_kernel
+    PASS_B_GENERAL = 6            // msd_fft_rows_power_kernel: every other row length (none of the shapes of shape_for)
+};
+
+// pass A of a launch: `single` as the engine decided it (mdx_msd_create), `fused` = the caller hands the partial-sum records
+inline int pass_a_kernel(const Shape &sh, bool single, bool fused)
+{
+    if (sh.r1 == 0)
+        return PASS_A_ROCFFT;
+    if (single)
+        return PASS_A_SINGLE400;
+    if (sh.r1 == 64 && fused)
+        return PASS_A_COLS_SMALL_FUSED;
+    if (sh.r1 == 400 && fused)
+        return PASS_A_COLS400_FUSED;
+    return PASS_A_COLS;
+}
+
+// pass B by the row length (the 400-point first factor has kernels of its own for rows of up to 64 points)
+constexpr int pass_b_kernel(int r1, int r2)
+{
+    return r2 == 512                                  ? PASS_B_ROWS512
+           : (r2 == 128 || r2 == 256)                 ? PASS_B_MID
+           : r2 == 1024                               ? PASS_B_ROWS1024
+           : (r1 == 400 && (r2 == 2 || r2 == 4))      ? PASS_B_TINY
+           : (r1 == 400 && r2 >= 8 && r2 <= 64)       ? PASS_B_SHORT
+                                                      : PASS_B_GENERAL;
+}
+
+// Coordinates by which a chunk that starts at particle `first` is entered early.  Rows whose length is a multiple of
+// 128 bytes (and positions from hipMalloc, `base_aligned`): a chunk that starts in the middle of a line is entered
+// `head` coordinates early, so that pass A's 128-byte pieces are whole lines (msd_fft_cols400_fused_kernel); the head
+// is staged as zeros.
+inline int chunk_head(const Shape &sh, bool single, bool fused, int64_t n_total, int64_t first, bool base_aligned)
+{
+    return ((single || (fused && aligns_head(sh))) && (n_total * 3) % 16 == 0 && base_aligned) ? int((first * 3) % 16) : 0;
+}
+// coordinates of a chunk of `count` particles as pass A counts them
+inline int64_t chunk_elems(int64_t count, int head) { return count * 3 + head; }
+// pairs of coordinates, padded to whole pair groups (pair_group_multiple of them)
+inline int chunk_p_pad(const Shape &sh, int64_t n_elem)
+{
+    const int64_t pmul = int64_t(PG) * pair_group_multiple(sh);
+    return (int)(((n_elem + 1) / 2 + pmul - 1) / pmul * pmul);
+}
+// blockIdx.x of the single-pass grid
+inline int single_grid_splits(int n_blocks, int p_pad) { return std::min(single_splits(n_blocks), p_pad / PG); }
+// blockIdx.y of msd_fft_cols_kernel: >= ~1024 blocks of pass A where the batch allows it
+inline int cols_split(const Shape &sh, int p_pad, int n_blocks)
+{
+    int split = 4;
+    while (split < sh.r2 / 2 && int64_t(p_pad / PG) * split * n_blocks < 1024)
+        split *= 2;
+    return split;
+}
+// blockIdx.y of msd_fft_cols_small_fused_kernel
+inline int small_fused_split(const Shape &sh, int n_sg, int n_blocks)
+{
+    const int nc = 512 / sh.r1, ng = sh.r2 / nc;
+    return std::min(ng, slots_split(int64_t(n_sg) * n_blocks, 1, 64));
+}
+// blockIdx.y of msd_fft_cols400_fused_kernel
+// (twelve rounds of the chip's block slots: C4 with one block 27.1 -> 26.2 ms of kernels per step against the
+// four rounds of round 2 — blocks in more different phases share a CU, and the tail is a twelfth)
+inline int cols400_fused_split(const Shape &sh, int n_sg, int n_blocks)
+{
+    return slots_split(int64_t(n_sg) * n_blocks, std::min(8, sh.r2), std::min(64, sh.r2), 12);
+}
+// The layout of Y that pass A writes and pass B reads.  400-point first factor: Y[block][pair group][k1][n2][pair]
+// where a (k1, pair group) run is at least 4 KB (measured: 1 and 2 KB runs cost pass B 0.3 ms more than the layout
+// saves pass A) and pass B takes the layout; the 64-point family gains nothing (this pass A already stores runs of
+// NC x 128 B = 1 KB: C4 size in 25 / 13 / 7 blocks 25.6 / 27.1 / 28.8 ms k1-major, 26.1 / 27.4 / 28.6 pair-group-major);
+// msd_fft_cols_kernel always writes it.
+inline int y_pg_major(const Shape &sh, int pass_a)
+{
+    return pass_a == PASS_A_COLS400_FUSED ? (sh.r2 >= 32 ? 1 : 0) : pass_a == PASS_A_COLS ? 1 : 0;
+}
+
 // one launch of the single-pass pipeline for a chunk; returns the number of Pfull parts written
 inline int launch_single(const Shape &sh, hipStream_t stream, const double *pos, int64_t n_total, int64_t first,
                          int64_t n_elem, int64_t t_block, int n_blocks, int zero_dims, int p_pad,
                          const double2 *tw_r1, const double2 *twN, double *Pfull, double2 *part, double *traj,
                          double *dsq, int head, const float *pos32 = nullptr)
 {
-    const int splits = std::min(single_splits(n_blocks), p_pad / PG);
+    const int splits = single_grid_splits(n_blocks, p_pad);
     const dim3 grid((unsigned)splits, (unsigned)n_blocks);
 #define MDX_MSDFFT_SINGLE(R2_)                                                                                   \
     if (pos32)                                                                                                   \
@@ -1833,19 +1928,26 @@ inline int launch_single(const Shape &sh, hipStream_t stream, const double *pos,
     return splits;
 }
 
-// pass B of shape R1 x R2: the register-staged kernel for 512-point rows, the general one for 1024
+// pass B of shape R1 x R2: the kernel pass_b_kernel names
 template <int R1, int R2>
 inline void launch_rows(dim3 gb, hipStream_t stream, const double2 *Y, int p_pad, const double2 *tw_r2,
                         double *Pfull, int accumulate, int pg_major = 0)
 {
-    if constexpr (R2 == 512)
+    constexpr int kernel = pass_b_kernel(R1, R2);
+    if constexpr (kernel == PASS_B_ROWS512)
         hipLaunchKernelGGL((msd_fft_rows512_power_kernel<R1>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
                            Pfull, accumulate, pg_major);
-    else if constexpr (R2 == 128 || R2 == 256)
+    else if constexpr (kernel == PASS_B_MID)
         hipLaunchKernelGGL((msd_fft_rows_mid_power_kernel<R1, R2>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
                            Pfull, accumulate, pg_major);
-    else if constexpr (R2 == 1024)
+    else if constexpr (kernel == PASS_B_ROWS1024)
         hipLaunchKernelGGL((msd_fft_rows1024_power_kernel<R1>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
+                           Pfull, accumulate, pg_major);
+    else if constexpr (kernel == PASS_B_TINY)
+        hipLaunchKernelGGL((msd_fft_rows_tiny_power_kernel<R1, R2>), gb, dim3(THREADS), 0, stream, Y, p_pad, Pfull,
+                           accumulate);
+    else if constexpr (kernel == PASS_B_SHORT)
+        hipLaunchKernelGGL((msd_fft_rows_short_power_kernel<R1, R2>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
                            Pfull, accumulate, pg_major);
     else
         hipLaunchKernelGGL((msd_fft_rows_power_kernel<R1, R2>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
@@ -1861,22 +1963,18 @@ inline void launch(const Shape &sh, hipStream_t stream, const double *pos, int64
                    double *traj = nullptr, double *dsq = nullptr, int head = 0, const float *pos32 = nullptr)
 {
     // pos32: the positions as float32 (400-point first factor with fused sums only: cols400_reads_f32); `pos` is unused then
-    // >= ~1024 blocks of pass A where the batch allows it
-    int split = 4;
-    while (split < sh.r2 / 2 && int64_t(p_pad / PG) * split * n_blocks < 1024)
-        split *= 2;
-    const dim3 ga((unsigned)(p_pad / PG), (unsigned)split, (unsigned)n_blocks);
+    const int pass_a = pass_a_kernel(sh, false, part != nullptr);
+    const int pgm = y_pg_major(sh, pass_a);
+    const dim3 ga((unsigned)(p_pad / PG), (unsigned)cols_split(sh, p_pad, n_blocks), (unsigned)n_blocks);
     const dim3 gb((unsigned)sh.r1, (unsigned)n_blocks, (unsigned)rows_parts(sh, n_blocks));
 #define MDX_MSDFFT_LAUNCH(A, B)                                                                    \
     hipLaunchKernelGGL((msd_fft_cols_kernel<A, B>), ga, dim3(THREADS), 0, stream, pos, n_total, first, \
-                       n_elem, t_block, zero_dims, p_pad, tw_r1, twN, Y, 1);                           \
-    launch_rows<A, B>(gb, stream, Y, p_pad, tw_r2, Pfull, accumulate, 1)
-    if (sh.r1 == 64 && part) {
+                       n_elem, t_block, zero_dims, p_pad, tw_r1, twN, Y, pgm);                         \
+    launch_rows<A, B>(gb, stream, Y, p_pad, tw_r2, Pfull, accumulate, pgm)
+    if (pass_a == PASS_A_COLS_SMALL_FUSED) {
         // per-frame sums fused into pass A (short first factors)
         const int n_sg = fused_super_groups(p_pad);
-        const int nc = 512 / sh.r1, ng = sh.r2 / nc;
-        const int fsplit = std::min(ng, slots_split(int64_t(n_sg) * n_blocks, 1, 64));
-        const dim3 gf((unsigned)n_sg, (unsigned)fsplit, (unsigned)n_blocks);
+        const dim3 gf((unsigned)n_sg, (unsigned)small_fused_split(sh, n_sg, n_blocks), (unsigned)n_blocks);
 #define MDX_MSDFFT_SMALL_FUSED(A, B)                                                                              \
     if (pos32)                                                                                                    \
         hipLaunchKernelGGL((msd_fft_cols_small_fused_kernel<A, B, float>), gf, dim3(THREADS), 0, stream, pos32, n_total, \
@@ -1887,9 +1985,6 @@ inline void launch(const Shape &sh, hipStream_t stream, const double *pos, int64
     hipLaunchKernelGGL(msd_partials_reduce_kernel, dim3((unsigned)((int64_t(B) * (A / 2) + 255) / 256),          \
                        (unsigned)n_blocks), dim3(256), 0, stream, part, n_sg, B, 512 / A, A / 2, t_block, traj, dsq); \
     launch_rows<A, B>(gb, stream, Y, p_pad, tw_r2, Pfull, accumulate, pgm)
-        // (the pair-group-major layout of the 400-point family gains nothing here — this pass A already stores runs of
-        // NC x 128 B = 1 KB: C4 size in 25 / 13 / 7 blocks 25.6 / 27.1 / 28.8 ms k1-major, 26.1 / 27.4 / 28.6 pair-group-major)
-        const int pgm = 0;
         if (sh.r2 == 128) {
             MDX_MSDFFT_SMALL_FUSED(64, 128);
         } else if (sh.r2 == 256) {
@@ -1900,24 +1995,21 @@ inline void launch(const Shape &sh, hipStream_t stream, const double *pos, int64
             MDX_MSDFFT_SMALL_FUSED(64, 1024);
         }
 #undef MDX_MSDFFT_SMALL_FUSED
-    } else if (sh.r1 == 400 && part) {
+    } else if (pass_a == PASS_A_COLS400_FUSED) {
         // per-frame sums fused into pass A: super groups of SG pair groups, >= ~1024 blocks
         const int n_sg = fused_super_groups(p_pad);
-        // (twelve rounds of the chip's block slots: C4 with one block 27.1 -> 26.2 ms of kernels per step against the
-        // four rounds of round 2 — blocks in more different phases share a CU, and the tail is a twelfth)
-        const int fsplit = slots_split(int64_t(n_sg) * n_blocks, std::min(8, sh.r2), std::min(64, sh.r2), 12);
-        // Y[block][pair group][k1][n2][pair] where a (k1, pair group) run is at least 4 KB (measured: 1 and 2 KB runs cost pass B
-        // 0.3 ms more than the layout saves pass A) and pass B takes the layout
-        const int pg_major = sh.r2 >= 32 ? 1 : 0;
+        const dim3 gf((unsigned)n_sg, (unsigned)cols400_fused_split(sh, n_sg, n_blocks), (unsigned)n_blocks);
 #define MDX_MSDFFT_COLS400(R2_)                                                                                       \
     if (pos32)                                                                                                       \
-        hipLaunchKernelGGL((msd_fft_cols400_fused_kernel<R2_, float>), dim3((unsigned)n_sg, (unsigned)fsplit,        \
-                           (unsigned)n_blocks), dim3(THREADS), 0, stream, pos32, n_total, first, n_elem, t_block,    \
-                           zero_dims, p_pad, tw_r1, twN, Y, part, head, pg_major);                                   \
+        hipLaunchKernelGGL((msd_fft_cols400_fused_kernel<R2_, float>), gf, dim3(THREADS), 0, stream, pos32, n_total, \
+                           first, n_elem, t_block, zero_dims, p_pad, tw_r1, twN, Y, part, head, pgm);                \
     else                                                                                                             \
-        hipLaunchKernelGGL((msd_fft_cols400_fused_kernel<R2_>), dim3((unsigned)n_sg, (unsigned)fsplit, (unsigned)n_blocks), \
-                           dim3(THREADS), 0, stream, pos, n_total, first, n_elem, t_block, zero_dims, p_pad, tw_r1, twN, Y, \
-                           part, head, pg_major)
+        hipLaunchKernelGGL((msd_fft_cols400_fused_kernel<R2_>), gf, dim3(THREADS), 0, stream, pos, n_total, first,   \
+                           n_elem, t_block, zero_dims, p_pad, tw_r1, twN, Y, part, head, pgm);                       \
+    hipLaunchKernelGGL(msd_partials_reduce_kernel,                                                                   \
+                       dim3((unsigned)((int64_t(R2_) * SUMS_ROWS + 255) / 256), (unsigned)n_blocks), dim3(256), 0,   \
+                       stream, part, n_sg, R2_, 1, SUMS_ROWS, t_block, traj, dsq);                                   \
+    launch_rows<400, R2_>(gb, stream, Y, p_pad, tw_r2, Pfull, accumulate, pgm)
         if (sh.r2 == 2) {
             MDX_MSDFFT_COLS400(2);
         } else if (sh.r2 == 4) {
@@ -1940,39 +2032,6 @@ inline void launch(const Shape &sh, hipStream_t stream, const double *pos, int64
             MDX_MSDFFT_COLS400(1024);     // 80.5 KB of LDS: still two blocks per CU
         }
 #undef MDX_MSDFFT_COLS400
-        hipLaunchKernelGGL(msd_partials_reduce_kernel,
-                           dim3((unsigned)((int64_t(sh.r2) * SUMS_ROWS + 255) / 256), (unsigned)n_blocks), dim3(256), 0,
-                           stream, part, n_sg, sh.r2, 1, SUMS_ROWS, t_block, traj, dsq);
-        if (sh.r2 == 2)
-            hipLaunchKernelGGL((msd_fft_rows_tiny_power_kernel<400, 2>), gb, dim3(THREADS), 0, stream, Y, p_pad, Pfull,
-                               accumulate);
-        else if (sh.r2 == 4)
-            hipLaunchKernelGGL((msd_fft_rows_tiny_power_kernel<400, 4>), gb, dim3(THREADS), 0, stream, Y, p_pad, Pfull,
-                               accumulate);
-        else if (sh.r2 == 8)
-            hipLaunchKernelGGL((msd_fft_rows_short_power_kernel<400, 8>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
-                               Pfull, accumulate, pg_major);
-        else if (sh.r2 == 16)
-            hipLaunchKernelGGL((msd_fft_rows_short_power_kernel<400, 16>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
-                               Pfull, accumulate, pg_major);
-        else if (sh.r2 == 32)
-            hipLaunchKernelGGL((msd_fft_rows_short_power_kernel<400, 32>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
-                               Pfull, accumulate, pg_major);
-        else if (sh.r2 == 64)
-            hipLaunchKernelGGL((msd_fft_rows_short_power_kernel<400, 64>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
-                               Pfull, accumulate, pg_major);
-        else if (sh.r2 == 128)
-            hipLaunchKernelGGL((msd_fft_rows_mid_power_kernel<400, 128>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
-                               Pfull, accumulate, pg_major);
-        else if (sh.r2 == 256)
-            hipLaunchKernelGGL((msd_fft_rows_mid_power_kernel<400, 256>), gb, dim3(THREADS), 0, stream, Y, p_pad, tw_r2,
-                               Pfull, accumulate, pg_major);
-        else if (sh.r2 == 512)
-            hipLaunchKernelGGL((msd_fft_rows512_power_kernel<400>), gb, dim3(THREADS), 0, stream, Y, p_pad,
-                               tw_r2, Pfull, accumulate, pg_major);
-        else
-            hipLaunchKernelGGL((msd_fft_rows1024_power_kernel<400>), gb, dim3(THREADS), 0, stream, Y, p_pad,
-                               tw_r2, Pfull, accumulate, pg_major);
     } else if (sh.r1 == 512 && sh.r2 == 512) {
         MDX_MSDFFT_LAUNCH(512, 512);
     } else if (sh.r1 == 1024 && sh.r2 == 512) {

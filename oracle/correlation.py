@@ -20,6 +20,7 @@ optional trailing vector axis) are the reference's.
 from __future__ import annotations
 
 import warnings
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 from scipy import fft as _fft
@@ -170,3 +171,83 @@ def msd_shift_ref(pos1, pos2=None, axis=None, *, average=True):
     if ndim - axis == 3 and average:
         disp = disp.mean(axis=ndim - 2)
     return disp
+
+
+def msd_series_tables(pos, t_block, n_blocks, lags):
+    """Per coordinate series of ``pos[T, n, 3]`` and block ``[b t_block, (b + 1) t_block)``, straight from the windowed
+    definition (nothing FFT-shaped), in ``np.longdouble``:
+
+    * ``sq[b, p, k, l]  = sum_t (x(t + m_l) - x(t))^2`` — differences taken in float64, squares and sums extended;
+    * ``acf[b, p, k, l] = sum_t x(t) x(t + m_l)``;
+    * ``e[b, p, k]      = sum_t x(t)^2``.
+
+    O(T n) per lag.  ``msd_definition_ref`` adds up the series of a particle range; tests that push many ranges of
+    one array build the tables once."""
+    pos = np.asarray(pos, dtype=np.float64)
+    lags = np.asarray(lags, dtype=np.int64)
+    n = pos.shape[1]
+    if pos.shape[0] < t_block * n_blocks or lags.min(initial=0) < 0 or lags.max(initial=0) >= t_block:
+        raise ValueError("blocks or lags outside the trajectory.")
+    sq = np.zeros((n_blocks, n, 3, len(lags)), dtype=np.longdouble)
+    acf = np.zeros_like(sq)
+    e = np.zeros((n_blocks, n, 3), dtype=np.longdouble)
+    step = max(1, (1 << 20) // (3 * n))       # rows per piece: the extended-precision temporaries stay in cache
+
+    def one(task):
+        b, l = task
+        m = int(lags[l])
+        x = pos[b * t_block:(b + 1) * t_block]
+        for t0 in range(0, t_block - m, step):
+            t1 = min(t0 + step, t_block - m)
+            lo, hi = x[t0:t1].astype(np.longdouble), x[t0 + m:t1 + m].astype(np.longdouble)
+            d = (x[t0 + m:t1 + m] - x[t0:t1]).astype(np.longdouble)
+            sq[b, :, :, l] += (d * d).sum(axis=0)
+            acf[b, :, :, l] += (lo * hi).sum(axis=0)
+
+    for b in range(n_blocks):
+        for t0 in range(0, t_block, step):
+            xl = pos[b * t_block + t0:b * t_block + min(t0 + step, t_block)].astype(np.longdouble)
+            e[b] += (xl * xl).sum(axis=0)
+    tasks = [(b, l) for b in range(n_blocks) for l in range(len(lags))]
+    if len(tasks) * t_block * n >= (1 << 24):
+        # numpy releases the interpreter lock inside these loops; every task writes its own slice
+        with ThreadPoolExecutor(max_workers=8) as pool:
+            list(pool.map(one, tasks))
+    else:
+        for task in tasks:
+            one(task)
+    return {"sq": sq, "acf": acf, "e": e, "lags": lags, "t_block": int(t_block)}
+
+
+def msd_definition_ref(pos, t_block, n_blocks, first, count, zero_dims, lags, tables=None):
+    """What ``MsdEngine`` accumulates for ONE push of particles ``[first, first + count)`` of ``pos[T, n, 3]`` with the
+    dimensions of the ``zero_dims`` mask dropped, from the windowed definition, accumulated in ``np.longdouble`` and
+    rounded to float64 once:
+
+    * ``msd[b, l]``   ``sum_p mean_t |r_p(t + m_l) - r_p(t)|^2`` over the kept dimensions;
+    * ``acf[b, l]``   ``sum_{p,k} sum_t x(t) x(t + m_l)``, not normalised (``result_acf``);
+    * ``traj[b, t, k]`` ``sum_p x_pk(t)`` (zero in a dropped dimension) and ``A[b, t, k] = sum_p |x_pk(t)|``;
+    * ``E[b]``        ``sum_{p, k kept, t} x^2``: the scale of the rounding floor of ``msd`` and ``acf``.
+
+    ``tables``: ``msd_series_tables`` of the same ``pos``, blocks and lags (computed here when not given)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    if tables is None:
+        tables = msd_series_tables(pos[:, first:first + count], t_block, n_blocks, lags)
+        rows = slice(0, count)
+    else:
+        rows = slice(first, first + count)
+    lags = np.asarray(lags, dtype=np.int64)
+    if not np.array_equal(tables["lags"], lags) or tables["t_block"] != t_block:
+        raise ValueError("tables of other lags or blocks.")
+    keep = [k for k in range(3) if not (zero_dims >> k) & 1]
+    windows = (t_block - lags).astype(np.longdouble)
+    msd = (tables["sq"][:, rows][:, :, keep].sum(axis=(1, 2)) / windows).astype(np.float64)
+    acf = tables["acf"][:, rows][:, :, keep].sum(axis=(1, 2)).astype(np.float64)
+    energy = tables["e"][:, rows][:, :, keep].sum(axis=(1, 2)).astype(np.float64)
+    x = pos[:t_block * n_blocks, first:first + count].reshape(n_blocks, t_block, count, 3).astype(np.longdouble)
+    for k in range(3):
+        if k not in keep:
+            x[..., k] = 0
+    traj = x.sum(axis=2).astype(np.float64)
+    a = np.abs(x).sum(axis=2).astype(np.float64)
+    return {"msd": msd, "acf": acf, "traj": traj, "A": a, "E": energy}

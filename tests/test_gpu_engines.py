@@ -630,8 +630,9 @@ def test_rdf_mixed_orthorhombic_and_triclinic_frames_in_one_batch():
                                   (51200, 1, 11, 0), (51201, 1, 7, 0), (45000, 2, 29, 5), (32769, 1, 64, 0),
                                   # 409 600 = 400 x 1024 points: 131 073 .. 204 800
                                   (204800, 1, 7, 0), (204801, 1, 5, 0), (131073, 1, 9, 2), (160000, 2, 6, 0),
-                                  # rows of whole 128-byte lines (16 | 3 n_atoms): the second push starts 9
-                                  # coordinates into a line and pass A enters its chunk early (head)
+                                  # 16 | 3 n_atoms.  (These pushes go through the host entry point, which stages the
+                                  # selection: the device side sees first = 0 and head = 0.  The pushes that pass A
+                                  # enters early are in test_gpu_msd_routes.py, case C.)
                                   (70001, 1, 16, 0), (40000, 2, 32, 5), (50000, 1, 48, 2)])
 def test_msd_own_two_pass_transform_equals_rocfft(case, monkeypatch):
     """n_fft = 2^13, 2^14, 25 600, 2^15, 51 200, 2^16, 102 400, 204 800, 2^18, 2^19, 2^20: the engine's own packed

@@ -101,3 +101,38 @@ def test_errors():
         oc.correlation_fft_ref(np.ones((2, 2, 2)), axis=2)
     with pytest.raises(ValueError):
         oc.msd_fft_ref(np.ones((4, 3)), np.ones((1, 3)))
+
+
+def test_msd_definition_ref_is_the_windowed_definition():
+    """Against msd_shift_ref / correlation_shift_ref, on a closed form, with shared tables, and its exact zeros."""
+    rng = np.random.default_rng(11)
+    t_block, n_blocks = 37, 2
+    pos = np.cumsum(rng.normal(0, 0.3, (t_block * n_blocks + 2, 9, 3)), axis=0) + 5.0    # 2 trailing frames unused
+    lags = np.array([0, 1, 5, 36])
+    first, count = 2, 6
+    sel = pos[:t_block * n_blocks, first:first + count].reshape(n_blocks, t_block, count, 3)
+    for zero_dims in (0, 2, 5):
+        x = sel.copy()
+        x[..., [k for k in range(3) if (zero_dims >> k) & 1]] = 0
+        ref = oc.msd_definition_ref(pos, t_block, n_blocks, first, count, zero_dims, lags)
+        assert np.allclose(ref["msd"], oc.msd_shift_ref(x, axis=1, average=False).sum(-1)[:, lags], rtol=1e-13)
+        acf = oc.correlation_shift_ref(x, axis=1, vector=True).sum(-1) * np.arange(t_block, 0, -1)
+        assert np.allclose(ref["acf"], acf[:, lags], rtol=1e-12)
+        assert np.allclose(ref["traj"], x.sum(2), rtol=1e-14) and np.allclose(ref["A"], np.abs(x).sum(2), rtol=1e-14)
+        assert np.allclose(ref["E"], (x * x).sum((1, 2, 3)), rtol=1e-14)
+        assert np.array_equal(ref["acf"][:, 0], ref["E"])                     # lag 0 of the ACF is the energy
+        # tables of the whole array, shared between pushes
+        tables = oc.msd_series_tables(pos, t_block, n_blocks, lags)
+        shared = oc.msd_definition_ref(pos, t_block, n_blocks, first, count, zero_dims, lags, tables)
+        assert all(np.array_equal(ref[k], shared[k]) for k in ref)
+    nothing = oc.msd_definition_ref(pos, t_block, n_blocks, first, count, 7, lags)
+    assert not any(v.any() for v in nothing.values())
+    # x(t) = v t: MSD(m) = |v|^2 m^2 per particle
+    t = np.arange(20.0)[:, None, None]
+    line = t * np.array([[1.0, 2.0, 2.0], [0.0, 3.0, 4.0]])[None]
+    ref = oc.msd_definition_ref(line, 20, 1, 0, 2, 0, np.arange(20))
+    assert np.array_equal(ref["msd"][0], (9.0 + 25.0) * np.arange(20.0) ** 2)
+    with pytest.raises(ValueError):
+        oc.msd_definition_ref(pos, t_block, n_blocks, first, count, 0, np.array([t_block]))
+    with pytest.raises(ValueError):
+        oc.msd_definition_ref(pos, t_block, n_blocks, first, count, 0, lags[:2], tables)
