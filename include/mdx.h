@@ -1057,6 +1057,50 @@ int mdx_boo_stats(mdx_boo_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *bonds, int64_t *degenerate, int64_t *max_row);
 int mdx_boo_enable_timing(mdx_boo_t h, int on);
 
+/* ---- self-overlap Q(t) and four-point susceptibility chi_4(t) ------------------------------------------------------
+ * Groups, rows, frames, lags, zero_dims, x, image and the unwrap rule as for mdx_vh_*; origin_step >= 1.  cutoffs:
+ * float64 [n_cutoffs], 1 ... 8 of them, finite, not negative, strictly increasing.  Per lag k, cutoff c and frame
+ * f >= lags[k] whose origin f0 = f - lags[k] satisfies f0 % origin_step == 0, in float64 with separate multiply and
+ * add (float32 coordinates are widened before any arithmetic):
+ *     d = x(f) - x(f0), +0.0 for a dropped component;  r2 = (dx*dx + dy*dy) + dz*dz;
+ *     w = r2 <= cutoffs[c] * cutoffs[c] (one float64 multiply on the host; no sqrt; a NaN r2 is not counted);
+ *     Q[k][g][c](f0) = the number of points of group g with w;  S1[k][g][c] += Q;  S2[k][g][c] += Q*Q;
+ *     n_origins[k] = the number of such f0.
+ * Everything added is an integer, so S1, S2 and n_origins are identical across the three input routes, across any split
+ * of the frames into calls, slabs or point segments, and after a reset (csrc/mdx_chi4_device.hpp).  The engine keeps
+ * max(lags) + one slab of float64 frames in HBM (MDX_ERR_OUT_OF_MEMORY when that does not fit).  A handle touches its
+ * device with the first frame: mdx_chi4_create and every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_chi4 *mdx_chi4_t;
+int mdx_chi4_create(mdx_chi4_t *out, int dev, int n_groups, const int64_t *n_points, int n_cutoffs,
+                    const double *cutoffs, int n_lags, const int64_t *lags, int64_t origin_step, int zero_dims);
+int mdx_chi4_destroy(mdx_chi4_t h);
+/* Forgets the frames seen, the history and the unwrap state and zeroes the sums. */
+int mdx_chi4_reset(mdx_chi4_t h);
+/* As mdx_vh_set_unwrap.  dims: float64 [3] box lengths, or NULL: off.  Only before the first frame. */
+int mdx_chi4_set_unwrap(mdx_chi4_t h, const double *dims);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history and the scratch), as
+ * mdx_vh_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
+int mdx_chi4_set_slab_frames(mdx_chi4_t h, int64_t frames);
+/* Points of the concatenated groups that one block of the counting kernel walks: a multiple of 64; 0 restores the
+ * default.  For tests and measurement: the results do not depend on it.  Only before the first frame. */
+int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points);
+/* The accumulate calls refuse (MDX_ERR_INVALID_VALUE), before they touch a device or read a frame, a call after which
+ * (frames seen) * max_g(n_points[g])^2 would reach 2^63: S2 could then leave an int64.  What was accumulated before
+ * stays valid.  Host float32 [n_frames][n][3] through the pinned ring. */
+int mdx_chi4_accumulate(mdx_chi4_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_chi4_synchronize). */
+int mdx_chi4_accumulate_device(mdx_chi4_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                               const int32_t *index, int64_t n_index);
+int mdx_chi4_accumulate_traj(mdx_chi4_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                             const int32_t *index, int64_t n_index);
+int mdx_chi4_synchronize(mdx_chi4_t h);
+/* sums, square_sums: int64 [n_lags][n_groups][n_cutoffs] = S1, S2; n_origins: int64 [n_lags]. */
+int mdx_chi4_result(mdx_chi4_t h, int64_t *sums, int64_t *square_sums, int64_t *n_origins);
+/* evaluations: the contract's count of displacements so far, sum over the lags of origins x points. */
+int mdx_chi4_stats(mdx_chi4_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations);
+int mdx_chi4_enable_timing(mdx_chi4_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

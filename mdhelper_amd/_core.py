@@ -917,6 +917,63 @@ class VanHoveEngine(_SlabbedFrameEngine):
         return out
 
 
+class FourPointEngine(_SlabbedFrameEngine):
+    """``mdx_chi4_*``: per lag, group and cutoff the number ``Q`` of points with ``|x(f0 + lag) - x(f0)|^2 <= a^2``
+    and, over the origins ``f0`` that are multiples of ``origin_step``, the sums of ``Q`` and of ``Q * Q``.  All
+    integers: the same bits whatever the route, split, slab or segment.  The device is first touched by the first
+    frame, so the argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_chi4"
+    _stats_extra = (("evaluations", c_int64),)
+    TILE = 64           # points per load: a load never spans two groups (CHI4_TILE of csrc/mdx_chi4_device.hpp)
+    MAX_CUTOFFS = 8     # cutoffs at most (CHI4_MAX_CUTOFFS)
+
+    def __init__(self, n_points, cutoffs, lags, *, origin_step=1, zero_dims=0, dev=0, timing=False):
+        self.n_per_group = np.ascontiguousarray(np.atleast_1d(n_points), dtype=np.int64)
+        if self.n_per_group.ndim != 1 or len(self.n_per_group) == 0:
+            raise ValueError("n_points must hold one entry per group.")
+        self.n_groups = len(self.n_per_group)
+        self.n_points = int(self.n_per_group.sum())
+        self.cutoffs = np.ascontiguousarray(np.atleast_1d(cutoffs), dtype=np.float64)
+        if self.cutoffs.ndim != 1 or not 1 <= len(self.cutoffs) <= self.MAX_CUTOFFS:
+            raise ValueError(f"cutoffs must hold 1 to {self.MAX_CUTOFFS} cutoffs.")
+        self.n_cutoffs = len(self.cutoffs)
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        h = c_void_p()
+        check(lib().mdx_chi4_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), self.n_cutoffs,
+                                    _ptr(self.cutoffs), self.n_lags, _ptr(self.lags), int(origin_step),
+                                    int(zero_dims)))
+        self._adopt(h, dev, timing)
+
+    def set_unwrap(self, dims):
+        """The reference's global unwrap from frame to frame with the box lengths ``dims``; the first frame is its
+        own start.  ``dims=None`` switches it off.  Only before the first frame."""
+        if dims is None:
+            check(lib().mdx_chi4_set_unwrap(self.handle, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        check(lib().mdx_chi4_set_unwrap(self.handle, _ptr(d)))
+
+    def set_segment_points(self, points):
+        """Points one block of the counting kernel walks: a multiple of 64, 0 restores the default.  For tests and
+        measurement: the results do not depend on it.  Only before the first frame."""
+        check(lib().mdx_chi4_set_segment_points(self.handle, int(points)))
+
+    def result(self):
+        """``(sums, square_sums, n_origins)``: int64 ``[n_lags, G, n_cutoffs]`` twice — the sums of ``Q`` and of
+        ``Q * Q`` over the origins — and int64 ``[n_lags]``, the origins of every lag."""
+        sums = np.zeros((self.n_lags, self.n_groups, self.n_cutoffs), dtype=np.int64)
+        square_sums = np.zeros_like(sums)
+        n_origins = np.zeros(self.n_lags, dtype=np.int64)
+        check(lib().mdx_chi4_result(self.handle, _ptr(sums), _ptr(square_sums), _ptr(n_origins)))
+        return sums, square_sums, n_origins
+
+
 class DistinctVanHoveEngine(_SlabbedFrameEngine):
     """``mdx_vhd_*``: per lag the histogram of the minimum-image distances ``|x2_j(f0 + lag) - x1_i(f0)|`` over every
     pair of points (``j != i`` with ``same``) and every frame pair whose origin ``f0`` is a multiple of

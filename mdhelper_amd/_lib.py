@@ -324,6 +324,20 @@ _SIGNATURES = {
     "mdx_boo_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_boo_enable_timing": (c_int, [_vp, c_int]),
+    # self-overlap and four-point susceptibility
+    "mdx_chi4_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int, _vp, c_int, _vp, c_int64, c_int]),
+    "mdx_chi4_destroy": (c_int, [_vp]),
+    "mdx_chi4_reset": (c_int, [_vp]),
+    "mdx_chi4_set_unwrap": (c_int, [_vp, _vp]),
+    "mdx_chi4_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_chi4_set_segment_points": (c_int, [_vp, c_int64]),
+    "mdx_chi4_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_chi4_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_chi4_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_chi4_synchronize": (c_int, [_vp]),
+    "mdx_chi4_result": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_chi4_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_chi4_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

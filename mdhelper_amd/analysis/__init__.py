@@ -6,7 +6,8 @@ from .structure import (IntermediateScatteringFunction, RadialDistributionFuncti
                         StructureFactor)
 from .angle import AngularDistribution  # noqa: F401
 from .cluster import Clusters  # noqa: F401
-from .dynamics import (DistinctVanHove, OrientationalRelaxation, PairResidence, VanHove,  # noqa: F401
+from .dynamics import (DistinctVanHove, FourPointSusceptibility, OrientationalRelaxation,  # noqa: F401
+                       PairResidence, VanHove, calculate_four_point_susceptibility,
                        calculate_non_gaussian_parameter, calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
 from .order import BondOrientationalOrder  # noqa: F401

@@ -4,7 +4,10 @@ displacement magnitudes after a lag and the non-Gaussian parameter — ``calcula
 ``DistinctVanHove`` — the distinct part ``G_d(r, t)``, the time-dependent pair distribution — and ``PairResidence`` —
 the intermittent and continuous survival functions of the contacts between two groups (ion-pair lifetimes, residence
 times) with ``calculate_residence_time`` — and ``OrientationalRelaxation`` — the reorientation functions ``C_1(t)`` and
-``C_2(t)`` of unit vectors (bonds, segments, molecular axes) and their nematic order tensor.
+``C_2(t)`` of unit vectors (bonds, segments, molecular axes) and their nematic order tensor — and
+``FourPointSusceptibility`` — the self-overlap function ``Q_s(t)``, its fluctuation over the time origins, the
+four-point susceptibility ``chi_4(t)``, the structural relaxation time and the peak of ``chi_4`` (whether the motion
+is cooperative), with ``calculate_four_point_susceptibility``.
 
 The reference package has no counterpart; this sits next to ``IntermediateScatteringFunction(incoherent=True)``
 (``F_s(q, t)``, the Fourier transform of ``G_s``) and the mean squared displacements of the correlation
@@ -21,7 +24,11 @@ histograms (csrc/mdx_vanhove_distinct_device.hpp).  ``PairResidence`` feeds them
 origin that are there again, or still (csrc/mdx_residence_device.hpp).  ``OrientationalRelaxation`` feeds the distinct
 atoms of its vectors to the orientation engine (``mdx_ori_*``), which keeps a history of float64 unit vectors in HBM,
 adds the first and second Legendre polynomials of ``u(f) . u(f - lag)`` per vector in frame order and the products
-``u_a u_b`` of every frame per group (csrc/mdx_orient_device.hpp).
+``u_a u_b`` of every frame per group (csrc/mdx_orient_device.hpp).  ``FourPointSusceptibility`` feeds its blocks to
+the four-point engine (``mdx_chi4_*``), which keeps the van Hove engine's history of float64 points, counts per frame
+pair, group and cutoff the points that moved at most the cutoff (a wave-wide count, not a per-point accumulator) and
+adds that count and its square over the time origins: all integers, the same bits on every route
+(csrc/mdx_chi4_device.hpp).
 """
 
 from __future__ import annotations
@@ -627,3 +634,199 @@ class OrientationalRelaxation(EngineFedAnalysis, DynamicAnalysisBase):
         self.results.relaxation_times = np.array(
             [[calculate_residence_time(self.results.times, c[:, g]) for g in range(self._n_groups)]
              for c in (self.results.c1, self.results.c2)])
+
+
+def _exact_integers(a, name: str) -> np.ndarray:
+    """``a`` as an object array of Python ints."""
+    a = np.asarray(a)
+    if a.dtype != object and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"'{name}' must hold integers.")
+    return a.astype(object)
+
+
+def calculate_four_point_susceptibility(sums, square_sums, n_origins, n_points):
+    r"""
+    Four-point susceptibility from the sums of the overlap ``Q`` and of its square over ``n`` time origins,
+
+    .. math:: \chi_4=N\big(\langle q^2\rangle-\langle q\rangle^2\big)=\frac{n\,S_2-S_1^2}{n^2N},\qquad q=Q/N
+
+    the population variance of ``q`` over the origins times the number of points ``N``.  ``n S_2 - S_1^2`` is formed
+    in exact integer arithmetic (Python ints) and divided only after that: both terms are of order ``10^18`` and more
+    for a long trajectory of a large group, and a float64 difference of them is noise.
+
+    sums, square_sums : integer array-like — ``S_1`` and ``S_2``; ``[N_t, N_g, N_a]`` as in
+        ``FourPointSusceptibility.results``, or anything that broadcasts with the two below
+    n_origins : integer array-like — the origins; ``[N_t]`` for three-dimensional sums
+    n_points : integer array-like — the points of the groups; ``[N_g]`` for three-dimensional sums
+
+    Returns float64 of the broadcast shape (a float for scalars): NaN without a warning where ``n_origins`` or
+    ``n_points`` is 0.
+    """
+    s1, s2 = _exact_integers(sums, "sums"), _exact_integers(square_sums, "square_sums")
+    n, size = _exact_integers(n_origins, "n_origins"), _exact_integers(n_points, "n_points")
+    if s1.ndim == 3 and n.ndim == 1 and size.ndim <= 1:
+        n = n.reshape(-1, 1, 1)
+        size = size.reshape(1, -1, 1)
+    numerator = n * s2 - s1 * s1
+    denominator = n * n * size
+    ratio = np.frompyfunc(lambda a, b: a / b if b else float("nan"), 2, 1)     # int / int: correctly rounded
+    out = np.asarray(ratio(numerator, denominator), dtype=float)
+    return float(out) if out.ndim == 0 else out
+
+
+class FourPointSusceptibility(EngineFedAnalysis, DynamicAnalysisBase):
+    r"""
+    Self-overlap function and four-point susceptibility: with
+    :math:`Q(t_0,t)=\sum_i\Theta\big(a-|\mathbf r_i(t_0+t)-\mathbf r_i(t_0)|\big)` the number of points of a group
+    that moved at most ``a`` in ``t``,
+
+    .. math:: Q_s(t)=\frac{\langle Q\rangle_{t_0}}N,\qquad
+              \chi_4(t)=\frac{\langle Q^2\rangle_{t_0}-\langle Q\rangle_{t_0}^2}N
+
+    per group and cutoff ``a``, over the time origins ``t_0`` of the analysed frames.  ``Q_s`` falls to ``1/e`` at the
+    structural relaxation time :math:`\tau_\alpha`; ``chi_4`` measures how cooperative the motion is: its peak height
+    gives the size of the dynamically correlated regions and the peak time their lifetime.
+
+    Parameters
+    ----------
+    groups : AtomGroup or sequence of AtomGroups
+    cutoffs : float or sequence of up to 8 floats — the overlap lengths ``a`` (Å), not negative, strictly increasing;
+        a displacement of exactly ``a`` counts
+    lags : array-like of int, keyword-only — lag times in frames of the analysed selection, strictly increasing,
+        non-negative
+    n_lags : int, keyword-only — shorthand for ``lags=arange(n_lags)``; with neither, every analysed frame is a lag
+    origin_step : int, keyword-only — every ``origin_step``-th analysed frame is a time origin
+    dt : float, keyword-only — time between trajectory frames (ps); defaults to the trajectory's
+    dimensions : array-like ``(3,)``, keyword-only — box lengths (Å) for ``unwrap``; defaults to the universe's
+    drop_axis : {0, 1, 2, "x", "y", "z"}, keyword-only — a component that takes no part (slabs, 2-D systems)
+    unwrap : bool, keyword-only — follow the particles across the periodic boundaries from frame to frame (a step
+        of at least half a box length between analysed frames counts as a crossing); for wrapped trajectories
+    verbose : bool
+    device : keyword-only — the HIP device
+
+    Results
+    -------
+    ``results.times`` ``[N_t]`` (ps), ``results.cutoffs`` ``[N_a]`` (Å), ``results.n_origins`` ``[N_t]``,
+    ``results.sums`` and ``results.square_sums`` ``[N_t, N_g, N_a]`` (int64, the sums of ``Q`` and of ``Q^2`` over the
+    origins), ``results.overlap`` — ``sums / (n_origins N_g)`` — ``results.chi4`` —
+    ``calculate_four_point_susceptibility``: ``N_g`` times the population variance of ``Q / N_g`` over the origins —
+    and ``results.units``.  A lag without an origin and an empty group give NaN without a warning.
+    ``calculate_relaxation_times()`` adds ``results.relaxation_time``, ``results.peak_time`` and
+    ``results.peak_height``.
+
+    Limits: ``chi_4`` is the variance over the time origins of one trajectory in its own ensemble (the constraints of
+    the simulation suppress a part of the fluctuations), and neighbouring origins are correlated: it needs many more
+    frames than ``Q_s``.  More than one rank raises ``ValueError``; molecule centres are not supported; the frames
+    must be evenly spaced and go forward in time; there is no CPU fallback: without a HIP device ``run()`` raises
+    ``RuntimeError``.
+    """
+
+    def __init__(self, groups, cutoffs, *, lags=None, n_lags: int = None, origin_step: int = 1, dt=None,
+                 dimensions=None, drop_axis=None, unwrap: bool = False, verbose: bool = True, **kwargs) -> None:
+        self._groups = [groups] if hasattr(groups, "universe") else list(groups)
+        self._n_groups = len(self._groups)
+        self.universe = self._groups[0].universe
+        super().__init__(self.universe.trajectory, False, verbose, **kwargs)
+        if self._comm.world_size > 1:
+            raise ValueError("FourPointSusceptibility runs on one rank: every lag needs every frame, and the overlap "
+                             "of a frame pair needs every point.")
+
+        a = np.atleast_1d(np.asarray(strip_unit(cutoffs, "angstrom")[0], dtype=float))
+        if a.ndim != 1 or not 1 <= len(a) <= _core.FourPointEngine.MAX_CUTOFFS:
+            raise ValueError(f"'cutoffs' must hold 1 to {_core.FourPointEngine.MAX_CUTOFFS} cutoffs.")
+        if not np.all(np.isfinite(a)) or a[0] < 0 or np.any(np.diff(a) <= 0):
+            raise ValueError("'cutoffs' must be finite, non-negative and strictly increasing.")
+        self._cutoffs = a
+
+        self._lags = parse_lags(lags, n_lags)
+        self._origin_step = int(origin_step)
+        if self._origin_step < 1:
+            raise ValueError("'origin_step' must be at least 1.")
+
+        self._dt = strip_unit(dt or self._trajectory.dt, "picosecond")[0]
+        self._drop_axis = parse_drop_axis(drop_axis)
+        if dimensions is not None:
+            if len(dimensions) != 3:
+                raise ValueError("'dimensions' must have length 3.")
+            self._dimensions = np.asarray(strip_unit(dimensions, "angstrom")[0], dtype=float)
+        elif self.universe.dimensions is not None:
+            self._dimensions = np.asarray(self.universe.dimensions[:3], dtype=float)
+        else:
+            self._dimensions = None
+        if unwrap and self._dimensions is None:
+            raise ValueError("unwrap=True needs the box lengths: no system dimensions found or provided.")
+        self._unwrap = unwrap
+
+        self._Ns = np.fromiter((g.n_atoms for g in self._groups), dtype=int, count=self._n_groups)
+        self._N = int(self._Ns.sum())
+        self._verbose = verbose
+
+    # ------------------------------------------------------------------ protocol
+
+    def _prepare(self) -> None:
+        df = self._frame_stride()
+        lags = np.arange(self.n_frames, dtype=np.int64) if self._lags is None else self._lags
+        self._lags_run = lags
+        self.results.times = lags * df * self._dt
+        self.results.cutoffs = self._cutoffs.copy()
+        # the origins of a lag: the multiples of origin_step below n_frames - lag
+        self.results.n_origins = -(-np.maximum(self.n_frames - lags, 0) // self._origin_step)
+        self.results.units = {"results.times": "picosecond", "results.cutoffs": "angstrom",
+                              "results.relaxation_time": "picosecond", "results.peak_time": "picosecond"}
+        _lib.require_device(self._device)
+        # lags without an origin never meet a frame pair: the engine gets the others
+        self._live = lags < self.n_frames
+        engine = None
+        if self._live.any():
+            engine = _core.FourPointEngine(self._Ns, self._cutoffs, lags[self._live], origin_step=self._origin_step,
+                                           zero_dims=zero_dims(self._drop_axis), dev=self._device)
+            if self._unwrap:
+                engine.set_unwrap(self._dimensions)
+        self._feed_engine(engine, np.concatenate([np.asarray(g.indices) for g in self._groups]))
+
+    def _conclude(self) -> None:
+        self._batch.flush()
+        shape = (len(self._lags_run), self._n_groups, len(self._cutoffs))
+        sums, square_sums = np.zeros(shape, dtype=np.int64), np.zeros(shape, dtype=np.int64)
+        if self._engine is not None:
+            try:
+                sums[self._live], square_sums[self._live], _ = self._engine.result()      # n_origins: as _prepare's
+            finally:
+                self._engine.close()
+        terms = (self.results.n_origins[:, None] * self._Ns[None, :]).astype(float)
+        terms[terms == 0] = np.nan          # no origin (or an empty group): NaN, without a warning
+        self.results.sums = sums
+        self.results.square_sums = square_sums
+        self.results.overlap = sums / terms[:, :, None]
+        self.results.chi4 = calculate_four_point_susceptibility(sums, square_sums, self.results.n_origins, self._Ns)
+
+    def calculate_relaxation_times(self) -> None:
+        """``results.relaxation_time`` ``[N_g, N_a]``: the time where ``results.overlap`` first falls to ``1/e``, by
+        linear interpolation between the two lags that bracket the crossing; NaN where it is not bracketed (the
+        overlap never falls that far, is there already at the first lag, or the lag before the crossing has no
+        value).  ``results.peak_time`` and ``results.peak_height`` ``[N_g, N_a]``: the largest finite value of
+        ``results.chi4`` and its time (the first one, if several lags share it); NaN where there is none.  A peak
+        at the last lag means that ``chi_4`` may still be rising there."""
+        if "overlap" not in self.results:
+            raise RuntimeError("Call run() before calculate_relaxation_times().")
+        times = np.asarray(self.results.times, dtype=float)
+        overlap = np.asarray(self.results.overlap, dtype=float)
+        chi4 = np.asarray(self.results.chi4, dtype=float)
+        level = np.exp(-1.0)
+        tau = np.full(overlap.shape[1:], np.nan)
+        for g, c in np.ndindex(*tau.shape):
+            q = overlap[:, g, c]
+            below = np.flatnonzero(q <= level)              # a NaN is not below
+            if len(below) == 0 or below[0] == 0:
+                continue
+            i = below[0]
+            if not q[i - 1] > level:                        # NaN before the crossing
+                continue
+            tau[g, c] = times[i - 1] + (q[i - 1] - level) / (q[i - 1] - q[i]) * (times[i] - times[i - 1])
+        finite = np.isfinite(chi4)
+        best = np.where(finite, chi4, -np.inf).argmax(axis=0) if len(chi4) else np.zeros(chi4.shape[1:], dtype=int)
+        some = finite.any(axis=0)
+        height = np.take_along_axis(chi4, best[None], axis=0)[0] if len(chi4) else np.full(chi4.shape[1:], np.nan)
+        self.results.relaxation_time = tau
+        self.results.peak_time = np.where(some, times[best] if len(times) else np.nan, np.nan)
+        self.results.peak_height = np.where(some, height, np.nan)
