@@ -844,12 +844,22 @@ struct FrameSource {
     virtual bool resident() const { return false; }
 };
 
-// frames per unwrap launch: ~64 MB of staged frames, or (resident sources: nothing is staged) as many as the
-// grid's second dimension takes
+// (MDX_MSD_STAGE_BYTES: test hook, so that small inputs run through several frame blocks and particle chunks;
+// 0 when unset)
+static int64_t msd_stage_bytes_hook()
+{
+    const char *env = getenv("MDX_MSD_STAGE_BYTES");
+    return env ? std::max<int64_t>(1, atoll(env)) : 0;
+}
+
+// frames per unwrap launch: ~64 MB of staged frames (test hook: that many bytes), or (resident sources: nothing is
+// staged) as many as the grid's second dimension takes
 static int64_t msd_frame_block(const FrameSource &src, int64_t n_frames, int64_t n_rows)
 {
+    const int64_t hook = msd_stage_bytes_hook();
+    const int64_t staged = hook ? hook : (int64_t(64) << 20);
     const int64_t most = src.resident() ? int64_t(32768) * UNWRAP_SEG
-                                        : (int64_t(64) << 20) / (int64_t(3) * src.elem() * n_rows);
+                                        : staged / (int64_t(3) * src.elem() * n_rows);
     return std::max<int64_t>(1, std::min(n_frames, most));
 }
 
@@ -1060,7 +1070,9 @@ static int msd_system_com_frames(mdx_msd *h, FrameSource &src, int64_t n_frames,
 // Centres of mass of molecules [m0, m0 + n_mol) from the unwrapped float64 block x[frame][c][3] of
 // their particles (rows a0 .. a0 + c of the selection): sum_a m_a x_a in row order with separate
 // multiply and add, one division — numpy.bincount(weights=m * x) / bincount(weights=m), the
-// reference's center_of_mass (algorithm/molecule.py:300-306) — then the frame's shift.
+// reference's center_of_mass (algorithm/molecule.py:300-306) — then the frame's shift.  (__dmul_rn / __dadd_rn are
+// plain * and + in HIP's headers and were contracted into one fused multiply-add, one rounding instead of two: an ulp
+// off the reference in a fifth of the centres.  The products and sums are written out under contract(off) instead.)
 __global__ void msd_molecule_com_kernel(
     const double *__restrict__ x, int64_t c, int64_t a0, const int64_t *__restrict__ offsets,
     const double *__restrict__ masses, const double *__restrict__ total, int64_t m0, int64_t n_mol,
@@ -1074,8 +1086,11 @@ __global__ void msd_molecule_com_kernel(
     const int k = int(i - 3 * m);
     const double *row = x + f * c * 3 + k;
     double acc = 0.0;
-    for (int64_t a = offsets[m0 + m]; a < offsets[m0 + m + 1]; ++a)
-        acc = __dadd_rn(acc, __dmul_rn(masses[a], row[3 * (a - a0)]));
+    for (int64_t a = offsets[m0 + m]; a < offsets[m0 + m + 1]; ++a) {
+#pragma clang fp contract(off)
+        const double p = masses[a] * row[3 * (a - a0)];
+        acc = acc + p;
+    }
     double v = acc / total[m0 + m];
     if (shift)
         v = __dsub_rn(v, shift[3 * f + k]);
@@ -1098,7 +1113,9 @@ static int msd_push_frames(mdx_msd *h, int group, FrameSource &src, int64_t n_se
     size_t free_b = 0, total_b = 0;
     MDX_HIP(hipMemGetInfo(&free_b, &total_b));
     free_b += h->d_stage.bytes + h->d_mol_com.bytes + cached_device_bytes(h->dev);
-    int64_t chunk = std::max<int64_t>(1, int64_t(double(free_b) * (molecules ? 0.2 : 0.3)) / (T * 24));
+    const int64_t hook = msd_stage_bytes_hook();   // test hook: the budget of a chunk in bytes
+    const int64_t budget = hook ? hook : int64_t(double(free_b) * (molecules ? 0.2 : 0.3));
+    int64_t chunk = std::max<int64_t>(1, budget / (T * 24));
     chunk = std::min(chunk, n_sel);
     chunk = ceil_div(n_sel, ceil_div(n_sel, chunk));
     // chunk boundaries in rows: whole molecules only

@@ -17,6 +17,12 @@ PASS_A = ("rocfft", "single400", "cols400_fused", "cols_small_fused", "cols")
 PASS_B = ("none", "tiny", "short", "mid", "rows512", "rows1024", "general")
 EPS = 2.0 ** -52
 C_MAX = 4096.0
+# the constant of the bound |got - ref| <= C[route] * unit (unit_of) per pass-A/pass-B route: 8 x the largest ratio
+# observed by test_gpu_msd_routes.py on an MI355X (the table in its docstring), rounded up to a power of two
+ROUTE_C = {"rocfft/none": 8.0, "single400/none": 8.0, "cols400_fused/tiny": 4.0, "cols400_fused/short": 8.0,
+           "cols400_fused/mid": 4.0, "cols400_fused/rows512": 4.0, "cols400_fused/rows1024": 8.0,
+           "cols_small_fused/mid": 8.0, "cols_small_fused/rows512": 4.0, "cols_small_fused/rows1024": 8.0,
+           "cols/rows512": 8.0, "cols/rows1024": 8.0}
 STEP = 0.3          # standard deviation of a walk's steps
 BOX = 33.0
 

@@ -55,9 +55,7 @@ from mdhelper_amd import _core  # noqa: E402
 from oracle import correlation as oc  # noqa: E402
 
 C_MAX = mc.C_MAX
-C = {"rocfft/none": 8.0, "single400/none": 8.0, "cols400_fused/tiny": 4.0, "cols400_fused/short": 8.0,
-     "cols400_fused/mid": 4.0, "cols400_fused/rows512": 4.0, "cols400_fused/rows1024": 8.0, "cols_small_fused/mid": 8.0,
-     "cols_small_fused/rows512": 4.0, "cols_small_fused/rows1024": 8.0, "cols/rows512": 8.0, "cols/rows1024": 8.0}
+C = mc.ROUTE_C              # one table for this module and test_gpu_msd_ingest.py
 OBSERVED = {}            # route -> (largest ratio seen, the case that gave it)
 PLAN = _core.MsdEngine.plan
 PASS_A, PASS_B = _core.MsdEngine.PASS_A, _core.MsdEngine.PASS_B
