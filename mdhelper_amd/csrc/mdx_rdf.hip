@@ -366,6 +366,7 @@ struct mdx_rdf {
     DeviceBuffer d_thresh, d_counts, d_total, d_pack1, d_pack2, d_misc, d_tri;
     DeviceBuffer d_stats;   // RDF_STAT_SHARDS x RDF_STAT_STRIDE 64-bit words (mdx_rdf_device.hpp)
     DeviceBuffer d_work;    // work counters of the persistent pair kernel (one line per XCD)
+    DeviceBuffer d_frame_geo;   // frame constants of one pair launch (rdf_cell_frame_geo_kernel)
     const void *occ_kernel = nullptr;   // occupancy of the persistent pair kernel: last kernel / LDS size asked for
     size_t occ_lds = 0;
     int64_t occ_blocks_per_xcd = 1;
@@ -494,11 +495,11 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
                            0, h->stream, d_boxes, n_frames, d_misc + 1);
 
     // LDS of the pair kernel: 4 wave slabs + thresholds + the histogram in n_hist interleaved replicas
-    // (HistLdsRep): 8 while seven blocks of a CU still fit (the kernel's static LDS is 8.4 KB), fewer for
+    // (HistLdsRep): 8 while seven blocks of a CU still fit (the kernel's static LDS is 8 992 B), fewer for
     // long bin tables
     size_t base = sizeof(float4) * 256 + sizeof(double) * (h->n_bins + 1);
     const size_t lds_budget = 64 * 1024;
-    const size_t lds_six_blocks = 13 * 1024;   // seven blocks of a CU: (160 KB / 7) - 8.4 KB static
+    const size_t lds_six_blocks = 13 * 1024;   // seven blocks of a CU: (160 KB / 7 = 22.8 KB) - 8.8 KB static = 14.0 KB
     int n_hist = 8;
     while (n_hist > 4 && base + size_t(n_hist) * cell_hist_stride(h->n_bins) * 4 > lds_six_blocks)
         n_hist >>= 1;
@@ -722,12 +723,30 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
             a.work = h->d_work.as<unsigned>();
             {
                 const char *fu = getenv("MDX_RDF_LDS_FLUSH_UNITS");   // test hook: flush the LDS bins (much) more often
-                a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), 1 << 18) : (1u << 18);
+                // (the cap: 1024 + 2 x flush_units <= 2^18, see the pair kernel)
+                const long long cap = (1 << 17) - 512;
+                a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), cap) : (unsigned)cap;
             }
-            const int64_t tiles = n1p / 128;
-            hipEvent_t ev = h->timer.begin();
+            // Items: an i tile against a chunk of its candidate j tiles — every `chunks`-th of them, so that each of an
+            // i tile's items gets its share of the tiles that survive the cull, which lie close together.  A wave
+            // takes an item through alone, and a launch ends with its longest items: where nearly every tile survives
+            // (the launches beyond the skipping step's range) a chunk is as many tiles as one cull pass tests, 64 —
+            // about what a block took over a whole i tile; elsewhere a quarter of the j tiles: four items to an i
+            // tile, as four waves shared it before.  (MDX_RDF_CHUNK_TILES, tiles per chunk: test hook.)
+            {
+                const char *ct = getenv("MDX_RDF_CHUNK_TILES");
+                int64_t c = ct ? atoll(ct) : (skip ? ceil_div(n2p / 64, 4) : 64);
+                c = ceil_div(std::max<int64_t>(c, 1), 64) * 64;
+                c = std::min<int64_t>(c, ceil_div(n2p / 64, 64) * 64);
+                a.chunks = (int)ceil_div(n2p / 64, c);
+            }
+            const int64_t tiles = (n1p / 128) * a.chunks;   // items of a frame
             // (frames per launch: the item index is 32 bits wide)
             const int64_t launch_frames = std::max<int64_t>(8, std::min<int64_t>(32768, ((int64_t(1) << 30) / tiles) * 8));
+            // (sized for the longest slab: it does not grow, and so is not freed, between the launches of a call)
+            MDX_TRY(h->d_frame_geo.ensure(sizeof(float) * CELL_GEO_FLOATS * size_t(std::min<int64_t>(launch_frames, slab))));
+            a.frame_geo = h->d_frame_geo.as<float>();
+            hipEvent_t ev = h->timer.begin();
             for (int64_t g0 = 0; g0 < nf; g0 += launch_frames) {
                 a.frame0 = (int)g0;
                 a.n_frames = (int)std::min<int64_t>(launch_frames, nf - g0);
@@ -736,6 +755,10 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
                                                        : ceil_div(a.n_frames, 8) * tiles;
                 const unsigned grid = 8u * (unsigned)std::min<int64_t>(blocks_per_xcd - holes / 8, items_per_xcd);
                 MDX_HIP(hipMemsetAsync(h->d_work.ptr, 0, CELL_WORK_BYTES, h->stream));
+                // the frames' constants, once per frame: behind this slab's sort (and the previous launch, which
+                // read the table), in front of the items that load them
+                hipLaunchKernelGGL(tri ? rdf_cell_frame_geo_kernel<true> : rdf_cell_frame_geo_kernel<false>,
+                                   dim3((unsigned)ceil_div(a.n_frames, 256)), dim3(256), 0, h->stream, a);
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, h->stream, a);
             }
             h->timer.end(ev);
@@ -1248,7 +1271,7 @@ int mdx_rdf_destroy(mdx_rdf_t h)
             (void)hipEventDestroy(e);
     for (DeviceBuffer *b : {&h->d_thresh, &h->d_counts, &h->d_total, &h->d_pack1, &h->d_pack2,
                             &h->d_stage1[0], &h->d_stage2[0], &h->d_boxes[0], &h->d_stage1[1],
-                            &h->d_stage2[1], &h->d_boxes[1], &h->d_rawslab[0], &h->d_rawslab[1], &h->d_index[0], &h->d_index[1], &h->d_tri, &h->d_misc, &h->d_stats, &h->d_work, &h->d_pw1,
+                            &h->d_stage2[1], &h->d_boxes[1], &h->d_rawslab[0], &h->d_rawslab[1], &h->d_index[0], &h->d_index[1], &h->d_tri, &h->d_misc, &h->d_stats, &h->d_work, &h->d_frame_geo, &h->d_pw1,
                             &h->d_po1, &h->d_bb1, &h->d_pw2, &h->d_po2, &h->d_bb2, &h->d_bb16_1,
                             &h->d_bb16_2, &h->d_drop[0], &h->d_drop[1], &h->d_drop_box})
         b->recycle();

@@ -11,9 +11,11 @@
 //        bounding box per 64-particle tile.  Everything in LDS, no global atomics.
 //   rdf_cell_sort_small_kernel   the same sort as persistent 256-thread blocks of the pair block's
 //        footprint: sorts slab k + 1 in block slots the pair kernel of slab k leaves free.
-//   rdf_cell_pair_kernel   one 256-thread block per (frame, 128-particle i tile);
-//        each WAVE walks its share of the 64-particle j tiles on its own (no block
-//        barrier in the loop): 64 candidate j tiles are tested per instruction
+//   rdf_cell_frame_geo_kernel   one thread per frame of a pair launch: the frame's constants (box,
+//        error bound, candidate window, cull radius), which every item of the frame loads.
+//   rdf_cell_pair_kernel   persistent 256-thread blocks; each WAVE takes (frame, 128-particle
+//        i tile) items from its XCD's counter and walks an item's 64-particle j tiles on its own
+//        (no block barrier in the item loop): 64 candidate j tiles are tested per instruction
 //        against the i tile's bounding box (minimum-image gap > r_max + error bound
 //        -> culled), survivors are staged into a wave-private LDS slab — already
 //        shifted by the tile pair's periodic image, so the inner loop has NO
@@ -58,8 +60,15 @@ struct CellArgs {
     // the (frame, i tile) items of the XCD's frames
     unsigned *work;
     // 32-bit LDS bins are flushed to the 64-bit replicas before this many j tiles of 2^14 possible adds each
-    // could have gone into one bin since the last flush (2^18; MDX_RDF_LDS_FLUSH_UNITS: test hook)
+    // could have gone into one bin since the last flush (at most 2^17 - 512, see the pair kernel;
+    // MDX_RDF_LDS_FLUSH_UNITS: test hook)
     unsigned flush_units;
+    // an item of the pair kernel: one i tile against every `chunks`-th of its candidate j tiles (`chunks` items to
+    // an i tile, one per residue)
+    int chunks;
+    // the frame constants of this launch, [n_frames][CELL_GEO_FLOATS]: written by rdf_cell_frame_geo_kernel
+    // directly in front of the pair launch, read by every item of the frame
+    float *frame_geo;
     // launches of fewer than eight frames (the function-level drop-in hands over ONE): the items are dealt to the
     // XCDs one by one instead of frame by frame — with a frame per XCD seven eighths of the chip would idle, and
     // the 0.5 MB of a frame's sorted copy read by eight L2s instead of one is nothing
@@ -71,7 +80,12 @@ constexpr size_t CELL_WORK_BYTES = 8 * CELL_WORK_STRIDE * 4;
 
 constexpr int CELL_MAX = 16384;   // cells per frame (64 KiB of LDS counters)
 constexpr int SORT_THREADS = 1024;
-constexpr int CELL_QCAP = 1024;   // surviving j tiles queued per round of the pair kernel
+constexpr int CELL_QCAP = 1024;   // queue entries of a pair block: CELL_QWAVE per wave
+constexpr int CELL_QWAVE = CELL_QCAP / 4;   // candidate j tiles per round of a wave of the pair kernel
+// Frame constants as the pair kernel's s_geo holds them: words 0..7 are s_geo[0..7], words 8..21 are
+// s_geo[26..39] (the last nine, the cell matrix, for triclinic frames only); two words of padding
+constexpr int CELL_GEO_FLOATS = 24;
+__host__ __device__ constexpr int cell_geo_slot(int word) { return word < 8 ? word : word + 18; }
 constexpr int CELL_CHUNK = 1;     // particles per j chunk of the second-level cull (1, 2, 4, 8, 16)
 constexpr int CELL_NCHUNK = 64 / CELL_CHUNK;
 constexpr int CELL_TODO = 128;    // per-wave list of pairs waiting for the exact arithmetic
@@ -887,6 +901,50 @@ __device__ inline void cell_slow_unit(const CellHot &c, const CellArgs &a, const
     }
 }
 
+// The constants of a frame (box, error-bound arithmetic in fp64, candidate window, cull radius): one thread per
+// frame of the launch, on the handle's stream directly in front of the pair kernel — the slab's sort has
+// finished by then, so *maxabs_bits holds at least this slab's maximum.  Every item of a frame used to derive
+// them again (256 items per frame at C2(i), one lane working and 255 waiting); now an item loads them.
+template <bool TRI> __global__ __launch_bounds__(256) void rdf_cell_frame_geo_kernel(CellArgs a)
+{
+    const int f = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (f >= a.n_frames)
+        return;
+    const int frame = a.frame0 + f;
+    float *g = a.frame_geo + int64_t(f) * CELL_GEO_FLOATS;
+    PairCtx<true> ctx;
+    if (TRI) {
+        // error bound of the float32 path: the shifted difference
+        // fl(fl(x_j + t) - x_i) against the contract's (double)(x_j - x_i) + t deviates by less
+        // than 7 * 2^-24 * sum|B| per component; the orthorhombic formula with the pseudo
+        // length 4 sum|B| gives 2^-22 (2 M + 4 sum|B|) >= 2^-20 sum|B|
+        const float *B = a.tri + int64_t(frame) * 9;
+        float sum = 0.f;
+        for (int i = 0; i < 9; ++i) {
+            g[13 + i] = B[i];
+            sum += fabsf(B[i]);
+        }
+        const float pseudo[3] = {4.f * sum, 4.f * sum, 4.f * sum};
+        ctx.init(pseudo, a.maxabs_bits, a.r0, a.r1, a.n_bins);
+    } else {
+        ctx.init(a.boxes + int64_t(frame) * 6, a.maxabs_bits, a.r0, a.r1, a.n_bins);
+    }
+    const float Lmax = fmaxf(ctx.Lf[0], fmaxf(ctx.Lf[1], ctx.Lf[2]));
+    // a tile pair is culled when its box gap exceeds r1 + error bound + slack
+    const float cut = sqrtf(ctx.cand_hi) + 1e-5f * Lmax;
+    for (int k = 0; k < 3; ++k) {
+        g[k] = ctx.Lf[k];
+        g[3 + k] = ctx.invf[k];
+    }
+    g[6] = cut;
+    g[7] = cut * cut;
+    g[8] = ctx.cand_hi;
+    g[9] = ctx.cand_lo;
+    g[10] = ctx.inv_wf;
+    g[11] = -ctx.r0f * ctx.inv_wf - ctx.eta;
+    g[12] = 1.0f - 2.0f * ctx.eta;
+}
+
 // SKIP: the steps of the shifted row loops leave behind their candidate test when no lane holds a candidate
 // (cell_step); chosen per launch by the host (mdx_rdf.hip, CELL_SKIP_MAX_RANGE), ignored by MODE 1.
 template <bool EXCL, bool LOWER, int MODE, bool TRI = false, bool SKIP = true>
@@ -904,6 +962,13 @@ template <bool EXCL, bool LOWER, int MODE, bool TRI = false, bool SKIP = true>
 // re-derived where it is used, behind an opaque copy of the block id (cell_opaque): carried across the hot loops
 // as loop invariants, those values cost 13 scalar registers the kernel does not have (SGPR spills go to VGPR
 // lanes, and with 72 VGPRs the hot loop then spills to scratch).
+//
+// A WAVE owns its items (NOTES.md round 15): each of the four waves pulls (frame, i tile) items from the XCD's counter on
+// its own, sets the item up in its own 48 floats of s_geo, culls the candidate j tiles into its own quarter of the
+// queue (slot = queue length in a scalar register + rank in the ballot: no LDS atomic) and walks that queue with
+// a scalar index.  Nothing in the item loop waits on another wave: the block meets at one barrier after the LDS
+// histogram and the threshold table are set up and at one before they are flushed.  What the waves still share is
+// that histogram and the count of units added to it since its 32-bit bins were last moved out (s_lds_units).
 __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArgs a)
 {
     constexpr bool GH = MODE == 1;
@@ -911,10 +976,11 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
     float4 *sJ = reinterpret_cast<float4 *>(smem_raw);                        // [4 waves][64]
     double *sT = reinterpret_cast<double *>(smem_raw + sizeof(float4) * 256); // [n_bins+1]
     unsigned *sh = reinterpret_cast<unsigned *>(sT + (a.n_bins + 1));         // [n_bins + 1][n_hist replicas]
-    __shared__ unsigned s_exact, s_units, s_general, s_qn, s_qnext, s_next;
-    __shared__ unsigned sQ[CELL_QCAP];
+    __shared__ unsigned s_exact, s_units, s_general, s_lds_units;
+    __shared__ unsigned s_next[4];                    // per wave: the item after the current one
+    __shared__ unsigned sQ[CELL_QCAP];                // per wave: CELL_QWAVE entries
     __shared__ uint2 s_todo[4][CELL_TODO];
-    __shared__ float s_geo[48];
+    __shared__ float s_geo_all[4][48];                // per wave: the geometry of its item
     __shared__ unsigned sQimg[TRI ? CELL_QCAP : 1];   // triclinic: surviving images of a queued tile
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -937,8 +1003,10 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
         s_exact = 0u;
         s_units = 0u;
         s_general = 0u;
-        s_next = atomicAdd(a.work + CELL_WORK_STRIDE * (blockIdx.x & 7u), 1u);
+        s_lds_units = 0u;
     }
+    if (lane == 0)
+        s_next[wave] = atomicAdd(a.work + CELL_WORK_STRIDE * (blockIdx.x & 7u), 1u);
     __syncthreads();
 
     unsigned long long *out = a.counts + int64_t(blockIdx.x % unsigned(a.n_rep)) * a.n_bins;
@@ -953,18 +1021,23 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
     float4 *sJw = sJ + wave * 64;
     CellWave wv{s_todo[wave], 0u, 0u, 0u};
     unsigned n_units = 0, n_general = 0;
-    // upper bound of what any 32-bit LDS bin may hold, in units of 2^14 adds (= 128 i x 64 j x weight 2, one
-    // j tile of one item); at 2^18 units the bins are flushed to the 64-bit replicas
-    unsigned lds_units = 0;
+    float *s_geo = s_geo_all[wave];
+    unsigned *sQw = sQ + wave * CELL_QWAVE;
+    unsigned *sQimgw = sQimg + (TRI ? wave * CELL_QWAVE : 0);
     for (;;) {
     // the item: frame = 8 (item / tiles) + xcd, i tile = item % tiles, over the frames of this launch with
     // frame % 8 == xcd
-    const unsigned item = __builtin_amdgcn_readfirstlane(s_next);
-    int frame_l, I;
+    // (s_next[wave] is written by this wave's lane 0 alone: LDS operations of one wave execute in order)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const unsigned item = __builtin_amdgcn_readfirstlane(s_next[wave]);
+    // An item is one CHUNK of an i tile's candidate j tiles (every A->chunks-th of them; the host's choice): with
+    // all tiles of an i tile to one wave a launch ended in the few longest of them — 9 ms at range L/2, four times
+    // what a block took over the same tile — and a call of one frame took 1.8 times as long.
+    int frame_l, I, chunk;
     {
         const unsigned xcd = cell_opaque(blockIdx.x) & 7u;
         const auto *A = cell_args();
-        const unsigned tiles = unsigned(A->n1p) >> 7;                       // 128-particle i tiles of a frame
+        const unsigned tiles = (unsigned(A->n1p) >> 7) * unsigned(A->chunks);   // items of a frame
         if (A->spread) {
             const unsigned g = item * 8u + xcd;                             // item of the launch, dealt one by one
             if (g >= unsigned(A->n_frames) * tiles)
@@ -982,9 +1055,15 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
             frame_l = int(fq * 8u + xcd);
             I = int(item - fq * tiles);
         }
-        frame_l += A->frame0;
+        // (I: the item's place in its frame so far; i tile and chunk from it)
+        chunk = 0;
+        if (A->chunks != 1) {   // (small systems: one chunk, and items so short that a second division shows)
+            const unsigned it = __builtin_amdgcn_readfirstlane(unsigned(I) / unsigned(A->chunks));
+            chunk = I - int(it * unsigned(A->chunks));
+            I = int(it);
+        }
     }
-    const int frame = frame_l;
+    const int frame = frame_l + cell_args()->frame0;   // frame_l: the frame's place in this launch
     // this frame's original coordinates, for the (cold) exact passes: formed where they are used
 #define MDX_PO1F()                                                                                             \
     CellOrig { a.po1 ? a.po1 + int64_t(cell_opaque(frame)) * a.n1p : nullptr, a.pw1 + int64_t(cell_opaque(frame)) * a.n1p, \
@@ -1000,48 +1079,37 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
         BB16 = A->bb16_2 + int64_t(frame) * t64_2 * 2 * CELL_NCHUNK;
     }
     {
-    // Per-item geometry and the frame's constants are derived by one thread (fp64 error-bound
-    // arithmetic included) and parked in LDS; the hot loop keeps only five floats of them, in SGPRs.
+    // The frame's constants come from the launch's table (rdf_cell_frame_geo_kernel: one load by the first
+    // lanes of the wave), the item's geometry is derived by lane 0; both are parked in the wave's own part of
+    // LDS, and the hot loop keeps only five floats of them, in SGPRs.
     //   s_geo: [0..2] L, [3..5] 1/L (float32), [6] cut, [7] cut^2,
     //          [8..10] cI, [11..13] hI, [14..19] cH[2][3], [20..25] hH[2][3],
     //          [26] cand_hi, [27] cand_lo, [28] inv_w, [29] -r0/w - eta, [30] 1 - 2 eta
     //   triclinic: [31..39] cell matrix B (rows a, b, c); L and 1/L are unused
-    // (the previous item's last barrier has passed: nobody reads s_geo or the queue any more)
-    if (tid == 0) {
+    // (s_geo and the queue are this wave's: its reads for the previous item are behind it)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    // the next item is requested now and parked in s_next[wave] behind the first round's cull, whose loads are
+    // waited for anyway
+    unsigned next_item = 0u;
+    if (lane == 0)
+        next_item = atomicAdd(cell_args()->work + CELL_WORK_STRIDE * (cell_opaque(blockIdx.x) & 7u), 1u);
+    // the item's candidate tiles: every `chunks`-th from Jfirst on, Jend of them (positions 0 .. Jend - 1; a self
+    // histogram counts from the diagonal).  The tiles an i tile meets lie close together in the sorted order: dealt
+    // as contiguous ranges they fell to one or two of its items; dealt by residue every item gets its share
+    const int Jfirst = (a.self ? 2 * I : 0) + chunk;
+    constexpr int Jbeg = 0;
+    int Jend = t64_2 - Jfirst;
+    if (cell_args()->chunks != 1)
+        Jend = int(__builtin_amdgcn_readfirstlane(unsigned(max(Jend, 0) + cell_args()->chunks - 1) / unsigned(cell_args()->chunks)));
+    if (Jfirst >= t64_2) {
+        if (lane == 0)
+            s_next[wave] = next_item;
+        continue;
+    }
+    if (lane < (TRI ? 22 : 13))
+        s_geo[cell_geo_slot(lane)] = cell_args()->frame_geo[int64_t(frame_l) * CELL_GEO_FLOATS + lane];
+    if (lane == 0) {
         const auto *A = cell_args();
-        {
-            PairCtx<true> ctx;
-            if (TRI) {
-                // error bound of the float32 path: the shifted difference
-                // fl(fl(x_j + t) - x_i) against the contract's (double)(x_j - x_i) + t deviates by less
-                // than 7 * 2^-24 * sum|B| per component; the orthorhombic formula with the pseudo
-                // length 4 sum|B| gives 2^-22 (2 M + 4 sum|B|) >= 2^-20 sum|B|
-                const float *B = A->tri + int64_t(frame) * 9;
-                float sum = 0.f;
-                for (int i = 0; i < 9; ++i) {
-                    s_geo[31 + i] = B[i];
-                    sum += fabsf(B[i]);
-                }
-                const float pseudo[3] = {4.f * sum, 4.f * sum, 4.f * sum};
-                ctx.init(pseudo, A->maxabs_bits, A->r0, A->r1, A->n_bins);
-            } else {
-                ctx.init(A->boxes + int64_t(frame) * 6, A->maxabs_bits, A->r0, A->r1, A->n_bins);
-            }
-            const float Lmax = fmaxf(ctx.Lf[0], fmaxf(ctx.Lf[1], ctx.Lf[2]));
-            // a tile pair is culled when its box gap exceeds r1 + error bound + slack
-            const float cut = sqrtf(ctx.cand_hi) + 1e-5f * Lmax;
-            for (int k = 0; k < 3; ++k) {
-                s_geo[k] = ctx.Lf[k];
-                s_geo[3 + k] = ctx.invf[k];
-            }
-            s_geo[6] = cut;
-            s_geo[7] = cut * cut;
-            s_geo[26] = ctx.cand_hi;
-            s_geo[27] = ctx.cand_lo;
-            s_geo[28] = ctx.inv_wf;
-            s_geo[29] = -ctx.r0f * ctx.inv_wf - ctx.eta;
-            s_geo[30] = 1.0f - 2.0f * ctx.eta;
-        }
         const float4 *BB1 = A->bb1 + int64_t(frame) * (A->n1p / 64) * 2 + int64_t(I) * 4;
         const float4 l0 = BB1[0], h0 = BB1[1], l1 = BB1[2], h1 = BB1[3];
         const float lo0[3] = {l0.x, l0.y, l0.z}, hi0[3] = {h0.x, h0.y, h0.z};
@@ -1055,8 +1123,6 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
             s_geo[20 + k] = 0.5f * (hi0[k] - lo0[k]);
             s_geo[23 + k] = 0.5f * (hi1[k] - lo1[k]);
         }
-        s_qn = 0u;        // the queue of the item's first round
-        s_qnext = 0u;
     }
     float4 p0, p1;
     {
@@ -1072,7 +1138,10 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
     }
     const unsigned i_base0 = unsigned(I) * 128u;   // wave-uniform; + lane = this lane's i index
     const unsigned i_idx0 = i_base0 + unsigned(lane);
-    __syncthreads();
+    // what lanes 0..21 wrote is read by all: ordered with the wavefront fences the slab uses
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     {
         hot.cand_hi = cell_uniform(s_geo[26]);
         hot.cand_lo = cell_uniform(s_geo[27]);
@@ -1087,43 +1156,50 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
         }
         hot.tri = TRI ? s_geo + 31 : nullptr;
     }
-    const int Jbeg = a.self ? 2 * I : 0;
-    // Rounds of up to CELL_QCAP candidate j tiles: all four waves test candidates and append
-    // the survivors to one LDS queue, then pull tiles from it one at a time (LDS atomic), so
-    // the waves of a block stay evenly loaded whatever the spatial distribution of survivors.
-    for (int round0 = Jbeg; round0 < t64_2; round0 += CELL_QCAP) {
-        const int round1 = min(t64_2, round0 + CELL_QCAP);
-        // 32-bit LDS bins: one round adds at most (128 i) x (64 j) x weight 2 = 2^14 per j tile to a bin.  Before
-        // a round could take a bin past 2^32 the bins are flushed to the 64-bit replicas, so no count can wrap
-        // however many items a block serves and however large the second set is (it could,
-        // silently, from ~1.6e7 particles with coarse bins).  Uniform decision; the adds of earlier rounds are
-        // behind a barrier, the next adds come after the barrier that closes the cull below.
-        if (!GH && lds_units + unsigned(round1 - round0) >= cell_args()->flush_units) {
-            for (int b = tid; b < a.n_bins; b += 256) {
-                unsigned long long sum = 0;
-                for (int h = 0; h < a.n_hist; ++h) {
-                    sum += sh[b * a.n_hist + h];
-                    sh[b * a.n_hist + h] = 0u;
+    // Rounds of up to CELL_QWAVE candidate j tiles: the wave tests 64 candidates per pass and appends the
+    // survivors to its own queue, then walks the queue.
+    for (int round0 = Jbeg; round0 < Jend; round0 += CELL_QWAVE) {
+        const int round1 = min(Jend, round0 + CELL_QWAVE);
+        // 32-bit LDS bins: one round adds at most (128 i) x (64 j) x weight 2 = 2^14 per j tile ("unit") to a
+        // bin.  Before the rounds could take a bin past 2^32 the bins are moved to the 64-bit replicas, so no
+        // count can wrap however many items a block serves and however large the second set is (it
+        // could, silently, from ~1.6e7 particles with coarse bins).  No barrier: a wave ANNOUNCES a round's units
+        // on s_lds_units (which only ever grows, modulo 2^32) before it adds anything of that round, and the wave
+        // whose announcement takes the sum across a multiple of F = flush_units moves the bins out with returning
+        // exchanges; an add of another wave lands before or after the exchange of its bin and is counted once
+        // either way.  (When the sum wraps, the quotients differ too: one flush more, which is harmless.)
+        // What a bin can collect between two exchanges of it, in units: the rounds the four waves had announced
+        // up to the first trigger and not finished (the triggering round included), at most 4 x CELL_QWAVE = 1024;
+        // the rounds announced between the two triggers, fewer than F; and the rounds the other waves announce
+        // while the second flush is on its way to the bin, fewer than F again as long as a flush (one exchange
+        // per replica and bin: at most 256 per lane) ends before another F units are announced — every
+        // announcement of at most 256 units stands behind the passes of a cull over global memory, so F / 256
+        // = 511 of them take some hundred times as long.  1024 + 2 F <= 2^18 units = 2^32 adds: the host caps
+        // F at 2^17 - 512.
+        if (!GH) {
+            const unsigned units = unsigned(round1 - round0);
+            unsigned before = 0u;
+            if (lane == 0)
+                before = atomicAdd(&s_lds_units, units);
+            before = __builtin_amdgcn_readfirstlane(before);
+            const unsigned F = cell_args()->flush_units;
+            if (before / F != (before + units) / F) {
+                for (int b = lane; b < a.n_bins; b += 64) {
+                    unsigned long long sum = 0;
+                    for (int h = 0; h < a.n_hist; ++h)
+                        sum += atomicExch(&sh[b * a.n_hist + h], 0u);
+                    if (sum)
+                        atomicAdd(out + b, sum);
                 }
-                if (sum)
-                    atomicAdd(out + b, sum);
             }
-            lds_units = 0u;
         }
-        lds_units += unsigned(round1 - round0);
-        if (round0 != Jbeg) {   // (the first round's queue was reset with the item's geometry)
-            if (tid == 0) {
-                s_qn = 0u;
-                s_qnext = 0u;
-            }
-            __syncthreads();
-        }
-        for (int Jb = round0; Jb < round1; Jb += 256) {
-            const int J = Jb + tid;
+        unsigned qn = 0u;   // the queue's length: wave-uniform, in a scalar register
+        for (int Jb = round0; Jb < round1; Jb += 64) {
+            const int J = Jfirst + (Jb + lane) * cell_args()->chunks;   // (Jb + lane: the tile's position in the item)
             float g2 = __int_as_float(0x7f800000);
             unsigned code = 0u;
             unsigned img_mask = 0u;
-            if (J < round1) {
+            if (Jb + lane < round1) {
                 const float4 lo = BB2[2 * J], hi = BB2[2 * J + 1];
                 const float cJ[3] = {0.5f * (lo.x + hi.x), 0.5f * (lo.y + hi.y), 0.5f * (lo.z + hi.z)};
                 const float hJ[3] = {0.5f * (hi.x - lo.x), 0.5f * (hi.y - lo.y), 0.5f * (hi.z - lo.z)};
@@ -1175,41 +1251,32 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
             }
             const bool keep = g2 <= s_geo[7];
             const unsigned long long mask = __ballot(keep);
-            if (mask) {
-                unsigned base = 0;
-                if (lane == 0)
-                    base = atomicAdd(&s_qn, (unsigned)__popcll(mask));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (keep) {
-                    const unsigned slot = base + __popcll(mask & ((1ull << lane) - 1ull));
-                    sQ[slot] = code;
-                    if (TRI)
-                        sQimg[slot] = img_mask;
-                }
+            if (keep) {
+                // slot = queue length + rank among the surviving lanes
+                const unsigned slot = __builtin_amdgcn_mbcnt_hi(
+                    (unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, qn));
+                sQw[slot] = code;
+                if (TRI)
+                    sQimgw[slot] = img_mask;
             }
+            qn += (unsigned)__popcll(mask);
         }
-        __syncthreads();
-        // the next item is requested while the other waves already pull tiles (the queue is dynamic: they take
-        // what this wave misses while it waits for the counter); every wave has read s_next before the item's
-        // first barrier, the next read comes after the round's last one
-        if (tid == 0 && round0 == Jbeg)
-            s_next = atomicAdd(cell_args()->work + CELL_WORK_STRIDE * (cell_opaque(blockIdx.x) & 7u), 1u);
-        const unsigned nq = s_qn;
-        while (true) {
-            unsigned e = 0;
-            if (lane == 0)
-                e = atomicAdd(&s_qnext, 1u);
-            e = __builtin_amdgcn_readfirstlane(e);
-            if (e >= nq)
-                break;
+        // the next item's number has arrived with the cull's loads (requested ahead of them)
+        if (lane == 0 && round0 == Jbeg)
+            s_next[wave] = next_item;
+        // the queue is read by all lanes (broadcast): the wave's own LDS writes are ordered before
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (unsigned e = 0; e < qn; ++e) {
             // (wave-uniform, but read from LDS: pinned into a scalar register, or the tile index and every j index
             // derived from it live in vector registers and cost a VALU instruction per turn of the loops below)
-            const unsigned code = __builtin_amdgcn_readfirstlane(sQ[e]);
+            const unsigned code = __builtin_amdgcn_readfirstlane(sQw[e]);
             const int Jt = int(code & 0x3fffffu);
             const float4 pj_raw = PW2[int64_t(Jt) * 64 + lane];
             // orthorhombic: one pass with the tile pair's image; triclinic: one pass per
             // surviving image of the tile
-            for (unsigned imgs = TRI ? sQimg[e] : 1u; imgs; imgs &= imgs - 1u) {
+            for (unsigned imgs = TRI ? sQimgw[e] : 1u; imgs; imgs &= imgs - 1u) {
             int gen = 0;
             float sx, sy, sz;
             if (TRI) {
@@ -1469,13 +1536,14 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
             }
             }   // images
         }
-        // the undecided pairs of an item are evaluated before its last barrier: their indices are the item's
+        // the undecided pairs of an item are evaluated before the wave leaves it: their indices are the item's
         // frame's, and the exact arithmetic reads the frame's constants
-        if (round0 + CELL_QCAP >= t64_2 && wv.n_todo) {
+        if (round0 + CELL_QWAVE >= Jend && wv.n_todo) {
             if (GH) cell_flush(hot, a, thr, hg, wv, MDX_PO1F(), MDX_PO2());
             else cell_flush(hot, a, thr, hl, wv, MDX_PO1F(), MDX_PO2());
         }
-        __syncthreads();   // the queue, s_geo and s_next are rewritten after this
+        // (the queue and s_geo are rewritten after this, by this wave alone)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     }
     }
 #undef MDX_PO1F

@@ -159,3 +159,66 @@ def step_model(units=40):
 
 
 step_model()
+
+
+# ---------------------------------------------------------------------------------------------
+# Fourth model: how evenly the four waves of a block end an item.  One uniform C2 frame in the sort kernel's
+# column / layer order; items are 128-particle i tiles I with the self schedule J >= 2 I over the 64-particle
+# j tiles; a tile is visited when its box comes within R of the item's 128-particle box, and a visit runs one
+# trip per (row, 64-particle half) whose row comes within R of the half's box.  Four waves take the visits
+# greedily in queue (J) order; `visit_cost` trip-equivalents are charged per visit for the pop and the staging.
+# Idle share at the closing barrier = 1 - work / (4 x length of the longest wave).
+def item_model():
+    rng = np.random.default_rng(3)
+    N, L, R = 32768, 68.94, 15.0
+    pos = rng.random((N, 3)) * L
+    a = (64 * L**3 / N) ** (1 / 3)
+    nc0 = nc1 = max(int(round(L / a)), 1); nc2 = max(int(round(16 * L / a)), 1)
+    c = np.minimum((pos / L * [nc0, nc1, nc2]).astype(int), [nc0 - 1, nc1 - 1, nc2 - 1])
+    cx, cy, cz = c[:, 0], c[:, 1].copy(), c[:, 2].copy()
+    cy = np.where(cx & 1, nc1 - 1 - cy, cy); col = cx * nc1 + cy
+    cz = np.where(col & 1, nc2 - 1 - cz, cz)
+    P = pos[np.argsort(col * nc2 + cz, kind="stable")]
+    T = P.reshape(N // 64, 64, 3)
+    tlo, thi = T.min(1), T.max(1)
+
+    def box_gap2(lo, hi, cen, half):
+        """squared minimum-image gap between the box (lo, hi) and boxes / points (cen, half)"""
+        d = cen - 0.5 * (lo + hi); d -= L * np.rint(d / L)
+        g = np.maximum(0.0, np.abs(d) - 0.5 * (hi - lo) - half)
+        return (g * g).sum(-1)
+
+    visits_per_item, trips_of_visits = [], []
+    for I in range(N // 128):
+        i0, i1 = T[2 * I], T[2 * I + 1]
+        lo, hi = np.minimum(tlo[2 * I], tlo[2 * I + 1]), np.maximum(thi[2 * I], thi[2 * I + 1])
+        J = np.arange(2 * I, N // 64)
+        J = J[box_gap2(lo, hi, 0.5 * (tlo[J] + thi[J]), 0.5 * (thi[J] - tlo[J])) <= R * R]
+        rows = T[J]                                                        # [visits, 64, 3]
+        t = (box_gap2(i0.min(0), i0.max(0), rows, 0.0) <= R * R).sum(1) \
+            + (box_gap2(i1.min(0), i1.max(0), rows, 0.0) <= R * R).sum(1)
+        visits_per_item.append(len(J))
+        trips_of_visits.append(t)
+    allt = np.concatenate(trips_of_visits)
+    print("--- the four waves of a block around an item (one frame, 256 items)")
+    print(f"trips per frame {allt.sum():.4g}; visits per item {np.mean(visits_per_item):.1f} "
+          f"(max {max(visits_per_item)}); trips per visit {allt.mean():.1f}")
+    print(f"visits with no trip: {(allt == 0).mean():.3f}; with at most 8 trips: {(allt <= 8).mean():.3f}, "
+          f"holding {allt[allt <= 8].sum() / allt.sum():.3f} of the trips")
+    for visit_cost in (0, 6):
+        length, work = [], 0
+        for t in trips_of_visits:
+            waves = np.zeros(4)
+            for v in t + visit_cost:                                       # greedy: the wave that is free first
+                waves[waves.argmin()] += v
+            length.append(waves.max())
+            work += waves.sum()
+        length = np.array(length)
+        print(f"{visit_cost} trip-equivalents per visit: item length {length.mean():.0f} trip units (max {length.max():.0f}), "
+              f"idle share at the closing barrier {1.0 - work / (4.0 * length.sum()):.3f}")
+    own = np.array([t.sum() for t in trips_of_visits])
+    print(f"an item owned by one wave: {own.mean():.0f} trip units (max {own.max()}); the last 32 items dealt of a "
+          f"frame {own[-32:].mean():.0f}")
+
+
+item_model()
