@@ -540,6 +540,13 @@ int mdx_prof_enable_timing(mdx_prof_t h, int on);
  * bin straight into global memory, -1 restores the engine's own choice.  The counts do not depend on it; it exists
  * for measurements and tests.  Only before the first frame. */
 int mdx_prof_set_replicas(mdx_prof_t h, int replicas);
+/* Host-only plan queries (no device is touched), for tests and tools that must know where a call is cut.
+ * mdx_feed_slab_frames: the frames a host-memory or trajectory-file call of n_frames frames stages at a time, for every
+ * per-frame engine (rows: the caller's n on the host route, the file's n_atoms on the file route).
+ * mdx_X_slab_frames: the frames an engine with n_points points, configured as the flags say, takes per kernel launch
+ * inside one call; a call of more frames is cut into such slabs, whose results do not depend on the cut. */
+int mdx_feed_slab_frames(int64_t n_frames, int64_t rows, int64_t *slab);
+int mdx_prof_slab_frames(int64_t n_points, int grouped, int recenter, int64_t *slab);
 
 /* ---- radii of gyration of polymer chains (reference analysis/polymer.py Gyradius, algorithm/molecule.py
  * radius_of_gyration) ------------------------------------------------------------------------------------------------
@@ -583,6 +590,8 @@ int mdx_gyr_synchronize(mdx_gyr_t h);
 int mdx_gyr_result(mdx_gyr_t h, double *out);
 int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_gyr_enable_timing(mdx_gyr_t h, int on);
+/* Host-only (mdx_prof_slab_frames): n_chains chains in all, of n_points points in all. */
+int mdx_gyr_slab_frames(int64_t n_chains, int64_t n_points, int grouped, int unwrap, int64_t *slab);
 
 /* ---- per-chain linear projections: Rouse mode amplitudes (analysis/polymer.py RouseModes; no counterpart in the
  * reference) ---------------------------------------------------------------------------------------------------------
@@ -624,6 +633,8 @@ int mdx_rouse_result(mdx_rouse_t h, double *out);
 int mdx_rouse_device_result(mdx_rouse_t h, const double **d_ptr, int64_t *n_frames, int64_t *n_series);
 int mdx_rouse_stats(mdx_rouse_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_rouse_enable_timing(mdx_rouse_t h, int on);
+/* Host-only (mdx_prof_slab_frames). */
+int mdx_rouse_slab_frames(int64_t n_points, int grouped, int unwrap, int64_t *slab);
 
 /* ---- chain internal distances and bond-orientation correlations (analysis/polymer.py InternalDistances; no
  * counterpart in the reference) --------------------------------------------------------------------------------------
@@ -665,6 +676,10 @@ int mdx_msid_synchronize(mdx_msid_t h);
 int mdx_msid_result(mdx_msid_t h, double *out);
 int mdx_msid_stats(mdx_msid_t h, int64_t *launches, double *kernel_ms, int64_t *frames);
 int mdx_msid_enable_timing(mdx_msid_t h, int on);
+/* Host-only (mdx_prof_slab_frames): the chain layout of mdx_msid_create, from which the per-unit partial sums of a
+ * frame follow; whole and unwrap exclude each other. */
+int mdx_msid_slab_frames(int n_groups, const int64_t *n_chains, const int64_t *n_monomers, int grouped, int whole,
+                         int unwrap, int64_t *slab);
 
 /* ---- instantaneous dipole moments (reference analysis/electrostatics.py DipoleMoment) ------------------------------
  * Rows arrive in the order of the concatenated groups: group g holds n_points[g] consecutive points; charges float64,

@@ -524,6 +524,24 @@ class IsfEngine(_Engine):
         return {"launches": n.value, "kernel_ms": ms.value, "frames": fr.value}
 
 
+def feed_slab_frames(n_frames, rows):
+    """``mdx_feed_slab_frames``: the frames a per-frame engine stages at a time when ``accumulate`` (``rows``: the
+    rows of a frame) or ``accumulate_traj`` (``rows``: the file's atoms) is given ``n_frames`` frames.  Needs no
+    device."""
+    out = c_int64()
+    check(lib().mdx_feed_slab_frames(int(n_frames), int(rows), byref(out)))
+    return out.value
+
+
+def _chain_layout(n_chains, n_monomers):
+    """``(n_chains, n_monomers)`` as int64 arrays of one entry per group."""
+    c = np.ascontiguousarray(np.atleast_1d(n_chains), dtype=np.int64)
+    m = np.ascontiguousarray(np.atleast_1d(n_monomers), dtype=np.int64)
+    if c.ndim != 1 or c.shape != m.shape or len(c) == 0:
+        raise ValueError("n_chains and n_monomers must hold one entry per group.")
+    return c, m
+
+
 class _FrameEngine(_Engine):
     """What the per-frame engines share: the three routes frames take (host memory, HBM, a trajectory file),
     ``synchronize``, ``reset``, ``stats`` and the ``timing=`` switch.  A subclass names the prefix of its symbols and
@@ -637,6 +655,14 @@ class ProfileEngine(_FrameEngine):
         if replicas is not None:
             self.set_replicas(replicas)
 
+    @staticmethod
+    def slab_frames(n_points, *, grouped=False, recenter=False):
+        """``mdx_prof_slab_frames``: the frames per kernel launch inside one call of an engine whose groups hold
+        ``n_points`` points, with a grouping and / or recentring set.  Needs no device."""
+        out = c_int64()
+        check(lib().mdx_prof_slab_frames(int(n_points), int(bool(grouped)), int(bool(recenter)), byref(out)))
+        return out.value
+
     def set_replicas(self, replicas):
         """Caps the LDS copies of the counters (8, 4, 2, 1), 0: global atomics, -1: the engine's own choice.
         For measurements and tests: the counts do not depend on it."""
@@ -698,6 +724,16 @@ class GyrationEngine(_FrameEngine):
                                    _ptr(m)))
         self._adopt(h, dev, timing)
 
+    @staticmethod
+    def slab_frames(n_chains, n_monomers, *, grouped=False, unwrap=False):
+        """``mdx_gyr_slab_frames``: the frames per kernel launch inside one call of an engine built from these chain
+        counts, with a grouping and / or the unwrap set.  Needs no device."""
+        c, m = _chain_layout(n_chains, n_monomers)
+        out = c_int64()
+        check(lib().mdx_gyr_slab_frames(int(c.sum()), int((c * m).sum()), int(bool(grouped)), int(bool(unwrap)),
+                                        byref(out)))
+        return out.value
+
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
         groups — whose float64 centres of mass are the points; ``offsets=None`` removes the grouping."""
@@ -745,6 +781,15 @@ class ChainProjectionEngine(_FrameEngine):
         check(lib().mdx_rouse_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers),
                                      self.n_rows, _ptr(flat)))
         self._adopt(h, dev, timing)
+
+    @staticmethod
+    def slab_frames(n_chains, n_monomers, *, grouped=False, unwrap=False):
+        """``mdx_rouse_slab_frames``: the frames per kernel launch inside one call of an engine built from these
+        chain counts, with a grouping and / or the unwrap set.  Needs no device."""
+        c, m = _chain_layout(n_chains, n_monomers)
+        out = c_int64()
+        check(lib().mdx_rouse_slab_frames(int((c * m).sum()), int(bool(grouped)), int(bool(unwrap)), byref(out)))
+        return out.value
 
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the
@@ -794,6 +839,16 @@ class InternalDistanceEngine(_FrameEngine):
         h = c_void_p()
         check(lib().mdx_msid_create(byref(h), dev, self.n_groups, _ptr(self.n_chains), _ptr(self.n_monomers)))
         self._adopt(h, dev, timing)
+
+    @staticmethod
+    def slab_frames(n_chains, n_monomers, *, grouped=False, whole=False, unwrap=False):
+        """``mdx_msid_slab_frames``: the frames per kernel launch inside one call of an engine built from these chain
+        counts, with a grouping, ``whole`` or the unwrap set.  Needs no device."""
+        c, m = _chain_layout(n_chains, n_monomers)
+        out = c_int64()
+        check(lib().mdx_msid_slab_frames(len(c), _ptr(c), _ptr(m), int(bool(grouped)), int(bool(whole)),
+                                         int(bool(unwrap)), byref(out)))
+        return out.value
 
     def set_grouping(self, offsets, masses):
         """Incoming rows become particles of monomers ``[offsets[m], offsets[m+1])`` — one per point of the

@@ -165,6 +165,8 @@ _SIGNATURES = {
     "mdx_prof_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int)]),
     "mdx_prof_enable_timing": (c_int, [_vp, c_int]),
     "mdx_prof_set_replicas": (c_int, [_vp, c_int]),
+    "mdx_feed_slab_frames": (c_int, [c_int64, c_int64, _vp]),
+    "mdx_prof_slab_frames": (c_int, [c_int64, c_int, c_int, _vp]),
     # radii of gyration
     "mdx_gyr_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp, _vp]),
     "mdx_gyr_destroy": (c_int, [_vp]),
@@ -178,6 +180,7 @@ _SIGNATURES = {
     "mdx_gyr_result": (c_int, [_vp, _vp]),
     "mdx_gyr_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_gyr_enable_timing": (c_int, [_vp, c_int]),
+    "mdx_gyr_slab_frames": (c_int, [c_int64, c_int64, c_int, c_int, _vp]),
     # per-chain linear projections (Rouse mode amplitudes)
     "mdx_rouse_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp, c_int64, _vp]),
     "mdx_rouse_destroy": (c_int, [_vp]),
@@ -193,6 +196,7 @@ _SIGNATURES = {
     "mdx_rouse_device_result": (c_int, [_vp, POINTER(_vp), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_rouse_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_rouse_enable_timing": (c_int, [_vp, c_int]),
+    "mdx_rouse_slab_frames": (c_int, [c_int64, c_int, c_int, _vp]),
     # chain internal distances and bond-orientation correlations
     "mdx_msid_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
     "mdx_msid_destroy": (c_int, [_vp]),
@@ -208,6 +212,7 @@ _SIGNATURES = {
     "mdx_msid_result": (c_int, [_vp, _vp]),
     "mdx_msid_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
     "mdx_msid_enable_timing": (c_int, [_vp, c_int]),
+    "mdx_msid_slab_frames": (c_int, [c_int, _vp, _vp, c_int, c_int, c_int, _vp]),
     # dipole moments
     "mdx_dip_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
     "mdx_dip_destroy": (c_int, [_vp]),

@@ -30,6 +30,13 @@ namespace {
 constexpr int64_t GYR_SLAB_FRAMES = 32768;                // frames per launch (grid y)
 constexpr int64_t GYR_SCRATCH_BYTES = int64_t(256) << 20; // centres / image counts / per-chain values of one slab
 
+// frames per slab of gyr_accumulate_rows: what its scratch of one frame allows; also what mdx_gyr_slab_frames reports
+int64_t gyr_slab_frames(int64_t n_chains, int64_t n_points, bool grouped, bool unwrap)
+{
+    const int64_t scratch = 32 * n_chains + (grouped ? 24 * n_points : 0) + (unwrap ? 12 * n_points : 0);
+    return std::min(GYR_SLAB_FRAMES, std::max<int64_t>(1, GYR_SCRATCH_BYTES / scratch));
+}
+
 }  // namespace
 
 struct mdx_gyr : FrameEngine {
@@ -92,8 +99,7 @@ static int gyr_accumulate_rows(mdx_gyr *h, const float *d_pos, int64_t src_rows,
         MDX_HIP(hipMemcpyAsync(h->d_prev.ptr, h->start.data(), size_t(24) * n, hipMemcpyHostToDevice, h->stream));
         MDX_HIP(hipMemsetAsync(h->d_image.ptr, 0, size_t(12) * n, h->stream));
     }
-    const int64_t scratch = 32 * h->n_chains + (grouped ? 24 * n : 0) + (h->unwrap ? 12 * n : 0);
-    const int64_t slab = std::min(GYR_SLAB_FRAMES, std::max<int64_t>(1, GYR_SCRATCH_BYTES / scratch));
+    const int64_t slab = gyr_slab_frames(h->n_chains, n, grouped, h->unwrap);
     hipEvent_t ev = h->timer.begin();
     for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
         const int64_t nf = std::min(slab, n_frames - f0);
@@ -202,6 +208,16 @@ int mdx_gyr_create(mdx_gyr_t *out, int dev, int n_groups, const int64_t *n_chain
         return rc;
     }
     *out = h;
+    return MDX_OK;
+}
+
+int mdx_gyr_slab_frames(int64_t n_chains, int64_t n_points, int grouped, int unwrap, int64_t *slab)
+{
+    MDX_REQUIRE(slab, "NULL argument");
+    const int64_t limit = (int64_t(1) << 31) / 3;
+    MDX_REQUIRE(n_chains >= 1 && n_points >= n_chains && n_points < limit,
+                "the groups must hold at least one point per chain and fewer than 2^31 / 3 points");
+    *slab = gyr_slab_frames(n_chains, n_points, grouped != 0, unwrap != 0);
     return MDX_OK;
 }
 

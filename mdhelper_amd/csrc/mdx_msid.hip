@@ -30,6 +30,33 @@ namespace {
 constexpr int64_t MSID_SLAB_FRAMES = 32768;                // frames per launch (grid y)
 constexpr int64_t MSID_SCRATCH_BYTES = int64_t(256) << 20; // partial sums / centres or whole points / image counts
 
+// frames per slab of msid_accumulate_rows: what its scratch of one frame allows; also what mdx_msid_slab_frames
+// reports
+int64_t msid_slab_frames(int64_t n_partial, int64_t n_points, bool grouped, bool whole, bool unwrap)
+{
+    const int64_t scratch = 8 * n_partial + (grouped || whole ? 24 * n_points : 0) + (unwrap ? 12 * n_points : 0);
+    return std::min(MSID_SLAB_FRAMES, std::max<int64_t>(1, MSID_SCRATCH_BYTES / scratch));
+}
+
+// the checks of mdx_msid_create on the chain layout; *n_points: the points of all groups, *n_partial: the partial
+// sums the units of a frame leave (2 (N - 1) per unit of msid_chains_per_unit(N) chains)
+int msid_layout(int n_groups, const int64_t *n_chains, const int64_t *n_monomers, int64_t *n_points,
+                int64_t *n_partial)
+{
+    MDX_REQUIRE(n_groups >= 1 && n_groups <= 4096, "n_groups out of range");
+    const int64_t limit = (int64_t(1) << 31) / 3;
+    *n_points = *n_partial = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        MDX_REQUIRE(n_chains[g] >= 1 && n_chains[g] < limit, "group %d: n_chains must be at least 1", g);
+        MDX_REQUIRE(n_monomers[g] >= 2 && n_monomers[g] < limit, "group %d: n_monomers must be at least 2", g);
+        MDX_REQUIRE(n_chains[g] * n_monomers[g] < limit - *n_points,
+                    "the groups must hold fewer than 2^31 / 3 points");
+        *n_points += n_chains[g] * n_monomers[g];
+        *n_partial += ceil_div(n_chains[g], msid_chains_per_unit(n_monomers[g])) * 2 * (n_monomers[g] - 1);
+    }
+    return MDX_OK;
+}
+
 }  // namespace
 
 struct mdx_msid : FrameEngine {
@@ -104,8 +131,7 @@ static int msid_accumulate_rows(mdx_msid *h, const float *d_pos, int64_t src_row
         MDX_HIP(hipMemcpyAsync(h->d_prev.ptr, h->start.data(), size_t(24) * n, hipMemcpyHostToDevice, h->stream));
         MDX_HIP(hipMemsetAsync(h->d_image.ptr, 0, size_t(12) * n, h->stream));
     }
-    const int64_t scratch = 8 * h->n_partial + (grouped || h->whole ? 24 * n : 0) + (h->unwrap ? 12 * n : 0);
-    const int64_t slab = std::min(MSID_SLAB_FRAMES, std::max<int64_t>(1, MSID_SCRATCH_BYTES / scratch));
+    const int64_t slab = msid_slab_frames(h->n_partial, n, grouped, h->whole, h->unwrap);
     hipEvent_t ev = h->timer.begin();
     for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
         const int64_t nf = std::min(slab, n_frames - f0);
@@ -148,16 +174,8 @@ extern "C" {
 int mdx_msid_create(mdx_msid_t *out, int dev, int n_groups, const int64_t *n_chains, const int64_t *n_monomers)
 {
     MDX_REQUIRE(out && n_chains && n_monomers, "NULL argument");
-    MDX_REQUIRE(n_groups >= 1 && n_groups <= 4096, "n_groups out of range");
-    const int64_t limit = (int64_t(1) << 31) / 3;
-    int64_t n_points = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        MDX_REQUIRE(n_chains[g] >= 1 && n_chains[g] < limit, "group %d: n_chains must be at least 1", g);
-        MDX_REQUIRE(n_monomers[g] >= 2 && n_monomers[g] < limit, "group %d: n_monomers must be at least 2", g);
-        MDX_REQUIRE(n_chains[g] * n_monomers[g] < limit - n_points,
-                    "the groups must hold fewer than 2^31 / 3 points");
-        n_points += n_chains[g] * n_monomers[g];
-    }
+    int64_t n_points = 0, n_partial = 0;
+    MDX_TRY(msid_layout(n_groups, n_chains, n_monomers, &n_points, &n_partial));
     // the units of the kernel and the groups' ranges of partial sums and rows
     std::vector<MsidUnit> units;
     std::vector<MsidGroup> groups;
@@ -180,7 +198,7 @@ int mdx_msid_create(mdx_msid_t *out, int dev, int n_groups, const int64_t *n_cha
     h->n_points = n_points;
     h->n_units = (int64_t)units.size();
     h->n_rows = row;
-    h->n_partial = partial;
+    h->n_partial = n_partial;       // == partial: the end of the last unit's range
     h->groups = groups;
     int rc = MDX_OK;
     do {
@@ -201,6 +219,17 @@ int mdx_msid_create(mdx_msid_t *out, int dev, int n_groups, const int64_t *n_cha
         return rc;
     }
     *out = h;
+    return MDX_OK;
+}
+
+int mdx_msid_slab_frames(int n_groups, const int64_t *n_chains, const int64_t *n_monomers, int grouped, int whole,
+                         int unwrap, int64_t *slab)
+{
+    MDX_REQUIRE(n_chains && n_monomers && slab, "NULL argument");
+    MDX_REQUIRE(!(whole && unwrap), "whole cannot be combined with unwrap");
+    int64_t n_points = 0, n_partial = 0;
+    MDX_TRY(msid_layout(n_groups, n_chains, n_monomers, &n_points, &n_partial));
+    *slab = msid_slab_frames(n_partial, n_points, grouped != 0, whole != 0, unwrap != 0);
     return MDX_OK;
 }
 

@@ -29,6 +29,15 @@ constexpr size_t PROF_LDS_LIMIT = size_t(60) << 10;        // ... one copy up to
 constexpr int64_t PROF_SLAB_FRAMES = 32768;                // frames per launch (grid y)
 constexpr int64_t PROF_SCRATCH_BYTES = int64_t(256) << 20; // centres / image counts of one slab
 
+// frames per slab of prof_accumulate_rows: what its scratch of one frame allows (plain atoms need none); also what
+// mdx_prof_slab_frames reports
+int64_t prof_slab_frames(int64_t n_points, bool grouped, bool recenter)
+{
+    const int64_t scratch = (grouped ? 24 * n_points : 0) + (recenter ? 12 * n_points + 24 : 0);
+    return scratch ? std::min(PROF_SLAB_FRAMES, std::max<int64_t>(1, PROF_SCRATCH_BYTES / scratch))
+                   : PROF_SLAB_FRAMES;
+}
+
 }  // namespace
 
 struct mdx_prof : FrameEngine {
@@ -168,9 +177,7 @@ static int prof_accumulate_rows(mdx_prof *h, const float *d_pos, int64_t src_row
     MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(prof_reserve_rows(h, n_frames));
     const int64_t n = h->n_points;
-    const int64_t scratch = (grouped ? 24 * n : 0) + (recenter ? 12 * n + 24 : 0);
-    const int64_t slab = scratch ? std::min(PROF_SLAB_FRAMES, std::max<int64_t>(1, PROF_SCRATCH_BYTES / scratch))
-                                 : PROF_SLAB_FRAMES;
+    const int64_t slab = prof_slab_frames(n, grouped, recenter);
     hipEvent_t ev = h->timer.begin();
     for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
         const int64_t nf = std::min(slab, n_frames - f0);
@@ -275,6 +282,24 @@ int mdx_prof_create(mdx_prof_t *out, int dev, int n_groups, const int64_t *group
     }
     *out = h;
     return mdx_prof_reset(h);
+}
+
+// the staging slab every per-frame engine's host and file route shares (FrameEngine::accumulate_host / _traj)
+int mdx_feed_slab_frames(int64_t n_frames, int64_t rows, int64_t *slab)
+{
+    MDX_REQUIRE(slab, "NULL argument");
+    MDX_REQUIRE(n_frames >= 1 && rows >= 1, "bad size");
+    *slab = feed_slab_frames(n_frames, rows);
+    return MDX_OK;
+}
+
+int mdx_prof_slab_frames(int64_t n_points, int grouped, int recenter, int64_t *slab)
+{
+    MDX_REQUIRE(slab, "NULL argument");
+    MDX_REQUIRE(n_points >= 1 && n_points < (int64_t(1) << 31) / 3,
+                "the groups must hold between 1 and 2^31 / 3 points");
+    *slab = prof_slab_frames(n_points, grouped != 0, recenter != 0);
+    return MDX_OK;
 }
 
 int mdx_prof_destroy(mdx_prof_t h)

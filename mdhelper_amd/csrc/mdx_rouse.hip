@@ -31,6 +31,14 @@ namespace {
 constexpr int64_t ROUSE_SLAB_FRAMES = 32768;                // frames per launch (grid y)
 constexpr int64_t ROUSE_SCRATCH_BYTES = int64_t(256) << 20; // centres / image counts of one slab
 
+// frames per slab of rouse_accumulate_rows: what its scratch of one frame allows; also what mdx_rouse_slab_frames
+// reports
+int64_t rouse_slab_frames(int64_t n_points, bool grouped, bool unwrap)
+{
+    const int64_t scratch = std::max<int64_t>(1, (grouped ? 24 * n_points : 0) + (unwrap ? 12 * n_points : 0));
+    return std::min(ROUSE_SLAB_FRAMES, std::max<int64_t>(1, ROUSE_SCRATCH_BYTES / scratch));
+}
+
 }  // namespace
 
 struct mdx_rouse : FrameEngine {
@@ -89,8 +97,7 @@ static int rouse_accumulate_rows(mdx_rouse *h, const float *d_pos, int64_t src_r
         MDX_HIP(hipMemcpyAsync(h->d_prev.ptr, h->start.data(), size_t(24) * n, hipMemcpyHostToDevice, h->stream));
         MDX_HIP(hipMemsetAsync(h->d_image.ptr, 0, size_t(12) * n, h->stream));
     }
-    const int64_t scratch = std::max<int64_t>(1, (grouped ? 24 * n : 0) + (h->unwrap ? 12 * n : 0));
-    const int64_t slab = std::min(ROUSE_SLAB_FRAMES, std::max<int64_t>(1, ROUSE_SCRATCH_BYTES / scratch));
+    const int64_t slab = rouse_slab_frames(n, grouped, h->unwrap);
     hipEvent_t ev = h->timer.begin();
     for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
         const int64_t nf = std::min(slab, n_frames - f0);
@@ -188,6 +195,15 @@ int mdx_rouse_create(mdx_rouse_t *out, int dev, int n_groups, const int64_t *n_c
         return rc;
     }
     *out = h;
+    return MDX_OK;
+}
+
+int mdx_rouse_slab_frames(int64_t n_points, int grouped, int unwrap, int64_t *slab)
+{
+    MDX_REQUIRE(slab, "NULL argument");
+    MDX_REQUIRE(n_points >= 1 && n_points < (int64_t(1) << 31) / 3,
+                "the groups must hold between 1 and 2^31 / 3 points");
+    *slab = rouse_slab_frames(n_points, grouped != 0, unwrap != 0);
     return MDX_OK;
 }
 
