@@ -150,9 +150,46 @@ typedef struct mdx_rdf *mdx_rdf_t;
 
 /* edges: the n_bins+1 float64 bin edges exactly as numpy.linspace(r_min, r_max,
  * n_bins+1) yields them (structure.py:737; numpy.histogram builds the same
- * array).  excl1/excl2: the reference's `exclusion` tuple, 0/0 for None. */
+ * array).  Enforced, for every algo and before the device is touched: an array that is not
+ * strictly increasing, or in which some edges[k] lies more than 4 ulp(edges[n_bins]) from
+ * edges[0] + k (edges[n_bins] - edges[0]) / n_bins (numpy.linspace stays within 2), is refused
+ * with MDX_ERR_INVALID_VALUE and a message that names the first such edge — the float32 filter
+ * and the cell-sorted kernel take bins from the uniform grid and would count other arrays
+ * wrongly.  excl1/excl2: the reference's `exclusion` tuple, 0/0 for None. */
 int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges,
                    int64_t excl1, int64_t excl2, int algo);
+/* The launch plan of an engine created with these arguments (checked as mdx_rdf_create checks them) for ONE run of
+ * n_frames frames of one cell kind, as every accumulate entry point hands it to the pair kernels: sets of n1 and n2
+ * points (same != 0: one set against itself, n2 ignored; no grouping, no dropped axis), boxes float32[n_frames][6] on
+ * the host or NULL for no periodic cell.  A batch that mixes orthorhombic and triclinic frames is cut into such runs
+ * by the engine and refused here (MDX_ERR_INVALID_VALUE).  Slots 17 and 18 describe a run handed over whole, that is
+ * one call of mdx_rdf_accumulate_device: the host-buffer and trajectory entry points stage a call in pieces of their
+ * own first (MDX_RDF_PIPE_MB, 256 MiB of source frames by default, the first two pieces of a call a quarter and a
+ * half of that or of the call), and every piece is a run of its own with slabs of its own.
+ * Touches no device; honours MDX_RDF_SLAB_BYTES, MDX_RDF_TRI_BRUTE and MDX_RDF_CHUNK_TILES as the engine does.  out:
+ *    0 kernel family: 0 rdf_tile_kernel, exact arithmetic; 1 rdf_tile_kernel, float32 filter; 2 rdf_cell_pair_kernel
+ *      on orthorhombic frames; 3 rdf_tri_tile_kernel (brute-force triclinic); 4 rdf_cell_pair_kernel on triclinic
+ *      frames (culled)
+ *    1 IPT: i particles per thread (tile rows T = 256 IPT; 1 outside family 0 / 1)
+ *    2 self: one set with one exclusion tag per row, mirror tile pairs counted twice
+ *    3 EXCL, 4 PBC (frames have a cell), 5 LOWER (range starts above 0; families 2 / 4, else 0)
+ *    6 SKIP (the step that leaves empty: families 2 / 4, always 1 in family 4; unused by the global form)
+ *    7 GH: thresholds and histogram in global memory
+ *    8 LDS histogram replicas n_hist (0 with GH)
+ *    9 dynamic LDS bytes of the pair launch, 10 whether hipFuncAttributeMaxDynamicSharedMemorySize is set for it
+ *      (above 48 KiB; the cell-sorted launches never set it)
+ *   11, 12 padded rows of set 1 and set 2 (multiples of T; of 128 in families 2 / 4)
+ *   13, 14 tiles of set 1 and set 2 (T rows; families 2 / 4: 128-row i tiles, 64-row j tiles)
+ *   15 chunk: j tiles one block (families 2 / 4: one item) walks
+ *   16 grid x of the pair launch (families 2 / 4: items per i tile; their grid is sized from the device's occupancy)
+ *   17 frames per slab, 18 slabs of the run: at most 32 768 frames each.  Families 2 / 4: as on the serial route
+ *      (MDX_RDF_SORT_BESIDE=0, or where the sort cannot run beside the pair kernel); with the sort beside, a run of
+ *      more than one slab starts with a quarter and a half slab and so takes more slabs than slot 18 says
+ *   19 lazy_orig: no sorted copy of the original coordinates (family 2 with exclusion 0 or 1)
+ *   20 .. 23 reserved, 0. */
+#define MDX_RDF_PLAN_SLOTS 24
+int mdx_rdf_plan(int n_bins, const double *edges, int64_t excl1, int64_t excl2, int algo, int64_t n1, int64_t n2,
+                 int same, const float *boxes, int64_t n_frames, int64_t out[MDX_RDF_PLAN_SLOTS]);
 int mdx_rdf_destroy(mdx_rdf_t h);
 int mdx_rdf_reset(mdx_rdf_t h);
 /* Host buffers.  pos2 == NULL (or == pos1 with n2 == n1) means ag2 is ag1: the

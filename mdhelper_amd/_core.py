@@ -238,6 +238,27 @@ class RdfEngine(_Engine):
         if timing:
             check(lib().mdx_rdf_enable_timing(h, 1))
 
+    PLAN_FIELDS = ("family", "ipt", "self", "excl", "pbc", "lower", "skip", "gh", "n_hist", "lds_bytes",
+                   "lds_attribute", "n1_pad", "n2_pad", "tiles1", "tiles2", "chunk", "grid_x", "slab_frames",
+                   "n_slabs", "lazy_orig")
+    FAMILIES = ("tile-exact", "tile-filter", "cell-ortho", "tri-brute", "tri-culled")
+
+    @staticmethod
+    def plan(edges, exclusion, algo, n1, n2=None, boxes=None, n_frames=1):
+        """``mdx_rdf_plan``: the pair kernel an engine built from ``edges``, ``exclusion`` and ``algo`` launches for ONE
+        run of ``n_frames`` frames of one cell kind, as a dict of ``PLAN_FIELDS`` — ``family`` indexes ``FAMILIES``.
+        ``n2=None``: one set against itself.  ``boxes``: ``None``, one cell or ``float32[n_frames, 6]``.  Needs no
+        device; reads ``MDX_RDF_SLAB_BYTES`` / ``MDX_RDF_TRI_BRUTE`` / ``MDX_RDF_CHUNK_TILES`` as the engine does."""
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        e1, e2 = (0, 0) if exclusion is None else (int(exclusion[0]), int(exclusion[1]))
+        b = None
+        if boxes is not None:
+            b = np.ascontiguousarray(np.broadcast_to(np.asarray(boxes, dtype=np.float32), (int(n_frames), 6)))
+        out = np.zeros(24, dtype=np.int64)
+        check(lib().mdx_rdf_plan(e.size - 1, _ptr(e), e1, e2, _lib.RDF_ALGO[algo], int(n1),
+                                 int(n1 if n2 is None else n2), int(n2 is None), _ptr(b), int(n_frames), _ptr(out)))
+        return dict(zip(RdfEngine.PLAN_FIELDS, (int(v) for v in out)))
+
     def accumulate(self, pos1, pos2=None, boxes=None):
         """pos: float32[F, N, 3] (host); boxes float32[F, 6] or None."""
         p1 = np.ascontiguousarray(pos1, dtype=np.float32)

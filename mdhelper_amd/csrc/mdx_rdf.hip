@@ -351,6 +351,263 @@ __global__ void rdf_reduce_kernel(const unsigned long long *__restrict__ rep, in
     total[b] = s;
 }
 
+// -------------------------------------------------------------- host planning
+//
+// Shared by the accumulate paths and by mdx_rdf_plan (which touches no device).  Every choice among the pair
+// kernels' instantiations, their histogram form, the padded sizes and the slab lengths is a pure function of the
+// engine's arguments, the set sizes, the frames' cells and the environment, and is made here and nowhere else.
+
+enum {
+    RDF_FAMILY_TILE_EXACT = 0,   // rdf_tile_kernel<MDX_RDF_ALGO_EXACT_F64, ...>
+    RDF_FAMILY_TILE_FILTER = 1,  // rdf_tile_kernel<MDX_RDF_ALGO_FILTER_F32, ...>
+    RDF_FAMILY_CELL_ORTHO = 2,   // rdf_cell_pair_kernel<..., TRI = false, ...>
+    RDF_FAMILY_TRI_BRUTE = 3,    // rdf_tri_tile_kernel
+    RDF_FAMILY_TRI_CULLED = 4    // rdf_cell_pair_kernel<..., TRI = true>
+};
+
+constexpr size_t RDF_LDS_BUDGET = 64 * 1024;      // dynamic LDS of one block: keeps >= 2 blocks per CU resident
+constexpr size_t RDF_LDS_ATTR_LINE = 48 * 1024;   // above it the tile kernels ask for the size with hipFuncSetAttribute
+constexpr int64_t RDF_MAX_SLAB = 32768;           // frames per slab of every route: no grid z beyond it
+
+// The pair kernel's step that leaves when none of its 64 pairs is a candidate (cell_step<..., SKIP>) pays one
+// scalar branch per step for the tail of the empty steps.  Fitted to the A/B series of round 7 (NOTES.md), a skipped
+// tail is worth 0.44 of a step and the branch costs 0.05: the step pays where more than 0.12 of the steps of the
+// shifted row loops are empty.  That share falls as the range grows against the 64-particle units — modelled at the
+// bench's density (scripts/cull_model.py): 0.17 at a range end of 0.22 L (C2(i): faster), 0.14 at 0.30 L, 0.12 at
+// 0.35 L, 0.07 at 0.5 L (C2(ii): slower) — so the launch takes the step up to 0.3 of the SHORTEST box length over its
+// frames and the unconditional tail beyond.  min_edge: that length (0 = not known: unconditional tail).
+constexpr float CELL_SKIP_MAX_RANGE = 0.3f;
+
+// the histogram of one pair kernel: LDS replicas, or the global form where the tables do not fit
+struct RdfHist {
+    int n_hist;   // LDS replicas (what the kernel is told; unused by the global form)
+    bool gh;      // tables too large for LDS: thresholds and histogram stay in global memory
+    size_t lds;   // dynamic LDS bytes of the launch
+};
+
+// brute-force tiles (rdf_tile_kernel with T = 256 IPT rows, rdf_tri_tile_kernel with T = 256): the j tile, the
+// thresholds and up to four per-wave histograms
+static RdfHist rdf_tile_hist(int n_bins, int T)
+{
+    const size_t base = sizeof(float4) * T + sizeof(double) * (size_t(n_bins) + 1);
+    RdfHist r;
+    r.n_hist = 4;
+    while (r.n_hist > 1 && base + size_t(r.n_hist) * n_bins * 4 > RDF_LDS_BUDGET)
+        r.n_hist >>= 1;
+    r.lds = base + size_t(r.n_hist) * n_bins * 4;
+    r.gh = r.lds > RDF_LDS_BUDGET;
+    if (r.gh)
+        r.lds = sizeof(float4) * T;
+    return r;
+}
+
+// cell-sorted pair kernel: 4 wave slabs + thresholds + the histogram in n_hist interleaved replicas (HistLdsRep):
+// 8 while seven blocks of a CU still fit (the kernel's static LDS is 8 992 B), fewer for long bin tables
+static RdfHist rdf_cell_hist(int n_bins)
+{
+    const size_t base = sizeof(float4) * 256 + sizeof(double) * (size_t(n_bins) + 1);
+    const size_t lds_seven_blocks = 13 * 1024;   // (160 KB / 7 = 22.8 KB) - 8.8 KB static = 14.0 KB
+    const size_t words = size_t(cell_hist_stride(n_bins));
+    RdfHist r;
+    r.n_hist = 8;
+    while (r.n_hist > 4 && base + size_t(r.n_hist) * words * 4 > lds_seven_blocks)
+        r.n_hist >>= 1;
+    while (r.n_hist > 1 && base + size_t(r.n_hist) * words * 4 > RDF_LDS_BUDGET)
+        r.n_hist >>= 1;
+    r.lds = base + size_t(r.n_hist) * words * 4;
+    r.gh = r.lds > RDF_LDS_BUDGET;
+    if (r.gh)
+        r.lds = sizeof(float4) * 256;
+    return r;
+}
+
+// one set against itself: the same rows AND the same tags, so that a tile pair may stand for its mirror image
+static void rdf_pair_flags(bool same, int64_t excl1, int64_t excl2, bool *self, bool *excl)
+{
+    *excl = excl1 > 0;
+    *self = same && (!*excl || excl1 == excl2);
+}
+
+// orthorhombic frames (or none): the pair kernel an algorithm stands for
+static int rdf_resolve_ortho_algo(int algo, bool has_boxes)
+{
+    // AUTO: the cell-sorted kernel whenever there is a periodic box — at every size.  Below 1 024 particles the
+    // tiles cannot be culled (the cutoff spans the cell), but its hot step (13 VALU instructions + the
+    // hand-placed tail per 64 evaluations, symmetric tile pairs evaluated once) is what the brute-force tile kernel
+    // spends 48 on: measured 1.1 x (16 particles) .. 3.4 x (1 000 particles, range to L/2: 0.88 -> 3.0 M frames/s)
+    // the frames per second, counts identical (scripts/diag/rdf_small_sweep.py, round 4).  Without a box: the
+    // brute-force tiles with the float32 filter.
+    if (algo == MDX_RDF_ALGO_AUTO)
+        algo = has_boxes ? MDX_RDF_ALGO_CELL : MDX_RDF_ALGO_FILTER_F32;
+    if (algo == MDX_RDF_ALGO_CELL && !has_boxes)
+        algo = MDX_RDF_ALGO_FILTER_F32;   // the cell grid is defined by the periodic box
+    return algo;
+}
+
+static int rdf_tile_ipt(int64_t n1, int64_t n2) { return std::max(n1, n2) >= 2048 ? 2 : 1; }
+// j tiles one block of the brute-force kernels walks
+static int rdf_tile_chunk(bool self) { return self ? 4 : 8; }
+
+// frames per slab of the brute-force routes (the packed float4 copies stay within 1 GiB), before the cut to the call
+static int64_t rdf_tile_slab_frames(int64_t n1p, int64_t n2p, bool self)
+{
+    const int64_t slab_bytes = int64_t(1) << 30;
+    const int64_t slab = std::max<int64_t>(1, slab_bytes / (int64_t(16) * (n1p + (self ? 0 : n2p))));
+    return std::min<int64_t>(slab, RDF_MAX_SLAB);
+}
+
+// frames per slab of the cell-sorted routes for a call of n_frames frames
+static int64_t rdf_cell_slab_frames(int64_t n1p, int64_t n2p, bool self, int64_t n_frames)
+{
+    // per frame: wrapped + original float4 copies, one box per 64 and per 16 particles
+    // (two-particle chunks take their boxes from the staged rows: no chunk-box array)
+    constexpr int64_t CHUNK_BOX_BYTES = CELL_CHUNK >= 4 ? 32 / CELL_CHUNK : 0;
+    const int64_t per_frame = (32 + 1 + CHUNK_BOX_BYTES) * (n1p + (self ? 0 : n2p));
+    // (MDX_RDF_SLAB_BYTES: test hook, so that small inputs run through several slabs and both sets)
+    const char *slab_env = getenv("MDX_RDF_SLAB_BYTES");
+    // (2.5 GiB = 2 304 frames at C2: the persistent kernel ends on a tail of about one item per block, so long
+    // launches pay — measured while the sort between two launches was still serial: 1 024 frames 45.3 k, 2 048
+    // 45.6–45.8 k, 4 096 45.7 k frames/s)
+    const int64_t slab_bytes = slab_env ? std::max<int64_t>(1, atoll(slab_env)) : (int64_t(5) << 29);
+    int64_t slab = std::max<int64_t>(1, slab_bytes / per_frame);
+    slab = std::min<int64_t>(slab, RDF_MAX_SLAB);
+    // whole rounds of the sort kernel: one 1 024-thread block per frame, one block per CU (65 VGPRs) —
+    // 993 frames were 3.9 rounds of 256 CUs and took 4
+    if (slab >= 256)
+        slab -= slab % 256;
+    return std::min<int64_t>(slab, n_frames);
+}
+
+// (triclinic launches keep the step: their range ends below half the smallest cell height)
+static bool rdf_cell_skip(bool tri, double r1, float min_edge)
+{
+    return tri || (float)r1 <= CELL_SKIP_MAX_RANGE * min_edge;
+}
+
+// exclusion 0 or 1: a particle's tag is its row, and the exact path reads the frames as they came in —
+// no sorted copy of the original coordinates (half of the sort kernel's scattered stores)
+static bool rdf_cell_lazy_orig(bool tri, int64_t excl1, int64_t excl2) { return !tri && excl1 <= 1 && excl2 <= 1; }
+
+// Items of the cell-sorted pair kernel: an i tile against a chunk of its candidate j tiles — every `chunks`-th of
+// them, so that each of an i tile's items gets its share of the tiles that survive the cull, which lie close
+// together.  A wave takes an item through alone, and a launch ends with its longest items: where nearly every tile
+// survives (the launches beyond the skipping step's range) a chunk is as many tiles as one cull pass tests, 64 —
+// about what a block took over a whole i tile; elsewhere a quarter of the j tiles: four items to an i tile, as four
+// waves shared it before.  (MDX_RDF_CHUNK_TILES, tiles per chunk: test hook.)  Returns the items of an i tile;
+// *tiles_per_chunk: the 64-row j tiles of one.
+static int rdf_cell_chunks(int64_t n2p, bool skip, int64_t *tiles_per_chunk)
+{
+    const char *ct = getenv("MDX_RDF_CHUNK_TILES");
+    int64_t c = ct ? atoll(ct) : (skip ? ceil_div(n2p / 64, 4) : 64);
+    c = ceil_div(std::max<int64_t>(c, 1), 64) * 64;
+    c = std::min<int64_t>(c, ceil_div(n2p / 64, 64) * 64);
+    if (tiles_per_chunk)
+        *tiles_per_chunk = c;
+    return (int)ceil_div(n2p / 64, c);
+}
+
+// cell matrix of (lx, ly, lz, alpha, beta, gamma): float64 arithmetic through libm, float32
+// entries, exact zeros for right angles (DESIGN.md §4.5)
+static void tri_vectors(const float *box6, float *B)
+{
+    const double lx = box6[0], ly = box6[1], lz = box6[2];
+    const double deg = 3.14159265358979323846 / 180.0;
+    const double ca = box6[3] == 90.0f ? 0.0 : std::cos((double)box6[3] * deg);
+    const double cb = box6[4] == 90.0f ? 0.0 : std::cos((double)box6[4] * deg);
+    const double cg = box6[5] == 90.0f ? 0.0 : std::cos((double)box6[5] * deg);
+    const double sg = box6[5] == 90.0f ? 1.0 : std::sin((double)box6[5] * deg);
+    for (int i = 0; i < 9; ++i)
+        B[i] = 0.0f;
+    B[0] = (float)lx;
+    B[3] = (float)(ly * cg);
+    B[4] = (float)(ly * sg);
+    const double cx = lz * cb;
+    const double cy = lz * (ca - cb * cg) / sg;
+    B[6] = (float)cx;
+    B[7] = (float)cy;
+    B[8] = (float)std::sqrt(lz * lz - cx * cx - cy * cy);
+}
+
+static inline bool box_is_ortho(const float *b) { return b[3] == 90.f && b[4] == 90.f && b[5] == 90.f; }
+
+// A batch is dispatched in runs of one cell kind: the run that starts at frame f0 ends before the returned frame.
+// *ortho: its kind; *min_edge: the shortest box length over its frames (rdf_cell_skip; orthorhombic runs only).
+static int64_t rdf_next_run(const float *h_boxes, int64_t f0, int64_t n_frames, bool *ortho, float *min_edge)
+{
+    *ortho = box_is_ortho(h_boxes + 6 * f0);
+    int64_t f1 = f0 + 1;
+    while (f1 < n_frames && box_is_ortho(h_boxes + 6 * f1) == *ortho)
+        ++f1;
+    *min_edge = h_boxes[6 * f0];
+    for (int64_t f = f0; f < f1; ++f)
+        *min_edge = std::min(*min_edge, std::min(h_boxes[6 * f], std::min(h_boxes[6 * f + 1], h_boxes[6 * f + 2])));
+    return f1;
+}
+
+// the cell matrices float[n_frames][9] of a run of triclinic frames, or why a frame has none
+static int rdf_tri_cells(const float *h_boxes, int64_t n_frames, std::vector<float> &tri)
+{
+    tri.resize(size_t(9) * n_frames);
+    for (int64_t f = 0; f < n_frames; ++f) {
+        const float *b = h_boxes + 6 * f;
+        if (!(b[0] > 0.f && b[1] > 0.f && b[2] > 0.f && b[3] > 0.f && b[3] < 180.f && b[4] > 0.f &&
+              b[4] < 180.f && b[5] > 0.f && b[5] < 180.f))
+            return fail(MDX_ERR_INVALID_VALUE, "frame %lld: invalid cell (%g %g %g %g %g %g)",
+                        (long long)f, b[0], b[1], b[2], b[3], b[4], b[5]);
+        tri_vectors(b, tri.data() + 9 * f);
+        if (!(tri[9 * f + 8] > 0.f) || !(tri[9 * f + 4] > 0.f))
+            return fail(MDX_ERR_INVALID_VALUE, "frame %lld: the cell angles do not span a volume",
+                        (long long)f);
+    }
+    return MDX_OK;
+}
+
+// Triclinic frames: the culled cell-sorted kernel (27 tile images, float32 filter, 27-image contract for the
+// undecided pairs) when the range ends below half the smallest cell height in every frame: then at most one image
+// of a pair can come within the cut.  Otherwise (or for small systems, or algo = exact / filter, or with
+// MDX_RDF_TRI_BRUTE set) the brute-force 27-image kernel.
+static bool rdf_tri_culled(int algo, int64_t n1, int64_t n2, double r1, const float *tri, int64_t n_frames)
+{
+    bool culled = algo == MDX_RDF_ALGO_AUTO || algo == MDX_RDF_ALGO_CELL;
+    culled = culled && std::max(n1, n2) >= 1024 && !getenv("MDX_RDF_TRI_BRUTE");
+    for (int64_t f = 0; culled && f < n_frames; ++f) {
+        const float *B = tri + 9 * f;
+        const double b00 = B[0], b10 = B[3], b11 = B[4], b20 = B[6], b21 = B[7], b22 = B[8];
+        const double vol = b00 * b11 * b22;
+        const double bcx = b11 * b22, bcy = -b10 * b22, bcz = b10 * b21 - b11 * b20;
+        const double hx = vol / std::sqrt(bcx * bcx + bcy * bcy + bcz * bcz);
+        const double hy = b11 * b22 / std::sqrt(b22 * b22 + b21 * b21);
+        const double r_in = 0.5 * std::min(hx, std::min(hy, b22));
+        culled = r1 * 1.02 + 1e-3 < r_in;
+    }
+    return culled;
+}
+
+// The contract binds the edges to numpy.linspace (mdx.h): the float32 filter and the cell kernel's sure path take
+// a pair's bin from floor((d - r0) * n_bins / (r1 - r0)) and only pairs near an edge of THAT grid go to the threshold
+// table, so any other increasing array would be binned wrongly there and rightly on the exact routes.  linspace
+// (one division, one multiplication, one addition) stays within 2 ulp of the real grid; 4 ulp(edges[n_bins]) are
+// allowed.  Precedes every device call, for every algorithm.
+static int rdf_check_edges(int n_bins, const double *edges)
+{
+    for (int b = 0; b < n_bins; ++b)
+        MDX_REQUIRE(edges[b] < edges[b + 1], "edges must increase strictly (edges[%d] = %.17g, edges[%d] = %.17g)",
+                    b, edges[b], b + 1, edges[b + 1]);
+    MDX_REQUIRE(edges[0] >= 0.0 && std::isfinite(edges[n_bins]), "range must be finite and >= 0");
+    const double top = std::fabs(edges[n_bins]);
+    const long double tol = 4.0L * ((long double)std::nextafter(top, INFINITY) - (long double)top);
+    const long double r0 = edges[0], span = (long double)edges[n_bins] - (long double)edges[0];
+    for (int k = 0; k <= n_bins; ++k) {
+        const long double want = r0 + (long double)k * span / (long double)n_bins;
+        const long double off = (long double)edges[k] - want;
+        if (!((off < 0 ? -off : off) <= tol))
+            return fail(MDX_ERR_INVALID_VALUE,
+                        "edges must be numpy.linspace(edges[0], edges[n_bins], n_bins + 1): edges[%d] = %.17g lies "
+                        "%.3g from the uniform grid's %.17g", k, edges[k], (double)off, (double)want);
+    }
+    return MDX_OK;
+}
+
 // --------------------------------------------------------------------- handle
 
 struct mdx_rdf {
@@ -405,19 +662,12 @@ struct mdx_rdf {
 static int launch_tiles(mdx_rdf *h, RdfArgs &a, int mode, int ipt, bool pbc, bool excl,
                         int64_t n_frames)
 {
-    const int T = 256 * ipt;
     // LDS: j tile + thresholds + per-wave histograms
-    size_t base = sizeof(float4) * T + sizeof(double) * (h->n_bins + 1);
-    const size_t lds_budget = 64 * 1024;   // keep >= 2 blocks per CU resident
-    int n_hist = 4;
-    while (n_hist > 1 && base + size_t(n_hist) * h->n_bins * 4 > lds_budget)
-        n_hist >>= 1;
-    size_t lds = base + size_t(n_hist) * h->n_bins * 4;
-    const bool gh = lds > lds_budget;   // tables too large for LDS: global histogram
-    if (gh)
-        lds = sizeof(float4) * T;
-    a.n_hist = n_hist;
-    a.chunk = a.self ? 4 : 8;
+    const RdfHist hist = rdf_tile_hist(h->n_bins, 256 * ipt);
+    const size_t lds = hist.lds;
+    const bool gh = hist.gh;
+    a.n_hist = hist.n_hist;
+    a.chunk = rdf_tile_chunk(a.self != 0);
     void (*kern)(RdfArgs) = nullptr;
 #define MDX_PICK(M, I, P, E) \
     kern = gh ? rdf_tile_kernel<M, I, P, E, true> : rdf_tile_kernel<M, I, P, E, false>
@@ -437,12 +687,13 @@ static int launch_tiles(mdx_rdf *h, RdfArgs &a, int mode, int ipt, bool pbc, boo
     }
 #undef MDX_PICK_PE
 #undef MDX_PICK
-    if (lds > 48 * 1024)
+    if (lds > RDF_LDS_ATTR_LINE)
         MDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipEvent_t ev = h->timer.begin();
-    for (int64_t f0 = 0; f0 < n_frames; f0 += 32768) {
-        int64_t nf = std::min<int64_t>(32768, n_frames - f0);
+    // (this loop never takes a second turn: the caller's slab, rdf_tile_slab_frames, is at most RDF_MAX_SLAB frames)
+    for (int64_t f0 = 0; f0 < n_frames; f0 += RDF_MAX_SLAB) {
+        int64_t nf = std::min<int64_t>(RDF_MAX_SLAB, n_frames - f0);
         a.frame0 = (int)f0;
         dim3 grid((unsigned)ceil_div(a.nt2, a.chunk), (unsigned)a.nt1, (unsigned)nf);
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, a);
@@ -454,65 +705,28 @@ static int launch_tiles(mdx_rdf *h, RdfArgs &a, int mode, int ipt, bool pbc, boo
 
 // Cell-sorted path (mdx_rdf_cell.hpp): sort + tile boxes per frame, then the culled pair kernel.
 // d_tri != nullptr: triclinic frames, d_tri = their cell matrices [n_frames][9] (d_boxes unused)
-// The pair kernel's step that leaves when none of its 64 pairs is a candidate (cell_step<..., SKIP>) pays one
-// scalar branch per step for the tail of the empty steps.  Fitted to the A/B series of round 7 (NOTES.md), a skipped
-// tail is worth 0.44 of a step and the branch costs 0.05: the step pays where more than 0.12 of the steps of the
-// shifted row loops are empty.  That share falls as the range grows against the 64-particle units — modelled at the
-// bench's density (scripts/cull_model.py): 0.17 at a range end of 0.22 L (C2(i): faster), 0.14 at 0.30 L, 0.12 at
-// 0.35 L, 0.07 at 0.5 L (C2(ii): slower) — so the launch takes the step up to 0.3 of the SHORTEST box length over its
-// frames and the unconditional tail beyond.  min_edge: that length (0 = not known: unconditional tail).
-constexpr float CELL_SKIP_MAX_RANGE = 0.3f;
-
+// min_edge: the shortest box length over the frames (rdf_cell_skip), 0 = not known
 static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
                            int64_t n2, const float *d_boxes, int64_t n_frames, bool self, bool excl,
                            const float *d_tri = nullptr, float min_edge = 0.f)
 {
     const bool tri = d_tri != nullptr;
     const int64_t n1p = ceil_div(n1, 128) * 128, n2p = ceil_div(n2, 128) * 128;
-    // per frame: wrapped + original float4 copies, one box per 64 and per 16 particles
-    // (two-particle chunks take their boxes from the staged rows: no chunk-box array)
-    constexpr int64_t CHUNK_BOX_BYTES = CELL_CHUNK >= 4 ? 32 / CELL_CHUNK : 0;
-    const int64_t per_frame = (32 + 1 + CHUNK_BOX_BYTES) * (n1p + (self ? 0 : n2p));
-    // (MDX_RDF_SLAB_BYTES: test hook, so that small inputs run through several slabs and both sets)
-    const char *slab_env = getenv("MDX_RDF_SLAB_BYTES");
-    // (2.5 GiB = 2 304 frames at C2: the persistent kernel ends on a tail of about one item per block, so long
-    // launches pay — measured while the sort between two launches was still serial: 1 024 frames 45.3 k, 2 048
-    // 45.6–45.8 k, 4 096 45.7 k frames/s)
-    const int64_t slab_bytes = slab_env ? std::max<int64_t>(1, atoll(slab_env)) : (int64_t(5) << 29);
-    int64_t slab = std::max<int64_t>(1, slab_bytes / per_frame);
-    slab = std::min<int64_t>(slab, 32768);
-    // whole rounds of the sort kernel: one 1 024-thread block per frame, one block per CU (65 VGPRs) —
-    // 993 frames were 3.9 rounds of 256 CUs and took 4
-    if (slab >= 256)
-        slab -= slab % 256;
-    slab = std::min<int64_t>(slab, n_frames);
-    // exclusion 0 or 1: a particle's tag is its row, and the exact path reads the frames as they came in —
-    // no sorted copy of the original coordinates (half of the sort kernel's scattered stores)
-    const bool lazy_orig = !tri && h->excl1 <= 1 && h->excl2 <= 1;
+    const int64_t slab = rdf_cell_slab_frames(n1p, n2p, self, n_frames);
+    const bool lazy_orig = rdf_cell_lazy_orig(tri, h->excl1, h->excl2);
     unsigned *d_misc = h->d_misc.as<unsigned>();
     if (!tri)
         hipLaunchKernelGGL(rdf_check_boxes_kernel, dim3((unsigned)ceil_div(n_frames, 256)), dim3(256),
                            0, h->stream, d_boxes, n_frames, d_misc + 1);
 
-    // LDS of the pair kernel: 4 wave slabs + thresholds + the histogram in n_hist interleaved replicas
-    // (HistLdsRep): 8 while seven blocks of a CU still fit (the kernel's static LDS is 8 992 B), fewer for
-    // long bin tables
-    size_t base = sizeof(float4) * 256 + sizeof(double) * (h->n_bins + 1);
-    const size_t lds_budget = 64 * 1024;
-    const size_t lds_six_blocks = 13 * 1024;   // seven blocks of a CU: (160 KB / 7 = 22.8 KB) - 8.8 KB static = 14.0 KB
-    int n_hist = 8;
-    while (n_hist > 4 && base + size_t(n_hist) * cell_hist_stride(h->n_bins) * 4 > lds_six_blocks)
-        n_hist >>= 1;
-    while (n_hist > 1 && base + size_t(n_hist) * cell_hist_stride(h->n_bins) * 4 > lds_budget)
-        n_hist >>= 1;
-    size_t lds = base + size_t(n_hist) * cell_hist_stride(h->n_bins) * 4;
-    const bool gh = lds > lds_budget;
-    if (gh)
-        lds = sizeof(float4) * 256;
+    // LDS of the pair kernel and the form of its histogram
+    const RdfHist hist = rdf_cell_hist(h->n_bins);
+    const int n_hist = hist.n_hist;
+    const size_t lds = hist.lds;
+    const bool gh = hist.gh;
     const bool lower = h->edges.front() > 0.0;
     void (*kern)(CellArgs) = nullptr;
-    // (triclinic launches keep the step: their range ends below half the smallest cell height)
-    const bool skip = tri || (float)h->edges.back() <= CELL_SKIP_MAX_RANGE * min_edge;
+    const bool skip = rdf_cell_skip(tri, h->edges.back(), min_edge);
 #define MDX_CELL_PICK(E, L)                                                                     \
     kern = tri ? (gh ? rdf_cell_pair_kernel<E, L, 1, true> : rdf_cell_pair_kernel<E, L, 0, true>) \
                : (gh ? rdf_cell_pair_kernel<E, L, 1>                                             \
@@ -727,19 +941,8 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
                 const long long cap = (1 << 17) - 512;
                 a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), cap) : (unsigned)cap;
             }
-            // Items: an i tile against a chunk of its candidate j tiles — every `chunks`-th of them, so that each of an
-            // i tile's items gets its share of the tiles that survive the cull, which lie close together.  A wave
-            // takes an item through alone, and a launch ends with its longest items: where nearly every tile survives
-            // (the launches beyond the skipping step's range) a chunk is as many tiles as one cull pass tests, 64 —
-            // about what a block took over a whole i tile; elsewhere a quarter of the j tiles: four items to an i
-            // tile, as four waves shared it before.  (MDX_RDF_CHUNK_TILES, tiles per chunk: test hook.)
-            {
-                const char *ct = getenv("MDX_RDF_CHUNK_TILES");
-                int64_t c = ct ? atoll(ct) : (skip ? ceil_div(n2p / 64, 4) : 64);
-                c = ceil_div(std::max<int64_t>(c, 1), 64) * 64;
-                c = std::min<int64_t>(c, ceil_div(n2p / 64, 64) * 64);
-                a.chunks = (int)ceil_div(n2p / 64, c);
-            }
+            // items: an i tile against a chunk of its candidate j tiles
+            a.chunks = rdf_cell_chunks(n2p, skip, nullptr);
             const int64_t tiles = (n1p / 128) * a.chunks;   // items of a frame
             // (frames per launch: the item index is 32 bits wide)
             const int64_t launch_frames = std::max<int64_t>(8, std::min<int64_t>(32768, ((int64_t(1) << 30) / tiles) * 8));
@@ -806,31 +1009,19 @@ static int accumulate_ortho(mdx_rdf *h, const float *d_pos1, int64_t n1, const f
         d_pos2 = d_pos1;
         n2 = n1;
     }
-    const bool excl = h->excl1 > 0;
-    const bool self = same && (!excl || h->excl1 == h->excl2);
+    bool excl, self;
+    rdf_pair_flags(same, h->excl1, h->excl2, &self, &excl);
     MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
 
-    // AUTO: the cell-sorted kernel whenever there is a periodic box — at every size.  Below 1 024 particles the
-    // tiles cannot be culled (the cutoff spans the cell), but its hot step (13 VALU instructions + the
-    // hand-placed tail per 64 evaluations, symmetric tile pairs evaluated once) is what the brute-force tile kernel
-    // spends 48 on: measured 1.1 x (16 particles) .. 3.4 x (1 000 particles, range to L/2: 0.88 -> 3.0 M frames/s)
-    // the frames per second, counts identical (scripts/diag/rdf_small_sweep.py, round 4).  Without a box: the
-    // brute-force tiles with the float32 filter.
-    int algo = h->algo;
-    if (algo == MDX_RDF_ALGO_AUTO)
-        algo = d_boxes ? MDX_RDF_ALGO_CELL : MDX_RDF_ALGO_FILTER_F32;
-    if (algo == MDX_RDF_ALGO_CELL && !d_boxes)
-        algo = MDX_RDF_ALGO_FILTER_F32;   // the cell grid is defined by the periodic box
+    const int algo = rdf_resolve_ortho_algo(h->algo, d_boxes != nullptr);
     if (algo == MDX_RDF_ALGO_CELL)
         return accumulate_cell(h, d_pos1, n1, d_pos2, n2, d_boxes, n_frames, self, excl, nullptr, min_edge);
-    const int ipt = (std::max(n1, n2) >= 2048) ? 2 : 1;
+    const int ipt = rdf_tile_ipt(n1, n2);
     const int T = 256 * ipt;
     const int64_t n1p = ceil_div(n1, T) * T, n2p = ceil_div(n2, T) * T;
 
     // frames are processed in slabs so the packed copies stay bounded
-    const int64_t slab_bytes = int64_t(1) << 30;
-    int64_t slab = std::max<int64_t>(1, slab_bytes / (int64_t(16) * (n1p + (self ? 0 : n2p))));
-    slab = std::min<int64_t>(slab, 32768);
+    const int64_t slab = rdf_tile_slab_frames(n1p, n2p, self);
     MDX_TRY(h->d_pack1.ensure(size_t(16) * n1p * std::min(slab, n_frames)));
     if (!self)
         MDX_TRY(h->d_pack2.ensure(size_t(16) * n2p * std::min(slab, n_frames)));
@@ -876,31 +1067,8 @@ static int accumulate_ortho(mdx_rdf *h, const float *d_pos1, int64_t n1, const f
     return MDX_OK;
 }
 
-// cell matrix of (lx, ly, lz, alpha, beta, gamma): float64 arithmetic through libm, float32
-// entries, exact zeros for right angles (DESIGN.md §4.5)
-static void tri_vectors(const float *box6, float *B)
-{
-    const double lx = box6[0], ly = box6[1], lz = box6[2];
-    const double deg = 3.14159265358979323846 / 180.0;
-    const double ca = box6[3] == 90.0f ? 0.0 : std::cos((double)box6[3] * deg);
-    const double cb = box6[4] == 90.0f ? 0.0 : std::cos((double)box6[4] * deg);
-    const double cg = box6[5] == 90.0f ? 0.0 : std::cos((double)box6[5] * deg);
-    const double sg = box6[5] == 90.0f ? 1.0 : std::sin((double)box6[5] * deg);
-    for (int i = 0; i < 9; ++i)
-        B[i] = 0.0f;
-    B[0] = (float)lx;
-    B[3] = (float)(ly * cg);
-    B[4] = (float)(ly * sg);
-    const double cx = lz * cb;
-    const double cy = lz * (ca - cb * cg) / sg;
-    B[6] = (float)cx;
-    B[7] = (float)cy;
-    B[8] = (float)std::sqrt(lz * lz - cx * cx - cy * cy);
-}
-
-static inline bool box_is_ortho(const float *b) { return b[3] == 90.f && b[4] == 90.f && b[5] == 90.f; }
-
-// Triclinic frames: brute-force tiles, 27-image search in double on every pair.
+// Triclinic frames: the culled cell-sorted kernel, or brute-force tiles with the 27-image search in double on every
+// pair (rdf_tri_culled).
 static int accumulate_triclinic(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
                                 int64_t n2, const float *h_boxes, int64_t n_frames)
 {
@@ -913,21 +1081,11 @@ static int accumulate_triclinic(mdx_rdf *h, const float *d_pos1, int64_t n1, con
         d_pos2 = d_pos1;
         n2 = n1;
     }
-    const bool excl = h->excl1 > 0;
-    const bool self = same && (!excl || h->excl1 == h->excl2);
+    bool excl, self;
+    rdf_pair_flags(same, h->excl1, h->excl2, &self, &excl);
     MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
-    std::vector<float> tri(size_t(9) * n_frames);
-    for (int64_t f = 0; f < n_frames; ++f) {
-        const float *b = h_boxes + 6 * f;
-        if (!(b[0] > 0.f && b[1] > 0.f && b[2] > 0.f && b[3] > 0.f && b[3] < 180.f && b[4] > 0.f &&
-              b[4] < 180.f && b[5] > 0.f && b[5] < 180.f))
-            return fail(MDX_ERR_INVALID_VALUE, "frame %lld: invalid cell (%g %g %g %g %g %g)",
-                        (long long)f, b[0], b[1], b[2], b[3], b[4], b[5]);
-        tri_vectors(b, tri.data() + 9 * f);
-        if (!(tri[9 * f + 8] > 0.f) || !(tri[9 * f + 4] > 0.f))
-            return fail(MDX_ERR_INVALID_VALUE, "frame %lld: the cell angles do not span a volume",
-                        (long long)f);
-    }
+    std::vector<float> tri;
+    MDX_TRY(rdf_tri_cells(h_boxes, n_frames, tri));
     // the previous call's kernels may still read the cell matrices
     MDX_HIP(hipStreamSynchronize(h->stream));
     MDX_TRY(h->d_tri.ensure(size_t(36) * n_frames));
@@ -935,44 +1093,23 @@ static int accumulate_triclinic(mdx_rdf *h, const float *d_pos1, int64_t n1, con
                            h->stream));
     MDX_HIP(hipStreamSynchronize(h->stream));   // `tri` leaves scope
 
-    // Culled cell-sorted kernel (27 tile images, float32 filter, 27-image contract for the
-    // undecided pairs) when the range ends below half the smallest cell height in every frame:
-    // then at most one image of a pair can come within the cut.  Otherwise (or for small
-    // systems, or algo = exact / filter) the brute-force 27-image kernel below.
-    bool culled = h->algo == MDX_RDF_ALGO_AUTO || h->algo == MDX_RDF_ALGO_CELL;
-    culled = culled && std::max(n1, n2) >= 1024 && !getenv("MDX_RDF_TRI_BRUTE");
-    for (int64_t f = 0; culled && f < n_frames; ++f) {
-        const float *B = tri.data() + 9 * f;
-        const double b00 = B[0], b10 = B[3], b11 = B[4], b20 = B[6], b21 = B[7], b22 = B[8];
-        const double vol = b00 * b11 * b22;
-        const double bcx = b11 * b22, bcy = -b10 * b22, bcz = b10 * b21 - b11 * b20;
-        const double hx = vol / std::sqrt(bcx * bcx + bcy * bcy + bcz * bcz);
-        const double hy = b11 * b22 / std::sqrt(b22 * b22 + b21 * b21);
-        const double r_in = 0.5 * std::min(hx, std::min(hy, b22));
-        culled = h->edges.back() * 1.02 + 1e-3 < r_in;
-    }
-    if (culled)
+    if (rdf_tri_culled(h->algo, n1, n2, h->edges.back(), tri.data(), n_frames))
         return accumulate_cell(h, d_pos1, n1, d_pos2, n2, nullptr, n_frames, self,
                                excl, h->d_tri.as<float>());
 
     const int64_t n1p = ceil_div(n1, 256) * 256, n2p = ceil_div(n2, 256) * 256;
-    int64_t slab = std::max<int64_t>(1, (int64_t(1) << 30) / (int64_t(16) * (n1p + (self ? 0 : n2p))));
-    slab = std::min<int64_t>(std::min<int64_t>(slab, 32768), n_frames);
+    const int64_t slab = std::min<int64_t>(rdf_tile_slab_frames(n1p, n2p, self), n_frames);
     MDX_TRY(h->d_pack1.ensure(size_t(16) * n1p * slab));
     if (!self)
         MDX_TRY(h->d_pack2.ensure(size_t(16) * n2p * slab));
 
-    size_t base = sizeof(float4) * 256 + sizeof(double) * (h->n_bins + 1);
-    int n_hist = 4;
-    while (n_hist > 1 && base + size_t(n_hist) * h->n_bins * 4 > size_t(64) * 1024)
-        n_hist >>= 1;
-    size_t lds = base + size_t(n_hist) * h->n_bins * 4;
-    const bool gh = lds > size_t(64) * 1024;
-    if (gh)
-        lds = sizeof(float4) * 256;
+    const RdfHist hist = rdf_tile_hist(h->n_bins, 256);
+    const int n_hist = hist.n_hist;
+    const size_t lds = hist.lds;
+    const bool gh = hist.gh;
     void (*kern)(TriArgs) = excl ? (gh ? rdf_tri_tile_kernel<true, true> : rdf_tri_tile_kernel<true, false>)
                                  : (gh ? rdf_tri_tile_kernel<false, true> : rdf_tri_tile_kernel<false, false>);
-    if (lds > 48 * 1024)
+    if (lds > RDF_LDS_ATTR_LINE)
         MDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const double width = (h->edges.back() - h->edges.front()) / h->n_bins;
@@ -1003,7 +1140,7 @@ static int accumulate_triclinic(mdx_rdf *h, const float *d_pos1, int64_t n1, con
         a.n_bins = h->n_bins;
         a.n_hist = n_hist;
         a.n_rep = h->n_rep;
-        a.chunk = self ? 4 : 8;
+        a.chunk = rdf_tile_chunk(self);
         a.self = self ? 1 : 0;
         a.frame0 = 0;
         hipEvent_t ev = h->timer.begin();
@@ -1127,18 +1264,14 @@ static int accumulate_device_points(mdx_rdf *h, const float *d_pos1, int64_t n1,
         h_boxes = copy.data();
     }
     for (int64_t f0 = 0; f0 < n_frames;) {
-        const bool ortho = box_is_ortho(h_boxes + 6 * f0);
-        int64_t f1 = f0 + 1;
-        while (f1 < n_frames && box_is_ortho(h_boxes + 6 * f1) == ortho)
-            ++f1;
+        bool ortho;
+        float min_edge;
+        const int64_t f1 = rdf_next_run(h_boxes, f0, n_frames, &ortho, &min_edge);
         const float *p1 = d_pos1 + f0 * n1 * 3;
         const float *p2 = d_pos2 ? d_pos2 + f0 * n2 * 3 : nullptr;
-        if (ortho) {
-            float min_edge = h_boxes[6 * f0];
-            for (int64_t f = f0; f < f1; ++f)
-                min_edge = std::min(min_edge, std::min(h_boxes[6 * f], std::min(h_boxes[6 * f + 1], h_boxes[6 * f + 2])));
+        if (ortho)
             MDX_TRY(accumulate_ortho(h, p1, n1, p2, n2, d_boxes + f0 * 6, f1 - f0, min_edge));
-        } else
+        else
             MDX_TRY(accumulate_triclinic(h, p1, n1, p2, n2, h_boxes + 6 * f0, f1 - f0));
         f0 = f1;
     }
@@ -1207,9 +1340,7 @@ int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges, int
     MDX_REQUIRE((excl1 > 0) == (excl2 > 0) && excl1 >= 0 && excl2 >= 0,
                 "exclusion must be two positive integers (or 0, 0 for none)");
     MDX_REQUIRE(algo >= MDX_RDF_ALGO_AUTO && algo <= MDX_RDF_ALGO_CELL, "unknown algo %d", algo);
-    for (int b = 0; b < n_bins; ++b)
-        MDX_REQUIRE(edges[b] < edges[b + 1], "edges must increase strictly");
-    MDX_REQUIRE(edges[0] >= 0.0 && std::isfinite(edges[n_bins]), "range must be finite and >= 0");
+    MDX_TRY(rdf_check_edges(n_bins, edges));
     MDX_TRY(set_device(dev));
     mdx_rdf *h = new mdx_rdf();
     h->dev = dev;
@@ -1249,6 +1380,98 @@ int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges, int
     }
     *out = h;
     return mdx_rdf_reset(h);
+}
+
+// What an engine created with these arguments would launch for one run of n_frames frames of one cell kind; touches
+// no device.  The slots are documented in mdx.h.
+int mdx_rdf_plan(int n_bins, const double *edges, int64_t excl1, int64_t excl2, int algo, int64_t n1, int64_t n2,
+                 int same, const float *boxes, int64_t n_frames, int64_t out[MDX_RDF_PLAN_SLOTS])
+{
+    MDX_REQUIRE(edges && out, "NULL argument");
+    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 20), "n_bins=%d out of range", n_bins);
+    MDX_REQUIRE((excl1 > 0) == (excl2 > 0) && excl1 >= 0 && excl2 >= 0,
+                "exclusion must be two positive integers (or 0, 0 for none)");
+    MDX_REQUIRE(algo >= MDX_RDF_ALGO_AUTO && algo <= MDX_RDF_ALGO_CELL, "unknown algo %d", algo);
+    MDX_TRY(rdf_check_edges(n_bins, edges));
+    if (same)
+        n2 = n1;
+    MDX_REQUIRE(n1 >= 1 && n2 >= 1 && n_frames >= 1, "bad size");
+    MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
+    bool ortho = true;
+    float min_edge = 0.f;
+    if (boxes) {
+        MDX_TRY(check_host_boxes(boxes, n_frames));
+        const int64_t f1 = rdf_next_run(boxes, 0, n_frames, &ortho, &min_edge);
+        MDX_REQUIRE(f1 == n_frames,
+                    "frame %lld: orthorhombic and triclinic frames in one run (plan each run of one kind)",
+                    (long long)f1);
+    }
+    bool self, excl;
+    rdf_pair_flags(same != 0, excl1, excl2, &self, &excl);
+    for (int k = 0; k < MDX_RDF_PLAN_SLOTS; ++k)
+        out[k] = 0;
+    const double r0 = edges[0], r1 = edges[n_bins];
+    int family;
+    bool culled = false;
+    if (ortho) {
+        const int a = rdf_resolve_ortho_algo(algo, boxes != nullptr);
+        family = a == MDX_RDF_ALGO_CELL ? RDF_FAMILY_CELL_ORTHO
+                                        : a == MDX_RDF_ALGO_EXACT_F64 ? RDF_FAMILY_TILE_EXACT : RDF_FAMILY_TILE_FILTER;
+    } else {
+        std::vector<float> tri;
+        MDX_TRY(rdf_tri_cells(boxes, n_frames, tri));
+        culled = rdf_tri_culled(algo, n1, n2, r1, tri.data(), n_frames);
+        family = culled ? RDF_FAMILY_TRI_CULLED : RDF_FAMILY_TRI_BRUTE;
+    }
+    out[0] = family;
+    out[2] = self;
+    out[3] = excl;
+    out[4] = boxes != nullptr;
+    if (family == RDF_FAMILY_CELL_ORTHO || family == RDF_FAMILY_TRI_CULLED) {
+        const bool tri = family == RDF_FAMILY_TRI_CULLED;
+        const int64_t n1p = ceil_div(n1, 128) * 128, n2p = ceil_div(n2, 128) * 128;
+        const RdfHist hist = rdf_cell_hist(n_bins);
+        const bool skip = rdf_cell_skip(tri, r1, min_edge);
+        int64_t tiles_per_chunk = 0;
+        const int chunks = rdf_cell_chunks(n2p, skip, &tiles_per_chunk);
+        const int64_t slab = rdf_cell_slab_frames(n1p, n2p, self, n_frames);
+        out[1] = 1;
+        out[5] = r0 > 0.0;
+        out[6] = skip;
+        out[7] = hist.gh;
+        out[8] = hist.gh ? 0 : hist.n_hist;
+        out[9] = (int64_t)hist.lds;
+        out[10] = 0;   // the cell-sorted launches never ask for the attribute
+        out[11] = n1p;
+        out[12] = n2p;
+        out[13] = n1p / 128;
+        out[14] = n2p / 64;
+        out[15] = tiles_per_chunk;
+        out[16] = chunks;
+        out[17] = slab;
+        out[18] = ceil_div(n_frames, slab);
+        out[19] = rdf_cell_lazy_orig(tri, excl1, excl2);
+        return MDX_OK;
+    }
+    const int ipt = family == RDF_FAMILY_TRI_BRUTE ? 1 : rdf_tile_ipt(n1, n2);
+    const int T = 256 * ipt;
+    const int64_t n1p = ceil_div(n1, T) * T, n2p = ceil_div(n2, T) * T;
+    const RdfHist hist = rdf_tile_hist(n_bins, T);
+    const int64_t slab = std::min<int64_t>(rdf_tile_slab_frames(n1p, n2p, self), n_frames);
+    out[1] = ipt;
+    out[7] = hist.gh;
+    out[8] = hist.gh ? 0 : hist.n_hist;
+    out[9] = (int64_t)hist.lds;
+    out[10] = hist.lds > RDF_LDS_ATTR_LINE;
+    out[11] = n1p;
+    out[12] = n2p;
+    out[13] = n1p / T;
+    out[14] = n2p / T;
+    out[15] = rdf_tile_chunk(self);
+    out[16] = ceil_div(n2p / T, out[15]);
+    out[17] = slab;
+    out[18] = ceil_div(n_frames, slab);
+    return MDX_OK;
 }
 
 int mdx_rdf_destroy(mdx_rdf_t h)
@@ -1576,6 +1799,7 @@ int mdx_radial_histogram(int dev, const float *pos1, int64_t n1, const float *po
 {
     MDX_REQUIRE(counts, "counts is NULL");
     mdx_rdf_t h = nullptr;
+    // (checks the arguments, the edges among them, before it touches the device)
     MDX_TRY(mdx_rdf_create(&h, dev, n_bins, edges, excl1, excl2, MDX_RDF_ALGO_AUTO));
     int rc = mdx_rdf_accumulate(h, pos1, n1, pos2, n2, dims, 1);
     if (rc == MDX_OK)
