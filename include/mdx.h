@@ -190,6 +190,19 @@ int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges,
 #define MDX_RDF_PLAN_SLOTS 24
 int mdx_rdf_plan(int n_bins, const double *edges, int64_t excl1, int64_t excl2, int algo, int64_t n1, int64_t n2,
                  int same, const float *boxes, int64_t n_frames, int64_t out[MDX_RDF_PLAN_SLOTS]);
+/* The constants of the float32 filter of rdf_cell_pair_kernel for one orthorhombic frame: cell lengths box[3], the
+ * batch's largest |coordinate| max_abs, range [r0, r1] in n_bins bins.  Touches no device; the values are those the
+ * frame-constant kernel computes (same functions, same arithmetic).  out:
+ *    0 eta: distance from a bin edge, in bins, within which a pair goes to the exact arithmetic
+ *    1 sure_w = 1 - 2 eta, 2 TQ = floor(2^16 sure_w) clamped to [0, 65 535]: a pair is sure when the low half of its
+ *      16.16 fixed-point bin position is below TQ (LDS histogram) or fract(pos) < sure_w (global histogram)
+ *    3 inv_w = fl32(1 / width), 4 pos0 = -r0 inv_w - eta: pos = fl32(sqrt(r2) inv_w + pos0)
+ *    5 IWQ = 2^16 inv_w, 6 P0Q = 2^16 pos0 (exact scalings): q = floor(fl32(sqrt(r2) IWQ + P0Q))
+ *    7, 8 the candidate window on the float32 squared distance (8: -1 when the range starts at 0)
+ *    9 reserved, 0. */
+#define MDX_RDF_FILTER_SLOTS 10
+int mdx_rdf_filter_constants(int n_bins, double r0, double r1, const float box[3], float max_abs,
+                             double out[MDX_RDF_FILTER_SLOTS]);
 int mdx_rdf_destroy(mdx_rdf_t h);
 int mdx_rdf_reset(mdx_rdf_t h);
 /* Host buffers.  pos2 == NULL (or == pos1 with n2 == n1) means ag2 is ag1: the

@@ -259,6 +259,22 @@ class RdfEngine(_Engine):
                                  int(n1 if n2 is None else n2), int(n2 is None), _ptr(b), int(n_frames), _ptr(out)))
         return dict(zip(RdfEngine.PLAN_FIELDS, (int(v) for v in out)))
 
+    FILTER_FIELDS = ("eta", "sure_w", "tq", "inv_w", "pos0", "iwq", "p0q", "cand_hi", "cand_lo")
+
+    @staticmethod
+    def filter_constants(edges, box, max_abs):
+        """``mdx_rdf_filter_constants``: the float32 filter constants of the cell-sorted pair kernel for one
+        orthorhombic frame with cell lengths ``box`` and a largest |coordinate| of ``max_abs``, as a dict of
+        ``FILTER_FIELDS`` (``tq`` an int, the others the float32 values as Python floats).  Needs no device."""
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        b = np.ascontiguousarray(np.asarray(box, dtype=np.float32).ravel()[:3])
+        out = np.zeros(10, dtype=np.float64)
+        check(lib().mdx_rdf_filter_constants(e.size - 1, float(e[0]), float(e[-1]), _ptr(b), float(max_abs),
+                                             _ptr(out)))
+        d = dict(zip(RdfEngine.FILTER_FIELDS, (float(v) for v in out)))
+        d["tq"] = int(d["tq"])
+        return d
+
     def accumulate(self, pos1, pos2=None, boxes=None):
         """pos: float32[F, N, 3] (host); boxes float32[F, 6] or None."""
         p1 = np.ascontiguousarray(pos1, dtype=np.float32)

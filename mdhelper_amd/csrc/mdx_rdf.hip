@@ -377,6 +377,7 @@ constexpr int64_t RDF_MAX_SLAB = 32768;           // frames per slab of every ro
 // 0.35 L, 0.07 at 0.5 L (C2(ii): slower) — so the launch takes the step up to 0.3 of the SHORTEST box length over its
 // frames and the unconditional tail beyond.  min_edge: that length (0 = not known: unconditional tail).
 constexpr float CELL_SKIP_MAX_RANGE = 0.3f;
+constexpr int CELL_FIXED_MAX_BINS = 32766;   // the LDS form's bin position is 16.16 fixed point (rdf_cell_hist)
 
 // the histogram of one pair kernel: LDS replicas, or the global form where the tables do not fit
 struct RdfHist {
@@ -415,7 +416,9 @@ static RdfHist rdf_cell_hist(int n_bins)
     while (r.n_hist > 1 && base + size_t(r.n_hist) * words * 4 > RDF_LDS_BUDGET)
         r.n_hist >>= 1;
     r.lds = base + size_t(r.n_hist) * words * 4;
-    r.gh = r.lds > RDF_LDS_BUDGET;
+    // The LDS form bins in 16.16 fixed point (cell_fixed_q): the bin is the high half of a signed 32-bit value, so
+    // n_bins + 1 <= 32 767.  The budget above is the tighter bound by far (some 5 000 bins); stated, not relied on.
+    r.gh = r.lds > RDF_LDS_BUDGET || n_bins > CELL_FIXED_MAX_BINS;
     if (r.gh)
         r.lds = sizeof(float4) * 256;
     return r;
@@ -1380,6 +1383,31 @@ int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges, int
     }
     *out = h;
     return mdx_rdf_reset(h);
+}
+
+// The float32 filter constants the cell-sorted pair kernel takes for an orthorhombic frame with cell lengths `box`
+// and a batch whose largest |coordinate| is max_abs; touches no device.  The slots are documented in mdx.h.
+int mdx_rdf_filter_constants(int n_bins, double r0, double r1, const float box[3], float max_abs,
+                             double out[MDX_RDF_FILTER_SLOTS])
+{
+    MDX_REQUIRE(box && out, "NULL argument");
+    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 20), "n_bins=%d out of range", n_bins);
+    MDX_REQUIRE(r0 >= 0.0 && r1 > r0, "bad range");
+    MDX_REQUIRE(box[0] > 0.f && box[1] > 0.f && box[2] > 0.f, "bad cell");
+    const double Lmax = std::max((double)box[0], std::max((double)box[1], (double)box[2]));
+    const RdfFilterConst f = rdf_filter_const(Lmax, (double)max_abs, r0, r1, n_bins);
+    const float pos0 = cell_pos0(f.r0f, f.inv_wf, f.eta), sure_w = cell_sure_w(f.eta);
+    out[0] = f.eta;
+    out[1] = sure_w;
+    out[2] = cell_fixed_tq(sure_w);
+    out[3] = f.inv_wf;
+    out[4] = pos0;
+    out[5] = f.inv_wf * 65536.0f;
+    out[6] = pos0 * 65536.0f;
+    out[7] = f.cand_hi;
+    out[8] = f.cand_lo;
+    out[9] = 0.0;
+    return MDX_OK;
 }
 
 // What an engine created with these arguments would launch for one run of n_frames frames of one cell kind; touches

@@ -105,6 +105,9 @@ struct HistLdsRep {
 };
 __device__ inline int cell_hist_shift(const HistLdsRep &h) { return h.sh; }
 template <typename Hist> __device__ inline int cell_hist_shift(const Hist &) { return 0; }
+// the LDS histogram is MODE 0's, whose steps bin in 16.16 fixed point (cell_fixed_q)
+template <typename Hist> struct CellHistFixed { static constexpr bool value = false; };
+template <> struct CellHistFixed<HistLdsRep> { static constexpr bool value = true; };
 
 struct CellGrid {
     int nc[3];
@@ -572,6 +575,10 @@ struct CellOrig {
 struct CellHot {
     float cand_hi, cand_lo, inv_w, sure_w;   // sure_w = 1 - 2 eta
     float pos0;   // -r0/width - eta; kept in a VECTOR register (an fma takes one scalar operand)
+    // MODE 0: the same three in 16.16 fixed point (cell_fixed_q): inv_w 2^16, pos0 2^16 (vector register) and
+    // floor(sure_w 2^16); a kernel instantiation keeps the form its step reads and drops the other
+    float iwq, p0q;
+    unsigned tq;
     float L[3], invL[3];   // box lengths and fl32(1/L): widened to fp64 only by the exact passes
     const float *tri;      // triclinic variant: the frame's cell matrix (LDS), else nullptr
 };
@@ -609,26 +616,60 @@ struct CellWave {
     unsigned n_exact;    // pairs sent to the exact arithmetic so far
 };
 
-// The float32 filter of one pair: bin coordinate, candidate and sure flags.
-template <bool LOWER, int TAGS>
+// pos0 and sure_w of the shifted bin coordinate (cell_filter), as rdf_cell_frame_geo_kernel writes them and
+// mdx_rdf_filter_constants reports them (this unit is compiled without contraction: a product and a difference)
+__host__ __device__ inline float cell_pos0(float r0f, float inv_wf, float eta) { return -r0f * inv_wf - eta; }
+__host__ __device__ inline float cell_sure_w(float eta) { return 1.0f - 2.0f * eta; }
+// tq of cell_fixed_q, below
+__host__ __device__ inline unsigned cell_fixed_tq(float sure_w)
+{
+    // (sure_w <= 0, an eta of half a bin or more: nothing is sure; 2^16 never reaches the 16-bit compare)
+    return (unsigned)fminf(fmaxf(floorf(sure_w * 65536.0f), 0.0f), 65535.0f);
+}
+
+// The bin position of MODE 0 in 16.16 fixed point: q = floor(2^16 pos) as a 32-bit integer, where
+// pos = fl(sqrt(r2) inv_w + pos0) is the float32 bin coordinate of cell_filter.  iwq and p0q are inv_w and pos0
+// times 2^16, and a scaling by a power of two commutes with the rounding of the fma, so the float the convert reads
+// IS 2^16 pos: the high half of q is floor(pos) and the low half floor(2^16 fract(pos)) — for a negative pos as well,
+// because the convert rounds towards minus infinity (v_cvt_flr_i32_f32; it saturates, and a candidate is nowhere
+// near 2^31).  A pair is sure when its low half is below tq = floor(2^16 sure_w): then fract(pos) < tq 2^-16 <=
+// sure_w, the test of cell_filter, and the pairs between the two thresholds — at most 2^-16 of a bin wide — go to
+// the exact path, which gives the contract's answer whichever pairs reach it.  The hot step spells the same three
+// instructions out by hand (MDX_CELL_SKIP_TAIL); the redo of an overflowed unit classifies through this function.
+__device__ inline unsigned cell_fixed_q(const CellHot &c, float r2)
+{
+    const float qf = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.iwq, c.p0q);
+    unsigned q;
+    asm("v_cvt_flr_i32_f32_e32 %0, %1" : "=v"(q) : "v"(qf));
+    return q;
+}
+__device__ inline bool cell_fixed_sure(const CellHot &c, unsigned q) { return (q & 0xffffu) < c.tq; }
+
+// The float32 filter of one pair: candidate and sure flags, as the step of this MODE forms them.
+template <bool LOWER, int TAGS, int MODE>
 __device__ inline void cell_filter(const CellHot &c, float fx, float fy, float fz, int tag_i,
-                                   int tag_j, float &pos, bool &cand, bool &sure)
+                                   int tag_j, bool &cand, bool &sure)
 {
     float r2 = __fmaf_rn(fz, fz, __fmaf_rn(fy, fy, fx * fx));
     // pos = (sqrt(r2) - r0) / width - eta; raw v_sqrt_f32 (a denormal r2 ends on the exact path).
     // "Farther than eta from both neighbouring bin edges" is fract(pos) < 1 - 2 eta in this
     // shifted coordinate: with pos = k + t, the unshifted fraction is t + eta, which lies in
-    // (eta, 1 - eta) exactly when t < 1 - 2 eta (t + eta >= 1 means it wrapped to < eta).  One
-    // v_fract and one compare; for a sure pair floor(pos) is the bin, and since a candidate has
-    // pos > -2 eta (window) the truncating v_cvt_i32_f32 is that floor.
-    pos = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.inv_w, c.pos0);
-    const float t = __builtin_amdgcn_fractf(pos);
+    // (eta, 1 - eta) exactly when t < 1 - 2 eta (t + eta >= 1 means it wrapped to < eta).  For a
+    // sure pair floor(pos) is the bin: a candidate has pos > -2 eta (window), and one below 0 has
+    // t > 1 - 2 eta.  MODE 1 tests t itself (v_fract_f32 and a compare), MODE 0 its first 16 bits.
+    if (MODE == 0) {
+        sure = cell_fixed_sure(c, cell_fixed_q(c, r2));
+    } else {
+        const float pos = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.inv_w, c.pos0);
+        sure = __builtin_amdgcn_fractf(pos) < c.sure_w;
+    }
     cand = LOWER ? (r2 < c.cand_hi && r2 >= c.cand_lo) : (r2 < c.cand_hi);
-    sure = t < c.sure_w;
     if (TAGS)
         cand = cand && (tag_i != tag_j);
 }
 
+// (FIXED: the instantiation keeps the fixed-point constants; inv_w 2^16 scaled back is inv_w to the bit)
+template <bool FIXED>
 __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairCtx<true> &cx)
 {
 #pragma unroll
@@ -637,7 +678,7 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
         cx.invd[k] = (double)c.invL[k];
     }
     cx.r0f = (float)a.r0;
-    cx.inv_wf = c.inv_w;
+    cx.inv_wf = FIXED ? c.iwq * 0x1p-16f : c.inv_w;
 }
 
 // One float32 distance evaluation + binning.  Without SKIP the bin arithmetic is unconditional
@@ -657,7 +698,7 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
 // the test are half of a step's issue cycles.  The steps of the straddling loops take the per-pair
 // image and keep the unconditional tail (SKIP = false), as does MODE 1.
 //
-// The tail of a SKIP step (v_sqrt_f32, v_fma_f32, v_fract_f32 and what follows) lives inside the asm
+// The tail of a SKIP step (v_sqrt_f32, v_fma_f32, the convert and what follows) lives inside the asm
 // block, behind s_cbranch_execz; r2 is still formed in C++, so the compiler goes on hoisting the next
 // step's subtractions and fmas over this step's block.  Wait states inside the block are placed by
 // hand: one (s_nop 0) between v_sqrt_f32 and the v_fma_f32 that reads its result (transcendental
@@ -675,12 +716,16 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
 // per step, no register live across steps.  (The redo of an overflowed unit, cell_slow_unit,
 // classifies with the same float32 operations in C++ and looks at candidates only: a step skipped
 // here is a step without undecided lanes there.  It needs no counterpart of the skip.)
+// The tail in 16.16 fixed point (cell_fixed_q): the 16-bit compare reads the LOW half of q (undecided <=> low half
+// >= tq), v_mad_u32_u16 with op_sel multiplies the HIGH half, the bin, by the byte stride of a bin (4 R) and adds
+// the lane's replica base — five VALU instructions where v_fract_f32, a float compare, the convert and
+// v_lshl_add_u32 made six.  Both halves' selection is checked on the device by scripts/issue_bench.hip.
 #define MDX_CELL_SKIP_TAIL                                                                          \
     "s_cbranch_execz .Lmdx_cell_skip%=\n\t"                                                          \
     "v_sqrt_f32_e32 %[tmp], %[r2]\n\ts_nop 0\n\tv_fma_f32 %[tmp], %[tmp], %[iw], %[p0]\n\t"          \
-    "v_fract_f32_e32 %[t], %[tmp]\n\t"                                                              \
-    "v_cmp_le_f32_e64 %[mt], %[sw], %[t]\n\tv_cvt_i32_f32_e32 %[tmp], %[tmp]\n\t"                   \
-    "s_andn2_b64 exec, exec, %[mt]\n\tv_lshl_add_u32 %[tmp], %[tmp], %[sh], %[hb]\n\t"              \
+    "v_cvt_flr_i32_f32_e32 %[tmp], %[tmp]\n\t"                                                      \
+    "v_cmp_le_u16_e64 %[mt], %[tq], %[tmp]\n\t"                                                     \
+    "s_andn2_b64 exec, exec, %[mt]\n\tv_mad_u32_u16 %[tmp], %[tmp], %[st], %[hb] op_sel:[1,0,0,0]\n\t" \
     "ds_add_u32 %[tmp], %[w]\n"                                                                     \
     ".Lmdx_cell_skip%=:\n\ts_mov_b64 exec, -1"
 template <bool LOWER, int TAGS, int MODE, bool SKIP, typename Hist>
@@ -693,44 +738,42 @@ __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist
     unsigned long long m_todo;
     if (MODE == 0 && SKIP) {
         const unsigned hbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)hist.h;
-        const int hshift = cell_hist_shift(hist) + 2;   // byte offset of a bin = bin << (2 + log2 R)
+        const unsigned hstride = 4u << cell_hist_shift(hist);   // byte offset of a bin = bin * 4 R
         unsigned tmp;
-        float t;
         // the candidate tests of the block below; the LAST one in its VOP3 form, writing the mask register too
         if (LOWER && TAGS)
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_le_f32_e32 %[lo], %[r2]\n\tv_cmpx_ne_u32_e64 %[mt], %[ti], %[tj]\n\t"
                          MDX_CELL_SKIP_TAIL
-                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
-                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w),
-                           [p0] "v"(c.pos0), [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift), [ti] "v"(tag_i), [tj] "v"(tag_j)
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
+                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [tq] "s"(c.tq), [iw] "s"(c.iwq),
+                           [p0] "v"(c.p0q), [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride), [ti] "v"(tag_i), [tj] "v"(tag_j)
                          : "memory");
         else if (LOWER)
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_le_f32_e64 %[mt], %[lo], %[r2]\n\t"
                          MDX_CELL_SKIP_TAIL
-                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
-                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w),
-                           [p0] "v"(c.pos0), [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
+                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [tq] "s"(c.tq), [iw] "s"(c.iwq),
+                           [p0] "v"(c.p0q), [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride)
                          : "memory");
         else if (TAGS)
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_ne_u32_e64 %[mt], %[ti], %[tj]\n\t"
                          MDX_CELL_SKIP_TAIL
-                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
-                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w), [p0] "v"(c.pos0),
-                           [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift), [ti] "v"(tag_i), [tj] "v"(tag_j)
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
+                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [tq] "s"(c.tq), [iw] "s"(c.iwq), [p0] "v"(c.p0q),
+                           [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride), [ti] "v"(tag_i), [tj] "v"(tag_j)
                          : "memory");
         else
             asm volatile("v_cmpx_gt_f32_e64 %[mt], %[hi], %[r2]\n\t"
                          MDX_CELL_SKIP_TAIL
-                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp), [t] "=&v"(t)
-                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [sw] "s"(c.sure_w), [iw] "s"(c.inv_w), [p0] "v"(c.pos0),
-                           [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
+                         : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
+                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [tq] "s"(c.tq), [iw] "s"(c.iwq), [p0] "v"(c.p0q),
+                           [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride)
                          : "memory");
-    } else {
-    // pos = (sqrt(r2) - r0) / width - eta; raw v_sqrt_f32 (a denormal r2 ends on the exact path).
-    // "Farther than eta from both neighbouring bin edges" is fract(pos) < 1 - 2 eta (see cell_filter).
-    const float pos = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.inv_w, c.pos0);
-    const float t = __builtin_amdgcn_fractf(pos);
-    if (MODE == 1) {   // global histogram (bin tables too large for LDS): compiler-generated masks
+    } else if (MODE == 1) {   // global histogram (bin tables too large for LDS): compiler-generated masks
+        // pos = (sqrt(r2) - r0) / width - eta; raw v_sqrt_f32 (a denormal r2 ends on the exact path).
+        // "Farther than eta from both neighbouring bin edges" is fract(pos) < 1 - 2 eta (see cell_filter).
+        const float pos = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.inv_w, c.pos0);
+        const float t = __builtin_amdgcn_fractf(pos);
         bool cand = LOWER ? (r2 < c.cand_hi && r2 >= c.cand_lo) : (r2 < c.cand_hi);
         if (TAGS)
             cand = cand && (tag_i != tag_j);
@@ -745,46 +788,46 @@ __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist
         // the candidate test narrows EXEC itself (v_cmpx), the undecided test is one compare inside
         // it, the sure lanes are what is left, and EXEC is restored once — two scalar instructions.
         // EXEC is all ones here: every call site sits in wave-uniform control flow of full waves.
+        // The bin position is the fixed-point one of the skipping step, formed in front of the block.
         const unsigned hbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned *)hist.h;
-        const int hshift = cell_hist_shift(hist) + 2;   // byte offset of a bin = bin << (2 + log2 R)
+        const unsigned hstride = 4u << cell_hist_shift(hist);   // byte offset of a bin = bin * 4 R
+        // (the convert of cell_fixed_q stands inside the block, behind the candidate tests: as an asm statement of
+        // its own it drew a wait state of the compiler's between the two)
+        const float qf = __fmaf_rn(__builtin_amdgcn_sqrtf(r2), c.iwq, c.p0q);
         unsigned tmp;
+#define MDX_CELL_TAIL                                                                                \
+    "v_cvt_flr_i32_f32_e32 %[tmp], %[qf]\n\tv_cmp_le_u16_e64 %[mt], %[tq], %[tmp]\n\t"                  \
+    "s_andn2_b64 exec, exec, %[mt]\n\tv_mad_u32_u16 %[tmp], %[tmp], %[st], %[hb] op_sel:[1,0,0,0]\n\t" \
+    "ds_add_u32 %[tmp], %[w]\n\ts_mov_b64 exec, -1"
         if (LOWER && TAGS)
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_le_f32_e32 %[lo], %[r2]\n\tv_cmpx_ne_u32_e32 %[ti], %[tj]\n\t"
-                         "v_cmp_le_f32_e64 %[mt], %[sw], %[t]\n\tv_cvt_i32_f32_e32 %[tmp], %[pos]\n\t"
-                         "s_andn2_b64 exec, exec, %[mt]\n\tv_lshl_add_u32 %[tmp], %[tmp], %[sh], %[hb]\n\t"
-                         "ds_add_u32 %[tmp], %[w]\n\ts_mov_b64 exec, -1"
+                         MDX_CELL_TAIL
                          : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
-                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [sw] "s"(c.sure_w), [t] "v"(t),
-                           [pos] "v"(pos), [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift), [ti] "v"(tag_i), [tj] "v"(tag_j)
+                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [tq] "s"(c.tq), [qf] "v"(qf),
+                           [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride), [ti] "v"(tag_i), [tj] "v"(tag_j)
                          : "memory");
         else if (LOWER)
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_le_f32_e32 %[lo], %[r2]\n\t"
-                         "v_cmp_le_f32_e64 %[mt], %[sw], %[t]\n\tv_cvt_i32_f32_e32 %[tmp], %[pos]\n\t"
-                         "s_andn2_b64 exec, exec, %[mt]\n\tv_lshl_add_u32 %[tmp], %[tmp], %[sh], %[hb]\n\t"
-                         "ds_add_u32 %[tmp], %[w]\n\ts_mov_b64 exec, -1"
+                         MDX_CELL_TAIL
                          : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
-                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [sw] "s"(c.sure_w), [t] "v"(t),
-                           [pos] "v"(pos), [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
+                         : [hi] "s"(c.cand_hi), [lo] "s"(c.cand_lo), [r2] "v"(r2), [tq] "s"(c.tq), [qf] "v"(qf),
+                           [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride)
                          : "memory");
         else if (TAGS)
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\tv_cmpx_ne_u32_e32 %[ti], %[tj]\n\t"
-                         "v_cmp_le_f32_e64 %[mt], %[sw], %[t]\n\tv_cvt_i32_f32_e32 %[tmp], %[pos]\n\t"
-                         "s_andn2_b64 exec, exec, %[mt]\n\tv_lshl_add_u32 %[tmp], %[tmp], %[sh], %[hb]\n\t"
-                         "ds_add_u32 %[tmp], %[w]\n\ts_mov_b64 exec, -1"
+                         MDX_CELL_TAIL
                          : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
-                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [sw] "s"(c.sure_w), [t] "v"(t), [pos] "v"(pos),
-                           [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift), [ti] "v"(tag_i), [tj] "v"(tag_j)
+                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [tq] "s"(c.tq), [qf] "v"(qf),
+                           [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride), [ti] "v"(tag_i), [tj] "v"(tag_j)
                          : "memory");
         else
             asm volatile("v_cmpx_gt_f32_e32 %[hi], %[r2]\n\t"
-                         "v_cmp_le_f32_e64 %[mt], %[sw], %[t]\n\tv_cvt_i32_f32_e32 %[tmp], %[pos]\n\t"
-                         "s_andn2_b64 exec, exec, %[mt]\n\tv_lshl_add_u32 %[tmp], %[tmp], %[sh], %[hb]\n\t"
-                         "ds_add_u32 %[tmp], %[w]\n\ts_mov_b64 exec, -1"
+                         MDX_CELL_TAIL
                          : [mt] "=&s"(m_todo), [tmp] "=&v"(tmp)
-                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [sw] "s"(c.sure_w), [t] "v"(t), [pos] "v"(pos),
-                           [hb] "v"(hbase), [w] "v"(w), [sh] "s"(hshift)
+                         : [hi] "s"(c.cand_hi), [r2] "v"(r2), [tq] "s"(c.tq), [qf] "v"(qf),
+                           [hb] "v"(hbase), [w] "v"(w), [st] "s"(hstride)
                          : "memory");
-    }
+#undef MDX_CELL_TAIL
     }
     // An undecided pair is not evaluated here, a lane or two at a time with fp64 temporaries in the
     // middle of the hot loop: it is appended to the wave's list in LDS (slot = list length + rank
@@ -836,7 +879,7 @@ __device__ inline void cell_flush(const CellHot &c, const CellArgs &a, const dou
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     PairCtx<true> cx;
-    cell_exact_ctx(c, a, cx);
+    cell_exact_ctx<CellHistFixed<Hist>::value>(c, a, cx);
     const unsigned lane = threadIdx.x & 63u;
     for (unsigned e0 = 0; e0 < wv.n_todo; e0 += 64u) {
         if (e0 + lane < wv.n_todo) {
@@ -856,7 +899,7 @@ __device__ inline void cell_flush(const CellHot &c, const CellArgs &a, const dou
 // the next step might not fit; sure pairs are skipped (the fast pass has binned them).
 // sJw: the wave's slab of (pre-shifted) j rows [j0, j0 + nj); u_mask: which i halves the fast
 // pass ran; general: per-pair image search.
-template <bool LOWER, bool EXCL, typename Hist>
+template <bool LOWER, bool EXCL, int MODE, typename Hist>
 __device__ inline void cell_slow_unit(const CellHot &c, const CellArgs &a, const double *sT,
                                       const Hist &hist, const float4 *sJw, int j0, int nj,
                                       unsigned u_mask, bool tags, int general, const float *geo,
@@ -879,9 +922,8 @@ __device__ inline void cell_slow_unit(const CellHot &c, const CellArgs &a, const
                 fy = fminf(fabsf(fy), c.L[1] - fabsf(fy));
             if (general & 4)
                 fz = fminf(fabsf(fz), c.L[2] - fabsf(fz));
-            float pos;
             bool cand, sure;
-            cell_filter<LOWER, 0>(c, fx, fy, fz, 0, 0, pos, cand, sure);
+            cell_filter<LOWER, 0, MODE>(c, fx, fy, fz, 0, 0, cand, sure);
             if (EXCL && tags)
                 cand = cand && (__float_as_int(p.w) != __float_as_int(q.w));
             const bool todo = cand && !sure;
@@ -941,8 +983,8 @@ template <bool TRI> __global__ __launch_bounds__(256) void rdf_cell_frame_geo_ke
     g[8] = ctx.cand_hi;
     g[9] = ctx.cand_lo;
     g[10] = ctx.inv_wf;
-    g[11] = -ctx.r0f * ctx.inv_wf - ctx.eta;
-    g[12] = 1.0f - 2.0f * ctx.eta;
+    g[11] = cell_pos0(ctx.r0f, ctx.inv_wf, ctx.eta);
+    g[12] = cell_sure_w(ctx.eta);
 }
 
 // SKIP: the steps of the shifted row loops leave behind their candidate test when no lane holds a candidate
@@ -1145,10 +1187,17 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
     {
         hot.cand_hi = cell_uniform(s_geo[26]);
         hot.cand_lo = cell_uniform(s_geo[27]);
-        hot.inv_w = cell_uniform(s_geo[28]);
-        hot.pos0 = s_geo[29];
-        asm volatile("" : "+v"(hot.pos0));   // stays in a VGPR
-        hot.sure_w = cell_uniform(s_geo[30]);
+        if (MODE == 0) {   // the 16.16 fixed-point forms (cell_fixed_q): exact scalings, so one frame constant serves both
+            hot.iwq = cell_uniform(s_geo[28] * 65536.0f);
+            hot.p0q = s_geo[29] * 65536.0f;
+            asm volatile("" : "+v"(hot.p0q));   // stays in a VGPR
+            hot.tq = __builtin_amdgcn_readfirstlane(cell_fixed_tq(s_geo[30]));
+        } else {
+            hot.inv_w = cell_uniform(s_geo[28]);
+            hot.pos0 = s_geo[29];
+            asm volatile("" : "+v"(hot.pos0));   // stays in a VGPR
+            hot.sure_w = cell_uniform(s_geo[30]);
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             hot.L[k] = cell_uniform(s_geo[k]);
@@ -1479,8 +1528,8 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                                                   ? (unsigned((sub >> s) & 1ull) | (unsigned((sub1 >> s) & 1ull) << 1))
                                                   : (unsigned(rem >> (2 * s)) & 3u);
                         rem &= CELL_CHUNK == 1 ? ~(1ull << s) : ~(3ull << (2 * s));
-                        if (GH) cell_slow_unit<LOWER, EXCL>(hot, a, thr, hg, sJw, CELL_CHUNK * s, CELL_CHUNK, bits, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
-                        else cell_slow_unit<LOWER, EXCL>(hot, a, thr, hl, sJw, CELL_CHUNK * s, CELL_CHUNK, bits, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
+                        if (GH) cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hg, sJw, CELL_CHUNK * s, CELL_CHUNK, bits, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
+                        else cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hl, sJw, CELL_CHUNK * s, CELL_CHUNK, bits, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
                     }
                 }
             } else {
@@ -1526,8 +1575,8 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                 if (__builtin_expect(wv.overflow != 0u, 0)) {
                     wv.overflow = 0u;
                     wv.n_todo = mark;
-                    if (GH) cell_slow_unit<LOWER, EXCL>(hot, a, thr, hg, sJw, 0, 64, 3u, true, gen, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
-                    else cell_slow_unit<LOWER, EXCL>(hot, a, thr, hl, sJw, 0, 64, 3u, true, gen, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
+                    if (GH) cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hg, sJw, 0, 64, 3u, true, gen, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
+                    else cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hl, sJw, 0, 64, 3u, true, gen, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
                 }
             }
             if (wv.n_todo >= 64u) {   // enough undecided pairs for a full-width exact pass

@@ -45,6 +45,41 @@ struct RdfArgs {
     int chunk, self, frame0;
 };
 
+// The float32 filter's constants of one frame: Lmax the longest cell length (0 without a cell), M the largest
+// |coordinate| of the batch.  Host and device: the pair kernels take them from PairCtx::init, and
+// mdx_rdf_filter_constants reports them without a device.
+struct RdfFilterConst {
+    float r0f, inv_wf;       // bin estimate: (d - r0) * inv_w
+    float cand_hi, cand_lo;  // candidate window on the float32 squared distance
+    float eta;               // edge proximity (in bin units) that forces the exact path
+};
+__host__ __device__ inline RdfFilterConst rdf_filter_const(double Lmax, double M, double r0, double r1, int n_bins)
+{
+    RdfFilterConst f;
+    // per-component bound on |w_contract - w_float32|, safety included
+    const double delta = 0x1p-22 * (2.0 * M + Lmax);
+    const double width = (r1 - r0) / n_bins;
+    const double margin_d = 1.7320508075688772 * delta + r1 * 0x1p-21;
+    f.r0f = (float)r0;
+    f.inv_wf = (float)(1.0 / width);
+    // Bin-coordinate budget.  Q = r1 / width is the largest magnitude the
+    // float32 bin arithmetic handles (n_bins only when r0 = 0).  Per unit of Q:
+    //   <= 0.625 * 2^-21  evaluating pos in float32 (sqrt 1 ulp, fma, 1/width, -r0/width),
+    //   <= 1.07  * 2^-21  how far the candidate window reaches past r1 + margin (and below
+    //                     r0 - margin) because of its own (1 +- 2^-20) safety factor,
+    // so Q * 2^-20 covers both at once: a candidate beyond either range end is never "sure".
+    const double Q = r1 / width;
+    double e = margin_d / width + Q * 0x1p-20 + 0x1p-20;
+    f.eta = (float)fmin(e, 1.0);
+    double hi = (r1 + margin_d);
+    f.cand_hi = (float)(hi * hi * (1.0 + 0x1p-20));
+    double lo = r0 - margin_d;
+    f.cand_lo = lo > 0.0 ? (float)(lo * lo * (1.0 - 0x1p-20)) : -1.0f;
+    if (!(M < 3.0e38))   // inf/NaN coordinates: everything goes to the exact path
+        f.eta = 1.0f;
+    return f;
+}
+
 template <bool PBC> struct PairCtx {
     // contract constants
     double Ld[3], invd[3];
@@ -76,29 +111,13 @@ template <bool PBC> struct PairCtx {
                 Lmax = fmax(Lmax, Ld[k]);
             }
         }
-        const double M = (double)__uint_as_float(*maxabs_bits);
-        // per-component bound on |w_contract - w_float32|, safety included
-        const double delta = 0x1p-22 * (2.0 * M + Lmax);
-        const double width = (r1 - r0) / n_bins;
-        const double margin_d = 1.7320508075688772 * delta + r1 * 0x1p-21;
-        r0f = (float)r0;
-        inv_wf = (float)(1.0 / width);
-        // Bin-coordinate budget.  Q = r1 / width is the largest magnitude the
-        // float32 bin arithmetic handles (n_bins only when r0 = 0).  Per unit of Q:
-        //   <= 0.625 * 2^-21  evaluating pos in float32 (sqrt 1 ulp, fma, 1/width, -r0/width),
-        //   <= 1.07  * 2^-21  how far the candidate window reaches past r1 + margin (and below
-        //                     r0 - margin) because of its own (1 +- 2^-20) safety factor,
-        // so Q * 2^-20 covers both at once: a candidate beyond either range end is never "sure".
-        const double Q = r1 / width;
-        double e = margin_d / width + Q * 0x1p-20 + 0x1p-20;
-        eta = (float)fmin(e, 1.0);
+        const RdfFilterConst f = rdf_filter_const(Lmax, (double)__uint_as_float(*maxabs_bits), r0, r1, n_bins);
+        r0f = f.r0f;
+        inv_wf = f.inv_wf;
+        eta = f.eta;
         posmax = (float)n_bins - eta;
-        double hi = (r1 + margin_d);
-        cand_hi = (float)(hi * hi * (1.0 + 0x1p-20));
-        double lo = r0 - margin_d;
-        cand_lo = lo > 0.0 ? (float)(lo * lo * (1.0 - 0x1p-20)) : -1.0f;
-        if (!(M < 3.0e38))   // inf/NaN coordinates: everything goes to the exact path
-            eta = 1.0f;
+        cand_hi = f.cand_hi;
+        cand_lo = f.cand_lo;
     }
 };
 

@@ -10,9 +10,16 @@
 //   * the price of what a trip issues AROUND the step (round 8), at the pair kernel's seven waves per SIMD: the
 //     skip step with no empty step, then with 1, 2, 4 and 8 independent s_add_i32 spread through it, with a
 //     compare and a not-taken s_cbranch_scc0 behind it, and with one and two more VALU instructions.
+//   * the skip step with the bin position in 16.16 fixed point (round 17): v_cvt_flr_i32_f32, a 16-bit compare on
+//     the low half and v_mad_u32_u16 on the high half instead of v_fract_f32, v_cmp_f32, v_cvt_i32_f32 and the
+//     shift — 12 VALU where there were 13 — after a check that the fixed-point value, the mask and the address
+//     come out as the C++ restatement says.
 // hipcc -O2 --offload-arch=gfx950 scripts/issue_bench.hip -o /tmp/issue_bench
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #define REP16(x) x x x x x x x x x x x x x x x x
 typedef float v2f __attribute__((ext_vector_type(2)));
 // One step with the skip, as cell_step<..., SKIP> writes it: lanes whose r2 is below `hi` are candidates.
@@ -29,9 +36,33 @@ __global__ void skip_check(const float *r2_in, float hi, unsigned long long *mas
     pos[threadIdx.x] = tmp;
     if (threadIdx.x == 0) *mask = m;
 }
+// One step with the fixed-point tail, as cell_step<..., SKIP> writes it from round 17 on (without the narrowing of
+// EXEC to the sure lanes, so that the address of every candidate lane can be looked at).
+__global__ void fixed_check(const float *r2_in, float hi, float iwq, float p0q, unsigned tq, unsigned stride,
+                            unsigned hb, unsigned long long *mask, float *root, unsigned *q_out, unsigned *ad_out)
+{
+    const float r2 = r2_in[threadIdx.x];
+    unsigned long long m;
+    float s = -7.f;
+    unsigned q = 0xdeadbeefu, ad = 0xdeadbeefu;
+    asm volatile("v_cmpx_gt_f32_e64 %[mt], %[hi], %[r2]\n\ts_cbranch_execz .Lfixed_check%=\n\t"
+                 "v_sqrt_f32_e32 %[s], %[r2]\n\ts_nop 0\n\tv_fma_f32 %[q], %[s], %[iw], %[p0]\n\t"
+                 "v_cvt_flr_i32_f32_e32 %[q], %[q]\n\t"
+                 "v_cmp_le_u16_e64 %[mt], %[tq], %[q]\n\t"
+                 "v_mad_u32_u16 %[ad], %[q], %[st], %[hb] op_sel:[1,0,0,0]\n"
+                 ".Lfixed_check%=:\n\ts_mov_b64 exec, -1"
+                 : [mt] "=&s"(m), [s] "+v"(s), [q] "+v"(q), [ad] "+v"(ad)
+                 : [hi] "s"(hi), [r2] "v"(r2), [iw] "s"(iwq), [p0] "v"(p0q), [tq] "s"(tq), [st] "s"(stride), [hb] "v"(hb)
+                 : "memory");
+    root[threadIdx.x] = s;
+    q_out[threadIdx.x] = q;
+    ad_out[threadIdx.x] = ad;
+    if (threadIdx.x == 0) *mask = m;
+}
 // MODE 9: the skip step of MODE 8 with EMPTY reused as the extra scalar work per step: 0, 1, 2, 4 = that many
 // s_add_i32 (8 as well, for a longer lever); 100 = s_cmp_eq_u32 (SCC = 1) + s_cbranch_scc0 that is never taken;
 // 201, 202 = one, two extra VALU instructions (v_max_f32 of a register with itself), the other yardstick.
+// MODE 10: the skip step of MODE 8 (bit k of EMPTY = step k has no candidate) with the fixed-point tail: 12 VALU.
 template <int MODE, unsigned EMPTY = 0u>
 __global__ void kern(float *out, long long *clk, int iters)
 {
@@ -93,6 +124,27 @@ __global__ void kern(float *out, long long *clk, int iters)
                              ".Lbench_skip%=:\n s_mov_b64 exec, -1\n"
                              : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
                              : "v"(b), "v"(c), "s"(((EMPTY >> k) & 1u) ? fail : pass) : "vcc");
+        } else if (MODE == 10 || MODE == 14 || MODE == 15) {
+            // 10: the fixed-point tail (12 VALU).  Its two yardsticks: 14, the bare tail of MODE 9 without its
+            // v_fract_f32 (12 plain VALU: what a removed instruction is worth), and 15, the bare tail with the pair
+            // kernel's own three-operand v_lshl_add_u32 where MODE 9 has v_lshlrev_b32 (13 VALU: what the kernel
+            // issued, the row the fixed-point tail has to beat).
+            const float pass = 3e38f, fail = -1.f;
+#define MDX_B10_STEP(TAIL)                                                                                           \
+    asm volatile("v_sub_f32 %0, %0, %8\n v_sub_f32 %1, %1, %8\n v_sub_f32 %2, %2, %8\n v_mul_f32 %3, %0, %0\n"           \
+                 "v_fma_f32 %3, %1, %1, %3\n v_fma_f32 %3, %2, %2, %3\n v_cmpx_gt_f32_e64 vcc, %10, %3\n"                 \
+                 "s_cbranch_execz .Lbench10_skip%=\n v_sqrt_f32 %4, %3\n s_nop 0\n v_fma_f32 %4, %4, %8, %9\n" TAIL       \
+                 ".Lbench10_skip%=:\n s_mov_b64 exec, -1\n"                                                            \
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)                       \
+                 : "v"(b), "v"(c), "s"(((EMPTY >> k) & 1u) ? fail : pass), "s"(s1), "s"(s2)                             \
+                 : "vcc")
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+                if (MODE == 10) MDX_B10_STEP("v_cvt_flr_i32_f32 %5, %4\n v_cmp_le_u16_e64 vcc, %11, %5\n v_mad_u32_u16 %7, %5, %12, %6 op_sel:[1,0,0,0]\n");
+                else if (MODE == 14) MDX_B10_STEP("v_cmp_gt_f32 vcc, %4, %9\n v_cvt_i32_f32 %6, %4\n v_lshlrev_b32 %7, 2, %6\n");
+                else MDX_B10_STEP("v_fract_f32 %5, %4\n v_cmp_gt_f32 vcc, %5, %9\n v_cvt_i32_f32 %6, %4\n v_lshl_add_u32 %7, %6, %12, %0\n");
+            }
+#undef MDX_B10_STEP
         } else if (MODE == 9) {
             // (operands %8 and %9 are b and c in MODE 8; here the four scalar counters sit at %8..%11, so the
             // strings below are written with their own numbering: b = %12, c = %13, pass = %14)
@@ -208,8 +260,73 @@ static bool check_skip()
     hipFree(r2); hipFree(pos); hipFree(mask);
     return ok;
 }
-int main()
+// The fixed-point tail against its C++ restatement: q = floor(sqrt(r2) * IWQ + P0Q) as a 32-bit integer, undecided
+// <=> low16(q) >= TQ, address = high16(q) * stride + base (all modulo 2^32).  inv_w = 1, pos0 = -0.25, sure_w = 0.5.
+static bool check_fixed()
 {
+    float *r2, *root, h_r2[64], h_root[64];
+    unsigned *q, *ad, h_q[64], h_ad[64];
+    unsigned long long *mask, h_mask;
+    hipMalloc(&r2, 256); hipMalloc(&root, 256); hipMalloc(&q, 256); hipMalloc(&ad, 256); hipMalloc(&mask, 8);
+    const float iwq = 65536.f, p0q = -0.25f * 65536.f;
+    const unsigned tq = 32768u, stride = 12u, hb = 0x1230u;
+    bool ok = true;
+    const char *names[5] = {"every lane sure", "every lane undecided", "no candidate (step skipped)",
+                            "odd lanes candidates", "negative positions"};
+    for (int variant = 0; variant < 5; ++variant) {
+        for (int l = 0; l < 64; ++l) {
+            float r = 2.5f + float(l);                          // position l + 2.25: sure, bin l + 2
+            if (variant == 1) r = 2.f + float(l);               // position l + 1.75: undecided
+            if (variant == 3) r = (l & 2) ? 2.f + float(l) : 2.5f + float(l);
+            if (variant == 4) r = float(l) * (1.f / 256.f);     // positions -0.25 ... -0.004: undecided, high half all ones
+            h_r2[l] = r * r;                                    // the candidate test is r2 < 5000
+            if (variant == 2 || (variant == 3 && !(l & 1))) h_r2[l] = 1e4f;
+        }
+        hipMemcpy(r2, h_r2, 256, hipMemcpyHostToDevice);
+        fixed_check<<<1, 64>>>(r2, 5000.f, iwq, p0q, tq, stride, hb, mask, root, q, ad);
+        hipMemcpy(&h_mask, mask, 8, hipMemcpyDeviceToHost);
+        hipMemcpy(h_root, root, 256, hipMemcpyDeviceToHost);
+        hipMemcpy(h_q, q, 256, hipMemcpyDeviceToHost);
+        hipMemcpy(h_ad, ad, 256, hipMemcpyDeviceToHost);
+        unsigned long long want = 0;
+        bool good = true;
+        for (int l = 0; l < 64; ++l) {
+            if (!(h_r2[l] < 5000.f)) {   // not a candidate: nothing written
+                good = good && h_root[l] == -7.f && h_q[l] == 0xdeadbeefu && h_ad[l] == 0xdeadbeefu;
+                continue;
+            }
+            const unsigned wq = unsigned(int(floorf(fmaf(h_root[l], iwq, p0q))));
+            if ((wq & 0xffffu) >= tq) want |= 1ull << l;
+            good = good && h_q[l] == wq && h_ad[l] == (wq >> 16) * stride + hb && h_root[l] >= 0.f;
+            if (variant == 4) good = good && (wq >> 16) == 0xffffu;
+            if (variant == 0) good = good && (wq >> 16) == unsigned(l + 2);
+        }
+        good = good && h_mask == want;
+        if (variant == 0) good = good && want == 0ull;
+        if (variant == 1 || variant == 4) good = good && want == ~0ull;
+        printf("fixed-point check, %s: mask %016llx (want %016llx) %s\n", names[variant], h_mask, want, good ? "ok" : "WRONG");
+        ok = ok && good;
+    }
+    hipFree(r2); hipFree(root); hipFree(q); hipFree(ad); hipFree(mask);
+    return ok;
+}
+int main(int argc, char **argv)
+{
+    const bool fixed_only = argc > 1 && !strcmp(argv[1], "--fixed");   // the round-17 rows alone
+    if (fixed_only) {
+        if (!check_fixed()) return 1;
+        const int passes = argc > 2 ? atoi(argv[2]) : 3;
+        for (int pass = 0; pass < passes; ++pass) {
+            run7<9, 0u>("skip step bare", 13, 2);
+            run7<10, 0u>("skip step fixed-point", 12, 2);
+            run7<8, 0x04082082u>("skip step, 5/32 empty", 13, 2);
+            run7<10, 0x04082082u>("skip step fixed-point, 5/32", 12, 2);
+            run7<14, 0u>("bare without v_fract_f32", 12, 2);
+            run7<15, 0u>("bare, v_lshl_add_u32", 13, 2);
+            run7<15, 0x04082082u>("bare, v_lshl_add_u32, 5/32", 13, 2);
+        }
+        return 0;
+    }
     run<0>("8 v_fma_f32", 8, 0);
     run<1>("8 SALU", 0, 8);
     run<2>("8 v_fma_f32 + 8 SALU", 8, 8);
@@ -219,6 +336,7 @@ int main()
     run<6>("4 pk_add + 4 pk_mul f32", 8, 0);
     run<7>("4 v_sub_u32+4 cvt_f32_i32", 8, 0);
     if (!check_skip()) return 1;
+    if (!check_fixed()) return 1;
     run<8, 0u>("skip step, 0/32 empty", 13, 1, 32);
     run<8, 0x04082082u>("skip step, 5/32 empty", 13, 1, 32);
     run<8, ~0u>("skip step, 32/32 empty", 13, 1, 32);
@@ -232,6 +350,9 @@ int main()
         run7<9, 100u>("skip step + s_cmp + s_cbranch", 13, 4);
         run7<9, 201u>("skip step + 1 VALU", 14, 2);
         run7<9, 202u>("skip step + 2 VALU", 15, 2);
+        run7<10, 0u>("skip step fixed-point", 12, 2);
+        run7<8, 0x04082082u>("skip step, 5/32 empty", 13, 2);
+        run7<10, 0x04082082u>("skip step fixed-point, 5/32", 12, 2);
     }
     return 0;
 }
