@@ -89,6 +89,15 @@ __host__ __device__ constexpr int cell_geo_slot(int word) { return word < 8 ? wo
 constexpr int CELL_CHUNK = 1;     // particles per j chunk of the second-level cull (1, 2, 4, 8, 16)
 constexpr int CELL_NCHUNK = 64 / CELL_CHUNK;
 constexpr int CELL_TODO = 128;    // per-wave list of pairs waiting for the exact arithmetic
+// The diagonal of a self histogram, every pair once (pair kernel): rotation steps k = 0 .. 32 of a 64-particle half
+// against itself.  The scheme applies to an i tile whose 128-particle box (half extents hI) is small against the
+// frame's box L: the centre of either half lies inside the tile's box, so a diagonal visit's reach |d| + hI + hJ is
+// at most 3 hI, below 0.4999 L — image shift 0 and no per-pair image search in BOTH visits, which therefore agree.
+constexpr unsigned CELL_DIAG_ROT_STEPS = 33;
+__host__ __device__ inline bool cell_diag_once(const float *hI, const float *L)
+{
+    return 3.0f * hI[0] < 0.4999f * L[0] && 3.0f * hI[1] < 0.4999f * L[1] && 3.0f * hI[2] < 0.4999f * L[2];
+}
 // Per-wave LDS histogram: n_bins bins and one slot that absorbs a (proven impossible)
 // index n_bins instead of letting it alias the next histogram's bin 0.
 __host__ __device__ constexpr int cell_hist_stride(int n_bins) { return n_bins + 1; }
@@ -728,7 +737,9 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
     "s_andn2_b64 exec, exec, %[mt]\n\tv_mad_u32_u16 %[tmp], %[tmp], %[st], %[hb] op_sel:[1,0,0,0]\n\t" \
     "ds_add_u32 %[tmp], %[w]\n"                                                                     \
     ".Lmdx_cell_skip%=:\n\ts_mov_b64 exec, -1"
-template <bool LOWER, int TAGS, int MODE, bool SKIP, typename Hist>
+// ROT: a rotated step of a diagonal tile (CELL_DIAG_ROT_STEPS): lane l met slab row (l + j_row + j_off) & 63, and
+// that is the row an undecided pair is listed under — formed behind the append branch like the rest of the entry.
+template <bool LOWER, int TAGS, int MODE, bool SKIP, bool ROT = false, typename Hist>
 __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist &hist, float fx,
                                  float fy, float fz, int tag_i, int tag_j, unsigned i_base,
                                  unsigned i_half, unsigned j_base, unsigned j_row, unsigned j_off,
@@ -853,7 +864,8 @@ __device__ inline void cell_step(const CellHot &c, const CellArgs &a, const Hist
             const unsigned addr =
                 (unsigned)(size_t)(__attribute__((address_space(3))) uint2 *)wv.todo + slot * 8u;
             // i index = (wave-uniform base of the half tile) + lane; j index carries the weight flag (bit 31)
-            const uint2 e = make_uint2((i_base + 64u * i_half) | (threadIdx.x & 63u), j_base + row);
+            const unsigned j_idx = j_base + (ROT ? ((threadIdx.x + row) & 63u) : row);
+            const uint2 e = make_uint2((i_base + 64u * i_half) | (threadIdx.x & 63u), j_idx);
             const unsigned long long ev = (unsigned long long)e.x | ((unsigned long long)e.y << 32);
             asm volatile("s_mov_b64 exec, %[m]\n\tds_write_b64 %[ad], %[ev]\n\ts_mov_b64 exec, -1"
                          :
@@ -1413,13 +1425,55 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
             asm volatile("" : "+v"(w));   // the add's data operand: one VGPR per tile, not a v_mov per step
             // bit 31 of every j index handed on = (weight - 1): formed here on the scalar unit, once per tile
             // (derived from `w`, which is pinned in a vector register, it was a v_or per chunk)
-            const unsigned jbase = unsigned(Jt) * 64u | ((a.self && !diag) ? 0x80000000u : 0u);
+            unsigned jbase = unsigned(Jt) * 64u | ((a.self && !diag) ? 0x80000000u : 0u);
             // exclusion tags can only collide inside the diagonal tiles when exclusion == (1, 1)
             const bool tags = EXCL && (a.tags_everywhere || diag);
             if (!gen) {
                 // The surviving (chunk, half) units of this tile.  Bookkeeping is per tile, not per
                 // unit: one roll-back mark, one overflow test, one popcount for the statistics.
                 const unsigned mark = wv.n_todo;
+                // The two diagonal visits of an i tile (halves a = tile 2 I and b = tile 2 I + 1), every pair once
+                // (DESIGN.md §4, row a-1): a half against itself by rotation — in step k lane l meets row (l + k) & 63 of
+                // its own tile; k = 1..31 reach every unordered pair once (weight 2), k = 32 reaches each from both
+                // sides and k = 0 is the pair (l, l) (weight 1) — and a x b in visit 2 I alone, at weight 2, by
+                // the row loops below.  Both visits decide from the i tile's own box (cell_diag_once): they usually
+                // run in different items, on different waves.
+                // (re-derived by the redo below: a flag carried across the row loops is a scalar register they lack)
+#define MDX_CELL_DIAG_ONCE()                                                                       \
+    (CELL_CHUNK == 1 && !TRI && diag &&                                                            \
+     __builtin_amdgcn_readfirstlane(unsigned(cell_diag_once(s_geo + 11, s_geo))) != 0u)
+                if (MDX_CELL_DIAG_ONCE()) {
+                    const unsigned second = unsigned(Jt) & 1u;   // visit 2 I + 1: half b, and nothing else
+                    float4 P = p0;
+                    if (second)
+                        P = p1;
+                    asm volatile("" : "+v"(P.x), "+v"(P.y), "+v"(P.z), "+v"(P.w));
+                    // k = 0 at weight 1, k = 1 .. 31 at weight 2, k = 32 at weight 1: the weight and the entry's
+                    // weight flag change between the three runs, nothing per step
+#pragma unroll 1
+                    for (unsigned ph = 0u; ph < 3u; ++ph) {
+                        w = ph == 1u ? 2u : 1u;
+                        asm volatile("" : "+v"(w));
+                        const unsigned jb = unsigned(Jt) * 64u | (ph == 1u ? 0x80000000u : 0u);
+                        const unsigned k1 = ph == 0u ? 1u : ph == 1u ? CELL_DIAG_ROT_STEPS - 1u : CELL_DIAG_ROT_STEPS;
+#pragma unroll 1
+                        for (unsigned k = ph == 0u ? 0u : ph == 1u ? 1u : CELL_DIAG_ROT_STEPS - 1u; k < k1; ++k) {
+                            const float4 q = sJw[(unsigned(lane) + k) & 63u];
+                            asm volatile("" ::"v"(q.w));   // whole 16-byte read
+                            if (GH) cell_step<LOWER, EXCL ? 1 : 0, MODE, false, true>(hot, a, hg, q.x - P.x, q.y - P.y, q.z - P.z, __float_as_int(P.w), __float_as_int(q.w), i_base0, second, jb, k, 0u, w, wv);
+                            else cell_step<LOWER, EXCL ? 1 : 0, MODE, false, true>(hot, a, hl, q.x - P.x, q.y - P.y, q.z - P.z, __float_as_int(P.w), __float_as_int(q.w), i_base0, second, jb, k, 0u, w, wv);
+                        }
+                    }
+                    n_units += CELL_DIAG_ROT_STEPS;
+                    // what is left for the row loops: in visit 2 I the rows of a within reach of b's box, against
+                    // p1, at weight 2
+                    sub = 0ull;
+                    if (second)
+                        sub1 = 0ull;
+                    w = 2u;
+                    asm volatile("" : "+v"(w));
+                    jbase |= 0x80000000u;
+                }
                 n_units += (unsigned)__popcll(sub) + (CELL_CHUNK == 1 ? (unsigned)__popcll(sub1) : 0u);
 // (H: the i half, R: the slab row of the turn, O: the row's offset in the turn — the pieces of the indices an
 // undecided pair is listed under; cell_step puts them together where it lists one)
@@ -1522,6 +1576,14 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                     // mark, then every unit again, undecided pairs only, flushing as needed
                     wv.overflow = 0u;
                     wv.n_todo = mark;
+                    if (MDX_CELL_DIAG_ONCE()) {
+                        // the rotated steps in the old order: the visit's own half against all 64 rows at weight 1
+                        // (both orders at 1 are one order at 2; k = 0 and k = 32 come out the same); the a x b rows
+                        // of visit 2 I follow below, at the weight they had
+                        const unsigned own = 1u << (unsigned(Jt) & 1u);
+                        if (GH) cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hg, sJw, 0, 64, own, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, unsigned(Jt) * 64u, 1u, wv);
+                        else cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hl, sJw, 0, 64, own, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, unsigned(Jt) * 64u, 1u, wv);
+                    }
                     for (unsigned long long rem = CELL_CHUNK == 1 ? (sub | sub1) : sub; rem;) {
                         const int s = CELL_CHUNK == 1 ? __builtin_ctzll(rem) : (__builtin_ctzll(rem) >> 1);
                         const unsigned bits = CELL_CHUNK == 1
@@ -1532,6 +1594,7 @@ __global__ __launch_bounds__(256, TRI ? 4 : 7) void rdf_cell_pair_kernel(CellArg
                         else cell_slow_unit<LOWER, EXCL, MODE>(hot, a, thr, hl, sJw, CELL_CHUNK * s, CELL_CHUNK, bits, tags, 0, s_geo, p0, p1, MDX_PO1F(), MDX_PO2(), i_idx0, jbase, w, wv);
                     }
                 }
+#undef MDX_CELL_DIAG_ONCE
             } else {
                 // Tile pair that straddles half a box in the components of `gen`: those components take the
                 // per-pair minimum image, as a magnitude (only the square is used): with both coordinates

@@ -188,19 +188,27 @@ def item_model():
         g = np.maximum(0.0, np.abs(d) - 0.5 * (hi - lo) - half)
         return (g * g).sum(-1)
 
-    visits_per_item, trips_of_visits = [], []
+    visits_per_item, trips_of_visits, trips_old = [], [], 0
     for I in range(N // 128):
         i0, i1 = T[2 * I], T[2 * I + 1]
         lo, hi = np.minimum(tlo[2 * I], tlo[2 * I + 1]), np.maximum(thi[2 * I], thi[2 * I + 1])
         J = np.arange(2 * I, N // 64)
         J = J[box_gap2(lo, hi, 0.5 * (tlo[J] + thi[J]), 0.5 * (thi[J] - tlo[J])) <= R * R]
         rows = T[J]                                                        # [visits, 64, 3]
-        t = (box_gap2(i0.min(0), i0.max(0), rows, 0.0) <= R * R).sum(1) \
-            + (box_gap2(i1.min(0), i1.max(0), rows, 0.0) <= R * R).sum(1)
+        t0 = (box_gap2(i0.min(0), i0.max(0), rows, 0.0) <= R * R).sum(1)
+        t1 = (box_gap2(i1.min(0), i1.max(0), rows, 0.0) <= R * R).sum(1)
+        t = t0 + t1
+        trips_old += t.sum()
+        # the diagonal, every pair once (round 18; the tile's half extents are far below L / 6 here): visit 2 I is 33
+        # rotated steps of half a and the rows of a within R of b's box, visit 2 I + 1 the 33 rotated steps of half b
+        assert J[0] == 2 * I and J[1] == 2 * I + 1 and np.all(3.0 * 0.5 * (hi - lo) < 0.4999 * L)
+        t[0], t[1] = 33 + t1[0], 33
         visits_per_item.append(len(J))
         trips_of_visits.append(t)
     allt = np.concatenate(trips_of_visits)
     print("--- the four waves of a block around an item (one frame, 256 items)")
+    print(f"trips per frame with both diagonal visits in full {trips_old:.7g}, every diagonal pair once {allt.sum():.7g} "
+          f"({trips_old - allt.sum():.0f} fewer, {1.0 - allt.sum() / trips_old:.4f})")
     print(f"trips per frame {allt.sum():.4g}; visits per item {np.mean(visits_per_item):.1f} "
           f"(max {max(visits_per_item)}); trips per visit {allt.mean():.1f}")
     print(f"visits with no trip: {(allt == 0).mean():.3f}; with at most 8 trips: {(allt <= 8).mean():.3f}, "

@@ -14,6 +14,9 @@
 //     the low half and v_mad_u32_u16 on the high half instead of v_fract_f32, v_cmp_f32, v_cvt_i32_f32 and the
 //     shift — 12 VALU where there were 13 — after a check that the fixed-point value, the mask and the address
 //     come out as the C++ restatement says.
+//   * the fixed-point skip step fed from an LDS slab (round 18, `--rot`): a broadcast row as in the row loops against
+//     the rotated row of a diagonal tile's steps (lane l reads row (l + k) & 63, by index and by a running byte
+//     offset) — after a check that every lane got that row.
 // hipcc -O2 --offload-arch=gfx950 scripts/issue_bench.hip -o /tmp/issue_bench
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -59,6 +62,24 @@ __global__ void fixed_check(const float *r2_in, float hi, float iwq, float p0q, 
     ad_out[threadIdx.x] = ad;
     if (threadIdx.x == 0) *mask = m;
 }
+// The rows the rotated steps of a diagonal tile read (round 18): in step k lane l takes row (l + k) & 63 of its wave's
+// slab — by the index the pair kernel forms (way 0) and by the running byte offset of MODE 18 (way 1).  Row r of wave
+// v holds 64 v + r.
+__global__ void rot_check(unsigned *rows, int way)
+{
+    __shared__ float4 slab[256];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    slab[threadIdx.x] = make_float4(0.f, 0.f, 0.f, float(threadIdx.x));
+    __syncthreads();
+    const float4 *sw = slab + wave * 64;
+    unsigned off = lane * 16u;
+    for (unsigned k = 0; k < 33u; ++k) {
+        const float4 q = way == 0 ? sw[(lane + k) & 63u]
+                                  : *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sw) + off);
+        off = (off + 16u) & 1023u;
+        rows[(wave * 33u + k) * 64u + lane] = unsigned(q.w);
+    }
+}
 // MODE 9: the skip step of MODE 8 with EMPTY reused as the extra scalar work per step: 0, 1, 2, 4 = that many
 // s_add_i32 (8 as well, for a longer lever); 100 = s_cmp_eq_u32 (SCC = 1) + s_cbranch_scc0 that is never taken;
 // 201, 202 = one, two extra VALU instructions (v_max_f32 of a register with itself), the other yardstick.
@@ -71,6 +92,13 @@ __global__ void kern(float *out, long long *clk, int iters)
     v2f p0 = {a0, a1}, p1 = {a2, a3}, p2 = {a4, a5}, p3 = {a6, a7}, p4 = p0 + 1.f, p5 = p1 + 1.f, p6 = p2 + 1.f, p7 = p3 + 1.f;
     v2f pb = {b, b}, pc = {c, c};
     unsigned s0 = blockIdx.x, s1 = 1, s2 = 2, s3 = 3;
+    // MODEs 16 - 18: a slab of 64 rows per wave of a 256-thread block (run7)
+    __shared__ float4 rot_slab[(MODE >= 16 && MODE <= 18) ? 256 : 1];
+    if (MODE >= 16 && MODE <= 18) {
+        if (threadIdx.x < 256)
+            rot_slab[threadIdx.x] = make_float4(1.f + float(threadIdx.x & 63u), 2.f, 3.f, float(threadIdx.x & 63u));
+        __syncthreads();
+    }
     const long long t0 = clock64(), w0 = wall_clock64();
     for (int i = 0; i < iters; ++i) {
         if (MODE == 0) {   // 8 independent v_fma_f32
@@ -145,6 +173,39 @@ __global__ void kern(float *out, long long *clk, int iters)
                 else MDX_B10_STEP("v_fract_f32 %5, %4\n v_cmp_gt_f32 vcc, %5, %9\n v_cvt_i32_f32 %6, %4\n v_lshl_add_u32 %7, %6, %12, %0\n");
             }
 #undef MDX_B10_STEP
+        } else if (MODE == 16 || MODE == 17 || MODE == 18) {
+            // The fixed-point skipping step of MODE 10 fed from a wave-private LDS slab of 64 rows, as the pair kernel
+            // feeds it (round 18).  16: the row loops' read — every lane the same row (a broadcast), the address a
+            // scalar moved into a vector register; the yardstick.  17: the rotated step of a diagonal tile — lane l
+            // reads row (l + k) & 63: v_add_u32, v_and_b32, v_lshl_add_u32 in front of the read.  18: the same rows
+            // through a running byte offset, off = (off + 16) & 1023, added to the slab's base.
+            const float pass = 3e38f;
+            const unsigned lane = threadIdx.x & 63u;
+            float4 *sw = rot_slab + (threadIdx.x >> 6) * 64;
+            unsigned kbase = (unsigned(i) * 32u) & 63u;
+            asm volatile("" : "+s"(kbase));
+            unsigned off = (lane * 16u + kbase * 16u) & 1023u;
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+                float4 q;
+                if (MODE == 16) {
+                    q = sw[(kbase + unsigned(k)) & 63u];
+                } else if (MODE == 17) {
+                    q = sw[(lane + kbase + unsigned(k)) & 63u];
+                } else {
+                    q = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sw) + off);
+                    off = (off + 16u) & 1023u;
+                }
+                asm volatile("" ::"v"(q.w));   // whole 16-byte read
+                asm volatile("v_sub_f32 %0, %13, %8\n v_sub_f32 %1, %14, %8\n v_sub_f32 %2, %15, %8\n v_mul_f32 %3, %0, %0\n"
+                             "v_fma_f32 %3, %1, %1, %3\n v_fma_f32 %3, %2, %2, %3\n v_cmpx_gt_f32_e64 vcc, %10, %3\n"
+                             "s_cbranch_execz .Lbench16_skip%=\n v_sqrt_f32 %4, %3\n s_nop 0\n v_fma_f32 %4, %4, %8, %9\n"
+                             "v_cvt_flr_i32_f32 %5, %4\n v_cmp_le_u16_e64 vcc, %11, %5\n v_mad_u32_u16 %7, %5, %12, %6 op_sel:[1,0,0,0]\n"
+                             ".Lbench16_skip%=:\n s_mov_b64 exec, -1\n"
+                             : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
+                             : "v"(b), "v"(c), "s"(pass), "s"(s1), "s"(s2), "v"(q.x), "v"(q.y), "v"(q.z)
+                             : "vcc");
+            }
         } else if (MODE == 9) {
             // (operands %8 and %9 are b and c in MODE 8; here the four scalar counters sit at %8..%11, so the
             // strings below are written with their own numbering: b = %12, c = %13, pass = %14)
@@ -310,9 +371,43 @@ static bool check_fixed()
     hipFree(r2); hipFree(root); hipFree(q); hipFree(ad); hipFree(mask);
     return ok;
 }
+// Every lane of every wave got row (lane + k) & 63 of its own slab in step k = 0 .. 32, either way.
+static bool check_rot()
+{
+    unsigned *rows, h[4 * 33 * 64];
+    hipMalloc(&rows, sizeof h);
+    bool ok = true;
+    for (int way = 0; way < 2; ++way) {
+        hipMemset(rows, 0xff, sizeof h);
+        rot_check<<<1, 256>>>(rows, way);
+        hipMemcpy(h, rows, sizeof h, hipMemcpyDeviceToHost);
+        int wrong = 0;
+        for (unsigned wave = 0; wave < 4; ++wave)
+            for (unsigned k = 0; k < 33; ++k)
+                for (unsigned lane = 0; lane < 64; ++lane)
+                    wrong += h[(wave * 33 + k) * 64 + lane] != 64 * wave + ((lane + k) & 63u);
+        printf("rotation check, %s: %d of %d rows wrong %s\n", way ? "running byte offset" : "index (lane + k) & 63", wrong,
+               4 * 33 * 64, wrong ? "WRONG" : "ok");
+        ok = ok && !wrong;
+    }
+    hipFree(rows);
+    return ok;
+}
 int main(int argc, char **argv)
 {
     const bool fixed_only = argc > 1 && !strcmp(argv[1], "--fixed");   // the round-17 rows alone
+    if (argc > 1 && !strcmp(argv[1], "--rot")) {   // the round-18 rows alone
+        if (!check_rot()) return 1;
+        const int passes = argc > 2 ? atoi(argv[2]) : 3;
+        for (int pass = 0; pass < passes; ++pass) {
+            run7<9, 0u>("skip step bare", 13, 2);
+            run7<10, 0u>("skip step fixed-point", 12, 2);
+            run7<16, 0u>("fixed-point, broadcast row", 13, 2);
+            run7<17, 0u>("fixed-point, rotated row", 15, 2);
+            run7<18, 0u>("fixed-point, rotated, offset", 15, 2);
+        }
+        return 0;
+    }
     if (fixed_only) {
         if (!check_fixed()) return 1;
         const int passes = argc > 2 ? atoi(argv[2]) : 3;
