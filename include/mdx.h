@@ -190,6 +190,11 @@ int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges,
 #define MDX_RDF_PLAN_SLOTS 24
 int mdx_rdf_plan(int n_bins, const double *edges, int64_t excl1, int64_t excl2, int algo, int64_t n1, int64_t n2,
                  int same, const float *boxes, int64_t n_frames, int64_t out[MDX_RDF_PLAN_SLOTS]);
+/* The same slots for the handle's most recent run, from the plan that run was launched from (the engine builds it
+ * with the function mdx_rdf_plan calls).  A run is what one piece of a call hands over in frames of one cell kind, so
+ * slots 17 and 18 follow the cuts of the entry point that fed it.  MDX_ERR_STATE before any run and after
+ * mdx_rdf_reset. */
+int mdx_rdf_last_plan(mdx_rdf_t h, int64_t out[MDX_RDF_PLAN_SLOTS]);
 /* The constants of the float32 filter of rdf_cell_pair_kernel for one orthorhombic frame: cell lengths box[3], the
  * batch's largest |coordinate| max_abs, range [r0, r1] in n_bins bins.  Touches no device; the values are those the
  * frame-constant kernel computes (same functions, same arithmetic).  out:

@@ -259,6 +259,13 @@ class RdfEngine(_Engine):
                                  int(n1 if n2 is None else n2), int(n2 is None), _ptr(b), int(n_frames), _ptr(out)))
         return dict(zip(RdfEngine.PLAN_FIELDS, (int(v) for v in out)))
 
+    def last_plan(self):
+        """``mdx_rdf_last_plan``: the plan of this engine's most recent run as it was launched, the dict ``plan()``
+        returns; an error before any run and after ``reset()``."""
+        out = np.zeros(24, dtype=np.int64)
+        check(lib().mdx_rdf_last_plan(self.handle, _ptr(out)))
+        return dict(zip(RdfEngine.PLAN_FIELDS, (int(v) for v in out)))
+
     FILTER_FIELDS = ("eta", "sure_w", "tq", "inv_w", "pos0", "iwq", "p0q", "cand_hi", "cand_lo")
 
     @staticmethod

@@ -80,6 +80,7 @@ _SIGNATURES = {
     "mdx_rdf_slabs_sorted_beside": (c_int, [_vp, POINTER(c_int64)]),
     "mdx_rdf_debug_sorted": (c_int, [_vp, c_int64, c_int64, _vp, _vp]),
     "mdx_rdf_plan": (c_int, [c_int, _vp, c_int64, c_int64, c_int, c_int64, c_int64, c_int, _vp, c_int64, _vp]),
+    "mdx_rdf_last_plan": (c_int, [_vp, _vp]),
     "mdx_rdf_filter_constants": (c_int, [c_int, c_double, c_double, _vp, c_float, _vp]),
     "mdx_radial_histogram": (c_int, [c_int, _vp, c_int64, _vp, c_int64, c_int, _vp, _vp, c_int64, c_int64, _vp]),
     # structure factor

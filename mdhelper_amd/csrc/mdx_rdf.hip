@@ -353,9 +353,10 @@ __global__ void rdf_reduce_kernel(const unsigned long long *__restrict__ rep, in
 
 // -------------------------------------------------------------- host planning
 //
-// Shared by the accumulate paths and by mdx_rdf_plan (which touches no device).  Every choice among the pair
-// kernels' instantiations, their histogram form, the padded sizes and the slab lengths is a pure function of the
-// engine's arguments, the set sizes, the frames' cells and the environment, and is made here and nowhere else.
+// Every choice among the pair kernels' instantiations, their histogram form, the padded sizes and the slab lengths is
+// a pure function of the engine's arguments, the set sizes, the frames' cells and the environment.  rdf_plan_run makes
+// them all, once per run, into an RdfRunPlan: the routes launch from that struct and mdx_rdf_plan (which touches no
+// device) copies it out, so what the query says is what runs.
 
 enum {
     RDF_FAMILY_TILE_EXACT = 0,   // rdf_tile_kernel<MDX_RDF_ALGO_EXACT_F64, ...>
@@ -381,9 +382,9 @@ constexpr int CELL_FIXED_MAX_BINS = 32766;   // the LDS form's bin position is 1
 
 // the histogram of one pair kernel: LDS replicas, or the global form where the tables do not fit
 struct RdfHist {
-    int n_hist;   // LDS replicas (what the kernel is told; unused by the global form)
-    bool gh;      // tables too large for LDS: thresholds and histogram stay in global memory
-    size_t lds;   // dynamic LDS bytes of the launch
+    int n_hist = 0;       // LDS replicas (what the kernel is told; unused by the global form)
+    bool gh = false;      // tables too large for LDS: thresholds and histogram stay in global memory
+    size_t lds = 0;       // dynamic LDS bytes of the launch
 };
 
 // brute-force tiles (rdf_tile_kernel with T = 256 IPT rows, rdf_tri_tile_kernel with T = 256): the j tile, the
@@ -424,13 +425,6 @@ static RdfHist rdf_cell_hist(int n_bins)
     return r;
 }
 
-// one set against itself: the same rows AND the same tags, so that a tile pair may stand for its mirror image
-static void rdf_pair_flags(bool same, int64_t excl1, int64_t excl2, bool *self, bool *excl)
-{
-    *excl = excl1 > 0;
-    *self = same && (!*excl || excl1 == excl2);
-}
-
 // orthorhombic frames (or none): the pair kernel an algorithm stands for
 static int rdf_resolve_ortho_algo(int algo, bool has_boxes)
 {
@@ -445,18 +439,6 @@ static int rdf_resolve_ortho_algo(int algo, bool has_boxes)
     if (algo == MDX_RDF_ALGO_CELL && !has_boxes)
         algo = MDX_RDF_ALGO_FILTER_F32;   // the cell grid is defined by the periodic box
     return algo;
-}
-
-static int rdf_tile_ipt(int64_t n1, int64_t n2) { return std::max(n1, n2) >= 2048 ? 2 : 1; }
-// j tiles one block of the brute-force kernels walks
-static int rdf_tile_chunk(bool self) { return self ? 4 : 8; }
-
-// frames per slab of the brute-force routes (the packed float4 copies stay within 1 GiB), before the cut to the call
-static int64_t rdf_tile_slab_frames(int64_t n1p, int64_t n2p, bool self)
-{
-    const int64_t slab_bytes = int64_t(1) << 30;
-    const int64_t slab = std::max<int64_t>(1, slab_bytes / (int64_t(16) * (n1p + (self ? 0 : n2p))));
-    return std::min<int64_t>(slab, RDF_MAX_SLAB);
 }
 
 // frames per slab of the cell-sorted routes for a call of n_frames frames
@@ -480,16 +462,6 @@ static int64_t rdf_cell_slab_frames(int64_t n1p, int64_t n2p, bool self, int64_t
         slab -= slab % 256;
     return std::min<int64_t>(slab, n_frames);
 }
-
-// (triclinic launches keep the step: their range ends below half the smallest cell height)
-static bool rdf_cell_skip(bool tri, double r1, float min_edge)
-{
-    return tri || (float)r1 <= CELL_SKIP_MAX_RANGE * min_edge;
-}
-
-// exclusion 0 or 1: a particle's tag is its row, and the exact path reads the frames as they came in —
-// no sorted copy of the original coordinates (half of the sort kernel's scattered stores)
-static bool rdf_cell_lazy_orig(bool tri, int64_t excl1, int64_t excl2) { return !tri && excl1 <= 1 && excl2 <= 1; }
 
 // Items of the cell-sorted pair kernel: an i tile against a chunk of its candidate j tiles — every `chunks`-th of
 // them, so that each of an i tile's items gets its share of the tiles that survive the cull, which lie close
@@ -534,7 +506,7 @@ static void tri_vectors(const float *box6, float *B)
 static inline bool box_is_ortho(const float *b) { return b[3] == 90.f && b[4] == 90.f && b[5] == 90.f; }
 
 // A batch is dispatched in runs of one cell kind: the run that starts at frame f0 ends before the returned frame.
-// *ortho: its kind; *min_edge: the shortest box length over its frames (rdf_cell_skip; orthorhombic runs only).
+// *ortho: its kind; *min_edge: the shortest box length over its frames (CELL_SKIP_MAX_RANGE; orthorhombic runs only).
 static int64_t rdf_next_run(const float *h_boxes, int64_t f0, int64_t n_frames, bool *ortho, float *min_edge)
 {
     *ortho = box_is_ortho(h_boxes + 6 * f0);
@@ -586,6 +558,140 @@ static bool rdf_tri_culled(int algo, int64_t n1, int64_t n2, double r1, const fl
     return culled;
 }
 
+// what mdx_rdf_create fixes for every run of an engine
+struct RdfConfig {
+    int n_bins;
+    double r0, r1;
+    int64_t excl1, excl2;
+    int algo;
+};
+
+// What one run (frames of one cell kind, handed over whole) launches: the slots of mdx_rdf_plan (mdx.h) in their
+// order.  The rows of a tile, T = 256 ipt, derive from ipt; n_slabs == 0 stands for "no run yet".
+struct RdfRunPlan {
+    int family = RDF_FAMILY_TILE_EXACT, ipt = 1;
+    bool self = false, excl = false, pbc = false, lower = false, skip = false;
+    RdfHist hist;
+    bool lds_attribute = false;
+    int64_t n1p = 0, n2p = 0, tiles1 = 0, tiles2 = 0;
+    int64_t chunk = 0, grid_x = 0;   // j tiles per chunk, chunks
+    int64_t slab = 0, n_slabs = 0;
+    bool lazy_orig = false;
+    int T() const { return 256 * ipt; }
+    bool cell() const { return family == RDF_FAMILY_CELL_ORTHO || family == RDF_FAMILY_TRI_CULLED; }
+};
+
+// The plan of one run of n_frames frames: `ortho` frames with boxes (has_boxes; min_edge: rdf_next_run) or without,
+// or triclinic frames with the cell matrices tri[n_frames][9].  Touches no device; reads MDX_RDF_SLAB_BYTES,
+// MDX_RDF_TRI_BRUTE and MDX_RDF_CHUNK_TILES at every call.
+static RdfRunPlan rdf_plan_run(const RdfConfig &c, int64_t n1, int64_t n2, bool same, bool has_boxes, bool ortho,
+                               float min_edge, const float *tri, int64_t n_frames)
+{
+    RdfRunPlan p;
+    // one set against itself: the same rows AND the same tags, so that a tile pair may stand for its mirror image
+    p.excl = c.excl1 > 0;
+    p.self = same && (!p.excl || c.excl1 == c.excl2);
+    p.pbc = has_boxes;
+    if (ortho) {
+        const int a = rdf_resolve_ortho_algo(c.algo, has_boxes);
+        p.family = a == MDX_RDF_ALGO_CELL ? RDF_FAMILY_CELL_ORTHO
+                                          : a == MDX_RDF_ALGO_EXACT_F64 ? RDF_FAMILY_TILE_EXACT : RDF_FAMILY_TILE_FILTER;
+    } else {
+        p.family = rdf_tri_culled(c.algo, n1, n2, c.r1, tri, n_frames) ? RDF_FAMILY_TRI_CULLED : RDF_FAMILY_TRI_BRUTE;
+    }
+    if (p.cell()) {
+        p.n1p = ceil_div(n1, 128) * 128;
+        p.n2p = ceil_div(n2, 128) * 128;
+        p.tiles1 = p.n1p / 128;   // 128-row i tiles, 64-row j tiles
+        p.tiles2 = p.n2p / 64;
+        p.lower = c.r0 > 0.0;
+        // (triclinic launches keep the step: their range ends below half the smallest cell height)
+        p.skip = !ortho || (float)c.r1 <= CELL_SKIP_MAX_RANGE * min_edge;
+        p.hist = rdf_cell_hist(c.n_bins);   // (the cell-sorted launches never ask for the LDS attribute)
+        p.grid_x = rdf_cell_chunks(p.n2p, p.skip, &p.chunk);
+        p.slab = rdf_cell_slab_frames(p.n1p, p.n2p, p.self, n_frames);
+        // exclusion 0 or 1: a particle's tag is its row, and the exact path reads the frames as they came in —
+        // no sorted copy of the original coordinates (half of the sort kernel's scattered stores)
+        p.lazy_orig = ortho && c.excl1 <= 1 && c.excl2 <= 1;
+    } else {
+        p.ipt = ortho && std::max(n1, n2) >= 2048 ? 2 : 1;
+        const int T = p.T();
+        p.n1p = ceil_div(n1, T) * T;
+        p.n2p = ceil_div(n2, T) * T;
+        p.tiles1 = p.n1p / T;
+        p.tiles2 = p.n2p / T;
+        p.hist = rdf_tile_hist(c.n_bins, T);
+        p.lds_attribute = p.hist.lds > RDF_LDS_ATTR_LINE;
+        p.chunk = p.self ? 4 : 8;   // j tiles one block of the brute-force kernels walks
+        p.grid_x = ceil_div(p.tiles2, p.chunk);
+        // the packed float4 copies of a slab stay within 1 GiB; a slab is ONE pair launch with its frames on grid z,
+        // which rests on the cut to RDF_MAX_SLAB here
+        const int64_t slab = std::max<int64_t>(1, (int64_t(1) << 30) / (16 * (p.n1p + (p.self ? 0 : p.n2p))));
+        p.slab = std::min(std::min(slab, RDF_MAX_SLAB), n_frames);
+    }
+    p.n_slabs = ceil_div(n_frames, p.slab);
+    return p;
+}
+
+// the plan as mdx_rdf_plan and mdx_rdf_last_plan report it
+static void rdf_plan_slots(const RdfRunPlan &p, int64_t out[MDX_RDF_PLAN_SLOTS])
+{
+    const int64_t slots[] = {p.family, p.ipt, p.self, p.excl, p.pbc, p.lower, p.skip, p.hist.gh,
+                             p.hist.gh ? 0 : p.hist.n_hist, (int64_t)p.hist.lds, p.lds_attribute, p.n1p, p.n2p,
+                             p.tiles1, p.tiles2, p.chunk, p.grid_x, p.slab, p.n_slabs, p.lazy_orig};
+    constexpr int n = sizeof(slots) / sizeof(slots[0]);
+    static_assert(n <= MDX_RDF_PLAN_SLOTS, "more plan fields than slots");
+    for (int k = 0; k < MDX_RDF_PLAN_SLOTS; ++k)
+        out[k] = k < n ? slots[k] : 0;
+}
+
+// The pair kernel a plan stands for: one function per kernel family, over a table of its instantiations
+// (tests/rdf_cases.py::instantiation states the same mapping).  `true` comes first in every table, the order in which
+// the instantiations are emitted into the unit's device code.
+static auto rdf_tile_kernel_of(const RdfRunPlan &p) -> void (*)(RdfArgs)
+{
+    constexpr int X = MDX_RDF_ALGO_EXACT_F64, F = MDX_RDF_ALGO_FILTER_F32;
+    static void (*const kern[2][2][2][2][2])(RdfArgs) = {   // [filter][IPT - 1][!PBC][!EXCL][!GH]
+        {{{{rdf_tile_kernel<X, 1, true, true, true>, rdf_tile_kernel<X, 1, true, true, false>},
+           {rdf_tile_kernel<X, 1, true, false, true>, rdf_tile_kernel<X, 1, true, false, false>}},
+          {{rdf_tile_kernel<X, 1, false, true, true>, rdf_tile_kernel<X, 1, false, true, false>},
+           {rdf_tile_kernel<X, 1, false, false, true>, rdf_tile_kernel<X, 1, false, false, false>}}},
+         {{{rdf_tile_kernel<X, 2, true, true, true>, rdf_tile_kernel<X, 2, true, true, false>},
+           {rdf_tile_kernel<X, 2, true, false, true>, rdf_tile_kernel<X, 2, true, false, false>}},
+          {{rdf_tile_kernel<X, 2, false, true, true>, rdf_tile_kernel<X, 2, false, true, false>},
+           {rdf_tile_kernel<X, 2, false, false, true>, rdf_tile_kernel<X, 2, false, false, false>}}}},
+        {{{{rdf_tile_kernel<F, 1, true, true, true>, rdf_tile_kernel<F, 1, true, true, false>},
+           {rdf_tile_kernel<F, 1, true, false, true>, rdf_tile_kernel<F, 1, true, false, false>}},
+          {{rdf_tile_kernel<F, 1, false, true, true>, rdf_tile_kernel<F, 1, false, true, false>},
+           {rdf_tile_kernel<F, 1, false, false, true>, rdf_tile_kernel<F, 1, false, false, false>}}},
+         {{{rdf_tile_kernel<F, 2, true, true, true>, rdf_tile_kernel<F, 2, true, true, false>},
+           {rdf_tile_kernel<F, 2, true, false, true>, rdf_tile_kernel<F, 2, true, false, false>}},
+          {{rdf_tile_kernel<F, 2, false, true, true>, rdf_tile_kernel<F, 2, false, true, false>},
+           {rdf_tile_kernel<F, 2, false, false, true>, rdf_tile_kernel<F, 2, false, false, false>}}}}};
+    return kern[p.family == RDF_FAMILY_TILE_FILTER][p.ipt - 1][!p.pbc][!p.excl][!p.hist.gh];
+}
+
+static auto rdf_cell_kernel_of(const RdfRunPlan &p) -> void (*)(CellArgs)
+{
+    // [!EXCL][!LOWER][form]: triclinic frames with the global and with the LDS histogram; orthorhombic frames with the
+    // LDS histogram and the step that leaves when it is empty or the unconditional tail, and with the global histogram
+    static void (*const kern[2][2][5])(CellArgs) = {
+        {{rdf_cell_pair_kernel<true, true, 1, true>, rdf_cell_pair_kernel<true, true, 0, true>,
+          rdf_cell_pair_kernel<true, true, 0, false, true>, rdf_cell_pair_kernel<true, true, 0, false, false>,
+          rdf_cell_pair_kernel<true, true, 1>},
+         {rdf_cell_pair_kernel<true, false, 1, true>, rdf_cell_pair_kernel<true, false, 0, true>,
+          rdf_cell_pair_kernel<true, false, 0, false, true>, rdf_cell_pair_kernel<true, false, 0, false, false>,
+          rdf_cell_pair_kernel<true, false, 1>}},
+        {{rdf_cell_pair_kernel<false, true, 1, true>, rdf_cell_pair_kernel<false, true, 0, true>,
+          rdf_cell_pair_kernel<false, true, 0, false, true>, rdf_cell_pair_kernel<false, true, 0, false, false>,
+          rdf_cell_pair_kernel<false, true, 1>},
+         {rdf_cell_pair_kernel<false, false, 1, true>, rdf_cell_pair_kernel<false, false, 0, true>,
+          rdf_cell_pair_kernel<false, false, 0, false, true>, rdf_cell_pair_kernel<false, false, 0, false, false>,
+          rdf_cell_pair_kernel<false, false, 1>}}};
+    const bool gh = p.hist.gh;
+    return kern[!p.excl][!p.lower][p.family == RDF_FAMILY_TRI_CULLED ? (gh ? 0 : 1) : gh ? 4 : p.skip ? 2 : 3];
+}
+
 // The contract binds the edges to numpy.linspace (mdx.h): the float32 filter and the cell kernel's sure path take
 // a pair's bin from floor((d - r0) * n_bins / (r1 - r0)) and only pairs near an edge of THAT grid go to the threshold
 // table, so any other increasing array would be binned wrongly there and rightly on the exact routes.  linspace
@@ -611,6 +717,25 @@ static int rdf_check_edges(int n_bins, const double *edges)
     return MDX_OK;
 }
 
+// what mdx_rdf_create and mdx_rdf_plan ask of an engine's arguments, before any device call
+static int rdf_check_engine_args(const void *out, int n_bins, const double *edges, int64_t excl1, int64_t excl2,
+                                 int algo)
+{
+    MDX_REQUIRE(out && edges, "NULL argument");
+    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 20), "n_bins=%d out of range", n_bins);
+    MDX_REQUIRE((excl1 > 0) == (excl2 > 0) && excl1 >= 0 && excl2 >= 0,
+                "exclusion must be two positive integers (or 0, 0 for none)");
+    MDX_REQUIRE(algo >= MDX_RDF_ALGO_AUTO && algo <= MDX_RDF_ALGO_CELL, "unknown algo %d", algo);
+    return rdf_check_edges(n_bins, edges);
+}
+
+// the sets of a run, as the engine and mdx_rdf_plan bound them (the kernels index padded rows with 32-bit ints)
+static int rdf_check_set_sizes(int64_t n1, int64_t n2)
+{
+    MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
+    return MDX_OK;
+}
+
 // --------------------------------------------------------------------- handle
 
 struct mdx_rdf {
@@ -630,11 +755,11 @@ struct mdx_rdf {
     const void *occ_kernel = nullptr;   // occupancy of the persistent pair kernel: last kernel / LDS size asked for
     size_t occ_lds = 0;
     int64_t occ_blocks_per_xcd = 1;
-    // what mdx_rdf_debug_sorted needs to find the most recent slab: its set of sorted copies, whether the
-    // sorted originals were materialised, its frame count
+    RdfRunPlan last_plan;   // of the most recent run since reset (mdx_rdf_last_plan)
+    // what mdx_rdf_debug_sorted needs beside it to find the most recent slab of the cell-sorted route: its set of
+    // sorted copies and its frame count
     size_t last_offset = 0;   // float4 elements from the start of d_pw1 / d_po1 to the slab
-    int64_t last_frames = 0, last_n_pad = 0;
-    bool last_lazy = false;
+    int64_t last_frames = 0;
     // optional centre-of-mass stage per set: incoming rows are particles grouped into molecules
     MoleculeStage grouping[2];
     // drop_axis (2-D mode, structure.py:761-770): coordinate zeroed, box length -> max(lx, ly, lz)
@@ -662,121 +787,179 @@ struct mdx_rdf {
     bool reduced_global = false;   // counts replica 0 holds an all-reduced total
 };
 
-static int launch_tiles(mdx_rdf *h, RdfArgs &a, int mode, int ipt, bool pbc, bool excl,
-                        int64_t n_frames)
+// ------------------- routes: each takes a run through the kernels of its plan and recomputes nothing the plan holds
+
+// The frames of one run on the device: pos float[n_frames][n][3] (pos2 == pos1 for one set against itself), and
+// boxes float[n_frames][6] for orthorhombic frames (nullptr: no cell) or tri float[n_frames][9] for triclinic ones.
+struct RdfFrames {
+    const float *pos1, *pos2;
+    int64_t n1, n2;
+    const float *boxes, *tri;
+};
+
+// The brute-force routes walk a run in slabs so that the packed float4 copies stay bounded.  Per slab, the fields
+// RdfArgs and TriArgs have in common are set here from the plan; pack(a, f0, nf) packs frames [f0, f0 + nf) into
+// d_pack1 / d_pack2 and sets what is its kernel's own; then the pair kernel, frames on grid z.
+template <typename Args, typename Pack>
+static int tile_slabs(mdx_rdf *h, const RdfRunPlan &p, const RdfFrames &in, int64_t n_frames, void (*kern)(Args),
+                      Pack pack)
 {
-    // LDS: j tile + thresholds + per-wave histograms
-    const RdfHist hist = rdf_tile_hist(h->n_bins, 256 * ipt);
-    const size_t lds = hist.lds;
-    const bool gh = hist.gh;
-    a.n_hist = hist.n_hist;
-    a.chunk = rdf_tile_chunk(a.self != 0);
-    void (*kern)(RdfArgs) = nullptr;
-#define MDX_PICK(M, I, P, E) \
-    kern = gh ? rdf_tile_kernel<M, I, P, E, true> : rdf_tile_kernel<M, I, P, E, false>
-#define MDX_PICK_PE(M, I)                         \
-    do {                                          \
-        if (pbc && excl) MDX_PICK(M, I, true, true);   \
-        else if (pbc) MDX_PICK(M, I, true, false);     \
-        else if (excl) MDX_PICK(M, I, false, true);    \
-        else MDX_PICK(M, I, false, false);             \
-    } while (0)
-    if (mode == MDX_RDF_ALGO_EXACT_F64) {
-        if (ipt == 1) MDX_PICK_PE(MDX_RDF_ALGO_EXACT_F64, 1);
-        else MDX_PICK_PE(MDX_RDF_ALGO_EXACT_F64, 2);
-    } else {
-        if (ipt == 1) MDX_PICK_PE(MDX_RDF_ALGO_FILTER_F32, 1);
-        else MDX_PICK_PE(MDX_RDF_ALGO_FILTER_F32, 2);
-    }
-#undef MDX_PICK_PE
-#undef MDX_PICK
-    if (lds > RDF_LDS_ATTR_LINE)
+    if (p.lds_attribute)
         MDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipEvent_t ev = h->timer.begin();
-    // (this loop never takes a second turn: the caller's slab, rdf_tile_slab_frames, is at most RDF_MAX_SLAB frames)
-    for (int64_t f0 = 0; f0 < n_frames; f0 += RDF_MAX_SLAB) {
-        int64_t nf = std::min<int64_t>(RDF_MAX_SLAB, n_frames - f0);
-        a.frame0 = (int)f0;
-        dim3 grid((unsigned)ceil_div(a.nt2, a.chunk), (unsigned)a.nt1, (unsigned)nf);
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, a);
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.hist.lds));
+    MDX_TRY(h->d_pack1.ensure(size_t(16) * p.n1p * p.slab));
+    if (!p.self)
+        MDX_TRY(h->d_pack2.ensure(size_t(16) * p.n2p * p.slab));
+    const int64_t tile_pairs = p.self ? p.tiles1 * (p.tiles1 + 1) / 2 : p.tiles1 * p.tiles2;
+    for (int64_t f0 = 0; f0 < n_frames; f0 += p.slab) {
+        const int64_t nf = std::min(p.slab, n_frames - f0);
+        Args a{};
+        a.p1 = h->d_pack1.as<float4>();
+        a.p2 = p.self ? a.p1 : h->d_pack2.as<float4>();
+        a.n1p = (int)p.n1p;
+        a.n2p = (int)p.n2p;
+        a.nt1 = (int)p.tiles1;
+        a.nt2 = (int)p.tiles2;
+        a.self = p.self ? 1 : 0;
+        a.n_bins = h->n_bins;
+        a.thresh = h->d_thresh.as<double>();
+        a.t_lo = h->t_lo;
+        a.t_hi = h->t_hi;
+        a.counts = h->d_counts.as<unsigned long long>();
+        a.n_rep = h->n_rep;
+        a.n_hist = p.hist.n_hist;
+        a.chunk = (int)p.chunk;
+        pack(a, f0, nf);
+        hipEvent_t ev = h->timer.begin();
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.grid_x, (unsigned)p.tiles1, (unsigned)nf), dim3(256), p.hist.lds,
+                           h->stream, a);
+        h->timer.end(ev);
+        MDX_HIP(hipGetLastError());
+        h->pairs_bruteforce += nf * tile_pairs * p.T() * p.T();
     }
-    h->timer.end(ev);
-    MDX_HIP(hipGetLastError());
+    h->pairs_evaluated += n_frames * in.n1 * in.n2;
     return MDX_OK;
 }
 
-// Cell-sorted path (mdx_rdf_cell.hpp): sort + tile boxes per frame, then the culled pair kernel.
-// d_tri != nullptr: triclinic frames, d_tri = their cell matrices [n_frames][9] (d_boxes unused)
-// min_edge: the shortest box length over the frames (rdf_cell_skip), 0 = not known
-static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
-                           int64_t n2, const float *d_boxes, int64_t n_frames, bool self, bool excl,
-                           const float *d_tri = nullptr, float min_edge = 0.f)
+// Orthorhombic frames (or none), brute-force tiles: exact arithmetic or the float32 filter.
+static int accumulate_tiles(mdx_rdf *h, const RdfRunPlan &p, const RdfFrames &in, int64_t n_frames)
 {
-    const bool tri = d_tri != nullptr;
-    const int64_t n1p = ceil_div(n1, 128) * 128, n2p = ceil_div(n2, 128) * 128;
-    const int64_t slab = rdf_cell_slab_frames(n1p, n2p, self, n_frames);
-    const bool lazy_orig = rdf_cell_lazy_orig(tri, h->excl1, h->excl2);
-    unsigned *d_misc = h->d_misc.as<unsigned>();
-    if (!tri)
-        hipLaunchKernelGGL(rdf_check_boxes_kernel, dim3((unsigned)ceil_div(n_frames, 256)), dim3(256),
-                           0, h->stream, d_boxes, n_frames, d_misc + 1);
+    unsigned *d_misc = h->d_misc.as<unsigned>();   // [0] maxabs bits, [1] status
+    return tile_slabs(h, p, in, n_frames, rdf_tile_kernel_of(p), [&](RdfArgs &a, int64_t f0, int64_t nf) {
+        hipLaunchKernelGGL(rdf_pack_kernel, dim3((unsigned)(p.n1p / 256), (unsigned)nf), dim3(256), 0,
+                           h->stream, in.pos1 + f0 * in.n1 * 3, h->d_pack1.as<float4>(), (int)in.n1,
+                           (int)p.n1p, p.excl ? h->excl1 : 0, d_misc);
+        if (!p.self)
+            hipLaunchKernelGGL(rdf_pack_kernel, dim3((unsigned)(p.n2p / 256), (unsigned)nf), dim3(256),
+                               0, h->stream, in.pos2 + f0 * in.n2 * 3, h->d_pack2.as<float4>(), (int)in.n2,
+                               (int)p.n2p, p.excl ? h->excl2 : 0, d_misc);
+        a.boxes = in.boxes ? in.boxes + f0 * 6 : nullptr;
+        a.r0 = h->edges.front();
+        a.r1 = h->edges.back();
+        a.maxabs_bits = d_misc;
+        a.exact_counter = h->d_stats.as<unsigned long long>();
+    });
+}
 
-    // LDS of the pair kernel and the form of its histogram
-    const RdfHist hist = rdf_cell_hist(h->n_bins);
-    const int n_hist = hist.n_hist;
-    const size_t lds = hist.lds;
-    const bool gh = hist.gh;
-    const bool lower = h->edges.front() > 0.0;
-    void (*kern)(CellArgs) = nullptr;
-    const bool skip = rdf_cell_skip(tri, h->edges.back(), min_edge);
-#define MDX_CELL_PICK(E, L)                                                                     \
-    kern = tri ? (gh ? rdf_cell_pair_kernel<E, L, 1, true> : rdf_cell_pair_kernel<E, L, 0, true>) \
-               : (gh ? rdf_cell_pair_kernel<E, L, 1>                                             \
-                     : (skip ? rdf_cell_pair_kernel<E, L, 0, false, true> : rdf_cell_pair_kernel<E, L, 0, false, false>))
-    if (excl && lower) MDX_CELL_PICK(true, true);
-    else if (excl) MDX_CELL_PICK(true, false);
-    else if (lower) MDX_CELL_PICK(false, true);
-    else MDX_CELL_PICK(false, false);
-#undef MDX_CELL_PICK
-    // resident blocks per XCD (32 CUs each) of this kernel at this LDS size (asked once per kernel and size)
-    if (h->occ_kernel != reinterpret_cast<const void *>(kern) || h->occ_lds != lds) {
-        int per_cu = 0, cus = 0;
-        hipFuncAttributes fa{};
-        MDX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(kern), 256, lds));
-        MDX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->dev));
-        MDX_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)));
-        h->occ_kernel = reinterpret_cast<const void *>(kern);
-        h->occ_lds = lds;
-        h->occ_static_lds = fa.sharedSizeBytes;
-        h->occ_per_cu = std::max(per_cu, 1);
-        h->occ_blocks_per_xcd = std::max<int64_t>(1, int64_t(std::max(per_cu, 1)) * std::max(cus, 8) / 8);
+// The cell-sorted route (mdx_rdf_cell.hpp), for orthorhombic frames and for culled triclinic ones: sort + tile boxes
+// per frame, then the culled pair kernel.  The plan fixes the kernel, its LDS, the padding, the items and the slab.
+// What the functions below decide on top of it depends on the device or on switches that only they read — the pair
+// kernel's occupancy, the memory that is free, MDX_RDF_SORT_BESIDE, MDX_RDF_LDS_FLUSH_UNITS — and is no part of the
+// plan: whether the next slab is sorted beside a pair launch, the quarter and half slabs that route starts with, the
+// grid of the persistent pair blocks.
+struct CellSide {   // the sorted copies of one particle set: wrapped and original rows, boxes of the 64-row tiles and
+    DeviceBuffer *pw, *po, *bb, *bc;   // of the chunks — and the float4 elements a slab of p.slab frames takes in each
+    size_t e_p, e_b, e_c;
+};
+
+struct CellSet {   // one set of sorted copies, [particle set 1 | 2] (the same pointers for one set against itself)
+    float4 *pw[2], *po[2], *bb[2], *bc[2];
+};
+
+struct CellRun {
+    mdx_rdf *h;
+    const RdfRunPlan &p;
+    const RdfFrames &in;
+    void (*kern)(CellArgs);
+    CellSide side[2];
+    bool beside;                 // the sort of slab k + 1 runs beside the pair kernel of slab k
+    std::vector<int64_t> lens;   // slab lengths of this run
+
+    bool tri() const { return p.family == RDF_FAMILY_TRI_CULLED; }
+};
+
+// resident blocks per XCD (32 CUs each) of the pair kernel at its LDS size (asked once per kernel and size)
+static int cell_occupancy(mdx_rdf *h, const void *kern, size_t lds)
+{
+    if (h->occ_kernel == kern && h->occ_lds == lds)
+        return MDX_OK;
+    int per_cu = 0, cus = 0;
+    hipFuncAttributes fa{};
+    MDX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds));
+    MDX_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->dev));
+    MDX_HIP(hipFuncGetAttributes(&fa, kern));
+    h->occ_kernel = kern;
+    h->occ_lds = lds;
+    h->occ_static_lds = fa.sharedSizeBytes;
+    h->occ_per_cu = std::max(per_cu, 1);
+    h->occ_blocks_per_xcd = std::max<int64_t>(1, int64_t(std::max(per_cu, 1)) * std::max(cus, 8) / 8);
+    return MDX_OK;
+}
+
+static int cell_sets_ensure(const CellRun &r, size_t n_sets)
+{
+    for (int g = 0; g < (r.p.self ? 1 : 2); ++g) {
+        const CellSide &d = r.side[g];
+        MDX_TRY(d.pw->ensure(16 * d.e_p * n_sets));
+        if (!r.p.lazy_orig)
+            MDX_TRY(d.po->ensure(16 * d.e_p * n_sets));
+        MDX_TRY(d.bb->ensure(16 * d.e_b * n_sets));
+        MDX_TRY(d.bc->ensure(16 * d.e_c * n_sets));
     }
-    const int64_t blocks_per_xcd = h->occ_blocks_per_xcd;
+    return MDX_OK;
+}
 
-    // The sort of slab k + 1 BESIDE the pair kernel of slab k.  Round 2 put it on a second stream (+1 %); with
-    // persistent pair blocks that lost 3 % (NOTES.md round 3): they hold every wave slot and nearly every register
-    // until their last items, and a 1 024-thread sort block could enter only where four of them had retired.  Here
-    // the sort is a block of the pair block's own shape (rdf_cell_sort_small_kernel), and the pair kernel is launched
-    // with S fewer blocks than the chip holds (S a multiple of 8: every XCD gives up the same number): S persistent
-    // sort blocks on the side stream have a place from the start, and neither kernel waits for the other to retire
-    // anything.  Two sets of the sorted copies alternate.  The first slab of a call has nothing to hide behind: the
-    // big kernel sorts it on the handle's stream, and it is a quarter slab, the second a half (the shape of the host
-    // and file routes), S scaled by the ratio of the sorted slab's length to the pair launch's.
-    // Today's serial route (one set, the big kernel) remains for: triclinic frames, more than 65 535 particles in a
-    // set (packed 16-bit counters), a pair kernel whose blocks leave the sort block's 33 KB of LDS no room beside
-    // all but one of them, calls of a single slab, a device without room for the second set, and
-    // MDX_RDF_SORT_BESIDE=0.
-    // S = 16 (profiles/r06_sort_beside_S_choice.txt): 16 blocks sort a slab of 2 304 C2 frames in half the time of
-    // its pair launch; with 8 the sort would take all of it
-    constexpr int64_t S0 = 16;
+static CellSet cell_set_of(const CellRun &r, int b)
+{
+    CellSet s;
+    for (int g = 0; g < 2; ++g) {
+        const CellSide &d = r.side[r.p.self ? 0 : g];
+        s.pw[g] = d.pw->as<float4>() + b * d.e_p;
+        s.po[g] = r.p.lazy_orig ? nullptr : d.po->as<float4>() + b * d.e_p;
+        s.bb[g] = d.bb->as<float4>() + b * d.e_b;
+        s.bc[g] = d.bc->as<float4>() + b * d.e_c;
+    }
+    return s;
+}
+
+// The sort of slab k + 1 BESIDE the pair kernel of slab k.  Round 2 put it on a second stream (+1 %); with
+// persistent pair blocks that lost 3 % (NOTES.md round 3): they hold every wave slot and nearly every register
+// until their last items, and a 1 024-thread sort block could enter only where four of them had retired.  Here
+// the sort is a block of the pair block's own shape (rdf_cell_sort_small_kernel), and the pair kernel is launched
+// with S fewer blocks than the chip holds (S a multiple of 8: every XCD gives up the same number): S persistent
+// sort blocks on the side stream have a place from the start, and neither kernel waits for the other to retire
+// anything.  Two sets of the sorted copies alternate.  The first slab of a call has nothing to hide behind: the
+// big kernel sorts it on the handle's stream, and it is a quarter slab, the second a half (the shape of the host
+// and file routes), S scaled by the ratio of the sorted slab's length to the pair launch's.
+// Today's serial route (one set, the big kernel) remains for: triclinic frames, more than 65 535 particles in a
+// set (packed 16-bit counters), a pair kernel whose blocks leave the sort block's 33 KB of LDS no room beside
+// all but one of them, calls of a single slab, a device without room for the second set, and
+// MDX_RDF_SORT_BESIDE=0.
+// S = 16 (profiles/r06_sort_beside_S_choice.txt): 16 blocks sort a slab of 2 304 C2 frames in half the time of
+// its pair launch; with 8 the sort would take all of it
+constexpr int64_t CELL_SORT_BESIDE_BLOCKS = 16;
+
+// decides r.beside (after cell_occupancy), creates the side stream and its events at the first need, and sizes the
+// buffers for two sets or one
+static int cell_sort_beside(CellRun &r, int64_t n_frames)
+{
+    mdx_rdf *h = r.h;
     const char *sb_env = getenv("MDX_RDF_SORT_BESIDE");
-    const size_t sort_small_lds = sort_small_lds_bytes();
     const size_t cu_lds = size_t(160) * 1024;
-    bool beside = !tri && !(sb_env && strcmp(sb_env, "0") == 0) && n_frames > slab && n1 <= SORT_SMALL_MAX_N &&
-                  n2 <= SORT_SMALL_MAX_N && blocks_per_xcd >= 2 &&
-                  size_t(h->occ_per_cu - 1) * (h->occ_static_lds + lds) + sort_small_lds <= cu_lds;
-    if (beside && !h->ev_join) {
+    r.beside = !r.tri() && !(sb_env && strcmp(sb_env, "0") == 0) && n_frames > r.p.slab &&
+               r.in.n1 <= SORT_SMALL_MAX_N && r.in.n2 <= SORT_SMALL_MAX_N && h->occ_blocks_per_xcd >= 2 &&
+               size_t(h->occ_per_cu - 1) * (h->occ_static_lds + r.p.hist.lds) + sort_small_lds_bytes() <= cu_lds;
+    if (r.beside && !h->ev_join) {
         // (the last event created is the guard: after a failure half-way the next call starts over)
         if (!h->side)
             MDX_TRY(stream_acquire(&h->side));
@@ -784,37 +967,21 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
             if (!*e)
                 MDX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
-
-    const size_t e_p1 = size_t(n1p) * slab, e_b1 = size_t(n1p / 64) * 2 * slab;
-    const size_t e_c1 = CELL_CHUNK >= 4 ? size_t(n1p / CELL_CHUNK) * 2 * slab : 16;
-    const size_t e_p2 = size_t(n2p) * slab, e_b2 = size_t(n2p / 64) * 2 * slab;
-    const size_t e_c2 = CELL_CHUNK >= 4 ? size_t(n2p / CELL_CHUNK) * 2 * slab : 16;
-    auto ensure_sets = [&](size_t n_sets) -> int {
-        MDX_TRY(h->d_pw1.ensure(16 * e_p1 * n_sets));
-        if (!lazy_orig)
-            MDX_TRY(h->d_po1.ensure(16 * e_p1 * n_sets));
-        MDX_TRY(h->d_bb1.ensure(16 * e_b1 * n_sets));
-        MDX_TRY(h->d_bb16_1.ensure(16 * e_c1 * n_sets));
-        if (!self) {
-            MDX_TRY(h->d_bb16_2.ensure(16 * e_c2 * n_sets));
-            MDX_TRY(h->d_pw2.ensure(16 * e_p2 * n_sets));
-            if (!lazy_orig)
-                MDX_TRY(h->d_po2.ensure(16 * e_p2 * n_sets));
-            MDX_TRY(h->d_bb2.ensure(16 * e_b2 * n_sets));
-        }
-        return MDX_OK;
-    };
     // two sets are twice the memory (5 GiB at C2): a device too full for them still has the serial route's one
     // (buffers the failed attempt had already grown stay at that size, and its message stays in mdx_last_error()
     // although the call then succeeds: nobody reads it after MDX_OK)
-    if (beside && ensure_sets(2) == MDX_ERR_OUT_OF_MEMORY)
-        beside = false;
-    MDX_TRY(ensure_sets(beside ? 2 : 1));
-    // slab lengths of this call
+    if (r.beside && cell_sets_ensure(r, 2) == MDX_ERR_OUT_OF_MEMORY)
+        r.beside = false;
+    return cell_sets_ensure(r, r.beside ? 2 : 1);
+}
+
+// slab lengths of a run: with the sort beside, a quarter and a half slab first (whole rounds of the big kernel)
+static std::vector<int64_t> cell_slab_lengths(int64_t slab, bool beside, int64_t n_frames)
+{
     std::vector<int64_t> lens;
     for (int64_t f0 = 0; f0 < n_frames;) {
         int64_t step = slab;
-        if (beside && slab >= 8 && lens.size() < 2) {   // a quarter, a half; whole rounds of the big kernel
+        if (beside && slab >= 8 && lens.size() < 2) {
             step = slab >> (2 - lens.size());
             if (step >= 256)
                 step -= step % 256;
@@ -823,347 +990,282 @@ static int accumulate_cell(mdx_rdf *h, const float *d_pos1, int64_t n1, const fl
         lens.push_back(step);
         f0 += step;
     }
+    return lens;
+}
+
+// the sort of frames [f0, f0 + nf) into a set: the big kernel (small_grid == 0) or `small_grid` persistent
+// blocks of the small one
+static void cell_launch_sort(const CellRun &r, const CellSet &s, int64_t f0, int64_t nf, hipStream_t stream,
+                             unsigned small_grid)
+{
+    // (Measured and dropped, round 3: the sort as a GATHER — slots noted per particle in LDS, rows written
+    // in slot order as whole lines — 0.66 ms per 1 000 frames against 0.74–0.82, +0.5 % on the step, but its
+    // 12-byte reads scattered over frames that are no longer in L2 fetch 4.0 MB per frame where the scatter's
+    // partial-sector stores cost 1.1: 6.5 MB per frame in all against 4.4.  Neither two blocks per CU (the
+    // kernel sits at 65 VGPRs: one over), float32 cell keys, a DPP box reduction nor a two-barrier scan moved
+    // the kernel's time: all 256 blocks of a round read, then write, in step — 25 µs counting from HBM, 81 µs
+    // writing rows — and the memory system sets the pace.)
+    mdx_rdf *h = r.h;
+    const float *pos[2] = {r.in.pos1 + f0 * r.in.n1 * 3, r.in.pos2 + f0 * r.in.n2 * 3};
+    const float *cells = r.tri() ? r.in.tri + f0 * 9 : r.in.boxes + f0 * 6;
+    const int n[2] = {(int)r.in.n1, (int)r.in.n2}, n_pad[2] = {(int)r.p.n1p, (int)r.p.n2p};
+    const int64_t excl[2] = {r.p.excl ? h->excl1 : 0, r.p.excl ? h->excl2 : 0};
+    unsigned *d_maxabs = h->d_misc.as<unsigned>();
+    for (int g = 0; g < (r.p.self ? 1 : 2); ++g) {
+        if (small_grid)
+            hipLaunchKernelGGL(rdf_cell_sort_small_kernel<SORT_SMALL_THREADS>, dim3(small_grid),
+                               dim3(SORT_SMALL_THREADS), sort_small_lds_bytes(), stream, pos[g], cells, n[g], n_pad[g],
+                               excl[g], s.pw[g], s.po[g], s.bb[g], s.bc[g], d_maxabs, (int)nf);
+        else
+            hipLaunchKernelGGL(r.tri() ? rdf_cell_sort_kernel<true> : rdf_cell_sort_kernel<false>, dim3((unsigned)nf),
+                               dim3(SORT_THREADS), 0, stream, pos[g], cells, n[g], n_pad[g], excl[g], s.pw[g], s.po[g],
+                               s.bb[g], s.bc[g], d_maxabs);
+    }
+}
+
+// the pair kernel over the sorted frames [f0, f0 + nf) of a set; holes: blocks it leaves to a sort beside it
+static int cell_launch_pairs(const CellRun &r, const CellSet &s, int64_t f0, int64_t nf, int64_t holes)
+{
+    mdx_rdf *h = r.h;
+    const RdfRunPlan &p = r.p;
+    const RdfFrames &in = r.in;
+    CellArgs a{};
+    a.pw1 = s.pw[0];
+    a.po1 = s.po[0];
+    a.bb1 = s.bb[0];
+    a.pw2 = s.pw[1];
+    a.po2 = s.po[1];
+    a.bb2 = s.bb[1];
+    a.bb16_2 = s.bc[1];
+    a.in1 = p.lazy_orig ? in.pos1 + f0 * in.n1 * 3 : nullptr;
+    a.in2 = p.lazy_orig ? in.pos2 + f0 * in.n2 * 3 : nullptr;
+    a.n1_in = (int)in.n1;
+    a.n2_in = (int)in.n2;
+    a.tags_everywhere = (p.self && h->excl1 == 1 && h->excl2 == 1) ? 0 : 1;
+    a.boxes = r.tri() ? nullptr : in.boxes + f0 * 6;
+    a.tri = r.tri() ? in.tri + f0 * 9 : nullptr;
+    a.thresh = h->d_thresh.as<double>();
+    a.counts = h->d_counts.as<unsigned long long>();
     // the batch's largest |coordinate| (the filter's error bound grows with it) is folded by the sort into ONE word
     // per handle.  A pair kernel beside which the next slab is sorted may read the maximum of that slab as well:
     // that only widens the filter's margin — more pairs take the exact path, which bins them as the contract does,
     // so the counts cannot change (the exact-path statistics can, by a few pairs).
-    unsigned *d_maxabs = d_misc;
-
-    struct Set {
-        float4 *pw1, *po1, *bb1, *bc1, *pw2, *po2, *bb2, *bc2;
-    };
-    auto set_of = [&](int b) {
-        Set s;
-        s.pw1 = h->d_pw1.as<float4>() + b * e_p1;
-        s.po1 = lazy_orig ? nullptr : h->d_po1.as<float4>() + b * e_p1;
-        s.bb1 = h->d_bb1.as<float4>() + b * e_b1;
-        s.bc1 = h->d_bb16_1.as<float4>() + b * e_c1;
-        s.pw2 = self ? s.pw1 : h->d_pw2.as<float4>() + b * e_p2;
-        s.po2 = self ? s.po1 : (lazy_orig ? nullptr : h->d_po2.as<float4>() + b * e_p2);
-        s.bb2 = self ? s.bb1 : h->d_bb2.as<float4>() + b * e_b2;
-        s.bc2 = self ? s.bc1 : h->d_bb16_2.as<float4>() + b * e_c2;
-        return s;
-    };
-    // the sort of frames [f0, f0 + nf) into a set: the big kernel (small_grid == 0) or `small_grid` persistent
-    // blocks of the small one
-    auto launch_sort = [&](const Set &s, int64_t f0, int64_t nf, hipStream_t stream, unsigned small_grid) {
-        // (Measured and dropped, round 3: the sort as a GATHER — slots noted per particle in LDS, rows written
-        // in slot order as whole lines — 0.66 ms per 1 000 frames against 0.74–0.82, +0.5 % on the step, but its
-        // 12-byte reads scattered over frames that are no longer in L2 fetch 4.0 MB per frame where the scatter's
-        // partial-sector stores cost 1.1: 6.5 MB per frame in all against 4.4.  Neither two blocks per CU (the
-        // kernel sits at 65 VGPRs: one over), float32 cell keys, a DPP box reduction nor a two-barrier scan moved
-        // the kernel's time: all 256 blocks of a round read, then write, in step — 25 µs counting from HBM, 81 µs
-        // writing rows — and the memory system sets the pace.)
-        const float *cells = tri ? d_tri + f0 * 9 : d_boxes + f0 * 6;
-        if (small_grid) {
-            auto sort = rdf_cell_sort_small_kernel<SORT_SMALL_THREADS>;
-            hipLaunchKernelGGL(sort, dim3(small_grid), dim3(SORT_SMALL_THREADS), sort_small_lds, stream, d_pos1 + f0 * n1 * 3,
-                               cells, (int)n1, (int)n1p, excl ? h->excl1 : 0, s.pw1, s.po1, s.bb1, s.bc1, d_maxabs,
-                               (int)nf);
-            if (!self)
-                hipLaunchKernelGGL(sort, dim3(small_grid), dim3(SORT_SMALL_THREADS), sort_small_lds, stream,
-                                   d_pos2 + f0 * n2 * 3, cells, (int)n2, (int)n2p, excl ? h->excl2 : 0, s.pw2,
-                                   s.po2, s.bb2, s.bc2, d_maxabs, (int)nf);
-            return;
-        }
-        auto sort = tri ? rdf_cell_sort_kernel<true> : rdf_cell_sort_kernel<false>;
-        hipLaunchKernelGGL(sort, dim3((unsigned)nf), dim3(SORT_THREADS), 0, stream, d_pos1 + f0 * n1 * 3, cells,
-                           (int)n1, (int)n1p, excl ? h->excl1 : 0, s.pw1, s.po1, s.bb1, s.bc1, d_maxabs);
-        if (!self)
-            hipLaunchKernelGGL(sort, dim3((unsigned)nf), dim3(SORT_THREADS), 0, stream, d_pos2 + f0 * n2 * 3,
-                               cells, (int)n2, (int)n2p, excl ? h->excl2 : 0, s.pw2, s.po2, s.bb2, s.bc2,
-                               d_maxabs);
-    };
-
-    auto slabs = [&]() -> int {
-        int64_t f0 = 0;
-        for (size_t k = 0; k < lens.size(); f0 += lens[k], ++k) {
-            const int64_t nf = lens[k];
-            const int b = beside ? int(k & 1) : 0;
-            const Set s = set_of(b);
-            h->last_offset = b * e_p1;
-            h->last_frames = nf;
-            h->last_n_pad = n1p;
-            h->last_lazy = lazy_orig;
-            if (!beside || k == 0)
-                launch_sort(s, f0, nf, h->stream, 0);
-            else
-                MDX_HIP(hipStreamWaitEvent(h->stream, h->ev_sorted[b], 0));
-            // blocks the pair kernel of this slab leaves to the sort of the next
-            int64_t holes = 0;
-            if (beside && k + 1 < lens.size()) {
-                const int64_t nf_next = lens[k + 1];
-                holes = ceil_div(ceil_div(S0 * nf_next, nf), 8) * 8;
-                holes = std::min<int64_t>(holes, 8 * (blocks_per_xcd / 2));
-                // the other set: free once the pair kernel of slab k - 1 has read it (before the first slab of a
-                // call: whatever the handle's stream held at the fork)
-                if (k > 0)
-                    MDX_HIP(hipStreamWaitEvent(h->side, h->ev_read[b ^ 1], 0));
-                launch_sort(set_of(b ^ 1), f0 + nf, nf_next, h->side, (unsigned)std::min<int64_t>(holes, nf_next));
-                MDX_HIP(hipEventRecord(h->ev_sorted[b ^ 1], h->side));
-                h->slabs_sorted_beside += 1;
-            }
-            CellArgs a{};
-            a.pw1 = s.pw1;
-            a.po1 = s.po1;
-            a.bb1 = s.bb1;
-            a.pw2 = s.pw2;
-            a.po2 = s.po2;
-            a.bb2 = s.bb2;
-            a.bb16_2 = s.bc2;
-            a.in1 = lazy_orig ? d_pos1 + f0 * n1 * 3 : nullptr;
-            a.in2 = lazy_orig ? d_pos2 + f0 * n2 * 3 : nullptr;
-            a.n1_in = (int)n1;
-            a.n2_in = (int)n2;
-            a.tags_everywhere = (self && h->excl1 == 1 && h->excl2 == 1) ? 0 : 1;
-            a.boxes = tri ? nullptr : d_boxes + f0 * 6;
-            a.tri = tri ? d_tri + f0 * 9 : nullptr;
-            a.thresh = h->d_thresh.as<double>();
-            a.counts = h->d_counts.as<unsigned long long>();
-            a.maxabs_bits = d_maxabs;
-            a.exact_counter = h->d_stats.as<unsigned long long>();
-            a.tilepair_counter = a.exact_counter + 1;
-            a.clock_counter = h->timer.enabled ? a.exact_counter + 3 : nullptr;
-            a.t_lo = h->t_lo;
-            a.t_hi = h->t_hi;
-            a.r0 = h->edges.front();
-            a.r1 = h->edges.back();
-            a.n1p = (int)n1p;
-            a.n2p = (int)n2p;
-            a.n_bins = h->n_bins;
-            a.n_hist = n_hist;
-            a.n_rep = h->n_rep;
-            a.self = self ? 1 : 0;
-            // persistent blocks: what the chip holds at once (blocks per CU from the kernel's own occupancy), a
-            // multiple of 8 so that every XCD gets the same number — less the holes of a sort that runs beside
-            // this launch; fewer when there is less work than that
-            a.work = h->d_work.as<unsigned>();
-            {
-                const char *fu = getenv("MDX_RDF_LDS_FLUSH_UNITS");   // test hook: flush the LDS bins (much) more often
-                // (the cap: 1024 + 2 x flush_units <= 2^18, see the pair kernel)
-                const long long cap = (1 << 17) - 512;
-                a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), cap) : (unsigned)cap;
-            }
-            // items: an i tile against a chunk of its candidate j tiles
-            a.chunks = rdf_cell_chunks(n2p, skip, nullptr);
-            const int64_t tiles = (n1p / 128) * a.chunks;   // items of a frame
-            // (frames per launch: the item index is 32 bits wide)
-            const int64_t launch_frames = std::max<int64_t>(8, std::min<int64_t>(32768, ((int64_t(1) << 30) / tiles) * 8));
-            // (sized for the longest slab: it does not grow, and so is not freed, between the launches of a call)
-            MDX_TRY(h->d_frame_geo.ensure(sizeof(float) * CELL_GEO_FLOATS * size_t(std::min<int64_t>(launch_frames, slab))));
-            a.frame_geo = h->d_frame_geo.as<float>();
-            hipEvent_t ev = h->timer.begin();
-            for (int64_t g0 = 0; g0 < nf; g0 += launch_frames) {
-                a.frame0 = (int)g0;
-                a.n_frames = (int)std::min<int64_t>(launch_frames, nf - g0);
-                a.spread = a.n_frames < 8 ? 1 : 0;
-                const int64_t items_per_xcd = a.spread ? ceil_div(int64_t(a.n_frames) * tiles, 8)
-                                                       : ceil_div(a.n_frames, 8) * tiles;
-                const unsigned grid = 8u * (unsigned)std::min<int64_t>(blocks_per_xcd - holes / 8, items_per_xcd);
-                MDX_HIP(hipMemsetAsync(h->d_work.ptr, 0, CELL_WORK_BYTES, h->stream));
-                // the frames' constants, once per frame: behind this slab's sort (and the previous launch, which
-                // read the table), in front of the items that load them
-                hipLaunchKernelGGL(tri ? rdf_cell_frame_geo_kernel<true> : rdf_cell_frame_geo_kernel<false>,
-                                   dim3((unsigned)ceil_div(a.n_frames, 256)), dim3(256), 0, h->stream, a);
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, h->stream, a);
-            }
-            h->timer.end(ev);
-            MDX_HIP(hipGetLastError());
-            if (beside)
-                MDX_HIP(hipEventRecord(h->ev_read[b], h->stream));
-        }
-        return MDX_OK;
-    };
-    int rc = MDX_OK;
-    if (beside) {
-        // fork: what the caller queued on the handle's stream (the unpack kernel of the file route, an earlier
-        // call's pair kernels that still read a set) is ahead of everything on the side stream; join: the handle's
-        // stream ends behind the side stream's last kernel — on the error exits too — so that synchronize(),
-        // counts(), reset() and close() mean what they meant
-        MDX_HIP(hipEventRecord(h->ev_fork, h->stream));
-        MDX_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-        rc = slabs();
-        hipError_t e = hipEventRecord(h->ev_join, h->side);
-        if (e == hipSuccess)
-            e = hipStreamWaitEvent(h->stream, h->ev_join, 0);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(h->side);
-            if (rc == MDX_OK)
-                rc = fail(MDX_ERR_HIP, "joining the sort stream failed: %s", hipGetErrorString(e));
-        }
-    } else {
-        rc = slabs();
+    a.maxabs_bits = h->d_misc.as<unsigned>();
+    a.exact_counter = h->d_stats.as<unsigned long long>();
+    a.tilepair_counter = a.exact_counter + 1;
+    a.clock_counter = h->timer.enabled ? a.exact_counter + 3 : nullptr;
+    a.t_lo = h->t_lo;
+    a.t_hi = h->t_hi;
+    a.r0 = h->edges.front();
+    a.r1 = h->edges.back();
+    a.n1p = (int)p.n1p;
+    a.n2p = (int)p.n2p;
+    a.n_bins = h->n_bins;
+    a.n_hist = p.hist.n_hist;
+    a.n_rep = h->n_rep;
+    a.self = p.self ? 1 : 0;
+    a.work = h->d_work.as<unsigned>();
+    {
+        const char *fu = getenv("MDX_RDF_LDS_FLUSH_UNITS");   // test hook: flush the LDS bins (much) more often
+        // (the cap: 1024 + 2 x flush_units <= 2^18, see the pair kernel)
+        const long long cap = (1 << 17) - 512;
+        a.flush_units = fu ? (unsigned)std::min<long long>(std::max<long long>(atoll(fu), 1), cap) : (unsigned)cap;
     }
-    MDX_TRY(rc);
-    h->pairs_evaluated += n_frames * n1 * n2;
+    // items: an i tile against a chunk of its candidate j tiles
+    a.chunks = (int)p.grid_x;
+    const int64_t tiles = p.tiles1 * p.grid_x;   // items of a frame
+    // (frames per launch: the item index is 32 bits wide)
+    const int64_t launch_frames = std::max<int64_t>(8, std::min<int64_t>(32768, ((int64_t(1) << 30) / tiles) * 8));
+    // (sized for the longest slab: it does not grow, and so is not freed, between the launches of a call)
+    MDX_TRY(h->d_frame_geo.ensure(sizeof(float) * CELL_GEO_FLOATS * size_t(std::min<int64_t>(launch_frames, p.slab))));
+    a.frame_geo = h->d_frame_geo.as<float>();
+    hipEvent_t ev = h->timer.begin();
+    for (int64_t g0 = 0; g0 < nf; g0 += launch_frames) {
+        a.frame0 = (int)g0;
+        a.n_frames = (int)std::min<int64_t>(launch_frames, nf - g0);
+        a.spread = a.n_frames < 8 ? 1 : 0;
+        // persistent blocks: what the chip holds at once (blocks per CU from the kernel's own occupancy), a
+        // multiple of 8 so that every XCD gets the same number — less the holes of a sort that runs beside
+        // this launch; fewer when there is less work than that
+        const int64_t items_per_xcd = a.spread ? ceil_div(int64_t(a.n_frames) * tiles, 8)
+                                               : ceil_div(a.n_frames, 8) * tiles;
+        const unsigned grid = 8u * (unsigned)std::min<int64_t>(h->occ_blocks_per_xcd - holes / 8, items_per_xcd);
+        MDX_HIP(hipMemsetAsync(h->d_work.ptr, 0, CELL_WORK_BYTES, h->stream));
+        // the frames' constants, once per frame: behind this slab's sort (and the previous launch, which
+        // read the table), in front of the items that load them
+        hipLaunchKernelGGL(r.tri() ? rdf_cell_frame_geo_kernel<true> : rdf_cell_frame_geo_kernel<false>,
+                           dim3((unsigned)ceil_div(a.n_frames, 256)), dim3(256), 0, h->stream, a);
+        hipLaunchKernelGGL(r.kern, dim3(grid), dim3(256), p.hist.lds, h->stream, a);
+    }
+    h->timer.end(ev);
+    MDX_HIP(hipGetLastError());
     return MDX_OK;
 }
 
-// min_edge: the shortest box length over the frames (accumulate_cell), 0 where the caller has no boxes
-static int accumulate_ortho(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
-                            int64_t n2, const float *d_boxes, int64_t n_frames, float min_edge = 0.f)
+// slab after slab: its sort (unless it ran beside the slab before), the sort of the next slab on the side stream,
+// its pair kernel
+static int cell_slabs(const CellRun &r)
 {
-    if (n_frames == 0 || n1 == 0 || n2 == 0)
-        return MDX_OK;
-    if (h->reduced_global)
-        return fail(MDX_ERR_STATE, "handle holds all-reduced counts; call mdx_rdf_reset() first");
-    const bool same = (d_pos2 == nullptr || (d_pos2 == d_pos1 && n2 == n1));
-    if (d_pos2 == nullptr) {
-        d_pos2 = d_pos1;
-        n2 = n1;
+    mdx_rdf *h = r.h;
+    int64_t f0 = 0;
+    for (size_t k = 0; k < r.lens.size(); f0 += r.lens[k], ++k) {
+        const int64_t nf = r.lens[k];
+        const int b = r.beside ? int(k & 1) : 0;
+        const CellSet s = cell_set_of(r, b);
+        h->last_offset = b * r.side[0].e_p;
+        h->last_frames = nf;
+        if (!r.beside || k == 0)
+            cell_launch_sort(r, s, f0, nf, h->stream, 0);
+        else
+            MDX_HIP(hipStreamWaitEvent(h->stream, h->ev_sorted[b], 0));
+        // blocks the pair kernel of this slab leaves to the sort of the next
+        int64_t holes = 0;
+        if (r.beside && k + 1 < r.lens.size()) {
+            const int64_t nf_next = r.lens[k + 1];
+            holes = ceil_div(ceil_div(CELL_SORT_BESIDE_BLOCKS * nf_next, nf), 8) * 8;
+            holes = std::min<int64_t>(holes, 8 * (h->occ_blocks_per_xcd / 2));
+            // the other set: free once the pair kernel of slab k - 1 has read it (before the first slab of a
+            // call: whatever the handle's stream held at the fork)
+            if (k > 0)
+                MDX_HIP(hipStreamWaitEvent(h->side, h->ev_read[b ^ 1], 0));
+            cell_launch_sort(r, cell_set_of(r, b ^ 1), f0 + nf, nf_next, h->side,
+                             (unsigned)std::min<int64_t>(holes, nf_next));
+            MDX_HIP(hipEventRecord(h->ev_sorted[b ^ 1], h->side));
+            h->slabs_sorted_beside += 1;
+        }
+        MDX_TRY(cell_launch_pairs(r, s, f0, nf, holes));
+        if (r.beside)
+            MDX_HIP(hipEventRecord(h->ev_read[b], h->stream));
     }
-    bool excl, self;
-    rdf_pair_flags(same, h->excl1, h->excl2, &self, &excl);
-    MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
-
-    const int algo = rdf_resolve_ortho_algo(h->algo, d_boxes != nullptr);
-    if (algo == MDX_RDF_ALGO_CELL)
-        return accumulate_cell(h, d_pos1, n1, d_pos2, n2, d_boxes, n_frames, self, excl, nullptr, min_edge);
-    const int ipt = rdf_tile_ipt(n1, n2);
-    const int T = 256 * ipt;
-    const int64_t n1p = ceil_div(n1, T) * T, n2p = ceil_div(n2, T) * T;
-
-    // frames are processed in slabs so the packed copies stay bounded
-    const int64_t slab = rdf_tile_slab_frames(n1p, n2p, self);
-    MDX_TRY(h->d_pack1.ensure(size_t(16) * n1p * std::min(slab, n_frames)));
-    if (!self)
-        MDX_TRY(h->d_pack2.ensure(size_t(16) * n2p * std::min(slab, n_frames)));
-
-    unsigned *d_misc = h->d_misc.as<unsigned>();   // [0] maxabs bits, [1] status, [2..3] exact counter
-    if (d_boxes) {
-        hipLaunchKernelGGL(rdf_check_boxes_kernel, dim3((unsigned)ceil_div(n_frames, 256)),
-                           dim3(256), 0, h->stream, d_boxes, n_frames, d_misc + 1);
-    }
-    for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
-        const int64_t nf = std::min(slab, n_frames - f0);
-        hipLaunchKernelGGL(rdf_pack_kernel, dim3((unsigned)(n1p / 256), (unsigned)nf), dim3(256), 0,
-                           h->stream, d_pos1 + f0 * n1 * 3, h->d_pack1.as<float4>(), (int)n1,
-                           (int)n1p, excl ? h->excl1 : 0, d_misc);
-        if (!self)
-            hipLaunchKernelGGL(rdf_pack_kernel, dim3((unsigned)(n2p / 256), (unsigned)nf), dim3(256),
-                               0, h->stream, d_pos2 + f0 * n2 * 3, h->d_pack2.as<float4>(), (int)n2,
-                               (int)n2p, excl ? h->excl2 : 0, d_misc);
-        RdfArgs a{};
-        a.p1 = h->d_pack1.as<float4>();
-        a.p2 = self ? a.p1 : h->d_pack2.as<float4>();
-        a.n1p = (int)n1p;
-        a.n2p = (int)n2p;
-        a.nt1 = (int)(n1p / T);
-        a.nt2 = (int)(n2p / T);
-        a.self = self ? 1 : 0;
-        a.boxes = d_boxes ? d_boxes + f0 * 6 : nullptr;
-        a.n_bins = h->n_bins;
-        a.thresh = h->d_thresh.as<double>();
-        a.t_lo = h->t_lo;
-        a.t_hi = h->t_hi;
-        a.r0 = h->edges.front();
-        a.r1 = h->edges.back();
-        a.counts = h->d_counts.as<unsigned long long>();
-        a.n_rep = h->n_rep;
-        a.maxabs_bits = d_misc;
-        a.exact_counter = h->d_stats.as<unsigned long long>();
-        MDX_TRY(launch_tiles(h, a, algo, ipt, d_boxes != nullptr, excl, nf));
-        const int64_t tile_pairs = self ? int64_t(a.nt1) * (a.nt1 + 1) / 2 : int64_t(a.nt1) * a.nt2;
-        h->pairs_bruteforce += nf * tile_pairs * T * T;
-    }
-    h->pairs_evaluated += n_frames * n1 * n2;
     return MDX_OK;
 }
 
-// Triclinic frames: the culled cell-sorted kernel, or brute-force tiles with the 27-image search in double on every
-// pair (rdf_tri_culled).
-static int accumulate_triclinic(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2,
-                                int64_t n2, const float *h_boxes, int64_t n_frames)
+// cell_slabs between a fork and a join of the side stream.  Fork: what the caller queued on the handle's stream (the
+// unpack kernel of the file route, an earlier call's pair kernels that still read a set) is ahead of everything on
+// the side stream; join: the handle's stream ends behind the side stream's last kernel — on the error exits too — so
+// that synchronize(), counts(), reset() and close() mean what they meant
+static int cell_slabs_forked(const CellRun &r)
 {
-    if (n_frames == 0 || n1 == 0 || n2 == 0)
-        return MDX_OK;
-    if (h->reduced_global)
-        return fail(MDX_ERR_STATE, "handle holds all-reduced counts; call mdx_rdf_reset() first");
-    const bool same = (d_pos2 == nullptr || (d_pos2 == d_pos1 && n2 == n1));
-    if (d_pos2 == nullptr) {
-        d_pos2 = d_pos1;
-        n2 = n1;
+    mdx_rdf *h = r.h;
+    MDX_HIP(hipEventRecord(h->ev_fork, h->stream));
+    MDX_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+    int rc = cell_slabs(r);
+    hipError_t e = hipEventRecord(h->ev_join, h->side);
+    if (e == hipSuccess)
+        e = hipStreamWaitEvent(h->stream, h->ev_join, 0);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->side);
+        if (rc == MDX_OK)
+            rc = fail(MDX_ERR_HIP, "joining the sort stream failed: %s", hipGetErrorString(e));
     }
-    bool excl, self;
-    rdf_pair_flags(same, h->excl1, h->excl2, &self, &excl);
-    MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
-    std::vector<float> tri;
-    MDX_TRY(rdf_tri_cells(h_boxes, n_frames, tri));
-    // the previous call's kernels may still read the cell matrices
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    MDX_TRY(h->d_tri.ensure(size_t(36) * n_frames));
-    MDX_HIP(hipMemcpyAsync(h->d_tri.ptr, tri.data(), size_t(36) * n_frames, hipMemcpyHostToDevice,
-                           h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));   // `tri` leaves scope
+    return rc;
+}
 
-    if (rdf_tri_culled(h->algo, n1, n2, h->edges.back(), tri.data(), n_frames))
-        return accumulate_cell(h, d_pos1, n1, d_pos2, n2, nullptr, n_frames, self,
-                               excl, h->d_tri.as<float>());
+// one run through the cell-sorted route
+static int accumulate_cell(mdx_rdf *h, const RdfRunPlan &p, const RdfFrames &in, int64_t n_frames)
+{
+    // (two-particle chunks take their boxes from the staged rows: a token chunk-box array)
+    auto side = [&](DeviceBuffer &pw, DeviceBuffer &po, DeviceBuffer &bb, DeviceBuffer &bc, int64_t n_pad) {
+        const size_t slab = size_t(p.slab);
+        return CellSide{&pw, &po, &bb, &bc, size_t(n_pad) * slab, size_t(n_pad / 64) * 2 * slab,
+                        CELL_CHUNK >= 4 ? size_t(n_pad / CELL_CHUNK) * 2 * slab : 16};
+    };
+    CellRun r{h, p, in, rdf_cell_kernel_of(p),
+              {side(h->d_pw1, h->d_po1, h->d_bb1, h->d_bb16_1, p.n1p), side(h->d_pw2, h->d_po2, h->d_bb2, h->d_bb16_2, p.n2p)},
+              false, {}};
+    MDX_TRY(cell_occupancy(h, reinterpret_cast<const void *>(r.kern), p.hist.lds));
+    MDX_TRY(cell_sort_beside(r, n_frames));
+    r.lens = cell_slab_lengths(p.slab, r.beside, n_frames);
+    MDX_TRY(r.beside ? cell_slabs_forked(r) : cell_slabs(r));
+    h->pairs_evaluated += n_frames * in.n1 * in.n2;
+    return MDX_OK;
+}
 
-    const int64_t n1p = ceil_div(n1, 256) * 256, n2p = ceil_div(n2, 256) * 256;
-    const int64_t slab = std::min<int64_t>(rdf_tile_slab_frames(n1p, n2p, self), n_frames);
-    MDX_TRY(h->d_pack1.ensure(size_t(16) * n1p * slab));
-    if (!self)
-        MDX_TRY(h->d_pack2.ensure(size_t(16) * n2p * slab));
+static auto rdf_tri_tile_kernel_of(const RdfRunPlan &p) -> void (*)(TriArgs)
+{
+    static void (*const kern[2][2])(TriArgs) = {   // [!EXCL][!GH]
+        {rdf_tri_tile_kernel<true, true>, rdf_tri_tile_kernel<true, false>},
+        {rdf_tri_tile_kernel<false, true>, rdf_tri_tile_kernel<false, false>}};
+    return kern[!p.excl][!p.hist.gh];
+}
 
-    const RdfHist hist = rdf_tile_hist(h->n_bins, 256);
-    const int n_hist = hist.n_hist;
-    const size_t lds = hist.lds;
-    const bool gh = hist.gh;
-    void (*kern)(TriArgs) = excl ? (gh ? rdf_tri_tile_kernel<true, true> : rdf_tri_tile_kernel<true, false>)
-                                 : (gh ? rdf_tri_tile_kernel<false, true> : rdf_tri_tile_kernel<false, false>);
-    if (lds > RDF_LDS_ATTR_LINE)
-        MDX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// Triclinic frames, brute-force tiles: the 27-image search in double on every pair.
+static int accumulate_tri_tiles(mdx_rdf *h, const RdfRunPlan &p, const RdfFrames &in, int64_t n_frames)
+{
     const double width = (h->edges.back() - h->edges.front()) / h->n_bins;
-    for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
-        const int64_t nf = std::min(slab, n_frames - f0);
-        const float *d_tri = h->d_tri.as<float>() + f0 * 9;
-        hipLaunchKernelGGL(rdf_tri_pack_kernel, dim3((unsigned)(n1p / 256), (unsigned)nf), dim3(256),
-                           0, h->stream, d_pos1 + f0 * n1 * 3, d_tri, h->d_pack1.as<float4>(),
-                           (int)n1, (int)n1p, excl ? h->excl1 : 0);
-        if (!self)
-            hipLaunchKernelGGL(rdf_tri_pack_kernel, dim3((unsigned)(n2p / 256), (unsigned)nf),
-                               dim3(256), 0, h->stream, d_pos2 + f0 * n2 * 3, d_tri,
-                               h->d_pack2.as<float4>(), (int)n2, (int)n2p, excl ? h->excl2 : 0);
-        TriArgs a{};
-        a.p1 = h->d_pack1.as<float4>();
-        a.p2 = self ? a.p1 : h->d_pack2.as<float4>();
-        a.tri = d_tri;
-        a.thresh = h->d_thresh.as<double>();
-        a.counts = h->d_counts.as<unsigned long long>();
-        a.t_lo = h->t_lo;
-        a.t_hi = h->t_hi;
+    return tile_slabs(h, p, in, n_frames, rdf_tri_tile_kernel_of(p), [&](TriArgs &a, int64_t f0, int64_t nf) {
+        a.tri = in.tri + f0 * 9;
+        hipLaunchKernelGGL(rdf_tri_pack_kernel, dim3((unsigned)(p.n1p / 256), (unsigned)nf), dim3(256),
+                           0, h->stream, in.pos1 + f0 * in.n1 * 3, a.tri, h->d_pack1.as<float4>(),
+                           (int)in.n1, (int)p.n1p, p.excl ? h->excl1 : 0);
+        if (!p.self)
+            hipLaunchKernelGGL(rdf_tri_pack_kernel, dim3((unsigned)(p.n2p / 256), (unsigned)nf),
+                               dim3(256), 0, h->stream, in.pos2 + f0 * in.n2 * 3, a.tri,
+                               h->d_pack2.as<float4>(), (int)in.n2, (int)p.n2p, p.excl ? h->excl2 : 0);
         a.r0f = (float)h->edges.front();
         a.inv_wf = (float)(1.0 / width);
-        a.n1p = (int)n1p;
-        a.n2p = (int)n2p;
-        a.nt1 = (int)(n1p / 256);
-        a.nt2 = (int)(n2p / 256);
-        a.n_bins = h->n_bins;
-        a.n_hist = n_hist;
-        a.n_rep = h->n_rep;
-        a.chunk = rdf_tile_chunk(self);
-        a.self = self ? 1 : 0;
-        a.frame0 = 0;
-        hipEvent_t ev = h->timer.begin();
-        dim3 grid((unsigned)ceil_div(a.nt2, a.chunk), (unsigned)a.nt1, (unsigned)nf);
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, h->stream, a);
-        h->timer.end(ev);
-        MDX_HIP(hipGetLastError());
-        const int64_t tile_pairs = self ? int64_t(a.nt1) * (a.nt1 + 1) / 2 : int64_t(a.nt1) * a.nt2;
-        h->pairs_bruteforce += nf * tile_pairs * 256 * 256;
-    }
-    h->pairs_evaluated += n_frames * n1 * n2;
-    return MDX_OK;
+    });
 }
 
-// Frames are dispatched by cell type: orthorhombic runs take the filter / cell-sorted kernels,
-// triclinic runs the 27-image kernel.  h_boxes: the same boxes on the host, or nullptr (then
-// they are copied back from d_boxes — 24 bytes per frame and one stream synchronisation).
-static int accumulate_device_points(mdx_rdf *h, const float *d_pos1, int64_t n1,
-                                    const float *d_pos2, int64_t n2, const float *d_boxes,
-                                    const float *h_boxes, int64_t n_frames);
+// Every accumulate entry point ends here, with points on the device.  Frames are dispatched in runs of one cell kind
+// (rdf_next_run): each run is planned once (rdf_plan_run) and goes to the route of its plan's family.  h_boxes: the
+// same boxes on the host, or nullptr (then they are copied back from d_boxes — 24 bytes per frame and one stream
+// synchronisation).
+static int accumulate_device_points(mdx_rdf *h, const float *d_pos1, int64_t n1, const float *d_pos2, int64_t n2,
+                                    const float *d_boxes, const float *h_boxes, int64_t n_frames)
+{
+    if (n_frames == 0 || n1 == 0 || n2 == 0)
+        return MDX_OK;
+    if (h->reduced_global)
+        return fail(MDX_ERR_STATE, "handle holds all-reduced counts; call mdx_rdf_reset() first");
+    const bool same = (d_pos2 == nullptr || (d_pos2 == d_pos1 && n2 == n1));
+    if (d_pos2 == nullptr) {
+        d_pos2 = d_pos1;
+        n2 = n1;
+    }
+    MDX_TRY(rdf_check_set_sizes(n1, n2));
+    const RdfConfig cfg{h->n_bins, h->edges.front(), h->edges.back(), h->excl1, h->excl2, h->algo};
+    std::vector<float> copy, tri;
+    if (d_boxes && !h_boxes) {
+        copy.resize(size_t(6) * n_frames);
+        MDX_HIP(hipMemcpyAsync(copy.data(), d_boxes, size_t(24) * n_frames, hipMemcpyDeviceToHost,
+                               h->stream));
+        MDX_HIP(hipStreamSynchronize(h->stream));
+        h_boxes = copy.data();
+    }
+    for (int64_t f0 = 0, f1; f0 < n_frames; f0 = f1) {
+        bool ortho = true;
+        float min_edge = 0.f;
+        f1 = d_boxes ? rdf_next_run(h_boxes, f0, n_frames, &ortho, &min_edge) : n_frames;
+        const int64_t nf = f1 - f0;
+        RdfFrames in{d_pos1 + f0 * n1 * 3, d_pos2 + f0 * n2 * 3, n1, n2, nullptr, nullptr};
+        if (!ortho)
+            MDX_TRY(rdf_tri_cells(h_boxes + 6 * f0, nf, tri));
+        const RdfRunPlan p = rdf_plan_run(cfg, n1, n2, same, d_boxes != nullptr, ortho, min_edge,
+                                          ortho ? nullptr : tri.data(), nf);
+        h->last_plan = p;
+        if (ortho && d_boxes) {
+            // once per orthorhombic run, ahead of its packs and sorts; mdx_rdf_synchronize reads the verdict
+            in.boxes = d_boxes + f0 * 6;
+            hipLaunchKernelGGL(rdf_check_boxes_kernel, dim3((unsigned)ceil_div(nf, 256)), dim3(256), 0, h->stream,
+                               in.boxes, nf, h->d_misc.as<unsigned>() + 1);
+        } else if (!ortho) {
+            // the previous call's kernels may still read the cell matrices
+            MDX_HIP(hipStreamSynchronize(h->stream));
+            MDX_TRY(h->d_tri.ensure(size_t(36) * nf));
+            MDX_HIP(hipMemcpyAsync(h->d_tri.ptr, tri.data(), size_t(36) * nf, hipMemcpyHostToDevice, h->stream));
+            MDX_HIP(hipStreamSynchronize(h->stream));   // `tri` is filled again for the next run
+            in.tri = h->d_tri.as<float>();
+        }
+        switch (p.family) {
+        case RDF_FAMILY_TRI_BRUTE: MDX_TRY(accumulate_tri_tiles(h, p, in, nf)); break;
+        case RDF_FAMILY_CELL_ORTHO:
+        case RDF_FAMILY_TRI_CULLED: MDX_TRY(accumulate_cell(h, p, in, nf)); break;
+        default: MDX_TRY(accumulate_tiles(h, p, in, nf));
+        }
+    }
+    return MDX_OK;
+}
 
 // Entry of every accumulate variant: sets with a grouping are reduced to centres of mass first.
 // drop_axis: dst = src with coordinate `axis` set to zero (may run in place)
@@ -1252,35 +1354,6 @@ static int accumulate_device(mdx_rdf *h, const float *d_pos1, int64_t n1, const 
     return accumulate_device_points(h, pts[0], n[0], pts[1], n[1], d_boxes, h_boxes, n_frames);
 }
 
-static int accumulate_device_points(mdx_rdf *h, const float *d_pos1, int64_t n1,
-                                    const float *d_pos2, int64_t n2, const float *d_boxes,
-                                    const float *h_boxes, int64_t n_frames)
-{
-    if (!d_boxes || n_frames == 0)
-        return accumulate_ortho(h, d_pos1, n1, d_pos2, n2, d_boxes, n_frames);
-    std::vector<float> copy;
-    if (!h_boxes) {
-        copy.resize(size_t(6) * n_frames);
-        MDX_HIP(hipMemcpyAsync(copy.data(), d_boxes, size_t(24) * n_frames, hipMemcpyDeviceToHost,
-                               h->stream));
-        MDX_HIP(hipStreamSynchronize(h->stream));
-        h_boxes = copy.data();
-    }
-    for (int64_t f0 = 0; f0 < n_frames;) {
-        bool ortho;
-        float min_edge;
-        const int64_t f1 = rdf_next_run(h_boxes, f0, n_frames, &ortho, &min_edge);
-        const float *p1 = d_pos1 + f0 * n1 * 3;
-        const float *p2 = d_pos2 ? d_pos2 + f0 * n2 * 3 : nullptr;
-        if (ortho)
-            MDX_TRY(accumulate_ortho(h, p1, n1, p2, n2, d_boxes + f0 * 6, f1 - f0, min_edge));
-        else
-            MDX_TRY(accumulate_triclinic(h, p1, n1, p2, n2, h_boxes + 6 * f0, f1 - f0));
-        f0 = f1;
-    }
-    return MDX_OK;
-}
-
 static int check_host_boxes(const float *boxes, int64_t n_frames)
 {
     for (int64_t f = 0; boxes && f < n_frames; ++f) {
@@ -1338,12 +1411,7 @@ extern "C" {
 int mdx_rdf_create(mdx_rdf_t *out, int dev, int n_bins, const double *edges, int64_t excl1,
                    int64_t excl2, int algo)
 {
-    MDX_REQUIRE(out && edges, "NULL argument");
-    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 20), "n_bins=%d out of range", n_bins);
-    MDX_REQUIRE((excl1 > 0) == (excl2 > 0) && excl1 >= 0 && excl2 >= 0,
-                "exclusion must be two positive integers (or 0, 0 for none)");
-    MDX_REQUIRE(algo >= MDX_RDF_ALGO_AUTO && algo <= MDX_RDF_ALGO_CELL, "unknown algo %d", algo);
-    MDX_TRY(rdf_check_edges(n_bins, edges));
+    MDX_TRY(rdf_check_engine_args(out, n_bins, edges, excl1, excl2, algo));
     MDX_TRY(set_device(dev));
     mdx_rdf *h = new mdx_rdf();
     h->dev = dev;
@@ -1415,90 +1483,36 @@ int mdx_rdf_filter_constants(int n_bins, double r0, double r1, const float box[3
 int mdx_rdf_plan(int n_bins, const double *edges, int64_t excl1, int64_t excl2, int algo, int64_t n1, int64_t n2,
                  int same, const float *boxes, int64_t n_frames, int64_t out[MDX_RDF_PLAN_SLOTS])
 {
-    MDX_REQUIRE(edges && out, "NULL argument");
-    MDX_REQUIRE(n_bins >= 1 && n_bins <= (1 << 20), "n_bins=%d out of range", n_bins);
-    MDX_REQUIRE((excl1 > 0) == (excl2 > 0) && excl1 >= 0 && excl2 >= 0,
-                "exclusion must be two positive integers (or 0, 0 for none)");
-    MDX_REQUIRE(algo >= MDX_RDF_ALGO_AUTO && algo <= MDX_RDF_ALGO_CELL, "unknown algo %d", algo);
-    MDX_TRY(rdf_check_edges(n_bins, edges));
+    MDX_TRY(rdf_check_engine_args(out, n_bins, edges, excl1, excl2, algo));
     if (same)
         n2 = n1;
     MDX_REQUIRE(n1 >= 1 && n2 >= 1 && n_frames >= 1, "bad size");
-    MDX_REQUIRE(n1 < (int64_t(1) << 30) && n2 < (int64_t(1) << 30), "too many particles");
+    MDX_TRY(rdf_check_set_sizes(n1, n2));
     bool ortho = true;
     float min_edge = 0.f;
+    std::vector<float> tri;
     if (boxes) {
         MDX_TRY(check_host_boxes(boxes, n_frames));
         const int64_t f1 = rdf_next_run(boxes, 0, n_frames, &ortho, &min_edge);
         MDX_REQUIRE(f1 == n_frames,
                     "frame %lld: orthorhombic and triclinic frames in one run (plan each run of one kind)",
                     (long long)f1);
+        if (!ortho)
+            MDX_TRY(rdf_tri_cells(boxes, n_frames, tri));
     }
-    bool self, excl;
-    rdf_pair_flags(same != 0, excl1, excl2, &self, &excl);
-    for (int k = 0; k < MDX_RDF_PLAN_SLOTS; ++k)
-        out[k] = 0;
-    const double r0 = edges[0], r1 = edges[n_bins];
-    int family;
-    bool culled = false;
-    if (ortho) {
-        const int a = rdf_resolve_ortho_algo(algo, boxes != nullptr);
-        family = a == MDX_RDF_ALGO_CELL ? RDF_FAMILY_CELL_ORTHO
-                                        : a == MDX_RDF_ALGO_EXACT_F64 ? RDF_FAMILY_TILE_EXACT : RDF_FAMILY_TILE_FILTER;
-    } else {
-        std::vector<float> tri;
-        MDX_TRY(rdf_tri_cells(boxes, n_frames, tri));
-        culled = rdf_tri_culled(algo, n1, n2, r1, tri.data(), n_frames);
-        family = culled ? RDF_FAMILY_TRI_CULLED : RDF_FAMILY_TRI_BRUTE;
-    }
-    out[0] = family;
-    out[2] = self;
-    out[3] = excl;
-    out[4] = boxes != nullptr;
-    if (family == RDF_FAMILY_CELL_ORTHO || family == RDF_FAMILY_TRI_CULLED) {
-        const bool tri = family == RDF_FAMILY_TRI_CULLED;
-        const int64_t n1p = ceil_div(n1, 128) * 128, n2p = ceil_div(n2, 128) * 128;
-        const RdfHist hist = rdf_cell_hist(n_bins);
-        const bool skip = rdf_cell_skip(tri, r1, min_edge);
-        int64_t tiles_per_chunk = 0;
-        const int chunks = rdf_cell_chunks(n2p, skip, &tiles_per_chunk);
-        const int64_t slab = rdf_cell_slab_frames(n1p, n2p, self, n_frames);
-        out[1] = 1;
-        out[5] = r0 > 0.0;
-        out[6] = skip;
-        out[7] = hist.gh;
-        out[8] = hist.gh ? 0 : hist.n_hist;
-        out[9] = (int64_t)hist.lds;
-        out[10] = 0;   // the cell-sorted launches never ask for the attribute
-        out[11] = n1p;
-        out[12] = n2p;
-        out[13] = n1p / 128;
-        out[14] = n2p / 64;
-        out[15] = tiles_per_chunk;
-        out[16] = chunks;
-        out[17] = slab;
-        out[18] = ceil_div(n_frames, slab);
-        out[19] = rdf_cell_lazy_orig(tri, excl1, excl2);
-        return MDX_OK;
-    }
-    const int ipt = family == RDF_FAMILY_TRI_BRUTE ? 1 : rdf_tile_ipt(n1, n2);
-    const int T = 256 * ipt;
-    const int64_t n1p = ceil_div(n1, T) * T, n2p = ceil_div(n2, T) * T;
-    const RdfHist hist = rdf_tile_hist(n_bins, T);
-    const int64_t slab = std::min<int64_t>(rdf_tile_slab_frames(n1p, n2p, self), n_frames);
-    out[1] = ipt;
-    out[7] = hist.gh;
-    out[8] = hist.gh ? 0 : hist.n_hist;
-    out[9] = (int64_t)hist.lds;
-    out[10] = hist.lds > RDF_LDS_ATTR_LINE;
-    out[11] = n1p;
-    out[12] = n2p;
-    out[13] = n1p / T;
-    out[14] = n2p / T;
-    out[15] = rdf_tile_chunk(self);
-    out[16] = ceil_div(n2p / T, out[15]);
-    out[17] = slab;
-    out[18] = ceil_div(n_frames, slab);
+    const RdfConfig cfg{n_bins, edges[0], edges[n_bins], excl1, excl2, algo};
+    rdf_plan_slots(rdf_plan_run(cfg, n1, n2, same != 0, boxes != nullptr, ortho, min_edge,
+                                ortho ? nullptr : tri.data(), n_frames), out);
+    return MDX_OK;
+}
+
+// The plan of the handle's most recent run, as it was launched.
+int mdx_rdf_last_plan(mdx_rdf_t h, int64_t out[MDX_RDF_PLAN_SLOTS])
+{
+    MDX_REQUIRE(h && out, "NULL argument");
+    if (h->last_plan.n_slabs == 0)
+        return fail(MDX_ERR_STATE, "no run since the handle was created or reset");
+    rdf_plan_slots(h->last_plan, out);
     return MDX_OK;
 }
 
@@ -1551,6 +1565,7 @@ int mdx_rdf_reset(mdx_rdf_t h)
     h->pairs_bruteforce = 0;
     h->slabs_sorted_beside = 0;
     h->reduced_global = false;
+    h->last_plan = RdfRunPlan();
     return MDX_OK;
 }
 
@@ -1774,14 +1789,14 @@ int mdx_rdf_debug_sorted(mdx_rdf_t h, int64_t frame, int64_t n_pad, float *pw, f
     MDX_REQUIRE(h && pw && po, "NULL argument");
     MDX_TRY(set_device(h->dev));
     MDX_HIP(hipStreamSynchronize(h->stream));
-    MDX_REQUIRE(h->last_frames > 0, "no slab has gone through the cell-sorted path yet");
+    MDX_REQUIRE(h->last_frames > 0 && h->last_plan.cell(), "no slab has gone through the cell-sorted path yet");
     MDX_REQUIRE(frame >= 0 && frame < h->last_frames, "frame %lld outside the last slab (%lld frames)",
                 (long long)frame, (long long)h->last_frames);
-    MDX_REQUIRE(n_pad == h->last_n_pad, "n_pad is %lld for the last slab", (long long)h->last_n_pad);
+    MDX_REQUIRE(n_pad == h->last_plan.n1p, "n_pad is %lld for the last slab", (long long)h->last_plan.n1p);
     // the slab's own set of sorted copies (two sets alternate when the sort runs beside the pair kernel)
     MDX_HIP(hipMemcpy(pw, h->d_pw1.as<float4>() + h->last_offset + frame * n_pad, size_t(16) * n_pad,
                       hipMemcpyDeviceToHost));
-    if (h->last_lazy)
+    if (h->last_plan.lazy_orig)
         // exclusion 0 or 1: no sorted copy of the original coordinates exists (the exact path reads the
         // incoming frame by the tag in pw[..].w); say so instead of returning something else in its place
         return fail(MDX_ERR_STATE, "the last slab has no sorted originals (exclusion 0 or 1): pw is filled, "

@@ -62,8 +62,12 @@ def test_route(c, monkeypatch):
     for _ in range(c.repeats):
         eng = _core.RdfEngine(rc.edges_of(c), c.excl, algo=c.algo)
         eng.accumulate(pos1, pos2, boxes)
-        got, st = eng.counts(), eng.stats()
+        got, st, ran = eng.counts(), eng.stats(), eng.last_plan()
         eng.close()
+        # what was launched is what was planned (the host route cuts a call into pieces of its own, each a run with
+        # slabs of its own: the two slab fields describe the last piece, not the call)
+        assert {k: v for k, v in ran.items() if k not in ("slab_frames", "n_slabs")} == \
+            {k: v for k, v in p.items() if k not in ("slab_frames", "n_slabs")}
         assert np.array_equal(got, want), (np.nonzero(got - want)[0][:10], (got - want)[np.nonzero(got - want)[0][:10]])
         assert st["pairs_evaluated"] == c.frames * c.n1 * (c.n1 if c.n2 is None else c.n2)
         if "exact" in c.claims:

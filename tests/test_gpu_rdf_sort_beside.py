@@ -1,6 +1,7 @@
 """
-RDF cell path: the sort of slab k + 1 beside the pair kernel of slab k (mdx_rdf.hip::accumulate_cell,
-rdf_cell_sort_small_kernel): two sets of sorted copies, a side stream, packed 16-bit cell counters.
+RDF cell path: the sort of slab k + 1 beside the pair kernel of slab k (mdx_rdf.hip::accumulate_cell with its
+cell_sort_beside and cell_slabs, rdf_cell_sort_small_kernel): two sets of sorted copies, a side stream, packed 16-bit
+cell counters.
 
 Bin counts must equal the CPU oracle (``oracle.cbind.c_radial_histogram``) bit for bit, and
 ``stats()["slabs_sorted_beside"]`` says whether the overlapped route ran.  MDX_RDF_SLAB_BYTES shrinks the
@@ -110,7 +111,7 @@ def test_join_caller_may_overwrite_after_synchronize(monkeypatch, walk, want_sel
     trajectory in HBM, and the counts are still those of the frames that were there.  Then reset() and a second
     call on the same engine, on the frames now in place.
 
-    What this does NOT cover: the explicit join at the exit of accumulate_cell.  On a successful call every kernel
+    What this does NOT cover: the explicit join at the exit of cell_slabs_forked.  On a successful call every kernel
     on the side stream is already followed by a pair kernel on the handle's stream that waits for it, so the counts
     here would be the same without the join; it matters on the error exits, which no test provokes."""
     a, _b, boxes = walk
