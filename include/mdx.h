@@ -1171,6 +1171,66 @@ int mdx_chi4_result(mdx_chi4_t h, int64_t *sums, int64_t *square_sums, int64_t *
 int mdx_chi4_stats(mdx_chi4_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations);
 int mdx_chi4_enable_timing(mdx_chi4_t h, int on);
 
+/* ---- hydrogen bonds: donor-H...acceptor counts, geometry and lifetimes ----------------------------------------------
+ * The incoming rows of a frame are n_rows distinct atoms; h_row[n_h] names the hydrogens, d_row[n_h] the donor each
+ * hydrogen is bonded to (it may repeat), a_row[n_a] the acceptors (int32 rows in [0, n_rows); no hydrogen and no
+ * acceptor twice, no row both, d_row[i] != h_row[i]; a donor may be an acceptor).  dims, frames, lags, origin_step and
+ * zero_dims as for mdx_prs_*.  Per frame, hydrogen i and acceptor j, with H, D, A their positions, in float64 with
+ * separate multiply and add and the minimum image w(x) = x - L * rint(x * (1.0 / L)) (+0.0 for a dropped component):
+ *     w_DA = w(A - D);  r2_DA = (w_DAx^2 + w_DAy^2) + w_DAz^2;  w_HD = w(D - H);  w_HA = w(A - H);
+ *     c = ((w_HDx*w_HAx + w_HDy*w_HAy) + w_HDz*w_HAz) / sqrt(r2_HD * r2_HA);
+ *     the pair is inside where r2_DA <= distance * distance and a_row[j] != d_row[i], and a bond where it is inside
+ *     and c <= cos_max (cos_max = cos(150 degrees): angles D-H...A of at least 150 degrees).
+ * A NaN r2_DA is not inside; an inside pair with NaN c (a hydrogen on its donor or on the acceptor) is no bond and
+ * counts in `degenerate`.  With B(f) the bonds of frame f:  bonds[f] = |B(f)|;  origin_counts, intermittent and
+ * continuous are those of mdx_prs_* with B for C;  donated[m], m = 0 ... max_neighbors: the (frame, hydrogen) cases
+ * with exactly m bonds;  distance_counts[b]: the bonds with b = #{m in 1 ... n_r - 1 : r2_DA >= r2_thresholds[m]};
+ * cosine_counts[b]: the bonds with b = #{m in 1 ... n_c - 1 : c <= cos_thresholds[m]}.
+ * distance: positive, finite, at most half the shortest kept box length.  cos_max in [-1, 1].  max_neighbors
+ * (1 ... 64): the bonds a hydrogen may hold in one frame.  A hydrogen that would hold more is never truncated
+ * silently: mdx_hb_synchronize, mdx_hb_result, mdx_hb_bonds and mdx_hb_geometry fail with MDX_ERR_INVALID_VALUE (the
+ * message names max_neighbors and the largest row seen) until mdx_hb_reset.  continuous == 0: only the frames a lag
+ * away from an origin are visited and continuous[] stays zero.  All results are integers and identical across the
+ * three input routes, across any split of the frames into calls or slabs, and after a reset
+ * (csrc/mdx_hbond_device.hpp).  The engine keeps max(lags) + one slab of frames of bond lists in HBM,
+ * (max_neighbors + 3) * n_h * 4 bytes each.  A handle touches its device with the first frame: mdx_hb_create,
+ * mdx_hb_set_bins and every argument error (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_hb *mdx_hb_t;
+int mdx_hb_create(mdx_hb_t *out, int dev, int64_t n_rows, int64_t n_h, const int32_t *h_row, const int32_t *d_row,
+                  int64_t n_a, const int32_t *a_row, double distance, double cos_max, int n_lags, const int64_t *lags,
+                  int64_t origin_step, const double *dims, int zero_dims, int max_neighbors, int continuous);
+/* r2_thresholds: float64 [n_r + 1], strictly increasing (thresholds of r2_DA, not of the distance); cos_thresholds:
+ * float64 [n_c + 1], strictly decreasing.  Only the inner ones are compared: the first and the last bin are open.
+ * Without this call both histograms have one bin.  Only before the first frame. */
+int mdx_hb_set_bins(mdx_hb_t h, int64_t n_r, const double *r2_thresholds, int64_t n_c, const double *cos_thresholds);
+int mdx_hb_destroy(mdx_hb_t h);
+/* Forgets the frames seen, the history and an overflowing row, and zeroes the results. */
+int mdx_hb_reset(mdx_hb_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history).  The results do
+ * not depend on it.  Only before the first frame. */
+int mdx_hb_set_slab_frames(mdx_hb_t h, int64_t frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n_rows. */
+int mdx_hb_accumulate(mdx_hb_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_hb_synchronize). */
+int mdx_hb_accumulate_device(mdx_hb_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames, const int32_t *index,
+                             int64_t n_index);
+int mdx_hb_accumulate_traj(mdx_hb_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames, const int32_t *index,
+                           int64_t n_index);
+int mdx_hb_synchronize(mdx_hb_t h);
+/* intermittent, continuous, origin_counts: int64 [n_lags] each. */
+int mdx_hb_result(mdx_hb_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts);
+/* out: int64 [n], the bonds of the first n frames seen. */
+int mdx_hb_bonds(mdx_hb_t h, int64_t *out, int64_t n);
+/* distance_counts: int64 [n_r]; cosine_counts: int64 [n_c]; donated: int64 [max_neighbors + 1]. */
+int mdx_hb_geometry(mdx_hb_t h, int64_t *distance_counts, int64_t *cosine_counts, int64_t *donated);
+/* evaluations: the contract's pair count so far, frames x (n_h * n_a - the pairs with a_row[j] == d_row[i]); max_row:
+ * the most bonds a hydrogen held in one frame (beyond max_neighbors: the results are refused); degenerate: the inside
+ * pairs without an angle. */
+int mdx_hb_stats(mdx_hb_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                 int64_t *max_row, int64_t *degenerate);
+int mdx_hb_enable_timing(mdx_hb_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1160,6 +1160,86 @@ class PairResidenceEngine(_SlabbedFrameEngine):
         return out
 
 
+class HydrogenBondEngine(_SlabbedFrameEngine):
+    """``mdx_hb_*``: per frame the hydrogen bonds among ``n_rows`` incoming rows.  ``h_row[i]`` is a hydrogen,
+    ``d_row[i]`` the donor it is bonded to (it may repeat), ``a_row[j]`` an acceptor; hydrogen ``i`` and acceptor ``j``
+    (not the hydrogen's own donor) are bonded where the minimum-image ``r2_DA <= distance ** 2`` and the cosine ``c``
+    of the angle D-H...A at the hydrogen is at most ``cos_max``, all in float64 (csrc/mdx_hbond_device.hpp).  Per lag
+    the intermittent and continuous intersections of ``PairResidenceEngine`` over the bond sets; per bond a count in
+    the histograms of ``r2_DA`` and ``c`` (``set_bins``); per (frame, hydrogen) a count in ``donated``.  A hydrogen
+    may hold ``max_neighbors`` bonds in one frame; one that would hold more makes ``synchronize()``, ``result()``,
+    ``bonds()`` and ``geometry()`` raise ``ValueError`` until ``reset()``.  The device is first touched by the first
+    frame, so the argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_hb"
+    _stats_extra = (("evaluations", c_int64), ("max_row", c_int64), ("degenerate", c_int64))
+    TILE = 256          # hydrogens per block (HB_TILE of csrc/mdx_hbond_device.hpp)
+    JCHUNK = 1024       # acceptors per block (HB_JCHUNK)
+    MAX_NEIGHBORS = 64  # slots of a row at most (HB_MAX_NEIGHBORS)
+
+    def __init__(self, n_rows, h_row, d_row, a_row, distance, cos_max, lags, dims, *, origin_step=1, zero_dims=0,
+                 max_neighbors=8, continuous=True, dev=0, timing=False):
+        self.n_rows = int(n_rows)
+        self.h_row = np.ascontiguousarray(np.atleast_1d(h_row), dtype=np.int32)
+        self.d_row = np.ascontiguousarray(np.atleast_1d(d_row), dtype=np.int32)
+        self.a_row = np.ascontiguousarray(np.atleast_1d(a_row), dtype=np.int32)
+        if self.h_row.ndim != 1 or self.h_row.shape != self.d_row.shape:
+            raise ValueError("h_row and d_row must be one-dimensional and of one length.")
+        if self.a_row.ndim != 1:
+            raise ValueError("a_row must be one-dimensional.")
+        self.n_h, self.n_a = len(self.h_row), len(self.a_row)
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.max_neighbors, self.continuous = int(max_neighbors), bool(continuous)
+        self.n_distance_bins = self.n_cosine_bins = 1
+        h = c_void_p()
+        check(lib().mdx_hb_create(byref(h), dev, self.n_rows, self.n_h, _ptr(self.h_row), _ptr(self.d_row), self.n_a,
+                                  _ptr(self.a_row), float(distance), float(cos_max), self.n_lags, _ptr(self.lags),
+                                  int(origin_step), _ptr(self.dims), int(zero_dims), self.max_neighbors,
+                                  int(self.continuous)))
+        self._adopt(h, dev, timing)
+
+    def set_bins(self, r2_thresholds, cos_thresholds):
+        """``r2_thresholds``: float64 ``[n_r + 1]``, strictly increasing thresholds of ``r2_DA``; ``cos_thresholds``:
+        float64 ``[n_c + 1]``, strictly decreasing thresholds of ``c``.  Only before the first frame."""
+        r = np.ascontiguousarray(r2_thresholds, dtype=np.float64)
+        c = np.ascontiguousarray(cos_thresholds, dtype=np.float64)
+        if r.ndim != 1 or len(r) < 2 or c.ndim != 1 or len(c) < 2:
+            raise ValueError("the thresholds must hold n_bins + 1 values, at least two.")
+        check(lib().mdx_hb_set_bins(self.handle, len(r) - 1, _ptr(r), len(c) - 1, _ptr(c)))
+        self.n_distance_bins, self.n_cosine_bins = len(r) - 1, len(c) - 1
+
+    def result(self):
+        """``{"intermittent", "continuous", "origin_counts"}``, ``int64 [n_lags]`` each."""
+        out = {key: np.zeros(self.n_lags, dtype=np.int64) for key in ("intermittent", "continuous", "origin_counts")}
+        check(lib().mdx_hb_result(self.handle, _ptr(out["intermittent"]), _ptr(out["continuous"]),
+                                  _ptr(out["origin_counts"])))
+        return out
+
+    def bonds(self):
+        """``int64 [frames]``: the bonds of every frame seen."""
+        frames = c_int64()
+        check(lib().mdx_hb_stats(self.handle, None, None, byref(frames), None, None, None))
+        out = np.zeros(frames.value, dtype=np.int64)
+        check(lib().mdx_hb_bonds(self.handle, _ptr(out), len(out)))
+        return out
+
+    def geometry(self):
+        """``{"distance_counts": int64 [n_r], "cosine_counts": int64 [n_c], "donated": int64 [max_neighbors + 1]}``
+        over the frames seen."""
+        out = {"distance_counts": np.zeros(self.n_distance_bins, dtype=np.int64),
+               "cosine_counts": np.zeros(self.n_cosine_bins, dtype=np.int64),
+               "donated": np.zeros(self.max_neighbors + 1, dtype=np.int64)}
+        check(lib().mdx_hb_geometry(self.handle, _ptr(out["distance_counts"]), _ptr(out["cosine_counts"]),
+                                    _ptr(out["donated"])))
+        return out
+
+
 class ClusterEngine(_SlabbedFrameEngine):
     """``mdx_clu_*``: per frame the connected components of the bond graph of ``n`` rows.  ``species`` (``int [n]``,
     ``0 ... G - 1``, ``G <= 8``) names the group of a row; ``cutoff`` is a float or a symmetric ``G x G`` table of

@@ -346,6 +346,23 @@ _SIGNATURES = {
     "mdx_chi4_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_chi4_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_chi4_enable_timing": (c_int, [_vp, c_int]),
+    # hydrogen bonds (donor-H...acceptor counts, geometry and lifetimes)
+    "mdx_hb_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp, c_int64, _vp, c_double, c_double, c_int,
+                              _vp, c_int64, _vp, c_int, c_int, c_int]),
+    "mdx_hb_set_bins": (c_int, [_vp, c_int64, _vp, c_int64, _vp]),
+    "mdx_hb_destroy": (c_int, [_vp]),
+    "mdx_hb_reset": (c_int, [_vp]),
+    "mdx_hb_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_hb_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_hb_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_hb_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_hb_synchronize": (c_int, [_vp]),
+    "mdx_hb_result": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_hb_bonds": (c_int, [_vp, _vp, c_int64]),
+    "mdx_hb_geometry": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_hb_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                             POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_hb_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

@@ -1,7 +1,7 @@
 """Analysis classes of the hot path (mirrors ``mdhelper.analysis``)."""
 
-from . import (angle, base, cluster, dynamics, electrostatics, order, polymer, profile, structure,  # noqa: F401
-               transport)
+from . import (angle, base, cluster, dynamics, electrostatics, hbond, order, polymer, profile,  # noqa: F401
+               structure, transport)
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
 from .angle import AngularDistribution  # noqa: F401
@@ -10,6 +10,7 @@ from .dynamics import (DistinctVanHove, FourPointSusceptibility, OrientationalRe
                        PairResidence, VanHove, calculate_four_point_susceptibility,
                        calculate_non_gaussian_parameter, calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
+from .hbond import HydrogenBonds  # noqa: F401
 from .order import BondOrientationalOrder  # noqa: F401
 from .polymer import (EndToEndVector, Gyradius, InternalDistances, RouseModes,  # noqa: F401
                       SingleChainStructureFactor)
