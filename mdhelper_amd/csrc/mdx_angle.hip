@@ -31,8 +31,7 @@ constexpr int64_t ANG_MAX_BINS = int64_t(1) << 20;
 
 }  // namespace
 
-struct mdx_ang : FrameEngine {
-    bool ready = false;                 // the device side exists
+struct mdx_ang : LazyFrameEngine {
     int n_species = 1, keep = 7;
     bool same = false, uniform = true, lds_hist = true;
     int64_t n0 = 0, n_lig = 0, n_rows = 0, n_bins = 0;
@@ -64,22 +63,18 @@ static int ang_zero(mdx_ang *h)
     return h->lists.zero(h->stream);
 }
 
-// the device side of the handle: stream, thresholds and counters
-static int ang_ensure_device(mdx_ang *h)
+// the device side of the handle: thresholds and counters
+static int ang_build(mdx_ang *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_inner.ensure(size_t(8) * std::max<size_t>(h->inner.size(), 1)));
     MDX_TRY(h->d_counts.ensure(size_t(8) * h->words()));
     MDX_TRY(h->lists.ensure_ctl());
     if (!h->inner.empty())
         MDX_HIP(hipMemcpy(h->d_inner.ptr, h->inner.data(), size_t(8) * h->inner.size(), hipMemcpyHostToDevice));
-    MDX_TRY(ang_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    return ang_zero(h);
 }
+
+static int ang_ensure_device(mdx_ang *h) { return h->ensure_device(ang_build); }
 
 // The buffers of a slab, sized before the first frame of a pass.  Nothing is in flight then (a reset waits for the
 // stream), so growing them loses nothing.
@@ -110,7 +105,6 @@ static int ang_accumulate_rows(mdx_ang *h, const float *d_pos, int64_t src_rows,
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the groups hold %lld", (long long)n_rows,
                 (long long)h->n_rows);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     const int n = (int)h->n_rows, n0 = (int)h->n0, n_lig = (int)h->n_lig, off = h->same ? 0 : n0;
     const int max_nb = h->lists.max_nb;
     int *len = h->lists.d_len.as<int>(), *list = h->lists.d_list.as<int>();
@@ -227,25 +221,14 @@ int mdx_ang_destroy(mdx_ang_t h)
 int mdx_ang_reset(mdx_ang_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;
     h->lists.max_row = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(ang_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(ang_zero);
 }
 
 int mdx_ang_set_slab_frames(mdx_ang_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= ANG_SLAB_MAX, "frames must lie in [0, %lld]", (long long)ANG_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_ang_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
+    return h->set_slab_frames(frames, ANG_SLAB_MAX, "mdx_ang_set_slab_frames");
 }
 
 // what a route prepares before the first kernel
@@ -282,19 +265,15 @@ int mdx_ang_accumulate_traj(mdx_ang_t h, mdx_traj_t traj, const int64_t *frames,
 int mdx_ang_synchronize(mdx_ang_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return ang_check_rows(h);
+    MDX_TRY(h->synchronize());
+    return h->ready ? ang_check_rows(h) : MDX_OK;
 }
 
 int mdx_ang_result(mdx_ang_t h, int64_t *counts, int64_t *degenerate, int64_t *coordination)
 {
     MDX_REQUIRE(h && counts && degenerate && coordination, "NULL argument");
     MDX_TRY(ang_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     MDX_TRY(ang_check_rows(h));
     // uint64 counts of fewer than 2^63 triplets each: they fit an int64
     const size_t n_counts = size_t(8) * h->pairs() * h->n_bins, n_degenerate = size_t(8) * h->pairs();
@@ -310,7 +289,7 @@ int mdx_ang_stats(mdx_ang_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *triplets, int64_t *max_row)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     int64_t sum = 0;
     if (h->ready) {
         MDX_TRY(h->lists.look());

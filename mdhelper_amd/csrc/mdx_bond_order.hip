@@ -84,8 +84,7 @@ void boo_kernels_from(int l, QlmKernel *qlm, AverageKernel *average)
 
 }  // namespace
 
-struct mdx_boo : FrameEngine {
-    bool ready = false;                 // the device side exists
+struct mdx_boo : LazyFrameEngine {
     bool same = false, averaged = false, keep_values = false, lds_hist = true;
     int D = 0, K = 1, l_max = 0;
     int degrees[BOO_MAX_DEGREES] = {0, 0, 0, 0};
@@ -135,12 +134,9 @@ static int boo_zero(mdx_boo *h)
     return h->lists.zero(h->stream);
 }
 
-// the device side of the handle: stream, edges, tables and counters
-static int boo_ensure_device(mdx_boo *h)
+// the device side of the handle: edges, tables and counters
+static int boo_build(mdx_boo *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_edges.ensure(size_t(8) * h->edges.size()));
     MDX_TRY(h->d_tables.ensure(sizeof(BooTables)));
     MDX_TRY(h->d_counts.ensure(size_t(8) * h->words()));
@@ -149,11 +145,10 @@ static int boo_ensure_device(mdx_boo *h)
     boo_fill_tables(&tables);
     MDX_HIP(hipMemcpy(h->d_edges.ptr, h->edges.data(), size_t(8) * h->edges.size(), hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_tables.ptr, &tables, sizeof tables, hipMemcpyHostToDevice));
-    MDX_TRY(boo_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    return boo_zero(h);
 }
+
+static int boo_ensure_device(mdx_boo *h) { return h->ensure_device(boo_build); }
 
 // The buffers of a slab, sized before the first frame of a pass.  Nothing is in flight then (a reset waits for the
 // stream), so growing them loses nothing.
@@ -200,7 +195,6 @@ static int boo_accumulate_rows(mdx_boo *h, const float *d_pos, int64_t src_rows,
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the groups hold %lld", (long long)n_rows,
                 (long long)h->n_rows);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     const int64_t DK = h->DK();
     MDX_TRY(grow_frames(h->d_frame_sums, h->stream, size_t(8) * DK, h->frames_seen, h->frames_seen + n_frames));
     MDX_TRY(grow_frames(h->d_counted, h->stream, 8, h->frames_seen, h->frames_seen + n_frames));
@@ -335,27 +329,16 @@ int mdx_boo_destroy(mdx_boo_t h)
 int mdx_boo_reset(mdx_boo_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;
     h->lists.max_row = 0;
     h->degenerate = 0;
     h->values.clear();
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(boo_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(boo_zero);
 }
 
 int mdx_boo_set_slab_frames(mdx_boo_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= BOO_SLAB_MAX, "frames must lie in [0, %lld]", (long long)BOO_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_boo_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
+    return h->set_slab_frames(frames, BOO_SLAB_MAX, "mdx_boo_set_slab_frames");
 }
 
 // what a route prepares before the first kernel
@@ -392,19 +375,15 @@ int mdx_boo_accumulate_traj(mdx_boo_t h, mdx_traj_t traj, const int64_t *frames,
 int mdx_boo_synchronize(mdx_boo_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return boo_check(h);
+    MDX_TRY(h->synchronize());
+    return h->ready ? boo_check(h) : MDX_OK;
 }
 
 int mdx_boo_result(mdx_boo_t h, int64_t *counts, int64_t *outside, int64_t *coordination)
 {
     MDX_REQUIRE(h && counts && outside && coordination, "NULL argument");
     MDX_TRY(boo_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     MDX_TRY(boo_check(h));
     // uint64 counts of fewer than 2^63 values each: they fit an int64
     MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->DK() * h->n_bins, hipMemcpyDeviceToHost));
@@ -448,7 +427,7 @@ int mdx_boo_stats(mdx_boo_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *bonds, int64_t *degenerate, int64_t *max_row)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     int64_t entries = 0;
     if (h->ready) {
         MDX_TRY(h->lists.look());

@@ -13,8 +13,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_lag_history.hpp"
 #include "mdx_chi4_device.hpp"
 
 #include <hip/hip_runtime.h>
@@ -44,19 +44,18 @@ constexpr int64_t CHI4_GRID_YZ = 65535;
 
 }  // namespace
 
-struct mdx_chi4 : FrameEngine {
-    bool ready = false;                 // the device side exists
-    int n_groups = 0, n_cutoffs = 0, n_lags = 0, keep = 7;
-    int64_t n_points = 0, max_group = 0, max_lag = 0, origin_step = 1;
-    int64_t n_entries = 0;              // n_lags * n_groups * n_cutoffs
+struct mdx_chi4 : LazyFrameEngine {
+    int n_groups = 0, n_cutoffs = 0, keep = 7;
+    int64_t n_points = 0, max_group = 0;
+    int64_t n_entries = 0;              // lags * n_groups * n_cutoffs
     int64_t segment_points = 0;         // 0 = the default
     int64_t evaluations = 0;
-    int64_t cap = 0;                    // frames the ring holds
-    bool unwrap = false;
-    double dims[3] = {0, 0, 0};
+    LagTable lags;
+    LagRing ring;
+    UnwrappedHistory hist;
     Chi4Cutoffs cut;
-    std::vector<int64_t> offsets, lags;
-    DeviceBuffer d_offsets, d_lags, d_s1, d_s2, d_qslab, d_hist, d_prev, d_image;
+    std::vector<int64_t> offsets;
+    DeviceBuffer d_offsets, d_s1, d_s2, d_qslab;
 };
 
 static int64_t chi4_slab(const mdx_chi4 *h)
@@ -82,50 +81,41 @@ static int chi4_zero(mdx_chi4 *h)
     return MDX_OK;
 }
 
-// the device side of the handle: stream, tables and sums
-static int chi4_ensure_device(mdx_chi4 *h)
+// the device side of the handle: tables and sums
+static int chi4_build(mdx_chi4 *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
-    const int64_t n = h->n_points;
     MDX_TRY(h->d_offsets.ensure(size_t(8) * (h->n_groups + 1)));
-    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
     MDX_TRY(h->d_s1.ensure(size_t(8) * h->n_entries));
     MDX_TRY(h->d_s2.ensure(size_t(8) * h->n_entries));
-    MDX_TRY(h->d_prev.ensure(size_t(24) * n));
-    MDX_TRY(h->d_image.ensure(size_t(12) * n));
+    MDX_TRY(h->hist.ensure_state(h->n_points));
     MDX_HIP(hipMemcpy(h->d_offsets.ptr, h->offsets.data(), size_t(8) * (h->n_groups + 1), hipMemcpyHostToDevice));
-    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
-    MDX_TRY(chi4_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    MDX_TRY(h->lags.upload());
+    return chi4_zero(h);
 }
 
-// The ring and the scratch, sized before the first frame of a pass: max(lags) carried frames plus the frames of a
-// slab, and one scratch row per frame of a slab.  Nothing is in flight then (a reset waits for the stream).
-static int chi4_ensure_history(mdx_chi4 *h)
+static int chi4_ensure_device(mdx_chi4 *h) { return h->ensure_device(chi4_build); }
+
+// What a route prepares before the first kernel: the device side, and before the first frame of a pass the ring and
+// the scratch, one row of it per frame of a slab.
+static int chi4_prepare(mdx_chi4 *h, int64_t)
 {
-    if (h->frames_seen > 0)
-        return MDX_OK;
-    const int64_t slab = chi4_slab(h), cap = h->max_lag + slab;
-    MDX_REQUIRE(cap < (int64_t(1) << 40) / (24 * h->n_points),
-                "a history of %lld frames of %lld points is too large", (long long)cap, (long long)h->n_points);
+    MDX_TRY(chi4_ensure_device(h));
+    MDX_TRY(h->ring.ensure(h->frames_seen, h->lags.max_lag, chi4_slab(h), 24 * h->n_points,
+                           "a history of %lld frames of %lld points is too large", (long long)h->n_points));
+    const int64_t slab = h->ring.slab(chi4_slab(h));
     MDX_REQUIRE(slab < (int64_t(1) << 40) / (4 * h->n_entries),
                 "a slab of %lld frames of %lld counters is too large", (long long)slab, (long long)h->n_entries);
-    MDX_TRY(h->d_hist.ensure(size_t(24) * h->n_points * cap));
-    MDX_TRY(h->d_qslab.ensure(size_t(4) * h->n_entries * slab));
-    h->cap = cap;
-    return MDX_OK;
+    MDX_TRY(h->hist.ensure_ring(h->n_points, h->ring.cap));
+    return h->d_qslab.ensure(size_t(4) * h->n_entries * slab);
 }
 
 template <int NC>
 static void chi4_launch_count(mdx_chi4 *h, dim3 grid, int64_t f0, int seg)
 {
-    hipLaunchKernelGGL(chi4_count_kernel<NC>, grid, dim3(CHI4_THREADS), 0, h->stream, h->d_hist.as<double>(), h->cap,
-                       (int)h->n_points, h->d_offsets.as<int64_t>(), h->n_groups, h->d_lags.as<int64_t>(), h->n_lags,
-                       f0, h->origin_step, h->keep, seg, h->cut, h->d_qslab.as<unsigned int>());
+    hipLaunchKernelGGL(chi4_count_kernel<NC>, grid, dim3(CHI4_THREADS), 0, h->stream, h->hist.d_hist.as<double>(),
+                       h->ring.cap, (int)h->n_points, h->d_offsets.as<int64_t>(), h->n_groups,
+                       h->lags.d_lags.as<int64_t>(), h->lags.n(), f0, h->lags.origin_step, h->keep, seg, h->cut,
+                       h->d_qslab.as<unsigned int>());
 }
 
 // n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
@@ -136,26 +126,18 @@ static int chi4_accumulate_rows(mdx_chi4 *h, const float *d_pos, int64_t src_row
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_points, "%lld rows given, the groups hold %lld", (long long)n_rows,
                 (long long)h->n_points);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     const int n = (int)h->n_points;
-    const int64_t slab = std::min(chi4_slab(h), h->cap - h->max_lag);
+    const int64_t slab = h->ring.slab(chi4_slab(h));
     const int seg = (int)chi4_segment(h);
-    const unsigned lag_runs = (unsigned)ceil_div(h->n_lags, CHI4_BLOCK_LAGS);
+    const unsigned lag_runs = (unsigned)ceil_div(h->lags.n(), CHI4_BLOCK_LAGS);
     const unsigned segments = (unsigned)ceil_div(h->n_points, int64_t(seg));
     hipEvent_t ev = h->timer.begin();
     for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f0 = h->frames_seen;
-        if (h->unwrap)
-            hipLaunchKernelGGL(vh_prepare_kernel<true>, dim3((unsigned)ceil_div(3 * int64_t(n), 256)), dim3(256), 0,
-                               h->stream, pos, src_rows, d_index, n, (int)nf, f0, h->cap, h->dims[0], h->dims[1],
-                               h->dims[2], f0 == 0 ? 1 : 0, h->d_prev.as<double>(), h->d_image.as<int>(),
-                               h->d_hist.as<double>());
-        else
-            hipLaunchKernelGGL(vh_prepare_kernel<false>, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf),
-                               dim3(256), 0, h->stream, pos, src_rows, d_index, n, (int)nf, f0, h->cap, 0.0, 0.0,
-                               0.0, 0, (double *)nullptr, (int *)nullptr, h->d_hist.as<double>());
+        h->hist.prepare(vh_prepare_kernel<true>, vh_prepare_kernel<false>, h->stream, pos, src_rows, d_index, n, nf, f0,
+                        h->ring.cap);
         MDX_HIP(hipMemsetAsync(h->d_qslab.ptr, 0, size_t(4) * h->n_entries * nf, h->stream));
         const dim3 grid((unsigned)nf, lag_runs, segments);
         switch (h->n_cutoffs) {
@@ -172,14 +154,10 @@ static int chi4_accumulate_rows(mdx_chi4 *h, const float *d_pos, int64_t src_row
                            dim3((unsigned)ceil_div(h->n_entries, int64_t(256)),
                                 (unsigned)ceil_div(nf, int64_t(CHI4_FOLD_FRAMES))),
                            dim3(256), 0, h->stream, h->d_qslab.as<unsigned int>(), (int)nf, h->n_entries,
-                           h->n_groups * h->n_cutoffs, h->d_lags.as<int64_t>(), f0, h->origin_step,
+                           h->n_groups * h->n_cutoffs, h->lags.d_lags.as<int64_t>(), f0, h->lags.origin_step,
                            h->d_s1.as<unsigned long long>(), h->d_s2.as<unsigned long long>());
         // the contract's count: origins f - lag that are multiples of origin_step, f among the new frames
-        for (int64_t lag : h->lags) {
-            const int64_t o_lo = std::max<int64_t>(0, f0 - lag), o_hi = f0 + nf - lag;      // origins [o_lo, o_hi)
-            if (o_hi > o_lo)
-                h->evaluations += h->n_points * (ceil_div(o_hi, h->origin_step) - ceil_div(o_lo, h->origin_step));
-        }
+        h->evaluations += h->n_points * h->lags.origins_met(f0, nf);
         h->frames_seen += nf;
     }
     h->timer.end(ev);
@@ -222,23 +200,17 @@ int mdx_chi4_create(mdx_chi4_t *out, int dev, int n_groups, const int64_t *n_poi
         MDX_REQUIRE(std::isfinite(cutoffs[c]) && cutoffs[c] >= 0.0, "cutoffs must be finite and not negative");
         MDX_REQUIRE(c == 0 || cutoffs[c] > cutoffs[c - 1], "cutoffs must be strictly increasing");
     }
-    for (int k = 0; k < n_lags; ++k) {
-        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
-        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
-    }
+    MDX_TRY(LagTable::check(n_lags, lags));
     MDX_REQUIRE(int64_t(n_lags) * n_groups * n_cutoffs < (int64_t(1) << 31), "too many counters");
     mdx_chi4 *h = new mdx_chi4();
     h->dev = dev;
     h->n_groups = n_groups;
     h->n_cutoffs = n_cutoffs;
-    h->n_lags = n_lags;
     h->n_entries = int64_t(n_lags) * n_groups * n_cutoffs;
     h->keep = 7 & ~zero_dims;
     h->n_points = total;
     h->max_group = largest;
-    h->origin_step = origin_step;
-    h->max_lag = lags[n_lags - 1];
-    h->lags.assign(lags, lags + n_lags);
+    h->lags.assign(n_lags, lags, origin_step);
     for (int c = 0; c < CHI4_MAX_CUTOFFS; ++c)
         h->cut.a2[c] = c < n_cutoffs ? cutoffs[c] * cutoffs[c] : -1.0;
     h->offsets.push_back(0);
@@ -253,8 +225,8 @@ int mdx_chi4_destroy(mdx_chi4_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_offsets, &h->d_lags, &h->d_s1, &h->d_s2, &h->d_qslab, &h->d_hist, &h->d_prev,
-                    &h->d_image});
+        h->release({&h->d_offsets, &h->lags.d_lags, &h->d_s1, &h->d_s2, &h->d_qslab, &h->hist.d_hist, &h->hist.d_prev,
+                    &h->hist.d_image});
     delete h;
     return MDX_OK;
 }
@@ -262,38 +234,20 @@ int mdx_chi4_destroy(mdx_chi4_t h)
 int mdx_chi4_reset(mdx_chi4_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;         // the history and the unwrap state start over with the next frame
     h->evaluations = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(chi4_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(chi4_zero);     // frames_seen = 0: the history and the unwrap state start over with the next frame
 }
 
 int mdx_chi4_set_unwrap(mdx_chi4_t h, const double *dims)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (dims)
-        for (int k = 0; k < 3; ++k)
-            MDX_REQUIRE(dims[k] > 0.0 && std::isfinite(dims[k]), "dims[%d] must be positive and finite", k);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_chi4_set_unwrap must be called before the first frame");
-    h->unwrap = dims != nullptr;
-    for (int k = 0; k < 3; ++k)
-        h->dims[k] = dims ? dims[k] : 0.0;
-    return MDX_OK;
+    return h->hist.set_unwrap(dims, h->frames_seen, "mdx_chi4_set_unwrap");
 }
 
 int mdx_chi4_set_slab_frames(mdx_chi4_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= CHI4_SLAB_MAX, "frames must lie in [0, %lld]", (long long)CHI4_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_chi4_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
+    return h->set_slab_frames(frames, CHI4_SLAB_MAX, "mdx_chi4_set_slab_frames");
 }
 
 int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points)
@@ -304,13 +258,6 @@ int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points)
     MDX_REQUIRE(h->frames_seen == 0, "mdx_chi4_set_segment_points must be called before the first frame");
     h->segment_points = points;
     return MDX_OK;
-}
-
-// what a route prepares before the first kernel
-static int chi4_prepare(mdx_chi4 *h, int64_t)
-{
-    MDX_TRY(chi4_ensure_device(h));
-    return chi4_ensure_history(h);
 }
 
 int mdx_chi4_accumulate_device(mdx_chi4_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
@@ -346,32 +293,26 @@ int mdx_chi4_accumulate_traj(mdx_chi4_t h, mdx_traj_t traj, const int64_t *frame
 int mdx_chi4_synchronize(mdx_chi4_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->synchronize();
 }
 
 int mdx_chi4_result(mdx_chi4_t h, int64_t *sums, int64_t *square_sums, int64_t *n_origins)
 {
     MDX_REQUIRE(h && sums && square_sums && n_origins, "NULL argument");
     MDX_TRY(chi4_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     // uint64 sums below 2^63 (chi4_check_overflow): they fit an int64
     MDX_HIP(hipMemcpy(sums, h->d_s1.ptr, size_t(8) * h->n_entries, hipMemcpyDeviceToHost));
     MDX_HIP(hipMemcpy(square_sums, h->d_s2.ptr, size_t(8) * h->n_entries, hipMemcpyDeviceToHost));
-    // the origins of a lag: the multiples of origin_step below frames_seen - lag
-    for (int k = 0; k < h->n_lags; ++k)
-        n_origins[k] = ceil_div(std::max<int64_t>(0, h->frames_seen - h->lags[k]), h->origin_step);
+    for (int k = 0; k < h->lags.n(); ++k)
+        n_origins[k] = h->lags.origins_seen(h->frames_seen, h->lags.lags[k]);
     return MDX_OK;
 }
 
 int mdx_chi4_stats(mdx_chi4_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     if (evaluations) *evaluations = h->evaluations;
     return MDX_OK;
 }

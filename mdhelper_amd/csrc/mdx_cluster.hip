@@ -29,8 +29,7 @@ constexpr int CLU_SWEEP_BATCH = 4;                      // sweeps queued between
 
 }  // namespace
 
-struct mdx_clu : FrameEngine {
-    bool ready = false;                 // the device side exists
+struct mdx_clu : LazyFrameEngine {
     int n_species = 1, keep = 7;
     bool uniform = true, keep_labels = false;
     int64_t n = 0;
@@ -64,23 +63,19 @@ static int clu_zero(mdx_clu *h)
     return h->lists.zero(h->stream);
 }
 
-// the device side of the handle: stream, tables and counters
-static int clu_ensure_device(mdx_clu *h)
+// the device side of the handle: tables and counters
+static int clu_build(mdx_clu *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_species.ensure(size_t(4) * h->n));
     MDX_TRY(h->d_table.ensure(sizeof(h->table)));
     MDX_TRY(h->d_counts.ensure(size_t(8) * (1 + h->n_species) * (h->n + 1)));
     MDX_TRY(h->lists.ensure_ctl());
     MDX_HIP(hipMemcpy(h->d_species.ptr, h->species.data(), size_t(4) * h->n, hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_table.ptr, h->table, sizeof(h->table), hipMemcpyHostToDevice));
-    MDX_TRY(clu_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    return clu_zero(h);
 }
+
+static int clu_ensure_device(mdx_clu *h) { return h->ensure_device(clu_build); }
 
 // The buffers of a slab, sized before the first frame of a pass.  Nothing is in flight then (a reset waits for the
 // stream), so growing them loses nothing.
@@ -150,7 +145,6 @@ static int clu_accumulate_rows(mdx_clu *h, const float *d_pos, int64_t src_rows,
     if (n_frames == 0)
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n, "%lld rows given, the groups hold %lld", (long long)n_rows, (long long)h->n);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(grow_frames(h->d_frames, h->stream, size_t(8) * CLU_FRAME_WORDS, h->frames_seen,
                         h->frames_seen + n_frames));
     if (h->keep_labels)
@@ -273,26 +267,15 @@ int mdx_clu_destroy(mdx_clu_t h)
 int mdx_clu_reset(mdx_clu_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;
     h->sweeps = 0;
     h->lists.max_row = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(clu_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(clu_zero);
 }
 
 int mdx_clu_set_slab_frames(mdx_clu_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= CLU_SLAB_MAX, "frames must lie in [0, %lld]", (long long)CLU_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_clu_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
+    return h->set_slab_frames(frames, CLU_SLAB_MAX, "mdx_clu_set_slab_frames");
 }
 
 // what a route prepares before the first kernel
@@ -329,19 +312,15 @@ int mdx_clu_accumulate_traj(mdx_clu_t h, mdx_traj_t traj, const int64_t *frames,
 int mdx_clu_synchronize(mdx_clu_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return clu_check_rows(h);
+    MDX_TRY(h->synchronize());
+    return h->ready ? clu_check_rows(h) : MDX_OK;
 }
 
 int mdx_clu_result(mdx_clu_t h, int64_t *size_counts, int64_t *species_counts)
 {
     MDX_REQUIRE(h && size_counts && species_counts, "NULL argument");
     MDX_TRY(clu_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     MDX_TRY(clu_check_rows(h));
     // uint64 counts of at most frames x n < 2^63 each: they fit an int64
     const size_t bytes = size_t(8) * (h->n + 1);
@@ -392,7 +371,7 @@ int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *max_row, int64_t *sweeps)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     if (h->ready)
         MDX_TRY(h->lists.look());
     if (evaluations) *evaluations = h->frames_seen * (h->n * (h->n - 1) / 2);

@@ -64,7 +64,6 @@ static int dip_accumulate_rows(mdx_dip *h, const float *d_pos, int64_t src_rows,
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_points, "%lld rows given, the groups hold %lld", (long long)n_rows,
                 (long long)h->n_points);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(dip_grow_rows(h, n_frames));
     const int64_t n = h->n_points;
     if (h->unwrap && h->frames_seen == 0) {

@@ -2,9 +2,11 @@
 // X_accumulate_rows(h, d_pos, src_rows, d_index, n_rows, n_frames): the staged host-memory and trajectory-file routes,
 // the particle index in HBM, the growing per-frame rows and the common part of a handle.  Host code only.
 //
-// An engine writes its own NULL checks, its preparation (set_device + grow_rows, or its ensure_device /
-// ensure_history) and X_accumulate_rows; the rest of a route is one call of FrameEngine::accumulate_device / _host /
-// _traj.
+// An engine writes its own NULL checks, its preparation (set_device + grow_rows, or X_prepare: its ensure_device and
+// the sizing of its slab or ring) and X_accumulate_rows; the rest of a route is one call of
+// FrameEngine::accumulate_device / _host / _traj.  An engine whose handle touches its device only with the first frame
+// (or result) derives from LazyFrameEngine, which holds that life cycle: ensure_device, reset, synchronize, collect.
+// What the lag engines share about time is in mdx_lag_history.hpp.
 #pragma once
 
 #include "mdx_common.hpp"
@@ -155,6 +157,15 @@ struct FrameEngine {
         return MDX_OK;
     }
 
+    // the body of X_set_slab_frames (entry_name); most: the frames a launch of the engine takes
+    int set_slab_frames(int64_t frames, int64_t most, const char *entry_name)
+    {
+        MDX_REQUIRE(frames >= 0 && frames <= most, "frames must lie in [0, %lld]", (long long)most);
+        MDX_REQUIRE(frames_seen == 0, "%s must be called before the first frame", entry_name);
+        slab_frames = frames;
+        return MDX_OK;
+    }
+
     // the head of X_stats; live = false: the handle has not touched its device yet
     int stats(bool live, int64_t *launches, double *kernel_ms, int64_t *frames)
     {
@@ -169,7 +180,7 @@ struct FrameEngine {
         return MDX_OK;
     }
 
-    // the head of a lazy X_ensure_device: the handle's device is current and its stream exists
+    // the head of LazyFrameEngine::ensure_device: the handle's device is current and its stream exists
     int acquire_stream()
     {
         MDX_TRY(set_device(dev));
@@ -184,9 +195,16 @@ struct FrameEngine {
     // checks.  want: the rows a frame must hold, `noun` holds them ("groups", "sets").  prepare(h, n_frames): what
     // has to exist before the first kernel (the device side of a lazy handle, room for the frames' rows);
     // rows_fn: the engine's X_accumulate_rows(h, d_pos, src_rows, d_index, n_rows, nf).  Argument errors come before
-    // anything touches the device, and no frames touch nothing.
+    // anything touches the device, and no frames touch nothing; only rows_too_large, which bounds the kernels' int
+    // offsets into a source frame, comes where the engines used to make it, behind prepare.
     template <typename H> using PrepareFn = int (*)(H *, int64_t);
     template <typename H> using RowsFn = int (*)(H *, const float *, int64_t, const int *, int64_t, int64_t);
+
+    static int rows_too_large(int64_t src_rows)
+    {
+        MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
+        return MDX_OK;
+    }
 
     // d_pos float32[n_frames][n_atoms][3] in HBM; index: host int32[n_index] rows of a frame, or NULL for all
     template <typename H>
@@ -203,6 +221,7 @@ struct FrameEngine {
         MDX_TRY(prepare(h, n_frames));
         const int *d_index = nullptr;
         MDX_TRY(feed.upload_index(stream, index, n_index, &d_index));
+        MDX_TRY(rows_too_large(n_atoms));
         return rows_fn(h, d_pos, n_atoms, d_index, n, n_frames);
     }
 
@@ -217,6 +236,7 @@ struct FrameEngine {
         if (n_frames == 0)
             return MDX_OK;
         MDX_TRY(prepare(h, n_frames));
+        MDX_TRY(rows_too_large(n));
         return feed.host(dev, stream, pos, n, n_frames, feed_slab_frames(n_frames, n),
                          [&](const float *d_pos, int64_t nf) -> int { return rows_fn(h, d_pos, n, nullptr, n, nf); });
     }
@@ -238,6 +258,7 @@ struct FrameEngine {
         MDX_TRY(prepare(h, n_frames));
         const int *d_index = nullptr;
         MDX_TRY(feed.upload_index(stream, index, n_index, &d_index));
+        MDX_TRY(rows_too_large(n));
         return feed.traj(dev, stream, t, frames, n_frames, d_index, n, feed_slab_frames(n_frames, t->n_atoms),
                          [&](const float *d_pos, int64_t nf) -> int { return rows_fn(h, d_pos, n, nullptr, n, nf); });
     }
@@ -254,6 +275,64 @@ struct FrameEngine {
             b->recycle();
         if (stream)
             stream_release(stream);
+    }
+};
+
+// A handle that touches its device only with the first frame (or result): creating one, and every argument error,
+// needs none.  A struct of its own rather than a flag in FrameEngine, whose other engines (gyration, rouse, msid,
+// dipole, profile) acquire their stream in create and would carry a field that is always true.
+struct LazyFrameEngine : FrameEngine {
+    bool ready = false;                 // the device side exists
+
+    // build(h): the engine's ensures, uploads and zero, on the stream that exists by then
+    template <typename H>
+    int ensure_device(int (*build)(H *))
+    {
+        if (ready)
+            return set_device(dev);
+        MDX_TRY(acquire_stream());
+        MDX_TRY(build(static_cast<H *>(this)));
+        MDX_HIP(hipStreamSynchronize(stream));
+        ready = true;
+        return MDX_OK;
+    }
+
+    // the body of X_reset, after the engine has cleared its own host counters; zero(h): the device side starts over
+    template <typename H>
+    int reset(int (*zero)(H *))
+    {
+        frames_seen = 0;
+        if (!ready)
+            return MDX_OK;
+        MDX_TRY(set_device(dev));
+        MDX_HIP(hipStreamSynchronize(stream));
+        timer.reset();
+        MDX_TRY(zero(static_cast<H *>(this)));
+        MDX_HIP(hipStreamSynchronize(stream));
+        return MDX_OK;
+    }
+
+    // the body of X_synchronize; where `ready`, the engine may look at its control words afterwards
+    int synchronize()
+    {
+        if (!ready)
+            return MDX_OK;
+        MDX_TRY(set_device(dev));
+        MDX_HIP(hipStreamSynchronize(stream));
+        return MDX_OK;
+    }
+
+    // the head of X_result behind the engine's ensure_device (and its fold, where it has one)
+    int collect()
+    {
+        MDX_HIP(hipStreamSynchronize(stream));
+        timer.collect();
+        return MDX_OK;
+    }
+
+    int stats(int64_t *launches, double *kernel_ms, int64_t *frames)
+    {
+        return FrameEngine::stats(ready, launches, kernel_ms, frames);
     }
 };
 

@@ -15,9 +15,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
-#include "mdx_pairs_host.hpp"
+#include "mdx_lag_history.hpp"
 #include "mdx_hbond_device.hpp"
 
 #include <algorithm>
@@ -26,8 +25,6 @@
 using namespace mdx;
 using namespace mdx_hb_dev;
 using mdx_prs_dev::prs_walk_kernel;
-using mdx_prs_dev::PRS_WALK_ORIGINS;
-using mdx_prs_dev::PRS_WALK_THREADS;
 
 namespace {
 
@@ -36,24 +33,23 @@ constexpr int64_t HB_MAX_BINS = int64_t(1) << 20;
 
 }  // namespace
 
-struct mdx_hb : FrameEngine {
-    bool ready = false;                 // the device side exists
-    int n_lags = 0, keep = 7;
-    bool continuous = true, lds_hist = true;
+struct mdx_hb : LazyFrameEngine {
+    int keep = 7;
+    bool lds_hist = true;
     int64_t n_rows = 0, n_h = 0, n_a = 0;
     int64_t excluded = 0;               // the (i, j) with a_row[j] == d_row[i]
-    int64_t max_lag = 0, origin_step = 1;
-    int64_t cap = 0;                    // frames the rings hold
     int64_t n_r = 1, n_c = 1;           // bins of the two histograms
+    LagTable lags;
+    LagRing ring;                       // frames the rings hold
     PairBox box;
     CappedLists lists;                  // the rings of bond lists
+    SurvivalWalk walk;
     double rc2 = 0.0, cos_max = 0.0;
-    std::vector<int64_t> lags;
     std::vector<int32_t> tables;        // h_row [n_h], d_row [n_h], a_row [n_a]
     std::vector<double> inner;          // the inner thresholds of r2_DA [n_r - 1], then those of c [n_c - 1]
-    // d_sums: uint64 [3][n_lags] intermittent, continuous, origin_counts; d_bonds: uint64, one per frame seen;
+    // d_bonds: uint64, one per frame seen;
     // d_geometry: uint64 distance_counts [n_r], cosine_counts [n_c], donated [max_nb + 1], degenerate [1]
-    DeviceBuffer d_lags, d_sums, d_bonds, d_slab, d_mask, d_tables, d_inner, d_geometry;
+    DeviceBuffer d_bonds, d_slab, d_tables, d_inner, d_geometry;
 
     int64_t geometry_words() const { return n_r + n_c + lists.max_nb + 2; }
 };
@@ -71,7 +67,7 @@ static int64_t hb_slab(const mdx_hb *h)
 
 static int hb_zero(mdx_hb *h)
 {
-    MDX_HIP(hipMemsetAsync(h->d_sums.ptr, 0, size_t(24) * h->n_lags, h->stream));
+    MDX_TRY(h->walk.zero(h->lags.n(), h->stream));
     MDX_HIP(hipMemsetAsync(h->d_geometry.ptr, 0, size_t(8) * h->geometry_words(), h->stream));
     if (h->d_bonds.ptr)
         MDX_HIP(hipMemsetAsync(h->d_bonds.ptr, 0, h->d_bonds.bytes, h->stream));
@@ -88,41 +84,31 @@ static int hb_upload_bins(mdx_hb *h)
     return MDX_OK;
 }
 
-// the device side of the handle: stream, tables and counters
-static int hb_ensure_device(mdx_hb *h)
+// the device side of the handle: tables and counters
+static int hb_build(mdx_hb *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
-    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
-    MDX_TRY(h->d_sums.ensure(size_t(24) * h->n_lags));
+    MDX_TRY(h->walk.ensure(h->lags.n()));
     MDX_TRY(h->d_tables.ensure(size_t(4) * h->tables.size()));
     MDX_TRY(h->lists.ensure_ctl());
     MDX_TRY(hb_upload_bins(h));
-    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
+    MDX_TRY(h->lags.upload());
     MDX_HIP(hipMemcpy(h->d_tables.ptr, h->tables.data(), size_t(4) * h->tables.size(), hipMemcpyHostToDevice));
-    MDX_TRY(hb_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    return hb_zero(h);
 }
 
-// The rings and the slab, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.
-// Nothing is in flight then (a reset waits for the stream), so growing them loses nothing.
-static int hb_ensure_rings(mdx_hb *h)
+static int hb_ensure_device(mdx_hb *h) { return h->ensure_device(hb_build); }
+
+// What a route prepares before the first kernel: the device side, and before the first frame of a pass the rings and
+// the slab.
+static int hb_prepare(mdx_hb *h, int64_t)
 {
-    if (h->frames_seen > 0)
-        return MDX_OK;
-    const int64_t slab = hb_slab(h), cap = h->max_lag + slab;
-    MDX_REQUIRE(cap < (int64_t(1) << 40) / hb_frame_bytes(h),
-                "a history of %lld frames of %lld hydrogens with %d neighbors each is too large", (long long)cap,
-                (long long)h->n_h, h->lists.max_nb);
-    MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * slab));
-    MDX_TRY(h->lists.ensure(h->n_h, cap));
-    if (h->continuous)
-        MDX_TRY(h->d_mask.ensure(size_t(8) * h->n_h * cap));
-    h->cap = cap;
-    return MDX_OK;
+    MDX_TRY(hb_ensure_device(h));
+    MDX_TRY(h->ring.ensure(h->frames_seen, h->lags.max_lag, hb_slab(h), hb_frame_bytes(h),
+                           "a history of %lld frames of %lld hydrogens with %d neighbors each is too large",
+                           (long long)h->n_h, h->lists.max_nb));
+    MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * h->ring.slab(hb_slab(h))));
+    MDX_TRY(h->lists.ensure(h->n_h, h->ring.cap));
+    return h->walk.ensure_mask(h->n_h, h->ring.cap);
 }
 
 // With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
@@ -139,7 +125,6 @@ static int hb_accumulate_rows(mdx_hb *h, const float *d_pos, int64_t src_rows, c
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the tables name %lld", (long long)n_rows,
                 (long long)h->n_rows);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(grow_frames(h->d_bonds, h->stream, 8, h->frames_seen, h->frames_seen + n_frames));
     const int n = (int)h->n_rows, n_h = (int)h->n_h, n_a = (int)h->n_a, max_nb = h->lists.max_nb;
     int *len = h->lists.d_len.as<int>(), *list = h->lists.d_list.as<int>();
@@ -148,43 +133,30 @@ static int hb_accumulate_rows(mdx_hb *h, const float *d_pos, int64_t src_rows, c
     unsigned long long *distance_counts = h->d_geometry.as<unsigned long long>();
     unsigned long long *cosine_counts = distance_counts + h->n_r, *donated = cosine_counts + h->n_c;
     unsigned long long *degenerate = donated + max_nb + 1;
-    const int64_t slab = std::min(hb_slab(h), h->cap - h->max_lag);
+    const int64_t slab = h->ring.slab(hb_slab(h)), cap = h->ring.cap;
     const int64_t n_jchunks = ceil_div(h->n_a, HB_JCHUNK);
     const int64_t blocks = ceil_div(h->n_h, HB_TILE) * n_jchunks;
     const int64_t geo_tiles = ceil_div(h->n_h, HB_GEO_THREADS);
-    const int64_t walk_tiles = ceil_div(h->n_h, PRS_WALK_THREADS);
     hipEvent_t ev = h->timer.begin();
     for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f_lo = h->frames_seen;
         launch_gather<false>(h->stream, pos, src_rows, d_index, n, nf, h->d_slab.as<float>());
-        // the rows of the new frames start empty: their ring slots are one range, or two where the ring wraps
-        const int64_t first = f_lo % h->cap, head = std::min(nf, h->cap - first);
-        MDX_HIP(hipMemsetAsync(len + first * n_h, 0, size_t(4) * n_h * head, h->stream));
-        if (nf > head)
-            MDX_HIP(hipMemsetAsync(len, 0, size_t(4) * n_h * (nf - head), h->stream));
+        // the rows of the new frames start empty
+        MDX_TRY(h->ring.zero_slots(len, size_t(4) * n_h, f_lo, nf, h->stream));
         const auto contact = h->keep == 7 ? hb_contact_kernel<true> : hb_contact_kernel<false>;
         hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(HB_THREADS), 0, h->stream,
-                           h->d_slab.as<float>(), h->cap, n, n_h, n_a, h_row, d_row, a_row, (int)n_jchunks, f_lo,
+                           h->d_slab.as<float>(), cap, n, n_h, n_a, h_row, d_row, a_row, (int)n_jchunks, f_lo,
                            h->box, h->keep, h->rc2, h->cos_max, max_nb, len, list,
                            h->d_bonds.as<unsigned long long>(), h->lists.d_ctl.as<int>(), degenerate);
         const auto geometry = h->lds_hist ? hb_geometry_kernel<true> : hb_geometry_kernel<false>;
         hipLaunchKernelGGL(geometry, dim3((unsigned)geo_tiles, (unsigned)nf), dim3(HB_GEO_THREADS), 0, h->stream,
-                           h->d_slab.as<float>(), h->cap, n, n_h, h_row, d_row, a_row, f_lo, h->box, h->keep, max_nb,
+                           h->d_slab.as<float>(), cap, n, n_h, h_row, d_row, a_row, f_lo, h->box, h->keep, max_nb,
                            len, list, inner_r, (int)h->n_r, inner_c, (int)h->n_c, distance_counts, cosine_counts,
                            donated);
-        // the origins that meet a new frame: multiples of origin_step in [f_lo - max_lag, f_lo + nf)
-        const int64_t o_lo = ceil_div(std::max<int64_t>(0, f_lo - h->max_lag), h->origin_step);
-        const int64_t o_hi = ceil_div(f_lo + nf, h->origin_step);
-        const auto walk = h->continuous ? prs_walk_kernel<true> : prs_walk_kernel<false>;
-        for (int64_t o = o_lo; o < o_hi; o += PRS_WALK_ORIGINS) {
-            const int64_t n_o = std::min<int64_t>(PRS_WALK_ORIGINS, o_hi - o);
-            hipLaunchKernelGGL(walk, dim3((unsigned)walk_tiles, (unsigned)n_o), dim3(PRS_WALK_THREADS), 0, h->stream,
-                               h->cap, n_h, max_nb, len, list, h->d_mask.as<unsigned long long>(),
-                               h->d_lags.as<int64_t>(), h->n_lags, h->max_lag, o, h->origin_step, f_lo, nf,
-                               h->d_sums.as<unsigned long long>());
-        }
+        h->walk.walk(prs_walk_kernel<true>, prs_walk_kernel<false>, h->stream, h->lags, h->ring, h->lists, n_h, f_lo,
+                     nf);
         h->frames_seen += nf;
     }
     h->timer.end(ev);
@@ -211,10 +183,7 @@ int mdx_hb_create(mdx_hb_t *out, int dev, int64_t n_rows, int64_t n_h, const int
                 "the frames and the tables must hold fewer than 2^31 / 3 rows");
     MDX_REQUIRE(ceil_div(n_h, HB_TILE) * ceil_div(n_a, HB_JCHUNK) < (int64_t(1) << 31),
                 "%lld hydrogens and %lld acceptors are too many pairs for one launch", (long long)n_h, (long long)n_a);
-    for (int k = 0; k < n_lags; ++k) {
-        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
-        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
-    }
+    MDX_TRY(LagTable::check(n_lags, lags));
     // what a row is: 1 a hydrogen, 2 an acceptor
     std::vector<char> role((size_t)n_rows, 0);
     for (int64_t i = 0; i < n_h; ++i) {
@@ -248,14 +217,11 @@ int mdx_hb_create(mdx_hb_t *out, int dev, int64_t n_rows, int64_t n_h, const int
     h->n_h = n_h;
     h->n_a = n_a;
     h->excluded = excluded;
-    h->continuous = continuous != 0;
-    h->n_lags = n_lags;
+    h->walk.continuous = continuous != 0;
     h->keep = keep;
     h->box = box;
     h->lists.max_nb = max_neighbors;
-    h->origin_step = origin_step;
-    h->max_lag = lags[n_lags - 1];
-    h->lags.assign(lags, lags + n_lags);
+    h->lags.assign(n_lags, lags, origin_step);
     h->rc2 = distance * distance;
     h->cos_max = cos_max;
     h->tables.assign(h_row, h_row + n_h);
@@ -300,8 +266,8 @@ int mdx_hb_destroy(mdx_hb_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_lags, &h->d_sums, &h->d_bonds, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
-                    &h->lists.d_list, &h->d_mask, &h->d_tables, &h->d_inner, &h->d_geometry});
+        h->release({&h->lags.d_lags, &h->walk.d_sums, &h->d_bonds, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
+                    &h->lists.d_list, &h->walk.d_mask, &h->d_tables, &h->d_inner, &h->d_geometry});
     delete h;
     return MDX_OK;
 }
@@ -309,32 +275,14 @@ int mdx_hb_destroy(mdx_hb_t h)
 int mdx_hb_reset(mdx_hb_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;         // the history starts over with the next frame
     h->lists.max_row = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(hb_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(hb_zero);   // frames_seen = 0: the history starts over with the next frame
 }
 
 int mdx_hb_set_slab_frames(mdx_hb_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= HB_SLAB_MAX, "frames must lie in [0, %lld]", (long long)HB_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_hb_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
-}
-
-// what a route prepares before the first kernel
-static int hb_prepare(mdx_hb *h, int64_t)
-{
-    MDX_TRY(hb_ensure_device(h));
-    return hb_ensure_rings(h);
+    return h->set_slab_frames(frames, HB_SLAB_MAX, "mdx_hb_set_slab_frames");
 }
 
 int mdx_hb_accumulate_device(mdx_hb_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames, const int32_t *index,
@@ -364,27 +312,18 @@ int mdx_hb_accumulate_traj(mdx_hb_t h, mdx_traj_t traj, const int64_t *frames, i
 int mdx_hb_synchronize(mdx_hb_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return hb_check_rows(h);
+    MDX_TRY(h->synchronize());
+    return h->ready ? hb_check_rows(h) : MDX_OK;
 }
 
 int mdx_hb_result(mdx_hb_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts)
 {
     MDX_REQUIRE(h && intermittent && continuous && origin_counts, "NULL argument");
     MDX_TRY(hb_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     MDX_TRY(hb_check_rows(h));
-    // uint64 sums of at most frames x n_h x max_neighbors < 2^63 each: they fit an int64
-    const size_t bytes = size_t(8) * h->n_lags;
-    const char *sums = h->d_sums.as<char>();
-    MDX_HIP(hipMemcpy(intermittent, sums, bytes, hipMemcpyDeviceToHost));
-    MDX_HIP(hipMemcpy(continuous, sums + bytes, bytes, hipMemcpyDeviceToHost));
-    MDX_HIP(hipMemcpy(origin_counts, sums + 2 * bytes, bytes, hipMemcpyDeviceToHost));
-    return MDX_OK;
+    // sums of at most frames x n_h x max_neighbors each
+    return h->walk.result(h->lags.n(), intermittent, continuous, origin_counts);
 }
 
 int mdx_hb_bonds(mdx_hb_t h, int64_t *out, int64_t n)
@@ -419,7 +358,7 @@ int mdx_hb_stats(mdx_hb_t h, int64_t *launches, double *kernel_ms, int64_t *fram
                  int64_t *max_row, int64_t *degenerate)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     uint64_t seen = 0;
     if (h->ready) {
         MDX_TRY(h->lists.look());

@@ -123,7 +123,6 @@ static int msid_accumulate_rows(mdx_msid *h, const float *d_pos, int64_t src_row
     const int64_t want = grouped ? h->mol.n_atoms : h->n_points;
     MDX_REQUIRE(n_rows == want, "%lld rows given, the groups%s hold %lld", (long long)n_rows,
                 grouped ? " (rows of the grouping)" : "", (long long)want);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(msid_grow_rows(h, n_frames));
     const int64_t n = h->n_points;
     if (h->unwrap && h->frames_seen == 0) {

@@ -13,8 +13,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_lag_history.hpp"
 #include "mdx_orient_device.hpp"
 
 #include <algorithm>
@@ -29,21 +29,20 @@ constexpr int64_t ORI_HISTORY_BYTES = int64_t(256) << 20;   // what the frames o
 
 }  // namespace
 
-struct mdx_ori : FrameEngine {
-    bool ready = false;                 // the device side exists
-    int n_groups = 0, n_lags = 0, keep = 7;
-    int64_t n_vectors = 0, n_rows = 0, max_lag = 0;
+struct mdx_ori : LazyFrameEngine {
+    int n_groups = 0, keep = 7;
+    int64_t n_vectors = 0, n_rows = 0;
     int64_t evaluations = 0;
-    int64_t cap = 0;                    // frames the ring holds
     int64_t degenerate = 0;             // degenerate vectors seen, as of the last look
+    LagTable lags;
+    LagRing ring;
     bool boxed = false;
     PairBox box = {{0, 0, 0}, {0, 0, 0}};
     std::vector<OriTile> tiles;
     std::vector<int> tile_offsets, pairs;
-    std::vector<int64_t> offsets, lags;
+    std::vector<int64_t> offsets;
     // d_frame_sums: double [frames seen][n_groups][6]; d_part: double [slab][tiles][6]; d_ctl: uint64 degenerate
-    DeviceBuffer d_tiles, d_tile_offsets, d_pairs, d_offsets, d_lags, d_acc, d_sums, d_hist, d_part, d_frame_sums,
-        d_ctl;
+    DeviceBuffer d_tiles, d_tile_offsets, d_pairs, d_offsets, d_acc, d_sums, d_hist, d_part, d_frame_sums, d_ctl;
 };
 
 static int64_t ori_slab(const mdx_ori *h)
@@ -55,7 +54,7 @@ static int64_t ori_slab(const mdx_ori *h)
 
 static int ori_zero(mdx_ori *h)
 {
-    MDX_HIP(hipMemsetAsync(h->d_acc.ptr, 0, size_t(16) * h->n_lags * h->n_vectors, h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_acc.ptr, 0, size_t(16) * h->lags.n() * h->n_vectors, h->stream));
     MDX_HIP(hipMemsetAsync(h->d_ctl.ptr, 0, 8, h->stream));
     if (h->d_frame_sums.ptr)
         MDX_HIP(hipMemsetAsync(h->d_frame_sums.ptr, 0, h->d_frame_sums.bytes, h->stream));
@@ -63,45 +62,36 @@ static int ori_zero(mdx_ori *h)
     return MDX_OK;
 }
 
-// the device side of the handle: stream, tables, counter and accumulators
-static int ori_ensure_device(mdx_ori *h)
+// the device side of the handle: tables, counter and accumulators
+static int ori_build(mdx_ori *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
     MDX_TRY(h->d_tiles.ensure(sizeof(OriTile) * h->tiles.size()));
     MDX_TRY(h->d_tile_offsets.ensure(size_t(4) * (h->n_groups + 1)));
     MDX_TRY(h->d_pairs.ensure(size_t(8) * h->n_vectors));
     MDX_TRY(h->d_offsets.ensure(size_t(8) * (h->n_groups + 1)));
-    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
-    MDX_TRY(h->d_acc.ensure(size_t(16) * h->n_lags * h->n_vectors));
-    MDX_TRY(h->d_sums.ensure(size_t(16) * h->n_lags * h->n_groups));
+    MDX_TRY(h->d_acc.ensure(size_t(16) * h->lags.n() * h->n_vectors));
+    MDX_TRY(h->d_sums.ensure(size_t(16) * h->lags.n() * h->n_groups));
     MDX_TRY(h->d_ctl.ensure(8));
     MDX_HIP(hipMemcpy(h->d_tiles.ptr, h->tiles.data(), sizeof(OriTile) * h->tiles.size(), hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_tile_offsets.ptr, h->tile_offsets.data(), size_t(4) * (h->n_groups + 1),
                       hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_pairs.ptr, h->pairs.data(), size_t(8) * h->n_vectors, hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_offsets.ptr, h->offsets.data(), size_t(8) * (h->n_groups + 1), hipMemcpyHostToDevice));
-    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
-    MDX_TRY(ori_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    MDX_TRY(h->lags.upload());
+    return ori_zero(h);
 }
 
-// The ring and the tile partials of a slab, sized before the first frame of a pass: max(lags) carried frames plus the
-// frames of a slab.  Nothing is in flight then (a reset waits for the stream), so growing them loses nothing.
-static int ori_ensure_history(mdx_ori *h)
+static int ori_ensure_device(mdx_ori *h) { return h->ensure_device(ori_build); }
+
+// What a route prepares before the first kernel: the device side, and before the first frame of a pass the ring and
+// the tile partials of a slab.
+static int ori_prepare(mdx_ori *h, int64_t)
 {
-    if (h->frames_seen > 0)
-        return MDX_OK;
-    const int64_t slab = ori_slab(h), cap = h->max_lag + slab;
-    MDX_REQUIRE(cap < (int64_t(1) << 40) / (24 * h->n_vectors),
-                "a history of %lld frames of %lld vectors is too large", (long long)cap, (long long)h->n_vectors);
-    MDX_TRY(h->d_hist.ensure(size_t(24) * h->n_vectors * cap));
-    MDX_TRY(h->d_part.ensure(size_t(48) * h->tiles.size() * slab));
-    h->cap = cap;
-    return MDX_OK;
+    MDX_TRY(ori_ensure_device(h));
+    MDX_TRY(h->ring.ensure(h->frames_seen, h->lags.max_lag, ori_slab(h), 24 * h->n_vectors,
+                           "a history of %lld frames of %lld vectors is too large", (long long)h->n_vectors));
+    MDX_TRY(h->d_hist.ensure(size_t(24) * h->n_vectors * h->ring.cap));
+    return h->d_part.ensure(size_t(48) * h->tiles.size() * h->ring.slab(ori_slab(h)));
 }
 
 // With the stream idle: the degenerate vectors seen; one of them refuses the results until a reset.
@@ -130,12 +120,11 @@ static int ori_accumulate_rows(mdx_ori *h, const float *d_pos, int64_t src_rows,
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the pairs hold %lld", (long long)n_rows,
                 (long long)h->n_rows);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(grow_frames(h->d_frame_sums, h->stream, size_t(48) * h->n_groups, h->frames_seen,
                         h->frames_seen + n_frames));
     const int n = (int)h->n_vectors, n_tiles = (int)h->tiles.size();
-    const int64_t slab = std::min(ori_slab(h), h->cap - h->max_lag);
-    const dim3 cor_grid((unsigned)n_tiles, (unsigned)ceil_div(h->n_lags, ORI_BLOCK_LAGS));
+    const int64_t slab = h->ring.slab(ori_slab(h)), cap = h->ring.cap;
+    const dim3 cor_grid((unsigned)n_tiles, (unsigned)ceil_div(h->lags.n(), ORI_BLOCK_LAGS));
     const auto prepare = h->boxed ? ori_prepare_kernel<true> : ori_prepare_kernel<false>;
     hipEvent_t ev = h->timer.begin();
     for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
@@ -144,16 +133,15 @@ static int ori_accumulate_rows(mdx_ori *h, const float *d_pos, int64_t src_rows,
         const int64_t f0 = h->frames_seen;
         hipLaunchKernelGGL(prepare, dim3((unsigned)ceil_div(n_tiles, ORI_BLOCK_TILES), (unsigned)nf),
                            dim3(ORI_TILE * ORI_BLOCK_TILES), 0, h->stream, pos, src_rows, d_index,
-                           h->d_pairs.as<int>(), h->d_tiles.as<OriTile>(), n_tiles, n, f0, h->cap, h->box, h->keep,
+                           h->d_pairs.as<int>(), h->d_tiles.as<OriTile>(), n_tiles, n, f0, cap, h->box, h->keep,
                            h->d_hist.as<double>(), h->d_part.as<double>(), h->d_ctl.as<unsigned long long>());
         hipLaunchKernelGGL(ori_group_kernel, dim3((unsigned)ceil_div(nf * h->n_groups * 6, 256)), dim3(256), 0,
                            h->stream, h->d_part.as<double>(), n_tiles, h->d_tile_offsets.as<int>(), h->n_groups,
                            (int)nf, f0, h->d_frame_sums.as<double>());
         hipLaunchKernelGGL(ori_correlate_kernel, cor_grid, dim3(ORI_THREADS), 0, h->stream, h->d_hist.as<double>(),
-                           h->cap, n, h->d_tiles.as<OriTile>(), h->d_lags.as<int64_t>(), h->n_lags, f0, f0 + nf,
+                           cap, n, h->d_tiles.as<OriTile>(), h->lags.d_lags.as<int64_t>(), h->lags.n(), f0, f0 + nf,
                            h->d_acc.as<double>());
-        for (int64_t lag : h->lags)
-            h->evaluations += h->n_vectors * std::max<int64_t>(0, f0 + nf - std::max(f0, lag));
+        h->evaluations += h->n_vectors * h->lags.origins_met(f0, nf);
         h->frames_seen += nf;
     }
     h->timer.end(ev);
@@ -185,20 +173,15 @@ int mdx_ori_create(mdx_ori_t *out, int dev, int n_groups, const int64_t *n_vecto
                     "vector %lld: pair (%d, %d) out of range [0, %lld)", (long long)v, tail, head, (long long)n_rows);
         MDX_REQUIRE(tail != head, "vector %lld: row %d is both tail and head", (long long)v, tail);
     }
-    for (int k = 0; k < n_lags; ++k) {
-        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
-        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
-    }
+    MDX_TRY(LagTable::check(n_lags, lags));
     MDX_REQUIRE(int64_t(n_lags) * n_groups < (int64_t(1) << 30), "too many sums");
     mdx_ori *h = new mdx_ori();
     h->dev = dev;
     h->n_groups = n_groups;
-    h->n_lags = n_lags;
     h->keep = 7 & ~zero_dims;
     h->n_vectors = total;
     h->n_rows = n_rows;
-    h->max_lag = lags[n_lags - 1];
-    h->lags.assign(lags, lags + n_lags);
+    h->lags.assign(n_lags, lags);
     h->pairs.assign(pairs, pairs + 2 * total);
     // the tiles of every group (a tile never spans two groups) and the groups' vector and tile ranges
     h->offsets.push_back(0);
@@ -220,8 +203,8 @@ int mdx_ori_destroy(mdx_ori_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_tiles, &h->d_tile_offsets, &h->d_pairs, &h->d_offsets, &h->d_lags, &h->d_acc, &h->d_sums,
-                    &h->d_hist, &h->d_part, &h->d_frame_sums, &h->d_ctl});
+        h->release({&h->d_tiles, &h->d_tile_offsets, &h->d_pairs, &h->d_offsets, &h->lags.d_lags, &h->d_acc,
+                    &h->d_sums, &h->d_hist, &h->d_part, &h->d_frame_sums, &h->d_ctl});
     delete h;
     return MDX_OK;
 }
@@ -229,17 +212,9 @@ int mdx_ori_destroy(mdx_ori_t h)
 int mdx_ori_reset(mdx_ori_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;         // the history starts over with the next frame
     h->evaluations = 0;
     h->degenerate = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(ori_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(ori_zero);  // frames_seen = 0: the history starts over with the next frame
 }
 
 int mdx_ori_set_box(mdx_ori_t h, const double *dims)
@@ -260,17 +235,7 @@ int mdx_ori_set_box(mdx_ori_t h, const double *dims)
 int mdx_ori_set_slab_frames(mdx_ori_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= ORI_SLAB_MAX, "frames must lie in [0, %lld]", (long long)ORI_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_ori_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
-}
-
-// what a route prepares before the first kernel
-static int ori_prepare(mdx_ori *h, int64_t)
-{
-    MDX_TRY(ori_ensure_device(h));
-    return ori_ensure_history(h);
+    return h->set_slab_frames(frames, ORI_SLAB_MAX, "mdx_ori_set_slab_frames");
 }
 
 int mdx_ori_accumulate_device(mdx_ori_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
@@ -300,24 +265,20 @@ int mdx_ori_accumulate_traj(mdx_ori_t h, mdx_traj_t traj, const int64_t *frames,
 int mdx_ori_synchronize(mdx_ori_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return ori_check(h);
+    MDX_TRY(h->synchronize());
+    return h->ready ? ori_check(h) : MDX_OK;
 }
 
 int mdx_ori_result(mdx_ori_t h, double *sums)
 {
     MDX_REQUIRE(h && sums, "NULL argument");
     MDX_TRY(ori_ensure_device(h));
-    hipLaunchKernelGGL(ori_fold_kernel, dim3((unsigned)ceil_div(int64_t(2) * h->n_lags * h->n_groups, 256)),
+    hipLaunchKernelGGL(ori_fold_kernel, dim3((unsigned)ceil_div(int64_t(2) * h->lags.n() * h->n_groups, 256)),
                        dim3(256), 0, h->stream, h->d_acc.as<double>(), (int)h->n_vectors,
-                       h->d_offsets.as<int64_t>(), h->n_groups, h->n_lags, h->d_sums.as<double>());
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+                       h->d_offsets.as<int64_t>(), h->n_groups, h->lags.n(), h->d_sums.as<double>());
+    MDX_TRY(h->collect());
     MDX_TRY(ori_check(h));
-    MDX_HIP(hipMemcpy(sums, h->d_sums.ptr, size_t(16) * h->n_lags * h->n_groups, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(sums, h->d_sums.ptr, size_t(16) * h->lags.n() * h->n_groups, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
@@ -327,7 +288,7 @@ int mdx_ori_vector_sums(mdx_ori_t h, double *out)
     MDX_TRY(ori_ensure_device(h));
     MDX_HIP(hipStreamSynchronize(h->stream));
     MDX_TRY(ori_check(h));
-    MDX_HIP(hipMemcpy(out, h->d_acc.ptr, size_t(16) * h->n_lags * h->n_vectors, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(out, h->d_acc.ptr, size_t(16) * h->lags.n() * h->n_vectors, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
@@ -349,7 +310,7 @@ int mdx_ori_stats(mdx_ori_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *degenerate)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     if (h->ready)
         MDX_TRY(ori_look(h));
     if (evaluations) *evaluations = h->evaluations;

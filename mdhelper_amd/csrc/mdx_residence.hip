@@ -12,9 +12,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
-#include "mdx_pairs_host.hpp"
+#include "mdx_lag_history.hpp"
 #include "mdx_residence_device.hpp"
 
 #include <algorithm>
@@ -29,19 +28,17 @@ constexpr int64_t PRS_HISTORY_BYTES = int64_t(256) << 20;   // what the frames o
 
 }  // namespace
 
-struct mdx_prs : FrameEngine {
-    bool ready = false;                 // the device side exists
-    int n_lags = 0, keep = 7;
-    bool same = false, continuous = true;
+struct mdx_prs : LazyFrameEngine {
+    int keep = 7;
+    bool same = false;
     int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
-    int64_t max_lag = 0, origin_step = 1;
-    int64_t cap = 0;                    // frames the rings hold
+    LagTable lags;
+    LagRing ring;                       // frames the rings hold
     PairBox box;
     CappedLists lists;                  // the rings of contact lists
+    SurvivalWalk walk;
     double rc2 = 0.0;
-    std::vector<int64_t> lags;
-    // d_sums: uint64 [3][n_lags] intermittent, continuous, origin_counts; d_contacts: uint64, one per frame seen
-    DeviceBuffer d_lags, d_sums, d_contacts, d_slab, d_mask;
+    DeviceBuffer d_contacts, d_slab;    // d_contacts: uint64, one per frame seen
 };
 
 // bytes a frame takes: its gathered rows while it is in flight, its lists and masks while it is in the rings
@@ -57,44 +54,34 @@ static int64_t prs_slab(const mdx_prs *h)
 
 static int prs_zero(mdx_prs *h)
 {
-    MDX_HIP(hipMemsetAsync(h->d_sums.ptr, 0, size_t(24) * h->n_lags, h->stream));
+    MDX_TRY(h->walk.zero(h->lags.n(), h->stream));
     if (h->d_contacts.ptr)
         MDX_HIP(hipMemsetAsync(h->d_contacts.ptr, 0, h->d_contacts.bytes, h->stream));
     return h->lists.zero(h->stream);
 }
 
-// the device side of the handle: stream, tables and counters
-static int prs_ensure_device(mdx_prs *h)
+// the device side of the handle: tables and counters
+static int prs_build(mdx_prs *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
-    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
-    MDX_TRY(h->d_sums.ensure(size_t(24) * h->n_lags));
+    MDX_TRY(h->walk.ensure(h->lags.n()));
     MDX_TRY(h->lists.ensure_ctl());
-    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
-    MDX_TRY(prs_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    MDX_TRY(h->lags.upload());
+    return prs_zero(h);
 }
 
-// The rings and the slab, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.
-// Nothing is in flight then (a reset waits for the stream), so growing them loses nothing.
-static int prs_ensure_rings(mdx_prs *h)
+static int prs_ensure_device(mdx_prs *h) { return h->ensure_device(prs_build); }
+
+// What a route prepares before the first kernel: the device side, and before the first frame of a pass the rings and
+// the slab.
+static int prs_prepare(mdx_prs *h, int64_t)
 {
-    if (h->frames_seen > 0)
-        return MDX_OK;
-    const int64_t slab = prs_slab(h), cap = h->max_lag + slab;
-    MDX_REQUIRE(cap < (int64_t(1) << 40) / prs_frame_bytes(h),
-                "a history of %lld frames of %lld points with %d neighbors each is too large", (long long)cap,
-                (long long)h->n1, h->lists.max_nb);
-    MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * slab));
-    MDX_TRY(h->lists.ensure(h->n1, cap));
-    if (h->continuous)
-        MDX_TRY(h->d_mask.ensure(size_t(8) * h->n1 * cap));
-    h->cap = cap;
-    return MDX_OK;
+    MDX_TRY(prs_ensure_device(h));
+    MDX_TRY(h->ring.ensure(h->frames_seen, h->lags.max_lag, prs_slab(h), prs_frame_bytes(h),
+                           "a history of %lld frames of %lld points with %d neighbors each is too large",
+                           (long long)h->n1, h->lists.max_nb));
+    MDX_TRY(h->d_slab.ensure(size_t(12) * h->n_rows * h->ring.slab(prs_slab(h))));
+    MDX_TRY(h->lists.ensure(h->n1, h->ring.cap));
+    return h->walk.ensure_mask(h->n1, h->ring.cap);
 }
 
 // With the stream idle: the largest row seen; a row beyond the cap refuses the results until a reset.
@@ -110,41 +97,27 @@ static int prs_accumulate_rows(mdx_prs *h, const float *d_pos, int64_t src_rows,
     if (n_frames == 0)
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n_rows, (long long)h->n_rows);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     MDX_TRY(grow_frames(h->d_contacts, h->stream, 8, h->frames_seen, h->frames_seen + n_frames));
     const int n = (int)h->n_rows, n1 = (int)h->n1, max_nb = h->lists.max_nb;
     int *len = h->lists.d_len.as<int>(), *list = h->lists.d_list.as<int>();
-    const int64_t slab = std::min(prs_slab(h), h->cap - h->max_lag);
+    const int64_t slab = h->ring.slab(prs_slab(h));
     const int64_t n_jchunks = ceil_div(h->n2, PRS_JCHUNK);
     const int64_t blocks = ceil_div(h->n1, PRS_TILE) * n_jchunks;
-    const int64_t walk_tiles = ceil_div(h->n1, PRS_WALK_THREADS);
     hipEvent_t ev = h->timer.begin();
     for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f_lo = h->frames_seen;
         launch_gather<false>(h->stream, pos, src_rows, d_index, n, nf, h->d_slab.as<float>());
-        // the rows of the new frames start empty: their ring slots are one range, or two where the ring wraps
-        const int64_t first = f_lo % h->cap, head = std::min(nf, h->cap - first);
-        MDX_HIP(hipMemsetAsync(len + first * n1, 0, size_t(4) * n1 * head, h->stream));
-        if (nf > head)
-            MDX_HIP(hipMemsetAsync(len, 0, size_t(4) * n1 * (nf - head), h->stream));
+        // the rows of the new frames start empty
+        MDX_TRY(h->ring.zero_slots(len, size_t(4) * n1, f_lo, nf, h->stream));
         const auto contact = h->keep == 7 ? prs_contact_kernel<true> : prs_contact_kernel<false>;
         hipLaunchKernelGGL(contact, dim3((unsigned)blocks, 1, (unsigned)nf), dim3(PRS_THREADS), 0, h->stream,
-                           h->d_slab.as<float>(), h->cap, n, n1, (int)h->n2, h->same ? 0 : n1, h->same ? 1 : 0,
+                           h->d_slab.as<float>(), h->ring.cap, n, n1, (int)h->n2, h->same ? 0 : n1, h->same ? 1 : 0,
                            (int)n_jchunks, f_lo, h->box, h->keep, h->rc2, max_nb, len, list,
                            h->d_contacts.as<unsigned long long>(), h->lists.d_ctl.as<int>());
-        // the origins that meet a new frame: multiples of origin_step in [f_lo - max_lag, f_lo + nf)
-        const int64_t o_lo = ceil_div(std::max<int64_t>(0, f_lo - h->max_lag), h->origin_step);
-        const int64_t o_hi = ceil_div(f_lo + nf, h->origin_step);
-        const auto walk = h->continuous ? prs_walk_kernel<true> : prs_walk_kernel<false>;
-        for (int64_t o = o_lo; o < o_hi; o += PRS_WALK_ORIGINS) {
-            const int64_t n_o = std::min<int64_t>(PRS_WALK_ORIGINS, o_hi - o);
-            hipLaunchKernelGGL(walk, dim3((unsigned)walk_tiles, (unsigned)n_o), dim3(PRS_WALK_THREADS), 0, h->stream,
-                               h->cap, n1, max_nb, len, list,
-                               h->d_mask.as<unsigned long long>(), h->d_lags.as<int64_t>(), h->n_lags, h->max_lag, o,
-                               h->origin_step, f_lo, nf, h->d_sums.as<unsigned long long>());
-        }
+        h->walk.walk(prs_walk_kernel<true>, prs_walk_kernel<false>, h->stream, h->lags, h->ring, h->lists, n1, f_lo,
+                     nf);
         h->frames_seen += nf;
     }
     h->timer.end(ev);
@@ -173,10 +146,7 @@ int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, do
                 "the sets must hold fewer than 2^31 / 3 points");
     MDX_REQUIRE(ceil_div(n1, PRS_TILE) * ceil_div(n2, PRS_JCHUNK) < (int64_t(1) << 31),
                 "%lld x %lld points are too many pairs for one launch", (long long)n1, (long long)n2);
-    for (int k = 0; k < n_lags; ++k) {
-        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
-        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
-    }
+    MDX_TRY(LagTable::check(n_lags, lags));
     MDX_REQUIRE(cutoff > 0.0 && std::isfinite(cutoff), "cutoff must be positive and finite");
     PairBox box;
     int keep = 7;
@@ -186,15 +156,12 @@ int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, do
     h->n1 = n1;
     h->n2 = n2;
     h->same = same != 0;
-    h->continuous = continuous != 0;
+    h->walk.continuous = continuous != 0;
     h->n_rows = same ? n1 : n1 + n2;
-    h->n_lags = n_lags;
     h->keep = keep;
     h->box = box;
     h->lists.max_nb = max_neighbors;
-    h->origin_step = origin_step;
-    h->max_lag = lags[n_lags - 1];
-    h->lags.assign(lags, lags + n_lags);
+    h->lags.assign(n_lags, lags, origin_step);
     h->rc2 = cutoff * cutoff;
     *out = h;
     return MDX_OK;
@@ -205,8 +172,8 @@ int mdx_prs_destroy(mdx_prs_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_lags, &h->d_sums, &h->d_contacts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
-                    &h->lists.d_list, &h->d_mask});
+        h->release({&h->lags.d_lags, &h->walk.d_sums, &h->d_contacts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
+                    &h->lists.d_list, &h->walk.d_mask});
     delete h;
     return MDX_OK;
 }
@@ -214,32 +181,14 @@ int mdx_prs_destroy(mdx_prs_t h)
 int mdx_prs_reset(mdx_prs_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;         // the history starts over with the next frame
     h->lists.max_row = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(prs_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(prs_zero);  // frames_seen = 0: the history starts over with the next frame
 }
 
 int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= PRS_SLAB_MAX, "frames must lie in [0, %lld]", (long long)PRS_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_prs_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
-}
-
-// what a route prepares before the first kernel
-static int prs_prepare(mdx_prs *h, int64_t)
-{
-    MDX_TRY(prs_ensure_device(h));
-    return prs_ensure_rings(h);
+    return h->set_slab_frames(frames, PRS_SLAB_MAX, "mdx_prs_set_slab_frames");
 }
 
 int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
@@ -269,27 +218,18 @@ int mdx_prs_accumulate_traj(mdx_prs_t h, mdx_traj_t traj, const int64_t *frames,
 int mdx_prs_synchronize(mdx_prs_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return prs_check_rows(h);
+    MDX_TRY(h->synchronize());
+    return h->ready ? prs_check_rows(h) : MDX_OK;
 }
 
 int mdx_prs_result(mdx_prs_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts)
 {
     MDX_REQUIRE(h && intermittent && continuous && origin_counts, "NULL argument");
     MDX_TRY(prs_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     MDX_TRY(prs_check_rows(h));
-    // uint64 sums of at most frames x n1 x max_neighbors < 2^63 each: they fit an int64
-    const size_t bytes = size_t(8) * h->n_lags;
-    const char *sums = h->d_sums.as<char>();
-    MDX_HIP(hipMemcpy(intermittent, sums, bytes, hipMemcpyDeviceToHost));
-    MDX_HIP(hipMemcpy(continuous, sums + bytes, bytes, hipMemcpyDeviceToHost));
-    MDX_HIP(hipMemcpy(origin_counts, sums + 2 * bytes, bytes, hipMemcpyDeviceToHost));
-    return MDX_OK;
+    // sums of at most frames x n1 x max_neighbors each
+    return h->walk.result(h->lags.n(), intermittent, continuous, origin_counts);
 }
 
 int mdx_prs_contacts(mdx_prs_t h, int64_t *out, int64_t n)
@@ -310,7 +250,7 @@ int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *max_row)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     if (h->ready)
         MDX_TRY(h->lists.look());
     if (evaluations) *evaluations = h->frames_seen * (h->n1 * h->n2 - (h->same ? h->n1 : 0));

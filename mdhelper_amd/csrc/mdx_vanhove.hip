@@ -12,8 +12,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
+#include "mdx_lag_history.hpp"
 #include "mdx_vanhove_device.hpp"
 
 #include <algorithm>
@@ -28,19 +28,18 @@ constexpr int64_t VH_HISTORY_BYTES = int64_t(256) << 20;    // what the frames o
 
 }  // namespace
 
-struct mdx_vh : FrameEngine {
-    bool ready = false;                 // the device side exists
-    int n_groups = 0, n_bins = 0, n_lags = 0, keep = 7;
-    int64_t n_points = 0, max_lag = 0;
+struct mdx_vh : LazyFrameEngine {
+    int n_groups = 0, n_bins = 0, keep = 7;
+    int64_t n_points = 0;
     int64_t evaluations = 0;
-    int64_t cap = 0;                    // frames the ring holds
-    bool unwrap = false;
-    double dims[3] = {0, 0, 0};
+    LagTable lags;
+    LagRing ring;
+    UnwrappedHistory hist;
     double inv_width = 0.0;
     std::vector<VhTile> tiles;
-    std::vector<int64_t> offsets, lags;
+    std::vector<int64_t> offsets;
     std::vector<double> edges;
-    DeviceBuffer d_tiles, d_offsets, d_lags, d_edges, d_counts, d_acc, d_moments, d_hist, d_prev, d_image;
+    DeviceBuffer d_tiles, d_offsets, d_edges, d_counts, d_acc, d_moments;
 };
 
 static int64_t vh_slab(const mdx_vh *h)
@@ -52,49 +51,37 @@ static int64_t vh_slab(const mdx_vh *h)
 
 static int vh_zero(mdx_vh *h)
 {
-    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->n_lags * h->n_groups * h->n_bins, h->stream));
-    MDX_HIP(hipMemsetAsync(h->d_acc.ptr, 0, size_t(16) * h->n_lags * h->n_points, h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->lags.n() * h->n_groups * h->n_bins, h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_acc.ptr, 0, size_t(16) * h->lags.n() * h->n_points, h->stream));
     return MDX_OK;
 }
 
-// the device side of the handle: stream, tables, counters and accumulators
-static int vh_ensure_device(mdx_vh *h)
+// the device side of the handle: tables, counters and accumulators
+static int vh_build(mdx_vh *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
-    const int64_t n = h->n_points;
     MDX_TRY(h->d_tiles.ensure(sizeof(VhTile) * h->tiles.size()));
     MDX_TRY(h->d_offsets.ensure(size_t(8) * (h->n_groups + 1)));
-    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
     MDX_TRY(h->d_edges.ensure(size_t(8) * (h->n_bins + 1)));
-    MDX_TRY(h->d_counts.ensure(size_t(8) * h->n_lags * h->n_groups * h->n_bins));
-    MDX_TRY(h->d_acc.ensure(size_t(16) * h->n_lags * n));
-    MDX_TRY(h->d_moments.ensure(size_t(16) * h->n_lags * h->n_groups));
-    MDX_TRY(h->d_prev.ensure(size_t(24) * n));
-    MDX_TRY(h->d_image.ensure(size_t(12) * n));
+    MDX_TRY(h->d_counts.ensure(size_t(8) * h->lags.n() * h->n_groups * h->n_bins));
+    MDX_TRY(h->d_acc.ensure(size_t(16) * h->lags.n() * h->n_points));
+    MDX_TRY(h->d_moments.ensure(size_t(16) * h->lags.n() * h->n_groups));
+    MDX_TRY(h->hist.ensure_state(h->n_points));
     MDX_HIP(hipMemcpy(h->d_tiles.ptr, h->tiles.data(), sizeof(VhTile) * h->tiles.size(), hipMemcpyHostToDevice));
     MDX_HIP(hipMemcpy(h->d_offsets.ptr, h->offsets.data(), size_t(8) * (h->n_groups + 1), hipMemcpyHostToDevice));
-    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
+    MDX_TRY(h->lags.upload());
     MDX_HIP(hipMemcpy(h->d_edges.ptr, h->edges.data(), size_t(8) * (h->n_bins + 1), hipMemcpyHostToDevice));
-    MDX_TRY(vh_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    return vh_zero(h);
 }
 
-// The ring, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.  Nothing is
-// in flight then (a reset waits for the stream), so growing it loses nothing.
-static int vh_ensure_history(mdx_vh *h)
+static int vh_ensure_device(mdx_vh *h) { return h->ensure_device(vh_build); }
+
+// what a route prepares before the first kernel: the device side, and before the first frame of a pass the ring
+static int vh_prepare(mdx_vh *h, int64_t)
 {
-    if (h->frames_seen > 0)
-        return MDX_OK;
-    const int64_t cap = h->max_lag + vh_slab(h);
-    MDX_REQUIRE(cap < (int64_t(1) << 40) / (24 * h->n_points),
-                "a history of %lld frames of %lld points is too large", (long long)cap, (long long)h->n_points);
-    MDX_TRY(h->d_hist.ensure(size_t(24) * h->n_points * cap));
-    h->cap = cap;
-    return MDX_OK;
+    MDX_TRY(vh_ensure_device(h));
+    MDX_TRY(h->ring.ensure(h->frames_seen, h->lags.max_lag, vh_slab(h), 24 * h->n_points,
+                           "a history of %lld frames of %lld points is too large", (long long)h->n_points));
+    return h->hist.ensure_ring(h->n_points, h->ring.cap);
 }
 
 // n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
@@ -105,38 +92,31 @@ static int vh_accumulate_rows(mdx_vh *h, const float *d_pos, int64_t src_rows, c
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_points, "%lld rows given, the groups hold %lld", (long long)n_rows,
                 (long long)h->n_points);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     const int n = (int)h->n_points;
-    const int64_t slab = std::min(vh_slab(h), h->cap - h->max_lag);
+    const int64_t slab = h->ring.slab(vh_slab(h)), cap = h->ring.cap;
     const bool lds = h->n_bins <= VH_LDS_BINS;
     const size_t lds_bytes = lds ? size_t(4) * VH_BLOCK_LAGS * h->n_bins : 0;
-    const dim3 bin_grid((unsigned)h->tiles.size(), (unsigned)ceil_div(h->n_lags, VH_BLOCK_LAGS));
+    const dim3 bin_grid((unsigned)h->tiles.size(), (unsigned)ceil_div(h->lags.n(), VH_BLOCK_LAGS));
     hipEvent_t ev = h->timer.begin();
     for (int64_t s0 = 0; s0 < n_frames; s0 += slab) {
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f0 = h->frames_seen;
-        if (h->unwrap)
-            hipLaunchKernelGGL(vh_prepare_kernel<true>, dim3((unsigned)ceil_div(3 * int64_t(n), 256)), dim3(256), 0,
-                               h->stream, pos, src_rows, d_index, n, (int)nf, f0, h->cap, h->dims[0], h->dims[1],
-                               h->dims[2], f0 == 0 ? 1 : 0, h->d_prev.as<double>(), h->d_image.as<int>(),
-                               h->d_hist.as<double>());
-        else
-            hipLaunchKernelGGL(vh_prepare_kernel<false>, dim3((unsigned)ceil_div(3 * int64_t(n), 256), (unsigned)nf),
-                               dim3(256), 0, h->stream, pos, src_rows, d_index, n, (int)nf, f0, h->cap, 0.0, 0.0,
-                               0.0, 0, (double *)nullptr, (int *)nullptr, h->d_hist.as<double>());
+        h->hist.prepare(vh_prepare_kernel<true>, vh_prepare_kernel<false>, h->stream, pos, src_rows, d_index, n, nf, f0,
+                        cap);
         if (lds)
             hipLaunchKernelGGL(vh_bin_kernel<true>, bin_grid, dim3(VH_THREADS), lds_bytes, h->stream,
-                               h->d_hist.as<double>(), h->cap, n, h->d_tiles.as<VhTile>(), h->d_lags.as<int64_t>(),
-                               h->n_lags, f0, f0 + nf, h->keep, h->d_edges.as<double>(), h->n_bins, h->inv_width,
-                               h->n_groups, h->d_counts.as<unsigned long long>(), h->d_acc.as<double>());
+                               h->hist.d_hist.as<double>(), cap, n, h->d_tiles.as<VhTile>(),
+                               h->lags.d_lags.as<int64_t>(), h->lags.n(), f0, f0 + nf, h->keep,
+                               h->d_edges.as<double>(), h->n_bins, h->inv_width, h->n_groups,
+                               h->d_counts.as<unsigned long long>(), h->d_acc.as<double>());
         else
             hipLaunchKernelGGL(vh_bin_kernel<false>, bin_grid, dim3(VH_THREADS), 0, h->stream,
-                               h->d_hist.as<double>(), h->cap, n, h->d_tiles.as<VhTile>(), h->d_lags.as<int64_t>(),
-                               h->n_lags, f0, f0 + nf, h->keep, h->d_edges.as<double>(), h->n_bins, h->inv_width,
-                               h->n_groups, h->d_counts.as<unsigned long long>(), h->d_acc.as<double>());
-        for (int64_t lag : h->lags)
-            h->evaluations += h->n_points * std::max<int64_t>(0, f0 + nf - std::max(f0, lag));
+                               h->hist.d_hist.as<double>(), cap, n, h->d_tiles.as<VhTile>(),
+                               h->lags.d_lags.as<int64_t>(), h->lags.n(), f0, f0 + nf, h->keep,
+                               h->d_edges.as<double>(), h->n_bins, h->inv_width, h->n_groups,
+                               h->d_counts.as<unsigned long long>(), h->d_acc.as<double>());
+        h->evaluations += h->n_points * h->lags.origins_met(f0, nf);
         h->frames_seen += nf;
     }
     h->timer.end(ev);
@@ -166,20 +146,15 @@ int mdx_vh_create(mdx_vh_t *out, int dev, int n_groups, const int64_t *n_points,
         MDX_REQUIRE(std::isfinite(edges[b]), "edges must be finite");
         MDX_REQUIRE(b == 0 || edges[b] > edges[b - 1], "edges must be strictly increasing");
     }
-    for (int k = 0; k < n_lags; ++k) {
-        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
-        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
-    }
+    MDX_TRY(LagTable::check(n_lags, lags));
     MDX_REQUIRE(int64_t(n_lags) * n_groups * n_bins < (int64_t(1) << 31), "too many counters");
     mdx_vh *h = new mdx_vh();
     h->dev = dev;
     h->n_groups = n_groups;
     h->n_bins = n_bins;
-    h->n_lags = n_lags;
     h->keep = 7 & ~zero_dims;
     h->n_points = total;
-    h->max_lag = lags[n_lags - 1];
-    h->lags.assign(lags, lags + n_lags);
+    h->lags.assign(n_lags, lags);
     h->edges.assign(edges, edges + n_bins + 1);
     h->inv_width = double(n_bins) / (edges[n_bins] - edges[0]);
     // the tiles of every group (a tile never spans two groups) and the groups' point ranges
@@ -200,8 +175,8 @@ int mdx_vh_destroy(mdx_vh_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_tiles, &h->d_offsets, &h->d_lags, &h->d_edges, &h->d_counts, &h->d_acc, &h->d_moments,
-                    &h->d_hist, &h->d_prev, &h->d_image});
+        h->release({&h->d_tiles, &h->d_offsets, &h->lags.d_lags, &h->d_edges, &h->d_counts, &h->d_acc, &h->d_moments,
+                    &h->hist.d_hist, &h->hist.d_prev, &h->hist.d_image});
     delete h;
     return MDX_OK;
 }
@@ -209,45 +184,20 @@ int mdx_vh_destroy(mdx_vh_t h)
 int mdx_vh_reset(mdx_vh_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;         // the history and the unwrap state start over with the next frame
     h->evaluations = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(vh_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(vh_zero);   // frames_seen = 0: the history and the unwrap state start over with the next frame
 }
 
 int mdx_vh_set_unwrap(mdx_vh_t h, const double *dims)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (dims)
-        for (int k = 0; k < 3; ++k)
-            MDX_REQUIRE(dims[k] > 0.0 && std::isfinite(dims[k]), "dims[%d] must be positive and finite", k);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_vh_set_unwrap must be called before the first frame");
-    h->unwrap = dims != nullptr;
-    for (int k = 0; k < 3; ++k)
-        h->dims[k] = dims ? dims[k] : 0.0;
-    return MDX_OK;
+    return h->hist.set_unwrap(dims, h->frames_seen, "mdx_vh_set_unwrap");
 }
 
 int mdx_vh_set_slab_frames(mdx_vh_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= VH_SLAB_MAX, "frames must lie in [0, %lld]", (long long)VH_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_vh_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
-}
-
-// what a route prepares before the first kernel
-static int vh_prepare(mdx_vh *h, int64_t)
-{
-    MDX_TRY(vh_ensure_device(h));
-    return vh_ensure_history(h);
+    return h->set_slab_frames(frames, VH_SLAB_MAX, "mdx_vh_set_slab_frames");
 }
 
 int mdx_vh_accumulate_device(mdx_vh_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
@@ -277,11 +227,7 @@ int mdx_vh_accumulate_traj(mdx_vh_t h, mdx_traj_t traj, const int64_t *frames, i
 int mdx_vh_synchronize(mdx_vh_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->synchronize();
 }
 
 int mdx_vh_result(mdx_vh_t h, int64_t *counts, double *moments)
@@ -289,16 +235,15 @@ int mdx_vh_result(mdx_vh_t h, int64_t *counts, double *moments)
     MDX_REQUIRE(h && counts, "NULL argument");
     MDX_TRY(vh_ensure_device(h));
     if (moments)
-        hipLaunchKernelGGL(vh_fold_kernel, dim3((unsigned)ceil_div(int64_t(2) * h->n_lags * h->n_groups, 256)),
+        hipLaunchKernelGGL(vh_fold_kernel, dim3((unsigned)ceil_div(int64_t(2) * h->lags.n() * h->n_groups, 256)),
                            dim3(256), 0, h->stream, h->d_acc.as<double>(), (int)h->n_points,
-                           h->d_offsets.as<int64_t>(), h->n_groups, h->n_lags, h->d_moments.as<double>());
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+                           h->d_offsets.as<int64_t>(), h->n_groups, h->lags.n(), h->d_moments.as<double>());
+    MDX_TRY(h->collect());
     // uint64 counters of at most frames x points each: they fit an int64
-    MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->n_lags * h->n_groups * h->n_bins,
+    MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->lags.n() * h->n_groups * h->n_bins,
                       hipMemcpyDeviceToHost));
     if (moments)
-        MDX_HIP(hipMemcpy(moments, h->d_moments.ptr, size_t(16) * h->n_lags * h->n_groups, hipMemcpyDeviceToHost));
+        MDX_HIP(hipMemcpy(moments, h->d_moments.ptr, size_t(16) * h->lags.n() * h->n_groups, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
@@ -307,14 +252,14 @@ int mdx_vh_point_moments(mdx_vh_t h, double *out)
     MDX_REQUIRE(h && out, "NULL argument");
     MDX_TRY(vh_ensure_device(h));
     MDX_HIP(hipStreamSynchronize(h->stream));
-    MDX_HIP(hipMemcpy(out, h->d_acc.ptr, size_t(16) * h->n_lags * h->n_points, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(out, h->d_acc.ptr, size_t(16) * h->lags.n() * h->n_points, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
 int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     if (evaluations) *evaluations = h->evaluations;
     return MDX_OK;
 }

@@ -11,9 +11,8 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
 #include "mdx_internal.hpp"
-#include "mdx_pairs_host.hpp"
+#include "mdx_lag_history.hpp"
 #include "mdx_vanhove_distinct_device.hpp"
 
 #include <algorithm>
@@ -28,19 +27,17 @@ constexpr int64_t VHD_HISTORY_BYTES = int64_t(256) << 20;   // what the frames o
 
 }  // namespace
 
-struct mdx_vhd : FrameEngine {
-    bool ready = false;                 // the device side exists
-    int n_bins = 0, n_lags = 0, keep = 7;
+struct mdx_vhd : LazyFrameEngine {
+    int n_bins = 0, keep = 7;
     bool same = false;
     int64_t n1 = 0, n2 = 0, n_rows = 0;         // n_rows: rows of an incoming frame (n1 with same, else n1 + n2)
-    int64_t max_lag = 0, origin_step = 1;
     int64_t evaluations = 0;
-    int64_t cap = 0;                    // frames the ring holds
+    LagTable lags;
+    LagRing ring;
     PairBox box;
     double inv_width = 0.0, r2_lo = 0.0, r2_hi = 0.0;
-    std::vector<int64_t> lags;
     std::vector<double> edges;
-    DeviceBuffer d_lags, d_edges, d_counts, d_ring;
+    DeviceBuffer d_edges, d_counts, d_ring;
 };
 
 static int64_t vhd_slab(const mdx_vhd *h)
@@ -50,39 +47,29 @@ static int64_t vhd_slab(const mdx_vhd *h)
 
 static int vhd_zero(mdx_vhd *h)
 {
-    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->n_lags * h->n_bins, h->stream));
+    MDX_HIP(hipMemsetAsync(h->d_counts.ptr, 0, size_t(8) * h->lags.n() * h->n_bins, h->stream));
     return MDX_OK;
 }
 
-// the device side of the handle: stream, tables and counters
-static int vhd_ensure_device(mdx_vhd *h)
+// the device side of the handle: tables and counters
+static int vhd_build(mdx_vhd *h)
 {
-    if (h->ready)
-        return set_device(h->dev);
-    MDX_TRY(h->acquire_stream());
-    MDX_TRY(h->d_lags.ensure(size_t(8) * h->n_lags));
     MDX_TRY(h->d_edges.ensure(size_t(8) * (h->n_bins + 1)));
-    MDX_TRY(h->d_counts.ensure(size_t(8) * h->n_lags * h->n_bins));
-    MDX_HIP(hipMemcpy(h->d_lags.ptr, h->lags.data(), size_t(8) * h->n_lags, hipMemcpyHostToDevice));
+    MDX_TRY(h->d_counts.ensure(size_t(8) * h->lags.n() * h->n_bins));
+    MDX_TRY(h->lags.upload());
     MDX_HIP(hipMemcpy(h->d_edges.ptr, h->edges.data(), size_t(8) * (h->n_bins + 1), hipMemcpyHostToDevice));
-    MDX_TRY(vhd_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->ready = true;
-    return MDX_OK;
+    return vhd_zero(h);
 }
 
-// The ring, sized before the first frame of a pass: max(lags) carried frames plus the frames of a slab.  Nothing is
-// in flight then (a reset waits for the stream), so growing it loses nothing.
-static int vhd_ensure_ring(mdx_vhd *h)
+static int vhd_ensure_device(mdx_vhd *h) { return h->ensure_device(vhd_build); }
+
+// what a route prepares before the first kernel: the device side, and before the first frame of a pass the ring
+static int vhd_prepare(mdx_vhd *h, int64_t)
 {
-    if (h->frames_seen > 0)
-        return MDX_OK;
-    const int64_t cap = h->max_lag + vhd_slab(h);
-    MDX_REQUIRE(cap < (int64_t(1) << 40) / (12 * h->n_rows), "a history of %lld frames of %lld points is too large",
-                (long long)cap, (long long)h->n_rows);
-    MDX_TRY(h->d_ring.ensure(size_t(12) * h->n_rows * cap));
-    h->cap = cap;
-    return MDX_OK;
+    MDX_TRY(vhd_ensure_device(h));
+    MDX_TRY(h->ring.ensure(h->frames_seen, h->lags.max_lag, vhd_slab(h), 12 * h->n_rows,
+                           "a history of %lld frames of %lld points is too large", (long long)h->n_rows));
+    return h->d_ring.ensure(size_t(12) * h->n_rows * h->ring.cap);
 }
 
 // n_frames frames of float32 rows in HBM: row index[i] (or i) of a frame of src_rows rows is incoming row i
@@ -92,9 +79,8 @@ static int vhd_accumulate_rows(mdx_vhd *h, const float *d_pos, int64_t src_rows,
     if (n_frames == 0)
         return MDX_OK;
     MDX_REQUIRE(n_rows == h->n_rows, "%lld rows given, the sets hold %lld", (long long)n_rows, (long long)h->n_rows);
-    MDX_REQUIRE(src_rows < (int64_t(1) << 31) / 3, "frames of %lld particles are too large", (long long)src_rows);
     const int n = (int)h->n_rows;
-    const int64_t slab = std::min(vhd_slab(h), h->cap - h->max_lag);
+    const int64_t slab = h->ring.slab(vhd_slab(h)), cap = h->ring.cap;
     const bool lds = h->n_bins <= VHD_LDS_BINS;
     const size_t lds_bytes =
         size_t(32) * VHD_STAGE + (lds ? size_t(8) * (h->n_bins + 1) + size_t(4) * VHD_WAVES * h->n_bins : 0);
@@ -106,20 +92,17 @@ static int vhd_accumulate_rows(mdx_vhd *h, const float *d_pos, int64_t src_rows,
         const int64_t nf = std::min(slab, n_frames - s0);
         const float *pos = d_pos + s0 * src_rows * 3;
         const int64_t f0 = h->frames_seen;
-        launch_gather<true>(h->stream, pos, src_rows, d_index, n, nf, h->d_ring.as<float>(), f0, h->cap);
-        const dim3 grid((unsigned)blocks, (unsigned)h->n_lags, (unsigned)nf);
+        launch_gather<true>(h->stream, pos, src_rows, d_index, n, nf, h->d_ring.as<float>(), f0, cap);
+        const dim3 grid((unsigned)blocks, (unsigned)h->lags.n(), (unsigned)nf);
         const auto kernel = lds ? (h->keep == 7 ? vhd_pair_kernel<true, true> : vhd_pair_kernel<true, false>)
                                 : (h->keep == 7 ? vhd_pair_kernel<false, true> : vhd_pair_kernel<false, false>);
-        hipLaunchKernelGGL(kernel, grid, dim3(VHD_THREADS), lds_bytes, h->stream, h->d_ring.as<float>(), h->cap, n,
+        hipLaunchKernelGGL(kernel, grid, dim3(VHD_THREADS), lds_bytes, h->stream, h->d_ring.as<float>(), cap, n,
                            (int)h->n1, (int)h->n2, h->same ? 0 : (int)h->n1, h->same ? 1 : 0, (int)n_jchunks,
-                           h->d_lags.as<int64_t>(), f0, h->origin_step, h->box, h->keep, h->d_edges.as<double>(),
-                           h->n_bins, h->inv_width, h->r2_lo, h->r2_hi, h->d_counts.as<unsigned long long>());
+                           h->lags.d_lags.as<int64_t>(), f0, h->lags.origin_step, h->box, h->keep,
+                           h->d_edges.as<double>(), h->n_bins, h->inv_width, h->r2_lo, h->r2_hi,
+                           h->d_counts.as<unsigned long long>());
         // the contract's pair count: origins f - lag that are multiples of origin_step, f among the new frames
-        for (int64_t lag : h->lags) {
-            const int64_t o_lo = std::max<int64_t>(0, f0 - lag), o_hi = f0 + nf - lag;      // origins [o_lo, o_hi)
-            if (o_hi > o_lo)
-                h->evaluations += per_pair * (ceil_div(o_hi, h->origin_step) - ceil_div(o_lo, h->origin_step));
-        }
+        h->evaluations += per_pair * h->lags.origins_met(f0, nf);
         h->frames_seen += nf;
     }
     h->timer.end(ev);
@@ -150,10 +133,7 @@ int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, in
         MDX_REQUIRE(std::isfinite(edges[b]), "edges must be finite");
         MDX_REQUIRE(b == 0 || edges[b] > edges[b - 1], "edges must be strictly increasing");
     }
-    for (int k = 0; k < n_lags; ++k) {
-        MDX_REQUIRE(lags[k] >= 0, "lags must not be negative");
-        MDX_REQUIRE(k == 0 || lags[k] > lags[k - 1], "lags must be strictly increasing");
-    }
+    MDX_TRY(LagTable::check(n_lags, lags));
     PairBox box;
     int keep = 7;
     MDX_TRY(check_box_cutoff(dims, zero_dims, edges[n_bins], &box, &keep,
@@ -166,12 +146,9 @@ int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, in
     h->same = same != 0;
     h->n_rows = same ? n1 : n1 + n2;
     h->n_bins = n_bins;
-    h->n_lags = n_lags;
     h->keep = keep;
     h->box = box;
-    h->origin_step = origin_step;
-    h->max_lag = lags[n_lags - 1];
-    h->lags.assign(lags, lags + n_lags);
+    h->lags.assign(n_lags, lags, origin_step);
     h->edges.assign(edges, edges + n_bins + 1);
     h->inv_width = double(n_bins) / (edges[n_bins] - edges[0]);
     // the margins of the early rejection (mdx_vanhove_distinct_device.hpp); an upper edge below 0 counts nothing
@@ -187,7 +164,7 @@ int mdx_vhd_destroy(mdx_vhd_t h)
     if (!h)
         return MDX_OK;
     if (h->stream)
-        h->release({&h->d_lags, &h->d_edges, &h->d_counts, &h->d_ring});
+        h->release({&h->lags.d_lags, &h->d_edges, &h->d_counts, &h->d_ring});
     delete h;
     return MDX_OK;
 }
@@ -195,32 +172,14 @@ int mdx_vhd_destroy(mdx_vhd_t h)
 int mdx_vhd_reset(mdx_vhd_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    h->frames_seen = 0;         // the history starts over with the next frame
     h->evaluations = 0;
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    MDX_TRY(vhd_zero(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->reset(vhd_zero);  // frames_seen = 0: the history starts over with the next frame
 }
 
 int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_REQUIRE(frames >= 0 && frames <= VHD_SLAB_MAX, "frames must lie in [0, %lld]", (long long)VHD_SLAB_MAX);
-    MDX_REQUIRE(h->frames_seen == 0, "mdx_vhd_set_slab_frames must be called before the first frame");
-    h->slab_frames = frames;
-    return MDX_OK;
-}
-
-// what a route prepares before the first kernel
-static int vhd_prepare(mdx_vhd *h, int64_t)
-{
-    MDX_TRY(vhd_ensure_device(h));
-    return vhd_ensure_ring(h);
+    return h->set_slab_frames(frames, VHD_SLAB_MAX, "mdx_vhd_set_slab_frames");
 }
 
 int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
@@ -250,28 +209,23 @@ int mdx_vhd_accumulate_traj(mdx_vhd_t h, mdx_traj_t traj, const int64_t *frames,
 int mdx_vhd_synchronize(mdx_vhd_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
-    if (!h->ready)
-        return MDX_OK;
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
+    return h->synchronize();
 }
 
 int mdx_vhd_result(mdx_vhd_t h, int64_t *counts)
 {
     MDX_REQUIRE(h && counts, "NULL argument");
     MDX_TRY(vhd_ensure_device(h));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.collect();
+    MDX_TRY(h->collect());
     // uint64 counters of at most frame pairs x n1 x n2 < 2^63 each: they fit an int64
-    MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->n_lags * h->n_bins, hipMemcpyDeviceToHost));
+    MDX_HIP(hipMemcpy(counts, h->d_counts.ptr, size_t(8) * h->lags.n() * h->n_bins, hipMemcpyDeviceToHost));
     return MDX_OK;
 }
 
 int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations)
 {
     MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->stats(h->ready, launches, kernel_ms, frames));
+    MDX_TRY(h->stats(launches, kernel_ms, frames));
     if (evaluations) *evaluations = h->evaluations;
     return MDX_OK;
 }

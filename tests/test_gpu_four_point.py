@@ -356,6 +356,42 @@ def test_one_set_of_bits_whatever_the_split_slab_segment_route_or_index(walk, un
         d_big.free()
 
 
+WRAP_LAGS = [0, 1, 3]
+
+
+@pytest.fixture(scope="module")
+def short_walk():
+    """9 frames of 65 points (a wave and one point) and the restatement for lags 0, 1, 3 without and with unwrap,
+    shared and left unchanged."""
+    pos = _walk(17, 9, 65, UNWRAP_DIMS)
+    want = {unwrap: restate(pos, [65], UNWRAP_CUTOFFS, WRAP_LAGS, dims=UNWRAP_DIMS if unwrap else None)
+            for unwrap in (False, True)}
+    assert (want[False][0] != want[True][0]).any()                  # points cross the box within 9 frames
+    assert all(w[0].all() for w in want.values())                   # every lag and cutoff counts something
+    np.testing.assert_array_equal(want[True][2], [9, 8, 6])
+    for a in (pos, *want[False][:3], *want[True][:3]):
+        a.setflags(write=False)
+    return pos, want
+
+
+@pytest.mark.parametrize("unwrap", [False, True])
+@pytest.mark.parametrize("slab", [1, 2])
+def test_the_ring_wraps(short_walk, slab, unwrap):
+    """With lags up to 3 the ring holds 3 + slab frames, fewer than the 9 fed in two calls: every slot is written
+    twice or more, the second call starts in the middle of the ring, and lag 3 reaches back across the wrap and
+    across the calls.  (The other tests of this file feed 37 frames to a ring of at least 41.)"""
+    pos, want = short_walk
+    assert WRAP_LAGS[-1] + slab < len(pos)
+
+    def setup(e):
+        if unwrap:
+            e.set_unwrap(UNWRAP_DIMS)
+        e.set_slab_frames(slab)
+
+    assert_same(engine_run(pos, [65], UNWRAP_CUTOFFS, WRAP_LAGS, splits=[0, 4, 9], setup=setup), want[unwrap])
+    assert_same(engine_run(pos, [65], UNWRAP_CUTOFFS, WRAP_LAGS, setup=setup), want[unwrap])
+
+
 def test_sums_equal_the_van_hove_counts_up_to_the_cutoff():
     """One cutoff a against the van Hove engine with the single bin [0, a] (closed on the right): the same points,
     found by r2 <= a*a here and by sqrt(r2) <= a there.  The two can disagree only for an r2 within an ulp or so of

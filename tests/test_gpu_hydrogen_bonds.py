@@ -118,6 +118,38 @@ def test_acceptors_around_one_chunk_and_rings_that_wrap_inside_one_call(n_a):
     assert_same(got, want)
 
 
+@pytest.fixture(scope="module")
+def short_walk():
+    """9 frames of 65 waters in a box of half the lengths (about twenty bonds a frame), the first 65 hydrogens, and the
+    restatement for lags 0, 1, 3, shared and left unchanged."""
+    box = BOX / 2
+    pos = water(400, 9, 65, box)
+    h_row, d_row, a_row = water_tables(65)
+    tables = (h_row[:65], d_row[:65], a_row)
+    want = restate(pos, *tables, DISTANCE, COS150, [0, 1, 3], box)
+    assert want["continuous"].all() and want["continuous"][2] < want["intermittent"][2] < want["origin_counts"][2]
+    assert want["bonds"].min() >= 10
+    pos.setflags(write=False)
+    return pos, tables, box, freeze(want)
+
+
+@pytest.mark.parametrize("continuous", [True, False])
+@pytest.mark.parametrize("slab", [1, 2])
+def test_the_rings_wrap_across_two_calls(short_walk, slab, continuous):
+    """With lags up to 3 the rings hold 3 + slab frames, fewer than the 9 fed as 4 + 5: every slot of the lists and
+    of the alive masks is emptied and written twice or more, the second call starts in the middle of the rings, and
+    lag 3 reaches back across the wrap and across the calls.  (The split tests below feed 12 frames to rings of at
+    least 14.)"""
+    pos, tables, box, want = short_walk
+
+    def run(**kw):
+        return engine_run(pos, tables, DISTANCE, COS150, [0, 1, 3], box, continuous=continuous,
+                          setup=lambda e: e.set_slab_frames(slab), **kw)
+
+    assert_same(run(splits=[0, 4, 9]), want, continuous=continuous)
+    assert_same(run(), want, continuous=continuous)
+
+
 def _three_rows(cases, dims):
     """float32 ``[len(cases), 3, 3]``: rows D, H, A of one frame per case ``(D, H - D, A - D)``, wrapped into the box
     (exact on the grid)."""

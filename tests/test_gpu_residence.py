@@ -171,6 +171,35 @@ def test_partners_around_one_chunk_and_rings_that_wrap_inside_one_call(n2):
                     restate(one, None, 4.0, [0, 1], BOX))
 
 
+@pytest.fixture(scope="module")
+def short_walk():
+    """9 frames of one set of 65 points and the restatement for lags 0, 1, 3, shared and left unchanged."""
+    pos = walk(400, 9, 65, step=0.25)
+    want = restate(pos, None, CUTOFF, [0, 1, 3], BOX)
+    assert want["continuous"].all() and want["continuous"][2] < want["intermittent"][2] < want["origin_counts"][2]
+    pos.setflags(write=False)
+    for key in KEYS + ("contacts",):
+        want[key].setflags(write=False)
+    return pos, want
+
+
+@pytest.mark.parametrize("continuous", [True, False])
+@pytest.mark.parametrize("slab", [1, 2])
+def test_the_rings_wrap_across_two_calls(short_walk, slab, continuous):
+    """With lags up to 3 the rings hold 3 + slab frames, fewer than the 9 fed as 4 + 5: every slot of the lists and
+    of the alive masks is emptied and written twice or more, the second call starts in the middle of the rings, and
+    lag 3 reaches back across the wrap and across the calls.  (The split tests below feed 12 frames to rings of at
+    least 14.)"""
+    pos, want = short_walk
+
+    def run(**kw):
+        return engine_run(pos, None, CUTOFF, [0, 1, 3], BOX, continuous=continuous,
+                          setup=lambda e: e.set_slab_frames(slab), **kw)
+
+    assert_same(run(splits=[0, 4, 9]), want, continuous=continuous)
+    assert_same(run(), want, continuous=continuous)
+
+
 def test_the_issue_figures_for_321_points():
     """The figures the restatement gives for walk(seed, 12, 321, step=0.25): rows well inside the default cap, the
     two functions apart from lag 2 on, lag 11 alive and lag 13 without an origin."""

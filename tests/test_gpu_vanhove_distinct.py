@@ -153,6 +153,29 @@ def test_partners_around_one_chunk_and_a_ring_that_wraps_inside_one_call(n2):
                     restate(one, None, EDGES, [0, 1], BOX), 3)
 
 
+@pytest.fixture(scope="module")
+def short_walk():
+    """9 frames of one set of 65 points and the restatement for lags 0, 1, 3, shared and left unchanged."""
+    pos = walk(400, 9, 65)
+    want = restate(pos, None, EDGES, [0, 1, 3], BOX)
+    assert want[0].sum(axis=-1).all()
+    np.testing.assert_array_equal(want[1], [9, 8, 6])
+    pos.setflags(write=False)
+    want[0].setflags(write=False)
+    return pos, want
+
+
+@pytest.mark.parametrize("slab", [1, 2])
+def test_the_ring_wraps_across_two_calls(short_walk, slab):
+    """With lags up to 3 the ring holds 3 + slab frames, fewer than the 9 fed as 4 + 5: every slot is written twice
+    or more, the second call starts in the middle of the ring, and lag 3 reaches back across the wrap and across the
+    calls.  (The split tests below feed 9 frames to a ring of at least 11.)"""
+    pos, want = short_walk
+    setup = lambda e: e.set_slab_frames(slab)      # noqa: E731
+    assert_same(engine_run(pos, None, EDGES, [0, 1, 3], BOX, splits=[0, 4, 9], setup=setup), want, 9)
+    assert_same(engine_run(pos, None, EDGES, [0, 1, 3], BOX, setup=setup), want, 9)
+
+
 @pytest.mark.parametrize("n", [65, T + 1])
 def test_self_exclusion_is_the_self_part(n):
     """Two sets of the same rows count the pair i == j as well: at lag 0 that is n * n_origins in the bin that
