@@ -761,6 +761,12 @@ int mdx_dip_set_unwrap(mdx_dip_t h, const double *dims, const double *start);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the scratch of a launch).
  * The rows do not depend on it; tests use it to make a few frames cross several slabs. */
 int mdx_dip_set_slab_frames(mdx_dip_t h, int64_t frames);
+/* The plan of the next call, as mdx_rdf_plan reports the launch: *slab_frames = the frames a kernel launch takes at
+ * most (the slab asked for, or the default: 32768, or fewer where 256 MiB of history or scratch hold fewer frames;
+ * a lag engine limits it by the ring once the ring is sized), *ring_frames = the frames the ring of a lag engine
+ * holds (max(lags) + slab, decided before the first frame of a pass; 0 for an engine without a ring).  Computed by
+ * the functions the accumulate path calls.  Needs no device and reads no frame. */
+int mdx_dip_plan(mdx_dip_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring. */
 int mdx_dip_accumulate(mdx_dip_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3], read where they lie; index: host int32[n_index] rows of a
@@ -804,6 +810,8 @@ int mdx_vh_set_unwrap(mdx_vh_t h, const double *dims);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history), as
  * mdx_dip_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
 int mdx_vh_set_slab_frames(mdx_vh_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_vh_plan(mdx_vh_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring. */
 int mdx_vh_accumulate(mdx_vh_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
@@ -847,6 +855,8 @@ int mdx_vhd_reset(mdx_vhd_t h);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history).  The results do
  * not depend on it.  Only before the first frame. */
 int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_vhd_plan(mdx_vhd_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring; n = n1 + n2, or n1 with same. */
 int mdx_vhd_accumulate(mdx_vhd_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
@@ -890,6 +900,8 @@ int mdx_prs_reset(mdx_prs_t h);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history).  The results do
  * not depend on it.  Only before the first frame. */
 int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_prs_plan(mdx_prs_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring; n = n1 + n2, or n1 with same. */
 int mdx_prs_accumulate(mdx_prs_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
@@ -938,6 +950,8 @@ int mdx_clu_reset(mdx_clu_t h);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the lists in HBM).  The results
  * do not depend on it.  Only before the first frame. */
 int mdx_clu_set_slab_frames(mdx_clu_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_clu_plan(mdx_clu_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring. */
 int mdx_clu_accumulate(mdx_clu_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
@@ -997,6 +1011,8 @@ int mdx_ang_reset(mdx_ang_t h);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the lists in HBM).  The results
  * do not depend on it.  Only before the first frame. */
 int mdx_ang_set_slab_frames(mdx_ang_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_ang_plan(mdx_ang_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring; n = n_centers + the ligands, or n_centers with same. */
 int mdx_ang_accumulate(mdx_ang_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
@@ -1046,6 +1062,8 @@ int mdx_ori_set_box(mdx_ori_t h, const double *dims);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history), as
  * mdx_vh_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
 int mdx_ori_set_slab_frames(mdx_ori_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_ori_plan(mdx_ori_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring; n = n_rows. */
 int mdx_ori_accumulate(mdx_ori_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in the order the
@@ -1102,6 +1120,8 @@ int mdx_boo_reset(mdx_boo_t h);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the slab's buffers in HBM), as
  * mdx_ang_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
 int mdx_boo_set_slab_frames(mdx_boo_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_boo_plan(mdx_boo_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring; n = the rows of a frame. */
 int mdx_boo_accumulate(mdx_boo_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
@@ -1151,6 +1171,8 @@ int mdx_chi4_set_unwrap(mdx_chi4_t h, const double *dims);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history and the scratch), as
  * mdx_vh_set_slab_frames.  The results do not depend on it.  Only before the first frame. */
 int mdx_chi4_set_slab_frames(mdx_chi4_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_chi4_plan(mdx_chi4_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Points of the concatenated groups that one block of the counting kernel walks: a multiple of 64; 0 restores the
  * default.  For tests and measurement: the results do not depend on it.  Only before the first frame. */
 int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points);
@@ -1209,6 +1231,8 @@ int mdx_hb_reset(mdx_hb_t h);
 /* Frames per kernel launch, at most (1 ... 32768; 0 restores the default, which bounds the history).  The results do
  * not depend on it.  Only before the first frame. */
 int mdx_hb_set_slab_frames(mdx_hb_t h, int64_t frames);
+/* As mdx_dip_plan. */
+int mdx_hb_plan(mdx_hb_t h, int64_t *slab_frames, int64_t *ring_frames);
 /* Host float32 [n_frames][n][3] through the pinned ring; n = n_rows. */
 int mdx_hb_accumulate(mdx_hb_t h, const float *pos, int64_t n, int64_t n_frames);
 /* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming

@@ -676,6 +676,14 @@ class _SlabbedFrameEngine(_FrameEngine):
         engine but the dipole one takes it only before the first frame."""
         check(self._fn("set_slab_frames")(self.handle, int(frames)))
 
+    def plan(self):
+        """``mdx_X_plan``: where the next call is cut.  ``slab_frames``: frames per kernel launch at most;
+        ``ring_frames``: frames in the ring of a lag engine (``max(lags) + slab``, decided before the first frame of a
+        pass), 0 for an engine without one.  Needs no device and reads no frame."""
+        slab, ring = c_int64(), c_int64()
+        check(self._fn("plan")(self.handle, byref(slab), byref(ring)))
+        return {"slab_frames": slab.value, "ring_frames": ring.value}
+
 
 class ProfileEngine(_FrameEngine):
     """``mdx_prof_*``: per-axis, per-group position histograms with ``numpy.histogram``'s counts."""

@@ -222,6 +222,7 @@ _SIGNATURES = {
     "mdx_dip_reset": (c_int, [_vp]),
     "mdx_dip_set_unwrap": (c_int, [_vp, _vp, _vp]),
     "mdx_dip_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_dip_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_dip_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_dip_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_dip_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -235,6 +236,7 @@ _SIGNATURES = {
     "mdx_vh_reset": (c_int, [_vp]),
     "mdx_vh_set_unwrap": (c_int, [_vp, _vp]),
     "mdx_vh_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_vh_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_vh_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_vh_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_vh_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -249,6 +251,7 @@ _SIGNATURES = {
     "mdx_vhd_destroy": (c_int, [_vp]),
     "mdx_vhd_reset": (c_int, [_vp]),
     "mdx_vhd_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_vhd_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_vhd_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_vhd_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_vhd_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -262,6 +265,7 @@ _SIGNATURES = {
     "mdx_prs_destroy": (c_int, [_vp]),
     "mdx_prs_reset": (c_int, [_vp]),
     "mdx_prs_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_prs_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_prs_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_prs_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_prs_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -276,6 +280,7 @@ _SIGNATURES = {
     "mdx_clu_destroy": (c_int, [_vp]),
     "mdx_clu_reset": (c_int, [_vp]),
     "mdx_clu_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_clu_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_clu_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_clu_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_clu_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -292,6 +297,7 @@ _SIGNATURES = {
     "mdx_ang_destroy": (c_int, [_vp]),
     "mdx_ang_reset": (c_int, [_vp]),
     "mdx_ang_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_ang_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_ang_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_ang_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_ang_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -306,6 +312,7 @@ _SIGNATURES = {
     "mdx_ori_reset": (c_int, [_vp]),
     "mdx_ori_set_box": (c_int, [_vp, _vp]),
     "mdx_ori_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_ori_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_ori_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_ori_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_ori_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -322,6 +329,7 @@ _SIGNATURES = {
     "mdx_boo_destroy": (c_int, [_vp]),
     "mdx_boo_reset": (c_int, [_vp]),
     "mdx_boo_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_boo_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_boo_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_boo_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_boo_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
@@ -338,6 +346,7 @@ _SIGNATURES = {
     "mdx_chi4_reset": (c_int, [_vp]),
     "mdx_chi4_set_unwrap": (c_int, [_vp, _vp]),
     "mdx_chi4_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_chi4_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_chi4_set_segment_points": (c_int, [_vp, c_int64]),
     "mdx_chi4_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_chi4_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
@@ -353,6 +362,7 @@ _SIGNATURES = {
     "mdx_hb_destroy": (c_int, [_vp]),
     "mdx_hb_reset": (c_int, [_vp]),
     "mdx_hb_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_hb_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_hb_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "mdx_hb_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
     "mdx_hb_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),

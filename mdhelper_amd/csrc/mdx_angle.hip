@@ -238,6 +238,14 @@ static int ang_prepare(mdx_ang *h, int64_t)
     return ang_ensure_slab(h);
 }
 
+int mdx_ang_plan(mdx_ang_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
+    *slab_frames = ang_slab(h);
+    *ring_frames = 0;           // no frame outlives its slab
+    return MDX_OK;
+}
+
 int mdx_ang_accumulate_device(mdx_ang_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {

@@ -348,6 +348,14 @@ static int boo_prepare(mdx_boo *h, int64_t)
     return boo_ensure_slab(h);
 }
 
+int mdx_boo_plan(mdx_boo_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
+    *slab_frames = boo_slab(h);
+    *ring_frames = 0;           // no frame outlives its slab
+    return MDX_OK;
+}
+
 int mdx_boo_accumulate_device(mdx_boo_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {

@@ -260,6 +260,12 @@ int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points)
     return MDX_OK;
 }
 
+int mdx_chi4_plan(mdx_chi4_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    return h->ring.plan(h->frames_seen, h->lags.max_lag, chi4_slab(h), slab_frames, ring_frames);
+}
+
 int mdx_chi4_accumulate_device(mdx_chi4_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                                const int32_t *index, int64_t n_index)
 {

@@ -285,6 +285,14 @@ static int clu_prepare(mdx_clu *h, int64_t)
     return clu_ensure_slab(h);
 }
 
+int mdx_clu_plan(mdx_clu_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
+    *slab_frames = clu_slab(h);
+    *ring_frames = 0;           // no frame outlives its slab
+    return MDX_OK;
+}
+
 int mdx_clu_accumulate_device(mdx_clu_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {

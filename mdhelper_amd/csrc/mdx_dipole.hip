@@ -38,6 +38,14 @@ struct mdx_dip : FrameEngine {
     DeviceBuffer d_tiles, d_tile_offsets, d_charges, d_rows, d_partial, d_prev, d_image;
 };
 
+// frames per launch: the one asked for, or what the scratch holds of frames of 24 B per tile
+static int64_t dip_slab(const mdx_dip *h)
+{
+    if (h->slab_frames > 0)
+        return h->slab_frames;
+    return std::min(DIP_SLAB_FRAMES, std::max<int64_t>(1, DIP_SCRATCH_BYTES / (24 * h->n_tiles)));
+}
+
 static int dip_grow_rows(mdx_dip *h, int64_t more)
 {
     return grow_rows(h->d_rows, h->stream, int64_t(24) * h->n_groups, h->frames_seen, more, &h->row_capacity);
@@ -71,9 +79,7 @@ static int dip_accumulate_rows(mdx_dip *h, const float *d_pos, int64_t src_rows,
         MDX_HIP(hipMemcpyAsync(h->d_prev.ptr, h->start.data(), size_t(24) * n, hipMemcpyHostToDevice, h->stream));
         MDX_HIP(hipMemsetAsync(h->d_image.ptr, 0, size_t(12) * n, h->stream));
     }
-    const int64_t slab = h->slab_frames > 0
-                             ? h->slab_frames
-                             : std::min(DIP_SLAB_FRAMES, std::max<int64_t>(1, DIP_SCRATCH_BYTES / (24 * h->n_tiles)));
+    const int64_t slab = dip_slab(h);
     hipEvent_t ev = h->timer.begin();
     for (int64_t f0 = 0; f0 < n_frames; f0 += slab) {
         const int64_t nf = std::min(slab, n_frames - f0);
@@ -202,6 +208,14 @@ static int dip_prepare(mdx_dip *h, int64_t n_frames)
 {
     MDX_TRY(set_device(h->dev));
     return dip_grow_rows(h, n_frames);
+}
+
+int mdx_dip_plan(mdx_dip_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
+    *slab_frames = dip_slab(h);
+    *ring_frames = 0;           // no frame outlives its slab
+    return MDX_OK;
 }
 
 int mdx_dip_accumulate_device(mdx_dip_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,

@@ -81,14 +81,34 @@ struct LagRing {
     {
         if (frames_seen > 0)
             return MDX_OK;
-        MDX_REQUIRE(lag + slab < (int64_t(1) << 40) / frame_bytes, too_large, (long long)(lag + slab), args...);
-        cap = lag + slab;
+        const int64_t frames = planned_cap(frames_seen, lag, slab);
+        MDX_REQUIRE(frames < (int64_t(1) << 40) / frame_bytes, too_large, (long long)frames, args...);
+        cap = frames;
         max_lag = lag;
         return MDX_OK;
     }
 
+    // the frames the ring holds once ensure has run with these arguments: the ring a pass already has, or before the
+    // first frame of a pass a new one of lag + slab frames
+    int64_t planned_cap(int64_t frames_seen, int64_t lag, int64_t slab) const
+    {
+        return frames_seen > 0 ? cap : lag + slab;
+    }
+
     // frames per slab: no more than the ring was sized for
-    int64_t slab(int64_t asked) const { return std::min(asked, cap - max_lag); }
+    int64_t slab(int64_t asked) const { return slab_within(asked, cap, max_lag); }
+
+    static int64_t slab_within(int64_t asked, int64_t frames, int64_t lag) { return std::min(asked, frames - lag); }
+
+    // The body of X_plan of a ring engine, asked = X_slab(h): what the next prepare and the loop after it use.  Needs
+    // no device and sizes nothing.
+    int plan(int64_t frames_seen, int64_t lag, int64_t asked, int64_t *slab_frames, int64_t *ring_frames) const
+    {
+        MDX_REQUIRE(slab_frames && ring_frames, "NULL argument");
+        *ring_frames = planned_cap(frames_seen, lag, asked);
+        *slab_frames = slab_within(asked, *ring_frames, lag);
+        return MDX_OK;
+    }
 
     // Empties the slots of frames [f_lo, f_lo + nf) of a ring of slot_bytes per frame: one range, or two where the
     // ring wraps.

@@ -238,6 +238,12 @@ int mdx_ori_set_slab_frames(mdx_ori_t h, int64_t frames)
     return h->set_slab_frames(frames, ORI_SLAB_MAX, "mdx_ori_set_slab_frames");
 }
 
+int mdx_ori_plan(mdx_ori_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    return h->ring.plan(h->frames_seen, h->lags.max_lag, ori_slab(h), slab_frames, ring_frames);
+}
+
 int mdx_ori_accumulate_device(mdx_ori_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {

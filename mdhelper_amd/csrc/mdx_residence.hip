@@ -191,6 +191,12 @@ int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames)
     return h->set_slab_frames(frames, PRS_SLAB_MAX, "mdx_prs_set_slab_frames");
 }
 
+int mdx_prs_plan(mdx_prs_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    return h->ring.plan(h->frames_seen, h->lags.max_lag, prs_slab(h), slab_frames, ring_frames);
+}
+
 int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {

@@ -182,6 +182,12 @@ int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames)
     return h->set_slab_frames(frames, VHD_SLAB_MAX, "mdx_vhd_set_slab_frames");
 }
 
+int mdx_vhd_plan(mdx_vhd_t h, int64_t *slab_frames, int64_t *ring_frames)
+{
+    MDX_REQUIRE(h, "NULL handle");
+    return h->ring.plan(h->frames_seen, h->lags.max_lag, vhd_slab(h), slab_frames, ring_frames);
+}
+
 int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                               const int32_t *index, int64_t n_index)
 {
