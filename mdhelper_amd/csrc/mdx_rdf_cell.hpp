@@ -708,8 +708,9 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
 // image and keep the unconditional tail (SKIP = false), as does MODE 1.
 //
 // The tail of a SKIP step (v_sqrt_f32, v_fma_f32, the convert and what follows) lives inside the asm
-// block, behind s_cbranch_execz; r2 is still formed in C++, so the compiler goes on hoisting the next
-// step's subtractions and fmas over this step's block.  Wait states inside the block are placed by
+// block, behind s_cbranch_execz; r2 is formed in C++ in front of it.  The blocks are volatile and every
+// step's arithmetic feeds its own block, so in the listing the steps stand strictly one after the other:
+// nothing of the next step is moved over this step's block.  Wait states inside the block are placed by
 // hand: one (s_nop 0) between v_sqrt_f32 and the v_fma_f32 that reads its result (transcendental
 // result read by a non-transcendental VALU instruction); none between the v_cmpx that writes EXEC and
 // s_cbranch_execz — the required-wait-state table of the CDNA ISA manuals lists EXEC written by a VALU
@@ -729,12 +730,17 @@ __device__ inline void cell_exact_ctx(const CellHot &c, const CellArgs &a, PairC
 // >= tq), v_mad_u32_u16 with op_sel multiplies the HIGH half, the bin, by the byte stride of a bin (4 R) and adds
 // the lane's replica base — five VALU instructions where v_fract_f32, a float compare, the convert and
 // v_lshl_add_u32 made six.  Both halves' selection is checked on the device by scripts/issue_bench.hip.
+// The address is formed for every candidate lane, in FRONT of the s_andn2_b64 that narrows EXEC to the sure ones
+// (it reads the convert's result, not the mask; an undecided lane's address is never used).  Measured, not
+// derived: with the v_mad_u32_u16 between the v_cmp that writes the mask and the scalar instruction that reads it,
+// the bench step takes 1.4 % less than with the two the other way round, in every build it was tried in; the
+// microbenchmark rows of scripts/issue_bench.hip --tail show no such gain (NOTES.md, round 19).
 #define MDX_CELL_SKIP_TAIL                                                                          \
     "s_cbranch_execz .Lmdx_cell_skip%=\n\t"                                                          \
     "v_sqrt_f32_e32 %[tmp], %[r2]\n\ts_nop 0\n\tv_fma_f32 %[tmp], %[tmp], %[iw], %[p0]\n\t"          \
     "v_cvt_flr_i32_f32_e32 %[tmp], %[tmp]\n\t"                                                      \
     "v_cmp_le_u16_e64 %[mt], %[tq], %[tmp]\n\t"                                                     \
-    "s_andn2_b64 exec, exec, %[mt]\n\tv_mad_u32_u16 %[tmp], %[tmp], %[st], %[hb] op_sel:[1,0,0,0]\n\t" \
+    "v_mad_u32_u16 %[tmp], %[tmp], %[st], %[hb] op_sel:[1,0,0,0]\n\ts_andn2_b64 exec, exec, %[mt]\n\t" \
     "ds_add_u32 %[tmp], %[w]\n"                                                                     \
     ".Lmdx_cell_skip%=:\n\ts_mov_b64 exec, -1"
 // ROT: a rotated step of a diagonal tile (CELL_DIAG_ROT_STEPS): lane l met slab row (l + j_row + j_off) & 63, and

@@ -17,6 +17,22 @@
 //   * the fixed-point skip step fed from an LDS slab (round 18, `--rot`): a broadcast row as in the row loops against
 //     the rotated row of a diagonal tile's steps (lane l reads row (l + k) & 63, by index and by a running byte
 //     offset) — after a check that every lane got that row.
+//   * the same step fed from registers (round 19, `--rotreg`): the wave's own row moved one lane per step by
+//     v_mov_b32_dpp with a whole-wave rotate — three registers, and four with the tag — after a check that after k
+//     rotations every lane of every wave holds row (lane - k) & 63 (wave_ror:1) or (lane + k) & 63 (wave_rol:1) in
+//     every register; and the rotated step as a LOOP, the way the pair kernel runs it: one step per turn, two steps
+//     per turn with both reads in front, and the register forms.  Outcome (ns per step): three registers 24.3 - 24.6
+//     against 24.6 - 25.0 of the LDS read, inside its scatter in one pass of three; four registers 26.3 - 26.6,
+//     above it: not built.  Two steps per turn 23.6 - 23.8 against 25.2 - 25.4 of one per turn: below in every
+//     pass — and in the pair kernel 0.3 ms per step SLOWER than the loop it has (NOTES.md, round 19): not built.
+//   * orders of the skipping step's tail (round 19, `--tail`): v_sqrt_f32 in front of the v_cmpx (no s_nop),
+//     v_mad_u32_u16 in front of the s_andn2_b64 of EXEC, and both — up to the address, as the rows of round 17 are,
+//     and with the ds_add_u32 behind it (the whole tail; there also with the v_sqrt_f32 between the v_cmpx and the
+//     branch).  Outcome at 5 of 32 steps empty: the moved root is above its yardstick in every form; the moved
+//     v_mad_u32_u16 is within the yardstick's scatter up to the address and 0.2 - 0.4 ns ABOVE it in the whole tail
+//     — and in the pair kernel 2.7 ms per step (1.4 %) FASTER, in five builds and five series.  These rows do not
+//     predict the pair kernel; why is not known (one difference: a row's steps chain through a0 .. a2, the
+//     kernel's steps are independent of each other).
 // hipcc -O2 --offload-arch=gfx950 scripts/issue_bench.hip -o /tmp/issue_bench
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -80,6 +96,26 @@ __global__ void rot_check(unsigned *rows, int way)
         rows[(wave * 33u + k) * 64u + lane] = unsigned(q.w);
     }
 }
+// The rows the register form holds (round 19): every lane starts with its own row in four registers and moves them
+// one lane per step with the whole-wave rotate CTRL (0x13C wave_ror:1, 0x134 wave_rol:1).  Register c of row r of
+// wave v holds 4 (64 v + r) + c.
+#define MDX_WAVE_ROT(x, CTRL) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, x), __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false))
+template <int CTRL>
+__global__ void rotreg_check(unsigned *rows)
+{
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    float4 q = make_float4(float(4u * threadIdx.x), float(4u * threadIdx.x + 1u), float(4u * threadIdx.x + 2u),
+                           float(4u * threadIdx.x + 3u));
+#pragma unroll 1
+    for (unsigned k = 0; k < 33u; ++k) {
+        reinterpret_cast<uint4 *>(rows)[(wave * 33u + k) * 64u + lane] =
+            make_uint4(unsigned(q.x), unsigned(q.y), unsigned(q.z), unsigned(q.w));
+        q.x = MDX_WAVE_ROT(q.x, CTRL);
+        q.y = MDX_WAVE_ROT(q.y, CTRL);
+        q.z = MDX_WAVE_ROT(q.z, CTRL);
+        q.w = MDX_WAVE_ROT(q.w, CTRL);
+    }
+}
 // MODE 9: the skip step of MODE 8 with EMPTY reused as the extra scalar work per step: 0, 1, 2, 4 = that many
 // s_add_i32 (8 as well, for a longer lever); 100 = s_cmp_eq_u32 (SCC = 1) + s_cbranch_scc0 that is never taken;
 // 201, 202 = one, two extra VALU instructions (v_max_f32 of a register with itself), the other yardstick.
@@ -93,8 +129,8 @@ __global__ void kern(float *out, long long *clk, int iters)
     v2f pb = {b, b}, pc = {c, c};
     unsigned s0 = blockIdx.x, s1 = 1, s2 = 2, s3 = 3;
     // MODEs 16 - 18: a slab of 64 rows per wave of a 256-thread block (run7)
-    __shared__ float4 rot_slab[(MODE >= 16 && MODE <= 18) ? 256 : 1];
-    if (MODE >= 16 && MODE <= 18) {
+    __shared__ float4 rot_slab[((MODE >= 16 && MODE <= 18) || (MODE >= 25 && MODE <= 32)) ? 256 : 1];
+    if ((MODE >= 16 && MODE <= 18) || (MODE >= 25 && MODE <= 32)) {
         if (threadIdx.x < 256)
             rot_slab[threadIdx.x] = make_float4(1.f + float(threadIdx.x & 63u), 2.f, 3.f, float(threadIdx.x & 63u));
         __syncthreads();
@@ -206,6 +242,136 @@ __global__ void kern(float *out, long long *clk, int iters)
                              : "v"(b), "v"(c), "s"(pass), "s"(s1), "s"(s2), "v"(q.x), "v"(q.y), "v"(q.z)
                              : "vcc");
             }
+        } else if (MODE == 19 || MODE == 20) {
+            // The step of MODEs 16 - 18 fed from registers (round 19): the lane's own row, moved one lane per step by
+            // three v_mov_b32_dpp wave_ror:1 (19), four with the tag (20).  No address, no LDS read.
+            const float pass = 3e38f;
+            float4 q = make_float4(1.f + float(threadIdx.x & 63u), 2.f, 3.f, float(threadIdx.x & 63u));
+            asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+                asm volatile("v_sub_f32 %0, %13, %8\n v_sub_f32 %1, %14, %8\n v_sub_f32 %2, %15, %8\n v_mul_f32 %3, %0, %0\n"
+                             "v_fma_f32 %3, %1, %1, %3\n v_fma_f32 %3, %2, %2, %3\n v_cmpx_gt_f32_e64 vcc, %10, %3\n"
+                             "s_cbranch_execz .Lbench19_skip%=\n v_sqrt_f32 %4, %3\n s_nop 0\n v_fma_f32 %4, %4, %8, %9\n"
+                             "v_cvt_flr_i32_f32 %5, %4\n v_cmp_le_u16_e64 vcc, %11, %5\n v_mad_u32_u16 %7, %5, %12, %6 op_sel:[1,0,0,0]\n"
+                             ".Lbench19_skip%=:\n s_mov_b64 exec, -1\n"
+                             : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)
+                             : "v"(b), "v"(c), "s"(pass), "s"(s1), "s"(s2), "v"(q.x), "v"(q.y), "v"(q.z)
+                             : "vcc");
+                q.x = MDX_WAVE_ROT(q.x, 0x13C);
+                q.y = MDX_WAVE_ROT(q.y, 0x13C);
+                q.z = MDX_WAVE_ROT(q.z, 0x13C);
+                if (MODE == 20) {
+                    q.w = MDX_WAVE_ROT(q.w, 0x13C);
+                    asm volatile("" ::"v"(q.w));
+                }
+            }
+            a7 += q.x + q.w;
+        } else if (MODE >= 25 && MODE <= 28) {
+            // The rotated step as a LOOP, which is how the pair kernel runs it (MODEs 16 - 20 unroll 32 steps, and the
+            // compiler issues their reads well ahead).  25: one step per turn — index, read, wait, step — the
+            // kernel's loop of round 18.  26: two steps per turn, both reads issued before the first wait, the rows
+            // through the running byte offset of MODE 18.  27, 28: one step per turn on registers, four and three
+            // v_mov_b32_dpp wave_ror:1.
+            const float pass = 3e38f;
+            const unsigned lane = threadIdx.x & 63u;
+            float4 *sw = rot_slab + (threadIdx.x >> 6) * 64;
+#define MDX_B25_STEP(Q)                                                                                              \
+    asm volatile("v_sub_f32 %0, %13, %8\n v_sub_f32 %1, %14, %8\n v_sub_f32 %2, %15, %8\n v_mul_f32 %3, %0, %0\n"        \
+                 "v_fma_f32 %3, %1, %1, %3\n v_fma_f32 %3, %2, %2, %3\n v_cmpx_gt_f32_e64 vcc, %10, %3\n"                 \
+                 "s_cbranch_execz .Lbench25_skip%=\n v_sqrt_f32 %4, %3\n s_nop 0\n v_fma_f32 %4, %4, %8, %9\n"            \
+                 "v_cvt_flr_i32_f32 %5, %4\n v_cmp_le_u16_e64 vcc, %11, %5\n v_mad_u32_u16 %7, %5, %12, %6 op_sel:[1,0,0,0]\n" \
+                 ".Lbench25_skip%=:\n s_mov_b64 exec, -1\n"                                                            \
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)                       \
+                 : "v"(b), "v"(c), "s"(pass), "s"(s1), "s"(s2), "v"(Q.x), "v"(Q.y), "v"(Q.z)                            \
+                 : "vcc")
+            if (MODE == 25) {
+                unsigned kbase = (unsigned(i) * 32u) & 63u;
+                asm volatile("" : "+s"(kbase));
+#pragma unroll 1
+                for (unsigned k = 0; k < 32u; ++k) {
+                    const float4 q = sw[(lane + kbase + k) & 63u];
+                    asm volatile("" ::"v"(q.w));   // whole 16-byte read
+                    MDX_B25_STEP(q);
+                }
+            } else if (MODE == 26) {
+                unsigned off = (lane * 16u + unsigned(i) * 512u) & 1023u;
+#pragma unroll 1
+                for (unsigned t = 0; t < 16u; ++t) {
+                    const float4 q0 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sw) + off);
+                    off = (off + 16u) & 1023u;
+                    const float4 q1 = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(sw) + off);
+                    off = (off + 16u) & 1023u;
+                    asm volatile("" ::"v"(q0.w), "v"(q1.w));   // both reads in front of the first step
+                    MDX_B25_STEP(q0);
+                    MDX_B25_STEP(q1);
+                }
+            } else {
+                float4 q = sw[lane];
+                asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z), "+v"(q.w));
+#pragma unroll 1
+                for (unsigned k = 0; k < 32u; ++k) {
+                    MDX_B25_STEP(q);
+                    q.x = MDX_WAVE_ROT(q.x, 0x13C);
+                    q.y = MDX_WAVE_ROT(q.y, 0x13C);
+                    q.z = MDX_WAVE_ROT(q.z, 0x13C);
+                    if (MODE == 27) {
+                        q.w = MDX_WAVE_ROT(q.w, 0x13C);
+                        asm volatile("" ::"v"(q.w));
+                    }
+                }
+                a7 += q.x + q.w;
+            }
+#undef MDX_B25_STEP
+        } else if ((MODE >= 21 && MODE <= 24) || (MODE >= 29 && MODE <= 32)) {
+            // Orders of the tail of the fixed-point skipping step of MODE 10 (round 19), with the s_andn2_b64 of EXEC
+            // that the pair kernel's tail has between the undecided test and the address.  21 - 24 end at the address,
+            // as MODE 10 does; 29 - 32 are the WHOLE tail: the ds_add_u32 that reads the address follows, every lane
+            // adding to a word of its own in the wave's slab (the stride operand is zero, the base the lane's word:
+            // no conflicts, nothing out of bounds).
+            //   22, 29: the kernel's order of round 17 — s_andn2_b64, v_mad_u32_u16 — the yardsticks.
+            //   23, 30: (b) v_mad_u32_u16 in front of the s_andn2_b64.
+            //   21: (a) v_sqrt_f32 in front of the v_cmpx, no s_nop (the compare and the branch stand between the root
+            //       and the v_fma_f32 that reads it).  24: (c) = (a) and (b).
+            //   31: v_sqrt_f32 between the v_cmpx and s_cbranch_execz, no s_nop (the root of the candidate lanes
+            //       alone).  32: 31 and (b).
+            const float pass = 3e38f, fail = -1.f;
+            constexpr bool WHOLE = MODE >= 29;
+            unsigned word = (unsigned)(size_t)(__attribute__((address_space(3))) float4 *)rot_slab + threadIdx.x * 4u;
+            unsigned stride = WHOLE ? 0u : s2, one = 1u;
+            asm volatile("" : "+v"(word), "+s"(stride), "+v"(one));
+// (ROOT0, ROOTX, ROOT1: the square root in front of the v_cmpx, between it and the branch, or behind the branch)
+#define MDX_B21_STEP(ROOT0, ROOTX, ROOT1, TAIL)                                                                       \
+    asm volatile("v_sub_f32 %0, %0, %8\n v_sub_f32 %1, %1, %8\n v_sub_f32 %2, %2, %8\n v_mul_f32 %3, %0, %0\n"           \
+                 "v_fma_f32 %3, %1, %1, %3\n v_fma_f32 %3, %2, %2, %3\n" ROOT0 "v_cmpx_gt_f32_e64 vcc, %10, %3\n" ROOTX  \
+                 "s_cbranch_execz .Lbench21_skip%=\n" ROOT1 "v_fma_f32 %4, %4, %8, %9\n"                                \
+                 "v_cvt_flr_i32_f32 %5, %4\n v_cmp_le_u16_e64 vcc, %11, %5\n" TAIL                                     \
+                 ".Lbench21_skip%=:\n s_mov_b64 exec, -1\n"                                                            \
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)                       \
+                 : "v"(b), "v"(c), "s"(((EMPTY >> k) & 1u) ? fail : pass), "s"(s1), "s"(stride), "v"(word), "v"(one)    \
+                 : "vcc", "scc", "memory")   /* (s_andn2_b64 writes SCC) */
+#define MDX_B21_ROOT "v_sqrt_f32 %4, %3\n"
+#define MDX_B21_ROOT_NOP "v_sqrt_f32 %4, %3\n s_nop 0\n"
+#define MDX_B21_NARROW_FIRST(BASE) "s_andn2_b64 exec, exec, vcc\n v_mad_u32_u16 %7, %5, %12, " BASE " op_sel:[1,0,0,0]\n"
+#define MDX_B21_MAD_FIRST(BASE) "v_mad_u32_u16 %7, %5, %12, " BASE " op_sel:[1,0,0,0]\n s_andn2_b64 exec, exec, vcc\n"
+#define MDX_B21_ADD "ds_add_u32 %7, %14\n"
+#pragma unroll
+            for (int k = 0; k < 32; ++k) {
+                if (MODE == 22) MDX_B21_STEP("", "", MDX_B21_ROOT_NOP, MDX_B21_NARROW_FIRST("%6"));
+                else if (MODE == 21) MDX_B21_STEP(MDX_B21_ROOT, "", "", MDX_B21_NARROW_FIRST("%6"));
+                else if (MODE == 23) MDX_B21_STEP("", "", MDX_B21_ROOT_NOP, MDX_B21_MAD_FIRST("%6"));
+                else if (MODE == 24) MDX_B21_STEP(MDX_B21_ROOT, "", "", MDX_B21_MAD_FIRST("%6"));
+                else if (MODE == 29) MDX_B21_STEP("", "", MDX_B21_ROOT_NOP, MDX_B21_NARROW_FIRST("%13") MDX_B21_ADD);
+                else if (MODE == 30) MDX_B21_STEP("", "", MDX_B21_ROOT_NOP, MDX_B21_MAD_FIRST("%13") MDX_B21_ADD);
+                else if (MODE == 31) MDX_B21_STEP("", MDX_B21_ROOT, "", MDX_B21_NARROW_FIRST("%13") MDX_B21_ADD);
+                else MDX_B21_STEP("", MDX_B21_ROOT, "", MDX_B21_MAD_FIRST("%13") MDX_B21_ADD);
+            }
+#undef MDX_B21_STEP
+#undef MDX_B21_ROOT
+#undef MDX_B21_ROOT_NOP
+#undef MDX_B21_NARROW_FIRST
+#undef MDX_B21_MAD_FIRST
+#undef MDX_B21_ADD
         } else if (MODE == 9) {
             // (operands %8 and %9 are b and c in MODE 8; here the four scalar counters sit at %8..%11, so the
             // strings below are written with their own numbering: b = %12, c = %13, pass = %14)
@@ -393,8 +559,81 @@ static bool check_rot()
     hipFree(rows);
     return ok;
 }
+// After k one-lane rotations (k = 0 .. 32) every lane of every wave holds, in all four registers, row (lane - k) & 63
+// (sign -1) or (lane + k) & 63 (sign +1) of its own wave.  Returns the sign found, 0 if a lane is wrong.
+template <int CTRL> static int check_rotreg(const char *name)
+{
+    static unsigned h[4 * 33 * 64 * 4];
+    unsigned *rows;
+    hipMalloc(&rows, sizeof h);
+    hipMemset(rows, 0xff, sizeof h);
+    rotreg_check<CTRL><<<1, 256>>>(rows);
+    hipMemcpy(h, rows, sizeof h, hipMemcpyDeviceToHost);
+    hipFree(rows);
+    const unsigned first = h[(0 * 33 + 1) * 64 * 4 + 4 * 1] / 4u;   // wave 0, k = 1, lane 1, register 0
+    const int sign = first == 0u ? -1 : first == 2u ? 1 : 0;
+    int wrong = 0;
+    for (unsigned wave = 0; wave < 4 && sign; ++wave)
+        for (unsigned k = 0; k < 33; ++k)
+            for (unsigned lane = 0; lane < 64; ++lane)
+                for (unsigned c = 0; c < 4; ++c) {
+                    const unsigned got = h[((wave * 33 + k) * 64 + lane) * 4 + c];
+                    const unsigned want = 4u * (64u * wave + ((lane + unsigned(sign * int(k))) & 63u)) + c;
+                    if (got != want && wrong++ < 8)
+                        printf("  wave %u step %u lane %u register %u holds %u, not %u\n", wave, k, lane, c, got, want);
+                }
+    if (!sign)
+        printf("register rotation check, %s: lane 1 holds row %u after one rotation — neither neighbour WRONG\n", name, first);
+    else
+        printf("register rotation check, %s: after k rotations lane l holds row (l %c k) & 63; %d of %d values wrong %s\n",
+               name, sign > 0 ? '+' : '-', wrong, 4 * 33 * 64 * 4, wrong ? "WRONG" : "ok");
+    return wrong ? 0 : sign;
+}
 int main(int argc, char **argv)
 {
+    if (argc > 1 && !strcmp(argv[1], "--rotreg")) {   // the round-19 register rows
+        const int ror = check_rotreg<0x13C>("wave_ror:1"), rol = check_rotreg<0x134>("wave_rol:1");
+        if (!ror || !rol) return 1;   // not timed
+        const int passes = argc > 2 ? atoi(argv[2]) : 3;
+        for (int pass = 0; pass < passes; ++pass) {
+            run7<10, 0u>("skip step fixed-point", 12, 2);
+            run7<16, 0u>("fixed-point, broadcast row", 13, 2);
+            run7<17, 0u>("fixed-point, rotated row", 15, 2);
+            run7<18, 0u>("fixed-point, rotated, offset", 15, 2);
+            run7<19, 0u>("fixed-point, 3 registers dpp", 15, 2);
+            run7<20, 0u>("fixed-point, 4 registers dpp", 16, 2);
+            run7<25, 0u>("loop, rotated row, 1 per turn", 15, 5);
+            run7<26, 0u>("loop, rotated rows, 2 per turn", 15, 4);
+            run7<28, 0u>("loop, 3 registers dpp", 15, 5);
+            run7<27, 0u>("loop, 4 registers dpp", 16, 5);
+        }
+        return 0;
+    }
+    if (argc > 1 && !strcmp(argv[1], "--tail")) {   // the round-19 tail orders
+        if (!check_fixed()) return 1;
+        const int passes = argc > 2 ? atoi(argv[2]) : 3;
+        for (int pass = 0; pass < passes; ++pass) {
+            run7<10, 0u>("skip step fixed-point", 12, 2);
+            run7<22, 0u>("fixed-point + s_andn2 exec", 12, 3);
+            run7<21, 0u>("(a) sqrt before cmpx", 12, 2);
+            run7<23, 0u>("(b) mad before s_andn2", 12, 3);
+            run7<24, 0u>("(c) both", 12, 2);
+            run7<10, 0x04082082u>("skip step fixed-point, 5/32", 12, 2);
+            run7<22, 0x04082082u>("fixed-point + s_andn2, 5/32", 12, 3);
+            run7<21, 0x04082082u>("(a) sqrt before cmpx, 5/32", 12, 2);
+            run7<23, 0x04082082u>("(b) mad before s_andn2, 5/32", 12, 3);
+            run7<24, 0x04082082u>("(c) both, 5/32", 12, 2);
+            run7<29, 0u>("whole tail, kernel's order", 12, 3);
+            run7<30, 0u>("whole tail, (b) mad first", 12, 3);
+            run7<31, 0u>("whole tail, sqrt behind cmpx", 12, 2);
+            run7<32, 0u>("whole tail, both", 12, 2);
+            run7<29, 0x04082082u>("whole tail, kernel's, 5/32", 12, 3);
+            run7<30, 0x04082082u>("whole tail, (b), 5/32", 12, 3);
+            run7<31, 0x04082082u>("whole tail, sqrt behind, 5/32", 12, 2);
+            run7<32, 0x04082082u>("whole tail, both, 5/32", 12, 2);
+        }
+        return 0;
+    }
     const bool fixed_only = argc > 1 && !strcmp(argv[1], "--fixed");   // the round-17 rows alone
     if (argc > 1 && !strcmp(argv[1], "--rot")) {   // the round-18 rows alone
         if (!check_rot()) return 1;
