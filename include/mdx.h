@@ -1255,6 +1255,70 @@ int mdx_hb_stats(mdx_hb_t h, int64_t *launches, double *kernel_ms, int64_t *fram
                  int64_t *max_row, int64_t *degenerate);
 int mdx_hb_enable_timing(mdx_hb_t h, int on);
 
+/* ---- dihedrals: torsion angles, their histogram, conformer states and the lifetimes of the states ------------------
+ * A frame delivers n_rows points; quads: int32 [D][4] row numbers (a, b, c, d) of the D dihedrals, four distinct rows
+ * each; group g holds n_dihedrals[g] consecutive dihedrals (a group may be empty, all of them together may not).
+ * Analysed frames are numbered f = 0, 1, ... in the order fed; lags: strictly increasing, non-negative frame offsets
+ * below 2^31; every frame is a time origin.  In float64 with separate multiply and add (float32 coordinates are
+ * widened before any arithmetic), per dihedral and frame:
+ *     b1 = x_b - x_a, b2 = x_c - x_b, b3 = x_d - x_c, each w = d - L * rint(d * (1.0 / L)) with a box (mdx_dih_set_box);
+ *     m = b1 x b2, n = b2 x b3 (m_x = b1y*b2z - b1z*b2y, ...);  m2, n2, l2 = the squares of m, n, b2;
+ *     p = m . n;  q = b1 . n;  den = sqrt(m2 * n2);  c = p / den (cos phi);  s = (sqrt(l2) * q) / den (sin phi, IUPAC sign)
+ * A dihedral whose m2 * n2 is not > 0 or not finite has no angle: it is counted, never averaged silently, and
+ * mdx_dih_synchronize and every read-out fail with MDX_ERR_INVALID_VALUE until mdx_dih_reset.
+ *     n_bins even, n_half = n_bins / 2; thresholds: float64 [n_half + 1], strictly decreasing (cos(m pi / n_half) bins
+ *     phi evenly over [-180, 180) degrees; only the inner ones are compared);
+ *     h = #{ m in 1 ... n_half - 1 : c <= thresholds[m] };  bin = q < 0 ? n_half - 1 - h : n_half + h
+ *     state(f) = state_of_bin[bin]   (int32 [n_bins], values 0 ... n_states - 1, 1 <= n_states <= 8)
+ *     run(0) = 0;  run(f) = state(f) == state(f - 1) ? min(run(f - 1) + 1, 2^31 - 1) : 0
+ * Integer results, added with integer atomics: counts[g][bin]; state_counts[f][g][s]; transitions[g][s0][s1] over the
+ * (dihedral, f >= 1) cases with state(f - 1) = s0 and state(f) = s1; same[k][g] over f >= lag_k with
+ * state(f) == state(f - lag_k); stay[k][g] over f >= lag_k with run(f) >= lag_k.  Float result:
+ * acc[k][v] += c(f)*c(f - lag_k) + s(f)*s(f - lag_k) in frame order, and sums[k][g] adds the accumulators of the group's
+ * dihedrals in row order (csrc/mdx_dihedral_device.hpp); no floating-point atomics are used, so every result is
+ * bit-identical across the three input routes, across any split of the frames into calls or slabs, and after a reset.
+ * The engine keeps max(max lag, 1) + one slab of frames of c, s, state and run in HBM (MDX_ERR_OUT_OF_MEMORY when that
+ * does not fit).  A handle touches its device with the first frame: mdx_dih_create and every argument error
+ * (MDX_ERR_INVALID_VALUE) need none. */
+typedef struct mdx_dih *mdx_dih_t;
+int mdx_dih_create(mdx_dih_t *out, int dev, int n_groups, const int64_t *n_dihedrals, int64_t n_rows,
+                   const int32_t *quads, int n_bins, const double *thresholds, int n_states,
+                   const int32_t *state_of_bin, int n_lags, const int64_t *lags);
+int mdx_dih_destroy(mdx_dih_t h);
+/* Forgets the frames seen, the history and the degenerate dihedrals and zeroes the results. */
+int mdx_dih_reset(mdx_dih_t h);
+/* One constant orthorhombic box for the minimum image of the three bond vectors.  dims: float64 [3] box lengths, or
+ * NULL: none (molecules that are whole already).  Only before the first frame. */
+int mdx_dih_set_box(mdx_dih_t h, const double *dims);
+/* As mdx_ori_set_slab_frames. */
+int mdx_dih_set_slab_frames(mdx_dih_t h, int64_t frames);
+/* As mdx_dip_plan; the ring holds max(max lag, 1) + slab frames. */
+int mdx_dih_plan(mdx_dih_t h, int64_t *slab_frames, int64_t *ring_frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n_rows. */
+int mdx_dih_accumulate(mdx_dih_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in the order the
+ * quads name them, or NULL for all n_atoms rows.  Asynchronous (mdx_dih_synchronize). */
+int mdx_dih_accumulate_device(mdx_dih_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_dih_accumulate_traj(mdx_dih_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_dih_synchronize(mdx_dih_t h);
+/* sums: float64 [n_lags][n_groups]; same, stay: int64 [n_lags][n_groups]. */
+int mdx_dih_result(mdx_dih_t h, double *sums, int64_t *same, int64_t *stay);
+/* out: float64 [n_lags][D]: the accumulators of every dihedral. */
+int mdx_dih_dihedral_sums(mdx_dih_t h, double *out);
+/* out: int64 [n_groups][n_bins]. */
+int mdx_dih_counts(mdx_dih_t h, int64_t *out);
+/* out: int64 [n][n_groups][n_states], the state populations of the first n frames seen. */
+int mdx_dih_state_counts(mdx_dih_t h, int64_t *out, int64_t n);
+/* out: int64 [n_groups][n_states][n_states]. */
+int mdx_dih_transitions(mdx_dih_t h, int64_t *out);
+/* evaluations: correlation terms formed so far (frame pairs x dihedrals, summed over the lags); degenerate: dihedrals
+ * without an angle seen since the last reset (not zero: the results are refused). */
+int mdx_dih_stats(mdx_dih_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *degenerate);
+int mdx_dih_enable_timing(mdx_dih_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

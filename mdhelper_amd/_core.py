@@ -1449,6 +1449,99 @@ class OrientationEngine(_SlabbedFrameEngine):
         return out
 
 
+class DihedralEngine(_SlabbedFrameEngine):
+    """``mdx_dih_*``: per frame ``cos`` and ``sin`` of the torsion angle of the rows ``quads[v] = (a, b, c, d)`` of the
+    ``n_rows`` incoming rows (with the minimum image where ``set_box`` gave a box), its bin among ``n_bins`` (even)
+    bins by the strictly decreasing ``thresholds`` (float64 ``[n_bins / 2 + 1]``) of the cosine and the sign of the
+    sine, and its state ``state_of_bin[bin]`` (``0 ... n_states - 1``, at most ``MAX_STATES`` states); per group the
+    histogram, per frame and group the state populations, per group the transitions between consecutive frames, and
+    per lag the sums of ``cos(phi(f) - phi(f - lag))``, the cases in the same state again and the cases that never
+    left it, in float64 and integers (csrc/mdx_dihedral_device.hpp).  Group ``g`` holds ``n_dihedrals[g]`` consecutive
+    dihedrals.  A dihedral without an angle (three atoms on a line, two on one point) makes ``synchronize()`` and
+    every read-out raise ``ValueError`` until ``reset()``.  The device is first touched by the first frame, so the
+    argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_dih"
+    _stats_extra = (("evaluations", c_int64), ("degenerate", c_int64))
+    TILE = 64           # dihedrals per tile: a tile never spans two groups (DIH_TILE of csrc/mdx_dihedral_device.hpp)
+    MAX_STATES = 8      # DIH_MAX_STATES
+    LDS_BINS = 1024     # bins at most for the LDS form of the histogram (DIH_LDS_BINS)
+
+    def __init__(self, n_dihedrals, quads, n_rows, thresholds, state_of_bin, lags, *, n_states=None, dev=0,
+                 timing=False):
+        self.n_per_group = np.ascontiguousarray(np.atleast_1d(n_dihedrals), dtype=np.int64)
+        if self.n_per_group.ndim != 1 or len(self.n_per_group) == 0:
+            raise ValueError("n_dihedrals must hold one entry per group.")
+        self.n_groups = len(self.n_per_group)
+        self.n_dihedrals = int(self.n_per_group.sum())
+        self.quads = np.ascontiguousarray(quads, dtype=np.int32)
+        if self.quads.ndim != 2 or self.quads.shape[1] != 4 or len(self.quads) != max(self.n_dihedrals, 0):
+            raise ValueError("quads must hold one (a, b, c, d) row per dihedral of the groups.")
+        self.n_rows = int(n_rows)
+        self.thresholds = np.ascontiguousarray(np.atleast_1d(thresholds), dtype=np.float64)
+        self.state_of_bin = np.ascontiguousarray(np.atleast_1d(state_of_bin), dtype=np.int32)
+        if self.thresholds.ndim != 1 or self.state_of_bin.ndim != 1 or len(self.state_of_bin) % 2 or \
+                len(self.thresholds) != len(self.state_of_bin) // 2 + 1:
+            raise ValueError("state_of_bin must hold an even number n_bins of entries and thresholds "
+                             "n_bins / 2 + 1.")
+        self.n_bins = len(self.state_of_bin)
+        self.n_states = int(self.state_of_bin.max(initial=0)) + 1 if n_states is None else int(n_states)
+        self.lags = np.ascontiguousarray(np.atleast_1d(lags), dtype=np.int64)
+        if self.lags.ndim != 1 or len(self.lags) == 0:
+            raise ValueError("lags must hold at least one lag.")
+        self.n_lags = len(self.lags)
+        h = c_void_p()
+        check(lib().mdx_dih_create(byref(h), dev, self.n_groups, _ptr(self.n_per_group), self.n_rows,
+                                   _ptr(self.quads), self.n_bins, _ptr(self.thresholds), self.n_states,
+                                   _ptr(self.state_of_bin), self.n_lags, _ptr(self.lags)))
+        self._adopt(h, dev, timing)
+
+    def set_box(self, dims):
+        """The box lengths ``dims`` of one constant orthorhombic box: the three bond vectors are then minimum images.
+        ``dims=None``: no box, for molecules that are whole already.  Only before the first frame."""
+        if dims is None:
+            check(lib().mdx_dih_set_box(self.handle, None))
+            return
+        d = np.ascontiguousarray(dims, dtype=np.float64)
+        if d.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        check(lib().mdx_dih_set_box(self.handle, _ptr(d)))
+
+    def result(self):
+        """``{"sums": float64 [n_lags, G], "same": int64 [n_lags, G], "stay": int64 [n_lags, G]}``."""
+        out = {"sums": np.zeros((self.n_lags, self.n_groups), dtype=np.float64),
+               "same": np.zeros((self.n_lags, self.n_groups), dtype=np.int64),
+               "stay": np.zeros((self.n_lags, self.n_groups), dtype=np.int64)}
+        check(lib().mdx_dih_result(self.handle, _ptr(out["sums"]), _ptr(out["same"]), _ptr(out["stay"])))
+        return out
+
+    def dihedral_sums(self):
+        """float64 ``[n_lags, D]``: every dihedral's own sums."""
+        out = np.zeros((self.n_lags, self.n_dihedrals), dtype=np.float64)
+        check(lib().mdx_dih_dihedral_sums(self.handle, _ptr(out)))
+        return out
+
+    def counts(self):
+        """int64 ``[G, n_bins]``: the histogram of every group over the frames seen."""
+        out = np.zeros((self.n_groups, self.n_bins), dtype=np.int64)
+        check(lib().mdx_dih_counts(self.handle, _ptr(out)))
+        return out
+
+    def state_counts(self):
+        """int64 ``[frames seen, G, n_states]``: the dihedrals of a group in every state, frame by frame."""
+        frames = c_int64()
+        check(lib().mdx_dih_stats(self.handle, None, None, byref(frames), None, None))
+        out = np.zeros((frames.value, self.n_groups, self.n_states), dtype=np.int64)
+        check(lib().mdx_dih_state_counts(self.handle, _ptr(out), len(out)))
+        return out
+
+    def transitions(self):
+        """int64 ``[G, n_states, n_states]``: the (dihedral, frame ``f >= 1``) cases by state at ``f - 1`` and ``f``."""
+        out = np.zeros((self.n_groups, self.n_states, self.n_states), dtype=np.int64)
+        check(lib().mdx_dih_transitions(self.handle, _ptr(out)))
+        return out
+
+
 class BondOrderEngine(_SlabbedFrameEngine):
     """``mdx_boo_*``: per frame the neighbours of each of ``n_centers`` centres among ``n_neighbors`` candidates
     (minimum-image ``r2 <= cutoff ** 2`` in float64), and per centre ``i`` with ``m_i >= 1`` neighbours and degree

@@ -373,6 +373,25 @@ _SIGNATURES = {
     "mdx_hb_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                              POINTER(c_int64), POINTER(c_int64)]),
     "mdx_hb_enable_timing": (c_int, [_vp, c_int]),
+    # dihedrals (torsion angles, conformer states and their lifetimes)
+    "mdx_dih_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int64, _vp, c_int, _vp, c_int, _vp, c_int, _vp]),
+    "mdx_dih_destroy": (c_int, [_vp]),
+    "mdx_dih_reset": (c_int, [_vp]),
+    "mdx_dih_set_box": (c_int, [_vp, _vp]),
+    "mdx_dih_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_dih_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_dih_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_dih_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_dih_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_dih_synchronize": (c_int, [_vp]),
+    "mdx_dih_result": (c_int, [_vp, _vp, _vp, _vp]),
+    "mdx_dih_dihedral_sums": (c_int, [_vp, _vp]),
+    "mdx_dih_counts": (c_int, [_vp, _vp]),
+    "mdx_dih_state_counts": (c_int, [_vp, _vp, c_int64]),
+    "mdx_dih_transitions": (c_int, [_vp, _vp]),
+    "mdx_dih_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64)]),
+    "mdx_dih_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

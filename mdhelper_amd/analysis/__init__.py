@@ -1,11 +1,12 @@
 """Analysis classes of the hot path (mirrors ``mdhelper.analysis``)."""
 
-from . import (angle, base, cluster, dynamics, electrostatics, hbond, order, polymer, profile,  # noqa: F401
+from . import (angle, base, cluster, dihedral, dynamics, electrostatics, hbond, order, polymer, profile,  # noqa: F401
                structure, transport)
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
 from .angle import AngularDistribution  # noqa: F401
 from .cluster import Clusters  # noqa: F401
+from .dihedral import Dihedrals  # noqa: F401
 from .dynamics import (DistinctVanHove, FourPointSusceptibility, OrientationalRelaxation,  # noqa: F401
                        PairResidence, VanHove, calculate_four_point_susceptibility,
                        calculate_non_gaussian_parameter, calculate_residence_time)
