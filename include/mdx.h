@@ -1319,6 +1319,62 @@ int mdx_dih_stats(mdx_dih_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *degenerate);
 int mdx_dih_enable_timing(mdx_dih_t h, int on);
 
+/* ---- spatial distribution: 3-D densities of partner atoms in the body-fixed frame of a reference molecule ----------
+ * The incoming rows of a frame are n_rows distinct atoms; o_row, a_row, b_row [n_ref] name the origin, the axis atom
+ * and the plane atom of every reference molecule (int32 rows in [0, n_rows); no origin twice, the three rows of a
+ * molecule differ pairwise); p_row [n_p] the partner atoms, group after group (no row twice), group_start
+ * [n_groups + 1] non-decreasing from 0 to n_p, 1 <= n_groups <= 8; owner [n_p]: the reference molecule a partner
+ * belongs to, in [0, n_ref), or -1: the pair (i, j) with owner[j] == i is never evaluated.  dims: float64 [3] lengths
+ * of one constant orthorhombic box; all three components take part.  In float64 with separate multiply and add and
+ * the minimum image w(x) = x - L * rint(x * (1.0 / L)), with O, A, B, P the positions of a frame:
+ *     a = w(A - O);  b = w(B - O);  p = a  (mode 0, axis)  or  a / sqrt(r2(a)) + b / sqrt(r2(b))  (mode 1, bisector);
+ *     e1 = p / sqrt(r2(p));  c = p x b;  e3 = c / sqrt(r2(c));  e2 = e3 x e1  (c_x = p_y*b_z - p_z*b_y, ...);
+ *     w = w(P - O);  near = r2(w) <= cutoff * cutoff and owner[j] != i and e1, e2, e3 all finite;
+ *     u = (w_x*e1_x + w_y*e1_y) + w_z*e1_z, v with e2, t with e3;
+ *     inside = near and ex[0] <= u <= ex[nx] and ey[0] <= v <= ey[ny] and ez[0] <= t <= ez[nz];
+ *     bin_x = #{m in 1 ... nx - 1 : u >= ex[m]}, likewise y and z (numpy.histogramdd: the last bin is closed above).
+ * A molecule with a non-finite e1, e2 or e3 (an atom on another, three collinear atoms) counts once per frame in
+ * `degenerate` and has no pair.  counts[g][bin_x][bin_y][bin_z]: the inside pairs of group g; inside[f]: those of
+ * frame f.  cutoff: positive, finite, at most half the shortest box length.  All results are integers and identical
+ * across the three input routes, across any split of the frames into calls or slabs, and after a reset
+ * (csrc/mdx_sdf_device.hpp).  A handle touches its device with the first frame: mdx_sdf_create, mdx_sdf_set_bins and
+ * every argument error (MDX_ERR_INVALID_VALUE, the message names the argument) need none. */
+typedef struct mdx_sdf *mdx_sdf_t;
+int mdx_sdf_create(mdx_sdf_t *out, int dev, int64_t n_rows, int64_t n_ref, const int32_t *o_row, const int32_t *a_row,
+                   const int32_t *b_row, int n_groups, const int64_t *group_start, const int32_t *p_row,
+                   const int32_t *owner, int mode, double cutoff, const double *dims);
+/* ex: float64 [nx + 1], ey: [ny + 1], ez: [nz + 1], strictly increasing and finite, 1 ... 512 bins per axis and
+ * n_groups * nx * ny * nz <= 2^26.  Without this call every axis has the one bin [-cutoff, cutoff].  Only before the
+ * first frame. */
+int mdx_sdf_set_bins(mdx_sdf_t h, int64_t nx, const double *ex, int64_t ny, const double *ey, int64_t nz,
+                     const double *ez);
+int mdx_sdf_destroy(mdx_sdf_t h);
+/* Forgets the frames seen and zeroes the results. */
+int mdx_sdf_reset(mdx_sdf_t h);
+/* Frames per kernel launch, at most (1 ... 32768; 0 restores the default).  The results do not depend on it.  Only
+ * before the first frame. */
+int mdx_sdf_set_slab_frames(mdx_sdf_t h, int64_t frames);
+/* As mdx_dip_plan; ring_frames = 0: a frame needs no other frame. */
+int mdx_sdf_plan(mdx_sdf_t h, int64_t *slab_frames, int64_t *ring_frames);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = n_rows. */
+int mdx_sdf_accumulate(mdx_sdf_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_sdf_synchronize). */
+int mdx_sdf_accumulate_device(mdx_sdf_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames, const int32_t *index,
+                              int64_t n_index);
+int mdx_sdf_accumulate_traj(mdx_sdf_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_sdf_synchronize(mdx_sdf_t h);
+/* counts: int64 [n_groups][nx][ny][nz]. */
+int mdx_sdf_result(mdx_sdf_t h, int64_t *counts);
+/* out: int64 [n], the inside pairs of the first n frames seen. */
+int mdx_sdf_inside(mdx_sdf_t h, int64_t *out, int64_t n);
+/* evaluations: the contract's pair count so far, frames x (n_ref * n_p - the pairs with owner[j] == i); degenerate:
+ * the (frame, molecule) cases without a frame of their own. */
+int mdx_sdf_stats(mdx_sdf_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *degenerate);
+int mdx_sdf_enable_timing(mdx_sdf_t h, int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1248,6 +1248,75 @@ class HydrogenBondEngine(_SlabbedFrameEngine):
         return out
 
 
+class SpatialDistributionEngine(_SlabbedFrameEngine):
+    """``mdx_sdf_*``: per frame the partner atoms around every reference molecule, counted in the molecule's own
+    frame.  ``o_row[i]``, ``a_row[i]`` and ``b_row[i]`` are the origin, the axis atom and the plane atom of molecule
+    ``i`` among the ``n_rows`` incoming rows; ``p_row`` the partners, group after group (``group_start``, at most
+    ``MAX_GROUPS`` groups); ``owner[j]`` the molecule partner ``j`` belongs to, or -1: that pair is never evaluated.
+    ``mode`` 0 puts the axis atom on local +x, 1 the bisector of the axis and the plane atom; the plane atom lies in
+    the local xy plane at y > 0.  A partner within ``cutoff`` of the origin (minimum image) is rotated into the frame
+    and counted per group with ``numpy.histogramdd``'s counts over the edges of ``set_bins``, all in float64
+    (csrc/mdx_sdf_device.hpp).  The device is first touched by the first frame, so the argument errors
+    (``ValueError``) need none."""
+
+    _prefix = "mdx_sdf"
+    _stats_extra = (("evaluations", c_int64), ("degenerate", c_int64))
+    TILE = 256          # reference molecules per block (SDF_TILE of csrc/mdx_sdf_device.hpp)
+    JCHUNK = 1024       # partners per block (SDF_JCHUNK)
+    MAX_GROUPS = 8      # partner groups at most (SDF_MAX_GROUPS)
+    MAX_AXIS_BINS = 512
+    AXIS, BISECTOR = 0, 1
+
+    def __init__(self, n_rows, o_row, a_row, b_row, group_start, p_row, owner, mode, cutoff, dims, *, dev=0,
+                 timing=False):
+        self.n_rows = int(n_rows)
+        self.o_row, self.a_row, self.b_row, self.p_row, self.owner = (
+            np.ascontiguousarray(np.atleast_1d(t), dtype=np.int32) for t in (o_row, a_row, b_row, p_row, owner))
+        if self.o_row.ndim != 1 or self.o_row.shape != self.a_row.shape or self.o_row.shape != self.b_row.shape:
+            raise ValueError("o_row, a_row and b_row must be one-dimensional and of one length.")
+        if self.p_row.ndim != 1 or self.p_row.shape != self.owner.shape:
+            raise ValueError("p_row and owner must be one-dimensional and of one length.")
+        self.group_start = np.ascontiguousarray(np.atleast_1d(group_start), dtype=np.int64)
+        if self.group_start.ndim != 1 or len(self.group_start) < 2:
+            raise ValueError("group_start must hold n_groups + 1 values, at least two.")
+        if self.group_start[-1] != len(self.p_row):
+            raise ValueError("group_start must end at the number of partners.")
+        self.n_ref, self.n_p, self.n_groups = len(self.o_row), len(self.p_row), len(self.group_start) - 1
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.n_bins = (1, 1, 1)
+        h = c_void_p()
+        check(lib().mdx_sdf_create(byref(h), dev, self.n_rows, self.n_ref, _ptr(self.o_row), _ptr(self.a_row),
+                                   _ptr(self.b_row), self.n_groups, _ptr(self.group_start), _ptr(self.p_row),
+                                   _ptr(self.owner), int(mode), float(cutoff), _ptr(self.dims)))
+        self._adopt(h, dev, timing)
+
+    def set_bins(self, ex, ey, ez):
+        """Strictly increasing float64 edges per axis, ``n + 1`` of them for ``n <= 512`` bins.  Only before the
+        first frame."""
+        e = [np.ascontiguousarray(t, dtype=np.float64) for t in (ex, ey, ez)]
+        if any(t.ndim != 1 or len(t) < 2 for t in e):
+            raise ValueError("the edges must hold n_bins + 1 values, at least two.")
+        check(lib().mdx_sdf_set_bins(self.handle, len(e[0]) - 1, _ptr(e[0]), len(e[1]) - 1, _ptr(e[1]),
+                                     len(e[2]) - 1, _ptr(e[2])))
+        self.n_bins = tuple(len(t) - 1 for t in e)
+
+    def result(self):
+        """``int64 [n_groups, nx, ny, nz]``: the counts over the frames seen."""
+        out = np.zeros((self.n_groups,) + self.n_bins, dtype=np.int64)
+        check(lib().mdx_sdf_result(self.handle, _ptr(out)))
+        return out
+
+    def inside(self):
+        """``int64 [frames]``: the counted pairs of every frame seen."""
+        frames = c_int64()
+        check(lib().mdx_sdf_stats(self.handle, None, None, byref(frames), None, None))
+        out = np.zeros(frames.value, dtype=np.int64)
+        check(lib().mdx_sdf_inside(self.handle, _ptr(out), len(out)))
+        return out
+
+
 class ClusterEngine(_SlabbedFrameEngine):
     """``mdx_clu_*``: per frame the connected components of the bond graph of ``n`` rows.  ``species`` (``int [n]``,
     ``0 ... G - 1``, ``G <= 8``) names the group of a row; ``cutoff`` is a float or a symmetric ``G x G`` table of

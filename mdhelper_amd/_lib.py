@@ -392,6 +392,23 @@ _SIGNATURES = {
     "mdx_dih_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
     "mdx_dih_enable_timing": (c_int, [_vp, c_int]),
+    # spatial distribution (3-D densities in a molecule's own frame)
+    "mdx_sdf_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_int,
+                               c_double, _vp]),
+    "mdx_sdf_set_bins": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, _vp]),
+    "mdx_sdf_destroy": (c_int, [_vp]),
+    "mdx_sdf_reset": (c_int, [_vp]),
+    "mdx_sdf_set_slab_frames": (c_int, [_vp, c_int64]),
+    "mdx_sdf_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_sdf_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "mdx_sdf_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "mdx_sdf_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "mdx_sdf_synchronize": (c_int, [_vp]),
+    "mdx_sdf_result": (c_int, [_vp, _vp]),
+    "mdx_sdf_inside": (c_int, [_vp, _vp, c_int64]),
+    "mdx_sdf_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64)]),
+    "mdx_sdf_enable_timing": (c_int, [_vp, c_int]),
 }
 
 EXPORTS = tuple(_SIGNATURES)

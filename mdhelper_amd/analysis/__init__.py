@@ -1,7 +1,7 @@
 """Analysis classes of the hot path (mirrors ``mdhelper.analysis``)."""
 
 from . import (angle, base, cluster, dihedral, dynamics, electrostatics, hbond, order, polymer, profile,  # noqa: F401
-               structure, transport)
+               spatial, structure, transport)
 from .structure import (IntermediateScatteringFunction, RadialDistributionFunction,  # noqa: F401
                         StructureFactor)
 from .angle import AngularDistribution  # noqa: F401
@@ -16,4 +16,5 @@ from .order import BondOrientationalOrder  # noqa: F401
 from .polymer import (EndToEndVector, Gyradius, InternalDistances, RouseModes,  # noqa: F401
                       SingleChainStructureFactor)
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401
+from .spatial import SpatialDistributionFunction  # noqa: F401
 from .transport import Onsager  # noqa: F401
