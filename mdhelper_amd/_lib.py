@@ -156,234 +156,108 @@ _SIGNATURES = {
                                           c_int, _vp]),
     # density profiles
     "mdx_prof_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int, _vp, _vp, _vp, c_int]),
-    "mdx_prof_destroy": (c_int, [_vp]),
-    "mdx_prof_reset": (c_int, [_vp]),
     "mdx_prof_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
     "mdx_prof_set_recenter": (c_int, [_vp, c_int, _vp, _vp]),
-    "mdx_prof_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_prof_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_prof_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_prof_synchronize": (c_int, [_vp]),
     "mdx_prof_counts": (c_int, [_vp, c_int, _vp]),
     "mdx_prof_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int)]),
-    "mdx_prof_enable_timing": (c_int, [_vp, c_int]),
     "mdx_prof_set_replicas": (c_int, [_vp, c_int]),
     "mdx_feed_slab_frames": (c_int, [c_int64, c_int64, _vp]),
     "mdx_prof_slab_frames": (c_int, [c_int64, c_int, c_int, _vp]),
     # radii of gyration
     "mdx_gyr_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp, _vp]),
-    "mdx_gyr_destroy": (c_int, [_vp]),
-    "mdx_gyr_reset": (c_int, [_vp]),
     "mdx_gyr_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
     "mdx_gyr_set_unwrap": (c_int, [_vp, _vp, _vp]),
-    "mdx_gyr_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_gyr_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_gyr_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_gyr_synchronize": (c_int, [_vp]),
     "mdx_gyr_result": (c_int, [_vp, _vp]),
     "mdx_gyr_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
-    "mdx_gyr_enable_timing": (c_int, [_vp, c_int]),
     "mdx_gyr_slab_frames": (c_int, [c_int64, c_int64, c_int, c_int, _vp]),
     # per-chain linear projections (Rouse mode amplitudes)
     "mdx_rouse_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp, c_int64, _vp]),
-    "mdx_rouse_destroy": (c_int, [_vp]),
-    "mdx_rouse_reset": (c_int, [_vp]),
     "mdx_rouse_reserve": (c_int, [_vp, c_int64]),
     "mdx_rouse_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
     "mdx_rouse_set_unwrap": (c_int, [_vp, _vp, _vp]),
-    "mdx_rouse_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_rouse_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_rouse_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_rouse_synchronize": (c_int, [_vp]),
     "mdx_rouse_result": (c_int, [_vp, _vp]),
     "mdx_rouse_device_result": (c_int, [_vp, POINTER(_vp), POINTER(c_int64), POINTER(c_int64)]),
     "mdx_rouse_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
-    "mdx_rouse_enable_timing": (c_int, [_vp, c_int]),
     "mdx_rouse_slab_frames": (c_int, [c_int64, c_int, c_int, _vp]),
     # chain internal distances and bond-orientation correlations
     "mdx_msid_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
-    "mdx_msid_destroy": (c_int, [_vp]),
-    "mdx_msid_reset": (c_int, [_vp]),
     "mdx_msid_reserve": (c_int, [_vp, c_int64]),
     "mdx_msid_set_grouping": (c_int, [_vp, c_int64, _vp, _vp]),
     "mdx_msid_set_unwrap": (c_int, [_vp, _vp, _vp]),
     "mdx_msid_set_whole": (c_int, [_vp, _vp]),
-    "mdx_msid_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_msid_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_msid_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_msid_synchronize": (c_int, [_vp]),
     "mdx_msid_result": (c_int, [_vp, _vp]),
     "mdx_msid_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
-    "mdx_msid_enable_timing": (c_int, [_vp, c_int]),
     "mdx_msid_slab_frames": (c_int, [c_int, _vp, _vp, c_int, c_int, c_int, _vp]),
     # dipole moments
     "mdx_dip_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, _vp]),
-    "mdx_dip_destroy": (c_int, [_vp]),
-    "mdx_dip_reset": (c_int, [_vp]),
     "mdx_dip_set_unwrap": (c_int, [_vp, _vp, _vp]),
-    "mdx_dip_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_dip_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_dip_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_dip_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_dip_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_dip_synchronize": (c_int, [_vp]),
     "mdx_dip_result": (c_int, [_vp, _vp]),
     "mdx_dip_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64)]),
-    "mdx_dip_enable_timing": (c_int, [_vp, c_int]),
     # self van Hove function and displacement moments
     "mdx_vh_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int, _vp, c_int, _vp, c_int]),
-    "mdx_vh_destroy": (c_int, [_vp]),
-    "mdx_vh_reset": (c_int, [_vp]),
     "mdx_vh_set_unwrap": (c_int, [_vp, _vp]),
-    "mdx_vh_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_vh_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_vh_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_vh_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_vh_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_vh_synchronize": (c_int, [_vp]),
     "mdx_vh_result": (c_int, [_vp, _vp, _vp]),
     "mdx_vh_point_moments": (c_int, [_vp, _vp]),
     "mdx_vh_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_vh_enable_timing": (c_int, [_vp, c_int]),
     # distinct van Hove function
     "mdx_vhd_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_int, _vp, c_int, _vp, c_int64, _vp,
                                c_int]),
-    "mdx_vhd_destroy": (c_int, [_vp]),
-    "mdx_vhd_reset": (c_int, [_vp]),
-    "mdx_vhd_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_vhd_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_vhd_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_vhd_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_vhd_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_vhd_synchronize": (c_int, [_vp]),
     "mdx_vhd_result": (c_int, [_vp, _vp]),
     "mdx_vhd_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_vhd_enable_timing": (c_int, [_vp, c_int]),
     # pair residence (contact survival functions)
     "mdx_prs_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_double, c_int, _vp, c_int64, _vp, c_int,
                                c_int, c_int]),
-    "mdx_prs_destroy": (c_int, [_vp]),
-    "mdx_prs_reset": (c_int, [_vp]),
-    "mdx_prs_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_prs_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_prs_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_prs_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_prs_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_prs_synchronize": (c_int, [_vp]),
     "mdx_prs_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_prs_contacts": (c_int, [_vp, _vp, c_int64]),
     "mdx_prs_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
-    "mdx_prs_enable_timing": (c_int, [_vp, c_int]),
     # ion clusters (connected components of a contact graph)
     "mdx_clu_create": (c_int, [POINTER(_vp), c_int, c_int64, _vp, c_int, _vp, _vp, c_int, c_int, c_int]),
-    "mdx_clu_destroy": (c_int, [_vp]),
-    "mdx_clu_reset": (c_int, [_vp]),
-    "mdx_clu_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_clu_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_clu_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_clu_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_clu_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_clu_synchronize": (c_int, [_vp]),
     "mdx_clu_result": (c_int, [_vp, _vp, _vp]),
     "mdx_clu_frames": (c_int, [_vp, _vp, _vp, _vp, _vp, c_int64]),
     "mdx_clu_labels": (c_int, [_vp, _vp, c_int64]),
     "mdx_clu_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_clu_enable_timing": (c_int, [_vp, c_int]),
     # angular distributions (ligand-center-ligand angles in the first shell)
     "mdx_ang_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int, _vp, c_int, _vp, c_int64, _vp, _vp, c_int,
                                c_int]),
-    "mdx_ang_destroy": (c_int, [_vp]),
-    "mdx_ang_reset": (c_int, [_vp]),
-    "mdx_ang_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_ang_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_ang_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_ang_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_ang_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_ang_synchronize": (c_int, [_vp]),
     "mdx_ang_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_ang_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_ang_enable_timing": (c_int, [_vp, c_int]),
     # orientational relaxation (P1 / P2 of unit vectors, order tensor)
     "mdx_ori_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int64, _vp, c_int, _vp, c_int]),
-    "mdx_ori_destroy": (c_int, [_vp]),
-    "mdx_ori_reset": (c_int, [_vp]),
     "mdx_ori_set_box": (c_int, [_vp, _vp]),
-    "mdx_ori_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_ori_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_ori_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_ori_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_ori_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_ori_synchronize": (c_int, [_vp]),
     "mdx_ori_result": (c_int, [_vp, _vp]),
     "mdx_ori_vector_sums": (c_int, [_vp, _vp]),
     "mdx_ori_frame_sums": (c_int, [_vp, _vp, c_int64]),
     "mdx_ori_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
-    "mdx_ori_enable_timing": (c_int, [_vp, c_int]),
     # bond-orientational order (Steinhardt q_l, neighbour-averaged qbar_l)
     "mdx_boo_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_double, c_int, _vp, c_int, c_int64, _vp,
                                _vp, c_int, c_int]),
-    "mdx_boo_destroy": (c_int, [_vp]),
-    "mdx_boo_reset": (c_int, [_vp]),
-    "mdx_boo_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_boo_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_boo_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_boo_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_boo_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_boo_synchronize": (c_int, [_vp]),
     "mdx_boo_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_boo_frames": (c_int, [_vp, _vp, _vp, c_int64]),
     "mdx_boo_values": (c_int, [_vp, _vp, c_int64]),
     "mdx_boo_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_boo_enable_timing": (c_int, [_vp, c_int]),
     # self-overlap and four-point susceptibility
     "mdx_chi4_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int, _vp, c_int, _vp, c_int64, c_int]),
-    "mdx_chi4_destroy": (c_int, [_vp]),
-    "mdx_chi4_reset": (c_int, [_vp]),
     "mdx_chi4_set_unwrap": (c_int, [_vp, _vp]),
-    "mdx_chi4_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_chi4_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
     "mdx_chi4_set_segment_points": (c_int, [_vp, c_int64]),
-    "mdx_chi4_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_chi4_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_chi4_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_chi4_synchronize": (c_int, [_vp]),
     "mdx_chi4_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_chi4_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_chi4_enable_timing": (c_int, [_vp, c_int]),
     # hydrogen bonds (donor-H...acceptor counts, geometry and lifetimes)
     "mdx_hb_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp, c_int64, _vp, c_double, c_double, c_int,
                               _vp, c_int64, _vp, c_int, c_int, c_int]),
     "mdx_hb_set_bins": (c_int, [_vp, c_int64, _vp, c_int64, _vp]),
-    "mdx_hb_destroy": (c_int, [_vp]),
-    "mdx_hb_reset": (c_int, [_vp]),
-    "mdx_hb_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_hb_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_hb_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_hb_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_hb_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_hb_synchronize": (c_int, [_vp]),
     "mdx_hb_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_hb_bonds": (c_int, [_vp, _vp, c_int64]),
     "mdx_hb_geometry": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_hb_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                              POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_hb_enable_timing": (c_int, [_vp, c_int]),
     # dihedrals (torsion angles, conformer states and their lifetimes)
     "mdx_dih_create": (c_int, [POINTER(_vp), c_int, c_int, _vp, c_int64, _vp, c_int, _vp, c_int, _vp, c_int, _vp]),
-    "mdx_dih_destroy": (c_int, [_vp]),
-    "mdx_dih_reset": (c_int, [_vp]),
     "mdx_dih_set_box": (c_int, [_vp, _vp]),
-    "mdx_dih_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_dih_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_dih_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_dih_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_dih_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_dih_synchronize": (c_int, [_vp]),
     "mdx_dih_result": (c_int, [_vp, _vp, _vp, _vp]),
     "mdx_dih_dihedral_sums": (c_int, [_vp, _vp]),
     "mdx_dih_counts": (c_int, [_vp, _vp]),
@@ -391,25 +265,37 @@ _SIGNATURES = {
     "mdx_dih_transitions": (c_int, [_vp, _vp]),
     "mdx_dih_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
-    "mdx_dih_enable_timing": (c_int, [_vp, c_int]),
     # spatial distribution (3-D densities in a molecule's own frame)
     "mdx_sdf_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, _vp, _vp, _vp, c_int, _vp, _vp, _vp, c_int,
                                c_double, _vp]),
     "mdx_sdf_set_bins": (c_int, [_vp, c_int64, _vp, c_int64, _vp, c_int64, _vp]),
-    "mdx_sdf_destroy": (c_int, [_vp]),
-    "mdx_sdf_reset": (c_int, [_vp]),
-    "mdx_sdf_set_slab_frames": (c_int, [_vp, c_int64]),
-    "mdx_sdf_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
-    "mdx_sdf_accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
-    "mdx_sdf_accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
-    "mdx_sdf_accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
-    "mdx_sdf_synchronize": (c_int, [_vp]),
     "mdx_sdf_result": (c_int, [_vp, _vp]),
     "mdx_sdf_inside": (c_int, [_vp, _vp, c_int64]),
     "mdx_sdf_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
-    "mdx_sdf_enable_timing": (c_int, [_vp, c_int]),
 }
+
+# The entry points every per-frame engine has (csrc/mdx_frame_entry.hpp); the last two only where the engine works in
+# slabs it reports.  Above stand the entries an engine has of its own: create, result, stats, setters, getters.
+_FRAME_ENGINES = ("prof", "gyr", "rouse", "msid", "dip", "vh", "vhd", "prs", "clu", "ang", "ori", "boo", "chi4", "hb",
+                  "dih", "sdf")
+_SLAB_ENGINES = ("dip", "vh", "vhd", "prs", "clu", "ang", "ori", "boo", "chi4", "hb", "dih", "sdf")
+_FRAME_ENTRY = {
+    "accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
+    "accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
+    "accumulate_traj": (c_int, [_vp, _vp, _vp, c_int64, _vp, c_int64]),
+    "enable_timing": (c_int, [_vp, c_int]),
+    "synchronize": (c_int, [_vp]),
+    "destroy": (c_int, [_vp]),
+    "reset": (c_int, [_vp]),
+    "set_slab_frames": (c_int, [_vp, c_int64]),
+    "plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64)]),
+}
+_SIGNATURES.update(
+    (f"mdx_{prefix}_{name}", signature)
+    for prefix in _FRAME_ENGINES
+    for name, signature in _FRAME_ENTRY.items()
+    if prefix in _SLAB_ENGINES or name not in ("set_slab_frames", "plan"))
 
 EXPORTS = tuple(_SIGNATURES)
 

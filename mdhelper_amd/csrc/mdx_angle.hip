@@ -12,7 +12,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_pairs_host.hpp"
 #include "mdx_angle_device.hpp"
@@ -44,6 +44,11 @@ struct mdx_ang : LazyFrameEngine {
 
     int64_t pairs() const { return int64_t(n_species) * (n_species + 1) / 2; }
     int64_t words() const { return pairs() * n_bins + pairs() + int64_t(n_species) * (lists.max_nb + 1); }
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "groups"; }
+    void clear_counters() { lists.max_row = 0; }
+    void free_device() { release({&d_inner, &d_counts, &lists.d_ctl, &d_slab, &lists.d_len, &lists.d_list}); }
 };
 
 // bytes a frame of a slab takes: its gathered rows, its lists and lengths
@@ -208,73 +213,11 @@ int mdx_ang_create(mdx_ang_t *out, int dev, int64_t n_centers, int n_species, co
     return MDX_OK;
 }
 
-int mdx_ang_destroy(mdx_ang_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_inner, &h->d_counts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len, &h->lists.d_list});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_ang_reset(mdx_ang_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->lists.max_row = 0;
-    return h->reset(ang_zero);
-}
-
-int mdx_ang_set_slab_frames(mdx_ang_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, ANG_SLAB_MAX, "mdx_ang_set_slab_frames");
-}
-
 // what a route prepares before the first kernel
 static int ang_prepare(mdx_ang *h, int64_t)
 {
     MDX_TRY(ang_ensure_device(h));
     return ang_ensure_slab(h);
-}
-
-int mdx_ang_plan(mdx_ang_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
-    *slab_frames = ang_slab(h);
-    *ring_frames = 0;           // no frame outlives its slab
-    return MDX_OK;
-}
-
-int mdx_ang_accumulate_device(mdx_ang_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "groups", ang_prepare,
-                                ang_accumulate_rows);
-}
-
-int mdx_ang_accumulate(mdx_ang_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "groups", ang_prepare, ang_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
-// the file's first n_index particles.
-int mdx_ang_accumulate_traj(mdx_ang_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "groups",
-                              ang_prepare, ang_accumulate_rows);
-}
-
-int mdx_ang_synchronize(mdx_ang_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? ang_check_rows(h) : MDX_OK;
 }
 
 int mdx_ang_result(mdx_ang_t h, int64_t *counts, int64_t *degenerate, int64_t *coordination)
@@ -314,10 +257,9 @@ int mdx_ang_stats(mdx_ang_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_ang_enable_timing(mdx_ang_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(ang, ang_prepare, ang_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(ang, ang_zero, ang_check_rows)
+MDX_FRAME_SET_SLAB_FRAMES(ang, ANG_SLAB_MAX)
+MDX_FRAME_PLAN(ang, ang_slab)

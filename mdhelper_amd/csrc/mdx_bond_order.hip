@@ -12,7 +12,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_pairs_host.hpp"
 #include "mdx_bond_order_device.hpp"
@@ -108,6 +108,15 @@ struct mdx_boo : LazyFrameEngine {
     unsigned long long *coordination_words() { return outside_words() + DK(); }
     unsigned long long *degenerate_word() { return coordination_words() + (lists.max_nb + 1); }
     int64_t qlm_frame_words() const { return int64_t(2) * (l_max + 1) * n0; }     // of one degree
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "groups"; }
+    void clear_counters() { lists.max_row = 0; degenerate = 0; values.clear(); }
+    void free_device()
+    {
+        release({&d_edges, &d_tables, &d_counts, &lists.d_ctl, &d_slab, &lists.d_len, &lists.d_list, &d_qlm, &d_values,
+                 &d_frame_sums, &d_counted});
+    }
 };
 
 // bytes a frame of a slab takes: its gathered rows, its lists and lengths, q_lm of every degree, its values
@@ -315,76 +324,11 @@ int mdx_boo_create(mdx_boo_t *out, int dev, int64_t n_centers, int64_t n_neighbo
     return MDX_OK;
 }
 
-int mdx_boo_destroy(mdx_boo_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_edges, &h->d_tables, &h->d_counts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
-                    &h->lists.d_list, &h->d_qlm, &h->d_values, &h->d_frame_sums, &h->d_counted});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_boo_reset(mdx_boo_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->lists.max_row = 0;
-    h->degenerate = 0;
-    h->values.clear();
-    return h->reset(boo_zero);
-}
-
-int mdx_boo_set_slab_frames(mdx_boo_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, BOO_SLAB_MAX, "mdx_boo_set_slab_frames");
-}
-
 // what a route prepares before the first kernel
 static int boo_prepare(mdx_boo *h, int64_t)
 {
     MDX_TRY(boo_ensure_device(h));
     return boo_ensure_slab(h);
-}
-
-int mdx_boo_plan(mdx_boo_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
-    *slab_frames = boo_slab(h);
-    *ring_frames = 0;           // no frame outlives its slab
-    return MDX_OK;
-}
-
-int mdx_boo_accumulate_device(mdx_boo_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "groups", boo_prepare,
-                                boo_accumulate_rows);
-}
-
-int mdx_boo_accumulate(mdx_boo_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "groups", boo_prepare, boo_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
-// the file's first n_index particles.
-int mdx_boo_accumulate_traj(mdx_boo_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "groups",
-                              boo_prepare, boo_accumulate_rows);
-}
-
-int mdx_boo_synchronize(mdx_boo_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? boo_check(h) : MDX_OK;
 }
 
 int mdx_boo_result(mdx_boo_t h, int64_t *counts, int64_t *outside, int64_t *coordination)
@@ -454,10 +398,9 @@ int mdx_boo_stats(mdx_boo_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_boo_enable_timing(mdx_boo_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(boo, boo_prepare, boo_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(boo, boo_zero, boo_check)
+MDX_FRAME_SET_SLAB_FRAMES(boo, BOO_SLAB_MAX)
+MDX_FRAME_PLAN(boo, boo_slab)

@@ -13,6 +13,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_chi4_device.hpp"
@@ -56,6 +57,15 @@ struct mdx_chi4 : LazyFrameEngine {
     Chi4Cutoffs cut;
     std::vector<int64_t> offsets;
     DeviceBuffer d_offsets, d_s1, d_s2, d_qslab;
+
+    int64_t rows_wanted() const { return n_points; }
+    const char *rows_noun() const { return "groups"; }
+    int64_t ring_lag() const { return lags.max_lag; }
+    void clear_counters() { evaluations = 0; }
+    void free_device()
+    {
+        release({&d_offsets, &lags.d_lags, &d_s1, &d_s2, &d_qslab, &hist.d_hist, &hist.d_prev, &hist.d_image});
+    }
 };
 
 static int64_t chi4_slab(const mdx_chi4 *h)
@@ -220,34 +230,10 @@ int mdx_chi4_create(mdx_chi4_t *out, int dev, int n_groups, const int64_t *n_poi
     return MDX_OK;
 }
 
-int mdx_chi4_destroy(mdx_chi4_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_offsets, &h->lags.d_lags, &h->d_s1, &h->d_s2, &h->d_qslab, &h->hist.d_hist, &h->hist.d_prev,
-                    &h->hist.d_image});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_chi4_reset(mdx_chi4_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->evaluations = 0;
-    return h->reset(chi4_zero);     // frames_seen = 0: the history and the unwrap state start over with the next frame
-}
-
 int mdx_chi4_set_unwrap(mdx_chi4_t h, const double *dims)
 {
     MDX_REQUIRE(h, "NULL handle");
     return h->hist.set_unwrap(dims, h->frames_seen, "mdx_chi4_set_unwrap");
-}
-
-int mdx_chi4_set_slab_frames(mdx_chi4_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, CHI4_SLAB_MAX, "mdx_chi4_set_slab_frames");
 }
 
 int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points)
@@ -260,20 +246,14 @@ int mdx_chi4_set_segment_points(mdx_chi4_t h, int64_t points)
     return MDX_OK;
 }
 
-int mdx_chi4_plan(mdx_chi4_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->lags.max_lag, chi4_slab(h), slab_frames, ring_frames);
-}
-
+// The routes have a rule of their own: frames that would overflow the sums are refused before the route's checks.
 int mdx_chi4_accumulate_device(mdx_chi4_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
                                const int32_t *index, int64_t n_index)
 {
     MDX_REQUIRE(h && d_pos, "NULL argument");
     MDX_REQUIRE(n_frames >= 0, "bad size");
     MDX_TRY(chi4_check_overflow(h, n_frames));
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_points, "groups", chi4_prepare,
-                                chi4_accumulate_rows);
+    return entry_accumulate_device(h, d_pos, n_atoms, n_frames, index, n_index, chi4_prepare, chi4_accumulate_rows);
 }
 
 int mdx_chi4_accumulate(mdx_chi4_t h, const float *pos, int64_t n, int64_t n_frames)
@@ -281,7 +261,7 @@ int mdx_chi4_accumulate(mdx_chi4_t h, const float *pos, int64_t n, int64_t n_fra
     MDX_REQUIRE(h && pos, "NULL argument");
     MDX_REQUIRE(n_frames >= 0, "bad size");
     MDX_TRY(chi4_check_overflow(h, n_frames));
-    return h->accumulate_host(pos, n, n_frames, h->n_points, "groups", chi4_prepare, chi4_accumulate_rows);
+    return entry_accumulate(h, pos, n, n_frames, chi4_prepare, chi4_accumulate_rows);
 }
 
 // Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
@@ -292,14 +272,7 @@ int mdx_chi4_accumulate_traj(mdx_chi4_t h, mdx_traj_t traj, const int64_t *frame
     MDX_REQUIRE(h && traj, "NULL handle");
     MDX_REQUIRE(n_frames >= 0, "bad frame list");
     MDX_TRY(chi4_check_overflow(h, n_frames));
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_points, "groups",
-                              chi4_prepare, chi4_accumulate_rows);
-}
-
-int mdx_chi4_synchronize(mdx_chi4_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->synchronize();
+    return entry_accumulate_traj(h, traj, frames, n_frames, index, n_index, chi4_prepare, chi4_accumulate_rows);
 }
 
 int mdx_chi4_result(mdx_chi4_t h, int64_t *sums, int64_t *square_sums, int64_t *n_origins)
@@ -323,10 +296,8 @@ int mdx_chi4_stats(mdx_chi4_t h, int64_t *launches, double *kernel_ms, int64_t *
     return MDX_OK;
 }
 
-int mdx_chi4_enable_timing(mdx_chi4_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_LAZY_FRAME_LIFE_CYCLE(chi4, chi4_zero, unchecked)
+MDX_FRAME_SET_SLAB_FRAMES(chi4, CHI4_SLAB_MAX)
+MDX_FRAME_RING_PLAN(chi4, chi4_slab)

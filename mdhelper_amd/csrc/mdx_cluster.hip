@@ -11,7 +11,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_pairs_host.hpp"
 #include "mdx_cluster_device.hpp"
@@ -42,6 +42,15 @@ struct mdx_clu : LazyFrameEngine {
     // d_counts: uint64 [1 + G][n + 1], size_counts then species_counts; d_frames: uint64 [frames][CLU_FRAME_WORDS];
     // d_labels: int32 [frames][n] (keep_labels)
     DeviceBuffer d_species, d_table, d_counts, d_frames, d_labels, d_slab, d_label, d_size;
+
+    int64_t rows_wanted() const { return n; }
+    const char *rows_noun() const { return "groups"; }
+    void clear_counters() { sweeps = lists.max_row = 0; }
+    void free_device()
+    {
+        release({&d_species, &d_table, &d_counts, &d_frames, &d_labels, &lists.d_ctl, &d_slab, &lists.d_len,
+                 &lists.d_list, &d_label, &d_size});
+    }
 };
 
 // bytes a frame of a slab takes: its gathered rows, its lists and lengths, its labels and sizes
@@ -253,75 +262,11 @@ int mdx_clu_create(mdx_clu_t *out, int dev, int64_t n, const int32_t *species, i
     return MDX_OK;
 }
 
-int mdx_clu_destroy(mdx_clu_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_species, &h->d_table, &h->d_counts, &h->d_frames, &h->d_labels, &h->lists.d_ctl, &h->d_slab,
-                    &h->lists.d_len, &h->lists.d_list, &h->d_label, &h->d_size});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_clu_reset(mdx_clu_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->sweeps = 0;
-    h->lists.max_row = 0;
-    return h->reset(clu_zero);
-}
-
-int mdx_clu_set_slab_frames(mdx_clu_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, CLU_SLAB_MAX, "mdx_clu_set_slab_frames");
-}
-
 // what a route prepares before the first kernel
 static int clu_prepare(mdx_clu *h, int64_t)
 {
     MDX_TRY(clu_ensure_device(h));
     return clu_ensure_slab(h);
-}
-
-int mdx_clu_plan(mdx_clu_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
-    *slab_frames = clu_slab(h);
-    *ring_frames = 0;           // no frame outlives its slab
-    return MDX_OK;
-}
-
-int mdx_clu_accumulate_device(mdx_clu_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n, "groups", clu_prepare,
-                                clu_accumulate_rows);
-}
-
-int mdx_clu_accumulate(mdx_clu_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n, "groups", clu_prepare, clu_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
-// the file's first n_index particles.
-int mdx_clu_accumulate_traj(mdx_clu_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n, "groups", clu_prepare,
-                              clu_accumulate_rows);
-}
-
-int mdx_clu_synchronize(mdx_clu_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? clu_check_rows(h) : MDX_OK;
 }
 
 int mdx_clu_result(mdx_clu_t h, int64_t *size_counts, int64_t *species_counts)
@@ -388,10 +333,9 @@ int mdx_clu_stats(mdx_clu_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_clu_enable_timing(mdx_clu_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(clu, clu_prepare, clu_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(clu, clu_zero, clu_check_rows)
+MDX_FRAME_SET_SLAB_FRAMES(clu, CLU_SLAB_MAX)
+MDX_FRAME_PLAN(clu, clu_slab)

@@ -17,6 +17,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_dihedral_device.hpp"
@@ -63,6 +64,15 @@ struct mdx_dih : LazyFrameEngine {
     unsigned long long *stay() const { return same() + n_lag_groups(); }
     unsigned long long *ctl() const { return stay() + n_lag_groups(); }
     int64_t ring_lag() const { return std::max<int64_t>(lags.max_lag, 1); }     // run(f) needs frame f - 1
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "quads"; }
+    void clear_counters() { evaluations = degenerate = 0; }
+    void free_device()
+    {
+        release({&d_tiles, &d_quads, &d_offsets, &d_inner, &d_state_of_bin, &lags.d_lags, &d_acc, &d_sums, &d_hist,
+                 &d_state, &d_run, &d_tally, &d_state_counts});
+    }
 };
 
 static int64_t dih_slab(const mdx_dih *h)
@@ -251,25 +261,6 @@ int mdx_dih_create(mdx_dih_t *out, int dev, int n_groups, const int64_t *n_dihed
     return MDX_OK;
 }
 
-int mdx_dih_destroy(mdx_dih_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_tiles, &h->d_quads, &h->d_offsets, &h->d_inner, &h->d_state_of_bin, &h->lags.d_lags,
-                    &h->d_acc, &h->d_sums, &h->d_hist, &h->d_state, &h->d_run, &h->d_tally, &h->d_state_counts});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_dih_reset(mdx_dih_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->evaluations = 0;
-    h->degenerate = 0;
-    return h->reset(dih_zero);  // frames_seen = 0: the history starts over with the next frame
-}
-
 int mdx_dih_set_box(mdx_dih_t h, const double *dims)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -283,49 +274,6 @@ int mdx_dih_set_box(mdx_dih_t h, const double *dims)
         h->box.inv[c] = dims ? 1.0 / dims[c] : 0.0;
     }
     return MDX_OK;
-}
-
-int mdx_dih_set_slab_frames(mdx_dih_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, DIH_SLAB_MAX, "mdx_dih_set_slab_frames");
-}
-
-int mdx_dih_plan(mdx_dih_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->ring_lag(), dih_slab(h), slab_frames, ring_frames);
-}
-
-int mdx_dih_accumulate_device(mdx_dih_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "quads", dih_prepare,
-                                dih_accumulate_rows);
-}
-
-int mdx_dih_accumulate(mdx_dih_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "quads", dih_prepare, dih_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the rows the
-// quads name, or NULL for the file's first n_index particles.
-int mdx_dih_accumulate_traj(mdx_dih_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "quads",
-                              dih_prepare, dih_accumulate_rows);
-}
-
-int mdx_dih_synchronize(mdx_dih_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? dih_check(h) : MDX_OK;
 }
 
 int mdx_dih_result(mdx_dih_t h, double *sums, int64_t *same, int64_t *stay)
@@ -395,10 +343,9 @@ int mdx_dih_stats(mdx_dih_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_dih_enable_timing(mdx_dih_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(dih, dih_prepare, dih_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(dih, dih_zero, dih_check)
+MDX_FRAME_SET_SLAB_FRAMES(dih, DIH_SLAB_MAX)
+MDX_FRAME_RING_PLAN(dih, dih_slab)

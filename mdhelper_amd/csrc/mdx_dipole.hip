@@ -12,8 +12,7 @@
 // slabs.
 #include "mdx_common.hpp"
 #include "mdx_dipole_device.hpp"
-#include "mdx_frame_feed.hpp"
-#include "mdx_internal.hpp"
+#include "mdx_frame_entry.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -36,6 +35,10 @@ struct mdx_dip : FrameEngine {
     double dims[3] = {0, 0, 0};
     std::vector<double> start;         // [n_points][3]: x_prev before the first frame
     DeviceBuffer d_tiles, d_tile_offsets, d_charges, d_rows, d_partial, d_prev, d_image;
+
+    int64_t rows_wanted() const { return n_points; }
+    const char *rows_noun() const { return "groups"; }
+    void free_device() { release({&d_tiles, &d_tile_offsets, &d_charges, &d_rows, &d_partial, &d_prev, &d_image}); }
 };
 
 // frames per launch: the one asked for, or what the scratch holds of frames of 24 B per tile
@@ -151,25 +154,6 @@ int mdx_dip_create(mdx_dip_t *out, int dev, int n_groups, const int64_t *n_point
     return MDX_OK;
 }
 
-int mdx_dip_destroy(mdx_dip_t h)
-{
-    if (!h)
-        return MDX_OK;
-    h->release({&h->d_tiles, &h->d_tile_offsets, &h->d_charges, &h->d_rows, &h->d_partial, &h->d_prev, &h->d_image});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_dip_reset(mdx_dip_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    h->frames_seen = 0;     // the unwrap state starts over from `start` with the next frame
-    return MDX_OK;
-}
-
 int mdx_dip_set_unwrap(mdx_dip_t h, const double *dims, const double *start)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -194,6 +178,7 @@ int mdx_dip_set_unwrap(mdx_dip_t h, const double *dims, const double *start)
     return MDX_OK;
 }
 
+// its own rule: it may be called after the first frame, which the other engines' set_slab_frames refuses
 int mdx_dip_set_slab_frames(mdx_dip_t h, int64_t frames)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -208,46 +193,6 @@ static int dip_prepare(mdx_dip *h, int64_t n_frames)
 {
     MDX_TRY(set_device(h->dev));
     return dip_grow_rows(h, n_frames);
-}
-
-int mdx_dip_plan(mdx_dip_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
-    *slab_frames = dip_slab(h);
-    *ring_frames = 0;           // no frame outlives its slab
-    return MDX_OK;
-}
-
-int mdx_dip_accumulate_device(mdx_dip_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_points, "groups",
-                                dip_prepare, dip_accumulate_rows);
-}
-
-int mdx_dip_accumulate(mdx_dip_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_points, "groups", dip_prepare, dip_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
-// concatenated groups, or NULL for the file's first n_index particles.
-int mdx_dip_accumulate_traj(mdx_dip_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_points,
-                              "groups", dip_prepare, dip_accumulate_rows);
-}
-
-int mdx_dip_synchronize(mdx_dip_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
 }
 
 int mdx_dip_result(mdx_dip_t h, double *out)
@@ -274,10 +219,9 @@ int mdx_dip_stats(mdx_dip_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return h->stats(true, launches, kernel_ms, frames);
 }
 
-int mdx_dip_enable_timing(mdx_dip_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(dip, dip_prepare, dip_accumulate_rows)
+MDX_FRAME_LIFE_CYCLE(dip)
+MDX_FRAME_RESET(dip)
+MDX_FRAME_PLAN(dip, dip_slab)

@@ -2,11 +2,12 @@
 // X_accumulate_rows(h, d_pos, src_rows, d_index, n_rows, n_frames): the staged host-memory and trajectory-file routes,
 // the particle index in HBM, the growing per-frame rows and the common part of a handle.  Host code only.
 //
-// An engine writes its own NULL checks, its preparation (set_device + grow_rows, or X_prepare: its ensure_device and
-// the sizing of its slab or ring) and X_accumulate_rows; the rest of a route is one call of
-// FrameEngine::accumulate_device / _host / _traj.  An engine whose handle touches its device only with the first frame
-// (or result) derives from LazyFrameEngine, which holds that life cycle: ensure_device, reset, synchronize, collect.
-// What the lag engines share about time is in mdx_lag_history.hpp.
+// An engine writes its preparation (set_device + grow_rows, or X_prepare: its ensure_device and the sizing of its
+// slab or ring) and X_accumulate_rows; the rest of a route is one call of FrameEngine::accumulate_device / _host /
+// _traj.  An engine whose handle touches its device only with the first frame (or result) derives from
+// LazyFrameEngine, which holds that life cycle: ensure_device, reset, synchronize, collect.  The entry points
+// themselves, their NULL checks included, come from mdx_frame_entry.hpp.  What the lag engines share about time is in
+// mdx_lag_history.hpp.
 #pragma once
 
 #include "mdx_common.hpp"
@@ -166,6 +167,23 @@ struct FrameEngine {
         return MDX_OK;
     }
 
+    // the body of X_synchronize of an engine whose handle holds its stream from create on ...
+    int synchronize()
+    {
+        MDX_TRY(set_device(dev));
+        MDX_HIP(hipStreamSynchronize(stream));
+        return MDX_OK;
+    }
+
+    // ... and of its X_reset: an unwrap state starts over from `start` with the next frame
+    int reset()
+    {
+        MDX_TRY(synchronize());
+        timer.reset();
+        frames_seen = 0;
+        return MDX_OK;
+    }
+
     // the head of X_stats; live = false: the handle has not touched its device yet
     int stats(bool live, int64_t *launches, double *kernel_ms, int64_t *frames)
     {
@@ -296,6 +314,16 @@ struct LazyFrameEngine : FrameEngine {
         ready = true;
         return MDX_OK;
     }
+
+    // a handle that never touched its device has nothing to give back
+    void release(std::initializer_list<DeviceBuffer *> own)
+    {
+        if (stream)
+            FrameEngine::release(own);
+    }
+
+    // the host counters a reset clears: an engine that has some declares its own
+    void clear_counters() {}
 
     // the body of X_reset, after the engine has cleared its own host counters; zero(h): the device side starts over
     template <typename H>

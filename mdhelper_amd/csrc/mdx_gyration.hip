@@ -11,7 +11,7 @@
 // of frames go to a scratch array that a second, small kernel averages per (frame, group).  Nothing is added with
 // atomics, so the rows repeat bit for bit whatever route the frames take and however they are split into calls.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_gyration_device.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
@@ -49,6 +49,15 @@ struct mdx_gyr : FrameEngine {
     DeviceBuffer d_units, d_masses, d_chain_mass, d_chain_offsets, d_rows, d_chain_out, d_centres, d_images, d_prev,
         d_image;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
+
+    int64_t rows_wanted() const { return mol.rows_wanted(n_points); }
+    const char *rows_noun() const { return mol.rows_noun(); }
+    void free_device()
+    {
+        release({&d_units, &d_masses, &d_chain_mass, &d_chain_offsets, &d_rows, &d_chain_out, &d_centres, &d_images,
+                 &d_prev, &d_image});
+        mol.recycle();
+    }
 };
 
 static int gyr_grow_rows(mdx_gyr *h, int64_t more)
@@ -220,27 +229,6 @@ int mdx_gyr_slab_frames(int64_t n_chains, int64_t n_points, int grouped, int unw
     return MDX_OK;
 }
 
-int mdx_gyr_destroy(mdx_gyr_t h)
-{
-    if (!h)
-        return MDX_OK;
-    h->release({&h->d_units, &h->d_masses, &h->d_chain_mass, &h->d_chain_offsets, &h->d_rows, &h->d_chain_out,
-                &h->d_centres, &h->d_images, &h->d_prev, &h->d_image});
-    h->mol.recycle();
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_gyr_reset(mdx_gyr_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    h->frames_seen = 0;     // the unwrap state starts over from `start` with the next frame
-    return MDX_OK;
-}
-
 int mdx_gyr_set_grouping(mdx_gyr_t h, int64_t n_molecules, const int64_t *offsets, const double *masses)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -283,39 +271,6 @@ static int gyr_prepare(mdx_gyr *h, int64_t n_frames)
     return gyr_grow_rows(h, n_frames);
 }
 
-int mdx_gyr_accumulate_device(mdx_gyr_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->mol.rows_wanted(h->n_points),
-                                h->mol.rows_noun(), gyr_prepare, gyr_accumulate_rows);
-}
-
-int mdx_gyr_accumulate(mdx_gyr_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), gyr_prepare,
-                              gyr_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
-// concatenated groups (rows of the grouping when one is set), or NULL for the file's first n_index particles.
-int mdx_gyr_accumulate_traj(mdx_gyr_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index,
-                              h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), gyr_prepare, gyr_accumulate_rows);
-}
-
-int mdx_gyr_synchronize(mdx_gyr_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
-}
-
 int mdx_gyr_result(mdx_gyr_t h, double *out)
 {
     MDX_REQUIRE(h && out, "NULL argument");
@@ -340,10 +295,8 @@ int mdx_gyr_stats(mdx_gyr_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return h->stats(true, launches, kernel_ms, frames);
 }
 
-int mdx_gyr_enable_timing(mdx_gyr_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(gyr, gyr_prepare, gyr_accumulate_rows)
+MDX_FRAME_LIFE_CYCLE(gyr)
+MDX_FRAME_RESET(gyr)

@@ -15,6 +15,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_hbond_device.hpp"
@@ -52,6 +53,16 @@ struct mdx_hb : LazyFrameEngine {
     DeviceBuffer d_bonds, d_slab, d_tables, d_inner, d_geometry;
 
     int64_t geometry_words() const { return n_r + n_c + lists.max_nb + 2; }
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "tables"; }
+    int64_t ring_lag() const { return lags.max_lag; }
+    void clear_counters() { lists.max_row = 0; }
+    void free_device()
+    {
+        release({&lags.d_lags, &walk.d_sums, &d_bonds, &lists.d_ctl, &d_slab, &lists.d_len, &lists.d_list, &walk.d_mask,
+                 &d_tables, &d_inner, &d_geometry});
+    }
 };
 
 // bytes a frame takes: its gathered rows while it is in flight, its lists and masks while it is in the rings
@@ -261,67 +272,6 @@ int mdx_hb_set_bins(mdx_hb_t h, int64_t n_r, const double *r2_thresholds, int64_
     return MDX_OK;
 }
 
-int mdx_hb_destroy(mdx_hb_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->lags.d_lags, &h->walk.d_sums, &h->d_bonds, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
-                    &h->lists.d_list, &h->walk.d_mask, &h->d_tables, &h->d_inner, &h->d_geometry});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_hb_reset(mdx_hb_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->lists.max_row = 0;
-    return h->reset(hb_zero);   // frames_seen = 0: the history starts over with the next frame
-}
-
-int mdx_hb_set_slab_frames(mdx_hb_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, HB_SLAB_MAX, "mdx_hb_set_slab_frames");
-}
-
-int mdx_hb_plan(mdx_hb_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->lags.max_lag, hb_slab(h), slab_frames, ring_frames);
-}
-
-int mdx_hb_accumulate_device(mdx_hb_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames, const int32_t *index,
-                             int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "tables", hb_prepare,
-                                hb_accumulate_rows);
-}
-
-int mdx_hb_accumulate(mdx_hb_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "tables", hb_prepare, hb_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
-// the file's first n_index particles.
-int mdx_hb_accumulate_traj(mdx_hb_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames, const int32_t *index,
-                           int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "tables",
-                              hb_prepare, hb_accumulate_rows);
-}
-
-int mdx_hb_synchronize(mdx_hb_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? hb_check_rows(h) : MDX_OK;
-}
-
 int mdx_hb_result(mdx_hb_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts)
 {
     MDX_REQUIRE(h && intermittent && continuous && origin_counts, "NULL argument");
@@ -378,10 +328,9 @@ int mdx_hb_stats(mdx_hb_t h, int64_t *launches, double *kernel_ms, int64_t *fram
     return MDX_OK;
 }
 
-int mdx_hb_enable_timing(mdx_hb_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(hb, hb_prepare, hb_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(hb, hb_zero, hb_check_rows)
+MDX_FRAME_SET_SLAB_FRAMES(hb, HB_SLAB_MAX)
+MDX_FRAME_RING_PLAN(hb, hb_slab)

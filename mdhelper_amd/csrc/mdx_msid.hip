@@ -11,7 +11,7 @@
 // writes rows[frame][2 sum_g (N_g - 1)] in HBM.  Nothing is added with atomics, so the rows repeat bit for bit
 // whatever route the frames take and however they are split into calls or slabs.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_msid_device.hpp"
@@ -69,6 +69,14 @@ struct mdx_msid : FrameEngine {
     std::vector<MsidGroup> groups;     // (the chains of group g start at point sum_{h<g} M_h N_h)
     DeviceBuffer d_units, d_groups, d_rows, d_partials, d_points, d_images, d_prev, d_image;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
+
+    int64_t rows_wanted() const { return mol.rows_wanted(n_points); }
+    const char *rows_noun() const { return mol.rows_noun(); }
+    void free_device()
+    {
+        release({&d_units, &d_groups, &d_rows, &d_partials, &d_points, &d_images, &d_prev, &d_image});
+        mol.recycle();
+    }
 };
 
 static int msid_grow_rows(mdx_msid *h, int64_t more, bool exact = false)
@@ -232,27 +240,6 @@ int mdx_msid_slab_frames(int n_groups, const int64_t *n_chains, const int64_t *n
     return MDX_OK;
 }
 
-int mdx_msid_destroy(mdx_msid_t h)
-{
-    if (!h)
-        return MDX_OK;
-    h->release({&h->d_units, &h->d_groups, &h->d_rows, &h->d_partials, &h->d_points, &h->d_images, &h->d_prev,
-                &h->d_image});
-    h->mol.recycle();
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_msid_reset(mdx_msid_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    h->frames_seen = 0;     // the unwrap state starts over from `start` with the next frame
-    return MDX_OK;
-}
-
 int mdx_msid_reserve(mdx_msid_t h, int64_t n_frames)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -320,39 +307,6 @@ static int msid_prepare(mdx_msid *h, int64_t n_frames)
     return msid_grow_rows(h, n_frames);
 }
 
-int mdx_msid_accumulate_device(mdx_msid_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                               const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->mol.rows_wanted(h->n_points),
-                                h->mol.rows_noun(), msid_prepare, msid_accumulate_rows);
-}
-
-int mdx_msid_accumulate(mdx_msid_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), msid_prepare,
-                              msid_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
-// concatenated groups (rows of the grouping when one is set), or NULL for the file's first n_index particles.
-int mdx_msid_accumulate_traj(mdx_msid_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                             const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index,
-                              h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), msid_prepare, msid_accumulate_rows);
-}
-
-int mdx_msid_synchronize(mdx_msid_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
-}
-
 int mdx_msid_result(mdx_msid_t h, double *out)
 {
     MDX_REQUIRE(h && out, "NULL argument");
@@ -371,10 +325,8 @@ int mdx_msid_stats(mdx_msid_t h, int64_t *launches, double *kernel_ms, int64_t *
     return h->stats(true, launches, kernel_ms, frames);
 }
 
-int mdx_msid_enable_timing(mdx_msid_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(msid, msid_prepare, msid_accumulate_rows)
+MDX_FRAME_LIFE_CYCLE(msid)
+MDX_FRAME_RESET(msid)

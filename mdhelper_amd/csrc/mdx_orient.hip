@@ -13,6 +13,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_orient_device.hpp"
@@ -43,6 +44,16 @@ struct mdx_ori : LazyFrameEngine {
     std::vector<int64_t> offsets;
     // d_frame_sums: double [frames seen][n_groups][6]; d_part: double [slab][tiles][6]; d_ctl: uint64 degenerate
     DeviceBuffer d_tiles, d_tile_offsets, d_pairs, d_offsets, d_acc, d_sums, d_hist, d_part, d_frame_sums, d_ctl;
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "pairs"; }
+    int64_t ring_lag() const { return lags.max_lag; }
+    void clear_counters() { evaluations = degenerate = 0; }
+    void free_device()
+    {
+        release({&d_tiles, &d_tile_offsets, &d_pairs, &d_offsets, &lags.d_lags, &d_acc, &d_sums, &d_hist, &d_part,
+                 &d_frame_sums, &d_ctl});
+    }
 };
 
 static int64_t ori_slab(const mdx_ori *h)
@@ -198,25 +209,6 @@ int mdx_ori_create(mdx_ori_t *out, int dev, int n_groups, const int64_t *n_vecto
     return MDX_OK;
 }
 
-int mdx_ori_destroy(mdx_ori_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_tiles, &h->d_tile_offsets, &h->d_pairs, &h->d_offsets, &h->lags.d_lags, &h->d_acc,
-                    &h->d_sums, &h->d_hist, &h->d_part, &h->d_frame_sums, &h->d_ctl});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_ori_reset(mdx_ori_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->evaluations = 0;
-    h->degenerate = 0;
-    return h->reset(ori_zero);  // frames_seen = 0: the history starts over with the next frame
-}
-
 int mdx_ori_set_box(mdx_ori_t h, const double *dims)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -230,49 +222,6 @@ int mdx_ori_set_box(mdx_ori_t h, const double *dims)
         h->box.inv[c] = dims ? 1.0 / dims[c] : 0.0;
     }
     return MDX_OK;
-}
-
-int mdx_ori_set_slab_frames(mdx_ori_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, ORI_SLAB_MAX, "mdx_ori_set_slab_frames");
-}
-
-int mdx_ori_plan(mdx_ori_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->lags.max_lag, ori_slab(h), slab_frames, ring_frames);
-}
-
-int mdx_ori_accumulate_device(mdx_ori_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "pairs", ori_prepare,
-                                ori_accumulate_rows);
-}
-
-int mdx_ori_accumulate(mdx_ori_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "pairs", ori_prepare, ori_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the rows the
-// pairs name, or NULL for the file's first n_index particles.
-int mdx_ori_accumulate_traj(mdx_ori_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "pairs",
-                              ori_prepare, ori_accumulate_rows);
-}
-
-int mdx_ori_synchronize(mdx_ori_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? ori_check(h) : MDX_OK;
 }
 
 int mdx_ori_result(mdx_ori_t h, double *sums)
@@ -324,10 +273,9 @@ int mdx_ori_stats(mdx_ori_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_ori_enable_timing(mdx_ori_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(ori, ori_prepare, ori_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(ori, ori_zero, ori_check)
+MDX_FRAME_SET_SLAB_FRAMES(ori, ORI_SLAB_MAX)
+MDX_FRAME_RING_PLAN(ori, ori_slab)

@@ -11,7 +11,7 @@
 // atomics (uint64 totals when averaging, a uint32 row per frame otherwise), so results repeat bit for bit.  When
 // the slots do not fit, the replica count steps down and finally the kernels bin straight into global memory.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_profile_device.hpp"
@@ -57,6 +57,14 @@ struct mdx_prof : FrameEngine {
     int rc_group = -1;
     int64_t rc_lo = 0, rc_hi = 0;
     double rc_mass = 0.0, rc_target[3] = {0, 0, 0};
+
+    int64_t rows_wanted() const { return mol.rows_wanted(n_points); }
+    const char *rows_noun() const { return mol.rows_noun(); }
+    void free_device()
+    {
+        release({&d_offsets, &d_total, &d_rows, &d_centres, &d_images, &d_shift, &d_prev, &d_image, &d_rmass});
+        mol.recycle();
+    }
 };
 
 // most LDS copies that fit, at most `limit` of them (limit < 0: no limit, 0: global atomics); -1: global atomics
@@ -301,26 +309,13 @@ int mdx_prof_slab_frames(int64_t n_points, int grouped, int recenter, int64_t *s
     return MDX_OK;
 }
 
-int mdx_prof_destroy(mdx_prof_t h)
-{
-    if (!h)
-        return MDX_OK;
-    h->release({&h->d_offsets, &h->d_total, &h->d_rows, &h->d_centres, &h->d_images, &h->d_shift, &h->d_prev,
-                &h->d_image, &h->d_rmass});
-    h->mol.recycle();
-    delete h;
-    return MDX_OK;
-}
-
+// its own rule: the totals start over too
 int mdx_prof_reset(mdx_prof_t h)
 {
     MDX_REQUIRE(h, "NULL handle");
     MDX_TRY(set_device(h->dev));
     MDX_HIP(hipMemsetAsync(h->d_total.ptr, 0, size_t(8) * h->plan.n_slots, h->stream));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    h->frames_seen = 0;     // the unwrap state starts over with the next frame
-    return MDX_OK;
+    return h->reset();      // the unwrap state starts over with the next frame
 }
 
 int mdx_prof_set_grouping(mdx_prof_t h, int64_t n_molecules, const int64_t *offsets, const double *masses)
@@ -388,39 +383,6 @@ static int prof_prepare(mdx_prof *h, int64_t n_frames)
     return prof_grow_rows(h, n_frames);
 }
 
-int mdx_prof_accumulate_device(mdx_prof_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                               const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->mol.rows_wanted(h->n_points),
-                                h->mol.rows_noun(), prof_prepare, prof_accumulate_rows);
-}
-
-int mdx_prof_accumulate(mdx_prof_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), prof_prepare,
-                              prof_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
-// concatenated groups (rows of the grouping when one is set), or NULL for the file's first n_index particles.
-int mdx_prof_accumulate_traj(mdx_prof_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                             const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index,
-                              h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), prof_prepare, prof_accumulate_rows);
-}
-
-int mdx_prof_synchronize(mdx_prof_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
-}
-
 int mdx_prof_counts(mdx_prof_t h, int axis_slot, int64_t *out)
 {
     MDX_REQUIRE(h && out, "NULL argument");
@@ -457,10 +419,7 @@ int mdx_prof_stats(mdx_prof_t h, int64_t *launches, double *kernel_ms, int64_t *
     return MDX_OK;
 }
 
-int mdx_prof_enable_timing(mdx_prof_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(prof, prof_prepare, prof_accumulate_rows)
+MDX_FRAME_LIFE_CYCLE(prof)

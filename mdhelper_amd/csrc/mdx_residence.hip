@@ -12,6 +12,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_residence_device.hpp"
@@ -39,6 +40,16 @@ struct mdx_prs : LazyFrameEngine {
     SurvivalWalk walk;
     double rc2 = 0.0;
     DeviceBuffer d_contacts, d_slab;    // d_contacts: uint64, one per frame seen
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "sets"; }
+    int64_t ring_lag() const { return lags.max_lag; }
+    void clear_counters() { lists.max_row = 0; }
+    void free_device()
+    {
+        release({&lags.d_lags, &walk.d_sums, &d_contacts, &lists.d_ctl, &d_slab, &lists.d_len, &lists.d_list,
+                 &walk.d_mask});
+    }
 };
 
 // bytes a frame takes: its gathered rows while it is in flight, its lists and masks while it is in the rings
@@ -167,67 +178,6 @@ int mdx_prs_create(mdx_prs_t *out, int dev, int64_t n1, int64_t n2, int same, do
     return MDX_OK;
 }
 
-int mdx_prs_destroy(mdx_prs_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->lags.d_lags, &h->walk.d_sums, &h->d_contacts, &h->lists.d_ctl, &h->d_slab, &h->lists.d_len,
-                    &h->lists.d_list, &h->walk.d_mask});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_prs_reset(mdx_prs_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->lists.max_row = 0;
-    return h->reset(prs_zero);  // frames_seen = 0: the history starts over with the next frame
-}
-
-int mdx_prs_set_slab_frames(mdx_prs_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, PRS_SLAB_MAX, "mdx_prs_set_slab_frames");
-}
-
-int mdx_prs_plan(mdx_prs_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->lags.max_lag, prs_slab(h), slab_frames, ring_frames);
-}
-
-int mdx_prs_accumulate_device(mdx_prs_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "sets", prs_prepare,
-                                prs_accumulate_rows);
-}
-
-int mdx_prs_accumulate(mdx_prs_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "sets", prs_prepare, prs_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
-// the file's first n_index particles.
-int mdx_prs_accumulate_traj(mdx_prs_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "sets",
-                              prs_prepare, prs_accumulate_rows);
-}
-
-int mdx_prs_synchronize(mdx_prs_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(h->synchronize());
-    return h->ready ? prs_check_rows(h) : MDX_OK;
-}
-
 int mdx_prs_result(mdx_prs_t h, int64_t *intermittent, int64_t *continuous, int64_t *origin_counts)
 {
     MDX_REQUIRE(h && intermittent && continuous && origin_counts, "NULL argument");
@@ -264,10 +214,9 @@ int mdx_prs_stats(mdx_prs_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_prs_enable_timing(mdx_prs_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(prs, prs_prepare, prs_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(prs, prs_zero, prs_check_rows)
+MDX_FRAME_SET_SLAB_FRAMES(prs, PRS_SLAB_MAX)
+MDX_FRAME_RING_PLAN(prs, prs_slab)

@@ -12,7 +12,7 @@
 // added with atomics and no sum is split across lanes, so the rows repeat bit for bit whatever route the frames
 // take and however they are split into calls.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_molecules.hpp"
 #include "mdx_points_device.hpp"
@@ -50,6 +50,14 @@ struct mdx_rouse : FrameEngine {
     std::vector<double> start;         // [n_points][3]: x_prev before the first frame
     DeviceBuffer d_units, d_weights, d_rows, d_centres, d_images, d_prev, d_image;
     MoleculeStage mol;                 // offsets / masses of the grouping; the centres are formed in float64 here
+
+    int64_t rows_wanted() const { return mol.rows_wanted(n_points); }
+    const char *rows_noun() const { return mol.rows_noun(); }
+    void free_device()
+    {
+        release({&d_units, &d_weights, &d_rows, &d_centres, &d_images, &d_prev, &d_image});
+        mol.recycle();
+    }
 };
 
 static int rouse_grow_rows(mdx_rouse *h, int64_t more, bool exact = false)
@@ -206,26 +214,6 @@ int mdx_rouse_slab_frames(int64_t n_points, int grouped, int unwrap, int64_t *sl
     return MDX_OK;
 }
 
-int mdx_rouse_destroy(mdx_rouse_t h)
-{
-    if (!h)
-        return MDX_OK;
-    h->release({&h->d_units, &h->d_weights, &h->d_rows, &h->d_centres, &h->d_images, &h->d_prev, &h->d_image});
-    h->mol.recycle();
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_rouse_reset(mdx_rouse_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    h->timer.reset();
-    h->frames_seen = 0;     // the unwrap state starts over from `start` with the next frame
-    return MDX_OK;
-}
-
 int mdx_rouse_reserve(mdx_rouse_t h, int64_t n_frames)
 {
     MDX_REQUIRE(h, "NULL handle");
@@ -276,40 +264,6 @@ static int rouse_prepare(mdx_rouse *h, int64_t n_frames)
     return rouse_grow_rows(h, n_frames);
 }
 
-int mdx_rouse_accumulate_device(mdx_rouse_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                                const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->mol.rows_wanted(h->n_points),
-                                h->mol.rows_noun(), rouse_prepare, rouse_accumulate_rows);
-}
-
-int mdx_rouse_accumulate(mdx_rouse_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), rouse_prepare,
-                              rouse_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
-// concatenated groups (rows of the grouping when one is set), or NULL for the file's first n_index particles.
-int mdx_rouse_accumulate_traj(mdx_rouse_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index,
-                              h->mol.rows_wanted(h->n_points), h->mol.rows_noun(), rouse_prepare,
-                              rouse_accumulate_rows);
-}
-
-int mdx_rouse_synchronize(mdx_rouse_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    MDX_TRY(set_device(h->dev));
-    MDX_HIP(hipStreamSynchronize(h->stream));
-    return MDX_OK;
-}
-
 int mdx_rouse_result(mdx_rouse_t h, double *out)
 {
     MDX_REQUIRE(h && out, "NULL argument");
@@ -340,10 +294,8 @@ int mdx_rouse_stats(mdx_rouse_t h, int64_t *launches, double *kernel_ms, int64_t
     return h->stats(true, launches, kernel_ms, frames);
 }
 
-int mdx_rouse_enable_timing(mdx_rouse_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(rouse, rouse_prepare, rouse_accumulate_rows)
+MDX_FRAME_LIFE_CYCLE(rouse)
+MDX_FRAME_RESET(rouse)

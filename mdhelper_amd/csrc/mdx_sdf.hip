@@ -10,8 +10,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
-#include "mdx_frame_feed.hpp"
-#include "mdx_internal.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_pairs_host.hpp"
 #include "mdx_sdf_device.hpp"
 
@@ -42,6 +41,9 @@ struct mdx_sdf : LazyFrameEngine {
     DeviceBuffer d_tables, d_edges, d_counts, d_inside, d_slab;
 
     int64_t cells() const { return int64_t(n_groups) * axes.n[0] * axes.n[1] * axes.n[2]; }
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "tables"; }
+    void free_device() { release({&d_tables, &d_edges, &d_counts, &d_inside, &d_slab}); }
 };
 
 static int64_t sdf_slab(const mdx_sdf *h)
@@ -247,66 +249,6 @@ int mdx_sdf_set_bins(mdx_sdf_t h, int64_t nx, const double *ex, int64_t ny, cons
     return MDX_OK;
 }
 
-int mdx_sdf_destroy(mdx_sdf_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_tables, &h->d_edges, &h->d_counts, &h->d_inside, &h->d_slab});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_sdf_reset(mdx_sdf_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->reset(sdf_zero);
-}
-
-int mdx_sdf_set_slab_frames(mdx_sdf_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, SDF_SLAB_MAX, "mdx_sdf_set_slab_frames");
-}
-
-int mdx_sdf_plan(mdx_sdf_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h && slab_frames && ring_frames, "NULL argument");
-    *slab_frames = sdf_slab(h);
-    *ring_frames = 0;           // no frame outlives its slab
-    return MDX_OK;
-}
-
-int mdx_sdf_accumulate_device(mdx_sdf_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames, const int32_t *index,
-                              int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "tables", sdf_prepare,
-                                sdf_accumulate_rows);
-}
-
-int mdx_sdf_accumulate(mdx_sdf_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "tables", sdf_prepare, sdf_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in incoming order, or NULL for
-// the file's first n_index particles.
-int mdx_sdf_accumulate_traj(mdx_sdf_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "tables",
-                              sdf_prepare, sdf_accumulate_rows);
-}
-
-int mdx_sdf_synchronize(mdx_sdf_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->synchronize();
-}
-
 int mdx_sdf_result(mdx_sdf_t h, int64_t *counts)
 {
     MDX_REQUIRE(h && counts, "NULL argument");
@@ -343,10 +285,9 @@ int mdx_sdf_stats(mdx_sdf_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_sdf_enable_timing(mdx_sdf_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(sdf, sdf_prepare, sdf_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(sdf, sdf_zero, unchecked)
+MDX_FRAME_SET_SLAB_FRAMES(sdf, SDF_SLAB_MAX)
+MDX_FRAME_PLAN(sdf, sdf_slab)

@@ -12,6 +12,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_vanhove_device.hpp"
@@ -40,6 +41,16 @@ struct mdx_vh : LazyFrameEngine {
     std::vector<int64_t> offsets;
     std::vector<double> edges;
     DeviceBuffer d_tiles, d_offsets, d_edges, d_counts, d_acc, d_moments;
+
+    int64_t rows_wanted() const { return n_points; }
+    const char *rows_noun() const { return "groups"; }
+    int64_t ring_lag() const { return lags.max_lag; }
+    void clear_counters() { evaluations = 0; }
+    void free_device()
+    {
+        release({&d_tiles, &d_offsets, &lags.d_lags, &d_edges, &d_counts, &d_acc, &d_moments, &hist.d_hist,
+                 &hist.d_prev, &hist.d_image});
+    }
 };
 
 static int64_t vh_slab(const mdx_vh *h)
@@ -170,70 +181,10 @@ int mdx_vh_create(mdx_vh_t *out, int dev, int n_groups, const int64_t *n_points,
     return MDX_OK;
 }
 
-int mdx_vh_destroy(mdx_vh_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->d_tiles, &h->d_offsets, &h->lags.d_lags, &h->d_edges, &h->d_counts, &h->d_acc, &h->d_moments,
-                    &h->hist.d_hist, &h->hist.d_prev, &h->hist.d_image});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_vh_reset(mdx_vh_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->evaluations = 0;
-    return h->reset(vh_zero);   // frames_seen = 0: the history and the unwrap state start over with the next frame
-}
-
 int mdx_vh_set_unwrap(mdx_vh_t h, const double *dims)
 {
     MDX_REQUIRE(h, "NULL handle");
     return h->hist.set_unwrap(dims, h->frames_seen, "mdx_vh_set_unwrap");
-}
-
-int mdx_vh_set_slab_frames(mdx_vh_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, VH_SLAB_MAX, "mdx_vh_set_slab_frames");
-}
-
-int mdx_vh_plan(mdx_vh_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->lags.max_lag, vh_slab(h), slab_frames, ring_frames);
-}
-
-int mdx_vh_accumulate_device(mdx_vh_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                             const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_points, "groups",
-                                vh_prepare, vh_accumulate_rows);
-}
-
-int mdx_vh_accumulate(mdx_vh_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_points, "groups", vh_prepare, vh_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices in the order of the
-// concatenated groups, or NULL for the file's first n_index particles.
-int mdx_vh_accumulate_traj(mdx_vh_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                           const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_points,
-                              "groups", vh_prepare, vh_accumulate_rows);
-}
-
-int mdx_vh_synchronize(mdx_vh_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->synchronize();
 }
 
 int mdx_vh_result(mdx_vh_t h, int64_t *counts, double *moments)
@@ -270,10 +221,9 @@ int mdx_vh_stats(mdx_vh_t h, int64_t *launches, double *kernel_ms, int64_t *fram
     return MDX_OK;
 }
 
-int mdx_vh_enable_timing(mdx_vh_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(vh, vh_prepare, vh_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(vh, vh_zero, unchecked)
+MDX_FRAME_SET_SLAB_FRAMES(vh, VH_SLAB_MAX)
+MDX_FRAME_RING_PLAN(vh, vh_slab)

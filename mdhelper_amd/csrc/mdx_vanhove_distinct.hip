@@ -11,6 +11,7 @@
 //
 // A handle touches its device with the first frame (or result): creating one, and every argument error, needs none.
 #include "mdx_common.hpp"
+#include "mdx_frame_entry.hpp"
 #include "mdx_internal.hpp"
 #include "mdx_lag_history.hpp"
 #include "mdx_vanhove_distinct_device.hpp"
@@ -38,6 +39,12 @@ struct mdx_vhd : LazyFrameEngine {
     double inv_width = 0.0, r2_lo = 0.0, r2_hi = 0.0;
     std::vector<double> edges;
     DeviceBuffer d_edges, d_counts, d_ring;
+
+    int64_t rows_wanted() const { return n_rows; }
+    const char *rows_noun() const { return "sets"; }
+    int64_t ring_lag() const { return lags.max_lag; }
+    void clear_counters() { evaluations = 0; }
+    void free_device() { release({&lags.d_lags, &d_edges, &d_counts, &d_ring}); }
 };
 
 static int64_t vhd_slab(const mdx_vhd *h)
@@ -159,65 +166,6 @@ int mdx_vhd_create(mdx_vhd_t *out, int dev, int64_t n1, int64_t n2, int same, in
     return MDX_OK;
 }
 
-int mdx_vhd_destroy(mdx_vhd_t h)
-{
-    if (!h)
-        return MDX_OK;
-    if (h->stream)
-        h->release({&h->lags.d_lags, &h->d_edges, &h->d_counts, &h->d_ring});
-    delete h;
-    return MDX_OK;
-}
-
-int mdx_vhd_reset(mdx_vhd_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    h->evaluations = 0;
-    return h->reset(vhd_zero);  // frames_seen = 0: the history starts over with the next frame
-}
-
-int mdx_vhd_set_slab_frames(mdx_vhd_t h, int64_t frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->set_slab_frames(frames, VHD_SLAB_MAX, "mdx_vhd_set_slab_frames");
-}
-
-int mdx_vhd_plan(mdx_vhd_t h, int64_t *slab_frames, int64_t *ring_frames)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->ring.plan(h->frames_seen, h->lags.max_lag, vhd_slab(h), slab_frames, ring_frames);
-}
-
-int mdx_vhd_accumulate_device(mdx_vhd_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
-                              const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && d_pos, "NULL argument");
-    return h->accumulate_device(d_pos, n_atoms, n_frames, index, n_index, h->n_rows, "sets", vhd_prepare,
-                                vhd_accumulate_rows);
-}
-
-int mdx_vhd_accumulate(mdx_vhd_t h, const float *pos, int64_t n, int64_t n_frames)
-{
-    MDX_REQUIRE(h && pos, "NULL argument");
-    return h->accumulate_host(pos, n, n_frames, h->n_rows, "sets", vhd_prepare, vhd_accumulate_rows);
-}
-
-// Frames straight from a trajectory file.  index: host int32[n_index] particle indices, set 1 then set 2, or NULL for
-// the file's first n_index particles.
-int mdx_vhd_accumulate_traj(mdx_vhd_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
-                            const int32_t *index, int64_t n_index)
-{
-    MDX_REQUIRE(h && traj, "NULL handle");
-    return h->accumulate_traj(mdx_traj_internal(traj), frames, n_frames, index, n_index, h->n_rows, "sets",
-                              vhd_prepare, vhd_accumulate_rows);
-}
-
-int mdx_vhd_synchronize(mdx_vhd_t h)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->synchronize();
-}
-
 int mdx_vhd_result(mdx_vhd_t h, int64_t *counts)
 {
     MDX_REQUIRE(h && counts, "NULL argument");
@@ -236,10 +184,9 @@ int mdx_vhd_stats(mdx_vhd_t h, int64_t *launches, double *kernel_ms, int64_t *fr
     return MDX_OK;
 }
 
-int mdx_vhd_enable_timing(mdx_vhd_t h, int on)
-{
-    MDX_REQUIRE(h, "NULL handle");
-    return h->enable_timing(on);
-}
-
 }  // extern "C"
+
+MDX_FRAME_ROUTES(vhd, vhd_prepare, vhd_accumulate_rows)
+MDX_LAZY_FRAME_LIFE_CYCLE(vhd, vhd_zero, unchecked)
+MDX_FRAME_SET_SLAB_FRAMES(vhd, VHD_SLAB_MAX)
+MDX_FRAME_RING_PLAN(vhd, vhd_slab)
