@@ -1147,6 +1147,76 @@ int mdx_boo_stats(mdx_boo_t h, int64_t *launches, double *kernel_ms, int64_t *fr
                   int64_t *bonds, int64_t *degenerate, int64_t *max_row);
 int mdx_boo_enable_timing(mdx_boo_t h, int on);
 
+/* ---- tetrahedral order: q and S_k over the four nearest of the n_nearest nearest neighbours of every center --------
+ * Rows, box and pair arithmetic as for mdx_boo_*.  Candidate j is in range of center i iff r2 <= cutoff^2 (cutoff *
+ * cutoff formed once; a NaN r2 never is).  The candidates of a center are ordered by ascending r2 as float64, ties by
+ * ascending j; its neighbours are the first min(n_nearest, m_i) of the m_i in range, 4 <= n_nearest <= 8: a function
+ * of the frame alone.  A center with m_i < 4 is short: its values are NaN, it is not binned and adds nothing to the
+ * sums.  For the others, with a, b = 0 ... 3 numbering the four nearest, in float64 with separate multiply and add:
+ *     cos_ab = ((w_ax*w_bx + w_ay*w_by) + w_az*w_bz) / sqrt(r2_a * r2_b)
+ *     q   = 1 - 0.375 * sum over (0,1) (0,2) (1,2) (0,3) (1,3) (2,3) of (cos_ab + 1.0 / 3.0)^2
+ *     S_k = 1 - (sum_a (r_a - rbar)^2) / (12 * rbar * rbar),  r_a = sqrt(r2_a),
+ *     rbar = (((r_0 + r_1) + r_2) + r_3) * 0.25
+ * (every operation and its order: csrc/mdx_tetrahedral_device.hpp).  q_edges [q_bins + 1] and s_edges [s_bins + 1]:
+ * float64, strictly increasing, each counted by numpy.histogram's rule as the edges of mdx_boo_create.
+ * distance_thresholds: float64 [distance_bins + 1], strictly increasing thresholds of r2; the r2 of the neighbour of
+ * every rank a = 0 ... n_nearest - 1 is counted against them by the same rule, short centers included.  dims: float64
+ * [3] lengths of one constant orthorhombic box; the cutoff may not exceed half the shortest.  One of the four nearest
+ * of a center that is not short on top of it (r2 == 0) has no direction; after that mdx_tet_synchronize,
+ * mdx_tet_result, mdx_tet_frames and mdx_tet_values fail with MDX_ERR_INVALID_VALUE until mdx_tet_reset.  A short
+ * center has no q, so a candidate on top of it is not an error: it is counted in found and at distance 0.  No floating-point atomics are used: every
+ * result is bit-identical across the three input routes, across any split of the frames into calls, slabs or
+ * candidate chunks, and after a reset.  Every (center, candidate) pair is evaluated, there is no cell list.  A handle
+ * touches its device with the first frame: mdx_tet_create and every argument error (MDX_ERR_INVALID_VALUE) need
+ * none. */
+typedef struct mdx_tet *mdx_tet_t;
+int mdx_tet_create(mdx_tet_t *out, int dev, int64_t n_centers, int64_t n_neighbors, int same, int n_nearest,
+                   double cutoff, int64_t q_bins, const double *q_edges, int64_t s_bins, const double *s_edges,
+                   int64_t distance_bins, const double *distance_thresholds, const double *dims, int keep_values);
+int mdx_tet_destroy(mdx_tet_t h);
+/* Forgets the frames seen, the neighbours without a direction and the kept values, and zeroes the results. */
+int mdx_tet_reset(mdx_tet_t h);
+/* As mdx_boo_set_slab_frames. */
+int mdx_tet_set_slab_frames(mdx_tet_t h, int64_t frames);
+/* Candidates a block of the selection kernel walks: a multiple of 256; 0 restores the plan's choice.  The results do
+ * not depend on it.  Only before the first frame. */
+int mdx_tet_set_chunk(mdx_tet_t h, int64_t candidates);
+/* Advisory, for planning and for tests of the rule without a device; no other entry point needs it.  The plan's
+ * choice for a launch of `frames` frames on a device of compute_units compute units: every candidate in
+ * one chunk where ceil(n_centers / 256) * frames >= compute_units, else the candidates in ceil(compute_units /
+ * (ceil(n_centers / 256) * frames)) parts rounded up to multiples of 256.  Needs no handle and no device. */
+int mdx_tet_chunk_for(int64_t n_centers, int64_t n_neighbors, int64_t frames, int64_t compute_units, int64_t *chunk);
+/* As mdx_dip_plan, and chunk: the candidates per block of a launch of slab_frames frames.  Where no chunk is set it
+ * reads the compute units of the handle's device. */
+int mdx_tet_plan(mdx_tet_t h, int64_t *slab_frames, int64_t *ring_frames, int64_t *chunk);
+/* Host float32 [n_frames][n][3] through the pinned ring; n = the rows of a frame. */
+int mdx_tet_accumulate(mdx_tet_t h, const float *pos, int64_t n, int64_t n_frames);
+/* Frames already in HBM, float32 [n_frames][n_atoms][3]; index: host int32[n_index] rows of a frame in incoming
+ * order, or NULL for all n_atoms rows.  Asynchronous (mdx_tet_synchronize), except with keep_values: every slab then
+ * ends in a wait for the stream and two copies of its values and neighbours to the host. */
+int mdx_tet_accumulate_device(mdx_tet_t h, const float *d_pos, int64_t n_atoms, int64_t n_frames,
+                              const int32_t *index, int64_t n_index);
+int mdx_tet_accumulate_traj(mdx_tet_t h, mdx_traj_t traj, const int64_t *frames, int64_t n_frames,
+                            const int32_t *index, int64_t n_index);
+int mdx_tet_synchronize(mdx_tet_t h);
+/* q_counts: int64 [q_bins]; s_counts: int64 [s_bins]; outside: int64 [2] (q, S_k); distance_counts: int64
+ * [n_nearest][distance_bins]; distance_outside: int64 [n_nearest]; found: int64 [n_nearest + 1], the (frame, center)
+ * cases with min(m_i, n_nearest) = m. */
+int mdx_tet_result(mdx_tet_t h, int64_t *q_counts, int64_t *s_counts, int64_t *outside, int64_t *distance_counts,
+                   int64_t *distance_outside, int64_t *found);
+/* Of the first n frames seen: sums float64 [n][2], the sums of q and of S_k over the frame's centers that are not
+ * short; counted int64 [n], how many those are. */
+int mdx_tet_frames(mdx_tet_t h, double *sums, int64_t *counted, int64_t n);
+/* Of the first n frames seen: values float64 [n][2][n_centers], NaN for a short center; neighbors int32
+ * [n][n_nearest][n_centers], candidate numbers in the contract's order, -1 beyond m_i; only with keep_values. */
+int mdx_tet_values(mdx_tet_t h, double *values, int32_t *neighbors, int64_t n);
+/* evaluations: frames * (n_centers * n_neighbors - (same ? n_centers : 0)); degenerate: the neighbours without a
+ * direction seen since the last reset (not zero: the results are refused); chunks: the candidate chunks of the last
+ * launch. */
+int mdx_tet_stats(mdx_tet_t h, int64_t *launches, double *kernel_ms, int64_t *frames, int64_t *evaluations,
+                  int64_t *degenerate, int64_t *chunks);
+int mdx_tet_enable_timing(mdx_tet_t h, int on);
+
 /* ---- self-overlap Q(t) and four-point susceptibility chi_4(t) ------------------------------------------------------
  * Groups, rows, frames, lags, zero_dims, x, image and the unwrap rule as for mdx_vh_*; origin_step >= 1.  cutoffs:
  * float64 [n_cutoffs], 1 ... 8 of them, finite, not negative, strictly increasing.  Per lag k, cutoff c and frame

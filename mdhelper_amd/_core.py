@@ -1690,6 +1690,113 @@ class BondOrderEngine(_SlabbedFrameEngine):
         return out
 
 
+class TetrahedralEngine(_SlabbedFrameEngine):
+    """``mdx_tet_*``: per frame the ``n_nearest`` (4 ... 8) nearest of the ``n_neighbors`` candidates in range
+    (minimum-image ``r2 <= cutoff ** 2`` in float64) of each of ``n_centers`` centres, ordered by ascending ``r2`` and,
+    where two are bit-equal, ascending candidate number; from the first four the orientational tetrahedral order ``q``
+    and its translational counterpart ``S_k`` (every operation: csrc/mdx_tetrahedral_device.hpp), a histogram of each
+    against its own ``edges`` (``numpy.histogram``'s rule), and per neighbour rank a histogram of ``r2`` against
+    ``distance_thresholds``.  A centre with fewer than four candidates in range is short: NaN values, counted in no
+    value histogram and no sum, but in the distance histograms of the ranks it has.  Incoming rows are the centres,
+    then the candidates; with ``same`` the candidates are the centres themselves, the rows arrive once and ``j == i``
+    never counts.  One of a centre's four nearest on top of it (no direction) makes ``synchronize()``, ``result()``,
+    ``frames()`` and ``values()`` raise ``ValueError`` until ``reset()``.  Every result is the same bits whatever the
+    route, the split into calls, the slab or the candidate chunk.  The device is first touched by the first frame, so
+    the argument errors (``ValueError``) need none."""
+
+    _prefix = "mdx_tet"
+    _stats_extra = (("evaluations", c_int64), ("degenerate", c_int64), ("chunks", c_int64))
+    TILE = 256          # centres per block of the selection kernel (TET_TILE of csrc/mdx_tetrahedral_device.hpp)
+    STAGE = 256         # candidates per LDS stage: a chunk is a multiple of it (TET_STAGE)
+    MIN_NEAREST = 4     # what q and S_k need (TET_MIN_NEAREST)
+    MAX_NEAREST = 8     # the largest n_nearest (TET_MAX_NEAREST)
+    SUM_TILE = 64       # centres per tile of the frame sums (TET_SUM_TILE)
+    LDS_BINS = 1024     # bins at most for a histogram in LDS (TET_LDS_BINS)
+
+    def __init__(self, n_centers, n_neighbors, cutoff, q_edges, s_edges, distance_thresholds, dims, *, n_nearest=4,
+                 same=False, keep_values=False, dev=0, timing=False):
+        self.n_centers, self.same, self.n_nearest = int(n_centers), bool(same), int(n_nearest)
+        self.n_neighbors = self.n_centers if n_neighbors is None else int(n_neighbors)
+        self.n_rows = self.n_centers if self.same else self.n_centers + self.n_neighbors
+        if not self.MIN_NEAREST <= self.n_nearest <= self.MAX_NEAREST:
+            raise ValueError(f"n_nearest must lie in [{self.MIN_NEAREST}, {self.MAX_NEAREST}].")
+        tables = []
+        for name, table in (("q_edges", q_edges), ("s_edges", s_edges), ("distance_thresholds", distance_thresholds)):
+            table = np.ascontiguousarray(table, dtype=np.float64)
+            if table.ndim != 1 or len(table) < 2:
+                raise ValueError(f"{name} must hold n_bins + 1 values, at least two.")
+            tables.append(table)
+        self.q_edges, self.s_edges, self.distance_thresholds = tables
+        self.q_bins, self.s_bins, self.distance_bins = (len(table) - 1 for table in tables)
+        self.dims = np.ascontiguousarray(dims, dtype=np.float64)
+        if self.dims.shape != (3,):
+            raise ValueError("dims must hold the three box lengths.")
+        self.cutoff, self.keep_values = float(cutoff), bool(keep_values)
+        h = c_void_p()
+        check(lib().mdx_tet_create(byref(h), dev, self.n_centers, self.n_neighbors, int(self.same), self.n_nearest,
+                                   self.cutoff, self.q_bins, _ptr(self.q_edges), self.s_bins, _ptr(self.s_edges),
+                                   self.distance_bins, _ptr(self.distance_thresholds), _ptr(self.dims),
+                                   int(self.keep_values)))
+        self._adopt(h, dev, timing)
+
+    @staticmethod
+    def chunk_for(n_centers, n_neighbors, frames, compute_units):
+        """``mdx_tet_chunk_for``: the candidates per block the plan chooses for a launch of ``frames`` frames on a
+        device of ``compute_units`` compute units.  Needs no device."""
+        chunk = c_int64()
+        check(lib().mdx_tet_chunk_for(int(n_centers), int(n_neighbors), int(frames), int(compute_units), byref(chunk)))
+        return chunk.value
+
+    def set_chunk(self, candidates):
+        """Candidates per block of the selection kernel, a multiple of ``STAGE``; 0 restores the plan's choice.  Only
+        before the first frame.  The results do not depend on it."""
+        check(lib().mdx_tet_set_chunk(self.handle, int(candidates)))
+
+    def plan(self):
+        """``mdx_tet_plan``: ``slab_frames`` and ``ring_frames`` as every engine's, and ``chunk``, the candidates per
+        block of a launch of ``slab_frames`` frames.  Where no chunk is set the choice reads the compute units of the
+        engine's device (and nothing else of it)."""
+        slab, ring, chunk = c_int64(), c_int64(), c_int64()
+        check(lib().mdx_tet_plan(self.handle, byref(slab), byref(ring), byref(chunk)))
+        return {"slab_frames": slab.value, "ring_frames": ring.value, "chunk": chunk.value}
+
+    def _frames_seen(self):
+        frames = c_int64()
+        check(lib().mdx_tet_stats(self.handle, None, None, byref(frames), None, None, None))
+        return frames.value
+
+    def result(self):
+        """``{"q_counts": int64 [q_bins], "s_counts": int64 [s_bins], "outside": int64 [2] (q, S_k),
+        "distance_counts": int64 [n_nearest, distance_bins], "distance_outside": int64 [n_nearest],
+        "found": int64 [n_nearest + 1]}`` over the frames seen."""
+        k = self.n_nearest
+        out = {"q_counts": np.zeros(self.q_bins, dtype=np.int64), "s_counts": np.zeros(self.s_bins, dtype=np.int64),
+               "outside": np.zeros(2, dtype=np.int64),
+               "distance_counts": np.zeros((k, self.distance_bins), dtype=np.int64),
+               "distance_outside": np.zeros(k, dtype=np.int64), "found": np.zeros(k + 1, dtype=np.int64)}
+        check(lib().mdx_tet_result(self.handle, *(_ptr(out[key]) for key in (
+            "q_counts", "s_counts", "outside", "distance_counts", "distance_outside", "found"))))
+        return out
+
+    def frames(self):
+        """``{"sums": float64 [frames, 2], "counted": int64 [frames]}`` of every frame seen: the sums of ``q`` and
+        ``S_k`` over the centres that are not short, and how many those are."""
+        n = self._frames_seen()
+        out = {"sums": np.zeros((n, 2), dtype=np.float64), "counted": np.zeros(n, dtype=np.int64)}
+        check(lib().mdx_tet_frames(self.handle, _ptr(out["sums"]), _ptr(out["counted"]), n))
+        return out
+
+    def values(self):
+        """``{"values": float64 [frames, 2, n_centers], "neighbors": int32 [frames, n_nearest, n_centers]}``: every
+        centre's ``q`` and ``S_k`` (NaN for a short one) and its neighbours in the contract's order, ``-1`` beyond
+        those it has (``keep_values``)."""
+        n = self._frames_seen()
+        out = {"values": np.zeros((n, 2, self.n_centers), dtype=np.float64),
+               "neighbors": np.zeros((n, self.n_nearest, self.n_centers), dtype=np.int32)}
+        check(lib().mdx_tet_values(self.handle, _ptr(out["values"]), _ptr(out["neighbors"]), n))
+        return out
+
+
 def fourier_sum_device(wavevectors, positions, dev=0):
     """``mdx_fourier_sum``: complex128[N_q] = sum_j exp(i q.r_j), float64 positions."""
     q = np.ascontiguousarray(wavevectors, dtype=np.float64).reshape(-1, 3)

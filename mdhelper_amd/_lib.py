@@ -273,13 +273,24 @@ _SIGNATURES = {
     "mdx_sdf_inside": (c_int, [_vp, _vp, c_int64]),
     "mdx_sdf_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
                               POINTER(c_int64)]),
+    # tetrahedral order over the k nearest neighbours; its plan also reports the candidate chunk
+    "mdx_tet_create": (c_int, [POINTER(_vp), c_int, c_int64, c_int64, c_int, c_int, c_double, c_int64, _vp, c_int64,
+                               _vp, c_int64, _vp, _vp, c_int]),
+    "mdx_tet_set_chunk": (c_int, [_vp, c_int64]),
+    "mdx_tet_chunk_for": (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_int64)]),
+    "mdx_tet_plan": (c_int, [_vp, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "mdx_tet_result": (c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mdx_tet_frames": (c_int, [_vp, _vp, _vp, c_int64]),
+    "mdx_tet_values": (c_int, [_vp, _vp, _vp, c_int64]),
+    "mdx_tet_stats": (c_int, [_vp, POINTER(c_int64), POINTER(c_double), POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64), POINTER(c_int64)]),
 }
 
 # The entry points every per-frame engine has (csrc/mdx_frame_entry.hpp); the last two only where the engine works in
 # slabs it reports.  Above stand the entries an engine has of its own: create, result, stats, setters, getters.
 _FRAME_ENGINES = ("prof", "gyr", "rouse", "msid", "dip", "vh", "vhd", "prs", "clu", "ang", "ori", "boo", "chi4", "hb",
-                  "dih", "sdf")
-_SLAB_ENGINES = ("dip", "vh", "vhd", "prs", "clu", "ang", "ori", "boo", "chi4", "hb", "dih", "sdf")
+                  "dih", "sdf", "tet")
+_SLAB_ENGINES = ("dip", "vh", "vhd", "prs", "clu", "ang", "ori", "boo", "chi4", "hb", "dih", "sdf", "tet")
 _FRAME_ENTRY = {
     "accumulate": (c_int, [_vp, _vp, c_int64, c_int64]),
     "accumulate_device": (c_int, [_vp, _vp, c_int64, c_int64, _vp, c_int64]),
@@ -295,7 +306,8 @@ _SIGNATURES.update(
     (f"mdx_{prefix}_{name}", signature)
     for prefix in _FRAME_ENGINES
     for name, signature in _FRAME_ENTRY.items()
-    if prefix in _SLAB_ENGINES or name not in ("set_slab_frames", "plan"))
+    if (prefix in _SLAB_ENGINES or name not in ("set_slab_frames", "plan"))
+    and f"mdx_{prefix}_{name}" not in _SIGNATURES)         # an engine's own form of an entry stands above
 
 EXPORTS = tuple(_SIGNATURES)
 

@@ -12,7 +12,7 @@ from .dynamics import (DistinctVanHove, FourPointSusceptibility, OrientationalRe
                        calculate_non_gaussian_parameter, calculate_residence_time)
 from .electrostatics import DipoleMoment, calculate_relative_permittivity  # noqa: F401
 from .hbond import HydrogenBonds  # noqa: F401
-from .order import BondOrientationalOrder  # noqa: F401
+from .order import BondOrientationalOrder, TetrahedralOrder  # noqa: F401
 from .polymer import (EndToEndVector, Gyradius, InternalDistances, RouseModes,  # noqa: F401
                       SingleChainStructureFactor)
 from .profile import DensityProfile, calculate_potential_profile  # noqa: F401

@@ -1,12 +1,18 @@
 """
 Local order: ``BondOrientationalOrder`` — the Steinhardt bond-orientational order parameters ``q_l`` of every particle
 and their neighbour-averaged form ``q̄_l`` (Lechner and Dellago), which tell a liquid-like shell from an fcc-, hcp- or
-bcc-like one.
+bcc-like one — and ``TetrahedralOrder`` — the orientational tetrahedral order ``q`` of water and other network
+liquids over the four nearest neighbours, its translational counterpart ``S_k`` and the distances to the nearest
+neighbours rank by rank.
 
 Whole blocks of frames go to the bond-order engine (``mdx_boo_*``), which tests every (centre, candidate) pair of a
 frame in float64 (minimum image, ``r2 <= cutoff ** 2``), keeps the neighbours as capped per-centre lists in HBM, sorts
 every list, sums the spherical harmonics of a centre's bonds in ascending neighbour order, and bins the invariants with
 integer atomics (csrc/mdx_bond_order_device.hpp).  A frame needs no other frame, so the frames shard across ranks.
+
+``TetrahedralOrder`` feeds the tetrahedral engine (``mdx_tet_*``), which walks the same pairs but keeps, per centre and
+in registers, the ``n_nearest`` nearest candidates in range, ordered by ``(r2, candidate number)``: a function of the
+frame alone (csrc/mdx_tetrahedral_device.hpp).
 """
 
 from __future__ import annotations
@@ -16,6 +22,7 @@ import numpy as np
 from .. import _core, _lib
 from ..algorithm.unit import strip_unit
 from .base import DynamicAnalysisBase, EngineFedAnalysis, pair_selection
+from .hbond import distance_thresholds
 
 
 class BondOrientationalOrder(EngineFedAnalysis, DynamicAnalysisBase):
@@ -178,3 +185,185 @@ class BondOrientationalOrder(EngineFedAnalysis, DynamicAnalysisBase):
         res.coordination_number = res.coordination_distribution @ np.arange(m_max + 1)
         if values is not None:
             res["values"] = self._gather_frame_rows(values)
+
+
+def distance_table(edges) -> np.ndarray:
+    """The increasing table of ``r2`` against which ``numpy.histogram``'s rule counts like ``edges`` of
+    ``r = sqrt(r2)``: ``hbond.distance_thresholds`` for every edge but the last, which a value may equal and still be
+    counted: there the table holds ``max{x : sqrt(x) <= edges[-1]}``."""
+    edges = np.asarray(edges, dtype=np.float64)
+    table = distance_thresholds(edges)
+    x, last = table[-1], edges[-1]
+    if np.sqrt(x) > last:                   # no r2 has this root: the largest below it
+        x = np.nextafter(x, -np.inf)
+    else:
+        while np.sqrt(np.nextafter(x, np.inf)) <= last:
+            x = np.nextafter(x, np.inf)
+    table[-1] = x
+    return table
+
+
+class TetrahedralOrder(EngineFedAnalysis, DynamicAnalysisBase):
+    r"""
+    Tetrahedral order.  With :math:`\psi_{ab}` the angle at a centre between its :math:`a`-th and :math:`b`-th nearest
+    neighbours and :math:`r_a` their distances, over the four nearest neighbours (Chau and Hardwick; Errington and
+    Debenedetti),
+
+    .. math:: q=1-\frac{3}{8}\sum_{a<b}\Big(\cos\psi_{ab}+\frac{1}{3}\Big)^2,\qquad
+              S_k=1-\frac{1}{3}\sum_{a=1}^{4}\frac{(r_a-\bar r)^2}{4\bar r^2}
+
+    :math:`q` is 1 for a regular tetrahedron and 0 on average for an ideal gas (its lowest value is :math:`-3`);
+    :math:`S_k` is 1 where the four distances are equal and falls towards 0 as they spread.  The neighbours of a
+    centre are the ``n_nearest`` nearest candidates within ``cutoff`` by minimum-image distance; two candidates at
+    bit-equal distances are ordered by their place in ``neighbors``, so the selection is a function of the frame
+    alone.
+
+    Parameters
+    ----------
+    group : AtomGroup — the centres
+    neighbors : AtomGroup, optional — the neighbour candidates.  ``None``, or the very atoms of ``group`` in the same
+        order: the neighbours of a centre are the other centres.  Otherwise it must be disjoint from ``group``
+    n_nearest : int, keyword-only — the neighbours selected per centre, ``4 ... 8``; :math:`q` and :math:`S_k` take
+        the first four, the distance distributions all of them
+    cutoff : float, keyword-only — the reach of the search (Å); defaults to half the shortest box length, which it
+        may not exceed.  A centre with fewer than four candidates within it is *short*: it has no :math:`q`
+    n_bins, range : keyword-only — the histogram of :math:`q`, ``edges = linspace(low, high, n_bins + 1)``, counted as
+        ``numpy.histogram`` does
+    sk_bins, sk_range : keyword-only — the same for :math:`S_k`
+    distance_bins, distance_range : keyword-only — the same for the distance to the neighbour of every rank (Å);
+        ``distance_range`` defaults to ``(0, cutoff)``
+    keep_values : bool, keyword-only — keep every centre's values and neighbours of every frame
+    dimensions : array-like ``(3,)``, keyword-only — box lengths (Å); defaults to the universe's
+    verbose : bool
+    device : keyword-only — the HIP device
+    comm : communicator, keyword-only — the frames shard across ranks
+
+    Results
+    -------
+    With ``k = n_nearest``, ``F`` analysed frames and ``n0`` centres: ``results.q_edges``, ``results.q_bins`` (the bin
+    centres), ``results.q_counts`` ``[n_bins]`` and ``results.q_outside`` (int64, over every (frame, centre) that is
+    not short), ``results.q_distribution`` — ``counts / (counts.sum() * bin width)``, NaN where nothing was counted
+    — and the same five with ``sk_``; ``results.distance_edges``, ``results.distance_bins``,
+    ``results.distance_counts`` ``[k, distance_bins]`` and ``results.distance_outside`` ``[k]`` — rank ``a``'s
+    distance over every (frame, centre) that has more than ``a`` candidates within the cutoff, short ones included —
+    and ``results.distance_distribution``, rows that integrate to 1; ``results.mean`` ``[F, 2]`` — the means of
+    :math:`q` and :math:`S_k` over the centres of a frame that are not short (NaN where all are) and ``results.mean_overall`` ``[2]``; ``results.found_counts``
+    ``[k + 1]`` — the (frame, centre) cases with ``min(candidates within the cutoff, k) = m``; with ``keep_values``
+    ``results["values"]`` ``[F, 2, n0]``, NaN for a short centre (read it by item: as an attribute ``values`` is the
+    mapping's own method) and ``results.neighbors`` ``[F, k, n0]``, int32 places in ``neighbors``, nearest first, ``-1``
+    beyond those a centre has; and ``results.units``.
+
+    Limits: a constant orthorhombic box, three dimensions, coordinates as given, every (centre, candidate) pair
+    evaluated (no cell list).  One of a centre's four nearest exactly on it has no direction: ``run()`` then raises
+    ``ValueError``.  No CPU fallback: without a HIP device ``run()`` raises ``RuntimeError``.
+    """
+
+    def __init__(self, group, neighbors=None, *, n_nearest: int = 4, cutoff=None, n_bins: int = 150,
+                 range=(-0.5, 1.0), sk_bins: int = 100, sk_range=(0.0, 1.0), distance_bins: int = 200,
+                 distance_range=None, keep_values: bool = False, dimensions=None, verbose: bool = True,
+                 **kwargs) -> None:
+        if "drop_axis" in kwargs:
+            raise TypeError("TetrahedralOrder takes no 'drop_axis': q is a quantity of three dimensions.")
+        self.universe = group.universe
+        super().__init__(self.universe.trajectory, False, verbose, **kwargs)
+        self._same, self._n_centers, self._n_neighbors, self._index = pair_selection(group, neighbors)
+
+        engine = _core.TetrahedralEngine
+        if int(n_nearest) != n_nearest or not engine.MIN_NEAREST <= n_nearest <= engine.MAX_NEAREST:
+            raise ValueError(f"'n_nearest' must be an integer in [{engine.MIN_NEAREST}, {engine.MAX_NEAREST}].")
+        self._n_nearest = int(n_nearest)
+
+        self._drop_axis = None              # q is a quantity of three dimensions
+        if cutoff is None:
+            self._dimensions = self._box_lengths(dimensions, 0.0, "cutoff")
+            self._cutoff = float(self._dimensions.min() / 2)
+        else:
+            cut = float(strip_unit(cutoff, "angstrom")[0])
+            if not (np.isfinite(cut) and cut > 0):
+                raise ValueError("'cutoff' must be positive and finite.")
+            self._cutoff = cut
+            self._dimensions = self._box_lengths(dimensions, cut, "cutoff")
+
+        def edges_of(bins, span, what, low_limit=-np.inf):
+            if int(bins) != bins or bins < 1:
+                raise ValueError(f"'{what[0]}' must be at least 1.")
+            if (span is None or len(span) != 2 or not np.all(np.isfinite(span)) or not span[0] < span[1]
+                    or span[0] < low_limit):
+                raise ValueError(f"'{what[1]}' must be (low, high) with low < high, both finite"
+                                 + (f" and low >= {low_limit:g}." if np.isfinite(low_limit) else "."))
+            return np.linspace(float(span[0]), float(span[1]), int(bins) + 1)
+
+        self._q_edges = edges_of(n_bins, range, ("n_bins", "range"))
+        self._s_edges = edges_of(sk_bins, sk_range, ("sk_bins", "sk_range"))
+        if distance_range is None:
+            distance_range = (0.0, self._cutoff)
+        else:
+            distance_range = tuple(strip_unit(x, "angstrom")[0] for x in distance_range)
+        self._d_edges = edges_of(distance_bins, distance_range, ("distance_bins", "distance_range"), 0.0)
+        self._keep_values = bool(keep_values)
+        self._verbose = verbose
+
+    @classmethod
+    def from_molecules(cls, group, n_molecules: int, atom: int = 0, **kwargs):
+        """``group`` holds ``n_molecules`` molecules of equal size laid end to end; the atom at place ``atom`` of every
+        molecule (the default: the first, the oxygen of an "O H H" water) is a centre, and the centres are their own
+        candidates."""
+        n_molecules = int(n_molecules)
+        if n_molecules < 1 or group.n_atoms % n_molecules:
+            raise ValueError("'group' must hold n_molecules molecules of equal size.")
+        size = group.n_atoms // n_molecules
+        if int(atom) != atom or not 0 <= atom < size:
+            raise ValueError(f"'atom' must lie in [0, {size}), the size of a molecule.")
+        return cls(group[np.arange(n_molecules) * size + int(atom)], **kwargs)
+
+    # ------------------------------------------------------------------ protocol
+
+    _shard_frames = True        # a frame needs no other frame
+
+    def _prepare(self) -> None:
+        self.results.units = {"results.q_edges": "dimensionless", "results.q_bins": "dimensionless",
+                              "results.sk_edges": "dimensionless", "results.sk_bins": "dimensionless",
+                              "results.distance_edges": "angstrom", "results.distance_bins": "angstrom",
+                              "results.distance_distribution": "angstrom^-1"}
+        _lib.require_device(self._device)
+        self._feed_engine(_core.TetrahedralEngine(
+            self._n_centers, self._n_neighbors, self._cutoff, self._q_edges, self._s_edges,
+            distance_table(self._d_edges), self._dimensions, n_nearest=self._n_nearest, same=self._same,
+            keep_values=self._keep_values, dev=self._device), self._index)
+
+    def _conclude(self) -> None:
+        try:
+            self._batch.flush()
+            got = self._engine.result()
+            rows = self._engine.frames()
+            kept = self._engine.values() if self._keep_values else None
+        finally:
+            self._engine.close()
+        if self._comm.world_size > 1:
+            got = {key: np.asarray(self._comm.allreduce(value, op="sum")) for key, value in got.items()}
+        sums = self._gather_frame_rows(rows["sums"])
+        counted = self._gather_frame_rows(rows["counted"])
+
+        def distribution(counts, edges):
+            total = counts.sum(axis=-1, keepdims=True).astype(float)
+            total[total == 0] = np.nan
+            return counts / (total * np.diff(edges))
+
+        res = self.results
+        for name, edges, counts, outside in (("q", self._q_edges, got["q_counts"], got["outside"][0]),
+                                             ("sk", self._s_edges, got["s_counts"], got["outside"][1]),
+                                             ("distance", self._d_edges, got["distance_counts"],
+                                              got["distance_outside"])):
+            res[f"{name}_edges"] = edges
+            res[f"{name}_bins"] = (edges[:-1] + edges[1:]) / 2
+            res[f"{name}_counts"] = counts
+            res[f"{name}_outside"] = outside
+            res[f"{name}_distribution"] = distribution(counts, edges)
+        per_frame = counted.astype(float)
+        per_frame[per_frame == 0] = np.nan          # a frame of short centres: NaN, without a warning
+        res.mean = sums / per_frame[:, None]
+        res.mean_overall = sums.sum(axis=0) / (counted.sum() if counted.sum() else np.nan)
+        res.found_counts = got["found"]
+        if kept is not None:
+            res["values"] = self._gather_frame_rows(kept["values"])
+            res.neighbors = self._gather_frame_rows(kept["neighbors"])
